@@ -26,6 +26,7 @@ PEAK_MFMA_F32_TFLOPS = 157.3     # /opt/skills/guides/MI355X_MICROARCH.md: fp32-
 PEAK_HBM_GBS = 8000.0            # same guide: HBM3E ~8 TB/s
 PMC_ROUND = "r03"                # profiles/<round>_pmc_*.json: the committed rocprofv3 counter passes of this round's build
 FWD_FLOP_PER_IMAGE = {(128, 6): 22384148480, (64, 6): 5004001280, (256, 16): 129805844480}     # (S, slots), 3 iters
+DUMP_SAMPLE = 1 << 22            # --dump-outputs: entries kept of a longer array (two flat buffers of 16 MB each stay under the 64 MB cap)
 
 
 def slate_config(obs_size, num_slots=6, num_iterations=3):
@@ -108,6 +109,19 @@ def committed_traffic(kernel_substr, B, S):
     except Exception:
         pass
     return None
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: what the last timed step computed, one DIR/<name>.npy per array.  Device values keep their float32 bits,
+    Python numbers are written as float64; an array longer than DUMP_SAMPLE entries is cut to the entries at a fixed seeded set
+    of flat indices, so two builds run with the same arguments can be compared file for file."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, v in arrays.items():
+        a = v.detach().cpu().numpy().astype(np.float32) if torch.is_tensor(v) else np.asarray(v, dtype=np.float64)
+        if a.size > DUMP_SAMPLE:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, DUMP_SAMPLE, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def timed_region(args, dev, dist, step_fn, prof_mask):
@@ -235,6 +249,8 @@ def bench_iodine(args, dev, dist, rank, world):
         return out[4]
 
     dt, ms, cnt, loss = timed_region(args, dev, dist, step_fn, 1 << 1)       # PROF_CONV_OTHER: every conv launch of IODINE is the 3x3 / 64-channel kernel
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"loss": loss, "params": mod.engine.flat_p, "grads": mod.engine.flat_g})
     if rank == 0:
         ips = B * world * args.steps / dt
         # decoder 1.236 GF per (image, slot, iteration) forward at 64x64: fwd I, in-forward bwd-data I-1, bwd 2I
@@ -324,7 +340,12 @@ def main():
     ap.add_argument("--conv-x3", action="store_true",
                     help="EXPLORATORY, never the headline: the 5x5 / 64-channel forward and backward-data convolutions on the bf16 matrix pipe "
                          "with fp32 operands split exactly into three bf16 numbers (csrc/conv_x3.hip); the line names the arithmetic in `dtype`")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps write what the last one computed (update() metrics, the updated parameters and the "
+                         "gradients, the last two as a fixed seeded sample of %d entries each) as DIR/<name>.npy" % DUMP_SAMPLE)
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.conv_x3:
         os.environ["OCRL_CONV_X3"] = "1"
 
@@ -377,6 +398,9 @@ def main():
         if dist is not None:
             dist.destroy_process_group()
         return
+    if args.dump_outputs:
+        eng = model._module.engine
+        dump_outputs(args.dump_outputs, {**metrics, "params": eng.flat_p, "grads": eng.flat_g})
     ips = B * world * args.steps / dt
     K, N = args.num_slots, S * S
     # dominant kernel conv_fwd_kernel<5,64,64>: 2*25*64*64 FLOP per output pixel.  Launches per step: CNN encoder layers 1-3 forward +
