@@ -202,6 +202,16 @@ int ocrl_pool_transformer_bwd(const float* slots, const float* dout, const float
 /* keep-mask (1 = kept) of one dropout site, for parity tests: which = 0 attention weights [B,h,S,S], 1 dropout1 [B,S,d],
  * 2 FFN hidden [B,S,ff], 3 dropout2 [B,S,d]; n = element count. */
 int ocrl_pool_transformer_dropout_mask(int layer, int which, long long n, float drop_p, unsigned long long seed, float* out, void* stream);
+/* The same head over long token sequences (the encoder's CNN feature map as tokens: K = H*W, rep_dim = channels + 3, as SLATE with
+ * use_cnn_feat returns them).  Arguments, `w` order, dropout sites and keep decisions as in ocrl_pool_transformer_*; any K >= 1, any
+ * Din >= 1, d_model a multiple of 64 up to 256, head size 16, 32, 48 or 64.  The workspace is linear in K: layers before the last keep
+ * the log-sum-exp of their attention instead of the weights, and the last layer is evaluated for the CLS row only. */
+size_t ocrl_pool_transformer_long_ws_floats(int B, int K, int Din, int d, int nhead, int ff, int L);
+int ocrl_pool_transformer_long_fwd(const float* slots, const float* const* w, const float* pos, float* out, int B, int K, int Din, int d, int nhead,
+                                   int ff, int L, float drop_p, unsigned long long seed, float* ws, size_t ws_floats, void* stream);
+int ocrl_pool_transformer_long_bwd(const float* slots, const float* dout, const float* const* w, float* dslots, float* const* dw, int B, int K,
+                                   int Din, int d, int nhead, int ff, int L, float drop_p, unsigned long long seed, float* ws, size_t ws_floats,
+                                   void* stream);
 
 /* ---- IODINE (ocrs/iodine/iodine_module.py:14-271, ocrs/iodine/iodine.py:4-14, ocrs/base.py:60-74): SURVEY.md §8 row a20 ----
  * Same conventions as the SLATE handle: flat fp32 parameter / gradient / Adam buffers in the reference's

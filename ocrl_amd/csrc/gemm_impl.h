@@ -555,7 +555,10 @@ static int sb_mode() {
 
 template <int BM, int BN, bool AKC, bool BKC, bool SB, int XF, int EPI = 0>
 static int launch_cfg3(const GemmArgs& a, hipStream_t st) {
-    constexpr int smem = ((SB ? 1 : 2) * TileA<BM, AKC>::ELEMS + (SB ? 1 : 2) * TileA<BN, BKC>::ELEMS) * 4;
+    // the operand tiles, and at least the four 32x36 staging patches the epilogues lay over them (a single-buffered 64x64 tile with
+    // an n- or m-contiguous operand holds 4480 floats: the last wave's patch rows 28..31, tile rows 60..63, would lie past the end)
+    constexpr int tiles = (SB ? 1 : 2) * TileA<BM, AKC>::ELEMS + (SB ? 1 : 2) * TileA<BN, BKC>::ELEMS;
+    constexpr int smem = (tiles > 4 * 32 * 36 ? tiles : 4 * 32 * 36) * 4;
     static bool attr_set = false;
     if (!attr_set) {
         OCRL_HIP(hipFuncSetAttribute((const void*)gemm_kernel<BM, BN, AKC, BKC, SB, XF, EPI>,

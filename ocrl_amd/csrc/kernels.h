@@ -66,6 +66,36 @@ int pool_rows_launch(const float* in, float* out, int B, int K, int d, int mode,
 int pool_attn_launch(const float* qkv, float* P, float* O, const float* dO, float* dqkv, int B, int S, int d, int h, float p, unsigned long long seed,
                      unsigned site, int backward, hipStream_t st);
 
+// ------------------------------------------------------------------ pool_long.hip (long token sequences: include/ocrl_hip.h ocrl_pool_transformer_long_*)
+int pool_cols_launch(const float* src, int lds, float* dst, int ldd, long long rows, int ncols, int ncopy, hipStream_t st);
+int pool_cls_drop_launch(const float* x, const float* resid, int ldr, float* out, int B, int N, int S, float p, unsigned long long seed, unsigned site,
+                         hipStream_t st);
+int pool_cls_add_launch(float* dX, const float* v, int B, int d, int S, hipStream_t st);
+int pool_cls_nchunk(int B, int S, int* chunk);     // position chunks per image of the CLS-row attention
+struct PoolClsArgs {                                // attention of the CLS row of the last layer over the S rows of X (pool_long.hip)
+    const float* X = nullptr;                       // [B][S][d] layer input
+    const float* Win = nullptr; const float* bin = nullptr;   // in_proj weight [3d][d], bias [3d]
+    const float* q = nullptr;                       // [B][d] query of row 0 (bias included)
+    float* U = nullptr;                             // [B][h][d]
+    float* part = nullptr;                          // [B][nchunk][h][d + 4] partial blocks (forward), [B][nchunk][h][d] (backward)
+    float* z = nullptr;                             // [B][h][d] sum_j p'_hj x_j
+    float* stat = nullptr;                          // [B][h][2] (sum_j p'_hj, log-sum-exp of the scores)
+    float* o = nullptr;                             // [B][d] attention output (before out_proj)
+    const float* dO = nullptr;                      // backward: [B][d] gradient of o
+    float* G = nullptr; float* gD = nullptr;        // [B][h][d], [B][h][2]
+    float* dX = nullptr;                            // [B][S][d] gradient of X through k and v (row 0's q part is added by the caller)
+    float* w = nullptr; float* dq = nullptr;        // [B][h][d] sum_j ds_hj x_j, [B][d]
+    const float* x0 = nullptr;                      // [B][d] row 0 of X
+    float* dW = nullptr; float* db = nullptr;       // in_proj gradients
+    int B = 0, S = 0, d = 0, h = 0;
+    float p = 0.f; unsigned long long seed = 0; unsigned site = 0;
+};
+int pool_cls_attn_fwd_launch(const PoolClsArgs& a, hipStream_t st);
+int pool_cls_attn_bwd_launch(const PoolClsArgs& a, hipStream_t st);
+// non-causal multi-head attention over all rows: forward O, lse [B*h][S]; backward dqkv from dO (Dd: [B*h][S] scratch)
+int pool_flash_launch(const float* qkv, float* O, float* lse, const float* dO, float* Dd, float* dqkv, int B, int S, int d, int h, float p,
+                      unsigned long long seed, unsigned site, int backward, hipStream_t st);
+
 // ------------------------------------------------------------------ conv.hip
 struct ConvArgs {
     const float* X = nullptr;       // [B,H,W,CIN] NHWC

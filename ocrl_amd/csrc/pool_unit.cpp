@@ -185,3 +185,201 @@ int ocrl_pool_transformer_dropout_mask(int layer, int which, long long n, float 
 }
 
 }  // extern "C"
+
+// ---------------------------------------------------------------- long token sequences (a CNN feature map: include/ocrl_hip.h ocrl_pool_transformer_long_*)
+// Same parameters, dropout sites and element indices as above.  Layers before the last run on all B*S rows (GEMM / LayerNorm family,
+// pool_flash attention: the saved log-sum-exp replaces the [B,h,S,S] weights).  The last layer is evaluated for the CLS row only: its
+// attention is one pass over the token rows (pool_cls_*, the projections folded), out_proj / LN1 / FFN / LN2 run on B rows.
+namespace {
+struct LongLayer {
+    size_t x, qkv, o, lse, y1, mr1, x1, hdn, y2, mr2;    // x = layer input; qkv .. mr2 only for the full layers (l < L-1)
+};
+struct LongLay {
+    int Dp;                                              // rep_dim padded to a multiple of 4
+    size_t sp, wp, dwp, dsp, lin;
+    LongLayer l[OCRL_POOL_MAX_LAYERS];
+    size_t x0c, q, U, part, z, stat, ov, at, y1, mr1, x1, hdn, y2, mr2;      // last layer (B rows / CLS attention)
+    size_t g2, gA, gB, dqkv, dhdn, Dd, G, gD, w, dq, dO, cA, cB, cAd, chd, dgb, dlin, tmp, sk, sk_floats, total;
+};
+LongLay long_layout(int B, int K, int Din, int d, int h, int ff, int L) {
+    LongLay y;
+    size_t a = 0;
+    auto take = [&](size_t n) { size_t r = a; a += (n + 63) & ~(size_t)63; return r; };
+    const size_t S = (size_t)K + 1, R = (size_t)B * S, BK = (size_t)B * K;
+    const int nchunk = pool_cls_nchunk(B, (int)S, nullptr);
+    y.Dp = (Din + 3) & ~3;
+    const bool pad = y.Dp != Din;
+    y.sp = take(pad ? BK * y.Dp : 0); y.wp = take(pad ? (size_t)d * y.Dp : 0); y.dwp = take(pad ? (size_t)d * y.Dp : 0); y.dsp = take(pad ? BK * y.Dp : 0);
+    y.lin = take(BK * d);
+    for (int l = 0; l < L; ++l) {
+        LongLayer& q = y.l[l];
+        q.x = take(R * d);
+        const size_t r = l + 1 < L ? R : 0;
+        q.qkv = take(r * 3 * d); q.o = take(r * d); q.lse = take(l + 1 < L ? (size_t)B * h * S : 0); q.y1 = take(r * d); q.mr1 = take(2 * r);
+        q.x1 = take(r * d); q.hdn = take(r * ff); q.y2 = take(r * d); q.mr2 = take(2 * r);
+    }
+    const size_t Bd = (size_t)B * d, Bhd = (size_t)B * h * d;
+    y.x0c = take(Bd); y.q = take(Bd); y.U = take(Bhd); y.part = take((size_t)B * nchunk * h * (d + 4)); y.z = take(Bhd); y.stat = take((size_t)2 * B * h);
+    y.ov = take(Bd); y.at = take(Bd); y.y1 = take(Bd); y.mr1 = take(2 * (size_t)B); y.x1 = take(Bd); y.hdn = take((size_t)B * ff); y.y2 = take(Bd);
+    y.mr2 = take(2 * (size_t)B);
+    const size_t rf = L > 1 ? R : 0;                     // gradient buffers of the full layers
+    y.g2 = take(R * d); y.gA = take(rf * d); y.gB = take(rf * d); y.dqkv = take(rf * 3 * d); y.dhdn = take(rf * ff); y.Dd = take(L > 1 ? (size_t)B * h * S : 0);
+    y.G = take(Bhd); y.gD = take((size_t)2 * B * h); y.w = take(Bhd); y.dq = take(Bd); y.dO = take(Bd);
+    y.cA = take(Bd); y.cB = take(Bd); y.cAd = take(Bd); y.chd = take((size_t)B * ff); y.dgb = take(2 * (size_t)d); y.dlin = take(BK * d);
+    y.tmp = take(TMP_FLOATS);
+    size_t slab = (size_t)ff * d;
+    if ((size_t)3 * d * d > slab) slab = (size_t)3 * d * d;
+    if ((size_t)d * y.Dp > slab) slab = (size_t)d * y.Dp;
+    size_t splits = R / 256;
+    if (splits > 32) splits = 32;
+    y.sk_floats = splits > 1 ? splits * (slab + (size_t)ff + 3 * (size_t)d + 8) : 0;
+    y.sk = take(y.sk_floats);
+    y.total = a;
+    return y;
+}
+int check_dims_long(int B, int K, int Din, int d, int h, int ff, int L) {
+    OCRL_REQUIRE(B > 0 && K >= 1 && Din >= 1, "pool_transformer_long: batch, tokens and rep_dim must be >= 1 (got %d, %d, %d)", B, K, Din);
+    OCRL_REQUIRE(L >= 1 && L <= OCRL_POOL_MAX_LAYERS, "pool_transformer_long: 1 <= num_layers <= %d (got %d)", OCRL_POOL_MAX_LAYERS, L);
+    OCRL_REQUIRE(ff >= 4 && ff % 4 == 0 && d % 64 == 0 && d >= 64 && d <= 256, "pool_transformer_long: d_model must be a multiple of 64 <= 256, ff a multiple of 4");
+    OCRL_REQUIRE(h >= 1 && d % h == 0 && (d / h == 16 || d / h == 32 || d / h == 48 || d / h == 64),
+                 "pool_transformer_long: head size d_model / nhead must be 16, 32, 48 or 64 (got %d / %d)", d, h);
+    OCRL_REQUIRE((long long)B * (K + 1) * 3 * d < (1LL << 31) && (L == 1 || (long long)B * (K + 1) * ff < (1LL << 31)),
+                 "pool_transformer_long: B * (K + 1) rows too many for one call");
+    return 0;
+}
+}  // namespace
+
+extern "C" {
+
+size_t ocrl_pool_transformer_long_ws_floats(int B, int K, int Din, int d, int nhead, int ff, int L) {
+    if (check_dims_long(B, K, Din, d, nhead, ff, L)) return 0;           // the shapes fwd / bwd reject get no workspace
+    return long_layout(B, K, Din, d, nhead, ff, L).total;
+}
+
+int ocrl_pool_transformer_long_fwd(const float* slots, const float* const* w, const float* pos, float* out, int B, int K, int Din, int d, int nhead, int ff,
+                                   int L, float drop_p, unsigned long long seed, float* ws, size_t ws_floats, void* stream) {
+    OCRL_REQUIRE(slots && w && out && ws, "ocrl_pool_transformer_long_fwd: null argument");
+    RC(check_dims_long(B, K, Din, d, nhead, ff, L));
+    const LongLay y = long_layout(B, K, Din, d, nhead, ff, L);
+    OCRL_REQUIRE(ws_floats >= y.total, "ocrl_pool_transformer_long_fwd: workspace too small (%zu < %zu floats)", ws_floats, y.total);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int S = K + 1, Dp = y.Dp;
+    const long long R = (long long)B * S, BK = (long long)B * K;
+    const float* xs = slots;
+    const float* w0 = w[0];
+    if (Dp != Din) {                                    // zero-padded stride-4 copies of the slots and the input Linear's weight
+        RC(pool_cols_launch(slots, Din, ws + y.sp, Dp, BK, Dp, Din, st));
+        RC(pool_cols_launch(w[0], Din, ws + y.wp, Dp, d, Dp, Din, st));
+        xs = ws + y.sp; w0 = ws + y.wp;
+    }
+    RC(lin_fwd(xs, w0, w[1], ws + y.lin, BK, d, Dp, 0, nullptr, 0.f, 0, 0, st));
+    RC(pool_embed_launch(ws + y.lin, w[2], pos, ws + y.l[0].x, B, K, d, st));
+    for (int l = 0; l + 1 < L; ++l) {
+        const float* const* q = w + 3 + 12 * l;
+        const LongLayer& a = y.l[l];
+        const unsigned site = SITE_POOL + 8 * l;
+        RC(lin_fwd(ws + a.x, q[0], q[1], ws + a.qkv, R, 3 * d, d, 0, nullptr, 0.f, 0, 0, st));
+        RC(pool_flash_launch(ws + a.qkv, ws + a.o, ws + a.lse, nullptr, nullptr, nullptr, B, S, d, nhead, drop_p, seed, site + 0, 0, st));
+        RC(lin_fwd(ws + a.o, q[2], q[3], ws + a.y1, R, d, d, 0, ws + a.x, drop_p, seed, site + 1, st));
+        RC(layernorm_fwd_launch(ws + a.y1, q[8], q[9], ws + a.x1, ws + a.mr1, ws + a.mr1 + R, R, d, st));
+        RC(lin_fwd(ws + a.x1, q[4], q[5], ws + a.hdn, R, ff, d, 1, nullptr, drop_p, seed, site + 2, st));
+        RC(lin_fwd(ws + a.hdn, q[6], q[7], ws + a.y2, R, d, ff, 0, ws + a.x1, drop_p, seed, site + 3, st));
+        RC(layernorm_fwd_launch(ws + a.y2, q[10], q[11], ws + y.l[l + 1].x, ws + a.mr2, ws + a.mr2 + R, R, d, st));
+    }
+    // last layer: the CLS row
+    const float* const* q = w + 3 + 12 * (L - 1);
+    const unsigned site = SITE_POOL + 8 * (L - 1);
+    const float* X = ws + y.l[L - 1].x;
+    RC(pool_rows_launch(X, ws + y.x0c, B, K, d, 2, st));
+    RC(lin_fwd(ws + y.x0c, q[0], q[1], ws + y.q, B, d, d, 0, nullptr, 0.f, 0, 0, st));            // rows 0..d-1 of in_proj: the query
+    PoolClsArgs c;
+    c.X = X; c.Win = q[0]; c.bin = q[1]; c.q = ws + y.q; c.U = ws + y.U; c.part = ws + y.part; c.z = ws + y.z; c.stat = ws + y.stat; c.o = ws + y.ov;
+    c.B = B; c.S = S; c.d = d; c.h = nhead; c.p = drop_p; c.seed = seed; c.site = site + 0;
+    RC(pool_cls_attn_fwd_launch(c, st));
+    RC(lin_fwd(ws + y.ov, q[2], q[3], ws + y.at, B, d, d, 0, nullptr, 0.f, 0, 0, st));
+    RC(pool_cls_drop_launch(ws + y.at, ws + y.x0c, d, ws + y.y1, B, d, S, drop_p, seed, site + 1, st));         // x + dropout1(attn)
+    RC(layernorm_fwd_launch(ws + y.y1, q[8], q[9], ws + y.x1, ws + y.mr1, ws + y.mr1 + B, B, d, st));
+    RC(lin_fwd(ws + y.x1, q[4], q[5], ws + y.hdn, B, ff, d, 1, nullptr, 0.f, 0, 0, st));
+    RC(pool_cls_drop_launch(ws + y.hdn, nullptr, 0, ws + y.hdn, B, ff, S, drop_p, seed, site + 2, st));         // dropout(relu(linear1))
+    RC(lin_fwd(ws + y.hdn, q[6], q[7], ws + y.at, B, d, ff, 0, nullptr, 0.f, 0, 0, st));
+    RC(pool_cls_drop_launch(ws + y.at, ws + y.x1, d, ws + y.y2, B, d, S, drop_p, seed, site + 3, st));          // x1 + dropout2(linear2)
+    RC(layernorm_fwd_launch(ws + y.y2, q[10], q[11], out, ws + y.mr2, ws + y.mr2 + B, B, d, st));
+    return 0;
+}
+
+int ocrl_pool_transformer_long_bwd(const float* slots, const float* dout, const float* const* w, float* dslots, float* const* dw, int B, int K, int Din,
+                                   int d, int nhead, int ff, int L, float drop_p, unsigned long long seed, float* ws, size_t ws_floats, void* stream) {
+    OCRL_REQUIRE(slots && dout && w && dw && ws, "ocrl_pool_transformer_long_bwd: null argument");
+    RC(check_dims_long(B, K, Din, d, nhead, ff, L));
+    const LongLay y = long_layout(B, K, Din, d, nhead, ff, L);
+    OCRL_REQUIRE(ws_floats >= y.total, "ocrl_pool_transformer_long_bwd: workspace too small (%zu < %zu floats)", ws_floats, y.total);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int S = K + 1, Dp = y.Dp;
+    const long long R = (long long)B * S, BK = (long long)B * K;
+    const float inv_keep = drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f;
+    float *g2 = ws + y.g2, *tmp = ws + y.tmp, *dgb = ws + y.dgb;
+    {   // last layer: B rows, then the CLS attention back to every token row (g2 = gradient of the layer input)
+        const float* const* q = w + 3 + 12 * (L - 1);
+        float* const* g = dw + 3 + 12 * (L - 1);
+        const unsigned site = SITE_POOL + 8 * (L - 1);
+        float *cA = ws + y.cA, *cB = ws + y.cB, *cAd = ws + y.cAd;
+        RC(layernorm_bwd_launch(dout, ws + y.y2, ws + y.mr2, ws + y.mr2 + B, q[10], cA, dgb, B, d, 0, 0, tmp, TMP_FLOATS, st));
+        RC(copy_launch(dgb, g[10], d, st)); RC(copy_launch(dgb + d, g[11], d, st));
+        RC(pool_cls_drop_launch(cA, nullptr, 0, cAd, B, d, S, drop_p, seed, site + 3, st));
+        RC(lin_bwd_w(cAd, ws + y.hdn, g[6], g[7], B, d, ff, 0.f, 0, 0, ws + y.sk, y.sk_floats, st));
+        RC(lin_bwd_x(cAd, q[6], ws + y.chd, B, d, ff, inv_keep, ws + y.hdn, nullptr, 0.f, 0, 0, st));
+        RC(lin_bwd_w(ws + y.chd, ws + y.x1, g[4], g[5], B, ff, d, 0.f, 0, 0, ws + y.sk, y.sk_floats, st));
+        RC(lin_bwd_x(ws + y.chd, q[4], cB, B, ff, d, 1.f, nullptr, cA, 0.f, 0, 0, st));                   // + residual
+        RC(layernorm_bwd_launch(cB, ws + y.y1, ws + y.mr1, ws + y.mr1 + B, q[8], cA, dgb, B, d, 0, 0, tmp, TMP_FLOATS, st));
+        RC(copy_launch(dgb, g[8], d, st)); RC(copy_launch(dgb + d, g[9], d, st));
+        RC(pool_cls_drop_launch(cA, nullptr, 0, cAd, B, d, S, drop_p, seed, site + 1, st));
+        RC(lin_bwd_w(cAd, ws + y.ov, g[2], g[3], B, d, d, 0.f, 0, 0, ws + y.sk, y.sk_floats, st));
+        RC(lin_bwd_x(cAd, q[2], ws + y.dO, B, d, d, 1.f, nullptr, nullptr, 0.f, 0, 0, st));
+        PoolClsArgs c;
+        c.X = ws + y.l[L - 1].x; c.Win = q[0]; c.bin = q[1]; c.q = ws + y.q; c.U = ws + y.U; c.part = ws + y.part; c.z = ws + y.z; c.stat = ws + y.stat;
+        c.dO = ws + y.dO; c.G = ws + y.G; c.gD = ws + y.gD; c.dX = g2; c.w = ws + y.w; c.dq = ws + y.dq; c.x0 = ws + y.x0c; c.dW = g[0]; c.db = g[1];
+        c.B = B; c.S = S; c.d = d; c.h = nhead; c.p = drop_p; c.seed = seed; c.site = site + 0;
+        RC(pool_cls_attn_bwd_launch(c, st));
+        RC(lin_bwd_x(ws + y.dq, q[0], cB, B, d, d, 1.f, nullptr, cA, 0.f, 0, 0, st));                    // row 0: W_q^T dq + residual
+        RC(pool_cls_add_launch(g2, cB, B, d, S, st));
+    }
+    float *gA = ws + y.gA, *gB = ws + y.gB;
+    for (int l = L - 2; l >= 0; --l) {
+        const float* const* q = w + 3 + 12 * l;
+        float* const* g = dw + 3 + 12 * l;
+        const LongLayer& a = y.l[l];
+        const unsigned site = SITE_POOL + 8 * l;
+        RC(layernorm_bwd_launch(g2, ws + a.y2, ws + a.mr2, ws + a.mr2 + R, q[10], gA, dgb, R, d, 0, 0, tmp, TMP_FLOATS, st));
+        RC(copy_launch(dgb, g[10], d, st)); RC(copy_launch(dgb + d, g[11], d, st));
+        RC(lin_bwd_w(gA, ws + a.hdn, g[6], g[7], R, d, ff, drop_p, seed, site + 3, ws + y.sk, y.sk_floats, st));
+        RC(lin_bwd_x(gA, q[6], ws + y.dhdn, R, d, ff, inv_keep, ws + a.hdn, nullptr, drop_p, seed, site + 3, st));
+        RC(lin_bwd_w(ws + y.dhdn, ws + a.x1, g[4], g[5], R, ff, d, 0.f, 0, 0, ws + y.sk, y.sk_floats, st));
+        RC(lin_bwd_x(ws + y.dhdn, q[4], gB, R, ff, d, 1.f, nullptr, gA, 0.f, 0, 0, st));
+        RC(layernorm_bwd_launch(gB, ws + a.y1, ws + a.mr1, ws + a.mr1 + R, q[8], gA, dgb, R, d, 0, 0, tmp, TMP_FLOATS, st));
+        RC(copy_launch(dgb, g[8], d, st)); RC(copy_launch(dgb + d, g[9], d, st));
+        RC(lin_bwd_w(gA, ws + a.o, g[2], g[3], R, d, d, drop_p, seed, site + 1, ws + y.sk, y.sk_floats, st));
+        RC(lin_bwd_x(gA, q[2], gB, R, d, d, 1.f, nullptr, nullptr, drop_p, seed, site + 1, st));
+        RC(pool_flash_launch(ws + a.qkv, ws + a.o, ws + a.lse, gB, ws + y.Dd, ws + y.dqkv, B, S, d, nhead, drop_p, seed, site + 0, 1, st));
+        RC(lin_bwd_w(ws + y.dqkv, ws + a.x, g[0], g[1], R, 3 * d, d, 0.f, 0, 0, ws + y.sk, y.sk_floats, st));
+        RC(lin_bwd_x(ws + y.dqkv, q[0], g2, R, 3 * d, d, 1.f, nullptr, gA, 0.f, 0, 0, st));
+    }
+    // x0 = [cls; Linear(slots)] (+pos)
+    RC(colsum_launch(g2, (long long)S * d, dw[2], B, d, 0, 1.f, tmp, TMP_FLOATS, st));
+    RC(pool_rows_launch(g2, ws + y.dlin, B, K, d, 0, st));
+    const float* xs = slots;
+    const float* w0 = w[0];
+    if (Dp != Din) {
+        RC(pool_cols_launch(slots, Din, ws + y.sp, Dp, BK, Dp, Din, st));
+        RC(pool_cols_launch(w[0], Din, ws + y.wp, Dp, d, Dp, Din, st));
+        xs = ws + y.sp; w0 = ws + y.wp;
+    }
+    RC(lin_bwd_w(ws + y.dlin, xs, Dp != Din ? ws + y.dwp : dw[0], dw[1], BK, d, Dp, 0.f, 0, 0, ws + y.sk, y.sk_floats, st));
+    if (Dp != Din) RC(pool_cols_launch(ws + y.dwp, Dp, dw[0], Din, d, Din, Din, st));
+    if (dslots) {
+        RC(lin_bwd_x(ws + y.dlin, w0, Dp != Din ? ws + y.dsp : dslots, BK, d, Dp, 1.f, nullptr, nullptr, 0.f, 0, 0, st));
+        if (Dp != Din) RC(pool_cols_launch(ws + y.dsp, Dp, dslots, Din, BK, Din, Din, st));
+    }
+    return 0;
+}
+
+}  // extern "C"

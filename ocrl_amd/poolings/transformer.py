@@ -144,13 +144,19 @@ class _PoolFn(torch.autograd.Function):
         B, K, Din = slots.shape
         slots = slots.contiguous().float()
         ps = [p.detach().contiguous() for p in params]
-        n = L.ocrl_pool_transformer_ws_floats(B, K, d, nhead, ff, nl)
+        # token sets beyond the short path's limits (a CNN feature map: thousands of tokens, rep_dim = channels + 3) take the long path
+        use_long = K + 1 > 32 or Din % 4 != 0
+        if use_long:
+            n = L.ocrl_pool_transformer_long_ws_floats(B, K, Din, d, nhead, ff, nl)
+        else:
+            n = L.ocrl_pool_transformer_ws_floats(B, K, d, nhead, ff, nl)
         ws = torch.empty(n, device=slots.device, dtype=torch.float32)
         out = torch.empty(B, d, device=slots.device, dtype=torch.float32)
         arr = (ctypes.c_void_p * len(ps))(*[p.data_ptr() for p in ps])
         st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-        _lib.check(L.ocrl_pool_transformer_fwd(_lib.ptr(slots), arr, _lib.ptr(pos), _lib.ptr(out), B, K, Din, d, nhead, ff, nl, drop_p, seed, _lib.ptr(ws), n, st))
-        ctx.geom, ctx.drop_p, ctx.seed, ctx.ws, ctx.ps, ctx.slots = geom, drop_p, seed, ws, ps, slots
+        fwd = L.ocrl_pool_transformer_long_fwd if use_long else L.ocrl_pool_transformer_fwd
+        _lib.check(fwd(_lib.ptr(slots), arr, _lib.ptr(pos), _lib.ptr(out), B, K, Din, d, nhead, ff, nl, drop_p, seed, _lib.ptr(ws), n, st))
+        ctx.geom, ctx.drop_p, ctx.seed, ctx.ws, ctx.ps, ctx.slots, ctx.use_long = geom, drop_p, seed, ws, ps, slots, use_long
         ctx.need_dslots = ctx.needs_input_grad[0]      # read from the autograd node: the converted copy above carries no requires_grad
         return out
 
@@ -165,8 +171,9 @@ class _PoolFn(torch.autograd.Function):
         arr = (ctypes.c_void_p * len(ctx.ps))(*[p.data_ptr() for p in ctx.ps])
         garr = (ctypes.c_void_p * len(gs))(*[g.data_ptr() for g in gs])
         st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-        _lib.check(L.ocrl_pool_transformer_bwd(_lib.ptr(ctx.slots), _lib.ptr(dout), arr, _lib.ptr(ds), garr, B, K, Din, d, nhead, ff, nl, ctx.drop_p, ctx.seed,
-                                               _lib.ptr(ctx.ws), ctx.ws.numel(), st))
+        bwd = L.ocrl_pool_transformer_long_bwd if ctx.use_long else L.ocrl_pool_transformer_bwd
+        _lib.check(bwd(_lib.ptr(ctx.slots), _lib.ptr(dout), arr, _lib.ptr(ds), garr, B, K, Din, d, nhead, ff, nl, ctx.drop_p, ctx.seed,
+                       _lib.ptr(ctx.ws), ctx.ws.numel(), st))
         return (ds, None, None, None, None, *gs)
 
 
