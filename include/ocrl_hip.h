@@ -112,6 +112,34 @@ int ocrl_slate_dropout_mask(const ocrl_slate* h, unsigned site, long long n, flo
 int ocrl_gemm(const float* A, const float* B, float* C, int M, int N, int K, int lda, int ldb, int ldc, int akc, int bkc,
               float alpha, const float* bias, int relu, const float* mask, int ldmask, const float* resid, int ldr,
               int splitk, float* ws, void* stream);
+/* The same GEMM with every argument the kernel takes (unit tests of each instantiation; csrc/kernels.h GemmArgs documents the fields).
+ * Fields left zero by memset are the defaults except alpha, x_scale and e_scale (set them to 1), batch, batch_inner and splitk (>= 1)
+ * and force_sb (-1 = the dispatch rule, 0 = double-buffered LDS, 1 = single).  force_tile: 0 = the rule, else BM*1000 + BN; a forced
+ * combination that is not built is an error.  splitk > 1 needs ldc == N and no epilogue; ws then holds splitk*M*N floats of partial
+ * products, plus splitk*sBias floats of bias partials when bias_out is set (sBias 0: M rounded up to 4); both are summed into C and
+ * bias_out.  ocrl_gemm_plan reports the kernel the arguments select, out = {BM, BN, single_buffer, xf, epi, 2*akc + bkc} (xf: 0 plain
+ * operands, 1 A-operand dropout, 2 soft-max operand transforms; epi = epi_mode); host only, pointers are only checked for alignment. */
+typedef struct ocrl_gemm_desc {
+    const float* A; const float* B; float* C;
+    int M, N, K, lda, ldb, ldc;
+    int akc, bkc;
+    int batch, batch_inner;
+    long long sA, sB, sC, sAi, sBi, sCi;
+    int splitk; float alpha;
+    const float* bias; int relu;
+    float drop_p; unsigned long long drop_seed; unsigned drop_site;
+    const float* mask; int ldmask; long long sMask; int mask_elu;
+    const float* resid; int ldr; long long sR;
+    float adrop_p; unsigned adrop_site; int adrop_ld;
+    float* bias_out; long long sBias;
+    int a_mode, b_mode; const float* x_lse; const int* x_tok; float x_scale;
+    int epi_mode; float* stat; float* hstat; int* hidx; const float* e1; const float* e2; unsigned long long e_seed;
+    const float* e_lse; const float* e_rowvec; float e_scale;
+    int force_tile, force_sb;
+} ocrl_gemm_desc;
+size_t ocrl_gemm_desc_size(void);
+int ocrl_gemm_ex(const ocrl_gemm_desc* d, float* ws, size_t ws_floats, void* stream);
+int ocrl_gemm_plan(const ocrl_gemm_desc* d, int out[6]);
 /* F.conv2d(x, w, b, stride 1, padding ks/2) on NHWC x [B,H,W,cin_pad] (cin_pad = 8 or 64; channels >= cin are
  * zero) with the reference-layout weight w [64,cin,ks,ks]; y [B,H,W,64] NHWC.  ws: ks*ks*cin_pad*64 floats. */
 int ocrl_conv2d_fwd(const float* x, const float* w, const float* bias, float* y, int B, int H, int W, int cin, int cin_pad, int ks,

@@ -19,6 +19,31 @@ class IodineConfig(ctypes.Structure):
                [("sigma", c_float), ("beta", c_float), ("layer_norm", c_int), ("ref_mlp_hidden", c_int), ("max_batch", c_int)]
 
 
+class GemmDesc(ctypes.Structure):
+    """mirror of ocrl_gemm_desc (include/ocrl_hip.h); make one with gemm_desc()"""
+    _fields_ = [("A", c_void_p), ("B", c_void_p), ("C", c_void_p)] + \
+               [(n, c_int) for n in ("M", "N", "K", "lda", "ldb", "ldc", "akc", "bkc", "batch", "batch_inner")] + \
+               [(n, c_longlong) for n in ("sA", "sB", "sC", "sAi", "sBi", "sCi")] + \
+               [("splitk", c_int), ("alpha", c_float), ("bias", c_void_p), ("relu", c_int),
+                ("drop_p", c_float), ("drop_seed", c_ulonglong), ("drop_site", c_uint),
+                ("mask", c_void_p), ("ldmask", c_int), ("sMask", c_longlong), ("mask_elu", c_int),
+                ("resid", c_void_p), ("ldr", c_int), ("sR", c_longlong),
+                ("adrop_p", c_float), ("adrop_site", c_uint), ("adrop_ld", c_int),
+                ("bias_out", c_void_p), ("sBias", c_longlong),
+                ("a_mode", c_int), ("b_mode", c_int), ("x_lse", c_void_p), ("x_tok", c_void_p), ("x_scale", c_float),
+                ("epi_mode", c_int), ("stat", c_void_p), ("hstat", c_void_p), ("hidx", c_void_p), ("e1", c_void_p), ("e2", c_void_p),
+                ("e_seed", c_ulonglong), ("e_lse", c_void_p), ("e_rowvec", c_void_p), ("e_scale", c_float),
+                ("force_tile", c_int), ("force_sb", c_int)]
+
+
+def gemm_desc(**kw):
+    """GemmDesc with the defaults of GemmArgs (alpha = 1, one batch, no split, the dispatch rule) and the given fields"""
+    d = GemmDesc(batch=1, batch_inner=1, splitk=1, alpha=1.0, x_scale=1.0, e_scale=1.0, force_sb=-1)
+    for k, v in kw.items():
+        setattr(d, k, v)
+    return d
+
+
 def lib():
     global _lib
     if _lib is not None:
@@ -66,6 +91,9 @@ def lib():
     L.ocrl_slate_soft_z.argtypes = [p, p]
     L.ocrl_gemm.argtypes = [p, p, p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, p, c_int, p, c_int, p, c_int,
                             c_int, p, p]
+    L.ocrl_gemm_desc_size.restype = c_size_t
+    L.ocrl_gemm_ex.argtypes = [POINTER(GemmDesc), p, c_size_t, p]
+    L.ocrl_gemm_plan.argtypes = [POINTER(GemmDesc), POINTER(c_int * 6)]
     L.ocrl_conv2d_fwd.argtypes = [p, p, p, p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, p, p]
     L.ocrl_conv2d_fwd_lowlat.argtypes = [p, p, p, p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, p, p]
     L.ocrl_conv2d_x3_ws_floats.restype = c_size_t

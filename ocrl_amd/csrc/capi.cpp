@@ -134,6 +134,53 @@ int ocrl_gemm(const float* A, const float* B, float* C, int M, int N, int K, int
     }
     return gemm_launch(a, ST(stream));
 }
+static GemmArgs gemm_args(const ocrl_gemm_desc& d) {
+    GemmArgs a;
+    a.A = d.A; a.B = d.B; a.C = d.C; a.M = d.M; a.N = d.N; a.K = d.K; a.lda = d.lda; a.ldb = d.ldb; a.ldc = d.ldc; a.akc = d.akc; a.bkc = d.bkc;
+    a.batch = d.batch; a.batch_inner = d.batch_inner; a.sA = d.sA; a.sB = d.sB; a.sC = d.sC; a.sAi = d.sAi; a.sBi = d.sBi; a.sCi = d.sCi;
+    a.splitk = d.splitk; a.alpha = d.alpha; a.bias = d.bias; a.relu = d.relu; a.drop_p = d.drop_p; a.drop_seed = d.drop_seed; a.drop_site = d.drop_site;
+    a.mask = d.mask; a.ldmask = d.ldmask; a.sMask = d.sMask; a.mask_elu = d.mask_elu; a.resid = d.resid; a.ldr = d.ldr; a.sR = d.sR;
+    a.adrop_p = d.adrop_p; a.adrop_site = d.adrop_site; a.adrop_ld = d.adrop_ld; a.bias_out = d.bias_out; a.sBias = d.sBias;
+    a.a_mode = d.a_mode; a.b_mode = d.b_mode; a.x_lse = d.x_lse; a.x_tok = d.x_tok; a.x_scale = d.x_scale;
+    a.epi_mode = d.epi_mode; a.stat = d.stat; a.hstat = d.hstat; a.hidx = d.hidx; a.e1 = d.e1; a.e2 = d.e2; a.e_seed = d.e_seed;
+    a.e_lse = d.e_lse; a.e_rowvec = d.e_rowvec; a.e_scale = d.e_scale; a.force_tile = d.force_tile; a.force_sb = d.force_sb;
+    return a;
+}
+size_t ocrl_gemm_desc_size(void) { return sizeof(ocrl_gemm_desc); }
+int ocrl_gemm_plan(const ocrl_gemm_desc* d, int out[6]) {
+    if (!d || !out) { ocrl_set_error("ocrl_gemm_plan: null argument"); return 1; }
+    GemmArgs a = gemm_args(*d);
+    if (a.splitk > 1) a.sCsplit = (long long)a.M * a.N;      // as ocrl_gemm_ex lays out its workspace
+    if (a.bias_out && a.splitk > 1 && a.sBias == 0) a.sBias = (a.M + 3) & ~3;
+    GemmPlan p;
+    if (gemm_plan(a, &p)) return 1;
+    out[0] = p.bm; out[1] = p.bn; out[2] = p.sb; out[3] = p.xf; out[4] = p.epi; out[5] = p.layout;
+    return 0;
+}
+// split-k as SlateModel::lin_bwd_w runs it: raw partial slabs in ws, then one reduction into C (and one into bias_out)
+int ocrl_gemm_ex(const ocrl_gemm_desc* d, float* ws, size_t ws_floats, void* stream) {
+    if (!d) { ocrl_set_error("ocrl_gemm_ex: null descriptor"); return 1; }
+    GemmArgs a = gemm_args(*d);
+    if (a.splitk <= 1) return gemm_launch(a, ST(stream));
+    const long long slab = (long long)a.M * a.N, bslab = a.sBias ? a.sBias : (a.M + 3) & ~3;
+    const size_t need = (size_t)a.splitk * slab + (a.bias_out ? (size_t)a.splitk * bslab : 0);
+    if (a.ldc != a.N || !ws || ws_floats < need || bslab % 4) {
+        ocrl_set_error("ocrl_gemm_ex: split-k needs ldc == N, sBias %% 4 == 0 and a workspace of %zu floats", need);
+        return 1;
+    }
+    if (a.bias || a.relu || a.drop_p > 0.f || a.mask || a.resid || a.epi_mode) {
+        ocrl_set_error("ocrl_gemm_ex: split-k partial products take no epilogue");
+        return 1;
+    }
+    float* C = a.C;
+    float* db = a.bias_out;
+    a.C = ws; a.sCsplit = slab;
+    if (db) { a.bias_out = ws + (size_t)a.splitk * slab; a.sBias = bslab; }
+    if (gemm_launch(a, ST(stream))) return 1;
+    if (splitk_reduce_launch(ws, C, slab, a.splitk, slab, 0, ST(stream))) return 1;
+    if (!db) return 0;
+    return splitk_reduce_launch(a.bias_out, db, a.M, a.splitk, bslab, 0, ST(stream));      // the dW form has M % 4 == 0
+}
 int ocrl_conv2d_fwd(const float* x, const float* w, const float* bias, float* y, int B, int H, int W, int cin, int cin_pad, int ks, int relu,
                     float* ws, void* stream) {
     if (conv_pack_launch(w, ws, nullptr, ks, cin_pad, 64, cin, ST(stream))) return 1;

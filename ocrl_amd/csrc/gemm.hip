@@ -12,14 +12,14 @@
 // per k-tile).  Within a tile, the k index fed to MFMA step j by lane-half h is  8*c + 4*h + j
 // for both operands, so a k-contiguous operand is one ds_read_b128 per 32 rows per 8 k.
 // The kernel and its tile dispatch live in gemm_impl.h, compiled per operand-layout family (gemm_tt.hip: A [M,K] x B [N,K];
-// gemm_tn.hip: A [M,K] x B [K,N]; gemm_nn.hip: A [K,M]); this file checks the arguments, picks the family and owns the split-k reduction.
+// gemm_tn.hip: A [M,K] x B [K,N]; gemm_nn.hip: A [K,M]); this file checks the arguments, selects the kernel (gemm_plan) and owns the split-k reduction.
 #include "common.h"
 #include "kernels.h"
 #include <stdlib.h>
 
-int gemm_launch_tt(const GemmArgs& a, hipStream_t st);
-int gemm_launch_tn(const GemmArgs& a, hipStream_t st);
-int gemm_launch_nn(const GemmArgs& a, hipStream_t st);
+int gemm_launch_tt(const GemmArgs& a, const GemmPlan& p, hipStream_t st);
+int gemm_launch_tn(const GemmArgs& a, const GemmPlan& p, hipStream_t st);
+int gemm_launch_nn(const GemmArgs& a, const GemmPlan& p, hipStream_t st);
 
 // out[i] = (accumulate ? out[i] : 0) + sum_s part[s*stride + i]   (n % 4 == 0)
 // block = 16 float4 columns x 16 split lanes: the slabs are read in parallel and combined through LDS.
@@ -54,8 +54,28 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
     }
 }
 
-int gemm_launch(const GemmArgs& a_in, hipStream_t st) {
-    GemmArgs a = a_in;
+// development overrides, read once: OCRL_GEMM_TILE=BMxBN (e.g. 128x64) forces one tile shape where that family builds it;
+// OCRL_GEMM_SB: 0 = the buffering rule, 1 = always single, 2 = always double
+static int env_tile() {
+    static int v = -1;
+    if (v < 0) {
+        const char* e = getenv("OCRL_GEMM_TILE");
+        v = 0;
+        if (e) { int bm = 0, bn = 0; if (sscanf(e, "%dx%d", &bm, &bn) == 2) v = bm * 1000 + bn; }
+    }
+    return v;
+}
+static int env_sb() {
+    static int v = -1;
+    if (v < 0) { const char* e = getenv("OCRL_GEMM_SB"); v = e ? atoi(e) : 0; }
+    return v;
+}
+// tile shapes instantiated in gemm_impl.h for an operand layout (128x192 only where A is k-contiguous or B is n-contiguous)
+static bool tile_built(int tile, int akc, int bkc) {
+    return tile == 128128 || tile == 128064 || tile == 64128 || tile == 64064 || (tile == 128192 && (akc || !bkc));
+}
+
+int gemm_plan(const GemmArgs& a, GemmPlan* plan) {
     OCRL_REQUIRE(a.M > 0 && a.N > 0 && a.K > 0, "gemm: empty problem %d %d %d", a.M, a.N, a.K);
     OCRL_REQUIRE(a.batch >= 1 && a.splitk >= 1, "gemm: bad batch/splitk");
     if (a.akc) OCRL_REQUIRE(a.K % 4 == 0 && a.lda % 4 == 0, "gemm: A k-contiguous needs K,lda %% 4 == 0 (K=%d lda=%d)", a.K, a.lda);
@@ -71,6 +91,9 @@ int gemm_launch(const GemmArgs& a_in, hipStream_t st) {
     if (a.bias_out) OCRL_REQUIRE(!a.akc && (a.splitk == 1 || a.sBias >= a.M), "gemm: fused bias gradient needs the dW form");
     OCRL_REQUIRE(!(a.a_mode || a.b_mode) || (a.batch == 1 && a.adrop_p == 0.f && a.x_lse && (a.a_mode != 3 || a.x_tok) &&
                  (a.a_mode == 0 || a.a_mode == 2 || a.a_mode == 3) && (a.b_mode == 0 || a.b_mode == 2)), "gemm: bad operand transform arguments");
+    OCRL_REQUIRE(a.force_sb >= -1 && a.force_sb <= 1, "gemm: force_sb must be -1, 0 or 1 (got %d)", a.force_sb);
+    GemmPlan p;
+    p.layout = 2 * (a.akc ? 1 : 0) + (a.bkc ? 1 : 0);
     if (a.epi_mode) {
         OCRL_REQUIRE(a.akc && a.batch == 1 && a.splitk == 1 && !a.a_mode && !a.b_mode && a.adrop_p == 0.f && a.relu == 0 && a.drop_p == 0.f && !a.resid,
                      "gemm: soft-max epilogue needs a plain k-contiguous A, no split-k / batches / activation");
@@ -81,17 +104,67 @@ int gemm_launch(const GemmArgs& a_in, hipStream_t st) {
             if (a.epi_mode == 2) {
                 OCRL_REQUIRE(a.hstat && a.hidx && (a.e1 == nullptr) == (a.e2 == nullptr) && a.ldc == a.N, "gemm: Gumbel head arguments");
                 OCRL_REQUIRE(!a.e1 || ((((uintptr_t)a.e1) | ((uintptr_t)a.e2)) & 15) == 0, "gemm: Gumbel noise must be 16-byte aligned");
-                return gemm_launch_tt(a, st);
             }
-            return gemm_launch_tt(a, st);
+        } else {
+            OCRL_REQUIRE(a.epi_mode == 3 && !a.bkc && a.mask && a.e_lse && a.e_rowvec && !a.bias && (a.ldmask & 3) == 0 && (((uintptr_t)a.mask) & 15) == 0,
+                         "gemm: soft-max backward epilogue arguments");
         }
-        OCRL_REQUIRE(a.epi_mode == 3 && !a.bkc && a.mask && a.e_lse && a.e_rowvec && !a.bias && (a.ldmask & 3) == 0 && (((uintptr_t)a.mask) & 15) == 0,
-                     "gemm: soft-max backward epilogue arguments");
-        return gemm_launch_tn(a, st);
+        // the soft-max epilogues are built for single-buffered 128x128 tiles only; the environment overrides do not apply to them
+        OCRL_REQUIRE((a.force_tile == 0 || a.force_tile == 128128) && a.force_sb != 0,
+                     "gemm: soft-max epilogue %d is built for single-buffered 128x128 tiles only", a.epi_mode);
+        p.bm = 128; p.bn = 128; p.sb = 1; p.epi = a.epi_mode;
+        *plan = p;
+        return 0;
     }
-    if (a.akc && a.bkc) return gemm_launch_tt(a, st);
-    if (a.akc && !a.bkc) return gemm_launch_tn(a, st);
-    return gemm_launch_nn(a, st);
+    if (a.a_mode || a.b_mode) {
+        OCRL_REQUIRE(a.akc || !a.bkc, "gemm: operand transforms are not built for akc=0 bkc=1");
+        p.xf = 2;
+    } else if (a.adrop_p > 0.f) {
+        p.xf = 1;
+    }
+    int tile = 0, sb = -1;
+    if (a.force_tile) {
+        OCRL_REQUIRE(tile_built(a.force_tile, a.akc, a.bkc), "gemm: tile %dx%d is not built for akc=%d bkc=%d", a.force_tile / 1000,
+                     a.force_tile % 1000, a.akc, a.bkc);
+        tile = a.force_tile;
+    } else if (env_tile() && tile_built(env_tile(), a.akc, a.bkc)) {
+        tile = env_tile();
+    } else if (a.akc && a.N == 192 && a.K >= 1024 && a.M >= 4096) {
+        // measured on MI355X (tools/bench_gemm.py): long-K activation x weight products with N = 192 (the model width), e.g. the
+        // vocabulary-head dX: one 128x192 tile reads A once and moves 38 FLOP per staged byte instead of 21 (+7 % measured at K = 4096;
+        // short K is faster on 128x64)
+        tile = 128192;
+    } else if (!a.akc && !a.bkc && a.N == 192 && a.K >= 4096) {
+        // weight gradients with 192 input features (dW = dY^T X over >= 10^5 rows, split-K): a 128x192 tile reads X once per split
+        // (PMC: the 128x64 tiling moved 643 MB per launch for 201 MB of operands); single LDS buffer to keep two workgroups per CU
+        tile = 128192;
+        sb = 1;
+    } else if (a.N % 128 == 0) {
+        // 128-wide column tiles only pay when N is a multiple of 128; N = 192 / 64 (projections, weight gradients with 192 inputs)
+        // run 10-20 % faster on 128x64 tiles
+        tile = a.M > 64 ? 128128 : 64128;
+    } else {
+        tile = a.M > 64 ? 128064 : 64064;
+    }
+    if (a.force_sb >= 0) {
+        sb = a.force_sb;
+    } else if (sb < 0) {
+        // measured (tools/bench_gemm.py): a single LDS buffer (twice the resident workgroups) wins for the short-K forward / dX forms
+        // (+8..37 %); the long split-K weight-gradient loops keep the double buffer
+        const int mode = env_sb();
+        sb = (mode == 1 || (mode == 0 && a.akc)) ? 1 : 0;
+    }
+    p.bm = tile / 1000; p.bn = tile % 1000; p.sb = sb;
+    *plan = p;
+    return 0;
+}
+
+int gemm_launch(const GemmArgs& a, hipStream_t st) {
+    GemmPlan p;
+    if (gemm_plan(a, &p)) return 1;
+    if (a.akc && a.bkc) return gemm_launch_tt(a, p, st);
+    if (a.akc) return gemm_launch_tn(a, p, st);
+    return gemm_launch_nn(a, p, st);
 }
 
 int splitk_reduce_launch(const float* part, float* out, long long n, int splits, long long stride,

@@ -11,8 +11,8 @@
 // K is consumed in 32-wide tiles, double-buffered in LDS with register prefetch (one barrier
 // per k-tile).  Within a tile, the k index fed to MFMA step j by lane-half h is  8*c + 4*h + j
 // for both operands, so a k-contiguous operand is one ds_read_b128 per 32 rows per 8 k.
-// This header holds the kernel and its tile-shape dispatch; it is compiled three times (gemm_tt.hip, gemm_tn.hip, gemm_nn.hip -- one per
-// operand-layout family) so that the ~110 instantiations build in parallel; gemm.hip keeps the argument checks and the split-k reduction.
+// This header holds the kernel and the launchers of its instantiations (gemm_plan in gemm.hip selects one); it is compiled three times (gemm_tt.hip, gemm_tn.hip, gemm_nn.hip -- one per
+// operand-layout family) so that the ~110 instantiations build in parallel; gemm.hip keeps the argument checks, the selection rule and the split-k reduction.
 #pragma once
 #include "common.h"
 #include "kernels.h"
@@ -547,12 +547,6 @@ __global__ __launch_bounds__(256, (BM * BN == 128 * 128) ? 3 : ((BM * BN == 128 
         }
 }
 
-static int sb_mode() {
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("OCRL_GEMM_SB"); v = e ? atoi(e) : 0; }
-    return v;
-}
-
 template <int BM, int BN, bool AKC, bool BKC, bool SB, int XF, int EPI = 0>
 static int launch_cfg3(const GemmArgs& a, hipStream_t st) {
     // the operand tiles, and at least the four 32x36 staging patches the epilogues lay over them (a single-buffered 64x64 tile with
@@ -572,62 +566,46 @@ static int launch_cfg3(const GemmArgs& a, hipStream_t st) {
     OCRL_CHECK_LAUNCH("gemm_kernel");
     return 0;
 }
+// the instantiations a family builds, selected by the plan gemm_plan (gemm.hip) made for these arguments
 template <int BM, int BN, bool AKC, bool BKC, bool SB>
-static int launch_cfg2(const GemmArgs& a, hipStream_t st) {
-    if (a.a_mode || a.b_mode) {
-        if constexpr (AKC || !BKC)
-            return launch_cfg3<BM, BN, AKC, BKC, SB, 2>(a, st);
-        else
-            OCRL_REQUIRE(false, "gemm: operand transform not built for tile %dx%d akc=%d bkc=%d", BM, BN, (int)AKC, (int)BKC);
+static int launch_xf(const GemmArgs& a, const GemmPlan& p, hipStream_t st) {
+    if (p.xf == 2) {
+        if constexpr (AKC || !BKC) return launch_cfg3<BM, BN, AKC, BKC, SB, 2>(a, st);
+        ocrl_set_error("gemm: operand transform not built for tile %dx%d akc=%d bkc=%d", BM, BN, (int)AKC, (int)BKC);
+        return 1;
     }
-    if (a.adrop_p > 0.f) return launch_cfg3<BM, BN, AKC, BKC, SB, 1>(a, st);
+    if (p.xf == 1) return launch_cfg3<BM, BN, AKC, BKC, SB, 1>(a, st);
     return launch_cfg3<BM, BN, AKC, BKC, SB, 0>(a, st);
 }
 template <int BM, int BN, bool AKC, bool BKC>
-static int launch_cfg(const GemmArgs& a, hipStream_t st) {
-    // measured (tools/bench_gemm.py): a single LDS buffer (twice the resident workgroups) wins for the short-K
-    // forward / dX forms (+8..37 %); the long split-K weight-gradient loops keep the double buffer.
-    const int mode = sb_mode();           // OCRL_GEMM_SB: 0 = rule above, 1 = always single, 2 = always double
-    const bool sb = mode == 1 || (mode == 0 && AKC);
-    if (sb) return launch_cfg2<BM, BN, AKC, BKC, true>(a, st);
-    return launch_cfg2<BM, BN, AKC, BKC, false>(a, st);
+static int launch_sb(const GemmArgs& a, const GemmPlan& p, hipStream_t st) {
+    if (p.sb) return launch_xf<BM, BN, AKC, BKC, true>(a, p, st);
+    return launch_xf<BM, BN, AKC, BKC, false>(a, p, st);
 }
-
-// development override: OCRL_GEMM_TILE=BMxBN (e.g. 128x64) forces one tile shape
-static int tile_override() {
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("OCRL_GEMM_TILE");
-        v = 0;
-        if (e) { int bm = 0, bn = 0; if (sscanf(e, "%dx%d", &bm, &bn) == 2) v = bm * 1000 + bn; }
-    }
-    return v;
-}
-
 template <bool AKC, bool BKC>
-static int launch_tr(const GemmArgs& a, hipStream_t st) {
-    switch (tile_override()) {
-        case 128128: return launch_cfg<128, 128, AKC, BKC>(a, st);
-        case 128064: return launch_cfg<128, 64, AKC, BKC>(a, st);
-        case 64128: return launch_cfg<64, 128, AKC, BKC>(a, st);
-        case 64064: return launch_cfg<64, 64, AKC, BKC>(a, st);
-        case 128192: if (AKC || !BKC) return launch_cfg<128, 192, AKC, BKC>(a, st); break;
+static int launch_family(const GemmArgs& a, const GemmPlan& p, hipStream_t st) {
+    if (p.epi) {
+        // soft-max epilogues: single-buffered 128x128 tiles, k-contiguous A (1, 2: k-contiguous B; 3: n-contiguous B)
+        if constexpr (AKC && BKC) {
+            if (p.epi == 1) return launch_cfg3<128, 128, true, true, true, 0, 1>(a, st);
+            if (p.epi == 2) return launch_cfg3<128, 128, true, true, true, 0, 2>(a, st);
+        }
+        if constexpr (AKC && !BKC) {
+            if (p.epi == 3) return launch_cfg3<128, 128, true, false, true, 0, 3>(a, st);
+        }
+        ocrl_set_error("gemm: soft-max epilogue %d not built for akc=%d bkc=%d", p.epi, (int)AKC, (int)BKC);
+        return 1;
+    }
+    switch (p.bm * 1000 + p.bn) {
+        case 128128: return launch_sb<128, 128, AKC, BKC>(a, p, st);
+        case 128064: return launch_sb<128, 64, AKC, BKC>(a, p, st);
+        case 64128: return launch_sb<64, 128, AKC, BKC>(a, p, st);
+        case 64064: return launch_sb<64, 64, AKC, BKC>(a, p, st);
+        case 128192:
+            if constexpr (AKC || !BKC) return launch_sb<128, 192, AKC, BKC>(a, p, st);
+            break;
         default: break;
     }
-    // measured on MI355X (tools/bench_gemm.py): 128-wide column tiles only pay when N is a multiple of 128;
-    // N = 192 / 64 (projections, weight gradients with 192 inputs) run 10-20 % faster on 128x64 tiles
-    // long-K activation x weight products with N = 192 (the model width), e.g. the vocabulary-head dX: one 128x192 tile reads A
-    // once and moves 38 FLOP per staged byte instead of 21 (+7 % measured at K = 4096; short K is faster on 128x64)
-    if (AKC && a.N == 192 && a.K >= 1024 && a.M >= 4096) return launch_cfg<128, 192, AKC, BKC>(a, st);
-    // weight gradients with 192 input features (dW = dY^T X over >= 10^5 rows, split-K): a 128x192 tile reads X once per split
-    // (PMC: the 128x64 tiling moved 643 MB per launch for 201 MB of operands); single LDS buffer to keep two workgroups per CU
-    if (!AKC && !BKC && a.N == 192 && a.K >= 4096) return launch_cfg2<128, 192, AKC, BKC, true>(a, st);
-    const bool wide = (a.N % 128 == 0);
-    if (wide) {
-        if (a.M > 64) return launch_cfg<128, 128, AKC, BKC>(a, st);
-        return launch_cfg<64, 128, AKC, BKC>(a, st);
-    }
-    if (a.M > 64) return launch_cfg<128, 64, AKC, BKC>(a, st);
-    return launch_cfg<64, 64, AKC, BKC>(a, st);
+    ocrl_set_error("gemm: tile %dx%d not built for akc=%d bkc=%d", p.bm, p.bn, (int)AKC, (int)BKC);
+    return 1;
 }
-

@@ -54,8 +54,19 @@ struct GemmArgs {
     float* stat = nullptr; float* hstat = nullptr; int* hidx = nullptr;
     const float* e1 = nullptr; const float* e2 = nullptr; unsigned long long e_seed = 0;
     const float* e_lse = nullptr; const float* e_rowvec = nullptr; float e_scale = 1.f;
+    // per-call dispatch choice (unit tests; no model call sets them): force_tile 0 = the rule, else BM*1000+BN (as OCRL_GEMM_TILE);
+    // force_sb -1 = the rule, 0 = double-buffered LDS, 1 = single.  They take precedence over the environment overrides, and a
+    // combination that is not built is an error, never a silent fall-back.
+    int force_tile = 0;
+    int force_sb = -1;
 };
 inline int gemm_stat_segments(int N) { return 2 * ((N + 127) / 128); }
+// The kernel gemm_launch runs for a set of arguments: gemm_kernel<bm, bn, akc, bkc, sb, xf, epi>, layout = 2*akc + bkc
+// (3: A [M,K] x B [N,K], 2: A [M,K] x B [K,N], 1: A [K,M] x B [N,K], 0: A [K,M] x B [K,N]).
+struct GemmPlan { int bm = 0, bn = 0, sb = 0, xf = 0, epi = 0, layout = 0; };
+// Checks the arguments and selects the kernel (host only); 0, or 1 with the message in ocrl_last_error().  gemm_launch uses it, so
+// what it reports is what runs.
+int gemm_plan(const GemmArgs& a, GemmPlan* plan);
 int gemm_launch(const GemmArgs& a, hipStream_t st);
 int splitk_reduce_launch(const float* part, float* out, long long n, int splits, long long stride,
                          int accumulate, hipStream_t st);

@@ -2,6 +2,7 @@
 import os
 import sys
 
+import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -172,3 +173,53 @@ def mask_matched_fp64_grads(cfg, P, obs, noise, step, masks, drop_masks=None):
     with ForcedRelu(masks) as fr:
         tr.loss_and_grads(obs.double(), {k: v.double() for k, v in noise.items()}, step, dm)
     return tr, fr
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# Host restatement of the counter RNG in csrc/common.h (rng_key, rng_mix32k, rng_bits4, rng_keep, drop_thresh): the exact keep
+# decisions of a dropout site, for tests that grade the kernels' keep patterns bit for bit.
+_M32 = 0xFFFFFFFF
+
+
+def rng_mix32(x):
+    x &= _M32
+    x ^= x >> 16; x = (x * 0x7FEB352D) & _M32
+    x ^= x >> 15; x = (x * 0x846CA68B) & _M32
+    x ^= x >> 16
+    return x
+
+
+def rng_key(seed, site, hi=0):
+    """csrc/common.h rng_key (Python ints)"""
+    return rng_mix32((seed & _M32) ^ ((site * 0x9E3779B9) & _M32)) ^ rng_mix32(((seed >> 32) + 0x85EBCA6B * (hi + 1)) & _M32)
+
+
+def _mix32k(x, k2):
+    x = x ^ (x >> np.uint64(16)); x = (x * np.uint64(0x7FEB352D)) & np.uint64(_M32)
+    x = (x + k2) & np.uint64(_M32)
+    x = x ^ (x >> np.uint64(15)); x = (x * np.uint64(0x846CA68B)) & np.uint64(_M32)
+    return x ^ (x >> np.uint64(16))
+
+
+def rng_bits4(seed, site, idx4):
+    """csrc/common.h rng_bits4 for an array of group counters (< 2^32): (x, y) as uint64 arrays holding 32-bit words"""
+    idx4 = np.asarray(idx4, dtype=np.uint64)
+    assert idx4.size == 0 or int(idx4.max()) < 2 ** 32
+    key = rng_key(seed, site, 0)
+    k2 = np.uint64((key * 0x9E3779B9 + 0x7F4A7C15) & _M32)
+    c = idx4 ^ np.uint64(key)
+    return _mix32k(c, k2), (_mix32k(c ^ np.uint64(0x68E31DA4), k2) + np.uint64(key)) & np.uint64(_M32)
+
+
+def drop_thresh(p):
+    return int(np.float32(np.float32(p) * np.float32(65536.0) + np.float32(0.5)))
+
+
+def dropout_keep(seed, site, p, idx):
+    """keep decision (bool array) of the elements with flat indices idx at a dropout site: rng_keep(rng_bits4(idx / 4), idx % 4)"""
+    idx = np.asarray(idx, dtype=np.uint64)
+    x, y = rng_bits4(seed, site, idx >> np.uint64(2))
+    e = idx & np.uint64(3)
+    w = np.where(e & np.uint64(2), y, x)
+    u = np.where(e & np.uint64(1), w >> np.uint64(16), w & np.uint64(0xFFFF))
+    return u >= np.uint64(drop_thresh(p))

@@ -7,6 +7,7 @@ import torch
 
 from oracle import slate_oracle as O
 from tests.gpu_util import dims_from_cfg, load_params
+from tests.gpu_util import rng_key as _rng_key
 
 pytestmark = pytest.mark.gpu
 
@@ -105,19 +106,6 @@ def test_device_rng_quality():
     assert abs(corr(a[:-1], a[1:])) < 4e-3 and abs(corr(a[:-4], a[4:])) < 4e-3 and abs(corr(a[:-64], a[64:])) < 4e-3      # serial
     assert abs(corr(a, b)) < 4e-3 and abs(corr(a, c)) < 4e-3                                                                   # site / seed
     assert not torch.equal(a, b) and not torch.equal(a, c)
-
-
-def _mix32(x):
-    x &= 0xFFFFFFFF
-    x ^= x >> 16; x = (x * 0x7FEB352D) & 0xFFFFFFFF
-    x ^= x >> 15; x = (x * 0x846CA68B) & 0xFFFFFFFF
-    x ^= x >> 16
-    return x
-
-
-def _rng_key(seed, site, hi=0):
-    """csrc/common.h rng_key"""
-    return _mix32((seed & 0xFFFFFFFF) ^ ((site * 0x9E3779B9) & 0xFFFFFFFF)) ^ _mix32(((seed >> 32) + 0x85EBCA6B * (hi + 1)) & 0xFFFFFFFF)
 
 
 def test_device_rng_streams_are_not_translates():
