@@ -5,9 +5,14 @@ vocab 4096 — BASELINE.json's metric — on N MI355X (one process per GPU, RCCL
     python bench.py --gpus 1 --steps 10 --warmup 3
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
-Rank 0 prints ONE JSON line.  `roofline` is measured live with HIP events on the launch stream around the
-dominant kernel family (the 5x5 / 64-channel MFMA convolution, forward and backward-data launches);
-`cpu_baseline` times the CPU oracle (oracle/slate_oracle.py, a port of the reference step) on the host cores.
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the line;
+`roofline` and `slot_attention.in_step` are measured live with HIP events on the launch stream around the dominant kernel
+family (the 5x5 / 64-channel MFMA convolution, forward and backward-data launches) and the slot-attention chain inside the
+timed steps.  `--full` adds what takes runs of its own: `slot_attention.fwd` / `bwd` (the chain on its own), the
+exploratory split-precision second pass (`exploratory_conv_x3`) and `cpu_baseline`, which times the CPU oracle
+(oracle/slate_oracle.py, a port of the reference step) on the host cores.
+
+    python bench.py --gpus 1 --steps 10 --warmup 3 --full
 """
 import argparse
 import ctypes
@@ -268,7 +273,7 @@ def bench_iodine(args, dev, dist, rank, world):
             "roofline": mfma_roofline("conv_fwd_kernel<3,64,64> (IODINE decoder 3x3 convs on B*K slot images: forward, in-forward and backward data gradients)",
                                       conv_flops_step, ms[1], cnt[1], args.steps, None),
             "decoder_mfma_frac": round(ips / world * flop_img / (PEAK_MFMA_F32_TFLOPS * 1e12), 4), "final_loss": round(float(loss.item()), 4)}
-        if world == 1 and not args.conv_x3 and not args.no_exploratory:
+        if args.full and world == 1 and not args.conv_x3 and not args.no_exploratory:
             # EXPLORATORY second pass, never `value`: the decoder's 3x3 / 64-channel convolutions on the split-precision bf16 kernels (csrc/conv_x3.hip)
             del model, mod
             torch.cuda.empty_cache()
@@ -293,7 +298,7 @@ def bench_iodine(args, dev, dist, rank, world):
                 out["exploratory_conv_x3"] = {"error": repr(e)}
             finally:
                 os.environ.pop("OCRL_CONV_X3", None)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline_iodine(S, K, 8, 3)
         print(json.dumps(out))
     if dist is not None:
@@ -329,14 +334,17 @@ def main():
     ap.add_argument("--batch", type=int, default=128, help="images per GPU")
     ap.add_argument("--obs-size", type=int, default=128)
     ap.add_argument("--num-slots", type=int, default=6, help="6 = headline; 16 with --obs-size 256 = BASELINE config 5")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need, each in runs of its own: the slot-attention chain alone, the "
+                         "exploratory split-precision second pass and the CPU-oracle baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU-oracle baseline")
     ap.add_argument("--workload", choices=["slate", "slotattn", "iodine"], default="slate",
                     help="slotattn = BASELINE config 2 (use_bcdec); iodine = config 4 (use --obs-size 64 --num-slots 7); headline = slate")
     ap.add_argument("--dropout", type=float, default=0.1, help="diagnostic only: the headline number uses the reference default 0.1")
     ap.add_argument("--rehearse-on-one-gpu", action="store_true",
                     help="development only: all ranks share cuda:0 and reduce over gloo, to rehearse the N > 1 launch / barrier / reduction "
                          "plumbing on a one-GPU box (RCCL refuses two ranks on one device); the line is marked and is not a measurement")
-    ap.add_argument("--no-exploratory", action="store_true", help="skip the exploratory split-precision second pass of the default run")
+    ap.add_argument("--no-exploratory", action="store_true", help="with --full: skip the exploratory split-precision second pass")
     ap.add_argument("--conv-x3", action="store_true",
                     help="EXPLORATORY, never the headline: the 5x5 / 64-channel forward and backward-data convolutions on the bf16 matrix pipe "
                          "with fp32 operands split exactly into three bf16 numbers (csrc/conv_x3.hip); the line names the arithmetic in `dtype`")
@@ -436,16 +444,18 @@ def main():
     if cnt[4] and cnt[5]:
         def leg(t_ms, nbytes):
             return {"avg_ms": round(t_ms, 4), "achieved": round(nbytes / t_ms / 1e6, 1), "frac": round(nbytes / t_ms / 1e6 / PEAK_HBM_GBS, 4)}
-        sf_ms, sb_ms = slot_attention_standalone(B, N, K)
-        out["slot_attention"] = {"bound": "hbm", "peak": PEAK_HBM_GBS, "unit": "GB/s", "kernels": "sa_stream_fwd/bwd_kernel + sa_slot_fwd/bwd_kernel (one chain per call)",
-                                 "fwd": leg(sf_ms, fwd_bytes), "bwd": leg(sb_ms, bwd_bytes),
-                                 "in_step": {"fwd": leg(ms[4] / cnt[4], fwd_bytes), "bwd": leg(ms[5] / cnt[5], bwd_bytes),
-                                             "note": "inside the step the forward chain shares the GPU with the dVAE branch on the side stream (OCRL_OVERLAP)"},
+        sa = {"bound": "hbm", "peak": PEAK_HBM_GBS, "unit": "GB/s", "kernels": "sa_stream_fwd/bwd_kernel + sa_slot_fwd/bwd_kernel (one chain per call)"}
+        if args.full:
+            sf_ms, sb_ms = slot_attention_standalone(B, N, K)
+            sa.update(fwd=leg(sf_ms, fwd_bytes), bwd=leg(sb_ms, bwd_bytes))
+        out["slot_attention"] = {**sa, "in_step": {"fwd": leg(ms[4] / cnt[4], fwd_bytes), "bwd": leg(ms[5] / cnt[5], bwd_bytes),
+                                                   "note": "inside the step the forward chain shares the GPU with the dVAE branch on the side stream (OCRL_OVERLAP)"},
                                  "pmc": committed_slot_attention_pmc(B, S),
                                  "note": "algorithmic bytes of the folded-projection form (12.6 MB/img forward, 33.5 MB/img backward at N=16384; the reference's "
-                                         "materialised k|v form would move 75.5 MB/img forward); fwd / bwd = the chain on its own at the same shape, HIP events "
-                                         "around its launches; pmc = matrix-pipe busy fraction / resident waves per SIMD / HBM bytes per launch from rocprofv3 counters"}
-    if world == 1 and not args.conv_x3 and not args.no_exploratory:
+                                         "materialised k|v form would move 75.5 MB/img forward); fwd / bwd (--full only) = the chain on its own at the same shape, "
+                                         "HIP events around its launches; pmc = matrix-pipe busy fraction / resident waves per SIMD / HBM bytes per launch from "
+                                         "rocprofv3 counters"}
+    if args.full and world == 1 and not args.conv_x3 and not args.no_exploratory:
         # EXPLORATORY second pass, never `value`: the same step with the 5x5 / 64-channel convolutions (forward, backward-data, weight
         # gradient) on the bf16 matrix pipe, every fp32 operand split exactly into three bf16 numbers and six products accumulated in fp32
         # (csrc/conv_x3.hip).  The GPU parity suite passes unchanged with OCRL_CONV_X3=1 (profiles/r03_exploratory_conv_x3_gpu_suite.log).
@@ -471,7 +481,7 @@ def main():
             out["exploratory_conv_x3"] = {"error": repr(e)}
         finally:
             os.environ.pop("OCRL_CONV_X3", None)
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(S, 8, 3, use_bcdec=bool(ocr.use_bcdec), num_slots=int(ocr.slotattr.num_slots))
     if args.rehearse_on_one_gpu:
         out["rehearsal"] = "all ranks on cuda:0, gradients reduced over gloo: exercises the launch / barrier / reduction plumbing only, not a measurement"
