@@ -241,6 +241,22 @@ int ocrl_pool_transformer_long_bwd(const float* slots, const float* dout, const 
                                    int Din, int d, int nhead, int ff, int L, float drop_p, unsigned long long seed, float* ws, size_t ws_floats,
                                    void* stream);
 
+/* ---- Relation Network pooling head: poolings/rn/rn_module.py:8-59 (RN_Module.forward: every ordered slot pair cat(s_i, s_j) in
+ * itertools.permutations order (:33-47) -> g = [Linear, ReLU] x len(g_dims) -> sum over the K (K-1) pairs (:57) -> f = [Linear, ReLU] x
+ * len(f_dims)), as built by poolings/rn/rn.py:6-9 with configs/pooling/rn.yaml; the consumer of the slots in sb3s/ocr_extractor.py:45.
+ * slots [B,K,D]; `w` = 2 (ng + nf) device pointers in the module's state_dict order: _g.0.{weight [g_dims[0], 2D], bias},
+ * _g.2.{weight, bias}, ..., _f.0.{weight [f_dims[0], g_dims[ng-1]], bias}, ...  out [B, f_dims[nf-1]].
+ * _bwd: dout [B, f_dims[nf-1]] -> dw (same order / shapes as w; every entry is overwritten) and dslots [B,K,D] (NULL = the slots are
+ * detached, poolings/base.py:53).  Call it with the same ws right after _fwd.  K >= 2; every g / f width a multiple of 4; any D >= 1;
+ * 1 <= ng, nf <= OCRL_POOL_RN_MAX_LAYERS.  Shapes whose pair rows (B K (K-1)) times the widest g layer leave the int32 range of one GEMM
+ * are rejected (a CNN feature map as slots).  Rejected shapes get ws_floats == 0; _fwd / _bwd return non-zero for them. */
+#define OCRL_POOL_RN_MAX_LAYERS 16
+size_t ocrl_pool_rn_ws_floats(int B, int K, int D, int ng, const int* g_dims, int nf, const int* f_dims);
+int ocrl_pool_rn_fwd(const float* slots, const float* const* w, float* out, int B, int K, int D, int ng, const int* g_dims, int nf, const int* f_dims,
+                     float* ws, size_t ws_floats, void* stream);
+int ocrl_pool_rn_bwd(const float* slots, const float* dout, const float* const* w, float* dslots, float* const* dw, int B, int K, int D, int ng,
+                     const int* g_dims, int nf, const int* f_dims, float* ws, size_t ws_floats, void* stream);
+
 /* ---- IODINE (ocrs/iodine/iodine_module.py:14-271, ocrs/iodine/iodine.py:4-14, ocrs/base.py:60-74): SURVEY.md §8 row a20 ----
  * Same conventions as the SLATE handle: flat fp32 parameter / gradient / Adam buffers in the reference's
  * _module.parameters() order and state_dict names, adopted from the caller; one workspace; all work on the caller's stream. */

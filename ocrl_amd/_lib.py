@@ -146,6 +146,10 @@ def lib():
     L.ocrl_pool_transformer_long_ws_floats.restype = c_size_t
     L.ocrl_pool_transformer_long_fwd.argtypes = L.ocrl_pool_transformer_fwd.argtypes
     L.ocrl_pool_transformer_long_bwd.argtypes = L.ocrl_pool_transformer_bwd.argtypes
+    L.ocrl_pool_rn_ws_floats.argtypes = [c_int, c_int, c_int, c_int, POINTER(c_int), c_int, POINTER(c_int)]
+    L.ocrl_pool_rn_ws_floats.restype = c_size_t
+    L.ocrl_pool_rn_fwd.argtypes = [p, POINTER(p), p, c_int, c_int, c_int, c_int, POINTER(c_int), c_int, POINTER(c_int), p, c_size_t, p]
+    L.ocrl_pool_rn_bwd.argtypes = [p, p, POINTER(p), p, POINTER(p), c_int, c_int, c_int, c_int, POINTER(c_int), c_int, POINTER(c_int), p, c_size_t, p]
     L.ocrl_comm_unique_id.argtypes = [p, c_size_t]
     L.ocrl_comm_init.argtypes = [POINTER(p), c_int, c_int, p]
     L.ocrl_comm_allreduce.argtypes = [p, p, c_longlong, p]

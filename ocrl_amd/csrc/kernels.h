@@ -107,6 +107,23 @@ int pool_cls_attn_bwd_launch(const PoolClsArgs& a, hipStream_t st);
 int pool_flash_launch(const float* qkv, float* O, float* lse, const float* dO, float* Dd, float* dqkv, int B, int S, int d, int h, float p,
                       unsigned long long seed, unsigned site, int backward, hipStream_t st);
 
+// ------------------------------------------------------------------ pool_unit.cpp: Linear layers of the pooling heads on the GEMM
+// y = epilogue(x W^T + b): relu, dropout at `site`, + resid
+int lin_fwd(const float* x, const float* W, const float* b, float* y, long long M, int N, int Kk, int relu, const float* resid, float p, unsigned long long seed,
+            unsigned site, hipStream_t st);
+// dx = alpha * (drop(dy) W) * (mask > 0) + resid
+int lin_bwd_x(const float* dy, const float* W, float* dx, long long M, int N_out, int K_in, float alpha, const float* mask, const float* resid, float p,
+              unsigned long long seed, unsigned site, hipStream_t st);
+// dW = drop(dy)^T x, db = column sums of drop(dy); split over the M rows through `sk` when there are enough of them
+int lin_bwd_w(const float* dy, const float* x, float* dW, float* db, long long M, int N_out, int K_in, float p, unsigned long long seed, unsigned site,
+              float* sk, size_t sk_floats, hipStream_t st);
+
+// ------------------------------------------------------------------ rn.hip (Relation Network pooling: include/ocrl_hip.h ocrl_pool_rn_*)
+int rn_pair_fwd_launch(const float* AB, const float* b1, float* h1, int B, int K, int g, hipStream_t st);
+int rn_pair_bwd_launch(const float* dh1, float* dAB, int B, int K, int g, hipStream_t st);
+int rn_pairsum_fwd_launch(const float* gL, float* y, int B, int P, int g, hipStream_t st);
+int rn_pairsum_bwd_launch(const float* dy, const float* gL, float* dgL, int B, int P, int g, hipStream_t st);
+
 // ------------------------------------------------------------------ conv.hip
 struct ConvArgs {
     const float* X = nullptr;       // [B,H,W,CIN] NHWC

@@ -51,7 +51,9 @@ Lay layout(int B, int K, int Din, int d, int h, int ff, int L) {
     y.total = a;
     return y;
 }
+}  // namespace
 
+// the Linear helpers are shared with the Relation Network head (rn_unit.cpp; declared in kernels.h)
 // y = epilogue(x W^T + b): relu, dropout at `site`, + resid
 int lin_fwd(const float* x, const float* W, const float* b, float* y, long long M, int N, int Kk, int relu, const float* resid, float p, unsigned long long seed,
             unsigned site, hipStream_t st) {
@@ -91,6 +93,8 @@ int lin_bwd_w(const float* dy, const float* x, float* dW, float* db, long long M
     a.bias_out = db;
     return gemm_launch(a, st);
 }
+
+namespace {
 int check_dims(int B, int K, int Din, int d, int h, int ff, int L) {
     OCRL_REQUIRE(B > 0 && K >= 1 && K + 1 <= 32, "pool_transformer: 1 <= num_slots <= 31 (got %d)", K);
     OCRL_REQUIRE(L >= 1 && L <= OCRL_POOL_MAX_LAYERS, "pool_transformer: 1 <= num_layers <= %d (got %d)", OCRL_POOL_MAX_LAYERS, L);

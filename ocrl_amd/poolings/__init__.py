@@ -1,6 +1,10 @@
-"""Drop-in for the reference's ``poolings`` package on the Transformer path:
-``getattr(poolings, config.pooling.name)(ocr, config.pooling)`` and ``getattr(poolings, name + "_Module")`` (sb3s/ocr_extractor.py:20-35)."""
+"""Drop-in for the reference's ``poolings`` package: ``getattr(poolings, config.pooling.name)(ocr, config.pooling)``
+and ``getattr(poolings, name + "_Module")`` (sb3s/ocr_extractor.py:20-35).  Built: Transformer, RN, MLP, Identity; not built: the
+NatureCNN heads CNN_Linear and CNN_Transformer."""
 from .base import Base
+from .identity import Identity, Identity_Module
+from .mlp import MLP, MLP_Module
+from .rn import RN, RN_Module
 from .transformer import Transformer, Transformer_Module
 
-__all__ = ["Base", "Transformer", "Transformer_Module"]
+__all__ = ["Base", "Transformer", "Transformer_Module", "RN", "RN_Module", "MLP", "MLP_Module", "Identity", "Identity_Module"]

@@ -20,10 +20,22 @@ except Exception:                                             # pragma: no cover
             return self._features_dim
 
 
+def make_pooling_module(config, rep_dim, num_slots):
+    """the pooling head ``config.pooling.name`` over ``num_slots`` slots of width ``rep_dim``.  The reference builds every head as
+    ``Name_Module(rep_dim, num_slots, config.pooling)`` (sb3s/ocr_extractor.py:32), which cannot build RN: RN_Module takes
+    (rep_dim, num_slots, num_stacked_obss, config) (poolings/rn/rn_module.py:9).  Here RN gets its arguments in its own order, with
+    num_stacked_obss from config.env (default 1); every other head is built exactly as the reference builds it."""
+    name = config.pooling.name
+    if name == "RN":
+        env = getattr(config, "env", None)
+        return poolings.RN_Module(rep_dim, num_slots, getattr(env, "num_stacked_obss", 1), config.pooling)
+    return getattr(poolings, name + "_Module")(rep_dim, num_slots, config.pooling)
+
+
 class OCRExtractor(_BaseExtractor):
     def __init__(self, observation_space, config=None):
         ocr = getattr(ocrs, config.ocr.name)(config.ocr, config.env)
-        rep_dim = getattr(poolings, config.pooling.name + "_Module")(ocr.rep_dim, ocr.num_slots, config.pooling).rep_dim
+        rep_dim = make_pooling_module(config, ocr.rep_dim, ocr.num_slots).rep_dim
         super().__init__(observation_space, rep_dim)
         self._num_envs = config.num_envs
         # get_ocr (utils/tools.py:323-347): without a checkpoint, or with ocr_checkpoint.finetuning, the extractor owns the encoder *module*
@@ -50,7 +62,7 @@ class OCRExtractor(_BaseExtractor):
             if hasattr(mod, "freeze_weights"):
                 mod.freeze_weights(True)                       # constant weights: no re-packing per call
             self._ocr = ocr
-        self._pooling = getattr(poolings, config.pooling.name + "_Module")(ocr.rep_dim, ocr.num_slots, config.pooling)
+        self._pooling = make_pooling_module(config, ocr.rep_dim, ocr.num_slots)
 
     def forward(self, observations):
         if self._trainable:
