@@ -257,6 +257,24 @@ int ocrl_pool_rn_fwd(const float* slots, const float* const* w, float* out, int 
 int ocrl_pool_rn_bwd(const float* slots, const float* dout, const float* const* w, float* dslots, float* const* dw, int B, int K, int D, int ng,
                      const int* g_dims, int nf, const int* f_dims, float* ws, size_t ws_floats, void* stream);
 
+/* ---- NatureCNN / MultipleCNN encoders: ocrs/naturecnn/naturecnn_module.py:11-63 (configs/ocr/naturecnn.yaml) and
+ * ocrs/multiple_cnns/multiple_cnn_module.py:12-38 (G = num_modules NatureCNN modules on the same image, stacked on axis 1).
+ * Per module: Conv2d(cin, 32, 8, s 4) ReLU  Conv2d(32, 64, 4, s 2) ReLU  Conv2d(64, 64, 3, s 1) ReLU  [Conv2d(64, 128, 3, s 1) ReLU when
+ * cnn_feat_size == 2], all padding 0; then, without use_cnn_feat, Flatten (NCHW order) and Linear(n_flatten, rep_dim) ReLU.
+ * obs [B, cin, H, W] (NCHW).  out: [B, G, rep_dim] without use_cnn_feat ([B, rep_dim] for G = 1); [B, OH OW, C] (HWC tokens) with it.
+ * `w` = the parameters in state_dict order, module-major for G > 1: _cnn.0.{weight, bias}, _cnn.2.*, _cnn.4.*[, _cnn.6.*][, _linear.0.*].
+ * They are read on every call (nothing is packed or cached).  save != 0 leaves in ws what _bwd needs; _bwd (called with the same ws right
+ * after a saving _fwd): dout (out's shape) -> dw (same order / shapes as w; every entry is overwritten, not accumulated).  The
+ * observation gets no gradient.  Rejected shapes get ws_floats == 0 and fail in _fwd / _bwd: B < 1, an input below 36 x 36 (52 x 52
+ * with the 4th conv), rep_dim not a positive multiple of 4, G outside 1 .. OCRL_NATURECNN_MAX_GROUPS, use_cnn_feat with G > 1. */
+#define OCRL_NATURECNN_MAX_GROUPS 16
+#define OCRL_NATURECNN_MAX_CONVS 4
+size_t ocrl_naturecnn_ws_floats(int B, int H, int W, int cin, int groups, int cnn_feat_size, int use_cnn_feat, int rep_dim);
+int ocrl_naturecnn_fwd(const float* obs, const float* const* w, float* out, int B, int H, int W, int cin, int groups, int cnn_feat_size,
+                       int use_cnn_feat, int rep_dim, int save, float* ws, size_t ws_floats, void* stream);
+int ocrl_naturecnn_bwd(const float* obs, const float* dout, const float* const* w, float* const* dw, int B, int H, int W, int cin, int groups,
+                       int cnn_feat_size, int use_cnn_feat, int rep_dim, float* ws, size_t ws_floats, void* stream);
+
 /* ---- IODINE (ocrs/iodine/iodine_module.py:14-271, ocrs/iodine/iodine.py:4-14, ocrs/base.py:60-74): SURVEY.md §8 row a20 ----
  * Same conventions as the SLATE handle: flat fp32 parameter / gradient / Adam buffers in the reference's
  * _module.parameters() order and state_dict names, adopted from the caller; one workspace; all work on the caller's stream. */

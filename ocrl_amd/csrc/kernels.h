@@ -2,6 +2,7 @@
 // orchestration (slate_model.cpp) and the C ABI (capi.cpp).  Not part of the public ABI.
 #pragma once
 #include "common.h"
+#include "../../include/ocrl_hip.h"
 
 // ------------------------------------------------------------------ prof.cpp
 enum { PROF_CONV5 = 0, PROF_CONV_OTHER = 1, PROF_WGRAD = 2, PROF_GEMM = 3, PROF_SA_FWD = 4, PROF_SA_BWD = 5, PROF_ATTN_FWD = 6, PROF_ATTN_BWD = 7, PROF_NTAGS = 8 };
@@ -123,6 +124,37 @@ int rn_pair_fwd_launch(const float* AB, const float* b1, float* h1, int B, int K
 int rn_pair_bwd_launch(const float* dh1, float* dAB, int B, int K, int g, hipStream_t st);
 int rn_pairsum_fwd_launch(const float* gL, float* y, int B, int P, int g, hipStream_t st);
 int rn_pairsum_bwd_launch(const float* dy, const float* gL, float* dgL, int B, int P, int g, hipStream_t st);
+
+// ------------------------------------------------------------------ naturecnn.hip (NatureCNN / MultipleCNN: include/ocrl_hip.h ocrl_naturecnn_*)
+// element offset of (image b, group g, channel c, row h, column w) in a map
+struct NcMap { long long sN = 0, sG = 0, sC = 0, sH = 0, sW = 0; };
+struct NcFwdArgs {
+    const float* X = nullptr; NcMap x;             // layer input, cin channels per group (x.sG = 0: every group reads the same channels)
+    float* Y = nullptr; float* Y2 = nullptr; NcMap y;   // relu(conv + bias), cout channels per group; Y2 (optional) gets a second copy
+    const float* w[OCRL_NATURECNN_MAX_GROUPS] = {}; const float* bias[OCRL_NATURECNN_MAX_GROUPS] = {};   // [cout, cin, ks, ks], [cout]
+    int B = 0, G = 1, cin = 0, cout = 0, H = 0, W = 0, OH = 0, OW = 0, ks = 0, stride = 0;
+};
+struct NcBwdArgs {
+    const float* X = nullptr; NcMap x;             // layer input; also the ReLU mask of dX
+    const float* dY = nullptr; NcMap dy;           // gradient of the pre-activation of this layer
+    float* dX = nullptr;                           // masked gradient of the lower layer's pre-activation, layout x (NULL: not wanted)
+    float* part = nullptr;                         // [slabs][G][cout][cin ks ks + 1] weight / bias gradient partials
+    int slabs = 1, slab_rows = 0;                  // the B OH OW rows in slabs of slab_rows (a multiple of 4)
+    const float* w[OCRL_NATURECNN_MAX_GROUPS] = {};
+    int B = 0, G = 1, cin = 0, cout = 0, H = 0, W = 0, OH = 0, OW = 0, ks = 0, stride = 0;
+    long long dw_tiles = 0, dx_tiles = 0; int dw_blocks = 0;   // set by nc_conv_bwd_launch
+};
+struct NcReduceLayer { const float* part = nullptr; int slabs = 0, G = 0, cout = 0, K = 0; long long n = 0; };
+struct NcReduceArgs {
+    NcReduceLayer L[OCRL_NATURECNN_MAX_CONVS];
+    float* dw[OCRL_NATURECNN_MAX_CONVS][OCRL_NATURECNN_MAX_GROUPS] = {};
+    float* db[OCRL_NATURECNN_MAX_CONVS][OCRL_NATURECNN_MAX_GROUPS] = {};
+    int nlayers = 0;
+};
+int nc_conv_fwd_launch(const NcFwdArgs& a, hipStream_t st);
+int nc_conv_bwd_launch(NcBwdArgs a, hipStream_t st);      // dW partials of the layer and, when a.dX, the masked data gradient: one launch
+int nc_dw_reduce_launch(const NcReduceArgs& a, hipStream_t st);
+int nc_relu_mask_launch(const float* d, const float* act, float* out, long long n, hipStream_t st);
 
 // ------------------------------------------------------------------ conv.hip
 struct ConvArgs {

@@ -12,11 +12,14 @@ class Base:
         if self._learn_downstream_loss:
             # poolings/base.py:53-55: the slots reach the pooling head undetached.  The encoder's forward is a library call, not a torch
             # graph: its module keeps the slots attached through an autograd function that routes d loss / d slots into
-            # ocrl_slate_encode_backward (ocrs/slate.py::_EncodeGrad); set_zero_grad() / do_step() then act on the flat buffers
+            # ocrl_slate_encode_backward (ocrs/slate.py::_EncodeGrad); set_zero_grad() / do_step() then act on the flat buffers.  Encoders
+            # whose module trains through torch autograd (NatureCNN, MultipleCNN: trains_through_autograd) need no routing: their torch
+            # Adam steps the gradients autograd leaves on the module's parameters
             mod = getattr(ocr, "_module", None)
-            if mod is None or not hasattr(mod, "finetune_through_slots") or getattr(mod, "_use_cnn_feat", False):
-                raise NotImplementedError("learn_downstream_loss=True is built for the SLATE / Slot-Attention encoder's slots (not use_cnn_feat, not IODINE)")
-            mod.finetune_through_slots = True
+            if not getattr(mod, "trains_through_autograd", False):
+                if mod is None or not hasattr(mod, "finetune_through_slots") or getattr(mod, "_use_cnn_feat", False):
+                    raise NotImplementedError("learn_downstream_loss=True is built for the SLATE / Slot-Attention encoder's slots (not use_cnn_feat, not IODINE)")
+                mod.finetune_through_slots = True
         self._load_ocr()
         self.rep_dim = self._module.rep_dim
         if hasattr(self._config, "learning") and hasattr(self._config.learning, "lr"):

@@ -51,11 +51,14 @@ class OCRExtractor(_BaseExtractor):
         ocr.to(config.device)                                 # get_ocr(..., config.device)
         self._trainable = (not path) or bool(getattr(ck, "finetuning", False))
         mod = getattr(ocr, "_module", None)
-        if self._trainable and (mod is None or not hasattr(mod, "finetune_through_slots") or getattr(mod, "_use_cnn_feat", False)):
+        # encoders whose module trains through torch autograd (NatureCNN, MultipleCNN: trains_through_autograd) need no routing
+        autograd_enc = getattr(mod, "trains_through_autograd", False)
+        if self._trainable and not autograd_enc and (mod is None or not hasattr(mod, "finetune_through_slots") or getattr(mod, "_use_cnn_feat", False)):
             raise NotImplementedError("training the encoder through the RL loss is built for the SLATE / Slot-Attention slots; give a "
                                       "pre-trained checkpoint (pooling.ocr_checkpoint.local_file) without finetuning for this encoder")
         if self._trainable:
-            mod.finetune_through_slots = True                 # the slots stay attached: d loss / d slots -> ocrl_slate_encode_backward
+            if not autograd_enc:
+                mod.finetune_through_slots = True             # the slots stay attached: d loss / d slots -> ocrl_slate_encode_backward
             self._ocr = mod                                    # registered as a sub-module: its parameters are the extractor's
         else:
             ocr.eval()
