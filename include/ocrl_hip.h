@@ -275,6 +275,28 @@ int ocrl_naturecnn_fwd(const float* obs, const float* const* w, float* out, int 
 int ocrl_naturecnn_bwd(const float* obs, const float* dout, const float* const* w, float* const* dw, int B, int H, int W, int cin, int groups,
                        int cnn_feat_size, int use_cnn_feat, int rep_dim, float* ws, size_t ws_floats, void* stream);
 
+/* ---- VAE representation module: ocrs/vaes/vae_module.py, ocrs/common/models.py:49-93 (VAEEncoder / VAEDecoder), configs/ocr/vae.yaml.
+ * n = log2(obs_size / cnn_feat_size) stages (1 .. OCRL_VAE_MAX_STAGES), f = cnn_feat_size, L = latent_dim (a multiple of 4), C =
+ * obs_channels (1 .. 4).  obs [B, C, S, S] (NCHW).  `w` = every parameter in state_dict order: _enc._encoder.{0 .. 4n - 1}.m.*,
+ * _enc._encoder.4n.*, _mu.*, _var.*, _in_dec.*, _dec._decoder.0.m.*, the 4n Conv2dBlocks of the decoder stages (the PixelShuffle slots
+ * have no parameters), _dec._decoder.(5n + 1).*: 2 (8n + 6) tensors, read in torch's layout on every call (packed into ws per call).
+ * full = 0 (encoder only, the rollout): rep = mu [B, L], or with use_cnn_feat the encoder map as img_to_slot tokens [B, f f, 64];
+ *   eps, metrics and recon are not read; only the encoder's and _mu's entries of dw are written by _bwd (the others may be NULL).
+ * full = 1 (get_loss): also eps [B, L] (the reparameterisation noise), metrics [3] = (loss, mse, kld) with
+ *   kld = mean_B(-0.5 sum(1 + logvar - mu^2 - exp(logvar))) (the reference's metric is -kld), recon [B, C, S, S] when not NULL.
+ * _bwd (called with the same ws right after _fwd, same arguments): dloss (device scalar) is the cotangent of loss, drep (same shape as
+ * rep; required when full = 0) the cotangent of rep; they are summed, and a NULL one counts as zero (dloss NULL: the decoder and KL
+ * terms are skipped and the decoder-side entries of dw are zeroed).  dw: same order / shapes as w, overwritten.
+ * The observation gets no gradient.  Rejected shapes get ws_floats == 0 and fail in _fwd / _bwd. */
+#define OCRL_VAE_MAX_STAGES 6
+size_t ocrl_vae_ws_floats(int B, int obs_size, int obs_channels, int cnn_feat_size, int latent_dim, int use_cnn_feat, int full);
+int ocrl_vae_fwd(const float* obs, const float* const* w, const float* eps, float* rep, float* metrics, float* recon, int B, int obs_size,
+                 int obs_channels, int cnn_feat_size, int latent_dim, int use_cnn_feat, float kld_weight, int full, float* ws, size_t ws_floats,
+                 void* stream);
+int ocrl_vae_bwd(const float* obs, const float* eps, const float* const* w, const float* dloss, const float* drep, float* const* dw, int B,
+                 int obs_size, int obs_channels, int cnn_feat_size, int latent_dim, int use_cnn_feat, float kld_weight, int full, float* ws,
+                 size_t ws_floats, void* stream);
+
 /* ---- IODINE (ocrs/iodine/iodine_module.py:14-271, ocrs/iodine/iodine.py:4-14, ocrs/base.py:60-74): SURVEY.md §8 row a20 ----
  * Same conventions as the SLATE handle: flat fp32 parameter / gradient / Adam buffers in the reference's
  * _module.parameters() order and state_dict names, adopted from the caller; one workspace; all work on the caller's stream. */

@@ -133,6 +133,7 @@ struct NcFwdArgs {
     float* Y = nullptr; float* Y2 = nullptr; NcMap y;   // relu(conv + bias), cout channels per group; Y2 (optional) gets a second copy
     const float* w[OCRL_NATURECNN_MAX_GROUPS] = {}; const float* bias[OCRL_NATURECNN_MAX_GROUPS] = {};   // [cout, cin, ks, ks], [cout]
     int B = 0, G = 1, cin = 0, cout = 0, H = 0, W = 0, OH = 0, OW = 0, ks = 0, stride = 0;
+    int pad = 0;                                   // zero padding on every side (VAE decoder: 3 x 3, pad 1)
 };
 struct NcBwdArgs {
     const float* X = nullptr; NcMap x;             // layer input; also the ReLU mask of dX
@@ -142,6 +143,7 @@ struct NcBwdArgs {
     int slabs = 1, slab_rows = 0;                  // the B OH OW rows in slabs of slab_rows (a multiple of 4)
     const float* w[OCRL_NATURECNN_MAX_GROUPS] = {};
     int B = 0, G = 1, cin = 0, cout = 0, H = 0, W = 0, OH = 0, OW = 0, ks = 0, stride = 0;
+    int pad = 0;
     long long dw_tiles = 0, dx_tiles = 0; int dw_blocks = 0;   // set by nc_conv_bwd_launch
 };
 struct NcReduceLayer { const float* part = nullptr; int slabs = 0, G = 0, cout = 0, K = 0; long long n = 0; };
@@ -155,6 +157,17 @@ int nc_conv_fwd_launch(const NcFwdArgs& a, hipStream_t st);
 int nc_conv_bwd_launch(NcBwdArgs a, hipStream_t st);      // dW partials of the layer and, when a.dX, the masked data gradient: one launch
 int nc_dw_reduce_launch(const NcReduceArgs& a, hipStream_t st);
 int nc_relu_mask_launch(const float* d, const float* act, float* out, long long n, hipStream_t st);
+
+// ------------------------------------------------------------------ vae.hip (VAE module: include/ocrl_hip.h ocrl_vae_*)
+// pack = 1: dst (NHWC side) <- src (NCHW side); 0: the reverse.  rows = 1: the C HW index runs over rows of R columns, else columns
+int vae_permute_launch(const float* src, float* dst, long long R, int C, int HW, int rows, int pack, hipStream_t st);
+int vae_pad_rows_launch(const float* src, float* dst, int rows, int rows_pad, int K, hipStream_t st);
+int vae_kl_fwd_launch(const float* ml, const float* eps, float* latent, float* part, float* rep, int B, int L, hipStream_t st);
+int vae_loss_launch(const float* part, float* metrics, int B, float kld_weight, hipStream_t st);
+int vae_kl_bwd_launch(const float* ml, const float* eps, const float* dlat, const float* drep, const float* dloss, float* dml, int B, int L,
+                      float kld_weight, hipStream_t st);
+int vae_scale_launch(const float* x, float* y, const float* g, long long n, hipStream_t st);
+int vae_recon_nchw_launch(const float* r4, float* out, int B, int C, int HW, hipStream_t st);
 
 // ------------------------------------------------------------------ conv.hip
 struct ConvArgs {

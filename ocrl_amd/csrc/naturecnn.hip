@@ -18,6 +18,8 @@
 //                                          over the output positions that cover input pixel i (gather form; no atomics)
 //   nc_dw_reduce    dW[g][n, k] = sum_s P[s][g][n][k] in slab order (all layers of a backward in one launch)
 //   nc_relu_mask    d = dout * (act > 0)
+// The VAE (vae_unit.cpp) adds two forms: 2 x 2 stride 2 (its encoder) and 3 x 3 with zero padding 1 (its decoder below 32 x 32; the
+// padding taps read nothing, and dX gathers from oh = (ih + PAD - kh) / S).  PAD is a template parameter: the PAD = 0 forms are unchanged.
 // Every sum runs in an order fixed by the shapes alone: results are reproducible bit for bit.
 #include "common.h"
 #include "kernels.h"
@@ -39,7 +41,7 @@ __device__ __forceinline__ bool reduce4(f32x4& acc0, f32x4& acc1, int wave, int 
     return true;
 }
 
-template <int KS, int S>
+template <int KS, int S, int PAD>
 __global__ __launch_bounds__(256) void nc_conv_fwd_kernel(NcFwdArgs p) {
     constexpr int KK = KS * KS;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -60,10 +62,12 @@ __global__ __launch_bounds__(256) void nc_conv_fwd_kernel(NcFwdArgs p) {
     const long long m = m0 + i;
     const bool mok = m < M;
     const float* xb = p.X;
+    int ih0 = 0, iw0 = 0;                                              // top-left input pixel of the window (PAD > 0: may lie outside)
     if (mok) {
         const long long b = m / OHW;
         const int r = (int)(m - b * OHW), oh = r / p.OW, ow = r - oh * p.OW;
-        xb = p.X + map_off(p.x, b, g, 0, oh * S, ow * S);
+        if constexpr (PAD == 0) xb = p.X + map_off(p.x, b, g, 0, oh * S, ow * S);
+        else { xb = p.X + map_off(p.x, b, g, 0, 0, 0); ih0 = oh * S - PAD; iw0 = ow * S - PAD; }
     }
     const int na = n0 + i, nb = n0 + 16 + i;
     const bool naok = na < p.cout, nbok = nb < p.cout;
@@ -79,7 +83,13 @@ __global__ __launch_bounds__(256) void nc_conv_fwd_kernel(NcFwdArgs p) {
             const int k = k0 + 4 * u + kq;
             const bool kok = k < K;
             const int ci = k / KK, rr = k - ci * KK, kh = rr / KS, kw = rr - kh * KS;
-            a[u] = (mok && kok) ? xb[(long long)ci * p.x.sC + (long long)kh * p.x.sH + (long long)kw * p.x.sW] : 0.f;
+            if constexpr (PAD == 0) {
+                a[u] = (mok && kok) ? xb[(long long)ci * p.x.sC + (long long)kh * p.x.sH + (long long)kw * p.x.sW] : 0.f;
+            } else {                                                   // zero padding: taps outside the map read nothing
+                const int ih = ih0 + kh, iw = iw0 + kw;
+                a[u] = (mok && kok && ih >= 0 && ih < p.H && iw >= 0 && iw < p.W)
+                           ? xb[(long long)ci * p.x.sC + (long long)ih * p.x.sH + (long long)iw * p.x.sW] : 0.f;
+            }
             b0[u] = (naok && kok) ? wa[k] : 0.f;
             b1[u] = (nbok && kok) ? wb[k] : 0.f;
         }
@@ -115,7 +125,7 @@ __global__ __launch_bounds__(256) void nc_conv_fwd_kernel(NcFwdArgs p) {
 }
 
 // partial weight (and bias) gradient of one (slab, group, 16 output channels, 32 k columns) tile
-template <int KS, int S>
+template <int KS, int S, int PAD>
 __device__ __forceinline__ void nc_dw_tile(const NcBwdArgs& p, long long t, int lane) {
     constexpr int KK = KS * KS;
     const int i = lane & 15, kq = lane >> 4;
@@ -138,6 +148,9 @@ __device__ __forceinline__ void nc_dw_tile(const NcBwdArgs& p, long long t, int 
         return (long long)ci * p.x.sC + (long long)kh * p.x.sH + (long long)kw * p.x.sW;
     };
     const long long offa = ka < K ? koff(ka) : 0, offb = kb < K ? koff(kb) : 0;
+    // PAD > 0: the (kh, kw) tap of each B column, to test the input pixel against the map
+    const int kha = ka < K ? (ka % KK) / KS : 0, kwa = ka < K ? (ka % KK) % KS : 0;
+    const int khb = kb < K ? (kb % KK) / KS : 0, kwb = kb < K ? (kb % KK) % KS : 0;
     // the lane's reduction row m = mbeg + kq + 4 j, tracked as (b, oh, ow) and stepped by 4
     long long b = 0;
     int oh = 0, ow = 0;
@@ -153,9 +166,18 @@ __device__ __forceinline__ void nc_dw_tile(const NcBwdArgs& p, long long t, int 
         float a = 0.f, b0 = 0.f, b1 = 0.f;
         if (mok) {
             if (nok) a = p.dY[map_off(p.dy, b, g, n, oh, ow)];
-            const float* xb = p.X + map_off(p.x, b, g, 0, oh * S, ow * S);
-            b0 = ka < K ? xb[offa] : (ka == K ? 1.f : 0.f);
-            b1 = kb < K ? xb[offb] : (kb == K ? 1.f : 0.f);
+            if constexpr (PAD == 0) {
+                const float* xb = p.X + map_off(p.x, b, g, 0, oh * S, ow * S);
+                b0 = ka < K ? xb[offa] : (ka == K ? 1.f : 0.f);
+                b1 = kb < K ? xb[offb] : (kb == K ? 1.f : 0.f);
+            } else {
+                const int ih = oh * S - PAD, iw = ow * S - PAD;
+                const float* xb = p.X + map_off(p.x, b, g, 0, 0, 0) + (long long)ih * p.x.sH + (long long)iw * p.x.sW;
+                const bool ina = ih + kha >= 0 && ih + kha < p.H && iw + kwa >= 0 && iw + kwa < p.W;
+                const bool inb = ih + khb >= 0 && ih + khb < p.H && iw + kwb >= 0 && iw + kwb < p.W;
+                b0 = ka < K ? (ina ? xb[offa] : 0.f) : (ka == K ? 1.f : 0.f);
+                b1 = kb < K ? (inb ? xb[offb] : 0.f) : (kb == K ? 1.f : 0.f);
+            }
         }
         acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b0, acc0, 0, 0, 0);
         acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b1, acc1, 0, 0, 0);
@@ -177,7 +199,7 @@ __device__ __forceinline__ void nc_dw_tile(const NcBwdArgs& p, long long t, int 
 }
 
 // masked data gradient of one (group, 16 input pixels, 32 input channels) tile
-template <int KS, int S>
+template <int KS, int S, int PAD>
 __device__ __forceinline__ void nc_dx_tile(const NcBwdArgs& p, long long t, int wave, int lane) {
     constexpr int KK = KS * KS;
     const int i = lane & 15, kq = lane >> 4;
@@ -209,7 +231,7 @@ __device__ __forceinline__ void nc_dx_tile(const NcBwdArgs& p, long long t, int 
             const int k = k0 + 4 * u + kq;
             const bool kok = k < K;
             const int co = k / KK, rr = k - co * KK, kh = rr / KS, kw = rr - kh * KS;
-            const int ohn = ih - kh, own = iw - kw;
+            const int ohn = ih + PAD - kh, own = iw + PAD - kw;
             const int oh = ohn / S, ow = own / S;
             a[u] = 0.f;
             if (mok && kok && ohn >= 0 && own >= 0 && oh * S == ohn && ow * S == own && oh < p.OH && ow < p.OW)
@@ -242,14 +264,14 @@ __device__ __forceinline__ void nc_dx_tile(const NcBwdArgs& p, long long t, int 
     }
 }
 
-template <int KS, int S>
+template <int KS, int S, int PAD>
 __global__ __launch_bounds__(256) void nc_conv_bwd_kernel(NcBwdArgs p) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     if ((int)blockIdx.x < p.dw_blocks) {
         const long long t = (long long)blockIdx.x * 4 + wave;
-        if (t < p.dw_tiles) nc_dw_tile<KS, S>(p, t, lane);
+        if (t < p.dw_tiles) nc_dw_tile<KS, S, PAD>(p, t, lane);
     } else {
-        nc_dx_tile<KS, S>(p, (long long)(blockIdx.x - p.dw_blocks), wave, lane);   // one tile per workgroup
+        nc_dx_tile<KS, S, PAD>(p, (long long)(blockIdx.x - p.dw_blocks), wave, lane);   // one tile per workgroup
     }
 }
 
@@ -284,10 +306,12 @@ int nc_conv_fwd_launch(const NcFwdArgs& a, hipStream_t st) {
                  "nc_conv_fwd: bad shape");
     const long long tiles = (((long long)a.B * a.OH * a.OW + 15) / 16) * ((a.cout + 31) / 32) * a.G;
     const dim3 grid((unsigned)tiles), block(256);
-    if (a.ks == 8 && a.stride == 4) hipLaunchKernelGGL((nc_conv_fwd_kernel<8, 4>), grid, block, 0, st, a);
-    else if (a.ks == 4 && a.stride == 2) hipLaunchKernelGGL((nc_conv_fwd_kernel<4, 2>), grid, block, 0, st, a);
-    else if (a.ks == 3 && a.stride == 1) hipLaunchKernelGGL((nc_conv_fwd_kernel<3, 1>), grid, block, 0, st, a);
-    else OCRL_REQUIRE(false, "nc_conv_fwd: (kernel %d, stride %d) is not built", a.ks, a.stride);
+    if (a.ks == 8 && a.stride == 4 && a.pad == 0) hipLaunchKernelGGL((nc_conv_fwd_kernel<8, 4, 0>), grid, block, 0, st, a);
+    else if (a.ks == 4 && a.stride == 2 && a.pad == 0) hipLaunchKernelGGL((nc_conv_fwd_kernel<4, 2, 0>), grid, block, 0, st, a);
+    else if (a.ks == 3 && a.stride == 1 && a.pad == 0) hipLaunchKernelGGL((nc_conv_fwd_kernel<3, 1, 0>), grid, block, 0, st, a);
+    else if (a.ks == 2 && a.stride == 2 && a.pad == 0) hipLaunchKernelGGL((nc_conv_fwd_kernel<2, 2, 0>), grid, block, 0, st, a);   // VAE encoder
+    else if (a.ks == 3 && a.stride == 1 && a.pad == 1) hipLaunchKernelGGL((nc_conv_fwd_kernel<3, 1, 1>), grid, block, 0, st, a);   // VAE decoder, small maps
+    else OCRL_REQUIRE(false, "nc_conv_fwd: (kernel %d, stride %d, padding %d) is not built", a.ks, a.stride, a.pad);
     OCRL_CHECK_LAUNCH("nc_conv_fwd");
     return 0;
 }
@@ -300,10 +324,12 @@ int nc_conv_bwd_launch(NcBwdArgs a, hipStream_t st) {
     a.dw_blocks = cdiv(a.dw_tiles, 4);
     a.dx_tiles = a.dX ? (((long long)a.B * a.H * a.W + 15) / 16) * ((a.cin + 31) / 32) * a.G : 0;
     const dim3 grid((unsigned)(a.dw_blocks + a.dx_tiles)), block(256);
-    if (a.ks == 8 && a.stride == 4) hipLaunchKernelGGL((nc_conv_bwd_kernel<8, 4>), grid, block, 0, st, a);
-    else if (a.ks == 4 && a.stride == 2) hipLaunchKernelGGL((nc_conv_bwd_kernel<4, 2>), grid, block, 0, st, a);
-    else if (a.ks == 3 && a.stride == 1) hipLaunchKernelGGL((nc_conv_bwd_kernel<3, 1>), grid, block, 0, st, a);
-    else OCRL_REQUIRE(false, "nc_conv_bwd: (kernel %d, stride %d) is not built", a.ks, a.stride);
+    if (a.ks == 8 && a.stride == 4 && a.pad == 0) hipLaunchKernelGGL((nc_conv_bwd_kernel<8, 4, 0>), grid, block, 0, st, a);
+    else if (a.ks == 4 && a.stride == 2 && a.pad == 0) hipLaunchKernelGGL((nc_conv_bwd_kernel<4, 2, 0>), grid, block, 0, st, a);
+    else if (a.ks == 3 && a.stride == 1 && a.pad == 0) hipLaunchKernelGGL((nc_conv_bwd_kernel<3, 1, 0>), grid, block, 0, st, a);
+    else if (a.ks == 2 && a.stride == 2 && a.pad == 0) hipLaunchKernelGGL((nc_conv_bwd_kernel<2, 2, 0>), grid, block, 0, st, a);   // VAE encoder
+    else if (a.ks == 3 && a.stride == 1 && a.pad == 1) hipLaunchKernelGGL((nc_conv_bwd_kernel<3, 1, 1>), grid, block, 0, st, a);   // VAE decoder, small maps
+    else OCRL_REQUIRE(false, "nc_conv_bwd: (kernel %d, stride %d, padding %d) is not built", a.ks, a.stride, a.pad);
     OCRL_CHECK_LAUNCH("nc_conv_bwd");
     return 0;
 }

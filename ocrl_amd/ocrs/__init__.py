@@ -1,11 +1,12 @@
 """Drop-in for the reference's ``ocrs`` package on the SLATE / Slot-Attention / IODINE paths:
 ``getattr(ocrs, config.ocr.name)(config.ocr, config.dataset)`` (train_ocr.py:37) and
 ``getattr(ocrs, name + "_Module")`` (utils/tools.py:327-331) resolve here; so do the NatureCNN and MultipleCNN encoders of the RL
-baselines."""
+baselines and the VAE."""
 from .base import Base
 from .iodine import Iodine, Iodine_Module
 from .multiple_cnn import MultipleCNN, MultipleCNN_Module
 from .naturecnn import NatureCNN, NatureCNN_Module
 from .slate import SLATE, SLATE_Module
+from .vae import VAE, VAE_Module
 
-__all__ = ["Base", "SLATE", "SLATE_Module", "Iodine", "Iodine_Module", "NatureCNN", "NatureCNN_Module", "MultipleCNN", "MultipleCNN_Module"]
+__all__ = ["Base", "SLATE", "SLATE_Module", "Iodine", "Iodine_Module", "NatureCNN", "NatureCNN_Module", "MultipleCNN", "MultipleCNN_Module", "VAE", "VAE_Module"]

@@ -32,7 +32,8 @@ log = logging.getLogger("train_ocr")
 def load(model, run_dir, resume_checkpoint=None):
     """utils/tools.py:223-263: explicit checkpoint > <run>/checkpoints/model_latest.pth > fresh"""
     ckpt = None
-    dev = model._module.engine.device
+    engine = getattr(model._module, "engine", None)      # SLATE / IODINE keep their parameters in a library engine
+    dev = engine.device if engine is not None else next(model._module.parameters()).device
     if resume_checkpoint is not None:
         ckpt = torch.load(resume_checkpoint, map_location=dev, weights_only=True)
     elif (latest := Path(run_dir) / "checkpoints" / "model_latest.pth").exists():
