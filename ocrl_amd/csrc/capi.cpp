@@ -128,9 +128,8 @@ int ocrl_gemm(const float* A, const float* B, float* C, int M, int N, int K, int
     a.bias = bias; a.relu = relu; a.mask = mask; a.ldmask = ldmask; a.resid = resid; a.ldr = ldr;
     if (splitk > 1) {
         if (!ws || ldc != N) { ocrl_set_error("ocrl_gemm: split-k needs a workspace and ldc == N"); return 1; }
-        a.splitk = splitk; a.C = ws; a.sCsplit = (long long)M * N;
-        if (gemm_launch(a, ST(stream))) return 1;
-        return splitk_reduce_launch(ws, C, (long long)M * N, splitk, (long long)M * N, 0, ST(stream));
+        a.splitk = splitk;
+        return gemm_splitk_launch(a, ws, 0, 0, ST(stream));
     }
     return gemm_launch(a, ST(stream));
 }
@@ -150,14 +149,14 @@ size_t ocrl_gemm_desc_size(void) { return sizeof(ocrl_gemm_desc); }
 int ocrl_gemm_plan(const ocrl_gemm_desc* d, int out[6]) {
     if (!d || !out) { ocrl_set_error("ocrl_gemm_plan: null argument"); return 1; }
     GemmArgs a = gemm_args(*d);
-    if (a.splitk > 1) a.sCsplit = (long long)a.M * a.N;      // as ocrl_gemm_ex lays out its workspace
-    if (a.bias_out && a.splitk > 1 && a.sBias == 0) a.sBias = (a.M + 3) & ~3;
+    // the workspace as ocrl_gemm_ex lays it out; the plan reads no pointer, so C's address stands in for it
+    if (a.splitk > 1) gemm_splitk_layout(a, a.C, a.sBias ? a.sBias : (a.M + 3) & ~3);
     GemmPlan p;
     if (gemm_plan(a, &p)) return 1;
     out[0] = p.bm; out[1] = p.bn; out[2] = p.sb; out[3] = p.xf; out[4] = p.epi; out[5] = p.layout;
     return 0;
 }
-// split-k as SlateModel::lin_bwd_w runs it: raw partial slabs in ws, then one reduction into C (and one into bias_out)
+// split-k as the Linear weight gradients run it (gemm_splitk_launch): raw partial slabs in ws, then one reduction into C (and one into bias_out)
 int ocrl_gemm_ex(const ocrl_gemm_desc* d, float* ws, size_t ws_floats, void* stream) {
     if (!d) { ocrl_set_error("ocrl_gemm_ex: null descriptor"); return 1; }
     GemmArgs a = gemm_args(*d);
@@ -172,14 +171,7 @@ int ocrl_gemm_ex(const ocrl_gemm_desc* d, float* ws, size_t ws_floats, void* str
         ocrl_set_error("ocrl_gemm_ex: split-k partial products take no epilogue");
         return 1;
     }
-    float* C = a.C;
-    float* db = a.bias_out;
-    a.C = ws; a.sCsplit = slab;
-    if (db) { a.bias_out = ws + (size_t)a.splitk * slab; a.sBias = bslab; }
-    if (gemm_launch(a, ST(stream))) return 1;
-    if (splitk_reduce_launch(ws, C, slab, a.splitk, slab, 0, ST(stream))) return 1;
-    if (!db) return 0;
-    return splitk_reduce_launch(a.bias_out, db, a.M, a.splitk, bslab, 0, ST(stream));      // the dW form has M % 4 == 0
+    return gemm_splitk_launch(a, ws, bslab, 0, ST(stream));
 }
 int ocrl_conv2d_fwd(const float* x, const float* w, const float* bias, float* y, int B, int H, int W, int cin, int cin_pad, int ks, int relu,
                     float* ws, void* stream) {

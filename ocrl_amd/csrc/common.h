@@ -18,6 +18,13 @@ void ocrl_set_error(const char* fmt, ...);
         }                                               \
     } while (0)
 
+// propagates a non-zero status of an internal call (the message is already set)
+#define RC(x)                  \
+    do {                       \
+        int rc__ = (x);        \
+        if (rc__) return rc__; \
+    } while (0)
+
 #define OCRL_CHECK_LAUNCH(name)                                              \
     do {                                                                     \
         hipError_t e__ = hipGetLastError();                                  \
@@ -37,6 +44,12 @@ void ocrl_set_error(const char* fmt, ...);
     } while (0)
 
 static inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
+
+// carves a workspace into 256-byte aligned blocks: take(n) returns the float offset of the next n floats; `end` is the total
+struct WsTake {
+    size_t end = 0;
+    size_t operator()(size_t n) { const size_t r = end; end += (n + 63) & ~(size_t)63; return r; }
+};
 
 // ---- counter-based RNG: stateless, so forward and backward regenerate the same dropout decisions without storing masks.
 // 64 bits per call from two passes of a 32-bit avalanche mixer (two multiplies and three xor-shifts each; the "lowbias32" constants,

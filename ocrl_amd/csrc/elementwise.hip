@@ -955,7 +955,6 @@ __global__ void dropout_mask_kernel(float* __restrict__ y, long long n, float p,
 // Q [B,T,d] (projected, unscaled), Km/Vm [B,K,d], heads h, dh = d/h (<= 64).  One thread per (b,head,q).
 // P [B,h,T,K] = softmax (pre-dropout) is saved for the backward.
 // MAXK (8 or 16) is the compile-time slot capacity: per-slot values live in registers.
-#define RC_(x) do { int rc__ = (x); if (rc__) return rc__; } while (0)
 #define CA_MAXDH 64
 template <int CA_MAXK>
 __global__ __launch_bounds__(256) void cross_attn_fwd_kernel(const float* __restrict__ Q, const float* __restrict__ Km,

@@ -13,6 +13,8 @@
 // for both operands, so a k-contiguous operand is one ds_read_b128 per 32 rows per 8 k.
 // The kernel and its tile dispatch live in gemm_impl.h, compiled per operand-layout family (gemm_tt.hip: A [M,K] x B [N,K];
 // gemm_tn.hip: A [M,K] x B [K,N]; gemm_nn.hip: A [K,M]); this file checks the arguments, selects the kernel (gemm_plan) and owns the split-k reduction.
+// It also holds the Linear layers every model and unit runs on the GEMM (lin_fwd / lin_bwd_x / lin_bwd_w) and the one rule that splits
+// their weight gradients over the rows (lin_splitk_count).
 #include "common.h"
 #include "kernels.h"
 #include <stdlib.h>
@@ -174,4 +176,80 @@ int splitk_reduce_launch(const float* part, float* out, long long n, int splits,
     hipLaunchKernelGGL(splitk_reduce_kernel, dim3(cdiv(n4, 16)), dim3(256), 0, st, part, out, n4, splits, stride, accumulate);
     OCRL_CHECK_LAUNCH("splitk_reduce");
     return 0;
+}
+
+void gemm_splitk_layout(GemmArgs& a, float* ws, long long bslab) {
+    const long long slab = (long long)a.M * a.N;
+    a.C = ws; a.sCsplit = slab;
+    if (a.bias_out) { a.bias_out = ws + a.splitk * slab; a.sBias = bslab; }
+}
+
+int gemm_splitk_launch(GemmArgs a, float* ws, long long bslab, int accumulate, hipStream_t st) {
+    float* const C = a.C;
+    float* const db = a.bias_out;
+    gemm_splitk_layout(a, ws, bslab);
+    RC(gemm_launch(a, st));
+    RC(splitk_reduce_launch(ws, C, a.sCsplit, a.splitk, a.sCsplit, accumulate, st));
+    if (db) RC(splitk_reduce_launch(a.bias_out, db, a.M, a.splitk, bslab, 0, st));      // the dW form has M % 4 == 0
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------- Linear layers
+static void set_xf(GemmArgs& a, const Xf& xf) {
+    a.a_mode = xf.a_mode; a.b_mode = xf.b_mode; a.x_lse = xf.lse; a.x_tok = xf.tok; a.x_scale = xf.scale;
+}
+static void set_adrop(GemmArgs& a, const Drop& dr, int ld) {
+    if (dr.p > 0.f) { a.adrop_p = dr.p; a.adrop_site = dr.site; a.adrop_ld = ld; a.drop_seed = dr.seed; }
+}
+
+int lin_fwd(const float* x, int ldx, const float* W, const float* b, float* y, int ldy, long long M, int N, int K, int relu, const float* resid,
+            int ldr, hipStream_t st, Drop dr) {
+    GemmArgs a;
+    a.A = x; a.B = W; a.C = y; a.M = (int)M; a.N = N; a.K = K; a.lda = ldx; a.ldb = K; a.ldc = ldy; a.akc = 1; a.bkc = 1;
+    a.bias = b; a.relu = relu; a.resid = resid; a.ldr = ldr; a.drop_p = dr.p; a.drop_seed = dr.seed; a.drop_site = dr.site;
+    return gemm_launch(a, st);
+}
+
+int lin_bwd_x(const float* dy, int ld_dy, const float* W, float* dx, int ldx, long long M, int N_out, int K_in, const float* mask, int ldmask,
+              const float* resid, int ldr, hipStream_t st, Drop dr, Xf xf, float alpha) {
+    GemmArgs a;
+    a.A = dy; a.B = W; a.C = dx; a.M = (int)M; a.N = K_in; a.K = N_out; a.lda = ld_dy; a.ldb = K_in; a.ldc = ldx; a.akc = 1; a.bkc = 0;
+    a.alpha = alpha; a.mask = mask; a.ldmask = ldmask; a.resid = resid; a.ldr = ldr;
+    set_adrop(a, dr, N_out);
+    set_xf(a, xf);
+    return gemm_launch(a, st);
+}
+
+// Split count of the weight gradient `a` (the dW form: K = the rows): about 1024 workgroups over the output tiles gemm_plan cuts (measured
+// on MI355X: counting the 128x192 tile as three 64-wide ones left 340 workgroups on 256 CUs, 0.95 waves per SIMD), at least 256 rows per
+// split, at most max_splits (0: no limit), and no more splits than the scratch holds at one M*N slab plus one bias slab each (reserved
+// whether or not the bias gradient is fused, so the count does not depend on it).
+static int lin_splitk_count(const GemmArgs& a, size_t sk_floats, int max_splits, int* splits) {
+    GemmPlan p;
+    RC(gemm_plan(a, &p));
+    long long s = 1024 / ((long long)cdiv(a.M, p.bm) * cdiv(a.N, p.bn));
+    if (s > a.K / 256) s = a.K / 256;
+    if (max_splits > 0 && s > max_splits) s = max_splits;
+    const long long per = (long long)a.M * a.N + ((a.M + 3) & ~3);
+    if (s * per > (long long)sk_floats) s = (long long)sk_floats / per;
+    *splits = s > 1 ? (int)s : 1;
+    return 0;
+}
+
+int lin_bwd_w(const float* dy, int ld_dy, const float* x, int ldx, float* dW, float* db, long long M, int N_out, int K_in, float alpha, float* sk,
+              size_t sk_floats, hipStream_t st, Drop dr, Xf xf, int accumulate, int max_splits) {
+    OCRL_REQUIRE(!(db && accumulate), "lin_bwd_w: a fused bias gradient is written, not accumulated");
+    GemmArgs a;
+    a.A = dy; a.B = x; a.C = dW; a.M = N_out; a.N = K_in; a.K = (int)M; a.lda = ld_dy; a.ldb = ldx; a.ldc = K_in; a.akc = 0; a.bkc = 0;
+    a.alpha = alpha; a.bias_out = db;
+    set_adrop(a, dr, N_out);
+    set_xf(a, xf);
+    int splits;
+    RC(lin_splitk_count(a, sk_floats, max_splits, &splits));
+    if (splits > 1) {
+        a.splitk = splits;
+        return gemm_splitk_launch(a, sk, (N_out + 3) & ~3, accumulate, st);
+    }
+    if (accumulate) { a.resid = dW; a.ldr = K_in; }
+    return gemm_launch(a, st);
 }

@@ -9,12 +9,6 @@
 #include <stdarg.h>
 #include <stdlib.h>
 
-#define RC(x)                 \
-    do {                      \
-        int rc__ = (x);       \
-        if (rc__) return rc__; \
-    } while (0)
-
 static std::string ifmt(const char* f, ...) {
     char buf[128];
     va_list ap;
@@ -158,45 +152,6 @@ int IodineModel::tensor(const char* name, float** ptr, long long* count) const {
     return 0;
 }
 
-// y[M,N] = act(x[M,K] W[N,K]^T + b) + resid
-int IodineModel::gemm_nt(const float* x, int ldx, const float* W, int ldw, const float* b, float* y, int ldy, long long M, int Nn, int Kk, int act,
-                         const float* resid, int ldr, hipStream_t st) {
-    GemmArgs a;
-    a.A = x; a.B = W; a.C = y; a.M = (int)M; a.N = Nn; a.K = Kk; a.lda = ldx; a.ldb = ldw; a.ldc = ldy; a.akc = 1; a.bkc = 1;
-    a.bias = b; a.relu = act; a.resid = resid; a.ldr = ldr;
-    return gemm_launch(a, st);
-}
-// dx[M,N_in] = dy[M,K_out] W[K_out,N_in] + resid
-int IodineModel::gemm_nn(const float* dy, int ld_dy, const float* W, int ldw, float* dx, int ldx, long long M, int K_out, int N_in, const float* resid,
-                         int ldr, hipStream_t st) {
-    GemmArgs a;
-    a.A = dy; a.B = W; a.C = dx; a.M = (int)M; a.N = N_in; a.K = K_out; a.lda = ld_dy; a.ldb = ldw; a.ldc = ldx; a.akc = 1; a.bkc = 0;
-    a.resid = resid; a.ldr = ldr;
-    return gemm_launch(a, st);
-}
-// dW[N_out,K_in] (+)= dy[M,N_out]^T x[M,K_in];  db[N_out] (+)= column sums of dy
-int IodineModel::gemm_tn(const float* dy, int ld_dy, const float* x, int ldx, float* dW, float* db, long long M, int N_out, int K_in, int accumulate,
-                         hipStream_t st) {
-    GemmArgs a;
-    a.A = dy; a.B = x; a.C = dW; a.M = N_out; a.N = K_in; a.K = (int)M; a.lda = ld_dy; a.ldb = ldx; a.ldc = K_in; a.akc = 0; a.bkc = 0;
-    const int tiles = cdiv(N_out, 128) * cdiv(K_in, (K_in % 128 == 0) ? 128 : 64);
-    long long splits = 1024 / tiles;
-    if (splits > M / 256) splits = M / 256;
-    if (splits < 1) splits = 1;
-    const long long slab = (long long)N_out * K_in;
-    if (splits * slab > (long long)scratch_floats_) splits = (long long)scratch_floats_ / slab;
-    if (splits > 1) {
-        a.splitk = (int)splits; a.C = scratch_; a.sCsplit = slab;
-        RC(gemm_launch(a, st));
-        RC(splitk_reduce_launch(scratch_, dW, slab, (int)splits, slab, accumulate, st));
-    } else {
-        if (accumulate) { a.resid = dW; a.ldr = K_in; }
-        RC(gemm_launch(a, st));
-    }
-    if (db) RC(colsum_launch(dy, ld_dy, db, M, N_out, accumulate, 1.f, scratch_, scratch_floats_, st));
-    return 0;
-}
-
 int IodineModel::pack_weights(hipStream_t st) {
     RC(io_w1_pack_launch(P("decoder.mlc.layers.0.weight"), W1r_, Wxy_, L, st));
     RC(io_p1_launch(Wxy_, P("decoder.mlc.layers.0.bias"), P1_, S, st));
@@ -210,7 +165,7 @@ int IodineModel::pack_weights(hipStream_t st) {
 
 int IodineModel::decoder_fwd(int i, hipStream_t st) {
     const long long BK = (long long)B_ * K;
-    RC(gemm_nt(slots_[i], L, W1r_, L, nullptr, M_, 576, BK, 576, L, 0, nullptr, 0, st));          // M[bk][tap][co] = W_tap s
+    RC(lin_fwd(slots_[i], L, W1r_, nullptr, M_, 576, BK, 576, L, 0, nullptr, 0, st));          // M[bk][tap][co] = W_tap s
     RC(io_class_sum_launch(M_, T_, BK, 1, st));
     RC(io_layer1_launch(P1_, T_, c_[0][i], BK, S, st));
     for (int l = 0; l < 3; ++l) {
@@ -253,9 +208,9 @@ int IodineModel::decoder_bwd(int i, const float* dout4, bool weights, hipStream_
     // first layer through the broadcast shortcut (cur = d pre-activation of layer 0)
     RC(io_layer1_bwd_launch(cur, T_, BK, S, scratch_, scratch_floats_, st));
     RC(io_class_sum_launch(T_, M_, BK, 0, st));
-    RC(gemm_nn(M_, 576, W1r_, L, dslots_, L, BK, 576, L, nullptr, 0, st));
+    RC(lin_bwd_x(M_, 576, W1r_, dslots_, L, BK, 576, L, nullptr, 0, nullptr, 0, st));
     if (weights) {
-        RC(gemm_tn(M_, 576, slots_[i], L, dW1r_, nullptr, BK, 576, L, 1, st));
+        RC(lin_bwd_w(M_, 576, slots_[i], L, dW1r_, nullptr, BK, 576, L, 1.f, scratch_, scratch_floats_, st, Drop(), Xf(), 1));
         RC(colsum_launch(cur, (long long)N * 64, G1_, BK, N * 64, 1, 1.f, scratch_, scratch_floats_, st));
     }
     return 0;
@@ -267,20 +222,20 @@ int IodineModel::refine_fwd(int i, hipStream_t st) {
     for (int l = 0; l < 4; ++l) {
         const int C = l ? 64 : 17, so = rs_[l + 1];
         RC(io_im2col_launch(x, col_, BK, C, rs_[l], rs_[l], ldc_[l], st));
-        RC(gemm_nt(col_, ldc_[l], Wp_[l], ldc_[l], P(ifmt("refine.mlc.layers.%d.bias", l)), r_[l][i], 64, BK * so * so, 64, ldc_[l], 2, nullptr, 0, st));
+        RC(lin_fwd(col_, ldc_[l], Wp_[l], P(ifmt("refine.mlc.layers.%d.bias", l)), r_[l][i], 64, BK * so * so, 64, ldc_[l], 2, nullptr, 0, st));
         x = r_[l][i];
     }
     RC(io_pool_launch(r_[3][i], pool_[i], BK, rs_[4] * rs_[4], st));
-    RC(gemm_nt(pool_[i], 64, P("refine.mlp.layers.0.weight"), 64, P("refine.mlp.layers.0.bias"), mlpa_[i], Hm, BK, Hm, 64, 0, nullptr, 0, st));
+    RC(lin_fwd(pool_[i], 64, P("refine.mlp.layers.0.weight"), P("refine.mlp.layers.0.bias"), mlpa_[i], Hm, BK, Hm, 64, 0, nullptr, 0, st));
     RC(io_elu2_launch(mlpa_[i], Hm, xin_[i], XW, BK, Hm, nullptr, 0, st));
     const float* hp = i ? hst_[i - 1] : zero_state_;
     const float* cp = i ? cst_[i - 1] : zero_state_;
-    RC(gemm_nt(xin_[i], XW, P("refine.lstm.weight_ih"), XW, P("refine.lstm.bias_ih"), gates_, 4 * Hm, BK, 4 * Hm, XW, 0, nullptr, 0, st));
-    RC(gemm_nt(hp, Hm, P("refine.lstm.weight_hh"), Hm, P("refine.lstm.bias_hh"), gates_, 4 * Hm, BK, 4 * Hm, Hm, 0, gates_, 4 * Hm, st));
+    RC(lin_fwd(xin_[i], XW, P("refine.lstm.weight_ih"), P("refine.lstm.bias_ih"), gates_, 4 * Hm, BK, 4 * Hm, XW, 0, nullptr, 0, st));
+    RC(lin_fwd(hp, Hm, P("refine.lstm.weight_hh"), P("refine.lstm.bias_hh"), gates_, 4 * Hm, BK, 4 * Hm, Hm, 0, gates_, 4 * Hm, st));
     RC(io_lstm_fwd_launch(gates_, cp, acts_[i], cst_[i], hst_[i], BK, Hm, st));
     // the reference binds the LSTMCell outputs as (c, h): the update heads read the CELL state (iodine_module.py:418-422)
-    RC(gemm_nt(cst_[i], Hm, P("refine.mean_update.weight"), Hm, P("refine.mean_update.bias"), mu_[i + 1], L, BK, L, Hm, 0, mu_[i], L, st));
-    RC(gemm_nt(cst_[i], Hm, P("refine.logsig_update.weight"), Hm, P("refine.logsig_update.bias"), ls_[i + 1], L, BK, L, Hm, 0, ls_[i], L, st));
+    RC(lin_fwd(cst_[i], Hm, P("refine.mean_update.weight"), P("refine.mean_update.bias"), mu_[i + 1], L, BK, L, Hm, 0, mu_[i], L, st));
+    RC(lin_fwd(cst_[i], Hm, P("refine.logsig_update.weight"), P("refine.logsig_update.bias"), ls_[i + 1], L, BK, L, Hm, 0, ls_[i], L, st));
     return 0;
 }
 
@@ -291,13 +246,9 @@ int IodineModel::forward(const float* obs, int B, unsigned long long seed, const
     const long long BK = (long long)B * K;
     RC(pack_weights(st));
     RC(fill_launch(parts_, I * 4, 0.f, st));
-    // posterior initialisation: every (image, slot) row starts from the shared init vectors
-    {
-        GemmArgs a;      // rows of ones would be a GEMM; a strided copy is simpler: use pad_cols with ldi = 0 (broadcast row)
-        RC(pad_cols_launch(P("slot_mean_init"), 0, mu_[0], L, BK, L, L, st));
-        RC(pad_cols_launch(P("slot_logsig_init"), 0, ls_[0], L, BK, L, L, st));
-        (void)a;
-    }
+    // posterior initialisation: every (image, slot) row starts from the shared init vectors (pad_cols with ldi = 0 broadcasts a row)
+    RC(pad_cols_launch(P("slot_mean_init"), 0, mu_[0], L, BK, L, L, st));
+    RC(pad_cols_launch(P("slot_logsig_init"), 0, ls_[0], L, BK, L, L, st));
     for (int i = 0; i < I; ++i) {
         const bool last = i == I - 1;
         RC(io_sample_launch(mu_[i], ls_[i], noise ? noise + (size_t)i * BK * L : nullptr, eps_[i], slots_[i], parts_ + i * 4 + 2, BK * L, seed,
@@ -324,21 +275,26 @@ int IodineModel::refine_bwd(int i, hipStream_t st) {
     const long long BK = (long long)B_ * K;
     const bool top = i == I - 2;                  // the last refinement step has no successor: no carried state gradients
     // heads: mu[i+1] = mu[i] + c W_m^T + b_m (same for logsig)
-    RC(gemm_nn(gmu_, L, P("refine.mean_update.weight"), Hm, dcH_, Hm, BK, L, Hm, top ? nullptr : dc_, Hm, st));
-    RC(gemm_nn(gls_, L, P("refine.logsig_update.weight"), Hm, dcH_, Hm, BK, L, Hm, dcH_, Hm, st));
-    RC(gemm_tn(gmu_, L, cst_[i], Hm, G("refine.mean_update.weight"), G("refine.mean_update.bias"), BK, L, Hm, 1, st));
-    RC(gemm_tn(gls_, L, cst_[i], Hm, G("refine.logsig_update.weight"), G("refine.logsig_update.bias"), BK, L, Hm, 1, st));
+    RC(lin_bwd_x(gmu_, L, P("refine.mean_update.weight"), dcH_, Hm, BK, L, Hm, nullptr, 0, top ? nullptr : dc_, Hm, st));
+    RC(lin_bwd_x(gls_, L, P("refine.logsig_update.weight"), dcH_, Hm, BK, L, Hm, nullptr, 0, dcH_, Hm, st));
+    RC(lin_bwd_w(gmu_, L, cst_[i], Hm, G("refine.mean_update.weight"), nullptr, BK, L, Hm, 1.f, scratch_, scratch_floats_, st, Drop(), Xf(), 1));
+    RC(colsum_launch(gmu_, L, G("refine.mean_update.bias"), BK, L, 1, 1.f, scratch_, scratch_floats_, st));
+    RC(lin_bwd_w(gls_, L, cst_[i], Hm, G("refine.logsig_update.weight"), nullptr, BK, L, Hm, 1.f, scratch_, scratch_floats_, st, Drop(), Xf(), 1));
+    RC(colsum_launch(gls_, L, G("refine.logsig_update.bias"), BK, L, 1, 1.f, scratch_, scratch_floats_, st));
     const float* hp = i ? hst_[i - 1] : zero_state_;
     const float* cp = i ? cst_[i - 1] : zero_state_;
     RC(io_lstm_bwd_launch(acts_[i], cp, cst_[i], top ? nullptr : dh_, dcH_, dgates_, dc_, BK, Hm, st));     // dc_ = gradient wrt c_{i-1}
-    RC(gemm_nn(dgates_, 4 * Hm, P("refine.lstm.weight_ih"), XW, dxin_, XW, BK, 4 * Hm, XW, nullptr, 0, st));
-    RC(gemm_nn(dgates_, 4 * Hm, P("refine.lstm.weight_hh"), Hm, dh_, Hm, BK, 4 * Hm, Hm, nullptr, 0, st));  // dh_ = gradient wrt h_{i-1}
-    RC(gemm_tn(dgates_, 4 * Hm, xin_[i], XW, G("refine.lstm.weight_ih"), G("refine.lstm.bias_ih"), BK, 4 * Hm, XW, 1, st));
-    RC(gemm_tn(dgates_, 4 * Hm, hp, Hm, G("refine.lstm.weight_hh"), G("refine.lstm.bias_hh"), BK, 4 * Hm, Hm, 1, st));
+    RC(lin_bwd_x(dgates_, 4 * Hm, P("refine.lstm.weight_ih"), dxin_, XW, BK, 4 * Hm, XW, nullptr, 0, nullptr, 0, st));
+    RC(lin_bwd_x(dgates_, 4 * Hm, P("refine.lstm.weight_hh"), dh_, Hm, BK, 4 * Hm, Hm, nullptr, 0, nullptr, 0, st));  // dh_ = gradient wrt h_{i-1}
+    RC(lin_bwd_w(dgates_, 4 * Hm, xin_[i], XW, G("refine.lstm.weight_ih"), nullptr, BK, 4 * Hm, XW, 1.f, scratch_, scratch_floats_, st, Drop(), Xf(), 1));
+    RC(colsum_launch(dgates_, 4 * Hm, G("refine.lstm.bias_ih"), BK, 4 * Hm, 1, 1.f, scratch_, scratch_floats_, st));
+    RC(lin_bwd_w(dgates_, 4 * Hm, hp, Hm, G("refine.lstm.weight_hh"), nullptr, BK, 4 * Hm, Hm, 1.f, scratch_, scratch_floats_, st, Drop(), Xf(), 1));
+    RC(colsum_launch(dgates_, 4 * Hm, G("refine.lstm.bias_hh"), BK, 4 * Hm, 1, 1.f, scratch_, scratch_floats_, st));
     // MLP with the double ELU
     RC(io_elu2_launch(mlpa_[i], Hm, da_, Hm, BK, Hm, dxin_, XW, st));
-    RC(gemm_nn(da_, Hm, P("refine.mlp.layers.0.weight"), 64, dpool_, 64, BK, Hm, 64, nullptr, 0, st));
-    RC(gemm_tn(da_, Hm, pool_[i], 64, G("refine.mlp.layers.0.weight"), G("refine.mlp.layers.0.bias"), BK, Hm, 64, 1, st));
+    RC(lin_bwd_x(da_, Hm, P("refine.mlp.layers.0.weight"), dpool_, 64, BK, Hm, 64, nullptr, 0, nullptr, 0, st));
+    RC(lin_bwd_w(da_, Hm, pool_[i], 64, G("refine.mlp.layers.0.weight"), nullptr, BK, Hm, 64, 1.f, scratch_, scratch_floats_, st, Drop(), Xf(), 1));
+    RC(colsum_launch(da_, Hm, G("refine.mlp.layers.0.bias"), BK, Hm, 1, 1.f, scratch_, scratch_floats_, st));
     // stride-2 convolutions, last to first
     float* dpre = dr_[0];
     float* other = dr_[1];
@@ -348,8 +304,9 @@ int IodineModel::refine_bwd(int i, hipStream_t st) {
         const long long rows = BK * so * so;
         const float* x = l ? r_[l - 1][i] : enc_[i];
         RC(io_im2col_launch(x, col_, BK, C, rs_[l], rs_[l], ldc_[l], st));
-        RC(gemm_tn(dpre, 64, col_, ldc_[l], dWp_[l], G(ifmt("refine.mlc.layers.%d.bias", l)), rows, 64, ldc_[l], 1, st));
-        RC(gemm_nn(dpre, 64, Wp_[l], ldc_[l], dcol_, ldc_[l], rows, 64, ldc_[l], nullptr, 0, st));
+        RC(lin_bwd_w(dpre, 64, col_, ldc_[l], dWp_[l], nullptr, rows, 64, ldc_[l], 1.f, scratch_, scratch_floats_, st, Drop(), Xf(), 1));
+        RC(colsum_launch(dpre, 64, G(ifmt("refine.mlc.layers.%d.bias", l)), rows, 64, 1, 1.f, scratch_, scratch_floats_, st));
+        RC(lin_bwd_x(dpre, 64, Wp_[l], dcol_, ldc_[l], rows, 64, ldc_[l], nullptr, 0, nullptr, 0, st));
         if (l) {
             RC(io_col2im_launch(dcol_, r_[l - 1][i], other, BK, 64, rs_[l], rs_[l], ldc_[l], st));
             float* t = dpre; dpre = other; other = t;

@@ -38,12 +38,6 @@ private:
     float* carve(const char* name, size_t n);
     void layout_workspace(bool commit);
     int pack_weights(hipStream_t st);
-    int gemm_nt(const float* x, int ldx, const float* W, int ldw, const float* b, float* y, int ldy, long long M, int N, int K, int act,
-                const float* resid, int ldr, hipStream_t st);
-    int gemm_nn(const float* dy, int ld_dy, const float* W, int ldw, float* dx, int ldx, long long M, int K_out, int N_in, const float* resid, int ldr,
-                hipStream_t st);
-    int gemm_tn(const float* dy, int ld_dy, const float* x, int ldx, float* dW, float* db, long long M, int N_out, int K_in, int accumulate,
-                hipStream_t st);
     int decoder_fwd(int i, hipStream_t st);
     int decoder_bwd(int i, const float* dout4, bool weights, hipStream_t st);      // -> dslots_
     int refine_fwd(int i, hipStream_t st);

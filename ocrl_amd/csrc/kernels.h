@@ -71,6 +71,28 @@ int gemm_plan(const GemmArgs& a, GemmPlan* plan);
 int gemm_launch(const GemmArgs& a, hipStream_t st);
 int splitk_reduce_launch(const float* part, float* out, long long n, int splits, long long stride,
                          int accumulate, hipStream_t st);
+// split-k workspace: a.splitk slabs of the raw C [M,N] partials from ws, then (with a fused bias gradient) a.splitk slabs of the bias
+// partials at stride bslab: points C / bias_out into ws
+void gemm_splitk_layout(GemmArgs& a, float* ws, long long bslab);
+// runs a.splitk partial products into that layout, then reduces the slabs into C (added to it when `accumulate`) and the bias partials
+// into bias_out.  C must be compact (ldc == N).
+int gemm_splitk_launch(GemmArgs a, float* ws, long long bslab, int accumulate, hipStream_t st);
+
+// ---- Linear layers on the GEMM (every model and unit): forward NT, input gradient NN, weight gradient TN split over the rows
+// dropout at (seed, site) with probability p: forward on the output, backward on dy as the product stages it
+struct Drop { float p = 0.f; unsigned long long seed = 0; unsigned site = 0; };
+// soft-max operand transform of a product (GemmArgs::a_mode / b_mode): the operand is rebuilt from stored scores + per-row log-sum-exp
+struct Xf { int a_mode = 0, b_mode = 0; const float* lse = nullptr; const int* tok = nullptr; float scale = 1.f; };
+// y[M,N] = drop(act(x[M,K] W[N,K]^T + b)) + resid          (act: GemmArgs::relu)
+int lin_fwd(const float* x, int ldx, const float* W, const float* b, float* y, int ldy, long long M, int N, int K, int relu, const float* resid,
+            int ldr, hipStream_t st, Drop dr = Drop());
+// dx[M,K_in] = alpha * (drop(dy)[M,N_out] W[N_out,K_in]) * (mask > 0) + resid
+int lin_bwd_x(const float* dy, int ld_dy, const float* W, float* dx, int ldx, long long M, int N_out, int K_in, const float* mask, int ldmask,
+              const float* resid, int ldr, hipStream_t st, Drop dr = Drop(), Xf xf = Xf(), float alpha = 1.f);
+// dW[N_out,K_in] = alpha * drop(dy)^T x (added to dW when `accumulate`);  db[N_out] = column sums of drop(dy), fused into the product
+// (nullptr: none).  Split over the M rows through the scratch (sk, sk_floats) as lin_splitk_count in gemm.hip decides; sk_floats = 0 never splits.
+int lin_bwd_w(const float* dy, int ld_dy, const float* x, int ldx, float* dW, float* db, long long M, int N_out, int K_in, float alpha, float* sk,
+              size_t sk_floats, hipStream_t st, Drop dr = Drop(), Xf xf = Xf(), int accumulate = 0, int max_splits = 0);
 
 // ------------------------------------------------------------------ pool.hip
 int pool_embed_launch(const float* lin, const float* cls, const float* pos, float* x0, int B, int K, int d, hipStream_t st);
@@ -107,17 +129,6 @@ int pool_cls_attn_bwd_launch(const PoolClsArgs& a, hipStream_t st);
 // non-causal multi-head attention over all rows: forward O, lse [B*h][S]; backward dqkv from dO (Dd: [B*h][S] scratch)
 int pool_flash_launch(const float* qkv, float* O, float* lse, const float* dO, float* Dd, float* dqkv, int B, int S, int d, int h, float p,
                       unsigned long long seed, unsigned site, int backward, hipStream_t st);
-
-// ------------------------------------------------------------------ pool_unit.cpp: Linear layers of the pooling heads on the GEMM
-// y = epilogue(x W^T + b): relu, dropout at `site`, + resid
-int lin_fwd(const float* x, const float* W, const float* b, float* y, long long M, int N, int Kk, int relu, const float* resid, float p, unsigned long long seed,
-            unsigned site, hipStream_t st);
-// dx = alpha * (drop(dy) W) * (mask > 0) + resid
-int lin_bwd_x(const float* dy, const float* W, float* dx, long long M, int N_out, int K_in, float alpha, const float* mask, const float* resid, float p,
-              unsigned long long seed, unsigned site, hipStream_t st);
-// dW = drop(dy)^T x, db = column sums of drop(dy); split over the M rows through `sk` when there are enough of them
-int lin_bwd_w(const float* dy, const float* x, float* dW, float* db, long long M, int N_out, int K_in, float p, unsigned long long seed, unsigned site,
-              float* sk, size_t sk_floats, hipStream_t st);
 
 // ------------------------------------------------------------------ rn.hip (Relation Network pooling: include/ocrl_hip.h ocrl_pool_rn_*)
 int rn_pair_fwd_launch(const float* AB, const float* b1, float* h1, int B, int K, int g, hipStream_t st);

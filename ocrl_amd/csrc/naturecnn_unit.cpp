@@ -10,12 +10,6 @@
 #include "../../include/ocrl_hip.h"
 #include "kernels.h"
 
-#define RC(x)                 \
-    do {                      \
-        int rc__ = (x);       \
-        if (rc__) return rc__; \
-    } while (0)
-
 namespace {
 struct NcLay {
     int L = 0, G = 1, np = 0, nflat = 0;
@@ -42,8 +36,7 @@ int check_nc(int B, int H, int W, int cin, int G, int feat, int use_feat, int re
 
 NcLay nc_layout(int B, int H, int W, int cin, int G, int feat, int use_feat, int rep) {
     NcLay y;
-    size_t a = 0;
-    auto take = [&](size_t n) { size_t r = a; a += (n + 63) & ~(size_t)63; return r; };
+    WsTake take;
     static const int KS[4] = {8, 4, 3, 3}, ST[4] = {4, 2, 1, 1}, CO[4] = {32, 64, 64, 128};
     y.L = feat == 2 ? 4 : 3;
     y.G = G;
@@ -75,7 +68,7 @@ NcLay nc_layout(int B, int H, int W, int cin, int G, int feat, int use_feat, int
     }
     y.nflat = y.cout[y.L - 1] * y.OH[y.L - 1] * y.OW[y.L - 1];
     if (!use_feat) { y.lin = take((size_t)B * G * rep); y.dz = take((size_t)B * G * rep); }
-    y.total = a;
+    y.total = take.end;
     return y;
 }
 }  // namespace
@@ -110,13 +103,9 @@ int ocrl_naturecnn_fwd(const float* obs, const float* const* w, float* out, int 
     if (use_cnn_feat) return 0;
     // module g's Linear: relu(flat_g W_g^T + b_g) -> column block g of [B, G, rep_dim]
     float* lo = save ? ws + y.lin : out;
-    for (int g = 0; g < G; ++g) {
-        GemmArgs a;
-        a.A = ws + y.act[L - 1] + (size_t)g * B * y.nflat; a.B = w[g * y.np + 2 * L]; a.C = lo + (size_t)g * rep_dim;
-        a.M = B; a.N = rep_dim; a.K = y.nflat; a.lda = y.nflat; a.ldb = y.nflat; a.ldc = G * rep_dim; a.akc = 1; a.bkc = 1;
-        a.bias = w[g * y.np + 2 * L + 1]; a.relu = 1;
-        RC(gemm_launch(a, st));
-    }
+    for (int g = 0; g < G; ++g)
+        RC(lin_fwd(ws + y.act[L - 1] + (size_t)g * B * y.nflat, y.nflat, w[g * y.np + 2 * L], w[g * y.np + 2 * L + 1], lo + (size_t)g * rep_dim,
+                   G * rep_dim, B, rep_dim, y.nflat, 1, nullptr, 0, st));
     if (save) RC(copy_launch(lo, out, (long long)B * G * rep_dim, st));
     return 0;
 }
@@ -136,16 +125,11 @@ int ocrl_naturecnn_bwd(const float* obs, const float* dout, const float* const* 
         RC(nc_relu_mask_launch(dout, ws + y.lin, ws + y.dz, (long long)B * G * rep_dim, st));
         for (int g = 0; g < G; ++g) {
             const size_t xo = (size_t)g * B * y.nflat;
-            GemmArgs a;                                  // dW_g = dz_g^T flat_g, db_g = column sums of dz_g
-            a.A = ws + y.dz + (size_t)g * rep_dim; a.B = ws + y.act[last] + xo; a.C = dw[g * y.np + 2 * L];
-            a.M = rep_dim; a.N = y.nflat; a.K = B; a.lda = G * rep_dim; a.ldb = y.nflat; a.ldc = y.nflat; a.akc = 0; a.bkc = 0;
-            a.bias_out = dw[g * y.np + 2 * L + 1];
-            RC(gemm_launch(a, st));
-            GemmArgs d;                                  // d flat_g = (dz_g W_g) * (flat_g > 0)
-            d.A = ws + y.dz + (size_t)g * rep_dim; d.B = w[g * y.np + 2 * L]; d.C = ws + y.dact[last] + xo;
-            d.M = B; d.N = y.nflat; d.K = rep_dim; d.lda = G * rep_dim; d.ldb = y.nflat; d.ldc = y.nflat; d.akc = 1; d.bkc = 0;
-            d.mask = ws + y.act[last] + xo; d.ldmask = y.nflat;
-            RC(gemm_launch(d, st));
+            const float* dz = ws + y.dz + (size_t)g * rep_dim;
+            const float* flat = ws + y.act[last] + xo;
+            // dW_g = dz_g^T flat_g, db_g = column sums of dz_g (B rows: no split-k scratch); d flat_g = (dz_g W_g) * (flat_g > 0)
+            RC(lin_bwd_w(dz, G * rep_dim, flat, y.nflat, dw[g * y.np + 2 * L], dw[g * y.np + 2 * L + 1], B, rep_dim, y.nflat, 1.f, nullptr, 0, st));
+            RC(lin_bwd_x(dz, G * rep_dim, w[g * y.np + 2 * L], ws + y.dact[last] + xo, y.nflat, B, rep_dim, y.nflat, flat, y.nflat, nullptr, 0, st));
         }
     }
     NcReduceArgs r;

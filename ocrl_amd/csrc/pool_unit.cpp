@@ -7,12 +7,6 @@
 #include "../../include/ocrl_hip.h"
 #include "kernels.h"
 
-#define RC(x)                 \
-    do {                      \
-        int rc__ = (x);       \
-        if (rc__) return rc__; \
-    } while (0)
-
 namespace {
 constexpr unsigned SITE_POOL = 300;      // + 8 * layer + {0: attention weights, 1: dropout1, 2: FFN hidden, 3: dropout2}
 constexpr size_t TMP_FLOATS = (size_t)1 << 17;
@@ -27,8 +21,7 @@ struct Lay {
 };
 Lay layout(int B, int K, int Din, int d, int h, int ff, int L) {
     Lay y;
-    size_t a = 0;
-    auto take = [&](size_t n) { size_t r = a; a += (n + 63) & ~(size_t)63; return r; };
+    WsTake take;
     const size_t S = K + 1, R = (size_t)B * S;
     y.lin = take((size_t)B * K * d);
     for (int l = 0; l < L; ++l) {
@@ -48,53 +41,10 @@ Lay layout(int B, int K, int Din, int d, int h, int ff, int L) {
     if (splits > 32) splits = 32;
     y.sk_floats = splits > 1 ? splits * (slab + (size_t)ff + 3 * (size_t)d + 8) : 0;
     y.sk = take(y.sk_floats);
-    y.total = a;
+    y.total = take.end;
     return y;
 }
-}  // namespace
 
-// the Linear helpers are shared with the Relation Network head (rn_unit.cpp; declared in kernels.h)
-// y = epilogue(x W^T + b): relu, dropout at `site`, + resid
-int lin_fwd(const float* x, const float* W, const float* b, float* y, long long M, int N, int Kk, int relu, const float* resid, float p, unsigned long long seed,
-            unsigned site, hipStream_t st) {
-    GemmArgs a;
-    a.A = x; a.B = W; a.C = y; a.M = (int)M; a.N = N; a.K = Kk; a.lda = Kk; a.ldb = Kk; a.ldc = N; a.akc = 1; a.bkc = 1;
-    a.bias = b; a.relu = relu; a.resid = resid; a.ldr = N; a.drop_p = p; a.drop_seed = seed; a.drop_site = site;
-    return gemm_launch(a, st);
-}
-// dx = alpha * (drop(dy) W) * (mask > 0) + resid
-int lin_bwd_x(const float* dy, const float* W, float* dx, long long M, int N_out, int K_in, float alpha, const float* mask, const float* resid, float p,
-              unsigned long long seed, unsigned site, hipStream_t st) {
-    GemmArgs a;
-    a.A = dy; a.B = W; a.C = dx; a.M = (int)M; a.N = K_in; a.K = N_out; a.lda = N_out; a.ldb = K_in; a.ldc = K_in; a.akc = 1; a.bkc = 0;
-    a.alpha = alpha; a.mask = mask; a.ldmask = K_in; a.resid = resid; a.ldr = K_in;
-    if (p > 0.f) { a.adrop_p = p; a.adrop_site = site; a.adrop_ld = N_out; a.drop_seed = seed; }
-    return gemm_launch(a, st);
-}
-// dW = drop(dy)^T x, db = column sums of drop(dy); split over the M rows through `sk` when there are enough of them
-int lin_bwd_w(const float* dy, const float* x, float* dW, float* db, long long M, int N_out, int K_in, float p, unsigned long long seed, unsigned site,
-              float* sk, size_t sk_floats, hipStream_t st) {
-    GemmArgs a;
-    a.A = dy; a.B = x; a.C = dW; a.M = N_out; a.N = K_in; a.K = (int)M; a.lda = N_out; a.ldb = K_in; a.ldc = K_in; a.akc = 0; a.bkc = 0;
-    if (p > 0.f) { a.adrop_p = p; a.adrop_site = site; a.adrop_ld = N_out; a.drop_seed = seed; }
-    const long long slab = (long long)N_out * K_in, bslab = (N_out + 3) & ~3;
-    const int tiles = cdiv(N_out, 128) * cdiv(K_in, (K_in % 128 == 0) ? 128 : 64);
-    long long splits = 1024 / tiles;
-    if (splits > M / 256) splits = M / 256;
-    if (splits * (slab + bslab) > (long long)sk_floats) splits = (long long)sk_floats / (slab + bslab);
-    if (splits > 1 && N_out % 4 == 0) {
-        a.splitk = (int)splits; a.C = sk; a.sCsplit = slab;
-        float* bpart = sk + splits * slab;
-        a.bias_out = bpart; a.sBias = bslab;
-        RC(gemm_launch(a, st));
-        RC(splitk_reduce_launch(sk, dW, slab, (int)splits, slab, 0, st));
-        return splitk_reduce_launch(bpart, db, N_out, (int)splits, bslab, 0, st);
-    }
-    a.bias_out = db;
-    return gemm_launch(a, st);
-}
-
-namespace {
 int check_dims(int B, int K, int Din, int d, int h, int ff, int L) {
     OCRL_REQUIRE(B > 0 && K >= 1 && K + 1 <= 32, "pool_transformer: 1 <= num_slots <= 31 (got %d)", K);
     OCRL_REQUIRE(L >= 1 && L <= OCRL_POOL_MAX_LAYERS, "pool_transformer: 1 <= num_layers <= %d (got %d)", OCRL_POOL_MAX_LAYERS, L);
@@ -120,19 +70,19 @@ int ocrl_pool_transformer_fwd(const float* slots, const float* const* w, const f
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int S = K + 1;
     const long long R = (long long)B * S;
-    RC(lin_fwd(slots, w[0], w[1], ws + y.lin, (long long)B * K, d, Din, 0, nullptr, 0.f, 0, 0, st));
+    RC(lin_fwd(slots, Din, w[0], w[1], ws + y.lin, d, (long long)B * K, d, Din, 0, nullptr, 0, st));
     RC(pool_embed_launch(ws + y.lin, w[2], pos, ws + y.l[0].x, B, K, d, st));
     for (int l = 0; l < L; ++l) {
         const float* const* q = w + 3 + 12 * l;
         const LayerLay& a = y.l[l];
         const unsigned site = SITE_POOL + 8 * l;
         float* xn = ws + (l + 1 < L ? y.l[l + 1].x : y.xlast);
-        RC(lin_fwd(ws + a.x, q[0], q[1], ws + a.qkv, R, 3 * d, d, 0, nullptr, 0.f, 0, 0, st));
+        RC(lin_fwd(ws + a.x, d, q[0], q[1], ws + a.qkv, 3 * d, R, 3 * d, d, 0, nullptr, 0, st));
         RC(pool_attn_launch(ws + a.qkv, ws + a.P, ws + a.o, nullptr, nullptr, B, S, d, nhead, drop_p, seed, site + 0, 0, st));
-        RC(lin_fwd(ws + a.o, q[2], q[3], ws + a.y1, R, d, d, 0, ws + a.x, drop_p, seed, site + 1, st));                 // x + dropout1(attn)
+        RC(lin_fwd(ws + a.o, d, q[2], q[3], ws + a.y1, d, R, d, d, 0, ws + a.x, d, st, Drop{drop_p, seed, site + 1}));                 // x + dropout1(attn)
         RC(layernorm_fwd_launch(ws + a.y1, q[8], q[9], ws + a.x1, ws + a.mr1, ws + a.mr1 + R, R, d, st));
-        RC(lin_fwd(ws + a.x1, q[4], q[5], ws + a.hdn, R, ff, d, 1, nullptr, drop_p, seed, site + 2, st));              // dropout(relu(linear1))
-        RC(lin_fwd(ws + a.hdn, q[6], q[7], ws + a.y2, R, d, ff, 0, ws + a.x1, drop_p, seed, site + 3, st));             // x1 + dropout2(linear2)
+        RC(lin_fwd(ws + a.x1, d, q[4], q[5], ws + a.hdn, ff, R, ff, d, 1, nullptr, 0, st, Drop{drop_p, seed, site + 2}));              // dropout(relu(linear1))
+        RC(lin_fwd(ws + a.hdn, ff, q[6], q[7], ws + a.y2, d, R, d, ff, 0, ws + a.x1, d, st, Drop{drop_p, seed, site + 3}));             // x1 + dropout2(linear2)
         RC(layernorm_fwd_launch(ws + a.y2, q[10], q[11], xn, ws + a.mr2, ws + a.mr2 + R, R, d, st));
     }
     RC(pool_rows_launch(ws + y.xlast, out, B, K, d, 2, st));
@@ -160,25 +110,25 @@ int ocrl_pool_transformer_bwd(const float* slots, const float* dout, const float
         RC(layernorm_bwd_launch(g2, ws + a.y2, ws + a.mr2, ws + a.mr2 + R, q[10], gA, dgb, R, d, 0, 0, tmp, TMP_FLOATS, st));
         RC(copy_launch(dgb, g[10], d, st)); RC(copy_launch(dgb + d, g[11], d, st));
         // y2 = x1 + dropout2(hdn W2^T + b2),  hdn = dropout(relu(x1 W1^T + b1))
-        RC(lin_bwd_w(gA, ws + a.hdn, g[6], g[7], R, d, ff, drop_p, seed, site + 3, ws + y.sk, y.sk_floats, st));
-        RC(lin_bwd_x(gA, q[6], ws + y.dhdn, R, d, ff, inv_keep, ws + a.hdn, nullptr, drop_p, seed, site + 3, st));
-        RC(lin_bwd_w(ws + y.dhdn, ws + a.x1, g[4], g[5], R, ff, d, 0.f, 0, 0, ws + y.sk, y.sk_floats, st));
-        RC(lin_bwd_x(ws + y.dhdn, q[4], gB, R, ff, d, 1.f, nullptr, gA, 0.f, 0, 0, st));                    // + residual
+        RC(lin_bwd_w(gA, d, ws + a.hdn, ff, g[6], g[7], R, d, ff, 1.f, ws + y.sk, y.sk_floats, st, Drop{drop_p, seed, site + 3}));
+        RC(lin_bwd_x(gA, d, q[6], ws + y.dhdn, ff, R, d, ff, ws + a.hdn, ff, nullptr, 0, st, Drop{drop_p, seed, site + 3}, Xf(), inv_keep));
+        RC(lin_bwd_w(ws + y.dhdn, ff, ws + a.x1, d, g[4], g[5], R, ff, d, 1.f, ws + y.sk, y.sk_floats, st));
+        RC(lin_bwd_x(ws + y.dhdn, ff, q[4], gB, d, R, ff, d, nullptr, 0, gA, d, st));                    // + residual
         // x1 = LN1(y1)
         RC(layernorm_bwd_launch(gB, ws + a.y1, ws + a.mr1, ws + a.mr1 + R, q[8], gA, dgb, R, d, 0, 0, tmp, TMP_FLOATS, st));
         RC(copy_launch(dgb, g[8], d, st)); RC(copy_launch(dgb + d, g[9], d, st));
         // y1 = x + dropout1(o Wo^T + bo)
-        RC(lin_bwd_w(gA, ws + a.o, g[2], g[3], R, d, d, drop_p, seed, site + 1, ws + y.sk, y.sk_floats, st));
-        RC(lin_bwd_x(gA, q[2], gB, R, d, d, 1.f, nullptr, nullptr, drop_p, seed, site + 1, st));
+        RC(lin_bwd_w(gA, d, ws + a.o, d, g[2], g[3], R, d, d, 1.f, ws + y.sk, y.sk_floats, st, Drop{drop_p, seed, site + 1}));
+        RC(lin_bwd_x(gA, d, q[2], gB, d, R, d, d, nullptr, 0, nullptr, 0, st, Drop{drop_p, seed, site + 1}));
         RC(pool_attn_launch(ws + a.qkv, ws + a.P, nullptr, gB, ws + y.dqkv, B, S, d, nhead, drop_p, seed, site + 0, 1, st));
-        RC(lin_bwd_w(ws + y.dqkv, ws + a.x, g[0], g[1], R, 3 * d, d, 0.f, 0, 0, ws + y.sk, y.sk_floats, st));
-        RC(lin_bwd_x(ws + y.dqkv, q[0], g2, R, 3 * d, d, 1.f, nullptr, gA, 0.f, 0, 0, st));                  // + residual
+        RC(lin_bwd_w(ws + y.dqkv, 3 * d, ws + a.x, d, g[0], g[1], R, 3 * d, d, 1.f, ws + y.sk, y.sk_floats, st));
+        RC(lin_bwd_x(ws + y.dqkv, 3 * d, q[0], g2, d, R, 3 * d, d, nullptr, 0, gA, d, st));                  // + residual
     }
     // x0 = [cls; Linear(slots)] (+pos)
     RC(colsum_launch(g2, (long long)S * d, dw[2], B, d, 0, 1.f, tmp, TMP_FLOATS, st));
     RC(pool_rows_launch(g2, ws + y.dlin, B, K, d, 0, st));
-    RC(lin_bwd_w(ws + y.dlin, slots, dw[0], dw[1], (long long)B * K, d, Din, 0.f, 0, 0, ws + y.sk, y.sk_floats, st));
-    if (dslots) RC(lin_bwd_x(ws + y.dlin, w[0], dslots, (long long)B * K, d, Din, 1.f, nullptr, nullptr, 0.f, 0, 0, st));
+    RC(lin_bwd_w(ws + y.dlin, d, slots, Din, dw[0], dw[1], (long long)B * K, d, Din, 1.f, ws + y.sk, y.sk_floats, st));
+    if (dslots) RC(lin_bwd_x(ws + y.dlin, d, w[0], dslots, Din, (long long)B * K, d, Din, nullptr, 0, nullptr, 0, st));
     return 0;
 }
 
@@ -207,8 +157,7 @@ struct LongLay {
 };
 LongLay long_layout(int B, int K, int Din, int d, int h, int ff, int L) {
     LongLay y;
-    size_t a = 0;
-    auto take = [&](size_t n) { size_t r = a; a += (n + 63) & ~(size_t)63; return r; };
+    WsTake take;
     const size_t S = (size_t)K + 1, R = (size_t)B * S, BK = (size_t)B * K;
     const int nchunk = pool_cls_nchunk(B, (int)S, nullptr);
     y.Dp = (Din + 3) & ~3;
@@ -238,7 +187,7 @@ LongLay long_layout(int B, int K, int Din, int d, int h, int ff, int L) {
     if (splits > 32) splits = 32;
     y.sk_floats = splits > 1 ? splits * (slab + (size_t)ff + 3 * (size_t)d + 8) : 0;
     y.sk = take(y.sk_floats);
-    y.total = a;
+    y.total = take.end;
     return y;
 }
 int check_dims_long(int B, int K, int Din, int d, int h, int ff, int L) {
@@ -276,18 +225,18 @@ int ocrl_pool_transformer_long_fwd(const float* slots, const float* const* w, co
         RC(pool_cols_launch(w[0], Din, ws + y.wp, Dp, d, Dp, Din, st));
         xs = ws + y.sp; w0 = ws + y.wp;
     }
-    RC(lin_fwd(xs, w0, w[1], ws + y.lin, BK, d, Dp, 0, nullptr, 0.f, 0, 0, st));
+    RC(lin_fwd(xs, Dp, w0, w[1], ws + y.lin, d, BK, d, Dp, 0, nullptr, 0, st));
     RC(pool_embed_launch(ws + y.lin, w[2], pos, ws + y.l[0].x, B, K, d, st));
     for (int l = 0; l + 1 < L; ++l) {
         const float* const* q = w + 3 + 12 * l;
         const LongLayer& a = y.l[l];
         const unsigned site = SITE_POOL + 8 * l;
-        RC(lin_fwd(ws + a.x, q[0], q[1], ws + a.qkv, R, 3 * d, d, 0, nullptr, 0.f, 0, 0, st));
+        RC(lin_fwd(ws + a.x, d, q[0], q[1], ws + a.qkv, 3 * d, R, 3 * d, d, 0, nullptr, 0, st));
         RC(pool_flash_launch(ws + a.qkv, ws + a.o, ws + a.lse, nullptr, nullptr, nullptr, B, S, d, nhead, drop_p, seed, site + 0, 0, st));
-        RC(lin_fwd(ws + a.o, q[2], q[3], ws + a.y1, R, d, d, 0, ws + a.x, drop_p, seed, site + 1, st));
+        RC(lin_fwd(ws + a.o, d, q[2], q[3], ws + a.y1, d, R, d, d, 0, ws + a.x, d, st, Drop{drop_p, seed, site + 1}));
         RC(layernorm_fwd_launch(ws + a.y1, q[8], q[9], ws + a.x1, ws + a.mr1, ws + a.mr1 + R, R, d, st));
-        RC(lin_fwd(ws + a.x1, q[4], q[5], ws + a.hdn, R, ff, d, 1, nullptr, drop_p, seed, site + 2, st));
-        RC(lin_fwd(ws + a.hdn, q[6], q[7], ws + a.y2, R, d, ff, 0, ws + a.x1, drop_p, seed, site + 3, st));
+        RC(lin_fwd(ws + a.x1, d, q[4], q[5], ws + a.hdn, ff, R, ff, d, 1, nullptr, 0, st, Drop{drop_p, seed, site + 2}));
+        RC(lin_fwd(ws + a.hdn, ff, q[6], q[7], ws + a.y2, d, R, d, ff, 0, ws + a.x1, d, st, Drop{drop_p, seed, site + 3}));
         RC(layernorm_fwd_launch(ws + a.y2, q[10], q[11], ws + y.l[l + 1].x, ws + a.mr2, ws + a.mr2 + R, R, d, st));
     }
     // last layer: the CLS row
@@ -295,17 +244,17 @@ int ocrl_pool_transformer_long_fwd(const float* slots, const float* const* w, co
     const unsigned site = SITE_POOL + 8 * (L - 1);
     const float* X = ws + y.l[L - 1].x;
     RC(pool_rows_launch(X, ws + y.x0c, B, K, d, 2, st));
-    RC(lin_fwd(ws + y.x0c, q[0], q[1], ws + y.q, B, d, d, 0, nullptr, 0.f, 0, 0, st));            // rows 0..d-1 of in_proj: the query
+    RC(lin_fwd(ws + y.x0c, d, q[0], q[1], ws + y.q, d, B, d, d, 0, nullptr, 0, st));            // rows 0..d-1 of in_proj: the query
     PoolClsArgs c;
     c.X = X; c.Win = q[0]; c.bin = q[1]; c.q = ws + y.q; c.U = ws + y.U; c.part = ws + y.part; c.z = ws + y.z; c.stat = ws + y.stat; c.o = ws + y.ov;
     c.B = B; c.S = S; c.d = d; c.h = nhead; c.p = drop_p; c.seed = seed; c.site = site + 0;
     RC(pool_cls_attn_fwd_launch(c, st));
-    RC(lin_fwd(ws + y.ov, q[2], q[3], ws + y.at, B, d, d, 0, nullptr, 0.f, 0, 0, st));
+    RC(lin_fwd(ws + y.ov, d, q[2], q[3], ws + y.at, d, B, d, d, 0, nullptr, 0, st));
     RC(pool_cls_drop_launch(ws + y.at, ws + y.x0c, d, ws + y.y1, B, d, S, drop_p, seed, site + 1, st));         // x + dropout1(attn)
     RC(layernorm_fwd_launch(ws + y.y1, q[8], q[9], ws + y.x1, ws + y.mr1, ws + y.mr1 + B, B, d, st));
-    RC(lin_fwd(ws + y.x1, q[4], q[5], ws + y.hdn, B, ff, d, 1, nullptr, 0.f, 0, 0, st));
+    RC(lin_fwd(ws + y.x1, d, q[4], q[5], ws + y.hdn, ff, B, ff, d, 1, nullptr, 0, st));
     RC(pool_cls_drop_launch(ws + y.hdn, nullptr, 0, ws + y.hdn, B, ff, S, drop_p, seed, site + 2, st));         // dropout(relu(linear1))
-    RC(lin_fwd(ws + y.hdn, q[6], q[7], ws + y.at, B, d, ff, 0, nullptr, 0.f, 0, 0, st));
+    RC(lin_fwd(ws + y.hdn, ff, q[6], q[7], ws + y.at, d, B, d, ff, 0, nullptr, 0, st));
     RC(pool_cls_drop_launch(ws + y.at, ws + y.x1, d, ws + y.y2, B, d, S, drop_p, seed, site + 3, st));          // x1 + dropout2(linear2)
     RC(layernorm_fwd_launch(ws + y.y2, q[10], q[11], out, ws + y.mr2, ws + y.mr2 + B, B, d, st));
     return 0;
@@ -330,21 +279,21 @@ int ocrl_pool_transformer_long_bwd(const float* slots, const float* dout, const 
         RC(layernorm_bwd_launch(dout, ws + y.y2, ws + y.mr2, ws + y.mr2 + B, q[10], cA, dgb, B, d, 0, 0, tmp, TMP_FLOATS, st));
         RC(copy_launch(dgb, g[10], d, st)); RC(copy_launch(dgb + d, g[11], d, st));
         RC(pool_cls_drop_launch(cA, nullptr, 0, cAd, B, d, S, drop_p, seed, site + 3, st));
-        RC(lin_bwd_w(cAd, ws + y.hdn, g[6], g[7], B, d, ff, 0.f, 0, 0, ws + y.sk, y.sk_floats, st));
-        RC(lin_bwd_x(cAd, q[6], ws + y.chd, B, d, ff, inv_keep, ws + y.hdn, nullptr, 0.f, 0, 0, st));
-        RC(lin_bwd_w(ws + y.chd, ws + y.x1, g[4], g[5], B, ff, d, 0.f, 0, 0, ws + y.sk, y.sk_floats, st));
-        RC(lin_bwd_x(ws + y.chd, q[4], cB, B, ff, d, 1.f, nullptr, cA, 0.f, 0, 0, st));                   // + residual
+        RC(lin_bwd_w(cAd, d, ws + y.hdn, ff, g[6], g[7], B, d, ff, 1.f, ws + y.sk, y.sk_floats, st));
+        RC(lin_bwd_x(cAd, d, q[6], ws + y.chd, ff, B, d, ff, ws + y.hdn, ff, nullptr, 0, st, Drop(), Xf(), inv_keep));
+        RC(lin_bwd_w(ws + y.chd, ff, ws + y.x1, d, g[4], g[5], B, ff, d, 1.f, ws + y.sk, y.sk_floats, st));
+        RC(lin_bwd_x(ws + y.chd, ff, q[4], cB, d, B, ff, d, nullptr, 0, cA, d, st));                   // + residual
         RC(layernorm_bwd_launch(cB, ws + y.y1, ws + y.mr1, ws + y.mr1 + B, q[8], cA, dgb, B, d, 0, 0, tmp, TMP_FLOATS, st));
         RC(copy_launch(dgb, g[8], d, st)); RC(copy_launch(dgb + d, g[9], d, st));
         RC(pool_cls_drop_launch(cA, nullptr, 0, cAd, B, d, S, drop_p, seed, site + 1, st));
-        RC(lin_bwd_w(cAd, ws + y.ov, g[2], g[3], B, d, d, 0.f, 0, 0, ws + y.sk, y.sk_floats, st));
-        RC(lin_bwd_x(cAd, q[2], ws + y.dO, B, d, d, 1.f, nullptr, nullptr, 0.f, 0, 0, st));
+        RC(lin_bwd_w(cAd, d, ws + y.ov, d, g[2], g[3], B, d, d, 1.f, ws + y.sk, y.sk_floats, st));
+        RC(lin_bwd_x(cAd, d, q[2], ws + y.dO, d, B, d, d, nullptr, 0, nullptr, 0, st));
         PoolClsArgs c;
         c.X = ws + y.l[L - 1].x; c.Win = q[0]; c.bin = q[1]; c.q = ws + y.q; c.U = ws + y.U; c.part = ws + y.part; c.z = ws + y.z; c.stat = ws + y.stat;
         c.dO = ws + y.dO; c.G = ws + y.G; c.gD = ws + y.gD; c.dX = g2; c.w = ws + y.w; c.dq = ws + y.dq; c.x0 = ws + y.x0c; c.dW = g[0]; c.db = g[1];
         c.B = B; c.S = S; c.d = d; c.h = nhead; c.p = drop_p; c.seed = seed; c.site = site + 0;
         RC(pool_cls_attn_bwd_launch(c, st));
-        RC(lin_bwd_x(ws + y.dq, q[0], cB, B, d, d, 1.f, nullptr, cA, 0.f, 0, 0, st));                    // row 0: W_q^T dq + residual
+        RC(lin_bwd_x(ws + y.dq, d, q[0], cB, d, B, d, d, nullptr, 0, cA, d, st));                    // row 0: W_q^T dq + residual
         RC(pool_cls_add_launch(g2, cB, B, d, S, st));
     }
     float *gA = ws + y.gA, *gB = ws + y.gB;
@@ -355,17 +304,17 @@ int ocrl_pool_transformer_long_bwd(const float* slots, const float* dout, const 
         const unsigned site = SITE_POOL + 8 * l;
         RC(layernorm_bwd_launch(g2, ws + a.y2, ws + a.mr2, ws + a.mr2 + R, q[10], gA, dgb, R, d, 0, 0, tmp, TMP_FLOATS, st));
         RC(copy_launch(dgb, g[10], d, st)); RC(copy_launch(dgb + d, g[11], d, st));
-        RC(lin_bwd_w(gA, ws + a.hdn, g[6], g[7], R, d, ff, drop_p, seed, site + 3, ws + y.sk, y.sk_floats, st));
-        RC(lin_bwd_x(gA, q[6], ws + y.dhdn, R, d, ff, inv_keep, ws + a.hdn, nullptr, drop_p, seed, site + 3, st));
-        RC(lin_bwd_w(ws + y.dhdn, ws + a.x1, g[4], g[5], R, ff, d, 0.f, 0, 0, ws + y.sk, y.sk_floats, st));
-        RC(lin_bwd_x(ws + y.dhdn, q[4], gB, R, ff, d, 1.f, nullptr, gA, 0.f, 0, 0, st));
+        RC(lin_bwd_w(gA, d, ws + a.hdn, ff, g[6], g[7], R, d, ff, 1.f, ws + y.sk, y.sk_floats, st, Drop{drop_p, seed, site + 3}));
+        RC(lin_bwd_x(gA, d, q[6], ws + y.dhdn, ff, R, d, ff, ws + a.hdn, ff, nullptr, 0, st, Drop{drop_p, seed, site + 3}, Xf(), inv_keep));
+        RC(lin_bwd_w(ws + y.dhdn, ff, ws + a.x1, d, g[4], g[5], R, ff, d, 1.f, ws + y.sk, y.sk_floats, st));
+        RC(lin_bwd_x(ws + y.dhdn, ff, q[4], gB, d, R, ff, d, nullptr, 0, gA, d, st));
         RC(layernorm_bwd_launch(gB, ws + a.y1, ws + a.mr1, ws + a.mr1 + R, q[8], gA, dgb, R, d, 0, 0, tmp, TMP_FLOATS, st));
         RC(copy_launch(dgb, g[8], d, st)); RC(copy_launch(dgb + d, g[9], d, st));
-        RC(lin_bwd_w(gA, ws + a.o, g[2], g[3], R, d, d, drop_p, seed, site + 1, ws + y.sk, y.sk_floats, st));
-        RC(lin_bwd_x(gA, q[2], gB, R, d, d, 1.f, nullptr, nullptr, drop_p, seed, site + 1, st));
+        RC(lin_bwd_w(gA, d, ws + a.o, d, g[2], g[3], R, d, d, 1.f, ws + y.sk, y.sk_floats, st, Drop{drop_p, seed, site + 1}));
+        RC(lin_bwd_x(gA, d, q[2], gB, d, R, d, d, nullptr, 0, nullptr, 0, st, Drop{drop_p, seed, site + 1}));
         RC(pool_flash_launch(ws + a.qkv, ws + a.o, ws + a.lse, gB, ws + y.Dd, ws + y.dqkv, B, S, d, nhead, drop_p, seed, site + 0, 1, st));
-        RC(lin_bwd_w(ws + y.dqkv, ws + a.x, g[0], g[1], R, 3 * d, d, 0.f, 0, 0, ws + y.sk, y.sk_floats, st));
-        RC(lin_bwd_x(ws + y.dqkv, q[0], g2, R, 3 * d, d, 1.f, nullptr, gA, 0.f, 0, 0, st));
+        RC(lin_bwd_w(ws + y.dqkv, 3 * d, ws + a.x, d, g[0], g[1], R, 3 * d, d, 1.f, ws + y.sk, y.sk_floats, st));
+        RC(lin_bwd_x(ws + y.dqkv, 3 * d, q[0], g2, d, R, 3 * d, d, nullptr, 0, gA, d, st));
     }
     // x0 = [cls; Linear(slots)] (+pos)
     RC(colsum_launch(g2, (long long)S * d, dw[2], B, d, 0, 1.f, tmp, TMP_FLOATS, st));
@@ -377,10 +326,10 @@ int ocrl_pool_transformer_long_bwd(const float* slots, const float* dout, const 
         RC(pool_cols_launch(w[0], Din, ws + y.wp, Dp, d, Dp, Din, st));
         xs = ws + y.sp; w0 = ws + y.wp;
     }
-    RC(lin_bwd_w(ws + y.dlin, xs, Dp != Din ? ws + y.dwp : dw[0], dw[1], BK, d, Dp, 0.f, 0, 0, ws + y.sk, y.sk_floats, st));
+    RC(lin_bwd_w(ws + y.dlin, d, xs, Dp, Dp != Din ? ws + y.dwp : dw[0], dw[1], BK, d, Dp, 1.f, ws + y.sk, y.sk_floats, st));
     if (Dp != Din) RC(pool_cols_launch(ws + y.dwp, Dp, dw[0], Din, d, Din, Din, st));
     if (dslots) {
-        RC(lin_bwd_x(ws + y.dlin, w0, Dp != Din ? ws + y.dsp : dslots, BK, d, Dp, 1.f, nullptr, nullptr, 0.f, 0, 0, st));
+        RC(lin_bwd_x(ws + y.dlin, d, w0, Dp != Din ? ws + y.dsp : dslots, Dp, BK, d, Dp, nullptr, 0, nullptr, 0, st));
         if (Dp != Din) RC(pool_cols_launch(ws + y.dsp, Dp, dslots, Din, BK, Din, Din, st));
     }
     return 0;

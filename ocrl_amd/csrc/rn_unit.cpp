@@ -8,12 +8,6 @@
 #include "../../include/ocrl_hip.h"
 #include "kernels.h"
 
-#define RC(x)                 \
-    do {                      \
-        int rc__ = (x);       \
-        if (rc__) return rc__; \
-    } while (0)
-
 namespace {
 struct RnLay {
     int Dp, P, gmax, fmax;
@@ -42,8 +36,7 @@ int check_rn(int B, int K, int D, int ng, const int* g_dims, int nf, const int* 
 
 RnLay rn_layout(int B, int K, int D, int ng, const int* g_dims, int nf, const int* f_dims) {
     RnLay y;
-    size_t a = 0;
-    auto take = [&](size_t n) { size_t r = a; a += (n + 63) & ~(size_t)63; return r; };
+    WsTake take;
     y.Dp = (D + 3) & ~3;
     y.P = K * (K - 1);
     const size_t BK = (size_t)B * K, BP = (size_t)B * y.P, g1 = g_dims[0], gL = g_dims[ng - 1];
@@ -69,7 +62,7 @@ RnLay rn_layout(int B, int K, int D, int ng, const int* g_dims, int nf, const in
     if (splits > 32) splits = 32;
     y.sk_floats = splits > 1 ? splits * (slab + bslab + 4) : 0;
     y.sk = take(y.sk_floats);
-    y.total = a;
+    y.total = take.end;
     return y;
 }
 }  // namespace
@@ -97,15 +90,16 @@ int ocrl_pool_rn_fwd(const float* slots, const float* const* w, float* out, int 
     }
     RC(pool_cols_launch(w[0], 2 * D, ws + y.w1s, Dp, g1, Dp, D, st));                              // U = W1[:, :D]
     RC(pool_cols_launch(w[0] + D, 2 * D, ws + y.w1s + (size_t)g1 * Dp, Dp, g1, Dp, D, st));        // V = W1[:, D:]
-    RC(lin_fwd(xs, ws + y.w1s, nullptr, ws + y.ab, BK, 2 * g1, Dp, 0, nullptr, 0.f, 0, 0, st));   // [A | Bq] on the slot rows
+    RC(lin_fwd(xs, Dp, ws + y.w1s, nullptr, ws + y.ab, 2 * g1, BK, 2 * g1, Dp, 0, nullptr, 0, st));   // [A | Bq] on the slot rows
     RC(rn_pair_fwd_launch(ws + y.ab, w[1], ws + y.h[0], B, K, g1, st));
     for (int l = 1; l < ng; ++l)
-        RC(lin_fwd(ws + y.h[l - 1], w[2 * l], w[2 * l + 1], ws + y.h[l], BP, g_dims[l], g_dims[l - 1], 1, nullptr, 0.f, 0, 0, st));
+        RC(lin_fwd(ws + y.h[l - 1], g_dims[l - 1], w[2 * l], w[2 * l + 1], ws + y.h[l], g_dims[l], BP, g_dims[l], g_dims[l - 1], 1, nullptr, 0, st));
     RC(rn_pairsum_fwd_launch(ws + y.h[ng - 1], ws + y.y, B, y.P, gL, st));
     const float* const* wf = w + 2 * ng;
-    for (int l = 0; l < nf; ++l)
-        RC(lin_fwd(l ? ws + y.f[l - 1] : ws + y.y, wf[2 * l], wf[2 * l + 1], ws + y.f[l], B, f_dims[l], l ? f_dims[l - 1] : gL, 1, nullptr, 0.f, 0, 0,
-                   st));
+    for (int l = 0; l < nf; ++l) {
+        const int kin = l ? f_dims[l - 1] : gL;
+        RC(lin_fwd(l ? ws + y.f[l - 1] : ws + y.y, kin, wf[2 * l], wf[2 * l + 1], ws + y.f[l], f_dims[l], B, f_dims[l], kin, 1, nullptr, 0, st));
+    }
     return copy_launch(ws + y.f[nf - 1], out, (long long)B * f_dims[nf - 1], st);
 }
 
@@ -126,27 +120,27 @@ int ocrl_pool_rn_bwd(const float* slots, const float* dout, const float* const* 
     RC(rn_pairsum_bwd_launch(dout, ws + y.f[nf - 1], fc, B, 1, f_dims[nf - 1], st));               // dout * (out > 0)
     for (int l = nf - 1; l >= 0; --l) {
         const int kin = l ? f_dims[l - 1] : gL;
-        RC(lin_bwd_w(fc, l ? ws + y.f[l - 1] : ws + y.y, dwf[2 * l], dwf[2 * l + 1], B, f_dims[l], kin, 0.f, 0, 0, sk, y.sk_floats, st));
-        RC(lin_bwd_x(fc, wf[2 * l], fn, B, f_dims[l], kin, 1.f, l ? ws + y.f[l - 1] : nullptr, nullptr, 0.f, 0, 0, st));
+        RC(lin_bwd_w(fc, f_dims[l], l ? ws + y.f[l - 1] : ws + y.y, kin, dwf[2 * l], dwf[2 * l + 1], B, f_dims[l], kin, 1.f, sk, y.sk_floats, st));
+        RC(lin_bwd_x(fc, f_dims[l], wf[2 * l], fn, kin, B, f_dims[l], kin, l ? ws + y.f[l - 1] : nullptr, kin, nullptr, 0, st));
         float* t = fc; fc = fn; fn = t;
     }
     // fc = d loss / d (pair sum); g: broadcast over the pairs under the last layer's ReLU, then layer by layer down to the first
     float *gc = ws + y.gA, *gn = ws + y.gB;
     RC(rn_pairsum_bwd_launch(fc, ws + y.h[ng - 1], gc, B, y.P, gL, st));
     for (int l = ng - 1; l >= 1; --l) {
-        RC(lin_bwd_w(gc, ws + y.h[l - 1], dw[2 * l], dw[2 * l + 1], BP, g_dims[l], g_dims[l - 1], 0.f, 0, 0, sk, y.sk_floats, st));
-        RC(lin_bwd_x(gc, w[2 * l], gn, BP, g_dims[l], g_dims[l - 1], 1.f, ws + y.h[l - 1], nullptr, 0.f, 0, 0, st));
+        RC(lin_bwd_w(gc, g_dims[l], ws + y.h[l - 1], g_dims[l - 1], dw[2 * l], dw[2 * l + 1], BP, g_dims[l], g_dims[l - 1], 1.f, sk, y.sk_floats, st));
+        RC(lin_bwd_x(gc, g_dims[l], w[2 * l], gn, g_dims[l - 1], BP, g_dims[l], g_dims[l - 1], ws + y.h[l - 1], g_dims[l - 1], nullptr, 0, st));
         float* t = gc; gc = gn; gn = t;
     }
     // the factored first layer: pair gradients -> [dA | dBq] on the slot rows -> dW1 = [dA^T s | dBq^T s], db1 = sum dA, dslots
     RC(rn_pair_bwd_launch(gc, ws + y.dab, B, K, g1, st));
     const float* xs = Dp != D ? ws + y.sp : slots;      // the padded copy the forward left in ws
-    RC(lin_bwd_w(ws + y.dab, xs, ws + y.dw1s, ws + y.db1s, BK, 2 * g1, Dp, 0.f, 0, 0, sk, y.sk_floats, st));
+    RC(lin_bwd_w(ws + y.dab, 2 * g1, xs, Dp, ws + y.dw1s, ws + y.db1s, BK, 2 * g1, Dp, 1.f, sk, y.sk_floats, st));
     RC(pool_cols_launch(ws + y.dw1s, Dp, dw[0], 2 * D, g1, D, D, st));
     RC(pool_cols_launch(ws + y.dw1s + (size_t)g1 * Dp, Dp, dw[0] + D, 2 * D, g1, D, D, st));
     RC(copy_launch(ws + y.db1s, dw[1], g1, st));
     if (dslots) {
-        RC(lin_bwd_x(ws + y.dab, ws + y.w1s, Dp != D ? ws + y.dsp : dslots, BK, 2 * g1, Dp, 1.f, nullptr, nullptr, 0.f, 0, 0, st));
+        RC(lin_bwd_x(ws + y.dab, 2 * g1, ws + y.w1s, Dp != D ? ws + y.dsp : dslots, Dp, BK, 2 * g1, Dp, nullptr, 0, nullptr, 0, st));
         if (Dp != D) RC(pool_cols_launch(ws + y.dsp, Dp, dslots, D, BK, D, D, st));
     }
     return 0;

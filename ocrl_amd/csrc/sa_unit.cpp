@@ -7,13 +7,8 @@
 #include "../../include/ocrl_hip.h"
 #include "kernels.h"
 
-#define RC(x)                 \
-    do {                      \
-        int rc__ = (x);       \
-        if (rc__) return rc__; \
-    } while (0)
-
 namespace {
+constexpr int SA_MAX_SPLITS = 64;        // split-k slabs of a weight gradient over the (image, iteration, slot) rows
 struct Lay {
     size_t wts, save, grows, small, table, xchg, parts, scratch, scratch_floats, total;
 };
@@ -23,8 +18,7 @@ Lay layout(int B, int K, int D, int H, int I, int NH) {
     const SaSave so = sa_save_layout(C, D, H, NH);
     const SaGrad go = sa_grad_layout(C, D, H, NH);
     Lay l;
-    size_t a = 0;
-    auto take = [&](size_t n) { size_t r = a; a += (n + 63) & ~(size_t)63; return r; };
+    WsTake take;
     l.wts = take(wo.total);
     l.save = take((size_t)B * I * K * so.ld);
     l.grows = take((size_t)B * I * K * go.ld);
@@ -34,25 +28,8 @@ Lay layout(int B, int K, int D, int H, int I, int NH) {
     l.parts = take(sa_parts_floats_host(B, K * NH));
     l.scratch_floats = (size_t)1024 * 3 * D * D / 4 + (1 << 18);
     l.scratch = take(l.scratch_floats);
-    l.total = a;
+    l.total = take.end;
     return l;
-}
-// dW[N_out,K_in] = alpha * dy^T x over M rows (split-K through `scr`), db[N_out] = column sums of dy
-int tn(const float* dy, int ld_dy, const float* x, int ldx, float* dW, float* db, long long M, int N_out, int K_in, float alpha, float* scr, size_t scr_floats,
-       hipStream_t st) {
-    GemmArgs a;
-    a.A = dy; a.B = x; a.C = dW; a.M = N_out; a.N = K_in; a.K = (int)M; a.lda = ld_dy; a.ldb = ldx; a.ldc = K_in; a.akc = 0; a.bkc = 0; a.alpha = alpha;
-    long long splits = M / 256;
-    const long long slab = (long long)N_out * K_in;
-    if (splits > 64) splits = 64;
-    if (splits * slab > (long long)scr_floats) splits = (long long)scr_floats / slab;
-    if (splits > 1) {
-        a.splitk = (int)splits; a.C = scr; a.sCsplit = slab;
-        RC(gemm_launch(a, st));
-        RC(splitk_reduce_launch(scr, dW, slab, (int)splits, slab, 0, st));
-    } else RC(gemm_launch(a, st));
-    if (db) RC(colsum_launch(dy, ld_dy, db, M, N_out, 0, 1.f, scr, scr_floats, st));
-    return 0;
 }
 }  // namespace
 
@@ -129,14 +106,20 @@ int ocrl_slot_attention_mh_bwd(const float* x, const float* dslots, float* dx, f
     RC(slot_attn_launch(a, 1, st));
     const long long R = (long long)B * I * K;
     const size_t sf = l.scratch_floats;
-    RC(tn(grows + go.out, go.ld, save + so.hid, so.ld, dw[15], dw[16], R, D, H, 1.f, scr, sf, st));        // mlp.2
-    RC(tn(grows + go.hid, go.ld, save + so.m, so.ld, dw[13], dw[14], R, H, D, 1.f, scr, sf, st));          // mlp.0
-    RC(tn(grows + go.gi, go.ld, save + so.u, so.ld, dw[9], dw[11], R, 3 * D, D, 1.f, scr, sf, st));        // gru ih
-    RC(tn(grows + go.gh, go.ld, save + so.sprev, so.ld, dw[10], dw[12], R, 3 * D, D, 1.f, scr, sf, st));   // gru hh
-    RC(tn(grows + go.q, go.ld, save + so.sn, so.ld, dw[6], nullptr, R, D, D, 1.f, scr, sf, st));           // project_q
+    // weight gradient over the R rows (split-k as every Linear, at most SA_MAX_SPLITS slabs); the bias gradient as column sums of dy
+    auto wgrad = [&](const float* dy, int ld_dy, const float* xr, int ldx, float* dW, float* db, int N_out, int K_in, float alpha) -> int {
+        RC(lin_bwd_w(dy, ld_dy, xr, ldx, dW, nullptr, R, N_out, K_in, alpha, scr, sf, st, Drop(), Xf(), 0, SA_MAX_SPLITS));
+        if (db) RC(colsum_launch(dy, ld_dy, db, R, N_out, 0, 1.f, scr, sf, st));
+        return 0;
+    };
+    RC(wgrad(grows + go.out, go.ld, save + so.hid, so.ld, dw[15], dw[16], D, H, 1.f));        // mlp.2
+    RC(wgrad(grows + go.hid, go.ld, save + so.m, so.ld, dw[13], dw[14], H, D, 1.f));          // mlp.0
+    RC(wgrad(grows + go.gi, go.ld, save + so.u, so.ld, dw[9], dw[11], 3 * D, D, 1.f));        // gru ih
+    RC(wgrad(grows + go.gh, go.ld, save + so.sprev, so.ld, dw[10], dw[12], 3 * D, D, 1.f));   // gru hh
+    RC(wgrad(grows + go.q, go.ld, save + so.sn, so.ld, dw[6], nullptr, D, D, 1.f));           // project_q
     for (int h = 0, dh = D / NH; h < NH; ++h) {       // head h: rows h*dh .. of project_v / project_k against that head's means / folded-query gradients
-        RC(tn(grows + go.u + h * dh, go.ld, save + so.up + h * C, so.ld, dw[8] + (size_t)h * dh * C, nullptr, R, dh, C, 1.f, scr, sf, st));           // project_v
-        RC(tn(save + so.q + h * dh, so.ld, grows + go.qp + h * C, go.ld, dw[7] + (size_t)h * dh * C, nullptr, R, dh, C, a.scale, scr, sf, st));       // project_k
+        RC(wgrad(grows + go.u + h * dh, go.ld, save + so.up + h * C, so.ld, dw[8] + (size_t)h * dh * C, nullptr, dh, C, 1.f));           // project_v
+        RC(wgrad(save + so.q + h * dh, so.ld, grows + go.qp + h * C, go.ld, dw[7] + (size_t)h * dh * C, nullptr, dh, C, a.scale));       // project_k
     }
     // LayerNorm gammas / betas: per-image partials [B][ln_s (2D) | ln_m (2D) | ln_in (2C)]; weight and bias are separate tensors here
     const int SM = 4 * D + 2 * C;

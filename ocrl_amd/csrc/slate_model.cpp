@@ -11,12 +11,6 @@
 #include <stdarg.h>
 #include <string.h>
 
-#define RC(x)                 \
-    do {                      \
-        int rc__ = (x);       \
-        if (rc__) return rc__; \
-    } while (0)
-
 static std::string fmt(const char* f, ...) {
     char buf[256];
     va_list ap;
@@ -383,58 +377,6 @@ int SlateModel::dropout_mask(unsigned site, long long n, float* out, hipStream_t
     return dropout_mask_launch(out, n, pdrop_, last_.seed, site, st);
 }
 
-// ---------------------------------------------------------------------------------------------
-int SlateModel::lin_fwd(const float* x, int ldx, const float* W, const float* b, float* y, int ldy, long long M, int Nn, int Kk, int relu,
-                        const float* resid, int ldr, float drop_p, unsigned site, hipStream_t st) {
-    GemmArgs a;
-    a.A = x; a.B = W; a.C = y; a.M = (int)M; a.N = Nn; a.K = Kk; a.lda = ldx; a.ldb = Kk; a.ldc = ldy; a.akc = 1; a.bkc = 1;
-    a.bias = b; a.relu = relu; a.resid = resid; a.ldr = ldr; a.drop_p = drop_p; a.drop_seed = last_.seed; a.drop_site = site;
-    return gemm_launch(a, st);
-}
-// dx[M,K_in] = (drop(dy)[M,N_out] W[N_out,K_in]) * (mask > 0) + resid
-int SlateModel::lin_bwd_x(const float* dy, int ld_dy, const float* W, float* dx, int ldx, long long M, int N_out, int K_in,
-                          const float* mask, int ldmask, const float* resid, int ldr, hipStream_t st, Drop dr, Xf xf) {
-    GemmArgs a;
-    a.a_mode = xf.a_mode; a.b_mode = xf.b_mode; a.x_lse = xf.lse; a.x_tok = xf.tok; a.x_scale = xf.scale;
-    a.A = dy; a.B = W; a.C = dx; a.M = (int)M; a.N = K_in; a.K = N_out; a.lda = ld_dy; a.ldb = K_in; a.ldc = ldx; a.akc = 1; a.bkc = 0;
-    a.mask = mask; a.ldmask = ldmask; a.resid = resid; a.ldr = ldr;
-    if (dr.p > 0.f) { a.adrop_p = dr.p; a.adrop_site = dr.site; a.adrop_ld = N_out; a.drop_seed = last_.seed; }
-    return gemm_launch(a, st);
-}
-// dW[N_out,K_in] = alpha * drop(dy)^T x (split over the M rows);  db[N_out] = column sums of drop(dy), fused into the GEMM
-int SlateModel::lin_bwd_w(const float* dy, int ld_dy, const float* x, int ldx, float* dW, float* db, long long M, int N_out, int K_in,
-                          float alpha, hipStream_t st, Drop dr, Xf xf) {
-    GemmArgs a;
-    a.a_mode = xf.a_mode; a.b_mode = xf.b_mode; a.x_lse = xf.lse; a.x_tok = xf.tok; a.x_scale = xf.scale;
-    a.A = dy; a.B = x; a.C = dW; a.M = N_out; a.N = K_in; a.K = (int)M; a.lda = ld_dy; a.ldb = ldx; a.ldc = K_in; a.akc = 0; a.bkc = 0;
-    a.alpha = alpha;
-    if (dr.p > 0.f) { a.adrop_p = dr.p; a.adrop_site = dr.site; a.adrop_ld = N_out; a.drop_seed = last_.seed; }
-    // output tiles as gemm.hip will cut them (128x192 for 192 input features over >= 4096 rows, else 128x128 / 128x64): the split count
-    // aims at ~1024 workgroups -- counting 64-wide tiles for the 128x192 case left 340 workgroups on 256 CUs (PMC: 0.95 waves per SIMD)
-    const int col_tiles = (K_in == 192 && M >= 4096) ? 1 : cdiv(K_in, (K_in % 128 == 0) ? 128 : 64);
-    const int tiles = cdiv(N_out, 128) * col_tiles;
-    long long splits = 1024 / tiles;
-    if (splits > M / 256) splits = M / 256;
-    if (splits < 1) splits = 1;
-    const long long slab = (long long)N_out * K_in;
-    const long long bslab = (N_out + 3) & ~3;
-    if (splits * (slab + bslab) > (long long)scratch_floats_) splits = (long long)scratch_floats_ / (slab + bslab);
-    if (splits > 1) {
-        a.splitk = (int)splits; a.C = scratch_; a.sCsplit = slab;
-        float* bpart = scratch_ + splits * slab;
-        if (db) { a.bias_out = bpart; a.sBias = bslab; }
-        RC(gemm_launch(a, st));
-        RC(splitk_reduce_launch(scratch_, dW, slab, (int)splits, slab, 0, st));
-        if (db) {
-            if (N_out % 4 == 0) RC(splitk_reduce_launch(bpart, db, N_out, (int)splits, bslab, 0, st));
-            else RC(colsum_launch(bpart, bslab, db, splits, N_out, 0, 1.f, bpart + splits * bslab, scratch_floats_ - (size_t)(splits * (slab + bslab)), st));
-        }
-    } else {
-        if (db) a.bias_out = db;
-        RC(gemm_launch(a, st));
-    }
-    return 0;
-}
 int SlateModel::conv_layer_fwd(const float* x, const float* pack, const float* bias, float* y, int Bn, int Hh, int Ww, int KS, int CIN,
                                int relu, const float* posmap, const float* mask, hipStream_t st) {
     ConvArgs a;
@@ -866,7 +808,7 @@ int SlateModel::bwd_decoder(hipStream_t st) {
     auto dw = [&](const float* dy, int ld_dy, const float* x, int ldx, float* dW, float* db, long long M, int N_out, int K_in, Xf xf = Xf()) -> int {
         float* keep = scratch_;
         if (dws) scratch_ = sw_scratch;
-        const int rc = lin_bwd_w(dy, ld_dy, x, ldx, dW, db, M, N_out, K_in, 1.f, sw, Drop(), xf);
+        const int rc = lin_bwd_w(dy, ld_dy, x, ldx, dW, db, M, N_out, K_in, 1.f, sw, xf);
         scratch_ = keep;
         return rc;
     };
@@ -1159,7 +1101,7 @@ int SlateModel::bwd_dvae(hipStream_t st) {
     have_scores_ = false;
     if (fused_heads()) {
         Xf zx; zx.b_mode = 2; zx.lse = zlse_;
-        RC(lin_bwd_w(gdA_, 64, zraw_, V, G("_dvae._decoder.0.m.weight"), G("_dvae._decoder.0.m.bias"), BT, 64, V, 1.f, st, Drop(), zx));
+        RC(lin_bwd_w(gdA_, 64, zraw_, V, G("_dvae._decoder.0.m.weight"), G("_dvae._decoder.0.m.bias"), BT, 64, V, 1.f, st, zx));
         // Gumbel soft-max backward in the epilogue of the dz product: d = z (dz - sum_v z_v dz_v) / tau with
         // sum_v z_v dz_v = sum_c g_c (z W^T)_c = sum_c g_c (dd0 - bias)_c  (g = gdA_ is zero where the ReLU of dd0 is closed)
         RC(rowdot_bias64_launch(gdA_, dd0_, P("_dvae._decoder.0.m.bias"), BT, zdot_, st));

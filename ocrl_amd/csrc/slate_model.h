@@ -39,11 +39,6 @@ struct StepInputs {
     const unsigned long long* seed_dev = nullptr;   // internal: the slot-noise seed read from device memory (captured encode graphs)
 };
 
-// dropout-backward mask applied to dy while the GEMM stages it
-struct Drop { float p = 0.f; unsigned site = 0; };
-// soft-max operand transform of a product (GemmArgs::a_mode / b_mode): the operand is rebuilt from stored scores + per-row log-sum-exp
-struct Xf { int a_mode = 0, b_mode = 0; const float* lse = nullptr; const int* tok = nullptr; float scale = 1.f; };
-
 class SlateModel {
 public:
     explicit SlateModel(const SlateConfig& c);
@@ -77,12 +72,15 @@ private:
     float* G(const std::string& n) const;
     float* carve(const char* name, size_t n);
     void layout_workspace(bool commit);
+    // the Linear helpers of gemm.hip with this step's dropout seed and the current scratch (lin_bwd_x is used as it is)
     int lin_fwd(const float* x, int ldx, const float* W, const float* b, float* y, int ldy, long long M, int N, int K, int relu,
-                const float* resid, int ldr, float drop_p, unsigned site, hipStream_t st);
-    int lin_bwd_x(const float* dy, int ld_dy, const float* W, float* dx, int ldx, long long M, int N_out, int K_in, const float* mask,
-                  int ldmask, const float* resid, int ldr, hipStream_t st, Drop dr = Drop(), Xf xf = Xf());
+                const float* resid, int ldr, float drop_p, unsigned site, hipStream_t st) {
+        return ::lin_fwd(x, ldx, W, b, y, ldy, M, N, K, relu, resid, ldr, st, Drop{drop_p, last_.seed, site});
+    }
     int lin_bwd_w(const float* dy, int ld_dy, const float* x, int ldx, float* dW, float* db, long long M, int N_out, int K_in,
-                  float alpha, hipStream_t st, Drop dr = Drop(), Xf xf = Xf());
+                  float alpha, hipStream_t st, Xf xf = Xf()) {
+        return ::lin_bwd_w(dy, ld_dy, x, ldx, dW, db, M, N_out, K_in, alpha, scratch_, scratch_floats_, st, Drop(), xf);
+    }
     // the Gumbel / cross-entropy soft-max heads live in the vocabulary GEMMs (soft samples; the straight-through `hard` form keeps z)
     bool fused_heads() const { return !cfg.hard; }
     int conv_layer_fwd(const float* x, const float* pack, const float* bias, float* y, int Bn, int Hh, int Ww, int KS, int CIN, int relu,

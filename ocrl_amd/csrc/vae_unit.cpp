@@ -12,12 +12,6 @@
 #include "../../include/ocrl_hip.h"
 #include "kernels.h"
 
-#define RC(x)                 \
-    do {                      \
-        int rc__ = (x);       \
-        if (rc__) return rc__; \
-    } while (0)
-
 namespace {
 constexpr int CONV_HIP_MIN = 32;      // decoder 3 x 3 maps from this size on run conv.hip's 4 x 32 pixel tiles; smaller ones naturecnn.hip's
 constexpr size_t SK_FLOATS = (size_t)1 << 22;
@@ -80,8 +74,7 @@ int check_vae(int B, int S, int C, int f, int L) {
 
 VaeLay vae_layout(int B, int S, int C, int f, int L, int cnn, int full) {
     VaeLay y;
-    size_t a = 0;
-    auto take = [&](size_t n) { size_t r = a; a += (n + 63) & ~(size_t)63; return r; };
+    WsTake take;
     y.n = stages_of(S, f); y.f = f; y.S = S; y.C = C; y.L = L; y.B = B; y.full = full; y.cnn = cnn;
     const size_t F = (size_t)64 * f * f;
     size_t gmax = (size_t)B * F;
@@ -121,7 +114,7 @@ VaeLay vae_layout(int B, int S, int C, int f, int L, int cnn, int full) {
     y.dWml = take((size_t)2 * L * F); y.dbml = take(2 * L);
     y.gA = take(gmax); y.gB = take(gmax);
     y.sk = take(y.sk_floats);
-    y.total = a;
+    y.total = take.end;
     return y;
 }
 
@@ -153,8 +146,8 @@ int nc_bwd(const float* x, NcMap xm, const float* dy, NcMap dym, float* dx, cons
 // a 1 x 1 Conv2dBlock / Linear layer's backward: dW, db; then dx = dy W (masked by `mask` > 0, + resid) when dx
 int lin_bwd(const float* dy, const float* x, const float* W, float* dW, float* db, float* dx, long long M, int N_out, int K_in, const float* mask,
             const float* resid, const VaeLay& y, float* ws, hipStream_t st) {
-    RC(lin_bwd_w(dy, x, dW, db, M, N_out, K_in, 0.f, 0, 0, ws + y.sk, y.sk_floats, st));
-    if (dx) RC(lin_bwd_x(dy, W, dx, M, N_out, K_in, 1.f, mask, resid, 0.f, 0, 0, st));
+    RC(lin_bwd_w(dy, N_out, x, K_in, dW, db, M, N_out, K_in, 1.f, ws + y.sk, y.sk_floats, st));
+    if (dx) RC(lin_bwd_x(dy, N_out, W, dx, K_in, M, N_out, K_in, mask, K_in, resid, K_in, st));
     return 0;
 }
 
@@ -184,9 +177,9 @@ int enc_fwd(const float* obs, const float* const* w, float* emap, const VaeLay& 
         const float* x = i ? ws + y.ea[i - 1][3] : obs;
         RC(nc_fwd(x, i ? nhwc(H, 64) : nchw(H, y.C), ws + y.ea[i][0], nhwc(s, 64), w[y.enc(i, 0)], w[y.enc(i, 0) + 1], B, i ? 64 : y.C, H, s, 2, 2, 0, st));
         for (int j = 1; j < 4; ++j)
-            RC(lin_fwd(ws + y.ea[i][j - 1], w[y.enc(i, j)], w[y.enc(i, j) + 1], ws + y.ea[i][j], M, 64, 64, 1, nullptr, 0.f, 0, 0, st));
+            RC(lin_fwd(ws + y.ea[i][j - 1], 64, w[y.enc(i, j)], w[y.enc(i, j) + 1], ws + y.ea[i][j], 64, M, 64, 64, 1, nullptr, 0, st));
     }
-    return lin_fwd(ws + y.ea[y.n - 1][3], w[y.enc_last()], w[y.enc_last() + 1], emap, (long long)B * y.f * y.f, 64, 64, 0, nullptr, 0.f, 0, 0, st);
+    return lin_fwd(ws + y.ea[y.n - 1][3], 64, w[y.enc_last()], w[y.enc_last() + 1], emap, 64, (long long)B * y.f * y.f, 64, 64, 0, nullptr, 0, st);
 }
 
 // encoder backward from ge = d (encoder map) [B f f, 64]; ga / gb are scratch maps
@@ -234,19 +227,19 @@ int ocrl_vae_fwd(const float* obs, const float* const* w, const float* eps, floa
     // _mu (and _var) weights with their columns moved from the NCHW flatten (c, h, w) to the map's (h, w, c)
     RC(vae_permute_launch(w[y.mu()], ws + y.Wml, L, 64, HW, 0, 1, st));
     if (!full) {
-        return lin_fwd(ws + y.e, ws + y.Wml, w[y.mu() + 1], rep, B, L, F, 0, nullptr, 0.f, 0, 0, st);
+        return lin_fwd(ws + y.e, F, ws + y.Wml, w[y.mu() + 1], rep, L, B, L, F, 0, nullptr, 0, st);
     }
     RC(vae_permute_launch(w[y.var()], ws + y.Wml + (size_t)L * F, L, 64, HW, 0, 1, st));
     RC(copy_launch(w[y.mu() + 1], ws + y.bml, L, st));
     RC(copy_launch(w[y.var() + 1], ws + y.bml + L, L, st));
-    RC(lin_fwd(ws + y.e, ws + y.Wml, ws + y.bml, ws + y.ml, B, 2 * L, F, 0, nullptr, 0.f, 0, 0, st));          // [mu | logvar]
+    RC(lin_fwd(ws + y.e, F, ws + y.Wml, ws + y.bml, ws + y.ml, 2 * L, B, 2 * L, F, 0, nullptr, 0, st));          // [mu | logvar]
     RC(vae_kl_fwd_launch(ws + y.ml, eps, ws + y.lat, ws + y.klp, use_cnn_feat ? nullptr : rep, B, L, st));
     if (use_cnn_feat) RC(copy_launch(ws + y.e, rep, (long long)B * F, st));                                     // img_to_slot order
     // _in_dec with its rows (and bias) moved to the map's (h, w, c) order: its output is the NHWC decoder input
     RC(vae_permute_launch(w[y.in_dec()], ws + y.Win, L, 64, HW, 1, 1, st));
     RC(vae_permute_launch(w[y.in_dec() + 1], ws + y.bin, 1, 64, HW, 1, 1, st));
-    RC(lin_fwd(ws + y.lat, ws + y.Win, ws + y.bin, ws + y.hin, B, F, L, 0, nullptr, 0.f, 0, 0, st));
-    RC(lin_fwd(ws + y.hin, w[y.dec0()], w[y.dec0() + 1], ws + y.d0, (long long)B * HW, 64, 64, 1, nullptr, 0.f, 0, 0, st));
+    RC(lin_fwd(ws + y.lat, L, ws + y.Win, ws + y.bin, ws + y.hin, F, B, F, L, 0, nullptr, 0, st));
+    RC(lin_fwd(ws + y.hin, 64, w[y.dec0()], w[y.dec0() + 1], ws + y.d0, 64, (long long)B * HW, 64, 64, 1, nullptr, 0, st));
     const float* x = ws + y.d0;
     for (int i = 0; i < y.n; ++i) {
         const int s = f << i;
@@ -260,16 +253,16 @@ int ocrl_vae_fwd(const float* obs, const float* const* w, const float* eps, floa
             a.X = x; a.Wp = ws + y.pkf[i]; a.Y = ws + y.x3[i]; a.B = B; a.H = s; a.W = s; a.bias = w[l3 + 1]; a.relu = 1;
             RC(conv_fwd_launch(a, 3, 64, 64, st));
         }
-        RC(lin_fwd(ws + y.x3[i], w[y.dec(i, 1)], w[y.dec(i, 1) + 1], ws + y.y1[i], M, 64, 64, 1, nullptr, 0.f, 0, 0, st));
-        RC(lin_fwd(ws + y.y1[i], w[y.dec(i, 2)], w[y.dec(i, 2) + 1], ws + y.y2[i], M, 64, 64, 1, nullptr, 0.f, 0, 0, st));
-        RC(lin_fwd(ws + y.y2[i], w[y.dec(i, 3)], w[y.dec(i, 3) + 1], ws + y.y4[i], M, 256, 64, 1, nullptr, 0.f, 0, 0, st));
+        RC(lin_fwd(ws + y.x3[i], 64, w[y.dec(i, 1)], w[y.dec(i, 1) + 1], ws + y.y1[i], 64, M, 64, 64, 1, nullptr, 0, st));
+        RC(lin_fwd(ws + y.y1[i], 64, w[y.dec(i, 2)], w[y.dec(i, 2) + 1], ws + y.y2[i], 64, M, 64, 64, 1, nullptr, 0, st));
+        RC(lin_fwd(ws + y.y2[i], 64, w[y.dec(i, 3)], w[y.dec(i, 3) + 1], ws + y.y4[i], 256, M, 256, 64, 1, nullptr, 0, st));
         RC(pixel_shuffle_launch(ws + y.y4[i], ws + y.ps[i], B, s, s, 64, 1, nullptr, st));
         x = ws + y.ps[i];
     }
     // 64 -> C output conv as a 4-wide GEMM (zero rows past C) into the [B, S, S, 4] layout of mse_launch
     RC(vae_pad_rows_launch(w[y.out()], ws + y.Wo4, y.C, 4, 64, st));
     RC(vae_pad_rows_launch(w[y.out() + 1], ws + y.bo4, y.C, 4, 1, st));
-    RC(lin_fwd(x, ws + y.Wo4, ws + y.bo4, ws + y.r4, (long long)B * S * S, 4, 64, 0, nullptr, 0.f, 0, 0, st));
+    RC(lin_fwd(x, 64, ws + y.Wo4, ws + y.bo4, ws + y.r4, 4, (long long)B * S * S, 4, 64, 0, nullptr, 0, st));
     RC(mse_launch(obs, ws + y.r4, ws + y.dr4, metrics + 1, B, y.C, S, S, ws + y.msews, 1024, st));
     RC(vae_loss_launch(ws + y.klp, metrics, B, kld_weight, st));
     if (recon) RC(vae_recon_nchw_launch(ws + y.r4, recon, B, y.C, S * S, st));

@@ -84,7 +84,9 @@ def test_plan_reports_the_documented_rule(L, akc, bkc, M, N, K):
                                              (192, 4096, 128 * 256), (576, 192, 4096), (192, 192, 4095), (64, 192, 896), (192, 64, 896),
                                              (4, 64, 4100), (64, 48, 777), (128, 192, 4096), (192, 100, 5000)])
 def test_weight_gradient_split_count_matches_the_plan(L, N_out, K_in, rows):
-    """SlateModel::lin_bwd_w sizes its split-k from the output tiles "as gemm.hip will cut them"; that count must be the plan's"""
+    """The split-count rule of the Linear weight gradients (lin_splitk_count in csrc/gemm.hip) divides its ~1024 workgroups by the output
+    tiles gemm_plan cuts for the dW form.  Pins that tiling: one 128x192 column tile for 192 input features over >= 4096 rows, else
+    128- or 64-wide column tiles, 128-row tiles above 64 outputs"""
     if _env_overrides():
         pytest.skip(f"{_env_overrides()} set: the dispatch is overridden")
     col_tiles = 1 if (K_in == 192 and rows >= 4096) else -(-K_in // (128 if K_in % 128 == 0 else 64))
