@@ -297,6 +297,38 @@ int ocrl_vae_bwd(const float* obs, const float* eps, const float* const* w, cons
                  int obs_size, int obs_channels, int cnn_feat_size, int latent_dim, int use_cnn_feat, float kld_weight, int full, float* ws,
                  size_t ws_floats, void* stream);
 
+/* ---- Slot property probe: utils/property_predictor.py:12-189 (configs/train_property_predictor.yaml) ----
+ * A head (nl Linear layers, LeakyReLU(slope) between them; `linear`: nl = 1, `mlp3`: nl = 4 with dims = {256, 256, 256, O}) reads the
+ * detached encoder rows and predicts, per slot, O = sum of the property widths.  slot_rows != 0: rows [B K, D], dims[nl-1] == O
+ * (SLATE, Slot-Attention, IODINE).  slot_rows == 0: rows [B, D], dims[nl-1] == K O, the outputs are read as K pseudo-slots (VAE).
+ * Targets y [B, N, T], fp32; property p reads the target columns [tgt_range[2p], tgt_range[2p+1]) and the outputs
+ * [out_range[2p], out_range[2p+1]) (ascending, not overlapping); kind[p] = 0: a class index, cost -log_softmax(softmax(out))[class] (the
+ * reference takes the soft-max twice); kind[p] = 1: xy, two outputs, cost mean((out - y)^2); at most one xy property.
+ * cost [B, N, K] (object, slot) sums the properties; col [B, N] is the exact minimum-cost assignment of the N objects to N distinct
+ * slots, N <= K <= OCRL_PROBE_MAX_SLOTS (dynamic programme over slot bit-masks; ties: the lowest slot index, so two runs agree bit for
+ * bit); above the limit the calls return non-zero and launch nothing.
+ * metrics [P + 2]: [0] loss = sum over images and objects of cost[o, col[o]] (a sum, not a mean); [1 + p] acc of a class property
+ * (argmax of the raw outputs) or the reference's R^2_xy (||out - mean(y)||^2 / ||y - mean(y)||^2, mean over images and coordinates);
+ * [P + 1] mse_xy = mean Euclidean distance of the matched xy outputs (the reference's definition, despite the name).
+ * A class index outside its property's range gives a NaN loss (the reference raises).
+ * `w` / `dw`: the head's parameters in state_dict order (0.weight, 0.bias, 2.weight, ...); dw is overwritten, the rows get no gradient.
+ * _fwd leaves in ws what _bwd needs; _bwd (same ws, same shapes) scales by the device scalar dloss (null = 1).
+ * out [B, K, O], cost and col of _fwd may be null.  _match takes head outputs directly: out[b, s, :] at b * ld_img + s * ld_row, dout
+ * alike (only its [K, O] entries are written; null = no gradient), ws of _match_ws_floats(B, P).  Rejected shapes get ws_floats == 0. */
+#define OCRL_PROBE_MAX_SLOTS 12
+#define OCRL_PROBE_MAX_PROPS 8
+#define OCRL_PROBE_MAX_LAYERS 8
+size_t ocrl_probe_ws_floats(int B, int K, int N, int D, int O, int slot_rows, int nl, const int* dims, int P);
+int ocrl_probe_fwd(const float* rows, const float* const* w, const float* y, float* out, float* cost, int* col, float* metrics, int B, int K, int N,
+                   int D, int T, int O, int slot_rows, int nl, const int* dims, float slope, int P, const int* tgt_range, const int* out_range,
+                   const int* kind, float* ws, size_t ws_floats, void* stream);
+int ocrl_probe_bwd(const float* rows, const float* dloss, const float* const* w, float* const* dw, int B, int K, int N, int D, int O, int slot_rows,
+                   int nl, const int* dims, float slope, int P, float* ws, size_t ws_floats, void* stream);
+size_t ocrl_probe_match_ws_floats(int B, int P);
+int ocrl_probe_match(const float* out, int ld_row, long long ld_img, const float* y, const float* dloss, float* cost, int* col, float* metrics,
+                     float* dout, int B, int K, int N, int T, int O, int P, const int* tgt_range, const int* out_range, const int* kind, float* ws,
+                     size_t ws_floats, void* stream);
+
 /* ---- IODINE (ocrs/iodine/iodine_module.py:14-271, ocrs/iodine/iodine.py:4-14, ocrs/base.py:60-74): SURVEY.md §8 row a20 ----
  * Same conventions as the SLATE handle: flat fp32 parameter / gradient / Adam buffers in the reference's
  * _module.parameters() order and state_dict names, adopted from the caller; one workspace; all work on the caller's stream. */

@@ -158,6 +158,14 @@ def lib():
     L.ocrl_vae_ws_floats.restype = c_size_t
     L.ocrl_vae_fwd.argtypes = [p, POINTER(p), p, p, p, p] + [c_int] * 6 + [c_float, c_int, p, c_size_t, p]
     L.ocrl_vae_bwd.argtypes = [p, p, POINTER(p), p, p, POINTER(p)] + [c_int] * 6 + [c_float, c_int, p, c_size_t, p]
+    L.ocrl_probe_ws_floats.argtypes = [c_int] * 7 + [POINTER(c_int), c_int]
+    L.ocrl_probe_ws_floats.restype = c_size_t
+    L.ocrl_probe_fwd.argtypes = [p, POINTER(p), p, p, p, p, p] + [c_int] * 8 + [POINTER(c_int), c_float, c_int, POINTER(c_int), POINTER(c_int),
+                                 POINTER(c_int), p, c_size_t, p]
+    L.ocrl_probe_bwd.argtypes = [p, p, POINTER(p), POINTER(p)] + [c_int] * 7 + [POINTER(c_int), c_float, c_int, p, c_size_t, p]
+    L.ocrl_probe_match_ws_floats.argtypes = [c_int, c_int]
+    L.ocrl_probe_match_ws_floats.restype = c_size_t
+    L.ocrl_probe_match.argtypes = [p, c_int, c_longlong, p, p, p, p, p, p] + [c_int] * 6 + [POINTER(c_int)] * 3 + [p, c_size_t, p]
     L.ocrl_comm_unique_id.argtypes = [p, c_size_t]
     L.ocrl_comm_init.argtypes = [POINTER(p), c_int, c_int, p]
     L.ocrl_comm_allreduce.argtypes = [p, p, c_longlong, p]

@@ -169,6 +169,21 @@ int nc_conv_bwd_launch(NcBwdArgs a, hipStream_t st);      // dW partials of the 
 int nc_dw_reduce_launch(const NcReduceArgs& a, hipStream_t st);
 int nc_relu_mask_launch(const float* d, const float* act, float* out, long long n, hipStream_t st);
 
+// ------------------------------------------------------------------ probe.hip (slot property probe: include/ocrl_hip.h ocrl_probe_*)
+#define PROBE_MAX_SLOTS 12      // 2^K assignment states per image in LDS
+#define PROBE_MAX_PROPS 8
+#define PROBE_MAX_WIDTH 256     // head outputs per slot / state entries per object
+// property p reads targets from column t[p] (1 wide; 2 for xy) and head outputs [a[p], b[p]); kind: 0 = categorical, 1 = xy
+struct ProbeSchema { int P; int t[PROBE_MAX_PROPS], a[PROBE_MAX_PROPS], b[PROBE_MAX_PROPS], kind[PROBE_MAX_PROPS]; };
+int probe_schema_check(const ProbeSchema& sc, int T, int O);
+int probe_match_check(int B, int K, int N, int T, int O);
+// out[b, s, :] at b * ld_img + s * ld_row (dout alike; only its [K, O] entries are written).  part: [B, P + 2] scratch; metrics: [P + 2] =
+// loss, per property acc / R^2, mse_xy.  cost [B, N, K], col [B, N], dout and dloss (device scalar, absent = 1) may be null.
+int probe_match_launch(const float* out, int ld_row, long long ld_img, const float* y, const float* dloss, float* cost, int* col, float* part,
+                       float* metrics, float* dout, int B, int K, int N, int T, int O, const ProbeSchema& sc, hipStream_t st);
+int probe_leaky_fwd_launch(float* x, long long n, float slope, hipStream_t st);
+int probe_leaky_bwd_launch(float* dx, const float* h, long long n, float slope, hipStream_t st);
+
 // ------------------------------------------------------------------ vae.hip (VAE module: include/ocrl_hip.h ocrl_vae_*)
 // pack = 1: dst (NHWC side) <- src (NCHW side); 0: the reverse.  rows = 1: the C HW index runs over rows of R columns, else columns
 int vae_permute_launch(const float* src, float* dst, long long R, int C, int HW, int rows, int pack, hipStream_t st);

@@ -23,32 +23,40 @@ def _mask(shape_id, xx, yy, cx, cy, r):
     return dx * dx + dy * dy <= r * r   # circle
 
 
-def random_sprite_scenes(n, size, seed=0, num_objs=5, with_masks=False):
-    """-> uint8 [n, size, size, 3] (and float masks [n, num_objs+1, size, size, 1], background last)"""
+def random_sprite_scenes(n, size, seed=0, num_objs=5, with_masks=False, with_objs=False):
+    """-> uint8 [n, size, size, 3] (and float masks [n, num_objs+1, size, size, 1], background last; and, with_objs, the object
+    states [n, num_objs, 5] = colour index, shape index, scale index, x, y that the property probe reads, last).  The states are
+    recorded from the draws the scene makes anyway: the random stream, hence images and masks of a seed, do not depend on with_objs"""
     rs = np.random.RandomState(seed)
     lin = (np.arange(size) + 0.5) / size
     xx, yy = np.meshgrid(lin, lin)
     out = np.zeros((n, size, size, 3), dtype=np.uint8)
     masks = np.zeros((n, num_objs + 1, size, size, 1), dtype=np.float32) if with_masks else None
+    objs = np.zeros((n, num_objs, 5), dtype=np.float32) if with_objs else None
     for i in range(n):
         centres = [(0.5, 0.5)]
         vis = np.zeros((size, size), dtype=np.int32)     # 0 = background, k = object k (later objects occlude)
         for k in range(num_objs):
-            scale = SCALES[rs.randint(2)]
-            r = scale / 2
+            scale_id = rs.randint(2)
+            r = SCALES[scale_id] / 2
             for _ in range(1000):
                 cx, cy = rs.uniform(r + 0.08, 1 - r - 0.08, size=2)
                 if all((cx - px) ** 2 + (cy - py) ** 2 >= 0.15 ** 2 for px, py in centres):
                     break
             centres.append((cx, cy))
-            m = _mask(rs.randint(4), xx, yy, cx, cy, r)
-            out[i][m] = COLORS[rs.randint(4)]
+            shape_id = rs.randint(4)
+            m = _mask(shape_id, xx, yy, cx, cy, r)
+            color_id = rs.randint(4)
+            out[i][m] = COLORS[color_id]
             vis[m] = k + 1
+            if with_objs:
+                objs[i, k] = (color_id, shape_id, scale_id, cx, cy)
         if with_masks:
             for k in range(num_objs):
                 masks[i, k, :, :, 0] = vis == k + 1
             masks[i, num_objs, :, :, 0] = vis == 0
-    return (out, masks) if with_masks else out
+    res = (out,) + ((masks,) if with_masks else ()) + ((objs,) if with_objs else ())
+    return res if len(res) > 1 else out
 
 
 def scenes_to_obs(u8):

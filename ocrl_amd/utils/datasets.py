@@ -13,9 +13,9 @@ from .data import random_sprite_scenes
 
 
 class SyntheticScenes(Dataset):
-    def __init__(self, n, size, seed=0, with_masks=False, num_objs=5, raw_uint8=False):
+    def __init__(self, n, size, seed=0, with_masks=False, num_objs=5, raw_uint8=False, with_objs=False):
         self.n, self.size, self.seed, self.with_masks, self.num_objs = int(n), int(size), int(seed), bool(with_masks), num_objs
-        self.raw_uint8 = bool(raw_uint8)
+        self.raw_uint8, self.with_objs = bool(raw_uint8), bool(with_objs)
 
     def _obs(self, img):
         if self.raw_uint8:
@@ -27,6 +27,12 @@ class SyntheticScenes(Dataset):
 
     def __getitem__(self, index):
         s = (self.seed * 1000003 + index) & 0x7FFFFFFF
+        if self.with_objs:                                # "objs" [num_objs, 5], the key H5DataSet forwards from the reference's files
+            res = random_sprite_scenes(1, self.size, seed=s, num_objs=self.num_objs, with_masks=self.with_masks, with_objs=True)
+            sample = {**self._obs(res[0][0]), "objs": torch.from_numpy(res[-1][0])}
+            if self.with_masks:
+                sample["masks"] = torch.from_numpy(res[1][0])
+            return sample
         if self.with_masks:
             img, m = random_sprite_scenes(1, self.size, seed=s, num_objs=self.num_objs, with_masks=True)
             return {**self._obs(img[0]), "masks": torch.from_numpy(m[0])}
@@ -72,9 +78,11 @@ def get_dataloaders(config, batch_size, num_workers, rank=0, world=1, seed=0, ra
         f = h5py.File(datafile, "r")
         train, val = H5DataSet(f["TrainingSet"], raw_uint8), H5DataSet(f["ValidationSet"], raw_uint8)
     else:
-        wm = bool(config.get("with_masks", False))
-        train = SyntheticScenes(config.get("synthetic_train", 100000), config.obs_size, seed=seed * 2 + 1, with_masks=wm, raw_uint8=raw_uint8)
-        val = SyntheticScenes(config.get("synthetic_val", 1000), config.obs_size, seed=seed * 2 + 2, with_masks=wm, raw_uint8=raw_uint8)
+        wm, wo = bool(config.get("with_masks", False)), bool(config.get("with_objs", False))
+        train = SyntheticScenes(config.get("synthetic_train", 100000), config.obs_size, seed=seed * 2 + 1, with_masks=wm, raw_uint8=raw_uint8,
+                                with_objs=wo)
+        val = SyntheticScenes(config.get("synthetic_val", 1000), config.obs_size, seed=seed * 2 + 2, with_masks=wm, raw_uint8=raw_uint8,
+                              with_objs=wo)
     sampler = None
     if world > 1:
         from torch.utils.data.distributed import DistributedSampler
