@@ -351,7 +351,7 @@ int IodineModel::clip_adam(float lr, float clip, int step, float gscale, hipStre
     RC(grad_norm(st));
     const ParamInfo& skip = params_[index_.at("slot_init")];
     const long long a1 = skip.offset, b0 = skip.offset + ((skip.numel + 3) & ~3ll);
-    RC(clip_adam_launch(p_, g_, m_, v_, a1, metrics_ + 3, clip, lr, 0.9f, 0.999f, 1e-8f, step, gscale, st));
-    RC(clip_adam_launch(p_ + b0, g_ + b0, m_ + b0, v_ + b0, flat_size_ - b0, metrics_ + 3, clip, lr, 0.9f, 0.999f, 1e-8f, step, gscale, st));
+    RC(clip_adam_launch(p_, g_, m_, v_, a1, metrics_ + 3, clip, lr, 0.9, 0.999, 1e-8, step, gscale, st));
+    RC(clip_adam_launch(p_ + b0, g_ + b0, m_ + b0, v_ + b0, flat_size_ - b0, metrics_ + 3, clip, lr, 0.9, 0.999, 1e-8, step, gscale, st));
     return 0;
 }

@@ -3,41 +3,58 @@
 #include "common.h"
 #include "kernels.h"
 
-// part[blk] = max |g| over the block's grid-stride range
-__global__ __launch_bounds__(256) void absmax_kernel(const float* __restrict__ g, long long n4, float* __restrict__ part) {
-    __shared__ float red[4];
-    float m = 0.f;
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x) {
-        const float4 v = reinterpret_cast<const float4*>(g)[i];
-        m = fmaxf(m, fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w))));
-    }
-    m = wave_max(m);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
-    __syncthreads();
-    if (threadIdx.x == 0) part[blockIdx.x] = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-}
-__global__ void absmax_final_kernel(const float* __restrict__ part, int n, float* __restrict__ out) {
-    float m = 0.f;
-    for (int i = threadIdx.x; i < n; i += 64) m = fmaxf(m, part[i]);
-    m = wave_max(m);
-    if (threadIdx.x == 0) out[0] = m;
+// The inf-norm is reduced on the bit patterns of |g|: for non-negative floats the unsigned integer order is the float order, +inf
+// lies above every finite value and every NaN pattern above +inf, so the maximum is exact, independent of the order of the fold, and
+// a NaN anywhere in the buffer reaches the norm (fmaxf would drop it, and with it the sign of a diverged run in the log), as in
+// torch.nn.utils.clip_grad_norm_.
+__device__ inline unsigned abs_bits(float x) { return __float_as_uint(x) & 0x7FFFFFFFu; }
+__device__ inline unsigned wave_max_bits(unsigned v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = max(v, (unsigned)__shfl_xor((int)v, o, 64));
+    return v;
 }
 
-// g *= min(1, clip/(norm+1e-6)) (clip <= 0: no clipping); then the Adam update, all in one pass.
+// part[blk] = max |g| over the block's grid-stride range
+__global__ __launch_bounds__(256) void absmax_kernel(const float* __restrict__ g, long long n4, float* __restrict__ part) {
+    __shared__ unsigned red[4];
+    unsigned m = 0u;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x) {
+        const float4 v = reinterpret_cast<const float4*>(g)[i];
+        m = max(m, max(max(abs_bits(v.x), abs_bits(v.y)), max(abs_bits(v.z), abs_bits(v.w))));
+    }
+    m = wave_max_bits(m);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
+    __syncthreads();
+    if (threadIdx.x == 0) part[blockIdx.x] = __uint_as_float(max(max(red[0], red[1]), max(red[2], red[3])));
+}
+__global__ void absmax_final_kernel(const float* __restrict__ part, int n, float* __restrict__ out) {
+    unsigned m = 0u;
+    for (int i = threadIdx.x; i < n; i += 64) m = max(m, abs_bits(part[i]));
+    m = wave_max_bits(m);
+    if (threadIdx.x == 0) out[0] = __uint_as_float(m);
+}
+
+// g *= min(1, clip/(norm+1e-6)) (clip <= 0: no clipping); then the Adam update, all in one pass.  The min keeps a NaN quotient
+// (torch.clamp(max=1) does; fminf would return 1), so a NaN norm reaches every weight.  omb1 / omb2 are 1 - beta and bc1 /
+// bc2_sqrt the bias corrections, all computed in double from the decimal betas and rounded once: 1.f - 0.999f is 1.3e-5 away from
+// 0.001 (the rounding of 0.999f, small against 1, is 2^-14 of the difference), and 1 - 0.999f^t carries the same error at small t.
 __global__ __launch_bounds__(256) void clip_adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                        float* __restrict__ v, long long n4, const float* __restrict__ norm, float clip,
-                                                       float lr, float b1, float b2, float eps, float bc1, float bc2_sqrt, float gscale) {
+                                                       float lr, float omb1, float b2, float omb2, float eps, float bc1, float bc2_sqrt, float gscale) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n4) return;
     float coef = gscale;
-    if (clip > 0.f) coef *= fminf(1.0f, clip / (norm[0] * gscale + 1e-6f));
+    if (clip > 0.f) {
+        const float c = clip / (norm[0] * gscale + 1e-6f);
+        coef *= c > 1.0f ? 1.0f : c;
+    }
     const float4 gv = reinterpret_cast<const float4*>(g)[i];
     float4 mv = reinterpret_cast<float4*>(m)[i], vv = reinterpret_cast<float4*>(v)[i], pv = reinterpret_cast<float4*>(p)[i];
     const float step = lr / bc1;
     auto upd = [&](float gg, float& mm, float& vq, float& pp) {
         gg *= coef;
-        mm = mm + (gg - mm) * (1.f - b1);                  // exp_avg.lerp_(grad, 1 - beta1)
-        vq = vq * b2 + (1.f - b2) * gg * gg;
+        mm = mm + (gg - mm) * omb1;                        // exp_avg.lerp_(grad, 1 - beta1)
+        vq = vq * b2 + omb2 * gg * gg;
         const float denom = sqrtf(vq) / bc2_sqrt + eps;
         pp -= step * (mm / denom);
     };
@@ -57,12 +74,12 @@ int absmax_launch(const float* g, long long n, float* out, float* ws, size_t ws_
     OCRL_CHECK_LAUNCH("absmax_final");
     return 0;
 }
-int clip_adam_launch(float* p, const float* g, float* m, float* v, long long n, const float* norm, float clip, float lr, float b1,
-                     float b2, float eps, int step, float gscale, hipStream_t st) {
+int clip_adam_launch(float* p, const float* g, float* m, float* v, long long n, const float* norm, float clip, float lr, double b1,
+                     double b2, double eps, int step, float gscale, hipStream_t st) {
     OCRL_REQUIRE(n % 4 == 0 && step >= 1, "clip_adam: n %% 4 != 0 or step < 1");
-    const double bc1 = 1.0 - pow((double)b1, step), bc2 = 1.0 - pow((double)b2, step);
-    hipLaunchKernelGGL(clip_adam_kernel, dim3(cdiv(n / 4, 256)), dim3(256), 0, st, p, g, m, v, n / 4, norm, clip, lr, b1, b2, eps,
-                       (float)bc1, (float)sqrt(bc2), gscale);
+    const double bc1 = 1.0 - pow(b1, step), bc2 = 1.0 - pow(b2, step);      // from the decimal betas, as torch.optim.Adam does
+    hipLaunchKernelGGL(clip_adam_kernel, dim3(cdiv(n / 4, 256)), dim3(256), 0, st, p, g, m, v, n / 4, norm, clip, lr,
+                       (float)(1.0 - b1), (float)b2, (float)(1.0 - b2), (float)eps, (float)bc1, (float)sqrt(bc2), gscale);
     OCRL_CHECK_LAUNCH("clip_adam");
     return 0;
 }

@@ -1198,12 +1198,12 @@ int SlateModel::clip_adam(const float lr[3], float clip, int step, float gscale,
         for (const ParamInfo& q : params_)
             if (q.group == 1 && (q.name.rfind("_slotproj.", 0) == 0 || q.name.rfind("_dec.", 0) == 0) && q.offset < end) end = q.offset;
         const long long b0 = group_begin_[1];
-        return clip_adam_launch(p_ + b0, g_ + b0, m_ + b0, v_ + b0, end - b0, metrics_ + 3, clip, lr[1], 0.9f, 0.999f, 1e-8f, step, gscale, st);
+        return clip_adam_launch(p_ + b0, g_ + b0, m_ + b0, v_ + b0, end - b0, metrics_ + 3, clip, lr[1], 0.9, 0.999, 1e-8, step, gscale, st);
     }
     for (int g = 0; g < 3; ++g) {
         if (cfg.use_bcdec && g != 1) continue;      // parameters without gradients are skipped, as torch's Adam does
         const long long b0 = group_begin_[g], n = group_begin_[g + 1] - b0;
-        RC(clip_adam_launch(p_ + b0, g_ + b0, m_ + b0, v_ + b0, n, metrics_ + 3, clip, lr[g], 0.9f, 0.999f, 1e-8f, step, gscale, st));
+        RC(clip_adam_launch(p_ + b0, g_ + b0, m_ + b0, v_ + b0, n, metrics_ + 3, clip, lr[g], 0.9, 0.999, 1e-8, step, gscale, st));
     }
     return 0;
 }

@@ -178,7 +178,9 @@ def test_train_mode_dropout_parity(over):
 
 
 def test_update_steps_match_oracle():
-    """three full update() steps (clip + Adam, schedules) against the oracle trainer"""
+    """three full update() steps (clip + Adam, schedules) against the oracle trainer: a whole-path smoke check.  At these warm-up
+    learning rates (lr_enc <= 1e-8, lr_dec <= 3e-8) the bars do not constrain groups 1 and 2; the optimiser's own parity is in
+    tests/test_gpu_optimizer.py"""
     cfg = O.default_cfg(**SMALL)
     B = 2
     P = O.formula_params(cfg)
