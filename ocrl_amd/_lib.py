@@ -186,3 +186,14 @@ def check(rc):
 def ptr(t):
     """device pointer of a torch tensor (or None)"""
     return None if t is None else ctypes.c_void_p(t.data_ptr())
+
+
+def ptrs(ts):
+    """array of the device pointers of a list of tensors (a None entry stays a null pointer)"""
+    return (ctypes.c_void_p * len(ts))(*[t.data_ptr() if t is not None else None for t in ts])
+
+
+def stream(device=None):
+    """torch's current stream on `device` (None: the current device), as the library's `void* stream` argument"""
+    import torch
+    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)

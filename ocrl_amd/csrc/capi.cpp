@@ -17,17 +17,53 @@ void ocrl_set_error(const char* fmt, ...) {
     va_end(ap);
 }
 
-struct ocrl_slate {
-    SlateModel* m;
+template <class M>
+struct Handle {
+    using Model = M;
+    M* m = nullptr;
 };
-
-struct ocrl_iodine {
-    IodineModel* m;
-};
+struct ocrl_slate : Handle<SlateModel> {};
+struct ocrl_iodine : Handle<IodineModel> {};
 
 #define ST(s) static_cast<hipStream_t>(s)
 #define GUARD(h) \
     if (!(h) || !(h)->m) { ocrl_set_error("null handle"); return 1; }
+
+// ---- the part of a stateful model's ABI that is the same for every model (ModelBase), over the handle type
+template <class H, class C>
+static int h_create(const C& k, H** out) {
+    H* h = new (std::nothrow) H;
+    if (!h) { ocrl_set_error("out of memory"); return 1; }
+    h->m = new (std::nothrow) typename H::Model(k);
+    if (!h->m) { delete h; ocrl_set_error("out of memory"); return 1; }
+    *out = h;
+    return 0;
+}
+template <class H>
+static void h_destroy(H* h) {
+    if (!h) return;
+    delete h->m;
+    delete h;
+}
+template <class H> static int h_param_count(const H* h) { return (h && h->m) ? (int)h->m->params().size() : -1; }
+template <class H>
+static int h_param_info(const H* h, int i, char* name, int name_cap, int shape[4], int* ndim, long long* offset, long long* numel, int* group) {
+    GUARD(h);
+    if (i < 0 || i >= (int)h->m->params().size()) { ocrl_set_error("param index out of range"); return 1; }
+    const ParamInfo& p = h->m->params()[i];
+    if (name && name_cap > 0) { strncpy(name, p.name.c_str(), name_cap - 1); name[name_cap - 1] = 0; }
+    if (shape) for (int k = 0; k < 4; ++k) shape[k] = p.shape[k];
+    if (ndim) *ndim = p.ndim;
+    if (offset) *offset = p.offset;
+    if (numel) *numel = p.numel;
+    if (group) *group = p.group;
+    return 0;
+}
+template <class H> static long long h_flat_size(const H* h) { return (h && h->m) ? h->m->flat_size() : -1; }
+template <class H> static size_t h_workspace_bytes(const H* h) { return (h && h->m) ? h->m->workspace_bytes() : 0; }
+template <class H> static int h_bind(H* h, float* p, float* g, float* m, float* v, void* ws, size_t n) { GUARD(h); return h->m->bind(p, g, m, v, ws, n); }
+template <class H> static float* h_metrics(const H* h) { return (h && h->m) ? h->m->metrics() : nullptr; }
+template <class H> static int h_tensor(const H* h, const char* name, float** ptr, long long* count) { GUARD(h); return h->m->tensor(name, ptr, count); }
 
 extern "C" {
 
@@ -59,36 +95,18 @@ int ocrl_slate_create(const ocrl_slate_config* c, ocrl_slate** out) {
         return 1;
     }
     if (k.use_bcdec && (c->num_slots > 16 || c->obs_size < 5)) { ocrl_set_error("ocrl_slate_create: broadcast decoder needs num_slots <= 16 and obs_size >= 5"); return 1; }
-    ocrl_slate* h = new (std::nothrow) ocrl_slate;
-    if (!h) { ocrl_set_error("out of memory"); return 1; }
-    h->m = new (std::nothrow) SlateModel(k);
-    if (!h->m) { delete h; ocrl_set_error("out of memory"); return 1; }
-    *out = h;
-    return 0;
+    return h_create(k, out);
 }
-void ocrl_slate_destroy(ocrl_slate* h) {
-    if (!h) return;
-    delete h->m;
-    delete h;
-}
-int ocrl_slate_param_count(const ocrl_slate* h) { return (h && h->m) ? (int)h->m->params().size() : -1; }
+void ocrl_slate_destroy(ocrl_slate* h) { h_destroy(h); }
+int ocrl_slate_param_count(const ocrl_slate* h) { return h_param_count(h); }
 int ocrl_slate_param_info(const ocrl_slate* h, int i, char* name, int name_cap, int shape[4], int* ndim, long long* offset,
                           long long* numel, int* group) {
-    GUARD(h);
-    if (i < 0 || i >= (int)h->m->params().size()) { ocrl_set_error("param index out of range"); return 1; }
-    const ParamInfo& p = h->m->params()[i];
-    if (name && name_cap > 0) { strncpy(name, p.name.c_str(), name_cap - 1); name[name_cap - 1] = 0; }
-    if (shape) for (int k = 0; k < 4; ++k) shape[k] = p.shape[k];
-    if (ndim) *ndim = p.ndim;
-    if (offset) *offset = p.offset;
-    if (numel) *numel = p.numel;
-    if (group) *group = p.group;
-    return 0;
+    return h_param_info(h, i, name, name_cap, shape, ndim, offset, numel, group);
 }
-long long ocrl_slate_flat_size(const ocrl_slate* h) { return (h && h->m) ? h->m->flat_size() : -1; }
+long long ocrl_slate_flat_size(const ocrl_slate* h) { return h_flat_size(h); }
 long long ocrl_slate_group_begin(const ocrl_slate* h, int g) { return (h && h->m && g >= 0 && g <= 3) ? h->m->group_begin(g) : -1; }
-size_t ocrl_slate_workspace_bytes(const ocrl_slate* h) { return (h && h->m) ? h->m->workspace_bytes() : 0; }
-int ocrl_slate_bind(ocrl_slate* h, float* p, float* g, float* m, float* v, void* ws, size_t n) { GUARD(h); return h->m->bind(p, g, m, v, ws, n); }
+size_t ocrl_slate_workspace_bytes(const ocrl_slate* h) { return h_workspace_bytes(h); }
+int ocrl_slate_bind(ocrl_slate* h, float* p, float* g, float* m, float* v, void* ws, size_t n) { return h_bind(h, p, g, m, v, ws, n); }
 
 int ocrl_slate_forward(ocrl_slate* h, const float* obs, int B, float tau, int train, unsigned long long seed, const float* nz,
                        const float* nzh, const float* ns, void* stream) {
@@ -112,8 +130,8 @@ int ocrl_slate_clip_adam(ocrl_slate* h, const float lr[3], float clip, int step,
     return h->m->clip_adam(lr, clip, step, gscale, ST(stream));
 }
 int ocrl_slate_grad_norm(ocrl_slate* h, void* stream) { GUARD(h); return h->m->grad_norm(ST(stream)); }
-float* ocrl_slate_metrics(const ocrl_slate* h) { return (h && h->m) ? h->m->metrics() : nullptr; }
-int ocrl_slate_tensor(const ocrl_slate* h, const char* name, float** ptr, long long* count) { GUARD(h); return h->m->tensor(name, ptr, count); }
+float* ocrl_slate_metrics(const ocrl_slate* h) { return h_metrics(h); }
+int ocrl_slate_tensor(const ocrl_slate* h, const char* name, float** ptr, long long* count) { return h_tensor(h, name, ptr, count); }
 int ocrl_slate_soft_z(ocrl_slate* h, void* stream) { GUARD(h); return h->m->soft_z(ST(stream)); }
 int ocrl_slate_dropout_mask(const ocrl_slate* h, unsigned site, long long n, float* out, void* stream) {
     GUARD(h);
@@ -263,33 +281,16 @@ int ocrl_iodine_create(const ocrl_iodine_config* c, ocrl_iodine** out) {
     k.obs_size = c->obs_size; k.obs_channels = c->obs_channels; k.slot_size = c->slot_size; k.num_iters = c->num_iterations;
     k.num_slots = c->num_slots; k.sigma = c->sigma; k.beta = c->beta; k.layer_norm = c->layer_norm; k.ref_mlp_hidden = c->ref_mlp_hidden;
     k.max_batch = c->max_batch;
-    ocrl_iodine* h = new (std::nothrow) ocrl_iodine;
-    if (!h) { ocrl_set_error("out of memory"); return 1; }
-    h->m = new (std::nothrow) IodineModel(k);
-    if (!h->m) { delete h; ocrl_set_error("out of memory"); return 1; }
-    *out = h;
-    return 0;
+    return h_create(k, out);
 }
-void ocrl_iodine_destroy(ocrl_iodine* h) {
-    if (!h) return;
-    delete h->m;
-    delete h;
-}
-int ocrl_iodine_param_count(const ocrl_iodine* h) { return (h && h->m) ? (int)h->m->params().size() : -1; }
+void ocrl_iodine_destroy(ocrl_iodine* h) { h_destroy(h); }
+int ocrl_iodine_param_count(const ocrl_iodine* h) { return h_param_count(h); }
 int ocrl_iodine_param_info(const ocrl_iodine* h, int i, char* name, int name_cap, int shape[4], int* ndim, long long* offset, long long* numel) {
-    GUARD(h);
-    if (i < 0 || i >= (int)h->m->params().size()) { ocrl_set_error("param index out of range"); return 1; }
-    const ParamInfo& p = h->m->params()[i];
-    if (name && name_cap > 0) { strncpy(name, p.name.c_str(), name_cap - 1); name[name_cap - 1] = 0; }
-    if (shape) for (int k = 0; k < 4; ++k) shape[k] = p.shape[k];
-    if (ndim) *ndim = p.ndim;
-    if (offset) *offset = p.offset;
-    if (numel) *numel = p.numel;
-    return 0;
+    return h_param_info(h, i, name, name_cap, shape, ndim, offset, numel, nullptr);       // one optimiser group: no `group` out-parameter
 }
-long long ocrl_iodine_flat_size(const ocrl_iodine* h) { return (h && h->m) ? h->m->flat_size() : -1; }
-size_t ocrl_iodine_workspace_bytes(const ocrl_iodine* h) { return (h && h->m) ? h->m->workspace_bytes() : 0; }
-int ocrl_iodine_bind(ocrl_iodine* h, float* p, float* g, float* m, float* v, void* ws, size_t n) { GUARD(h); return h->m->bind(p, g, m, v, ws, n); }
+long long ocrl_iodine_flat_size(const ocrl_iodine* h) { return h_flat_size(h); }
+size_t ocrl_iodine_workspace_bytes(const ocrl_iodine* h) { return h_workspace_bytes(h); }
+int ocrl_iodine_bind(ocrl_iodine* h, float* p, float* g, float* m, float* v, void* ws, size_t n) { return h_bind(h, p, g, m, v, ws, n); }
 int ocrl_iodine_forward(ocrl_iodine* h, const float* obs, int B, unsigned long long seed, const float* noise, void* stream) {
     GUARD(h);
     return h->m->forward(obs, B, seed, noise, ST(stream));
@@ -300,6 +301,6 @@ int ocrl_iodine_clip_adam(ocrl_iodine* h, float lr, float clip, int step, float 
     return h->m->clip_adam(lr, clip, step, gscale, ST(stream));
 }
 int ocrl_iodine_grad_norm(ocrl_iodine* h, void* stream) { GUARD(h); return h->m->grad_norm(ST(stream)); }
-float* ocrl_iodine_metrics(const ocrl_iodine* h) { return (h && h->m) ? h->m->metrics() : nullptr; }
-int ocrl_iodine_tensor(const ocrl_iodine* h, const char* name, float** ptr, long long* count) { GUARD(h); return h->m->tensor(name, ptr, count); }
+float* ocrl_iodine_metrics(const ocrl_iodine* h) { return h_metrics(h); }
+int ocrl_iodine_tensor(const ocrl_iodine* h, const char* name, float** ptr, long long* count) { return h_tensor(h, name, ptr, count); }
 }  // extern "C"

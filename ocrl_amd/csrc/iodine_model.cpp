@@ -25,44 +25,26 @@ IodineModel::IodineModel(const IodineConfig& c) : cfg(c) {
     for (int l = 1; l <= 4; ++l) rs_[l] = (rs_[l - 1] - 1) / 2 + 1;
     ldc_[0] = (9 * 17 + 3) & ~3;
     ldc_[1] = ldc_[2] = ldc_[3] = 9 * 64;
-    auto add = [&](const std::string& name, std::vector<int> shp) {
-        ParamInfo p;
-        p.name = name; p.ndim = (int)shp.size(); p.group = 0; p.numel = 1;
-        for (size_t i = 0; i < shp.size(); ++i) { p.shape[i] = shp[i]; p.numel *= shp[i]; }
-        params_.push_back(p);
-    };
     // order = the reference module's parameters() order (own Parameters first, then refine, then decoder)
-    add("slot_mean_init", {1, 1, L}); add("slot_logsig_init", {1, 1, L}); add("slot_init", {1, 1, L});
-    for (int l = 0; l < 4; ++l) { add(ifmt("refine.mlc.layers.%d.weight", l), {64, l ? 64 : 17, 3, 3}); add(ifmt("refine.mlc.layers.%d.bias", l), {64}); }
-    add("refine.mlp.layers.0.weight", {Hm, 64}); add("refine.mlp.layers.0.bias", {Hm});
-    add("refine.lstm.weight_ih", {4 * Hm, XW}); add("refine.lstm.weight_hh", {4 * Hm, Hm});
-    add("refine.lstm.bias_ih", {4 * Hm}); add("refine.lstm.bias_hh", {4 * Hm});
-    add("refine.mean_update.weight", {L, Hm}); add("refine.mean_update.bias", {L});
-    add("refine.logsig_update.weight", {L, Hm}); add("refine.logsig_update.bias", {L});
-    for (int l = 0; l < 4; ++l) { add(ifmt("decoder.mlc.layers.%d.weight", l), {64, l ? 64 : L + 2, 3, 3}); add(ifmt("decoder.mlc.layers.%d.bias", l), {64}); }
-    add("decoder.conv.weight", {4, 64, 3, 3}); add("decoder.conv.bias", {4});
-    long long off = 0;
-    for (size_t i = 0; i < params_.size(); ++i) {
-        params_[i].offset = off;
-        index_[params_[i].name] = (int)i;
-        off += (params_[i].numel + 3) & ~3ll;
+    add_param("slot_mean_init", {1, 1, L}); add_param("slot_logsig_init", {1, 1, L}); add_param("slot_init", {1, 1, L});
+    for (int l = 0; l < 4; ++l) {
+        add_param(ifmt("refine.mlc.layers.%d.weight", l), {64, l ? 64 : 17, 3, 3}); add_param(ifmt("refine.mlc.layers.%d.bias", l), {64});
     }
-    flat_size_ = off;
-    ws_ = nullptr;
+    add_param("refine.mlp.layers.0.weight", {Hm, 64}); add_param("refine.mlp.layers.0.bias", {Hm});
+    add_param("refine.lstm.weight_ih", {4 * Hm, XW}); add_param("refine.lstm.weight_hh", {4 * Hm, Hm});
+    add_param("refine.lstm.bias_ih", {4 * Hm}); add_param("refine.lstm.bias_hh", {4 * Hm});
+    add_param("refine.mean_update.weight", {L, Hm}); add_param("refine.mean_update.bias", {L});
+    add_param("refine.logsig_update.weight", {L, Hm}); add_param("refine.logsig_update.bias", {L});
+    for (int l = 0; l < 4; ++l) {
+        add_param(ifmt("decoder.mlc.layers.%d.weight", l), {64, l ? 64 : L + 2, 3, 3}); add_param(ifmt("decoder.mlc.layers.%d.bias", l), {64});
+    }
+    add_param("decoder.conv.weight", {4, 64, 3, 3}); add_param("decoder.conv.bias", {4});
+    finish_params();
     layout_workspace(false);
 }
 
-float* IodineModel::carve(const char* name, size_t n) {
-    const size_t bytes = (n * 4 + 255) & ~(size_t)255;
-    float* p = reinterpret_cast<float*>(ws_ + ws_off_);
-    ws_off_ += bytes;
-    if (ws_commit_ && name) named_[name] = std::make_pair(p, n);
-    return p;
-}
-
 void IodineModel::layout_workspace(bool commit) {
-    ws_commit_ = commit;
-    ws_off_ = 0;
+    begin_layout(commit);
     const size_t BK = (size_t)Bmax * K, BKN = BK * N;
     metrics_ = carve("metrics", 64);
     parts_ = carve("parts", (size_t)I * 4 + 4);
@@ -119,36 +101,18 @@ void IodineModel::layout_workspace(bool commit) {
     denc_ = carve(nullptr, BKN * 17); dout4_ = carve(nullptr, BKN * 4); gA_ = carve(nullptr, BKN * 64); gB_ = carve(nullptr, BKN * 64);
     G1_ = carve(nullptr, (size_t)N * 64); dW1r_ = carve(nullptr, (size_t)576 * L);
     masks_ = carve("masks", BKN); recon_ = carve("recon", (size_t)Bmax * 3 * N); rmasked_ = carve("recons_masked", BKN * 3);
-    if (!commit) ws_bytes_ = ws_off_ + 4096;
+    end_layout();
 }
 
 int IodineModel::bind(float* p, float* g, float* m, float* v, void* ws, size_t ws_bytes) {
-    OCRL_REQUIRE(p && g && ws, "bind: null buffer");
-    OCRL_REQUIRE(ws_bytes >= ws_bytes_, "bind: workspace too small (%zu < %zu)", ws_bytes, ws_bytes_);
-    OCRL_REQUIRE(((uintptr_t)p & 255) == 0 && ((uintptr_t)g & 255) == 0 && ((uintptr_t)ws & 255) == 0, "bind: buffers must be 256-byte aligned");
+    RC(check_buffers(p, g, ws, ws_bytes));
     OCRL_REQUIRE(cfg.obs_channels == 3 && S % 16 == 0 && S >= 16 && L % 4 == 0 && L >= 4 && L <= 256 && Hm % 64 == 0 && K >= 1 && K <= 16 && I >= 1,
                  "iodine: unsupported configuration (obs_size %% 16, slot_size %% 4, mlp hidden %% 64, 1..16 slots)");
-    p_ = p; g_ = g; m_ = m; v_ = v;
-    ws_ = static_cast<char*>(ws);
-    named_.clear();
+    adopt_buffers(p, g, m, v, ws);
     layout_workspace(true);
     RC(fill_launch(zero_state_, (long long)Bmax * K * Hm, 0.f, 0));
     OCRL_HIP(hipDeviceSynchronize());
     have_fwd_ = false;
-    return 0;
-}
-
-int IodineModel::tensor(const char* name, float** ptr, long long* count) const {
-    auto it = named_.find(name);
-    if (it == named_.end()) {
-        auto pi = index_.find(name);
-        OCRL_REQUIRE(pi != index_.end(), "tensor: unknown name '%s'", name);
-        *ptr = p_ + params_[pi->second].offset;
-        *count = params_[pi->second].numel;
-        return 0;
-    }
-    *ptr = it->second.first;
-    *count = (long long)it->second.second;
     return 0;
 }
 
@@ -349,8 +313,8 @@ int IodineModel::grad_norm(hipStream_t st) { return io_l2norm_launch(g_, flat_si
 int IodineModel::clip_adam(float lr, float clip, int step, float gscale, hipStream_t st) {
     OCRL_REQUIRE(m_ && v_, "clip_adam: optimiser state not bound");
     RC(grad_norm(st));
-    const ParamInfo& skip = params_[index_.at("slot_init")];
-    const long long a1 = skip.offset, b0 = skip.offset + ((skip.numel + 3) & ~3ll);
+    const ParamInfo& skip = param("slot_init");
+    const long long a1 = skip.offset, b0 = skip.offset + padded(skip.numel);
     RC(clip_adam_launch(p_, g_, m_, v_, a1, metrics_ + 3, clip, lr, 0.9, 0.999, 1e-8, step, gscale, st));
     RC(clip_adam_launch(p_ + b0, g_ + b0, m_ + b0, v_ + b0, flat_size_ - b0, metrics_ + 3, clip, lr, 0.9, 0.999, 1e-8, step, gscale, st));
     return 0;

@@ -1,12 +1,11 @@
 // IODINE training-step orchestration over the HIP kernels (host code): reference ocrs/iodine/iodine_module.py:79-252 and
 // ocrs/base.py:60-74.  One object per process per GPU; not thread-safe; every launch goes to the caller's stream.
 #pragma once
-#include <map>
 #include <string>
 #include <vector>
 
 #include "kernels.h"
-#include "slate_model.h"      // ParamInfo
+#include "model_base.h"
 
 struct IodineConfig {
     int obs_size = 64, obs_channels = 3, slot_size = 64, num_iters = 5, num_slots = 7;
@@ -16,42 +15,25 @@ struct IodineConfig {
     int max_batch = 1;
 };
 
-class IodineModel {
+class IodineModel : public ModelBase {
 public:
     explicit IodineModel(const IodineConfig& c);
-    const std::vector<ParamInfo>& params() const { return params_; }
-    long long flat_size() const { return flat_size_; }
-    size_t workspace_bytes() const { return ws_bytes_; }
     int bind(float* p, float* g, float* m, float* v, void* ws, size_t ws_bytes);
     // obs [B,3,S,S] NCHW; noise: optional injected N(0,1) draws [I,B,K,L] (else the device RNG stream `seed`)
     int forward(const float* obs, int B, unsigned long long seed, const float* noise, hipStream_t st);
     int backward(hipStream_t st);
     int grad_norm(hipStream_t st);                                       // metrics()[3] = ||g||_2
     int clip_adam(float lr, float clip, int step, float gscale, hipStream_t st);
-    float* metrics() const { return metrics_; }                          // device float[8]: loss, mse, kld, grad norm
-    int tensor(const char* name, float** ptr, long long* count) const;
+    // metrics(): loss, mse, kld, grad norm
     const IodineConfig cfg;
 
 private:
-    float* P(const std::string& n) const { return p_ + params_[index_.at(n)].offset; }
-    float* G(const std::string& n) const { return g_ + params_[index_.at(n)].offset; }
-    float* carve(const char* name, size_t n);
     void layout_workspace(bool commit);
     int pack_weights(hipStream_t st);
     int decoder_fwd(int i, hipStream_t st);
     int decoder_bwd(int i, const float* dout4, bool weights, hipStream_t st);      // -> dslots_
     int refine_fwd(int i, hipStream_t st);
     int refine_bwd(int i, hipStream_t st);                                         // -> denc_, dxin_ (latent part)
-
-    std::vector<ParamInfo> params_;
-    std::map<std::string, int> index_;
-    long long flat_size_ = 0;
-    float *p_ = nullptr, *g_ = nullptr, *m_ = nullptr, *v_ = nullptr;
-    char* ws_ = nullptr;
-    size_t ws_bytes_ = 0, ws_off_ = 0;
-    bool ws_commit_ = false;
-    std::map<std::string, std::pair<float*, size_t>> named_;
-    float* metrics_ = nullptr;
 
     int S, N, K, I, L, Hm, Bmax, XW;          // XW = Hm + 4L (LSTM input width)
     int rs_[5];                               // spatial side of the refinement feature maps: S, S/2, ...

@@ -26,77 +26,61 @@ SlateModel::SlateModel(const SlateConfig& c) : cfg(c) {
     K = c.num_slots; I = c.num_iters; D = c.slot_size; H = c.mlp_hidden; NB = c.num_blocks; NH = c.num_heads;
     DH = d / NH; Bmax = c.max_batch; SH = c.slot_heads > 0 ? c.slot_heads : 1;
     const int ch = c.obs_channels;
-    auto add = [&](const std::string& name, std::vector<int> shp, int g) {
-        ParamInfo p;
-        p.name = name; p.ndim = (int)shp.size(); p.group = g; p.numel = 1;
-        for (size_t i = 0; i < shp.size(); ++i) { p.shape[i] = shp[i]; p.numel *= shp[i]; }
-        params_.push_back(p);
-    };
     // group 0: dVAE (ocrs/common/models.py:10-37) — order = reference module.parameters() order
-    add("_dvae._encoder.0.m.weight", {64, ch, 4, 4}, 0); add("_dvae._encoder.0.m.bias", {64}, 0);
-    for (int i = 1; i < 7; ++i) { add(fmt("_dvae._encoder.%d.m.weight", i), {64, 64, 1, 1}, 0); add(fmt("_dvae._encoder.%d.m.bias", i), {64}, 0); }
-    add("_dvae._encoder.7.weight", {V, 64, 1, 1}, 0); add("_dvae._encoder.7.bias", {V}, 0);
+    add_param("_dvae._encoder.0.m.weight", {64, ch, 4, 4}, 0); add_param("_dvae._encoder.0.m.bias", {64}, 0);
+    for (int i = 1; i < 7; ++i) { add_param(fmt("_dvae._encoder.%d.m.weight", i), {64, 64, 1, 1}, 0); add_param(fmt("_dvae._encoder.%d.m.bias", i), {64}, 0); }
+    add_param("_dvae._encoder.7.weight", {V, 64, 1, 1}, 0); add_param("_dvae._encoder.7.bias", {V}, 0);
     const int di[9] = {0, 1, 2, 3, 4, 6, 7, 8, 9};
     const int dshape[9][4] = {{64, V, 1, 1}, {64, 64, 3, 3}, {64, 64, 1, 1}, {64, 64, 1, 1}, {256, 64, 1, 1},
                               {64, 64, 3, 3}, {64, 64, 1, 1}, {64, 64, 1, 1}, {256, 64, 1, 1}};
     for (int i = 0; i < 9; ++i) {
-        add(fmt("_dvae._decoder.%d.m.weight", di[i]), {dshape[i][0], dshape[i][1], dshape[i][2], dshape[i][3]}, 0);
-        add(fmt("_dvae._decoder.%d.m.bias", di[i]), {dshape[i][0]}, 0);
+        add_param(fmt("_dvae._decoder.%d.m.weight", di[i]), {dshape[i][0], dshape[i][1], dshape[i][2], dshape[i][3]}, 0);
+        add_param(fmt("_dvae._decoder.%d.m.bias", di[i]), {dshape[i][0]}, 0);
     }
-    add("_dvae._decoder.11.weight", {ch, 64, 1, 1}, 0); add("_dvae._decoder.11.bias", {ch}, 0);
+    add_param("_dvae._decoder.11.weight", {ch, 64, 1, 1}, 0); add_param("_dvae._decoder.11.bias", {ch}, 0);
     // group 1
-    add("_enc._encoder.0.m.weight", {C, ch, 5, 5}, 1); add("_enc._encoder.0.m.bias", {C}, 1);
-    for (int i = 1; i < 3; ++i) { add(fmt("_enc._encoder.%d.m.weight", i), {C, C, 5, 5}, 1); add(fmt("_enc._encoder.%d.m.bias", i), {C}, 1); }
-    add("_enc._encoder.3.weight", {C, C, 5, 5}, 1); add("_enc._encoder.3.bias", {C}, 1);
-    add("_enc_pos.channels_map.weight", {C, 4, 1, 1}, 1); add("_enc_pos.channels_map.bias", {C}, 1);
-    add("_slotattn.slot_mu", {1, 1, D}, 1); add("_slotattn.slot_log_sigma", {1, 1, D}, 1);
-    add("_slotattn.layer_norm.weight", {C}, 1); add("_slotattn.layer_norm.bias", {C}, 1);
-    add("_slotattn.mlp.0.weight", {C, C}, 1); add("_slotattn.mlp.0.bias", {C}, 1);
-    add("_slotattn.mlp.2.weight", {C, C}, 1); add("_slotattn.mlp.2.bias", {C}, 1);
+    add_param("_enc._encoder.0.m.weight", {C, ch, 5, 5}, 1); add_param("_enc._encoder.0.m.bias", {C}, 1);
+    for (int i = 1; i < 3; ++i) { add_param(fmt("_enc._encoder.%d.m.weight", i), {C, C, 5, 5}, 1); add_param(fmt("_enc._encoder.%d.m.bias", i), {C}, 1); }
+    add_param("_enc._encoder.3.weight", {C, C, 5, 5}, 1); add_param("_enc._encoder.3.bias", {C}, 1);
+    add_param("_enc_pos.channels_map.weight", {C, 4, 1, 1}, 1); add_param("_enc_pos.channels_map.bias", {C}, 1);
+    add_param("_slotattn.slot_mu", {1, 1, D}, 1); add_param("_slotattn.slot_log_sigma", {1, 1, D}, 1);
+    add_param("_slotattn.layer_norm.weight", {C}, 1); add_param("_slotattn.layer_norm.bias", {C}, 1);
+    add_param("_slotattn.mlp.0.weight", {C, C}, 1); add_param("_slotattn.mlp.0.bias", {C}, 1);
+    add_param("_slotattn.mlp.2.weight", {C, C}, 1); add_param("_slotattn.mlp.2.bias", {C}, 1);
     const std::string sa = "_slotattn.slot_attention.";
-    add(sa + "norm_inputs.weight", {C}, 1); add(sa + "norm_inputs.bias", {C}, 1);
-    add(sa + "norm_slots.weight", {D}, 1); add(sa + "norm_slots.bias", {D}, 1);
-    add(sa + "norm_mlp.weight", {D}, 1); add(sa + "norm_mlp.bias", {D}, 1);
-    add(sa + "project_q.weight", {D, D}, 1); add(sa + "project_k.weight", {D, C}, 1); add(sa + "project_v.weight", {D, C}, 1);
-    add(sa + "gru.weight_ih", {3 * D, D}, 1); add(sa + "gru.weight_hh", {3 * D, D}, 1);
-    add(sa + "gru.bias_ih", {3 * D}, 1); add(sa + "gru.bias_hh", {3 * D}, 1);
-    add(sa + "mlp.0.weight", {H, D}, 1); add(sa + "mlp.0.bias", {H}, 1);
-    add(sa + "mlp.2.weight", {D, H}, 1); add(sa + "mlp.2.bias", {D}, 1);
-    add("_slotproj.weight", {d, D}, 1);
+    add_param(sa + "norm_inputs.weight", {C}, 1); add_param(sa + "norm_inputs.bias", {C}, 1);
+    add_param(sa + "norm_slots.weight", {D}, 1); add_param(sa + "norm_slots.bias", {D}, 1);
+    add_param(sa + "norm_mlp.weight", {D}, 1); add_param(sa + "norm_mlp.bias", {D}, 1);
+    add_param(sa + "project_q.weight", {D, D}, 1); add_param(sa + "project_k.weight", {D, C}, 1); add_param(sa + "project_v.weight", {D, C}, 1);
+    add_param(sa + "gru.weight_ih", {3 * D, D}, 1); add_param(sa + "gru.weight_hh", {3 * D, D}, 1);
+    add_param(sa + "gru.bias_ih", {3 * D}, 1); add_param(sa + "gru.bias_hh", {3 * D}, 1);
+    add_param(sa + "mlp.0.weight", {H, D}, 1); add_param(sa + "mlp.0.bias", {H}, 1);
+    add_param(sa + "mlp.2.weight", {D, H}, 1); add_param(sa + "mlp.2.bias", {D}, 1);
+    add_param("_slotproj.weight", {d, D}, 1);
     if (c.use_bcdec) {      // ocrs/common/models.py:110-126, appended to the slot-attention group (slate_module.py:96-103)
-        add("_dec._decoder.0.m.weight", {C, D, 5, 5}, 1); add("_dec._decoder.0.m.bias", {C}, 1);
-        for (int i = 1; i < 3; ++i) { add(fmt("_dec._decoder.%d.m.weight", i), {C, C, 5, 5}, 1); add(fmt("_dec._decoder.%d.m.bias", i), {C}, 1); }
-        add("_dec._decoder.3.weight", {ch + 1, C, 3, 3}, 1); add("_dec._decoder.3.bias", {ch + 1}, 1);
-        add("_dec._pos_emb.channels_map.weight", {D, 4, 1, 1}, 1); add("_dec._pos_emb.channels_map.bias", {D}, 1);
+        add_param("_dec._decoder.0.m.weight", {C, D, 5, 5}, 1); add_param("_dec._decoder.0.m.bias", {C}, 1);
+        for (int i = 1; i < 3; ++i) { add_param(fmt("_dec._decoder.%d.m.weight", i), {C, C, 5, 5}, 1); add_param(fmt("_dec._decoder.%d.m.bias", i), {C}, 1); }
+        add_param("_dec._decoder.3.weight", {ch + 1, C, 3, 3}, 1); add_param("_dec._decoder.3.bias", {ch + 1}, 1);
+        add_param("_dec._pos_emb.channels_map.weight", {D, 4, 1, 1}, 1); add_param("_dec._pos_emb.channels_map.bias", {D}, 1);
     }
     // group 2
-    add("_dict.dictionary.weight", {V, d}, 2);
-    add("_bos_token._bos_token", {1, 1, d}, 2);
-    add("_z_pos.pe", {1, 1 + T, d}, 2);
+    add_param("_dict.dictionary.weight", {V, d}, 2);
+    add_param("_bos_token._bos_token", {1, 1, d}, 2);
+    add_param("_z_pos.pe", {1, 1 + T, d}, 2);
     for (int b = 0; b < NB; ++b) {
         const std::string p = fmt("_tfdec.blocks.%d.", b);
-        add(p + "self_attn_layer_norm.weight", {d}, 2); add(p + "self_attn_layer_norm.bias", {d}, 2);
-        for (const char* q : {"q", "k", "v", "o"}) add(p + "self_attn.proj_" + q + ".weight", {d, d}, 2);
-        add(p + "encoder_decoder_attn_layer_norm.weight", {d}, 2); add(p + "encoder_decoder_attn_layer_norm.bias", {d}, 2);
-        for (const char* q : {"q", "k", "v", "o"}) add(p + "encoder_decoder_attn.proj_" + q + ".weight", {d, d}, 2);
-        add(p + "ffn_layer_norm.weight", {d}, 2); add(p + "ffn_layer_norm.bias", {d}, 2);
-        add(p + "ffn.0.weight", {4 * d, d}, 2); add(p + "ffn.0.bias", {4 * d}, 2);
-        add(p + "ffn.2.weight", {d, 4 * d}, 2); add(p + "ffn.2.bias", {d}, 2);
+        add_param(p + "self_attn_layer_norm.weight", {d}, 2); add_param(p + "self_attn_layer_norm.bias", {d}, 2);
+        for (const char* q : {"q", "k", "v", "o"}) add_param(p + "self_attn.proj_" + q + ".weight", {d, d}, 2);
+        add_param(p + "encoder_decoder_attn_layer_norm.weight", {d}, 2); add_param(p + "encoder_decoder_attn_layer_norm.bias", {d}, 2);
+        for (const char* q : {"q", "k", "v", "o"}) add_param(p + "encoder_decoder_attn.proj_" + q + ".weight", {d, d}, 2);
+        add_param(p + "ffn_layer_norm.weight", {d}, 2); add_param(p + "ffn_layer_norm.bias", {d}, 2);
+        add_param(p + "ffn.0.weight", {4 * d, d}, 2); add_param(p + "ffn.0.bias", {4 * d}, 2);
+        add_param(p + "ffn.2.weight", {d, 4 * d}, 2); add_param(p + "ffn.2.bias", {d}, 2);
     }
-    add("_tfdec.layer_norm.weight", {d}, 2); add("_tfdec.layer_norm.bias", {d}, 2);
-    add("_out.weight", {V, d}, 2);
+    add_param("_tfdec.layer_norm.weight", {d}, 2); add_param("_tfdec.layer_norm.bias", {d}, 2);
+    add_param("_out.weight", {V, d}, 2);
 
-    long long off = 0;
-    int g = 0;
-    group_begin_[0] = 0;
-    for (size_t i = 0; i < params_.size(); ++i) {
-        while (g < params_[i].group) group_begin_[++g] = off;
-        params_[i].offset = off;
-        off += (params_[i].numel + 3) & ~3ll;       // keep every tensor 16-byte aligned (float4 / MFMA staging)
-        index_[params_[i].name] = (int)i;
-    }
-    while (g < 3) group_begin_[++g] = off;
-    flat_size_ = off;
+    finish_params(group_begin_, 3);
     blk_.resize(NB);
     layout_workspace(false);
 }
@@ -113,20 +97,8 @@ SlateModel::~SlateModel() {
     if (cap_) (void)hipStreamDestroy(cap_);
 }
 
-float* SlateModel::P(const std::string& n) const { return p_ + params_[index_.at(n)].offset; }
-float* SlateModel::G(const std::string& n) const { return g_ + params_[index_.at(n)].offset; }
-
-float* SlateModel::carve(const char* name, size_t n) {
-    const size_t bytes = (n * 4 + 255) & ~(size_t)255;
-    float* p = reinterpret_cast<float*>(ws_ + ws_off_);
-    ws_off_ += bytes;
-    if (ws_commit_ && name) named_[name] = std::make_pair(p, n);
-    return p;
-}
-
 void SlateModel::layout_workspace(bool commit) {
-    ws_commit_ = commit;
-    ws_off_ = 0;
+    begin_layout(commit);
     x3_of_.clear();
     const size_t B = Bmax, BT = B * T, BN = B * N, BK = B * K;
     metrics_ = carve("metrics", 64);
@@ -243,12 +215,12 @@ void SlateModel::layout_workspace(bool commit) {
     bg_.resize(NB);
     {   // folded cross attention (xattn.hip)
         const size_t NC = xattn_supported(K, d, NH) ? (size_t)NH * xattn_kp(K, NH) : 16;
-        xa_zero_base_ = reinterpret_cast<float*>(ws_ + ws_off_);
+        xa_zero_base_ = carve_pos();
         for (int b = 0; b < NB; ++b) {
             Blk& k = blk_[b];
             k.xaAb = carve(nullptr, B * NC * d); k.xaAbT = carve(nullptr, B * NC * d); k.xaVo = carve(nullptr, B * NC * d); k.xaVoT = carve(nullptr, B * NC * d);
         }
-        xa_zero_floats_ = (size_t)(reinterpret_cast<float*>(ws_ + ws_off_) - xa_zero_base_);
+        xa_zero_floats_ = (size_t)(carve_pos() - xa_zero_base_);
         for (int b = 0; b < NB; ++b) { bg_[b].xaPd = carve(nullptr, BT * NC); bg_[b].xaDs = carve(nullptr, BT * NC); }
         xa_dAb_ = carve(nullptr, B * NC * d); xa_dVo_ = carve(nullptr, B * NC * d);
         xa_pq_ = carve(nullptr, B * (size_t)d * d); xa_po_ = carve(nullptr, B * (size_t)d * d);
@@ -272,20 +244,16 @@ void SlateModel::layout_workspace(bool commit) {
         const int ldc0 = (25 * cfg.obs_channels + 3) & ~3;
         col0_ = carve(nullptr, BN * ldc0); dw0p_ = carve(nullptr, (size_t)64 * ldc0);
     }
-    if (!commit) ws_bytes_ = ws_off_ + 4096;
+    end_layout();
 }
 
 int SlateModel::bind(float* p, float* g, float* m, float* v, void* ws, size_t ws_bytes) {
-    OCRL_REQUIRE(p && g && ws, "bind: null buffer");
-    OCRL_REQUIRE(ws_bytes >= ws_bytes_, "bind: workspace too small (%zu < %zu)", ws_bytes, ws_bytes_);
-    OCRL_REQUIRE(((uintptr_t)p & 255) == 0 && ((uintptr_t)g & 255) == 0 && ((uintptr_t)ws & 255) == 0, "bind: buffers must be 256-byte aligned");
+    RC(check_buffers(p, g, ws, ws_bytes));
     OCRL_REQUIRE(d % 64 == 0 && d <= 256 && D % 64 == 0 && C == 64 && V % 256 == 0 && S % 4 == 0 && d % NH == 0 && DH % 4 == 0 && DH <= 64,
                  "unsupported configuration (d_model/slot_size multiples of 64 <= 256, cnn hidden 64, vocab %% 256, obs_size %% 4)");
     OCRL_REQUIRE(cfg.obs_channels == 3, "obs_channels must be 3");
     OCRL_REQUIRE(T % 4 == 0, "obs_size/4 squared must be a multiple of 4");
-    p_ = p; g_ = g; m_ = m; v_ = v;
-    ws_ = static_cast<char*>(ws);
-    named_.clear();
+    adopt_buffers(p, g, m, v, ws);
     clear_encode_graphs();       // captured against the old buffers
     packs_valid_ = false;
     layout_workspace(true);
@@ -351,20 +319,6 @@ int SlateModel::bind(float* p, float* g, float* m, float* v, void* ws, size_t ws
     OCRL_HIP(hipMemcpy(sa_pack_dev_, ent.data(), ent.size() * sizeof(PackEntry), hipMemcpyHostToDevice));
     OCRL_HIP(hipDeviceSynchronize());
     have_fwd_ = false;
-    return 0;
-}
-
-int SlateModel::tensor(const char* name, float** ptr, long long* count) const {
-    auto it = named_.find(name);
-    if (it == named_.end()) {
-        auto pi = index_.find(name);
-        OCRL_REQUIRE(pi != index_.end(), "tensor: unknown name '%s'", name);
-        *ptr = p_ + params_[pi->second].offset;
-        *count = params_[pi->second].numel;
-        return 0;
-    }
-    *ptr = it->second.first;
-    *count = (long long)it->second.second;
     return 0;
 }
 

@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "kernels.h"
+#include "model_base.h"
 
 struct SlateConfig {
     int obs_size = 64, obs_channels = 3, vocab = 4096, d_model = 192, cnn_hidden = 64;
@@ -16,15 +17,6 @@ struct SlateConfig {
     int use_bcdec = 0;      // Slot-Attention configuration: spatial-broadcast decoder instead of dVAE + transformer
     int hard = 0;           // ocr_config.hard: straight-through Gumbel sample for the dVAE decoder (utils.py:81-83)
     int slot_heads = 1;     // ocr_config.slotattr.num_slot_heads (ocrs/common/slot_attn.py:28)
-};
-
-struct ParamInfo {
-    std::string name;
-    int shape[4] = {1, 1, 1, 1};
-    int ndim = 1;
-    long long numel = 0;
-    long long offset = 0;   // element offset into the flat parameter buffer (16-byte aligned)
-    int group = 0;          // optimiser group: 0 dvae, 1 slot-attention side, 2 transformer decoder
 };
 
 struct StepInputs {
@@ -39,16 +31,11 @@ struct StepInputs {
     const unsigned long long* seed_dev = nullptr;   // internal: the slot-noise seed read from device memory (captured encode graphs)
 };
 
-class SlateModel {
+class SlateModel : public ModelBase {
 public:
     explicit SlateModel(const SlateConfig& c);
     ~SlateModel();
-    SlateModel(const SlateModel&) = delete;
-    SlateModel& operator=(const SlateModel&) = delete;
-    const std::vector<ParamInfo>& params() const { return params_; }
-    long long flat_size() const { return flat_size_; }
     long long group_begin(int g) const { return group_begin_[g]; }   // group g = [begin(g), begin(g+1))
-    size_t workspace_bytes() const { return ws_bytes_; }
     int bind(float* p, float* g, float* m, float* v, void* ws, size_t ws_bytes);
     int forward(const StepInputs& in, hipStream_t st);          // loss terms -> metrics()
     int backward(hipStream_t st);                               // fills the flat gradient buffer
@@ -59,8 +46,7 @@ public:
     int generate(hipStream_t st);                               // greedy autoregressive image from the last step's slots
     int clip_adam(const float lr[3], float clip, int step, float gscale, hipStream_t st);
     int grad_norm(hipStream_t st);                              // metrics()[3] = max |g|
-    float* metrics() const { return metrics_; }                 // device float[8]: dvae_mse, ce, loss, grad absmax
-    int tensor(const char* name, float** ptr, long long* count) const;
+    // metrics(): dvae_mse, ce, loss, grad absmax
     int dropout_mask(unsigned site, long long n, float* out, hipStream_t st) const;
     // writes the soft sample z = softmax(scores) of the last forward into the named tensor "z" (the fused heads keep only the scores;
     // valid between forward and backward -- the backward builds d logits in place of the scores)
@@ -68,9 +54,6 @@ public:
     const SlateConfig cfg;
 
 private:
-    float* P(const std::string& n) const;
-    float* G(const std::string& n) const;
-    float* carve(const char* name, size_t n);
     void layout_workspace(bool commit);
     // the Linear helpers of gemm.hip with this step's dropout seed and the current scratch (lin_bwd_x is used as it is)
     int lin_fwd(const float* x, int ldx, const float* W, const float* b, float* y, int ldy, long long M, int N, int K, int relu,
@@ -99,16 +82,7 @@ private:
     int fwd_bcdec(hipStream_t st);
     int bwd_bcdec(hipStream_t st);
 
-    std::vector<ParamInfo> params_;
-    std::map<std::string, int> index_;
-    long long flat_size_ = 0;
     long long group_begin_[4] = {0, 0, 0, 0};
-    float *p_ = nullptr, *g_ = nullptr, *m_ = nullptr, *v_ = nullptr;
-    char* ws_ = nullptr;
-    size_t ws_bytes_ = 0, ws_off_ = 0;
-    bool ws_commit_ = false;
-    std::map<std::string, std::pair<float*, size_t>> named_;
-    float* metrics_ = nullptr;
 
     // dims
     int S, E, T, N, V, d, C, K, I, D, H, NB, NH, DH, Bmax;

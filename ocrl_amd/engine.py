@@ -1,4 +1,4 @@
-"""SlateEngine — owns the C handle, the flat parameter / gradient / Adam buffers (torch-allocated,
+"""SlateEngine / IodineEngine — own the C handle, the flat parameter / gradient / Adam buffers (torch-allocated,
 adopted by the library) and the workspace.  Host-side plumbing only; all arithmetic is in HIP."""
 import ctypes
 from types import SimpleNamespace
@@ -18,10 +18,55 @@ def _aligned_empty(nbytes, device):
     return raw[off:off + nbytes]
 
 
-class SlateEngine:
+def param_table(L, prefix, h, with_group):
+    """The parameter table a handle publishes, in the reference module's parameters() order: one
+    SimpleNamespace(name, shape, offset, numel, group) per tensor.  `with_group`: ocrl_<prefix>_param_info has the `group`
+    out-parameter (a model with one optimiser group has none, and every entry gets group 0)."""
+    count, info = getattr(L, f"ocrl_{prefix}_param_count"), getattr(L, f"ocrl_{prefix}_param_info")
+    name = ctypes.create_string_buffer(256)
+    shape = (ctypes.c_int * 4)()
+    nd, off, ne, grp = ctypes.c_int(), ctypes.c_longlong(), ctypes.c_longlong(), ctypes.c_int()
+    tail = (ctypes.byref(grp),) if with_group else ()
+    out = []
+    for i in range(count(h)):
+        _lib.check(info(h, i, name, 256, ctypes.byref(shape), ctypes.byref(nd), ctypes.byref(off), ctypes.byref(ne), *tail))
+        out.append(SimpleNamespace(name=name.value.decode(), shape=tuple(shape[k] for k in range(nd.value)), offset=off.value,
+                                   numel=ne.value, group=grp.value))
+    return out
+
+
+class Engine:
+    """What the stateful handles (include/ocrl_hip.h: ocrl_slate_*, ocrl_iodine_*) have in common: the handle, its parameter
+    table, the flat parameter / gradient / Adam buffers and the workspace it adopts, and views into them.  A subclass names its
+    `prefix`, builds its config struct and adds its own calls."""
+    prefix = None           # ocrl_<prefix>_* is this engine's part of the ABI
+    has_groups = False      # the parameter table carries optimiser groups
+
+    @staticmethod
+    def config(dims, max_batch):
+        """the model's config struct (_lib.*Config) for `dims`"""
+        raise NotImplementedError
+
+    def _fn(self, name):
+        return getattr(self.L, f"ocrl_{self.prefix}_{name}")
+
+    @classmethod
+    def _create(cls, L, dims, max_batch):
+        c, h = cls.config(dims, max_batch), ctypes.c_void_p()
+        _lib.check(getattr(L, f"ocrl_{cls.prefix}_create")(ctypes.byref(c), ctypes.byref(h)))
+        return h
+
+    @classmethod
+    def param_spec(cls, dims):
+        """the parameter table for `dims`, read from a one-image handle (creating one needs no GPU)"""
+        L = _lib.lib()
+        h = cls._create(L, dims, 1)
+        try:
+            return param_table(L, cls.prefix, h, cls.has_groups)
+        finally:
+            getattr(L, f"ocrl_{cls.prefix}_destroy")(h)
+
     def __init__(self, dims, max_batch, device="cuda:0", with_optimizer=True):
-        """dims: namespace with obs_size, obs_channels, vocab_size, d_model, cnn_hidden, num_slots,
-        num_iterations, slot_size, mlp_hidden, num_dec_blocks, num_dec_heads, dropout."""
         dev = torch.device(device)
         if dev.type != "cuda":
             raise RuntimeError(f"ocrl_amd runs on an AMD GPU only (device={device!r}); there is no CPU path")
@@ -31,40 +76,24 @@ class SlateEngine:
         self.device = dev
         self.dims = dims
         self.max_batch = int(max_batch)
-        c = _lib.SlateConfig(dims.obs_size, dims.obs_channels, dims.vocab_size, dims.d_model, dims.cnn_hidden, dims.num_slots,
-                             dims.num_iterations, dims.slot_size, dims.mlp_hidden, dims.num_dec_blocks, dims.num_dec_heads,
-                             float(dims.dropout), self.max_batch, int(bool(getattr(dims, "use_bcdec", False))),
-                             int(bool(getattr(dims, "hard", False))), int(getattr(dims, "num_slot_heads", 1)))
-        h = ctypes.c_void_p()
-        _lib.check(self.L.ocrl_slate_create(ctypes.byref(c), ctypes.byref(h)))
-        self.h = h
-        self.params = []          # list of SimpleNamespace(name, shape, offset, numel, group)
-        name = ctypes.create_string_buffer(256)
-        shape = (ctypes.c_int * 4)()
-        nd, off, ne, grp = ctypes.c_int(), ctypes.c_longlong(), ctypes.c_longlong(), ctypes.c_int()
-        for i in range(self.L.ocrl_slate_param_count(h)):
-            _lib.check(self.L.ocrl_slate_param_info(h, i, name, 256, ctypes.byref(shape), ctypes.byref(nd), ctypes.byref(off),
-                                                    ctypes.byref(ne), ctypes.byref(grp)))
-            self.params.append(SimpleNamespace(name=name.value.decode(), shape=tuple(shape[k] for k in range(nd.value)),
-                                               offset=off.value, numel=ne.value, group=grp.value))
-        self.flat_size = self.L.ocrl_slate_flat_size(h)
-        self.group_begin = [self.L.ocrl_slate_group_begin(h, g) for g in range(4)]
+        self.h = h = self._create(self.L, dims, self.max_batch)
+        self.params = param_table(self.L, self.prefix, h, self.has_groups)
+        self.flat_size = self._fn("flat_size")(h)
         with torch.cuda.device(dev):
             mk = lambda: _aligned_empty(self.flat_size * 4, dev).view(torch.float32).zero_()
             self.flat_p, self.flat_g = mk(), mk()
             self.flat_m, self.flat_v = (mk(), mk()) if with_optimizer else (None, None)
-            self.ws_bytes = self.L.ocrl_slate_workspace_bytes(h)
+            self.ws_bytes = self._fn("workspace_bytes")(h)
             self.ws = _aligned_empty(self.ws_bytes, dev)
-            _lib.check(self.L.ocrl_slate_bind(h, _lib.ptr(self.flat_p), _lib.ptr(self.flat_g), _lib.ptr(self.flat_m), _lib.ptr(self.flat_v),
-                                              _lib.ptr(self.ws), self.ws_bytes))
-        mp = self.L.ocrl_slate_metrics(h)
-        self.metrics = self._view(mp, 8, torch.float32)
+            _lib.check(self._fn("bind")(h, _lib.ptr(self.flat_p), _lib.ptr(self.flat_g), _lib.ptr(self.flat_m), _lib.ptr(self.flat_v),
+                                        _lib.ptr(self.ws), self.ws_bytes))
+        self.metrics = self._view(self._fn("metrics")(h), 8, torch.float32)
         self.adam_step = 0
 
     def __del__(self):
         try:
             if getattr(self, "h", None):
-                self.L.ocrl_slate_destroy(self.h)
+                self._fn("destroy")(self.h)
                 self.h = None
         except Exception:
             pass
@@ -87,10 +116,8 @@ class SlateEngine:
         return self.view(self.flat_g, p)
 
     def tensor(self, name, shape, dtype=torch.float32):
-        if name == "z":      # the soft sample is not a by-product of the step (fused soft-max heads): written on request
-            _lib.check(self.L.ocrl_slate_soft_z(self.h, self.stream))
         p, n = ctypes.c_void_p(), ctypes.c_longlong()
-        _lib.check(self.L.ocrl_slate_tensor(self.h, name.encode(), ctypes.byref(p), ctypes.byref(n)))
+        _lib.check(self._fn("tensor")(self.h, name.encode(), ctypes.byref(p), ctypes.byref(n)))
         cnt = 1
         for s in shape:
             cnt *= s
@@ -99,7 +126,38 @@ class SlateEngine:
 
     @property
     def stream(self):
-        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        return _lib.stream(self.device)
+
+    # ---- step pieces every model has (forward and clip_adam differ in their arguments)
+    def backward(self):
+        _lib.check(self._fn("backward")(self.h, self.stream))
+
+    def grad_norm(self):
+        _lib.check(self._fn("grad_norm")(self.h, self.stream))
+        return self.metrics[3]
+
+
+class SlateEngine(Engine):
+    """dims: namespace with obs_size, obs_channels, vocab_size, d_model, cnn_hidden, num_slots,
+    num_iterations, slot_size, mlp_hidden, num_dec_blocks, num_dec_heads, dropout."""
+    prefix = "slate"
+    has_groups = True
+
+    @staticmethod
+    def config(dims, max_batch):
+        return _lib.SlateConfig(dims.obs_size, dims.obs_channels, dims.vocab_size, dims.d_model, dims.cnn_hidden, dims.num_slots,
+                                dims.num_iterations, dims.slot_size, dims.mlp_hidden, dims.num_dec_blocks, dims.num_dec_heads,
+                                float(dims.dropout), max_batch, int(bool(getattr(dims, "use_bcdec", False))),
+                                int(bool(getattr(dims, "hard", False))), int(getattr(dims, "num_slot_heads", 1)))
+
+    def __init__(self, dims, max_batch, device="cuda:0", with_optimizer=True):
+        super().__init__(dims, max_batch, device, with_optimizer)
+        self.group_begin = [self.L.ocrl_slate_group_begin(self.h, g) for g in range(4)]
+
+    def tensor(self, name, shape, dtype=torch.float32):
+        if name == "z":      # the soft sample is not a by-product of the step (fused soft-max heads): written on request
+            _lib.check(self.L.ocrl_slate_soft_z(self.h, self.stream))
+        return super().tensor(name, shape, dtype)
 
     # ---- step pieces
     def forward(self, obs, tau, train, seed, noise=None):
@@ -114,9 +172,6 @@ class SlateEngine:
         _lib.check(self.L.ocrl_slate_forward(self.h, _lib.ptr(obs), obs.shape[0], float(tau), int(bool(train)), int(seed),
                                              _lib.ptr(nz), _lib.ptr(nzh), _lib.ptr(ns), self.stream))
         return self.metrics
-
-    def backward(self):
-        _lib.check(self.L.ocrl_slate_backward(self.h, self.stream))
 
     def generate(self):
         _lib.check(self.L.ocrl_slate_generate(self.h, self.stream))
@@ -142,10 +197,6 @@ class SlateEngine:
         _lib.check(self.L.ocrl_slate_clip_adam(self.h, ctypes.byref(arr), float(clip if clip is not None else 0.0), self.adam_step,
                                                float(grad_scale), self.stream))
 
-    def grad_norm(self):
-        _lib.check(self.L.ocrl_slate_grad_norm(self.h, self.stream))
-        return self.metrics[3]
-
     def dropout_mask(self, site, shape):
         n = 1
         for s in shape:
@@ -155,67 +206,14 @@ class SlateEngine:
         return out.view(shape)
 
 
-class IodineEngine:
-    """Same role as SlateEngine for the IODINE handle (include/ocrl_hip.h: ocrl_iodine_*)."""
+class IodineEngine(Engine):
+    """dims: namespace with obs_size, obs_channels, slot_size, num_iterations, num_slots, sigma, beta, layer_norm, ref_mlp_hidden."""
+    prefix = "iodine"
 
-    def __init__(self, dims, max_batch, device="cuda:0", with_optimizer=True):
-        """dims: namespace with obs_size, obs_channels, slot_size, num_iterations, num_slots, sigma, beta, layer_norm, ref_mlp_hidden."""
-        dev = torch.device(device)
-        if dev.type != "cuda":
-            raise RuntimeError(f"ocrl_amd runs on an AMD GPU only (device={device!r}); there is no CPU path")
-        if not torch.cuda.is_available():
-            raise RuntimeError("ocrl_amd: no GPU visible to PyTorch-ROCm")
-        self.L = _lib.lib()
-        self.device = dev
-        self.dims = dims
-        self.max_batch = int(max_batch)
-        c = _lib.IodineConfig(dims.obs_size, dims.obs_channels, dims.slot_size, dims.num_iterations, dims.num_slots, float(dims.sigma),
-                              float(dims.beta), int(bool(dims.layer_norm)), dims.ref_mlp_hidden, self.max_batch)
-        h = ctypes.c_void_p()
-        _lib.check(self.L.ocrl_iodine_create(ctypes.byref(c), ctypes.byref(h)))
-        self.h = h
-        self.params = []
-        name = ctypes.create_string_buffer(256)
-        shape = (ctypes.c_int * 4)()
-        nd, off, ne = ctypes.c_int(), ctypes.c_longlong(), ctypes.c_longlong()
-        for i in range(self.L.ocrl_iodine_param_count(h)):
-            _lib.check(self.L.ocrl_iodine_param_info(h, i, name, 256, ctypes.byref(shape), ctypes.byref(nd), ctypes.byref(off), ctypes.byref(ne)))
-            self.params.append(SimpleNamespace(name=name.value.decode(), shape=tuple(shape[k] for k in range(nd.value)), offset=off.value,
-                                               numel=ne.value, group=0))
-        self.flat_size = self.L.ocrl_iodine_flat_size(h)
-        with torch.cuda.device(dev):
-            mk = lambda: _aligned_empty(self.flat_size * 4, dev).view(torch.float32).zero_()
-            self.flat_p, self.flat_g = mk(), mk()
-            self.flat_m, self.flat_v = (mk(), mk()) if with_optimizer else (None, None)
-            self.ws_bytes = self.L.ocrl_iodine_workspace_bytes(h)
-            self.ws = _aligned_empty(self.ws_bytes, dev)
-            _lib.check(self.L.ocrl_iodine_bind(h, _lib.ptr(self.flat_p), _lib.ptr(self.flat_g), _lib.ptr(self.flat_m), _lib.ptr(self.flat_v),
-                                               _lib.ptr(self.ws), self.ws_bytes))
-        self.metrics = self._view(self.L.ocrl_iodine_metrics(h), 8, torch.float32)
-        self.adam_step = 0
-
-    def __del__(self):
-        try:
-            if getattr(self, "h", None):
-                self.L.ocrl_iodine_destroy(self.h)
-                self.h = None
-        except Exception:
-            pass
-
-    _view = SlateEngine._view
-    view = SlateEngine.view
-    param = SlateEngine.param
-    grad = SlateEngine.grad
-    stream = SlateEngine.stream
-
-    def tensor(self, name, shape, dtype=torch.float32):
-        p, n = ctypes.c_void_p(), ctypes.c_longlong()
-        _lib.check(self.L.ocrl_iodine_tensor(self.h, name.encode(), ctypes.byref(p), ctypes.byref(n)))
-        cnt = 1
-        for s in shape:
-            cnt *= s
-        assert cnt <= n.value, (name, shape, n.value)
-        return self._view(p.value, cnt, dtype).view(shape)
+    @staticmethod
+    def config(dims, max_batch):
+        return _lib.IodineConfig(dims.obs_size, dims.obs_channels, dims.slot_size, dims.num_iterations, dims.num_slots, float(dims.sigma),
+                                 float(dims.beta), int(bool(dims.layer_norm)), dims.ref_mlp_hidden, max_batch)
 
     def forward(self, obs, seed, noise=None):
         """obs [B,3,S,S] fp32 contiguous on device; noise: optional [I,B,K,L] N(0,1) draws."""
@@ -225,14 +223,7 @@ class IodineEngine:
         _lib.check(self.L.ocrl_iodine_forward(self.h, _lib.ptr(obs), obs.shape[0], int(seed), _lib.ptr(noise), self.stream))
         return self.metrics
 
-    def backward(self):
-        _lib.check(self.L.ocrl_iodine_backward(self.h, self.stream))
-
     def clip_adam(self, lr, clip, grad_scale=1.0):
         self.adam_step += 1
         _lib.check(self.L.ocrl_iodine_clip_adam(self.h, float(lr), float(clip if clip is not None else 0.0), self.adam_step, float(grad_scale),
                                                 self.stream))
-
-    def grad_norm(self):
-        _lib.check(self.L.ocrl_iodine_grad_norm(self.h, self.stream))
-        return self.metrics[3]

@@ -13,7 +13,8 @@ from torch import nn
 from ..dist_utils import allreduce_grads_
 from ..engine import IodineEngine
 from .base import Base
-from .slate import FusedAdam, _Holder
+from .flat_module import FlatParamModule
+from .slate import FusedAdam
 
 
 def _dims(ocr_config, env_config):
@@ -43,7 +44,10 @@ def _reference_init_(name, t):
     return t          # biases are filled once the matching weight's fan-in is known (see Iodine_Module.__init__)
 
 
-class Iodine_Module(nn.Module):
+class Iodine_Module(FlatParamModule):
+    engine_cls = IodineEngine
+    backend = "Iodine"
+
     def __init__(self, ocr_config, env_config):
         super().__init__()
         self._dims = _dims(ocr_config, env_config)
@@ -54,8 +58,7 @@ class Iodine_Module(nn.Module):
         self.beta, self.sigma = self._dims.beta, self._dims.sigma
         self.use_layernorm = self._dims.layer_norm
         self.rep_dim = self.slot_size
-        from .. import _lib
-        self._spec = self._query_spec(_lib)
+        self._spec = self._query_spec()
         fan = {}
         for p in self._spec:
             t = _reference_init_(p.name, torch.empty(p.shape))
@@ -65,84 +68,11 @@ class Iodine_Module(nn.Module):
                 k = 1.0 / math.sqrt(fan[p.name[:-len("bias")]])
                 nn.init.uniform_(t, -k, k)
             self._register(p.name, nn.Parameter(t))
-        self.engine = None
-        self._max_batch = 0
-        self._seed = 0
-        self._step_seed = 0
-        self._injected_noise = None
 
-    def _query_spec(self, _lib):
-        import ctypes
-        L = _lib.lib()
-        d = self._dims
-        c = _lib.IodineConfig(d.obs_size, d.obs_channels, d.slot_size, d.num_iterations, d.num_slots, d.sigma, d.beta, int(d.layer_norm),
-                              d.ref_mlp_hidden, 1)
-        h = ctypes.c_void_p()
-        _lib.check(L.ocrl_iodine_create(ctypes.byref(c), ctypes.byref(h)))
-        out = []
-        name = ctypes.create_string_buffer(256)
-        shape = (ctypes.c_int * 4)()
-        nd, off, ne = ctypes.c_int(), ctypes.c_longlong(), ctypes.c_longlong()
-        for i in range(L.ocrl_iodine_param_count(h)):
-            _lib.check(L.ocrl_iodine_param_info(h, i, name, 256, ctypes.byref(shape), ctypes.byref(nd), ctypes.byref(off), ctypes.byref(ne)))
-            out.append(SimpleNamespace(name=name.value.decode(), shape=tuple(shape[k] for k in range(nd.value))))
-        L.ocrl_iodine_destroy(h)
-        return out
-
-    def _get(self, path):
-        node = self
-        for part in path.split("."):
-            if part not in node._modules:
-                node.add_module(part, _Holder())
-            node = node._modules[part]
-        return node
-
-    def _register(self, name, param):
-        path, leaf = name.rsplit(".", 1) if "." in name else ("", name)
-        (self._get(path) if path else self).register_parameter(leaf, param)
-
-    # ---- device placement: parameters become views of the library's flat buffer
-    def to(self, device):
-        dev = torch.device(device)
-        if dev.type != "cuda":
-            raise RuntimeError(f"ocrl_amd Iodine runs on an AMD GPU only (got device={device!r}); there is no CPU path")
-        self._device = dev
-        self._ensure_engine(max(self._max_batch, 1))
-        return self
-
-    def _ensure_engine(self, batch):
-        if self.engine is not None and batch <= self._max_batch:
-            return
-        old = self.engine
-        eng = IodineEngine(self._dims, max_batch=batch, device=self._device)
-        named = dict(self.named_parameters())
-        for p in eng.params:
-            eng.view(eng.flat_p, p).copy_(named[p.name].data.to(eng.device))
-        if old is not None:
-            eng.flat_m.copy_(old.flat_m)
-            eng.flat_v.copy_(old.flat_v)
-            eng.adam_step = old.adam_step
-        for p in eng.params:
-            named[p.name].data = eng.view(eng.flat_p, p)
-            named[p.name].grad = eng.view(eng.flat_g, p) if p.name != "slot_init" else None     # never receives a gradient (iodine_module.py:76-78)
-        self.engine = eng
-        self._max_batch = batch
-        pending, self._pending_opt = getattr(self, "_pending_opt", None), None
-        if pending is not None:       # optimiser state loaded before .to(device)
-            pending[0].load_state_dict(pending[1])
-        torch.cuda.synchronize(eng.device)
-
-    def _need(self, obs):
-        if getattr(self, "_device", None) is None:
-            raise RuntimeError("call .to('cuda:N') before using the HIP backend")
-        if not obs.is_cuda:
-            raise RuntimeError("ocrl_amd: observations must live on the GPU (to_device(batch, device))")
-        self._ensure_engine(obs.shape[0])
-        return obs.contiguous().float()
-
-    def set_seed(self, seed: int) -> None:
-        self._seed = int(seed)
-        self._step_seed = 0
+    def _grad_view(self, eng, p):
+        if p.name == "slot_init":       # never receives a gradient (iodine_module.py:76-78): .grad stays None
+            return None
+        return super()._grad_view(eng, p)
 
     def inject_noise(self, eps):
         """parity hook: [I,B,K,L] N(0,1) draws consumed by the next _forward (the reference's per-iteration rsample)"""

@@ -8,7 +8,6 @@ checkpoints load unchanged, and SB3's ``ortho_init`` finds the layers.  The cont
 
 Differences from the reference: ``get_loss(obs, with_rep=True)`` without ``use_cnn_feat`` returns the representation
 (the reference reads a non-existent ``self._nets``), and the observation gets no gradient (``obs.requires_grad`` raises)."""
-import ctypes
 from types import SimpleNamespace
 
 import torch
@@ -79,8 +78,8 @@ def _encode(obs, dims, params, save):
         out = torch.empty(B, rep, device=obs.device, dtype=torch.float32)
     else:
         out = torch.empty(B, groups, rep, device=obs.device, dtype=torch.float32)
-    arr = (ctypes.c_void_p * len(params))(*[p.data_ptr() for p in params])
-    st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    arr = _lib.ptrs(params)
+    st = _lib.stream()
     _lib.check(L.ocrl_naturecnn_fwd(_lib.ptr(obs), arr, _lib.ptr(out), B, H, W, C, groups, feat, use_feat, rep, int(save), _lib.ptr(ws), n, st))
     return out, ws
 
@@ -104,9 +103,9 @@ class _NatureCNNFn(torch.autograd.Function):
         B, C, H, W = obs.shape
         dout = dout.contiguous().float()
         gs = [torch.empty_like(p) for p in ps]
-        arr = (ctypes.c_void_p * len(ps))(*[p.data_ptr() for p in ps])
-        garr = (ctypes.c_void_p * len(gs))(*[g.data_ptr() for g in gs])
-        st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+        arr = _lib.ptrs(ps)
+        garr = _lib.ptrs(gs)
+        st = _lib.stream()
         _lib.check(L.ocrl_naturecnn_bwd(_lib.ptr(obs), _lib.ptr(dout), arr, garr, B, H, W, C, groups, feat, use_feat, rep,
                                         _lib.ptr(ctx.ws), ctx.ws.numel(), st))
         return (None, None, *gs)

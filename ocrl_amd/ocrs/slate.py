@@ -14,6 +14,7 @@ from torch import nn
 from ..dist_utils import allreduce_grads_
 from ..engine import SlateEngine
 from .base import Base
+from .flat_module import FlatParamModule
 
 
 # schedules: ocrs/common/utils.py:37-65
@@ -95,11 +96,10 @@ def reference_init_(name, t, num_blocks):
     return t
 
 
-class _Holder(nn.Module):
-    """plain container node used to reproduce the reference's dotted state_dict names"""
+class SLATE_Module(FlatParamModule):
+    engine_cls = SlateEngine
+    backend = "SLATE"
 
-
-class SLATE_Module(nn.Module):
     def __init__(self, ocr_config, env_config) -> None:
         super().__init__()
         self._obs_size = int(env_config.obs_size)
@@ -120,8 +120,7 @@ class SLATE_Module(nn.Module):
             self.num_slots = self._dims.num_slots
             self.rep_dim = self._dims.slot_size
         # parameter containers in the reference's order / names; CPU tensors until .to(cuda)
-        from .. import _lib
-        self._spec = self._query_spec(_lib)
+        self._spec = self._query_spec()
         T = self._enc_size ** 2
         self._pnames = []
         block_masks = {}
@@ -136,53 +135,9 @@ class SLATE_Module(nn.Module):
             mask = torch.triu(torch.ones((T, T), dtype=torch.bool), diagonal=1)
             self._register(blk + ".self_attn_mask", nn.Parameter(mask, requires_grad=False), first=True)
         self._get("_enc_pos").register_buffer("linear_position_embedding", _position_grid(self._obs_size))
-        self.engine = None
-        self._max_batch = 0
-        self._seed = 0
-        self._step_seed = 0
-        self._injected_noise = None
         self.finetune_through_slots = False      # set by poolings.Base when learn_downstream_loss=True: forward() returns attached slots
 
     # ---- container plumbing
-    def _query_spec(self, _lib):
-        import ctypes
-        L = _lib.lib()
-        d = self._dims
-        c = _lib.SlateConfig(d.obs_size, d.obs_channels, d.vocab_size, d.d_model, d.cnn_hidden, d.num_slots, d.num_iterations,
-                             d.slot_size, d.mlp_hidden, d.num_dec_blocks, d.num_dec_heads, d.dropout, 1, int(d.use_bcdec), int(d.hard),
-                             int(getattr(d, "num_slot_heads", 1)))
-        h = ctypes.c_void_p()
-        _lib.check(L.ocrl_slate_create(ctypes.byref(c), ctypes.byref(h)))
-        out = []
-        name = ctypes.create_string_buffer(256)
-        shape = (ctypes.c_int * 4)()
-        nd, off, ne, grp = ctypes.c_int(), ctypes.c_longlong(), ctypes.c_longlong(), ctypes.c_int()
-        for i in range(L.ocrl_slate_param_count(h)):
-            _lib.check(L.ocrl_slate_param_info(h, i, name, 256, ctypes.byref(shape), ctypes.byref(nd), ctypes.byref(off), ctypes.byref(ne), ctypes.byref(grp)))
-            out.append(SimpleNamespace(name=name.value.decode(), shape=tuple(shape[k] for k in range(nd.value)), group=grp.value))
-        L.ocrl_slate_destroy(h)
-        return out
-
-    def _get(self, path):
-        node = self
-        for part in path.split("."):
-            if part not in node._modules:
-                node.add_module(part, _Holder())
-            node = node._modules[part]
-        return node
-
-    def _register(self, name, param, first=False):
-        path, leaf = name.rsplit(".", 1) if "." in name else ("", name)
-        node = self._get(path) if path else self
-        node.register_parameter(leaf, param)
-        if first:       # the mask is the block's first attribute in the reference -> first in state_dict order
-            items = list(node._parameters.items())
-            node._parameters.clear()
-            node._parameters[leaf] = param
-            for k, v in items:
-                if k != leaf:
-                    node._parameters[k] = v
-
     def _named_trainable(self):
         d = dict(self.named_parameters())
         return [(n, d[n]) for n in self._pnames]
@@ -205,51 +160,16 @@ class SLATE_Module(nn.Module):
             out.append(d[s.name])
         return out
 
-    # ---- device placement: parameters become views of the library's flat buffer
-    def to(self, device):
-        dev = torch.device(device)
-        if dev.type != "cuda":
-            raise RuntimeError(f"ocrl_amd SLATE runs on an AMD GPU only (got device={device!r}); there is no CPU path")
-        self._device = dev
-        self._ensure_engine(max(self._max_batch, 1))
-        return self
-
-    def _ensure_engine(self, batch):
-        if self.engine is not None and batch <= self._max_batch:
-            return
-        old = self.engine
-        eng = SlateEngine(self._dims, max_batch=batch, device=self._device)
-        named = dict(self.named_parameters())
-        for p in eng.params:
-            eng.view(eng.flat_p, p).copy_(named[p.name].data.to(eng.device))
-        if old is not None:
-            eng.flat_m.copy_(old.flat_m)
-            eng.flat_v.copy_(old.flat_v)
-            eng.adam_step = old.adam_step
-        for p in eng.params:
-            named[p.name].data = eng.view(eng.flat_p, p)
-            named[p.name].grad = eng.view(eng.flat_g, p)
+    def _engine_built(self, eng):
+        """the bool mask Parameters and the position buffers are not in the flat buffer: they follow it to the device; a
+        freeze_weights() promise made to the old engine is made again to the new one"""
         for n, q in self.named_parameters():
             if q.dtype == torch.bool:
                 q.data = q.data.to(eng.device)
         for n, b in self.named_buffers():
             b.data = b.data.to(eng.device)
-        self.engine = eng
-        self._max_batch = batch
         if getattr(self, "_frozen", False):
             eng.freeze_weights(True)
-        pending, self._pending_opt = getattr(self, "_pending_opt", None), None
-        if pending is not None:       # optimiser state loaded before .to(device), as the reference's callers do (sb3s/ocr_extractor.py:33-36)
-            pending[0].load_state_dict(pending[1])
-        torch.cuda.synchronize(eng.device)
-
-    def _need(self, obs):
-        if getattr(self, "_device", None) is None:
-            raise RuntimeError("call .to('cuda:N') before using the HIP backend")
-        if not obs.is_cuda:
-            raise RuntimeError("ocrl_amd: observations must live on the GPU (to_device(batch, device))")
-        self._ensure_engine(obs.shape[0])
-        return obs.contiguous().float()
 
     def freeze_weights(self, on=True):
         """Serving with a frozen, pre-trained encoder (sb3s/ocr_extractor.py:33-36 without finetuning): promise that the parameters do not
@@ -283,10 +203,6 @@ class SLATE_Module(nn.Module):
     # ---- reference surface
     def update_tau(self, step: int) -> None:
         self._tau = cosine_anneal(step, self._tau_start, self._tau_final, 0, self._tau_steps)
-
-    def set_seed(self, seed: int) -> None:
-        self._seed = int(seed)
-        self._step_seed = 0
 
     def inject_noise(self, noise):
         """parity hook: dict(z=[B,T,V], z_hard=[B,T,V], slots=[B,K,D]) consumed by the next get_loss/forward"""

@@ -9,7 +9,6 @@ No CPU fallback: a CPU tensor raises.
 
 Differences from the reference: the observation gets no gradient (``obs.requires_grad`` raises), and
 ``get_loss(obs, masks)`` as ``train_ocr.py`` calls it (a mask tensor in the ``with_rep`` slot) returns the metrics alone."""
-import ctypes
 import math
 
 import numpy as np
@@ -18,6 +17,7 @@ from torch import nn
 from torch.nn.utils import clip_grad_norm_
 
 from .. import _lib
+from .._lib import ptrs as _ptrs, stream as _stream
 from ..dist_utils import active_dist
 from .base import Base
 
@@ -112,14 +112,6 @@ def _rep_like(obs, dims):
     S, C, f, L, cnn, _ = dims
     shape = (obs.shape[0], f * f, 64) if cnn else (obs.shape[0], L)
     return torch.empty(shape, device=obs.device, dtype=torch.float32)
-
-
-def _ptrs(ts):
-    return (ctypes.c_void_p * len(ts))(*[t.data_ptr() if t is not None else None for t in ts])
-
-
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def _fwd(obs, dims, params, full, eps=None, recon=None):

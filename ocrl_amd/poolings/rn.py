@@ -35,8 +35,8 @@ class _RNFn(torch.autograd.Function):
                              f"times the widest g layer below 2^31)")
         ws = torch.empty(n, device=slots.device, dtype=torch.float32)
         out = torch.empty(B, f_dims[-1], device=slots.device, dtype=torch.float32)
-        arr = (ctypes.c_void_p * len(ps))(*[p.data_ptr() for p in ps])
-        st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+        arr = _lib.ptrs(ps)
+        st = _lib.stream()
         _lib.check(L.ocrl_pool_rn_fwd(_lib.ptr(slots), arr, _lib.ptr(out), B, K, D, len(g_dims), gd, len(f_dims), fd, _lib.ptr(ws), n, st))
         ctx.dims, ctx.ws, ctx.ps, ctx.slots = (g_dims, f_dims), ws, ps, slots
         ctx.need_dslots = ctx.needs_input_grad[0]      # read from the autograd node: the converted copy above carries no requires_grad
@@ -50,9 +50,9 @@ class _RNFn(torch.autograd.Function):
         dout = dout.contiguous().float()
         gs = [torch.empty_like(p) for p in ctx.ps]
         ds = torch.empty_like(ctx.slots) if ctx.need_dslots else None
-        arr = (ctypes.c_void_p * len(ctx.ps))(*[p.data_ptr() for p in ctx.ps])
-        garr = (ctypes.c_void_p * len(gs))(*[g.data_ptr() for g in gs])
-        st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+        arr = _lib.ptrs(ctx.ps)
+        garr = _lib.ptrs(gs)
+        st = _lib.stream()
         _lib.check(L.ocrl_pool_rn_bwd(_lib.ptr(ctx.slots), _lib.ptr(dout), arr, _lib.ptr(ds), garr, B, K, D, len(g_dims), _int_array(g_dims),
                                       len(f_dims), _int_array(f_dims), _lib.ptr(ctx.ws), ctx.ws.numel(), st))
         return (ds, None, None, *gs)

@@ -5,7 +5,6 @@ nn.TransformerEncoder) so that ``state_dict()`` keys, shapes and initialisation 
 unchanged -- but their ``forward`` is never called: the arithmetic is ``ocrl_pool_transformer_fwd/_bwd`` (HIP), wrapped in a
 ``torch.autograd.Function`` because in the reference the pooling parameters belong to the RL policy's torch optimiser
 (sb3s/ocr_extractor.py:33-35).  No CPU fallback: a CPU tensor raises."""
-import ctypes
 import math
 
 import torch
@@ -81,7 +80,7 @@ class _LinearFn(torch.autograd.Function):
         M, K = x2.shape
         N = weight.shape[0]
         y = torch.empty(M, N, device=x.device, dtype=torch.float32)
-        st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+        st = _lib.stream()
         _lib.check(L.ocrl_gemm(_lib.ptr(x2), _lib.ptr(w), _lib.ptr(y), M, N, K, K, K, N, 1, 1, 1.0, _lib.ptr(b), int(relu), None, 0, None, 0, 1, None, st))
         ctx.save_for_backward(x2, w, y)
         ctx.relu, ctx.shape = bool(relu), shp
@@ -96,7 +95,7 @@ class _LinearFn(torch.autograd.Function):
         dy2 = dy.reshape(M, N).contiguous().float()
         if ctx.relu:
             dy2 = dy2 * (y > 0)
-        st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+        st = _lib.stream()
         dx = dw = None
         if ctx.needs_input_grad[0]:
             dx = torch.empty(M, K, device=dy.device, dtype=torch.float32)           # dx = dy W        (NN)
@@ -152,8 +151,8 @@ class _PoolFn(torch.autograd.Function):
             n = L.ocrl_pool_transformer_ws_floats(B, K, d, nhead, ff, nl)
         ws = torch.empty(n, device=slots.device, dtype=torch.float32)
         out = torch.empty(B, d, device=slots.device, dtype=torch.float32)
-        arr = (ctypes.c_void_p * len(ps))(*[p.data_ptr() for p in ps])
-        st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+        arr = _lib.ptrs(ps)
+        st = _lib.stream()
         fwd = L.ocrl_pool_transformer_long_fwd if use_long else L.ocrl_pool_transformer_fwd
         _lib.check(fwd(_lib.ptr(slots), arr, _lib.ptr(pos), _lib.ptr(out), B, K, Din, d, nhead, ff, nl, drop_p, seed, _lib.ptr(ws), n, st))
         ctx.geom, ctx.drop_p, ctx.seed, ctx.ws, ctx.ps, ctx.slots, ctx.use_long = geom, drop_p, seed, ws, ps, slots, use_long
@@ -168,9 +167,9 @@ class _PoolFn(torch.autograd.Function):
         dout = dout.contiguous().float()
         gs = [torch.empty_like(p) for p in ctx.ps]
         ds = torch.empty_like(ctx.slots) if ctx.need_dslots else None
-        arr = (ctypes.c_void_p * len(ctx.ps))(*[p.data_ptr() for p in ctx.ps])
-        garr = (ctypes.c_void_p * len(gs))(*[g.data_ptr() for g in gs])
-        st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+        arr = _lib.ptrs(ctx.ps)
+        garr = _lib.ptrs(gs)
+        st = _lib.stream()
         bwd = L.ocrl_pool_transformer_long_bwd if ctx.use_long else L.ocrl_pool_transformer_bwd
         _lib.check(bwd(_lib.ptr(ctx.slots), _lib.ptr(dout), arr, _lib.ptr(ds), garr, B, K, Din, d, nhead, ff, nl, ctx.drop_p, ctx.seed,
                        _lib.ptr(ctx.ws), ctx.ws.numel(), st))

@@ -70,8 +70,8 @@ class _ProbeFn(torch.autograd.Function):
         cost = torch.empty(B, N, K, device=dev, dtype=torch.float32)
         col = torch.empty(B, N, device=dev, dtype=torch.int32)
         metrics = torch.empty(P + 2, device=dev, dtype=torch.float32)
-        arr = (ctypes.c_void_p * len(ps))(*[p.data_ptr() for p in ps])
-        st = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        arr = _lib.ptrs(ps)
+        st = _lib.stream(dev)
         _lib.check(L.ocrl_probe_fwd(_lib.ptr(rows), arr, _lib.ptr(y), _lib.ptr(out), _lib.ptr(cost), _lib.ptr(col), _lib.ptr(metrics), B, K, N, D, T,
                                     O, int(spec.slot_rows), len(spec.dims), dims, spec.slope, P, _ints(sum(spec.tgt, [])), _ints(sum(spec.out, [])),
                                     _ints(spec.kind), _lib.ptr(ws), n, st))
@@ -86,9 +86,9 @@ class _ProbeFn(torch.autograd.Function):
         B, K, N, D, O, P = ctx.shape
         dloss = dloss.contiguous().float()
         gs = [torch.empty_like(p) for p in ctx.ps]
-        arr = (ctypes.c_void_p * len(ctx.ps))(*[p.data_ptr() for p in ctx.ps])
-        garr = (ctypes.c_void_p * len(gs))(*[g.data_ptr() for g in gs])
-        st = ctypes.c_void_p(torch.cuda.current_stream(dloss.device).cuda_stream)
+        arr = _lib.ptrs(ctx.ps)
+        garr = _lib.ptrs(gs)
+        st = _lib.stream(dloss.device)
         _lib.check(L.ocrl_probe_bwd(_lib.ptr(ctx.rows), _lib.ptr(dloss), arr, garr, B, K, N, D, O, int(spec.slot_rows), len(spec.dims),
                                     _ints(spec.dims), spec.slope, P, _lib.ptr(ctx.ws), ctx.ws.numel(), st))
         return (None, None, None, *gs)
@@ -110,7 +110,7 @@ def probe_match(out, y, tgt, outr, kind, dloss=None, want_grad=True):
     col = torch.empty(B, N, device=dev, dtype=torch.int32)
     metrics = torch.empty(P + 2, device=dev, dtype=torch.float32)
     dout = torch.zeros_like(out) if want_grad else None
-    st = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    st = _lib.stream(dev)
     _lib.check(L.ocrl_probe_match(_lib.ptr(out), O, K * O, _lib.ptr(y), _lib.ptr(dloss), _lib.ptr(cost), _lib.ptr(col), _lib.ptr(metrics),
                                   _lib.ptr(dout), B, K, N, T, O, P, _ints(sum(tgt, [])), _ints(sum(outr, [])), _ints(kind), _lib.ptr(ws), n, st))
     return dict(cost=cost, col=col, metrics=metrics, dout=dout)
