@@ -275,6 +275,25 @@ int ocrl_naturecnn_fwd(const float* obs, const float* const* w, float* out, int 
 int ocrl_naturecnn_bwd(const float* obs, const float* dout, const float* const* w, float* const* dw, int B, int H, int W, int cin, int groups,
                        int cnn_feat_size, int use_cnn_feat, int rep_dim, float* ws, size_t ws_floats, void* stream);
 
+/* ---- NatureCNN pooling heads: poolings/cnn_linear/cnn_linear_module.py:7-14 (CNN_Linear) and the CNN front end of
+ * poolings/cnn_transformer/cnn_transformer_module.py:12-40 (CNN_Transformer), both over slot_to_img(tokens) (utils/tools.py:33-36;
+ * configs/pooling/cnn_linear.yaml, cnn_transformer.yaml).  poolings/common/naturecnn.py:10-29: Conv2d(D, 32, 8, s 4) ReLU
+ * Conv2d(32, 64, 4, s 2) ReLU  Conv2d(64, 64, 3, s 1) ReLU, all padding 0; then, with rep_dim > 0, Flatten (NCHW order) and
+ * Linear(64 OH OW, rep_dim) ReLU.  tokens [B, H W, D]: the channels-last H x W map that SLATE with use_cnn_feat returns (D = channels + 3);
+ * slot_to_img is a view of it, nothing is permuted.  out: [B, rep_dim] with rep_dim > 0 (CNN_Linear); [B, OH OW, 64] (the last map as HWC
+ * tokens, the pooling transformer's input) with rep_dim == 0.  `w` = the parameters in state_dict order: _net.0.{weight [32, D, 8, 8],
+ * bias}, _net.2.*, _net.4.*[, _net.7.{weight [rep_dim, 64 OH OW], bias}], in torch's layouts; they are read on every call (the first
+ * layer's weight is reordered into ws per call, nothing is cached).  The Linear's input width is derived from H and W.  save != 0 leaves
+ * in ws what _bwd needs; _bwd (called with the same ws right after a saving _fwd): dout (out's shape) -> dw (same order / shapes as w;
+ * every entry is overwritten, not accumulated) and dtokens [B, H W, D] (NULL = the tokens are detached, poolings/base.py:53; every
+ * element is written, 0 at border pixels that no window covers).  Rejected shapes get ws_floats == 0 and fail in _fwd / _bwd: B < 1,
+ * D < 1, a map below 36 x 36, rep_dim not a non-negative multiple of 4, index ranges past int32. */
+size_t ocrl_pool_cnn_ws_floats(int B, int H, int W, int D, int rep_dim);
+int ocrl_pool_cnn_fwd(const float* tokens, const float* const* w, float* out, int B, int H, int W, int D, int rep_dim, int save, float* ws,
+                      size_t ws_floats, void* stream);
+int ocrl_pool_cnn_bwd(const float* tokens, const float* dout, const float* const* w, float* dtokens, float* const* dw, int B, int H, int W, int D,
+                      int rep_dim, float* ws, size_t ws_floats, void* stream);
+
 /* ---- VAE representation module: ocrs/vaes/vae_module.py, ocrs/common/models.py:49-93 (VAEEncoder / VAEDecoder), configs/ocr/vae.yaml.
  * n = log2(obs_size / cnn_feat_size) stages (1 .. OCRL_VAE_MAX_STAGES), f = cnn_feat_size, L = latent_dim (a multiple of 4), C =
  * obs_channels (1 .. 4).  obs [B, C, S, S] (NCHW).  `w` = every parameter in state_dict order: _enc._encoder.{0 .. 4n - 1}.m.*,

@@ -154,6 +154,10 @@ def lib():
     L.ocrl_naturecnn_ws_floats.restype = c_size_t
     L.ocrl_naturecnn_fwd.argtypes = [p, POINTER(p), p] + [c_int] * 9 + [p, c_size_t, p]
     L.ocrl_naturecnn_bwd.argtypes = [p, p, POINTER(p), POINTER(p)] + [c_int] * 8 + [p, c_size_t, p]
+    L.ocrl_pool_cnn_ws_floats.argtypes = [c_int] * 5
+    L.ocrl_pool_cnn_ws_floats.restype = c_size_t
+    L.ocrl_pool_cnn_fwd.argtypes = [p, POINTER(p), p] + [c_int] * 6 + [p, c_size_t, p]
+    L.ocrl_pool_cnn_bwd.argtypes = [p, p, POINTER(p), p, POINTER(p)] + [c_int] * 5 + [p, c_size_t, p]
     L.ocrl_vae_ws_floats.argtypes = [c_int] * 7
     L.ocrl_vae_ws_floats.restype = c_size_t
     L.ocrl_vae_fwd.argtypes = [p, POINTER(p), p, p, p, p] + [c_int] * 6 + [c_float, c_int, p, c_size_t, p]

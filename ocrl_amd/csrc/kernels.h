@@ -169,6 +169,39 @@ int nc_conv_bwd_launch(NcBwdArgs a, hipStream_t st);      // dW partials of the 
 int nc_dw_reduce_launch(const NcReduceArgs& a, hipStream_t st);
 int nc_relu_mask_launch(const float* d, const float* act, float* out, long long n, hipStream_t st);
 
+// ------------------------------------------------------------------ pool_cnn.hip (first layer of the CNN pooling heads: include/ocrl_hip.h ocrl_pool_cnn_*)
+// Conv2d(D, 32, k 8, s 4) + ReLU over channels-last tokens [B, H, W, D]; output and dY in the [B, 32, OH, OW] layout layer 2 reads
+struct PcGeom {
+    int OH = 0, OW = 0, OWT = 0;                   // output map; 16-column tiles per output row
+    int NG = 0, nchunk = 0;                        // groups of 16 columns per half window row (4 D floats); steps of 4 groups
+    size_t wp_floats = 0;                          // packed forward weight [8 nchunk][32][128]
+    long long units = 0; int slab_units = 0, slabs = 0; size_t part_floats = 0;   // dW: (image, output row, tile) units in slabs
+    int passes = 0, nbg = 0, Dp = 0; size_t wd_floats = 0;                         // dX: channel passes, blocks per pass, padded D
+    int HB = 0, WB = 0, WT = 0; long long dx_units = 0; int upw = 0;               // dX: (image, row quad, 16 column quads) units per workgroup
+};
+PcGeom pc_geom(int B, int H, int W, int D);
+struct PcFwdArgs {
+    const float* X = nullptr; const float* Wp = nullptr; const float* bias = nullptr; float* Y = nullptr;
+    int B = 0, H = 0, W = 0, D = 0, OH = 0, OW = 0, OWT = 0, nchunk = 0, NG = 0;
+};
+struct PcDwArgs {
+    const float* X = nullptr; const float* dY = nullptr; float* part = nullptr; float* partb = nullptr;
+    int B = 0, H = 0, W = 0, D = 0, OH = 0, OW = 0, OWT = 0, nchunk = 0, slab_units = 0;
+    long long units = 0;
+};
+struct PcDxArgs {
+    const float* dY = nullptr; const float* Wd = nullptr; float* dX = nullptr;
+    int H = 0, W = 0, D = 0, OH = 0, OW = 0, HB = 0, WT = 0, Dp = 0, passes = 0, upw = 0;
+    long long units = 0, groups = 0;
+};
+// Wp: pc_geom().wp_floats of scratch (the weight is reordered per call); Y = relu(conv + bias)
+int pc_conv1_fwd_launch(const float* X, const float* w, const float* bias, float* Wp, float* Y, int B, int H, int W, int D, hipStream_t st);
+// part: pc_geom().part_floats; dY = gradient of the pre-activation; the reduce writes dw [32, D, 8, 8] and db [32]
+int pc_conv1_dw_launch(const float* X, const float* dY, float* part, int B, int H, int W, int D, hipStream_t st);
+int pc_conv1_dw_reduce_launch(const float* part, float* dw, float* db, int B, int H, int W, int D, hipStream_t st);
+// Wd: pc_geom().wd_floats of scratch; dX [B, H, W, D], every element written
+int pc_conv1_dx_launch(const float* dY, const float* w, float* Wd, float* dX, int B, int H, int W, int D, hipStream_t st);
+
 // ------------------------------------------------------------------ probe.hip (slot property probe: include/ocrl_hip.h ocrl_probe_*)
 #define PROBE_MAX_SLOTS 12      // 2^K assignment states per image in LDS
 #define PROBE_MAX_PROPS 8
