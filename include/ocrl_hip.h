@@ -348,6 +348,23 @@ int ocrl_probe_match(const float* out, int ld_row, long long ld_img, const float
                      float* dout, int B, int K, int N, int T, int O, int P, const int* tgt_range, const int* out_range, const int* kind, float* ws,
                      size_t ws_floats, void* stream);
 
+/* ---- Segmentation ARI counts: utils/tools.py:309-320 (calculate_ari) with the masking of slate_module.py:211-213 /
+ * iodine_module.py:263-265 folded in ----
+ * Two stacks of per-pixel channel scores, each addressed by ELEMENT strides (batch, channel, pixel), so [B, C, N] and [B, N, C] are both
+ * read in place; no alignment is required (pixel-contiguous, 16-byte aligned stacks take 16-byte loads).  Per image:
+ *   true label  t = first maximum over the Ct channels of `truth`, predicted label p = first maximum over Cp channels (torch.argmax:
+ *               a NaN is the maximum, the first NaN wins)
+ *   fuse_fg = 0: `pred` holds the Cp channels.  fuse_fg = 1: `pred` holds K = Cp - 1 channels; with fg = 1 - truth[Ct-1] (one fp32
+ *               subtract) channel k < K scores pred_k * fg (one fp32 multiply) and channel K scores fg, which is
+ *               torch.cat([attns * fg_mask, fg_mask], dim=1) bit for bit, ties included
+ *   table [B, Ct, Cp] int32   pixels per (t, p); zeroed by the call
+ *   sums  [B, 3]      int64   sum_ij C(n_ij), sum_i C(a_i) (row sums), sum_j C(b_j) (column sums), C(x) = x (x - 1) / 2
+ * Exact integers: the result does not depend on the order of the additions.  1 <= Ct, Cp <= OCRL_ARI_MAX_CHANNELS, B >= 1,
+ * 1 <= N < 2^31; anything else is rejected ("invalid ...") before any memory is touched.  The zeroing and both kernels go on `stream`. */
+#define OCRL_ARI_MAX_CHANNELS 32
+int ocrl_ari_counts(const float* truth, long long t_sb, long long t_sc, long long t_sn, int Ct, const float* pred, long long p_sb,
+                    long long p_sc, long long p_sn, int Cp, int fuse_fg, int B, long long N, int* table, long long* sums, void* stream);
+
 /* ---- IODINE (ocrs/iodine/iodine_module.py:14-271, ocrs/iodine/iodine.py:4-14, ocrs/base.py:60-74): SURVEY.md §8 row a20 ----
  * Same conventions as the SLATE handle: flat fp32 parameter / gradient / Adam buffers in the reference's
  * _module.parameters() order and state_dict names, adopted from the caller; one workspace; all work on the caller's stream. */

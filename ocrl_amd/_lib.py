@@ -170,6 +170,7 @@ def lib():
     L.ocrl_probe_match_ws_floats.argtypes = [c_int, c_int]
     L.ocrl_probe_match_ws_floats.restype = c_size_t
     L.ocrl_probe_match.argtypes = [p, c_int, c_longlong, p, p, p, p, p, p] + [c_int] * 6 + [POINTER(c_int)] * 3 + [p, c_size_t, p]
+    L.ocrl_ari_counts.argtypes = [p, c_longlong, c_longlong, c_longlong, c_int, p, c_longlong, c_longlong, c_longlong, c_int, c_int, c_int, c_longlong, p, p, p]
     L.ocrl_comm_unique_id.argtypes = [p, c_size_t]
     L.ocrl_comm_init.argtypes = [POINTER(p), c_int, c_int, p]
     L.ocrl_comm_allreduce.argtypes = [p, p, c_longlong, p]

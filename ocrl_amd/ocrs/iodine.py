@@ -105,12 +105,16 @@ class Iodine_Module(FlatParamModule):
 
     def get_loss(self, obs, masks, with_rep=False) -> dict:
         """iodine_module.py:261-269 (masks are required, as in the reference)"""
-        _, _, _, attns, loss, mse, kl, _, _ = self._forward(obs)
-        fg_mask = 1 - masks[:, -1].unsqueeze(1)
-        attns = torch.cat([attns * fg_mask, fg_mask], dim=1)
-        from ..utils.tools import calculate_ari
-        ari = float(np.mean(calculate_ari(masks, attns)))
-        return {"loss": loss, "mse": mse.detach(), "ari": ari, "kld": kl.detach()}
+        if masks is None:
+            raise TypeError("Iodine.get_loss: masks are required (iodine_module.py:263)")
+        _, _, _, _, loss, mse, kl, _, _ = self._forward(obs)
+        return {"loss": loss, "mse": mse.detach(), "ari": float(np.mean(self.last_ari(masks))), "kld": kl.detach()}
+
+    def last_ari(self, masks):
+        """per-image ARI of the masks of the most recent forward against masks [B, Ct, 1, S, S] (iodine_module.py:263-267)"""
+        from ..utils.tools import segmentation_ari
+        B, K, S = masks.shape[0], self.num_slots, self.img_size
+        return segmentation_ari(masks, self.engine.tensor("masks", (B, K, 1, S, S)))
 
     def backward(self):
         self.engine.backward()

@@ -8,6 +8,7 @@ the reference's names and shapes); forward/backward never 
 import math
 from types import SimpleNamespace
 
+import numpy as np
 import torch
 from torch import nn
 
@@ -260,14 +261,8 @@ class SLATE_Module(FlatParamModule):
                 "cross_entropy": m[1],
                 "tau": torch.Tensor([self._tau]),
             }
-        if masks is not None:
-            from ..utils.tools import calculate_ari
-            import numpy as np
-            attns = self._attns_image(B)
-            fg_mask = 1 - masks[:, -1].unsqueeze(1)
-            attns = torch.cat([attns * fg_mask, fg_mask], dim=1)
-            if self._use_bcdec:     # the SLATE branch of the reference computes but does not report ari (slate_module.py:231)
-                metrics["ari"] = float(np.mean(calculate_ari(masks, attns)))
+        if masks is not None and self._use_bcdec:     # the SLATE branch of the reference computes the ari and drops it (slate_module.py:231)
+            metrics["ari"] = float(np.mean(self.last_ari(masks)))
         if with_mse and not self._use_bcdec:      # slate_module.py:234-237: autoregressive reconstruction error
             metrics = {k: (v.clone() if torch.is_tensor(v) else v) for k, v in metrics.items()}
             self.engine.generate()
@@ -279,6 +274,11 @@ class SLATE_Module(FlatParamModule):
             z = self.engine.tensor("z_st" if self._hard else "z", (B, E, E, V)).permute(0, 3, 1, 2)
             return metrics, z
         return metrics
+
+    def last_ari(self, masks):
+        """per-image ARI of the attention maps of the most recent forward against masks [B, Ct, 1, S, S] (slate_module.py:211-216)"""
+        from ..utils.tools import segmentation_ari
+        return segmentation_ari(masks, self._attns_image(masks.shape[0]))
 
     def backward(self):
         self.engine.backward()
