@@ -365,6 +365,48 @@ int ocrl_probe_match(const float* out, int ld_row, long long ld_img, const float
 int ocrl_ari_counts(const float* truth, long long t_sb, long long t_sc, long long t_sn, int Ct, const float* pred, long long p_sb,
                     long long p_sc, long long p_sn, int Cp, int fuse_fg, int B, long long N, int* table, long long* sums, void* stream);
 
+/* ---- actor-critic head and PPO minibatch step: sb3s/custom_acnets.py:8-96 (CustomNetwork: shared_net, then policy_net and value_net,
+ *      each [Linear, ReLU | Tanh] x n, the configs/sb3_acnet files) with the heads its ActorCriticPolicy (custom_acnets.py:99-128) inherits
+ *      from stable-baselines3: action_net = Linear(latent_dim_pi, A), value_net = Linear(latent_dim_vf, 1), a categorical distribution,
+ *      and the loss of PPO.train (configs/sb3/ppo.yaml; clip_range_vf = None).  The heads and the loss are restated from the published
+ *      algorithm, not from an import.
+ * Stateless; fp32 device pointers; everything is enqueued on `stream` with no host synchronisation.
+ * desc: B rows of F features, A actions (A == 0: the trunks alone, no heads), trunk t = 0 shared, 1 policy, 2 value with n[t] layers of
+ *   widths dims[t][] and activations acts[t][] (0 none, 1 ReLU, 2 tanh).  Supported: B >= 1, F >= 1, B * max(F, widths) < 2^31, widths
+ *   multiples of 4 up to 256, at most OCRL_ACNET_MAX_LAYERS layers per trunk (any trunk may be empty), 1 <= A <= 64 (or 0).  Anything
+ *   else is rejected: ws_floats == 0, the other entry points return non-zero with a message.
+ * w / dw: state_dict order: shared_net, policy_net, value_net as (weight [out, in], bias) per layer, then with A > 0 action_net.weight
+ *   [A, latent_pi], action_net.bias, value_net.weight [1, latent_vf], value_net.bias.
+ * _fwd: latent_pi [B, latent_dim_pi], latent_vf [B, latent_dim_vf], logits [B, A], values [B]; each may be NULL.  One kernel launch.
+ *   save != 0 leaves every trunk layer's output in ws for _bwd (ws may be NULL otherwise).
+ * _bwd: after a _fwd with save != 0 on the same features and ws.  Any of dlatent_pi, dlatent_vf, dlogits, dvalues may be NULL (zero).
+ *   Overwrites every entry of dw and, unless NULL (detached features), dfeatures [B, F].
+ * _ppo_fwd_bwd: the whole minibatch step.  actions: int64 [B] in [0, A) (clamped into the range); scalars [6] = loss, policy_loss,
+ *   value_loss, entropy_loss, approx_kl, clip_fraction; dw, dfeatures = gradients of `loss`.  With normalize_advantage the advantages
+ *   become (adv - mean) / (std + 1e-8), unbiased std; B == 1 is then rejected.  At most three launches.
+ * Bit-reproducible: no atomics; per-tile partial gradients are summed in a fixed order; a row's outputs do not depend on its position. */
+#define OCRL_ACNET_MAX_LAYERS 8
+typedef struct {
+    int B, F, A;
+    int n[3];
+    int dims[3][OCRL_ACNET_MAX_LAYERS];
+    int acts[3][OCRL_ACNET_MAX_LAYERS];
+} ocrl_acnet_desc;
+size_t ocrl_acnet_desc_size(void);
+size_t ocrl_acnet_ws_floats(const ocrl_acnet_desc* d);
+int ocrl_acnet_fwd(const ocrl_acnet_desc* d, const float* features, const float* const* w, float* latent_pi, float* latent_vf, float* logits,
+                   float* values, int save, float* ws, size_t ws_floats, void* stream);
+int ocrl_acnet_bwd(const ocrl_acnet_desc* d, const float* features, const float* const* w, const float* dlatent_pi, const float* dlatent_vf,
+                   const float* dlogits, const float* dvalues, float* dfeatures, float* const* dw, float* ws, size_t ws_floats, void* stream);
+int ocrl_acnet_ppo_fwd_bwd(const ocrl_acnet_desc* d, const float* features, const float* const* w, const long long* actions,
+                           const float* old_log_prob, const float* advantages, const float* returns, float clip_range, float vf_coef,
+                           float ent_coef, int normalize_advantage, float* scalars, float* dfeatures, float* const* dw, float* ws,
+                           size_t ws_floats, void* stream);
+/* Generalised advantage estimation as stable-baselines3's RolloutBuffer.compute_returns_and_advantage: rewards, values, episode_starts
+ * [T, E], last_values, dones [E] -> advantages, returns [T, E]; one thread per environment walks T backwards. */
+int ocrl_gae(const float* rewards, const float* values, const float* episode_starts, const float* last_values, const float* dones,
+             float* advantages, float* returns, int T, int E, float gamma, float gae_lambda, void* stream);
+
 /* ---- IODINE (ocrs/iodine/iodine_module.py:14-271, ocrs/iodine/iodine.py:4-14, ocrs/base.py:60-74): SURVEY.md §8 row a20 ----
  * Same conventions as the SLATE handle: flat fp32 parameter / gradient / Adam buffers in the reference's
  * _module.parameters() order and state_dict names, adopted from the caller; one workspace; all work on the caller's stream. */

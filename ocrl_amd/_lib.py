@@ -36,6 +36,23 @@ class GemmDesc(ctypes.Structure):
                 ("force_tile", c_int), ("force_sb", c_int)]
 
 
+class AcnetDesc(ctypes.Structure):
+    """mirror of ocrl_acnet_desc (include/ocrl_hip.h); make one with acnet_desc()"""
+    _fields_ = [("B", c_int), ("F", c_int), ("A", c_int), ("n", c_int * 3), ("dims", (c_int * 8) * 3), ("acts", (c_int * 8) * 3)]
+
+
+def acnet_desc(B, F, A, dims, acts):
+    """AcnetDesc of three trunks: dims / acts = (shared, policy, value) sequences of widths / activation codes (0 none, 1 relu, 2 tanh)"""
+    d = AcnetDesc(B=B, F=F, A=A)
+    for t in range(3):
+        if len(dims[t]) > 8:
+            raise ValueError(f"ocrl_amd: at most 8 layers per trunk (got {len(dims[t])})")
+        d.n[t] = len(dims[t])
+        for l, (w, a) in enumerate(zip(dims[t], acts[t])):
+            d.dims[t][l], d.acts[t][l] = int(w), int(a)
+    return d
+
+
 def gemm_desc(**kw):
     """GemmDesc with the defaults of GemmArgs (alpha = 1, one batch, no split, the dispatch rule) and the given fields"""
     d = GemmDesc(batch=1, batch_inner=1, splitk=1, alpha=1.0, x_scale=1.0, e_scale=1.0, force_sb=-1)
@@ -171,6 +188,15 @@ def lib():
     L.ocrl_probe_match_ws_floats.restype = c_size_t
     L.ocrl_probe_match.argtypes = [p, c_int, c_longlong, p, p, p, p, p, p] + [c_int] * 6 + [POINTER(c_int)] * 3 + [p, c_size_t, p]
     L.ocrl_ari_counts.argtypes = [p, c_longlong, c_longlong, c_longlong, c_int, p, c_longlong, c_longlong, c_longlong, c_int, c_int, c_int, c_longlong, p, p, p]
+    L.ocrl_acnet_desc_size.restype = c_size_t
+    if L.ocrl_acnet_desc_size() != ctypes.sizeof(AcnetDesc):
+        raise RuntimeError(f"libocrl_hip.so: ocrl_acnet_desc is {L.ocrl_acnet_desc_size()} bytes, this binding's AcnetDesc {ctypes.sizeof(AcnetDesc)}")
+    L.ocrl_acnet_ws_floats.argtypes = [POINTER(AcnetDesc)]
+    L.ocrl_acnet_ws_floats.restype = c_size_t
+    L.ocrl_acnet_fwd.argtypes = [POINTER(AcnetDesc), p, POINTER(p), p, p, p, p, c_int, p, c_size_t, p]
+    L.ocrl_acnet_bwd.argtypes = [POINTER(AcnetDesc), p, POINTER(p), p, p, p, p, p, POINTER(p), p, c_size_t, p]
+    L.ocrl_acnet_ppo_fwd_bwd.argtypes = [POINTER(AcnetDesc), p, POINTER(p), p, p, p, p, c_float, c_float, c_float, c_int, p, p, POINTER(p), p, c_size_t, p]
+    L.ocrl_gae.argtypes = [p, p, p, p, p, p, p, c_int, c_int, c_float, c_float, p]
     L.ocrl_comm_unique_id.argtypes = [p, c_size_t]
     L.ocrl_comm_init.argtypes = [POINTER(p), c_int, c_int, p]
     L.ocrl_comm_allreduce.argtypes = [p, p, c_longlong, p]

@@ -1,3 +1,4 @@
+from .custom_acnets import CustomActorCriticPolicy, CustomNetwork, compute_gae, ppo_loss
 from .ocr_extractor import OCRExtractor
 
-__all__ = ["OCRExtractor"]
+__all__ = ["OCRExtractor", "CustomNetwork", "CustomActorCriticPolicy", "ppo_loss", "compute_gae"]
