@@ -41,8 +41,7 @@ class CabiComm:
 
     def allreduce_(self, flat):
         assert flat.is_cuda and flat.dtype == torch.float32 and flat.is_contiguous()
-        st = ctypes.c_void_p(torch.cuda.current_stream(flat.device).cuda_stream)
-        self._lib.check(self.L.ocrl_comm_allreduce(self.h, self._lib.ptr(flat), flat.numel(), st))
+        self._lib.check(self.L.ocrl_comm_allreduce(self.h, self._lib.ptr(flat), flat.numel(), self._lib.stream(flat.device)))
 
     def close(self):
         if self.h:

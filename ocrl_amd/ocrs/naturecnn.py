@@ -13,112 +13,82 @@ from types import SimpleNamespace
 import torch
 from torch import nn
 
-from .. import _lib
+from .. import _bridge, _lib
+from .._bridge import NATURE_CONVS, conv_map_size, conv_shapes
 from .base import Base
 
-_CONVS = ((32, 8, 4), (64, 4, 2), (64, 3, 1), (128, 3, 1))       # (out channels, kernel, stride) of _cnn.0 / .2 / .4 / .6
-
-
-def _map_size(obs_size, n_convs):
-    s = obs_size
-    for _, k, st in _CONVS[:n_convs]:
-        s = (s - k) // st + 1 if s >= k else 0
-    return s
+_WHO = "ocrl_amd.ocrs.NatureCNN"
 
 
 def _check_inputs(obs, params, dims, cin):
     """everything the C entry points cannot check themselves: they get no parameter sizes, and derive the Linear's input width from the
     observation's H and W.  So the observation must flatten to the width the Linear was built for (the reference's Linear raises
-    torch's shape-mismatch error otherwise), and every parameter must have the shape, dtype and device the kernels read it with."""
+    torch's shape-mismatch error otherwise), and every parameter must have the shape, dtype and device the kernels read it with.
+    Returns (observation, parameters) as the kernels read them"""
     groups, feat, use_feat, rep = dims
     n_conv = 4 if feat == 2 else 3
     if obs.dim() != 4 or obs.shape[1] != cin:
-        raise ValueError(f"ocrl_amd.ocrs.NatureCNN: expected observations [B, {cin}, H, W], got {list(obs.shape)}")
-    shapes, c = [], cin
-    for cout, k, _ in _CONVS[:n_conv]:
-        shapes += [(cout, c, k, k), (cout,)]
-        c = cout
+        raise ValueError(f"{_WHO}: expected observations [B, {cin}, H, W], got {list(obs.shape)}")
+    shapes = conv_shapes(cin, n_conv)
     if not use_feat:
         lin = params[2 * n_conv]                              # module 0's Linear weight; every module must match it
-        oh, ow = _map_size(obs.shape[2], n_conv), _map_size(obs.shape[3], n_conv)
+        c, oh, ow = NATURE_CONVS[n_conv - 1][0], conv_map_size(obs.shape[2], n_conv), conv_map_size(obs.shape[3], n_conv)
         if lin.dim() != 2 or c * oh * ow != lin.shape[1]:
-            raise ValueError(f"ocrl_amd.ocrs.NatureCNN: {obs.shape[2]} x {obs.shape[3]} observations flatten to {c} x {oh} x {ow} = "
+            raise ValueError(f"{_WHO}: {obs.shape[2]} x {obs.shape[3]} observations flatten to {c} x {oh} x {ow} = "
                              f"{c * oh * ow} features, but the Linear takes {list(lin.shape)[1:]} (built for another obs_size)")
         shapes += [(rep, c * oh * ow), (rep,)]
-    shapes = shapes * groups
-    if len(params) != len(shapes) or any(tuple(p.shape) != sh for p, sh in zip(params, shapes)):
-        raise ValueError(f"ocrl_amd.ocrs.NatureCNN: parameter shapes {[list(p.shape) for p in params]} are not the encoder's "
-                         f"{[list(sh) for sh in shapes]}")
-    if not obs.is_cuda:
-        raise RuntimeError("ocrl_amd.ocrs: tensors must live on the GPU (there is no CPU fallback)")
+    x, ps = _bridge.inputs(_WHO, obs, params, shapes * groups)
     if obs.requires_grad:
-        raise RuntimeError("ocrl_amd.ocrs.NatureCNN: the observation gets no gradient (the first convolution's input gradient is not built)")
-    for p in params:
-        if p.dtype != torch.float32 or p.device != obs.device:
-            raise RuntimeError(f"ocrl_amd.ocrs.NatureCNN: parameters must be float32 on the observations' device {obs.device} "
-                               f"(got {p.dtype} on {p.device})")
+        raise RuntimeError(f"{_WHO}: the observation gets no gradient (the first convolution's input gradient is not built)")
+    return x, ps
 
 
 def _encode(obs, dims, params, save):
     """one ocrl_naturecnn_fwd call; returns (out, ws)"""
     groups, feat, use_feat, rep = dims
-    L = _lib.lib()
+    L, dev = _lib.lib(), obs.device
     B, C, H, W = obs.shape
-    n = L.ocrl_naturecnn_ws_floats(B, H, W, C, groups, feat, use_feat, rep)
-    if n == 0:
-        raise ValueError(f"ocrl_amd.ocrs.NatureCNN: shape not supported: batch {B} of {C} x {H} x {W} images, {groups} module(s), "
-                         f"cnn_feat_size {feat}, use_cnn_feat {bool(use_feat)}, rep_dim {rep}: "
-                         + L.ocrl_last_error().decode())
-    ws = torch.empty(n, device=obs.device, dtype=torch.float32)
+    ws = _bridge.workspace(_WHO, L.ocrl_naturecnn_ws_floats(B, H, W, C, *dims), dev,
+                           f"batch {B} of {C} x {H} x {W} images, {groups} module(s), cnn_feat_size {feat}, use_cnn_feat {bool(use_feat)}, rep_dim {rep}")
     if use_feat:
         n_conv = 4 if feat == 2 else 3
-        oh, ow = _map_size(H, n_conv), _map_size(W, n_conv)
-        out = torch.empty(B, oh * ow, _CONVS[n_conv - 1][0], device=obs.device, dtype=torch.float32)
-    elif groups == 1:
-        out = torch.empty(B, rep, device=obs.device, dtype=torch.float32)
+        shape = (B, conv_map_size(H, n_conv) * conv_map_size(W, n_conv), NATURE_CONVS[n_conv - 1][0])
     else:
-        out = torch.empty(B, groups, rep, device=obs.device, dtype=torch.float32)
-    arr = _lib.ptrs(params)
-    st = _lib.stream()
-    _lib.check(L.ocrl_naturecnn_fwd(_lib.ptr(obs), arr, _lib.ptr(out), B, H, W, C, groups, feat, use_feat, rep, int(save), _lib.ptr(ws), n, st))
+        shape = (B, rep) if groups == 1 else (B, groups, rep)
+    out = torch.empty(shape, device=dev, dtype=torch.float32)
+    _bridge.launch(dev, L.ocrl_naturecnn_fwd, _lib.ptr(obs), _lib.ptrs(params), _lib.ptr(out), B, H, W, C, *dims, int(save), _lib.ptr(ws), ws.numel())
     return out, ws
 
 
 class _NatureCNNFn(torch.autograd.Function):
+    """over the observation and the parameters `ps` as _check_inputs returned them; `params` are their attached originals, which get
+    the gradients"""
+
     @staticmethod
-    def forward(ctx, obs, dims, *params):
-        ps = [p.contiguous() for p in params]
+    def forward(ctx, obs, dims, ps, *params):
         out, ws = _encode(obs, dims, ps, save=True)
-        # through save_for_backward, so that torch's version check raises if the observation or a weight changes in place before
-        # the backward (the backward reads both again)
         ctx.save_for_backward(obs, *ps)
         ctx.dims, ctx.ws = dims, ws
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        groups, feat, use_feat, rep = ctx.dims
         obs, *ps = ctx.saved_tensors
-        L = _lib.lib()
         B, C, H, W = obs.shape
-        dout = dout.contiguous().float()
+        dout = _bridge.cotangent(dout)
         gs = [torch.empty_like(p) for p in ps]
-        arr = _lib.ptrs(ps)
-        garr = _lib.ptrs(gs)
-        st = _lib.stream()
-        _lib.check(L.ocrl_naturecnn_bwd(_lib.ptr(obs), _lib.ptr(dout), arr, garr, B, H, W, C, groups, feat, use_feat, rep,
-                                        _lib.ptr(ctx.ws), ctx.ws.numel(), st))
-        return (None, None, *gs)
+        _bridge.launch(obs.device, _lib.lib().ocrl_naturecnn_bwd, _lib.ptr(obs), _lib.ptr(dout), _lib.ptrs(ps), _lib.ptrs(gs), B, H, W, C, *ctx.dims,
+                       _lib.ptr(ctx.ws), ctx.ws.numel())
+        return (None, None, None, *gs)
 
 
 def run_naturecnn(obs, dims, params, cin):
     """the encoders' forward: an autograd node that keeps the activations when a parameter needs a gradient, a bare call otherwise
     (a no_grad rollout keeps nothing)"""
-    _check_inputs(obs, params, dims, cin)
-    obs = obs.contiguous().float()
+    x, ps = _check_inputs(obs, params, dims, cin)
     if torch.is_grad_enabled() and any(p.requires_grad for p in params):
-        return _NatureCNNFn.apply(obs, dims, *params)
-    return _encode(obs, dims, [p.contiguous() for p in params], save=False)[0]
+        return _NatureCNNFn.apply(x, dims, ps, *params)
+    return _encode(x, dims, ps, save=False)[0]
 
 
 class NatureCNN_Module(nn.Module):
@@ -145,13 +115,13 @@ class NatureCNN_Module(nn.Module):
         n_conv = 4 if self._cnn_feat_size == 2 else 3        # the 4th conv comes with cnn_feat_size 2, with or without use_cnn_feat
         cnn = []
         cin = obs_channels
-        for cout, k, s in _CONVS[:n_conv]:
+        for cout, k, s in NATURE_CONVS[:n_conv]:      # _cnn.0 / .2 / .4 / .6
             cnn += [nn.Conv2d(cin, cout, kernel_size=k, stride=s, padding=0), nn.Identity()]
             cin = cout
         if not self._use_cnn_feat:
             cnn.append(nn.Flatten())
         self._cnn = nn.Sequential(*cnn)
-        side = _map_size(obs_size, n_conv)
+        side = conv_map_size(obs_size, n_conv)
         if side < 1:
             raise ValueError(f"NatureCNN: obs_size {obs_size} leaves an empty feature map (at least {36 if n_conv == 3 else 52} needed)")
         self._obs_channels = obs_channels

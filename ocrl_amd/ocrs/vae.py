@@ -16,10 +16,12 @@ import torch
 from torch import nn
 from torch.nn.utils import clip_grad_norm_
 
-from .. import _lib
-from .._lib import ptrs as _ptrs, stream as _stream
+from .. import _bridge, _lib
+from .._lib import ptrs as _ptrs
 from ..dist_utils import active_dist
 from .base import Base
+
+_WHO = "ocrl_amd.ocrs.VAE"
 
 
 def stages(obs_size, cnn_feat_size):
@@ -86,26 +88,19 @@ def param_shapes(C, n, f, L):
 
 
 def _check_inputs(obs, params, shapes, C, S):
+    """(observation, parameters) as the kernels read them"""
     if obs.dim() != 4 or obs.shape[1] != C or obs.shape[2] != S or obs.shape[3] != S:
-        raise ValueError(f"ocrl_amd.ocrs.VAE: expected observations [B, {C}, {S}, {S}], got {list(obs.shape)}")
-    if len(params) != len(shapes) or any(tuple(p.shape) != sh for p, sh in zip(params, shapes)):
-        raise ValueError(f"ocrl_amd.ocrs.VAE: parameter shapes {[list(p.shape) for p in params]} are not the module's {[list(s) for s in shapes]}")
-    if not obs.is_cuda:
-        raise RuntimeError("ocrl_amd.ocrs: tensors must live on the GPU (there is no CPU fallback)")
+        raise ValueError(f"{_WHO}: expected observations [B, {C}, {S}, {S}], got {list(obs.shape)}")
+    x, ps = _bridge.inputs(_WHO, obs, params, shapes)
     if obs.requires_grad:
-        raise RuntimeError("ocrl_amd.ocrs.VAE: the observation gets no gradient (the first convolution's input gradient is not built)")
-    for p in params:
-        if p.dtype != torch.float32 or p.device != obs.device:
-            raise RuntimeError(f"ocrl_amd.ocrs.VAE: parameters must be float32 on the observations' device {obs.device} (got {p.dtype} on {p.device})")
+        raise RuntimeError(f"{_WHO}: the observation gets no gradient (the first convolution's input gradient is not built)")
+    return x, ps
 
 
 def _ws(obs, dims, full):
     S, C, f, L, cnn, _ = dims
-    n = _lib.lib().ocrl_vae_ws_floats(obs.shape[0], S, C, f, L, cnn, int(full))
-    if n == 0:
-        raise ValueError(f"ocrl_amd.ocrs.VAE: shape not supported: batch {obs.shape[0]} of {C} x {S} x {S} images, cnn_feat_size {f}, "
-                         f"latent_dim {L}: " + _lib.lib().ocrl_last_error().decode())
-    return torch.empty(n, device=obs.device, dtype=torch.float32)
+    return _bridge.workspace(_WHO, _lib.lib().ocrl_vae_ws_floats(obs.shape[0], S, C, f, L, cnn, int(full)), obs.device,
+                             f"batch {obs.shape[0]} of {C} x {S} x {S} images, cnn_feat_size {f}, latent_dim {L}")
 
 
 def _rep_like(obs, dims):
@@ -120,9 +115,8 @@ def _fwd(obs, dims, params, full, eps=None, recon=None):
     ws = _ws(obs, dims, full)
     rep = _rep_like(obs, dims)
     metrics = torch.empty(3, device=obs.device, dtype=torch.float32) if full else None
-    _lib.check(_lib.lib().ocrl_vae_fwd(_lib.ptr(obs), _ptrs(params), _lib.ptr(eps) if full else None, _lib.ptr(rep),
-                                       _lib.ptr(metrics) if full else None, _lib.ptr(recon) if recon is not None else None, obs.shape[0], S, C,
-                                       f, L, cnn, float(kw), int(full), _lib.ptr(ws), ws.numel(), _stream()))
+    _bridge.launch(obs.device, _lib.lib().ocrl_vae_fwd, _lib.ptr(obs), _ptrs(params), _lib.ptr(eps), _lib.ptr(rep),
+                   _lib.ptr(metrics), _lib.ptr(recon), obs.shape[0], S, C, f, L, cnn, float(kw), int(full), _lib.ptr(ws), ws.numel())
     return rep, metrics, ws
 
 
@@ -131,38 +125,36 @@ def _bwd(obs, eps, dims, params, dloss, drep, ws, full):
     n = len(params) if full else 4 * stages(S, f) * 2 + 4            # the encoder's and _mu's entries
     gs = [torch.empty_like(p) for p in params[:n]]
     gptr = _ptrs(gs + [None] * (len(params) - n))
-    _lib.check(_lib.lib().ocrl_vae_bwd(_lib.ptr(obs), _lib.ptr(eps) if full else None, _ptrs(params),
-                                       _lib.ptr(dloss) if dloss is not None else None, _lib.ptr(drep) if drep is not None else None, gptr,
-                                       obs.shape[0], S, C, f, L, cnn, float(kw), int(full), _lib.ptr(ws), ws.numel(), _stream()))
+    _bridge.launch(obs.device, _lib.lib().ocrl_vae_bwd, _lib.ptr(obs), _lib.ptr(eps), _ptrs(params), _lib.ptr(dloss),
+                   _lib.ptr(drep), gptr, obs.shape[0], S, C, f, L, cnn, float(kw), int(full), _lib.ptr(ws), ws.numel())
     if cnn and not full:
         gs[-2:] = [None, None]                  # the token output does not pass through _mu
     return gs + [None] * (len(params) - n)
 
 
 class _EncodeFn(torch.autograd.Function):
-    """the encoder (and _mu): obs -> rep; backward from d rep"""
+    """the encoder (and _mu): obs -> rep; backward from d rep.  Over the observation and the parameters `ps` as _check_inputs returned
+    them; `params` are their attached originals, which get the gradients"""
 
     @staticmethod
-    def forward(ctx, obs, dims, *params):
-        ps = [p.contiguous() for p in params]
+    def forward(ctx, obs, dims, ps, *params):
         rep, _, ws = _fwd(obs, dims, ps, False)
-        ctx.save_for_backward(obs, *ps)     # torch's version check raises if the observation or a weight changes before the backward
+        ctx.save_for_backward(obs, *ps)
         ctx.dims, ctx.ws = dims, ws
         return rep
 
     @staticmethod
     def backward(ctx, drep):
         obs, *ps = ctx.saved_tensors
-        gs = _bwd(obs, None, ctx.dims, ps, None, drep.contiguous().float(), ctx.ws, False)
-        return (None, None, *gs)
+        gs = _bwd(obs, None, ctx.dims, ps, None, _bridge.cotangent(drep), ctx.ws, False)
+        return (None, None, None, *gs)
 
 
 class _LossFn(torch.autograd.Function):
     """get_loss: (obs, eps) -> (loss, mse, kld, rep); backward from d loss and d rep, summed (mse and kld are detached metrics)"""
 
     @staticmethod
-    def forward(ctx, obs, eps, dims, *params):
-        ps = [p.contiguous() for p in params]
+    def forward(ctx, obs, eps, dims, ps, *params):
         rep, m, ws = _fwd(obs, dims, ps, True, eps=eps)
         ctx.save_for_backward(obs, eps, *ps)
         ctx.dims, ctx.ws = dims, ws
@@ -175,14 +167,12 @@ class _LossFn(torch.autograd.Function):
     def backward(ctx, dloss, _dmse, _dkld, drep):
         obs, eps, *ps = ctx.saved_tensors
         if dloss is None and drep is None:
-            return (None, None, None) + (None,) * len(ps)
+            return (None, None, None, None) + (None,) * len(ps)
         # a missing cotangent counts as zero: without d loss the C backward skips the decoder and KL terms (zero gradients there)
         if dloss is not None:
-            dloss = dloss.reshape(1).contiguous().float()
-        if drep is not None:
-            drep = drep.contiguous().float()
-        gs = _bwd(obs, eps, ctx.dims, ps, dloss, drep, ctx.ws, True)
-        return (None, None, None, *gs)
+            dloss = dloss.reshape(1)
+        gs = _bwd(obs, eps, ctx.dims, ps, _bridge.cotangent(dloss), _bridge.cotangent(drep), ctx.ws, True)
+        return (None, None, None, None, *gs)
 
 
 class VAE_Module(nn.Module):
@@ -226,8 +216,7 @@ class VAE_Module(nn.Module):
         return param_shapes(self._obs_channels, self._n, self._cnn_feat_size, self._latent_dim)
 
     def _check(self, obs, params):
-        _check_inputs(obs, params, self._shapes(), self._obs_channels, self._obs_size)
-        return obs.contiguous().float()
+        return _check_inputs(obs, params, self._shapes()[:len(params)], self._obs_channels, self._obs_size)
 
     def _enc_params(self):
         n = 4 * self._n * 2 + 4
@@ -235,12 +224,11 @@ class VAE_Module(nn.Module):
 
     def forward(self, obs):
         """mu [B, latent], or with use_cnn_feat img_to_slot(enc(obs)) [B, f^2, 64]; the decoder does not run"""
-        ps = self._enc_params()
-        _check_inputs(obs, ps, self._shapes()[:len(ps)], self._obs_channels, self._obs_size)
-        obs = obs.contiguous().float()
-        if torch.is_grad_enabled() and any(p.requires_grad for p in ps):
-            return _EncodeFn.apply(obs, self._dims(), *ps)
-        return _fwd(obs, self._dims(), [p.contiguous() for p in ps], False)[0]
+        params = self._enc_params()
+        obs, ps = self._check(obs, params)
+        if torch.is_grad_enabled() and any(p.requires_grad for p in params):
+            return _EncodeFn.apply(obs, self._dims(), ps, *params)
+        return _fwd(obs, self._dims(), ps, False)[0]
 
     def draw_eps(self, obs):
         """eps = randn_like(std) [B, latent] on the observations' device (vae_module.py:52)"""
@@ -249,16 +237,16 @@ class VAE_Module(nn.Module):
 
     def loss_terms(self, obs, eps=None):
         """(loss, mse, kld, rep) through the HIP kernels; eps drawn here when not given (tests pass recorded noise)"""
-        ps = self._params()
-        obs = self._check(obs, ps)
+        params = self._params()
+        obs, ps = self._check(obs, params)
         if eps is None:
             eps = self.draw_eps(obs)
         eps = eps.contiguous().float()
         if eps.shape != (obs.shape[0], self._latent_dim) or eps.device != obs.device:
-            raise ValueError(f"ocrl_amd.ocrs.VAE: eps must be [{obs.shape[0]}, {self._latent_dim}] on {obs.device} (got {list(eps.shape)} on {eps.device})")
-        if torch.is_grad_enabled() and any(p.requires_grad for p in ps):
-            return _LossFn.apply(obs, eps, self._dims(), *ps)
-        rep, m, _ = _fwd(obs, self._dims(), [p.contiguous() for p in ps], True, eps=eps)
+            raise ValueError(f"{_WHO}: eps must be [{obs.shape[0]}, {self._latent_dim}] on {obs.device} (got {list(eps.shape)} on {eps.device})")
+        if torch.is_grad_enabled() and any(p.requires_grad for p in params):
+            return _LossFn.apply(obs, eps, self._dims(), ps, *params)
+        rep, m, _ = _fwd(obs, self._dims(), ps, True, eps=eps)
         return m[0], m[1], m[2], rep
 
     def get_loss(self, obs, with_rep=False, eps=None):
@@ -271,12 +259,11 @@ class VAE_Module(nn.Module):
     @torch.no_grad()
     def reconstruct(self, obs, eps=None):
         """the decoder's output [B, C, S, S] for obs (vae_module.py:80-87)"""
-        ps = self._params()
-        obs = self._check(obs, ps)
+        obs, ps = self._check(obs, self._params())
         if eps is None:
             eps = self.draw_eps(obs)
         recon = torch.empty_like(obs)
-        _fwd(obs, self._dims(), [p.contiguous() for p in ps], True, eps=eps.contiguous().float(), recon=recon)
+        _fwd(obs, self._dims(), ps, True, eps=eps.contiguous().float(), recon=recon)
         return recon
 
     def get_samples(self, obs) -> dict:

@@ -12,17 +12,12 @@ import math
 import torch
 from torch import nn
 
-from .. import _lib
+from .. import _bridge, _lib
+from .._bridge import NATURE_CONVS, conv_map_size, conv_shapes
 from .base import Base
 
-_CONVS = ((32, 8, 4), (64, 4, 2), (64, 3, 1))                    # (out channels, kernel, stride) of _net.0 / .2 / .4
+_WHO = "ocrl_amd.poolings.CNN"
 _FLAT = 1024                                                     # the reference's Linear(1024, rep_dim): a 64 x 64 map
-
-
-def _map_size(s):
-    for _, k, st in _CONVS:
-        s = (s - k) // st + 1 if s >= k else 0
-    return s
 
 
 class _NatureCNN(nn.Module):
@@ -31,7 +26,7 @@ class _NatureCNN(nn.Module):
     def __init__(self, in_dim, rep_dim, use_cnn_feat):
         super().__init__()
         net, c = [], in_dim
-        for cout, k, s in _CONVS:
+        for cout, k, s in NATURE_CONVS[:3]:            # _net.0 / .2 / .4
             net += [nn.Conv2d(c, cout, kernel_size=k, stride=s, padding=0), nn.Identity()]
             c = cout
         if not use_cnn_feat:
@@ -45,56 +40,40 @@ class _NatureCNN(nn.Module):
 
 
 def _check_inputs(tokens, params, in_dim, rep):
-    """what the C entry points cannot check: they get no parameter sizes and derive the Linear's input width from the map's side"""
+    """what the C entry points cannot check: they get no parameter sizes and derive the Linear's input width from the map's side.
+    Returns (tokens, parameters) as the kernels read them, and the map's side"""
     if tokens.dim() != 3 or tokens.shape[2] != in_dim:
-        raise ValueError(f"ocrl_amd.poolings.CNN: expected tokens [B, N, {in_dim}], got {list(tokens.shape)}")
+        raise ValueError(f"{_WHO}: expected tokens [B, N, {in_dim}], got {list(tokens.shape)}")
     side = math.isqrt(tokens.shape[1])
     if side * side != tokens.shape[1]:
-        raise ValueError(f"ocrl_amd.poolings.CNN: slot_to_img needs a square token map, got N = {tokens.shape[1]}")
-    o = _map_size(side)
+        raise ValueError(f"{_WHO}: slot_to_img needs a square token map, got N = {tokens.shape[1]}")
+    o = conv_map_size(side)
     if rep and 64 * o * o != _FLAT:
         raise ValueError(f"ocrl_amd.poolings.CNN_Linear: a {side} x {side} token map flattens to 64 x {o} x {o} = {64 * o * o} features, "
                          f"but the Linear takes {_FLAT} (a 64 x 64 map)")
-    shapes, c = [], in_dim
-    for cout, k, _ in _CONVS:
-        shapes += [(cout, c, k, k), (cout,)]
-        c = cout
-    if rep:
-        shapes += [(rep, _FLAT), (rep,)]
-    if len(params) != len(shapes) or any(tuple(p.shape) != sh for p, sh in zip(params, shapes)):
-        raise ValueError(f"ocrl_amd.poolings.CNN: parameter shapes {[list(p.shape) for p in params]} are not the head's "
-                         f"{[list(sh) for sh in shapes]}")
-    if not tokens.is_cuda:
-        raise RuntimeError("ocrl_amd.poolings: tensors must live on the GPU (there is no CPU fallback)")
-    for p in params:
-        if p.dtype != torch.float32 or p.device != tokens.device:
-            raise RuntimeError(f"ocrl_amd.poolings.CNN: parameters must be float32 on the tokens' device {tokens.device} "
-                               f"(got {p.dtype} on {p.device})")
-    return side
+    return (*_bridge.inputs(_WHO, tokens, params, conv_shapes(in_dim) + ([(rep, _FLAT), (rep,)] if rep else [])), side)
 
 
 def _run(tokens, side, rep, params, save):
     """one ocrl_pool_cnn_fwd call; returns (out, ws)"""
-    L = _lib.lib()
+    L, dev = _lib.lib(), tokens.device
     B, _, D = tokens.shape
-    n = L.ocrl_pool_cnn_ws_floats(B, side, side, D, rep)
-    if n == 0:
-        raise ValueError(f"ocrl_amd.poolings.CNN: shape not supported: batch {B} of {side} x {side} x {D} token maps, rep_dim {rep}: "
-                         + L.ocrl_last_error().decode())
-    ws = torch.empty(n, device=tokens.device, dtype=torch.float32)
-    o = _map_size(side)
-    out = torch.empty((B, rep) if rep else (B, o * o, 64), device=tokens.device, dtype=torch.float32)
-    _lib.check(L.ocrl_pool_cnn_fwd(_lib.ptr(tokens), _lib.ptrs(params), _lib.ptr(out), B, side, side, D, rep, int(save), _lib.ptr(ws), n,
-                                   _lib.stream()))
+    ws = _bridge.workspace(_WHO, L.ocrl_pool_cnn_ws_floats(B, side, side, D, rep), dev,
+                           f"batch {B} of {side} x {side} x {D} token maps, rep_dim {rep}")
+    o = conv_map_size(side)
+    out = torch.empty((B, rep) if rep else (B, o * o, 64), device=dev, dtype=torch.float32)
+    _bridge.launch(dev, L.ocrl_pool_cnn_fwd, _lib.ptr(tokens), _lib.ptrs(params), _lib.ptr(out), B, side, side, D, rep, int(save), _lib.ptr(ws),
+                   ws.numel())
     return out, ws
 
 
 class _PoolCnnFn(torch.autograd.Function):
+    """over the tokens and the parameters `ps` as _check_inputs returned them; `params` are their attached originals, which get the
+    gradients"""
+
     @staticmethod
-    def forward(ctx, tokens, side, rep, *params):
-        ps = [p.detach().contiguous() for p in params]
+    def forward(ctx, tokens, side, rep, ps, *params):
         out, ws = _run(tokens, side, rep, ps, save=True)
-        # through save_for_backward, so that torch's version check raises if the tokens or a weight change in place before the backward
         ctx.save_for_backward(tokens, *ps)
         ctx.side, ctx.rep, ctx.ws = side, rep, ws
         return out
@@ -102,25 +81,23 @@ class _PoolCnnFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout):
         tokens, *ps = ctx.saved_tensors
-        L = _lib.lib()
         B, _, D = tokens.shape
-        dout = dout.contiguous().float()
+        dout = _bridge.cotangent(dout)
         gs = [torch.empty_like(p) for p in ps]
         dt = torch.empty_like(tokens) if ctx.needs_input_grad[0] else None
-        _lib.check(L.ocrl_pool_cnn_bwd(_lib.ptr(tokens), _lib.ptr(dout), _lib.ptrs(ps), _lib.ptr(dt), _lib.ptrs(gs), B, ctx.side, ctx.side, D,
-                                       ctx.rep, _lib.ptr(ctx.ws), ctx.ws.numel(), _lib.stream()))
-        return (dt, None, None, *gs)
+        _bridge.launch(tokens.device, _lib.lib().ocrl_pool_cnn_bwd, _lib.ptr(tokens), _lib.ptr(dout), _lib.ptrs(ps), _lib.ptr(dt), _lib.ptrs(gs),
+                       B, ctx.side, ctx.side, D, ctx.rep, _lib.ptr(ctx.ws), ctx.ws.numel())
+        return (dt, None, None, None, *gs)
 
 
 def run_pool_cnn(tokens, net):
     """NatureCNN over slot_to_img(tokens): an autograd node that keeps the activations when anything needs a gradient, a bare call
     otherwise (a no_grad rollout keeps nothing)"""
     params = net.param_list()
-    side = _check_inputs(tokens, params, net.in_dim, net.rep_dim)
-    tokens = tokens.contiguous().float()
+    x, ps, side = _check_inputs(tokens, params, net.in_dim, net.rep_dim)
     if torch.is_grad_enabled() and (tokens.requires_grad or any(p.requires_grad for p in params)):
-        return _PoolCnnFn.apply(tokens, side, net.rep_dim, *params)
-    return _run(tokens, side, net.rep_dim, [p.detach().contiguous() for p in params], save=False)[0]
+        return _PoolCnnFn.apply(x, side, net.rep_dim, ps, *params)
+    return _run(x, side, net.rep_dim, ps, save=False)[0]
 
 
 class CNN_Linear_Module(nn.Module):

@@ -5,56 +5,39 @@ then an MLP f.
 ``state_dict()`` keys, shapes and initialisation are the reference's and its checkpoints load unchanged; the containers' ``forward`` is
 never called.  The arithmetic is ``ocrl_pool_rn_fwd/_bwd`` (HIP: the first g layer factored over the slots, the pairs expanded by an
 addition), wrapped in a ``torch.autograd.Function``.  No CPU fallback: a CPU tensor raises."""
-import ctypes
-
 import torch
 from torch import nn
 
-from .. import _lib
+from .. import _bridge, _lib
 from .base import Base
 
-
-def _int_array(v):
-    return (ctypes.c_int * len(v))(*v)
+_WHO = "ocrl_amd.poolings.RN"
 
 
 class _RNFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, slots, g_dims, f_dims, *params):
-        if not slots.is_cuda:
-            raise RuntimeError("ocrl_amd.poolings: tensors must live on the GPU (there is no CPU fallback)")
-        L = _lib.lib()
+        slots, ps = _bridge.inputs(_WHO, slots, params)
+        L, dev = _lib.lib(), slots.device
         B, K, D = slots.shape
-        slots = slots.contiguous().float()
-        ps = [p.detach().contiguous() for p in params]
-        gd, fd = _int_array(g_dims), _int_array(f_dims)
-        n = L.ocrl_pool_rn_ws_floats(B, K, D, len(g_dims), gd, len(f_dims), fd)
-        if n == 0:
-            raise ValueError(f"ocrl_amd.poolings.RN: shape not supported: batch {B}, {K} slots of width {D}, g_dims {list(g_dims)}, "
-                             f"f_dims {list(f_dims)} (needs >= 2 slots, widths that are multiples of 4, and batch * K * (K - 1) pair rows "
-                             f"times the widest g layer below 2^31)")
-        ws = torch.empty(n, device=slots.device, dtype=torch.float32)
-        out = torch.empty(B, f_dims[-1], device=slots.device, dtype=torch.float32)
-        arr = _lib.ptrs(ps)
-        st = _lib.stream()
-        _lib.check(L.ocrl_pool_rn_fwd(_lib.ptr(slots), arr, _lib.ptr(out), B, K, D, len(g_dims), gd, len(f_dims), fd, _lib.ptr(ws), n, st))
-        ctx.dims, ctx.ws, ctx.ps, ctx.slots = (g_dims, f_dims), ws, ps, slots
-        ctx.need_dslots = ctx.needs_input_grad[0]      # read from the autograd node: the converted copy above carries no requires_grad
+        dims = (len(g_dims), _bridge.ints(g_dims), len(f_dims), _bridge.ints(f_dims))
+        ws = _bridge.workspace(_WHO, L.ocrl_pool_rn_ws_floats(B, K, D, *dims), dev,
+                               f"batch {B}, {K} slots of width {D}, g_dims {list(g_dims)}, f_dims {list(f_dims)}")
+        out = torch.empty(B, f_dims[-1], device=dev, dtype=torch.float32)
+        _bridge.launch(dev, L.ocrl_pool_rn_fwd, _lib.ptr(slots), _lib.ptrs(ps), _lib.ptr(out), B, K, D, *dims, _lib.ptr(ws), ws.numel())
+        ctx.save_for_backward(slots, *ps)
+        ctx.dims, ctx.ws = dims, ws
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        L = _lib.lib()
-        g_dims, f_dims = ctx.dims
-        B, K, D = ctx.slots.shape
-        dout = dout.contiguous().float()
-        gs = [torch.empty_like(p) for p in ctx.ps]
-        ds = torch.empty_like(ctx.slots) if ctx.need_dslots else None
-        arr = _lib.ptrs(ctx.ps)
-        garr = _lib.ptrs(gs)
-        st = _lib.stream()
-        _lib.check(L.ocrl_pool_rn_bwd(_lib.ptr(ctx.slots), _lib.ptr(dout), arr, _lib.ptr(ds), garr, B, K, D, len(g_dims), _int_array(g_dims),
-                                      len(f_dims), _int_array(f_dims), _lib.ptr(ctx.ws), ctx.ws.numel(), st))
+        slots, *ps = ctx.saved_tensors
+        B, K, D = slots.shape
+        dout = _bridge.cotangent(dout)
+        gs = [torch.empty_like(p) for p in ps]
+        ds = torch.empty_like(slots) if ctx.needs_input_grad[0] else None
+        _bridge.launch(slots.device, _lib.lib().ocrl_pool_rn_bwd, _lib.ptr(slots), _lib.ptr(dout), _lib.ptrs(ps), _lib.ptr(ds), _lib.ptrs(gs),
+                       B, K, D, *ctx.dims, _lib.ptr(ctx.ws), ctx.ws.numel())
         return (ds, None, None, *gs)
 
 
@@ -84,8 +67,6 @@ class RN_Module(nn.Module):
         return [p for seq in (self._g, self._f) for m in seq if isinstance(m, nn.Linear) for p in (m.weight, m.bias)]
 
     def forward(self, state):
-        if state.shape[1] < 2:
-            raise ValueError(f"RN pooling needs at least 2 slots (got {state.shape[1]})")
         return _RNFn.apply(state, self._g_dims, self._f_dims, *self._param_list())
 
 

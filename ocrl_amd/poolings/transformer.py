@@ -10,8 +10,10 @@ import math
 import torch
 from torch import nn
 
-from .. import _lib
+from .. import _bridge, _lib
 from .base import Base
+
+_WHO = "ocrl_amd.poolings.Transformer"
 
 
 class _ClsToken(nn.Module):
@@ -67,12 +69,8 @@ class _LinearFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias, relu):
-        if not x.is_cuda:
-            raise RuntimeError("ocrl_amd.poolings: tensors must live on the GPU (there is no CPU fallback)")
-        L = _lib.lib()
         shp = x.shape
-        x2 = x.reshape(-1, shp[-1]).contiguous().float()
-        w, b = weight.detach().contiguous(), bias.detach().contiguous()
+        x2, (w, b) = _bridge.inputs(_WHO + ".Linear", x.reshape(-1, shp[-1]), (weight, bias))
         ctx.kpad = (-x2.shape[1]) % 4            # the GEMM wants a k extent that is a multiple of 4 (obj_emb of cw_embedding: 3*128 + 3 inputs)
         if ctx.kpad:
             x2 = torch.nn.functional.pad(x2, (0, ctx.kpad))
@@ -80,31 +78,30 @@ class _LinearFn(torch.autograd.Function):
         M, K = x2.shape
         N = weight.shape[0]
         y = torch.empty(M, N, device=x.device, dtype=torch.float32)
-        st = _lib.stream()
-        _lib.check(L.ocrl_gemm(_lib.ptr(x2), _lib.ptr(w), _lib.ptr(y), M, N, K, K, K, N, 1, 1, 1.0, _lib.ptr(b), int(relu), None, 0, None, 0, 1, None, st))
+        _bridge.launch(x.device, _lib.lib().ocrl_gemm, _lib.ptr(x2), _lib.ptr(w), _lib.ptr(y), M, N, K, K, K, N, 1, 1, 1.0, _lib.ptr(b), int(relu),
+                       None, 0, None, 0, 1, None)
         ctx.save_for_backward(x2, w, y)
         ctx.relu, ctx.shape = bool(relu), shp
         return y.reshape(*shp[:-1], N)
 
     @staticmethod
     def backward(ctx, dy):
-        L = _lib.lib()
+        gemm = _lib.lib().ocrl_gemm
         x2, w, y = ctx.saved_tensors
         M, K = x2.shape
         N = w.shape[0]
-        dy2 = dy.reshape(M, N).contiguous().float()
+        dy2 = _bridge.cotangent(dy.reshape(M, N))
         if ctx.relu:
             dy2 = dy2 * (y > 0)
-        st = _lib.stream()
-        dx = dw = None
+        dx = None
         if ctx.needs_input_grad[0]:
             dx = torch.empty(M, K, device=dy.device, dtype=torch.float32)           # dx = dy W        (NN)
-            _lib.check(L.ocrl_gemm(_lib.ptr(dy2), _lib.ptr(w), _lib.ptr(dx), M, K, N, N, K, K, 1, 0, 1.0, None, 0, None, 0, None, 0, 1, None, st))
+            _bridge.launch(x2.device, gemm, _lib.ptr(dy2), _lib.ptr(w), _lib.ptr(dx), M, K, N, N, K, K, 1, 0, 1.0, None, 0, None, 0, None, 0, 1, None)
             if ctx.kpad:
                 dx = dx[:, :K - ctx.kpad]
             dx = dx.reshape(ctx.shape)
         dw = torch.empty(N, K, device=dy.device, dtype=torch.float32)               # dW = dy^T x     (TN over the rows)
-        _lib.check(L.ocrl_gemm(_lib.ptr(dy2), _lib.ptr(x2), _lib.ptr(dw), N, K, M, N, K, K, 0, 0, 1.0, None, 0, None, 0, None, 0, 1, None, st))
+        _bridge.launch(x2.device, gemm, _lib.ptr(dy2), _lib.ptr(x2), _lib.ptr(dw), N, K, M, N, K, K, 0, 0, 1.0, None, 0, None, 0, None, 0, 1, None)
         if ctx.kpad:
             dw = dw[:, :K - ctx.kpad].contiguous()
         return dx, dw, dy2.sum(0), None
@@ -136,43 +133,30 @@ def _slot_mlp(widths):
 class _PoolFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, slots, pos, geom, drop_p, seed, *params):
-        if not slots.is_cuda:
-            raise RuntimeError("ocrl_amd.poolings: tensors must live on the GPU (there is no CPU fallback)")
-        L = _lib.lib()
-        d, nhead, ff, nl = geom
+        slots, ps = _bridge.inputs(_WHO, slots, params)
+        L, dev = _lib.lib(), slots.device
         B, K, Din = slots.shape
-        slots = slots.contiguous().float()
-        ps = [p.detach().contiguous() for p in params]
         # token sets beyond the short path's limits (a CNN feature map: thousands of tokens, rep_dim = channels + 3) take the long path
         use_long = K + 1 > 32 or Din % 4 != 0
-        if use_long:
-            n = L.ocrl_pool_transformer_long_ws_floats(B, K, Din, d, nhead, ff, nl)
-        else:
-            n = L.ocrl_pool_transformer_ws_floats(B, K, d, nhead, ff, nl)
-        ws = torch.empty(n, device=slots.device, dtype=torch.float32)
-        out = torch.empty(B, d, device=slots.device, dtype=torch.float32)
-        arr = _lib.ptrs(ps)
-        st = _lib.stream()
-        fwd = L.ocrl_pool_transformer_long_fwd if use_long else L.ocrl_pool_transformer_fwd
-        _lib.check(fwd(_lib.ptr(slots), arr, _lib.ptr(pos), _lib.ptr(out), B, K, Din, d, nhead, ff, nl, drop_p, seed, _lib.ptr(ws), n, st))
-        ctx.geom, ctx.drop_p, ctx.seed, ctx.ws, ctx.ps, ctx.slots, ctx.use_long = geom, drop_p, seed, ws, ps, slots, use_long
-        ctx.need_dslots = ctx.needs_input_grad[0]      # read from the autograd node: the converted copy above carries no requires_grad
+        n = L.ocrl_pool_transformer_long_ws_floats(B, K, Din, *geom) if use_long else L.ocrl_pool_transformer_ws_floats(B, K, *geom)
+        ws = _bridge.workspace(_WHO, n, dev, f"batch {B}, {K} tokens of width {Din}, (d_model, nhead, dim_feedforward, num_layers) {tuple(geom)}",
+                               reason=None if use_long else "num_layers must be 1 .. 8")   # the short path's size function records no reason
+        out = torch.empty(B, geom[0], device=dev, dtype=torch.float32)
+        _bridge.launch(dev, L.ocrl_pool_transformer_long_fwd if use_long else L.ocrl_pool_transformer_fwd, _lib.ptr(slots), _lib.ptrs(ps),
+                       _lib.ptr(pos), _lib.ptr(out), B, K, Din, *geom, drop_p, seed, _lib.ptr(ws), n)
+        ctx.save_for_backward(slots, *ps)
+        ctx.args, ctx.ws, ctx.use_long = (*geom, drop_p, seed), ws, use_long
         return out
 
     @staticmethod
     def backward(ctx, dout):
         L = _lib.lib()
-        d, nhead, ff, nl = ctx.geom
-        B, K, Din = ctx.slots.shape
-        dout = dout.contiguous().float()
-        gs = [torch.empty_like(p) for p in ctx.ps]
-        ds = torch.empty_like(ctx.slots) if ctx.need_dslots else None
-        arr = _lib.ptrs(ctx.ps)
-        garr = _lib.ptrs(gs)
-        st = _lib.stream()
-        bwd = L.ocrl_pool_transformer_long_bwd if ctx.use_long else L.ocrl_pool_transformer_bwd
-        _lib.check(bwd(_lib.ptr(ctx.slots), _lib.ptr(dout), arr, _lib.ptr(ds), garr, B, K, Din, d, nhead, ff, nl, ctx.drop_p, ctx.seed,
-                       _lib.ptr(ctx.ws), ctx.ws.numel(), st))
+        slots, *ps = ctx.saved_tensors
+        dout = _bridge.cotangent(dout)
+        gs = [torch.empty_like(p) for p in ps]
+        ds = torch.empty_like(slots) if ctx.needs_input_grad[0] else None
+        _bridge.launch(slots.device, L.ocrl_pool_transformer_long_bwd if ctx.use_long else L.ocrl_pool_transformer_bwd, _lib.ptr(slots),
+                       _lib.ptr(dout), _lib.ptrs(ps), _lib.ptr(ds), _lib.ptrs(gs), *slots.shape, *ctx.args, _lib.ptr(ctx.ws), ctx.ws.numel())
         return (ds, None, None, None, None, *gs)
 
 

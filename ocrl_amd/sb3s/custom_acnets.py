@@ -16,25 +16,18 @@ import numbers
 import torch
 from torch import nn
 
-from .. import _lib
+from .. import _bridge, _lib
 
+_WHO = "ocrl_amd.sb3s"
 _ACT_CODE = {nn.ReLU: 1, nn.Tanh: 2}
 PPO_SCALARS = ("loss", "policy_loss", "value_loss", "entropy_loss", "approx_kl", "clip_fraction")
 
 
-def _require_gpu(t):
-    if not t.is_cuda:
-        raise RuntimeError("ocrl_amd.sb3s: tensors must live on the GPU (there is no CPU fallback)")
-
-
-def _desc(B, F, A, dims, acts):
+def _desc(B, F, A, dims, acts, dev, keep=True):
+    """(descriptor, workspace) of a call"""
     d = _lib.acnet_desc(B, F, A, dims, acts)
-    n = _lib.lib().ocrl_acnet_ws_floats(ctypes.byref(d))
-    if n == 0:
-        raise ValueError(f"ocrl_amd.sb3s: shape not supported: batch {B}, feature_dim {F}, {A} actions, trunk widths {[list(x) for x in dims]} "
-                         f"(needs batch >= 1, widths that are multiples of 4 up to 256, at most 8 layers per trunk, at most 64 actions): "
-                         + _lib.lib().ocrl_last_error().decode())
-    return d, n
+    return d, _bridge.workspace(_WHO, _lib.lib().ocrl_acnet_ws_floats(ctypes.byref(d)), dev,
+                                f"batch {B}, feature_dim {F}, {A} actions, trunk widths {[list(x) for x in dims]}", keep)
 
 
 class _AcnetFn(torch.autograd.Function):
@@ -42,68 +35,60 @@ class _AcnetFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, features, dims, acts, A, *params):
-        _require_gpu(features)
-        L = _lib.lib()
-        x = features.contiguous().float()
+        x, ps = _bridge.inputs(_WHO, features, params)
+        dev = x.device
         B, F = x.shape
-        ps = [p.detach().contiguous() for p in params]
-        d, n = _desc(B, F, A, dims, acts)
         need_grad = any(ctx.needs_input_grad)
-        ws = torch.empty(n if need_grad else 0, device=x.device, dtype=torch.float32)
+        d, ws = _desc(B, F, A, dims, acts, dev, need_grad)
         h = dims[0][-1] if dims[0] else F
         if A > 0:
-            outs = (torch.empty(B, A, device=x.device), torch.empty(B, device=x.device))
+            outs = (torch.empty(B, A, device=dev), torch.empty(B, device=dev))
             args = (None, None, _lib.ptr(outs[0]), _lib.ptr(outs[1]))
         else:
-            outs = (torch.empty(B, dims[1][-1] if dims[1] else h, device=x.device), torch.empty(B, dims[2][-1] if dims[2] else h, device=x.device))
+            outs = (torch.empty(B, dims[1][-1] if dims[1] else h, device=dev), torch.empty(B, dims[2][-1] if dims[2] else h, device=dev))
             args = (_lib.ptr(outs[0]), _lib.ptr(outs[1]), None, None)
-        _lib.check(L.ocrl_acnet_fwd(ctypes.byref(d), _lib.ptr(x), _lib.ptrs(ps) if ps else None, *args, 1 if need_grad else 0,
-                                    _lib.ptr(ws) if need_grad else None, ws.numel(), _lib.stream()))
-        ctx.d, ctx.ws, ctx.ps, ctx.x, ctx.A = d, ws, ps, x, A
-        ctx.need_dx = ctx.needs_input_grad[0]          # read from the autograd node: the converted copy above carries no requires_grad
+        _bridge.launch(dev, _lib.lib().ocrl_acnet_fwd, ctypes.byref(d), _lib.ptr(x), _lib.ptrs(ps) if ps else None, *args, int(need_grad),
+                       _lib.ptr(ws) if need_grad else None, ws.numel())
+        ctx.save_for_backward(x, *ps)
+        ctx.d, ctx.ws, ctx.A = d, ws, A
         ctx.set_materialize_grads(False)
         return outs
 
     @staticmethod
     def backward(ctx, g0, g1):
-        L = _lib.lib()
-        g0 = None if g0 is None else g0.contiguous().float()
-        g1 = None if g1 is None else g1.contiguous().float()
-        gs = [torch.empty_like(p) for p in ctx.ps]
-        dx = torch.empty_like(ctx.x) if ctx.need_dx else None
+        x, *ps = ctx.saved_tensors
+        g0, g1 = _bridge.cotangent(g0), _bridge.cotangent(g1)          # kept alive to the launch: the conversion may have copied them
+        gs = [torch.empty_like(p) for p in ps]
+        dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
         cot = (None, None, _lib.ptr(g0), _lib.ptr(g1)) if ctx.A > 0 else (_lib.ptr(g0), _lib.ptr(g1), None, None)
-        _lib.check(L.ocrl_acnet_bwd(ctypes.byref(ctx.d), _lib.ptr(ctx.x), _lib.ptrs(ctx.ps) if gs else None, *cot, _lib.ptr(dx),
-                                    _lib.ptrs(gs) if gs else None, _lib.ptr(ctx.ws), ctx.ws.numel(), _lib.stream()))
+        _bridge.launch(x.device, _lib.lib().ocrl_acnet_bwd, ctypes.byref(ctx.d), _lib.ptr(x), _lib.ptrs(ps) if gs else None, *cot, _lib.ptr(dx),
+                       _lib.ptrs(gs) if gs else None, _lib.ptr(ctx.ws), ctx.ws.numel())
         return (dx, None, None, None, *gs)
 
 
 class _PPOFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, features, actions, old_log_prob, advantages, returns, hyper, dims, acts, A, *params):
-        _require_gpu(features)
-        L = _lib.lib()
-        x = features.contiguous().float()
+        x, ps = _bridge.inputs(_WHO, features, params)
+        dev = x.device
         B, F = x.shape
         clip_range, vf_coef, ent_coef, normalize = hyper
         if normalize and B < 2:
-            raise ValueError("ocrl_amd.sb3s.ppo_loss: normalize_advantage needs a batch of at least 2 (the std of one advantage is undefined)")
-        dev = x.device
+            raise ValueError(f"{_WHO}.ppo_loss: normalize_advantage needs a batch of at least 2 (the std of one advantage is undefined)")
         vec = lambda t, dt: t.to(device=dev, dtype=dt).reshape(-1).contiguous()
         actions, old_log_prob = vec(actions, torch.int64), vec(old_log_prob, torch.float32)
         advantages, returns = vec(advantages, torch.float32), vec(returns, torch.float32)
         for name, t in (("actions", actions), ("old_log_prob", old_log_prob), ("advantages", advantages), ("returns", returns)):
             if t.numel() != B:
-                raise ValueError(f"ocrl_amd.sb3s.ppo_loss: {name} has {t.numel()} entries for a batch of {B}")
-        ps = [p.detach().contiguous() for p in params]
-        d, n = _desc(B, F, A, dims, acts)
-        ws = torch.empty(n, device=dev, dtype=torch.float32)
+                raise ValueError(f"{_WHO}.ppo_loss: {name} has {t.numel()} entries for a batch of {B}")
+        d, ws = _desc(B, F, A, dims, acts, dev)
         scal = torch.empty(6, device=dev, dtype=torch.float32)
         gs = [torch.empty_like(p) for p in ps]
         dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
-        _lib.check(L.ocrl_acnet_ppo_fwd_bwd(ctypes.byref(d), _lib.ptr(x), _lib.ptrs(ps), _lib.ptr(actions), _lib.ptr(old_log_prob), _lib.ptr(advantages),
-                                            _lib.ptr(returns), float(clip_range), float(vf_coef), float(ent_coef), int(bool(normalize)), _lib.ptr(scal),
-                                            _lib.ptr(dx), _lib.ptrs(gs), _lib.ptr(ws), n, _lib.stream()))
-        ctx.gs, ctx.dx = gs, dx
+        _bridge.launch(dev, _lib.lib().ocrl_acnet_ppo_fwd_bwd, ctypes.byref(d), _lib.ptr(x), _lib.ptrs(ps), _lib.ptr(actions), _lib.ptr(old_log_prob),
+                       _lib.ptr(advantages), _lib.ptr(returns), float(clip_range), float(vf_coef), float(ent_coef), int(bool(normalize)),
+                       _lib.ptr(scal), _lib.ptr(dx), _lib.ptrs(gs), _lib.ptr(ws), ws.numel())
+        ctx.gs, ctx.dx = gs, dx              # the gradients are the forward's own outputs: the backward reads nothing else again
         ctx.mark_non_differentiable(scal)
         return scal[0].clone(), scal
 
@@ -152,9 +137,9 @@ class CustomNetwork(nn.Module):
         return [p for seq in self._trunks() for m in seq if isinstance(m, nn.Linear) for p in (m.weight, m.bias)]
 
     def forward(self, features):
-        _require_gpu(features)
         dims, acts = self._layout()
         if not any(dims):                                   # the reference returns its input object itself, twice
+            _bridge.gpu_input(_WHO, features)               # no CPU path, even where nothing is computed
             return features, features
         return _AcnetFn.apply(features, dims, acts, 0, *self._param_list())
 
@@ -268,15 +253,15 @@ def ppo_loss(policy, features, actions, old_log_prob, advantages, returns, clip_
 
 def compute_gae(rewards, values, episode_starts, last_values, dones, gamma, gae_lambda):
     """advantages, returns [T, E] of a rollout on the device (rewards, values, episode_starts [T, E]; last_values, dones [E])"""
-    _require_gpu(rewards)
+    rewards = _bridge.gpu_input(_WHO + ".compute_gae", rewards)
     f = lambda t: t.to(device=rewards.device, dtype=torch.float32).contiguous()
-    rewards, values, episode_starts = f(rewards), f(values), f(episode_starts)
+    values, episode_starts = f(values), f(episode_starts)
     T, E = rewards.shape
     last_values, dones = f(last_values).reshape(E), f(dones).reshape(E)
     if values.shape != (T, E) or episode_starts.shape != (T, E):
-        raise ValueError(f"ocrl_amd.sb3s.compute_gae: rewards, values and episode_starts must share the shape [T, E] (got {tuple(rewards.shape)}, "
+        raise ValueError(f"{_WHO}.compute_gae: rewards, values and episode_starts must share the shape [T, E] (got {tuple(rewards.shape)}, "
                          f"{tuple(values.shape)}, {tuple(episode_starts.shape)})")
     adv, ret = torch.empty_like(rewards), torch.empty_like(rewards)
-    _lib.check(_lib.lib().ocrl_gae(_lib.ptr(rewards), _lib.ptr(values), _lib.ptr(episode_starts), _lib.ptr(last_values), _lib.ptr(dones), _lib.ptr(adv),
-                                   _lib.ptr(ret), T, E, float(gamma), float(gae_lambda), _lib.stream()))
+    _bridge.launch(rewards.device, _lib.lib().ocrl_gae, _lib.ptr(rewards), _lib.ptr(values), _lib.ptr(episode_starts), _lib.ptr(last_values),
+                   _lib.ptr(dones), _lib.ptr(adv), _lib.ptr(ret), T, E, float(gamma), float(gae_lambda))
     return adv, ret

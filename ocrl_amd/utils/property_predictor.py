@@ -11,20 +11,17 @@ Kept from the reference: the soft-max is taken twice on the class outputs, the l
 ``mse_xy`` are its formulas, ``matching_mode`` is read and unused.  Different on purpose: the encoder is called under
 ``torch.no_grad()`` with frozen weights and ``update`` does not step the encoder's optimiser (the reference steps it on zero
 gradients, which moves a loaded encoder by its Adam momentum)."""
-import ctypes
 from types import SimpleNamespace
 
 import torch
 from torch import nn
 
-from .. import _lib
+from .. import _bridge, _lib
+from .._bridge import ints as _ints
 
+_WHO = "ocrl_amd.PropertyPredictor"
 SLOT_ENCODERS = ("SLATE", "SlotAttn", "Iodine")
 MAX_SLOTS = 12          # OCRL_PROBE_MAX_SLOTS
-
-
-def _ints(v):
-    return (ctypes.c_int * len(v))(*[int(x) for x in v])
 
 
 def property_indices(property_list, properties):
@@ -49,70 +46,53 @@ class _ProbeFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, rows, y, spec, *params):
-        if not (rows.is_cuda and y.is_cuda and all(p.is_cuda for p in params)):
-            raise RuntimeError("ocrl_amd.PropertyPredictor: tensors must live on the GPU (there is no CPU fallback)")
-        L = _lib.lib()
-        rows = rows.detach().contiguous().float()
-        y = y.contiguous().float()
+        rows, ps = _bridge.inputs(_WHO, rows.detach(), params)
+        y = _bridge.gpu_input(_WHO, y)
+        L, dev = _lib.lib(), rows.device
         B, N, T = y.shape
-        K, O, D = spec.K, spec.O, rows.shape[-1]
+        K, O, D, P = spec.K, spec.O, rows.shape[-1], len(spec.kind)
         if N > K:
-            raise ValueError(f"ocrl_amd.PropertyPredictor: {N} objects cannot be matched to {K} slots")
-        ps = [p.detach().contiguous() for p in params]
-        dims, P = _ints(spec.dims), len(spec.kind)
-        n = L.ocrl_probe_ws_floats(B, K, N, D, O, int(spec.slot_rows), len(spec.dims), dims, P)
-        if n == 0:
-            raise ValueError(f"ocrl_amd.PropertyPredictor: shape not supported: batch {B}, {K} slots (at most {MAX_SLOTS}), {N} objects, "
-                             f"rep_dim {D}, {O} outputs per slot, head widths {list(spec.dims)}")
-        dev = rows.device
-        ws = torch.empty(n, device=dev, dtype=torch.float32)
+            raise ValueError(f"{_WHO}: {N} objects cannot be matched to {K} slots")
+        head = (B, K, N, D, O, int(spec.slot_rows), len(spec.dims), _ints(spec.dims))
+        ws = _bridge.workspace(_WHO, L.ocrl_probe_ws_floats(*head, P), dev, f"batch {B}, {K} slots (at most {MAX_SLOTS}), {N} objects, "
+                               f"rep_dim {D}, {O} outputs per slot, head widths {list(spec.dims)}")
         out = torch.empty(B, K, O, device=dev, dtype=torch.float32)
         cost = torch.empty(B, N, K, device=dev, dtype=torch.float32)
         col = torch.empty(B, N, device=dev, dtype=torch.int32)
         metrics = torch.empty(P + 2, device=dev, dtype=torch.float32)
-        arr = _lib.ptrs(ps)
-        st = _lib.stream(dev)
-        _lib.check(L.ocrl_probe_fwd(_lib.ptr(rows), arr, _lib.ptr(y), _lib.ptr(out), _lib.ptr(cost), _lib.ptr(col), _lib.ptr(metrics), B, K, N, D, T,
-                                    O, int(spec.slot_rows), len(spec.dims), dims, spec.slope, P, _ints(sum(spec.tgt, [])), _ints(sum(spec.out, [])),
-                                    _ints(spec.kind), _lib.ptr(ws), n, st))
-        ctx.spec, ctx.ws, ctx.ps, ctx.rows, ctx.shape = spec, ws, ps, rows, (B, K, N, D, O, P)
+        _bridge.launch(dev, L.ocrl_probe_fwd, _lib.ptr(rows), _lib.ptrs(ps), _lib.ptr(y), _lib.ptr(out), _lib.ptr(cost), _lib.ptr(col),
+                       _lib.ptr(metrics), B, K, N, D, T, O, *head[5:], spec.slope, P, _ints(sum(spec.tgt, [])), _ints(sum(spec.out, [])),
+                       _ints(spec.kind), _lib.ptr(ws), ws.numel())
+        ctx.save_for_backward(rows, *ps)
+        ctx.args, ctx.ws = (*head, spec.slope, P), ws
         ctx.mark_non_differentiable(out, cost, col, metrics)
         return metrics[0].clone(), out, cost, col, metrics
 
     @staticmethod
     def backward(ctx, dloss, *_):
-        L = _lib.lib()
-        spec = ctx.spec
-        B, K, N, D, O, P = ctx.shape
-        dloss = dloss.contiguous().float()
-        gs = [torch.empty_like(p) for p in ctx.ps]
-        arr = _lib.ptrs(ctx.ps)
-        garr = _lib.ptrs(gs)
-        st = _lib.stream(dloss.device)
-        _lib.check(L.ocrl_probe_bwd(_lib.ptr(ctx.rows), _lib.ptr(dloss), arr, garr, B, K, N, D, O, int(spec.slot_rows), len(spec.dims),
-                                    _ints(spec.dims), spec.slope, P, _lib.ptr(ctx.ws), ctx.ws.numel(), st))
+        rows, *ps = ctx.saved_tensors
+        dloss = _bridge.cotangent(dloss)
+        gs = [torch.empty_like(p) for p in ps]
+        _bridge.launch(rows.device, _lib.lib().ocrl_probe_bwd, _lib.ptr(rows), _lib.ptr(dloss), _lib.ptrs(ps), _lib.ptrs(gs), *ctx.args,
+                       _lib.ptr(ctx.ws), ctx.ws.numel())
         return (None, None, None, *gs)
 
 
 def probe_match(out, y, tgt, outr, kind, dloss=None, want_grad=True):
     """ocrl_probe_match on head outputs a host brings itself: out [B, K, O], y [B, N, T] on the GPU ->
     dict(cost [B, N, K], col [B, N] int32, metrics [P + 2], dout [B, K, O] or None)"""
-    if not (out.is_cuda and y.is_cuda):
-        raise RuntimeError("ocrl_amd.probe_match: tensors must live on the GPU (there is no CPU fallback)")
-    L = _lib.lib()
-    out, y = out.contiguous().float(), y.contiguous().float()
+    out, y = _bridge.gpu_input("ocrl_amd.probe_match", out), _bridge.gpu_input("ocrl_amd.probe_match", y)
+    L, dev = _lib.lib(), out.device
     (B, K, O), (_, N, T) = out.shape, y.shape
     P = len(kind)
-    dev = out.device
-    n = max(L.ocrl_probe_match_ws_floats(B, P), 1)
-    ws = torch.empty(n, device=dev, dtype=torch.float32)
+    ws = _bridge.workspace("ocrl_amd.probe_match", L.ocrl_probe_match_ws_floats(B, P), dev, f"batch {B}, {P} properties",
+                           reason="the batch must be at least 1 and the properties 1 .. 8")
     cost = torch.empty(B, N, K, device=dev, dtype=torch.float32)
     col = torch.empty(B, N, device=dev, dtype=torch.int32)
     metrics = torch.empty(P + 2, device=dev, dtype=torch.float32)
     dout = torch.zeros_like(out) if want_grad else None
-    st = _lib.stream(dev)
-    _lib.check(L.ocrl_probe_match(_lib.ptr(out), O, K * O, _lib.ptr(y), _lib.ptr(dloss), _lib.ptr(cost), _lib.ptr(col), _lib.ptr(metrics),
-                                  _lib.ptr(dout), B, K, N, T, O, P, _ints(sum(tgt, [])), _ints(sum(outr, [])), _ints(kind), _lib.ptr(ws), n, st))
+    _bridge.launch(dev, L.ocrl_probe_match, _lib.ptr(out), O, K * O, _lib.ptr(y), _lib.ptr(dloss), _lib.ptr(cost), _lib.ptr(col), _lib.ptr(metrics),
+                   _lib.ptr(dout), B, K, N, T, O, P, _ints(sum(tgt, [])), _ints(sum(outr, [])), _ints(kind), _lib.ptr(ws), ws.numel())
     return dict(cost=cost, col=col, metrics=metrics, dout=dout)
 
 
@@ -185,7 +165,7 @@ class PropertyPredictor:
             B, D = x.shape
             K, rows = self._num_slots_for_dist_rep, x
         if y.shape[1] > K:
-            raise ValueError(f"ocrl_amd.PropertyPredictor: {y.shape[1]} objects cannot be matched to {K} slots")
+            raise ValueError(f"{_WHO}: {y.shape[1]} objects cannot be matched to {K} slots")
         params = [p for m in self._linears() for p in (m.weight, m.bias)]
         loss, out, cost, col, m = _ProbeFn.apply(rows, y, self._spec(K), *params)
         self.last_matching, self.last_output, self.last_cost = col, out, cost

@@ -15,14 +15,13 @@ def to_device(batch, device):
 def obs_from_uint8(u8):
     """uint8 [B,H,W,C] on the GPU -> fp32 [B,C,H,W] in [0,1] (utils/datasets.py:17 + the H2D copy of train_ocr.py:52-53), converted by
     the library's kernel: the host ships a quarter of the bytes and never touches the pixels"""
-    import ctypes
     from .. import _lib
     if not (u8.is_cuda and u8.dtype == torch.uint8 and u8.dim() == 4):
         raise RuntimeError("obs_from_uint8: expected a uint8 [B,H,W,C] tensor on the GPU")
     u8 = u8.contiguous()
     B, H, W, C = u8.shape
     out = torch.empty(B, C, H, W, dtype=torch.float32, device=u8.device)
-    _lib.check(_lib.lib().ocrl_obs_u8_to_f32(_lib.ptr(u8), _lib.ptr(out), B, H, W, C, ctypes.c_void_p(torch.cuda.current_stream(u8.device).cuda_stream)))
+    _lib.check(_lib.lib().ocrl_obs_u8_to_f32(_lib.ptr(u8), _lib.ptr(out), B, H, W, C, _lib.stream(u8.device)))
     return out
 
 
@@ -90,7 +89,7 @@ def ari_counts(truth, pred, fuse_fg=False):
     """ocrl_ari_counts on the current stream: truth [B, Ct, ...] and pred [B, Cp or K, ...] CUDA fp32 score stacks over the same pixels
     (any strides that flatten(2) can express are read in place).  Returns (table [B, Ct, Cp] int32, sums [B, 3] int64) on the device;
     fuse_fg: pred holds K = Cp - 1 maps and the foreground channel 1 - truth[:, -1] is formed in the kernel."""
-    from .. import _lib
+    from .. import _bridge, _lib
     t, p = truth.flatten(2), pred.flatten(2)
     B, Ct, N = t.shape
     Cp = p.shape[1] + (1 if fuse_fg else 0)
@@ -98,9 +97,8 @@ def ari_counts(truth, pred, fuse_fg=False):
         raise RuntimeError(f"ari_counts: truth {tuple(truth.shape)} and pred {tuple(pred.shape)} do not cover the same pixels")
     table = torch.empty(B, Ct, Cp, dtype=torch.int32, device=t.device)
     sums = torch.empty(B, 3, dtype=torch.int64, device=t.device)
-    with torch.cuda.device(t.device):
-        _lib.check(_lib.lib().ocrl_ari_counts(_lib.ptr(t), *t.stride(), Ct, _lib.ptr(p), *p.stride(), Cp, int(fuse_fg), B, N, _lib.ptr(table),
-                                              _lib.ptr(sums), _lib.stream(t.device)))
+    _bridge.launch(t.device, _lib.lib().ocrl_ari_counts, _lib.ptr(t), *t.stride(), Ct, _lib.ptr(p), *p.stride(), Cp, int(fuse_fg), B, N,
+                   _lib.ptr(table), _lib.ptr(sums))
     return table, sums
 
 

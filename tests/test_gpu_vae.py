@@ -200,12 +200,12 @@ def _raw_full(m, obs, eps, fill):
     met = torch.full((3,), fill, device=DEV)
     from ocrl_amd import _lib
     _lib.check(_lib.lib().ocrl_vae_fwd(_lib.ptr(obs), V._ptrs(ps), _lib.ptr(eps), _lib.ptr(rep), _lib.ptr(met), None, obs.shape[0], *dims[:5],
-                                       float(dims[5]), 1, _lib.ptr(ws), ws.numel(), V._stream()))
+                                       float(dims[5]), 1, _lib.ptr(ws), ws.numel(), _lib.stream()))
     gs = [torch.full_like(p, fill) for p in ps]
     drep = torch.ones_like(rep) * 0.01
     dloss = torch.ones(1, device=DEV)
     _lib.check(_lib.lib().ocrl_vae_bwd(_lib.ptr(obs), _lib.ptr(eps), V._ptrs(ps), _lib.ptr(dloss), _lib.ptr(drep), V._ptrs(gs), obs.shape[0], *dims[:5],
-                                       float(dims[5]), 1, _lib.ptr(ws), ws.numel(), V._stream()))
+                                       float(dims[5]), 1, _lib.ptr(ws), ws.numel(), _lib.stream()))
     torch.cuda.synchronize()
     return [met, rep] + gs
 
