@@ -316,6 +316,35 @@ int ocrl_vae_bwd(const float* obs, const float* eps, const float* const* w, cons
                  int obs_size, int obs_channels, int cnn_feat_size, int latent_dim, int use_cnn_feat, float kld_weight, int full, float* ws,
                  size_t ws_floats, void* stream);
 
+/* ---- Masked autoencoder (MAE, a ViT encoder and a lighter ViT decoder): ocrs/mae/models_mae.py, mae_module.py, configs/ocr/mae.yaml.
+ * obs [B, 3, S, S]; patch p, L = (S / p)^2 patches (<= 1024), P = 3 p p.  Encoder width D, `depth` blocks of `heads` heads; decoder
+ * width Dd, `ddepth` blocks of `dheads` heads; MLP ratio 4, LayerNorm eps 1e-6, exact GELU, no dropout.  Head sizes 16 / 32 / 48 / 64;
+ * D, Dd and P multiples of 4.  `w` = every parameter in state_dict order: cls_token [D], pos_embed [L + 1, D], mask_token [Dd],
+ * decoder_pos_embed [L + 1, Dd], patch_embed.proj.{weight [D, 3, p, p], bias}, per block {norm1, attn.qkv, attn.proj, norm2, mlp.fc1,
+ * mlp.fc2}.{weight, bias}, norm.*, decoder_embed.*, the decoder blocks, decoder_norm.*, decoder_pred.*: 14 + 12 (depth + ddepth) tensors.
+ * The two position tables are inputs without a gradient (their dw entries are not written and may be NULL).
+ * full = 0 (encode_full_patches, the rollout): all L patches; rep [B, L + 1, D] (the CLS row first) is the final norm's output.  noise,
+ *   metrics, pred, mask, ids_restore and len_keep are not read; _bwd starts from drep and writes the encoder-side entries of dw
+ *   (cls_token, patch_embed, blocks, norm).
+ * full = 1 (the masked pre-training loss): noise [B, L] is ranked per image (ties by index), the len_keep patches of the lowest noise
+ *   are embedded and encoded; rep [B, len_keep + 1, D] is the latent (may be NULL).  The decoder runs on L + 1 tokens.  metrics [2] =
+ *   (loss, mse), both sum(mask mean_j (pred - target)^2) / sum(mask), as the reference reports them; pred [B, L, P] in patchify's
+ *   (ph, pw, c) order, mask [B, L] (0 kept, 1 removed), ids_restore [B, L] (int) may each be NULL.  At len_keep == L no patch is removed,
+ *   the divisor is zero and the loss is NaN, as in the reference; pred is still valid.
+ * _bwd (same ws right after _fwd, same arguments): dloss (device scalar) the cotangent of the loss, drep that of rep; summed, a NULL one
+ *   counts as zero (dloss NULL: the decoder is skipped and the decoder-side entries of dw are zeroed); full = 0 requires drep.
+ * The observation gets no gradient.  Rejected shapes get ws_floats == 0 and fail in _fwd / _bwd. */
+#define OCRL_MAE_MAX_DEPTH 32
+size_t ocrl_mae_ws_floats(int B, int obs_size, int patch, int D, int depth, int heads, int Dd, int ddepth, int dheads, int len_keep, int full);
+int ocrl_mae_fwd(const float* obs, const float* const* w, const float* noise, float* rep, float* metrics, float* pred, float* mask,
+                 int* ids_restore, int B, int obs_size, int patch, int D, int depth, int heads, int Dd, int ddepth, int dheads, int len_keep,
+                 int full, float* ws, size_t ws_floats, void* stream);
+int ocrl_mae_bwd(const float* obs, const float* const* w, const float* dloss, const float* drep, float* const* dw, int B, int obs_size,
+                 int patch, int D, int depth, int heads, int Dd, int ddepth, int dheads, int len_keep, int full, float* ws, size_t ws_floats,
+                 void* stream);
+/* mae_rank alone (tests): ids_restore [B, L], ids_keep [B, len_keep] (int), mask [B, L] of noise [B, L] */
+int ocrl_mae_rank(const float* noise, int* ids_restore, int* ids_keep, float* mask, int B, int L, int len_keep, void* stream);
+
 /* ---- Slot property probe: utils/property_predictor.py:12-189 (configs/train_property_predictor.yaml) ----
  * A head (nl Linear layers, LeakyReLU(slope) between them; `linear`: nl = 1, `mlp3`: nl = 4 with dims = {256, 256, 256, O}) reads the
  * detached encoder rows and predicts, per slot, O = sum of the property widths.  slot_rows != 0: rows [B K, D], dims[nl-1] == O

@@ -179,6 +179,11 @@ def lib():
     L.ocrl_vae_ws_floats.restype = c_size_t
     L.ocrl_vae_fwd.argtypes = [p, POINTER(p), p, p, p, p] + [c_int] * 6 + [c_float, c_int, p, c_size_t, p]
     L.ocrl_vae_bwd.argtypes = [p, p, POINTER(p), p, p, POINTER(p)] + [c_int] * 6 + [c_float, c_int, p, c_size_t, p]
+    L.ocrl_mae_ws_floats.argtypes = [c_int] * 11
+    L.ocrl_mae_ws_floats.restype = c_size_t
+    L.ocrl_mae_fwd.argtypes = [p, POINTER(p), p, p, p, p, p, p] + [c_int] * 11 + [p, c_size_t, p]
+    L.ocrl_mae_bwd.argtypes = [p, POINTER(p), p, p, POINTER(p)] + [c_int] * 11 + [p, c_size_t, p]
+    L.ocrl_mae_rank.argtypes = [p, p, p, p, c_int, c_int, c_int, p]
     L.ocrl_probe_ws_floats.argtypes = [c_int] * 7 + [POINTER(c_int), c_int]
     L.ocrl_probe_ws_floats.restype = c_size_t
     L.ocrl_probe_fwd.argtypes = [p, POINTER(p), p, p, p, p, p] + [c_int] * 8 + [POINTER(c_int), c_float, c_int, POINTER(c_int), POINTER(c_int),

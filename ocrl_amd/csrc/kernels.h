@@ -228,6 +228,33 @@ int vae_kl_bwd_launch(const float* ml, const float* eps, const float* dlat, cons
 int vae_scale_launch(const float* x, float* y, const float* g, long long n, hipStream_t st);
 int vae_recon_nchw_launch(const float* r4, float* out, int B, int C, int HW, hipStream_t st);
 
+// ------------------------------------------------------------------ mae.hip (masked autoencoder: include/ocrl_hip.h ocrl_mae_*)
+#define MAE_MAX_PATCHES 1024    // a noise row is ranked in LDS
+// ranks of noise [B, L], ties by index: restore [B, L] = rank, keep [B, len_keep] = the indices of ranks < len_keep, mask [B, L] = (rank >=
+// len_keep); restore_out / mask_out (optional) get second copies
+int mae_rank_launch(const float* noise, int* restore, int* keep, float* mask, int* restore_out, float* mask_out, int B, int L, int len_keep,
+                    hipStream_t st);
+// out [B n, 3 p p]: patch ids[b, i] (null: i) of obs [B, 3, S, S] in (c, ph, pw) order
+int mae_patch_gather_launch(const float* obs, const int* ids, float* out, int B, int n, int S, int p, hipStream_t st);
+// x0 [B, n + 1, D]: row 0 = cls + pos[0], row 1 + i = embed[b, i] + pos[1 + ids[b, i]] (null: i); backward: dembed [B n, D], dcls [D]
+int mae_tokens_fwd_launch(const float* embed, const float* cls, const float* pos, const int* ids, float* x0, int B, int n, int D, hipStream_t st);
+int mae_tokens_bwd_launch(const float* dx0, float* dembed, float* dcls, int B, int n, int D, hipStream_t st);
+// xd [B, L + 1, Dd] from e [B, len_keep + 1, Dd]; backward: de, dmtok [Dd] (part: [B, Dd] scratch)
+int mae_unshuffle_fwd_launch(const float* e, const float* mtok, const float* dpos, const int* restore, float* xd, int B, int L, int len_keep, int Dd,
+                             hipStream_t st);
+int mae_unshuffle_bwd_launch(const float* dxd, const int* keep, const float* mask, float* de, float* dmtok, float* part, int B, int L, int len_keep,
+                             int Dd, hipStream_t st);
+int mae_gelu_fwd_launch(const float* pre, float* y, long long n, hipStream_t st);
+int mae_gelu_bwd_launch(const float* dy, const float* pre, float* dpre, long long n, hipStream_t st);     // dpre may be dy
+// LayerNorm of width F % 4 == 0; backward dx = LN'(dy) (+ resid), dg / db [F] through part: mae_ln_chunks(R) * 2 F floats
+int mae_ln_fwd_launch(const float* x, const float* g, const float* b, float* y, float* mean, float* rstd, long long R, int F, float eps, hipStream_t st);
+int mae_ln_chunks(long long R);
+int mae_ln_bwd_launch(const float* dy, const float* x, const float* mean, const float* rstd, const float* g, const float* resid, float* dx, float* dg,
+                      float* db, float* part, long long R, int F, hipStream_t st);
+// pred [B, L, 3 p p] against obs; part [B L] scratch and loss [1] (both null: no loss), dpred [B, L + 1, 3 p p] with a zero CLS row (null: none)
+int mae_loss_launch(const float* pred, const float* obs, const float* mask, const float* dloss, float* part, float* loss, float* dpred, int B, int L,
+                    int len_keep, int S, int p, hipStream_t st);
+
 // ------------------------------------------------------------------ conv.hip
 struct ConvArgs {
     const float* X = nullptr;       // [B,H,W,CIN] NHWC

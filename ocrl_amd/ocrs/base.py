@@ -1,6 +1,9 @@
 """Encoder wrapper API of the reference (ocrs/base.py:8-88), kept verbatim at the Python surface.
 Subclasses own ``_module`` (parameters, state_dict) and ``_opt``; the arithmetic is in libocrl_hip."""
 import torch
+from torch.nn.utils import clip_grad_norm_
+
+from ..dist_utils import active_dist
 
 
 class Base:
@@ -59,3 +62,35 @@ class Base:
         self._module.load_state_dict(checkpoint["ocr_module_state_dict"])
         if hasattr(self, "_opt") and "ocr_opt_state_dict" in checkpoint:
             self._opt.load_state_dict(checkpoint["ocr_opt_state_dict"])
+
+
+class AutogradUpdate:
+    """``to`` and ``update`` of the wrappers whose module trains through torch autograd and a torch optimiser in ``_opt`` (VAE, MAE)"""
+
+    def to(self, device) -> None:
+        self._module.to(device)
+        if hasattr(self, "_opt"):                                 # optimizer_to (utils/tools.py) for a resumed state
+            for st in self._opt.state.values():
+                for k, v in st.items():
+                    if torch.is_tensor(v):
+                        st[k] = v.to(device)
+
+    def update(self, obs, masks, step: int) -> dict:
+        """ocrs/base.py:60-74: zero_grad, loss, backward, [gradient all-reduce], optional clip_grad_norm_, optimiser step"""
+        if not hasattr(self, "_opt"):
+            return {}
+        self._opt.zero_grad()
+        metrics = self._module.get_loss(obs)
+        metrics["loss"].backward()
+        dist = active_dist()
+        if dist is not None:                                      # data-parallel: the mean gradient over the ranks
+            for p in self._module.parameters():
+                if p.grad is not None:
+                    dist.all_reduce(p.grad, op=dist.ReduceOp.SUM)
+                    p.grad.div_(dist.get_world_size())
+        lr = self._config.learning
+        if hasattr(lr, "clip"):
+            norm_type = getattr(lr, "clip_norm_type", "inf")
+            metrics["norm"] = clip_grad_norm_(self._module.parameters(), lr.clip, float(norm_type))
+        self._opt.step()
+        return metrics

@@ -14,12 +14,10 @@ import math
 import numpy as np
 import torch
 from torch import nn
-from torch.nn.utils import clip_grad_norm_
 
 from .. import _bridge, _lib
 from .._lib import ptrs as _ptrs
-from ..dist_utils import active_dist
-from .base import Base
+from .base import AutogradUpdate, Base
 
 _WHO = "ocrl_amd.ocrs.VAE"
 
@@ -271,7 +269,7 @@ class VAE_Module(nn.Module):
         return {"samples": np.concatenate([for_viz(obs), for_viz(self.reconstruct(obs))], axis=-2)}
 
 
-class VAE(Base):
+class VAE(AutogradUpdate, Base):
     def __init__(self, ocr_config, env_config) -> None:
         self._module = VAE_Module(ocr_config, env_config)
         super().__init__(ocr_config, env_config)
@@ -279,33 +277,5 @@ class VAE(Base):
         if learning is not None and hasattr(learning, "lr"):      # ocrs/base.py:20-25
             self._opt = torch.optim.Adam(self._module.parameters(), lr=learning.lr)
 
-    def to(self, device) -> None:
-        self._module.to(device)
-        if hasattr(self, "_opt"):                                 # optimizer_to (utils/tools.py) for a resumed state
-            for st in self._opt.state.values():
-                for k, v in st.items():
-                    if torch.is_tensor(v):
-                        st[k] = v.to(device)
-
     def get_loss(self, obs, with_rep=False):
         return self._module.get_loss(obs, with_rep)
-
-    def update(self, obs, masks, step: int) -> dict:
-        """ocrs/base.py:60-74: zero_grad, loss, backward, [gradient all-reduce], optional clip_grad_norm_, Adam"""
-        if not hasattr(self, "_opt"):
-            return {}
-        self._opt.zero_grad()
-        metrics = self._module.get_loss(obs)
-        metrics["loss"].backward()
-        dist = active_dist()
-        if dist is not None:                                      # data-parallel: the mean gradient over the ranks
-            for p in self._module.parameters():
-                if p.grad is not None:
-                    dist.all_reduce(p.grad, op=dist.ReduceOp.SUM)
-                    p.grad.div_(dist.get_world_size())
-        lr = self._config.learning
-        if hasattr(lr, "clip"):
-            norm_type = getattr(lr, "clip_norm_type", "inf")
-            metrics["norm"] = clip_grad_norm_(self._module.parameters(), lr.clip, float(norm_type))
-        self._opt.step()
-        return metrics
