@@ -12,7 +12,7 @@
 // Stateless: the caller owns the parameters (torch layout, state_dict order), the gradients and the workspace.  Sums run in orders
 // fixed by the shapes (no atomics).
 #include "../../include/ocrl_hip.h"
-#include "kernels.h"
+#include "unit_base.h"
 
 namespace {
 constexpr size_t SK_FLOATS = (size_t)1 << 25;      // split-k scratch of the weight gradients (fc1 / fc2 of ViT-large: 4 M floats a slab)
@@ -182,7 +182,7 @@ int ocrl_mae_fwd(const float* obs, const float* const* w, const float* noise, fl
     const Dims m = dims_of(B, obs_size, patch, D, depth, heads, Dd, ddepth, dheads, len_keep, full);
     RC(check_mae(m));
     const MaeLay y = mae_layout(m);
-    OCRL_REQUIRE(ws_floats >= y.total, "ocrl_mae_fwd: workspace too small (%zu < %zu floats)", ws_floats, y.total);
+    RC(ws_check("ocrl_mae_fwd", ws_floats, y.total));
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int n = full ? len_keep : m.L, L = m.L, P = m.P;
     const int* keep = nullptr;
@@ -222,7 +222,7 @@ int ocrl_mae_bwd(const float* obs, const float* const* w, const float* dloss, co
     const Dims m = dims_of(B, obs_size, patch, D, depth, heads, Dd, ddepth, dheads, len_keep, full);
     RC(check_mae(m));
     const MaeLay y = mae_layout(m);
-    OCRL_REQUIRE(ws_floats >= y.total, "ocrl_mae_bwd: workspace too small (%zu < %zu floats)", ws_floats, y.total);
+    RC(ws_check("ocrl_mae_bwd", ws_floats, y.total));
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int n = full ? len_keep : m.L, L = m.L, P = m.P;
     const long long Re = y.enc.R;

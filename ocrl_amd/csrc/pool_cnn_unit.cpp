@@ -2,19 +2,18 @@
 // front end of poolings/cnn_transformer/cnn_transformer_module.py:12-40, over slot_to_img(tokens) (utils/tools.py:33-36), which for a
 // [B, H W, D] token map is a view: the map already is the channels-last image.  The first convolution, its weight gradient and its
 // input gradient are pool_cnn.hip; layers 2 and 3, the ReLU masks and the Linear are the launches of the NatureCNN encoder
-// (naturecnn.hip, gemm.hip) with one group.
+// (naturecnn.hip, gemm.hip) with one group, through the conv-layer calls of unit_base.h.
 //   forward   1 pack + 3 conv launches [+ 1 GEMM (+ 1 copy of the output into ws when saving)]
 //   backward  1 mask [+ 2 GEMMs] + 2 conv launches (layers 3, 2: dW partials and the masked dX in one) + the first layer's dW partials
 //             + 2 reduces [+ 1 pack + the per-phase dX when the tokens want a gradient]
 // Stateless: the caller owns the parameters, their gradients and the workspace.
 #include "../../include/ocrl_hip.h"
-#include "kernels.h"
+#include "unit_base.h"
 
 namespace {
 struct PcLay {
     PcGeom g;
-    int cin[3], cout[3], ks[3], st[3], H[3], W[3], OH[3], OW[3], slabs[3], slab_rows[3];
-    NcMap ymap[3];
+    ConvLayer c[3];                                // the NatureCNN stack; layer 0 runs on pool_cnn.hip (its slab is g's)
     size_t act[3], dact[3], part[3], wp = 0, wd = 0, lin = 0, dz = 0, total = 0;
     int nflat = 0;
 };
@@ -32,34 +31,22 @@ int check_pc(int B, int H, int W, int D, int rep) {
 PcLay pc_layout(int B, int H, int W, int D, int rep) {
     PcLay y;
     WsTake take;
-    static const int KS[3] = {8, 4, 3}, ST[3] = {4, 2, 1}, CO[3] = {32, 64, 64};
     y.g = pc_geom(B, H, W, D);
-    int h = H, w = W, c = D;
-    for (int l = 0; l < 3; ++l) {
-        y.cin[l] = c; y.cout[l] = CO[l]; y.ks[l] = KS[l]; y.st[l] = ST[l]; y.H[l] = h; y.W[l] = w;
-        y.OH[l] = (h - KS[l]) / ST[l] + 1; y.OW[l] = (w - KS[l]) / ST[l] + 1;
-        h = y.OH[l]; w = y.OW[l]; c = CO[l];
-    }
+    nc_stack(y.c, 3, B, D, H, W);
     y.wp = take(y.g.wp_floats);
     y.wd = take(y.g.wd_floats);
     for (int l = 0; l < 3; ++l) {
-        const long long C = y.cout[l], hw = (long long)y.OH[l] * y.OW[l];
-        NcMap& o = y.ymap[l];
-        if (l < 2 || rep > 0) { o.sN = C * hw; o.sG = 0; o.sC = hw; o.sH = y.OW[l]; o.sW = 1; }       // [B, C, OH, OW]; the last one flattens NCHW
-        else { o.sN = hw * C; o.sG = 0; o.sC = 1; o.sH = y.OW[l] * C; o.sW = C; }                       // [B, OH OW, C] tokens
+        ConvLayer& c = y.c[l];
+        const long long C = c.cout, hw = (long long)c.OH * c.OW;
+        NcMap& o = c.y;
+        if (l < 2 || rep > 0) { o.sN = C * hw; o.sG = 0; o.sC = hw; o.sH = c.OW; o.sW = 1; }       // [B, C, OH, OW]; the last one flattens NCHW
+        else { o.sN = hw * C; o.sG = 0; o.sC = 1; o.sH = c.OW * C; o.sW = C; }                       // [B, OH OW, C] tokens
+        if (l) c.x = y.c[l - 1].y;
         const size_t n = (size_t)B * C * hw;
         y.act[l] = take(n); y.dact[l] = take(n);
-        if (l == 0) { y.part[0] = take(y.g.part_floats); continue; }
-        // as the NatureCNN encoder: up to 64 slabs of >= 64 of the B OH OW rows, summed in slab order by nc_dw_reduce
-        const long long M = (long long)B * hw;
-        long long s = (M + 63) / 64;
-        if (s > 64) s = 64;
-        const long long rows = ((M + s - 1) / s + 3) & ~3LL;
-        y.slab_rows[l] = (int)rows;
-        y.slabs[l] = (int)((M + rows - 1) / rows);
-        y.part[l] = take((size_t)y.slabs[l] * C * ((size_t)y.cin[l] * KS[l] * KS[l] + 1));
+        y.part[l] = take(l ? (size_t)c.slab.slabs * C * ((size_t)c.K() + 1) : y.g.part_floats);
     }
-    y.nflat = y.cout[2] * y.OH[2] * y.OW[2];
+    y.nflat = y.c[2].cout * y.c[2].OH * y.c[2].OW;
     if (rep > 0) { y.lin = take((size_t)B * rep); y.dz = take((size_t)B * rep); }
     y.total = take.end;
     return y;
@@ -78,20 +65,12 @@ int ocrl_pool_cnn_fwd(const float* tokens, const float* const* w, float* out, in
     OCRL_REQUIRE(tokens && w && out && ws, "ocrl_pool_cnn_fwd: null argument");
     RC(check_pc(B, H, W, D, rep_dim));
     const PcLay y = pc_layout(B, H, W, D, rep_dim);
-    OCRL_REQUIRE(ws_floats >= y.total, "ocrl_pool_cnn_fwd: workspace too small (%zu < %zu floats)", ws_floats, y.total);
+    RC(ws_check("ocrl_pool_cnn_fwd", ws_floats, y.total));
     hipStream_t st = static_cast<hipStream_t>(stream);
     RC(pc_conv1_fwd_launch(tokens, w[0], w[1], ws + y.wp, ws + y.act[0], B, H, W, D, st));
     for (int l = 1; l < 3; ++l) {
-        NcFwdArgs a;
-        a.X = ws + y.act[l - 1]; a.x = y.ymap[l - 1];
         const bool to_out = rep_dim == 0 && l == 2;
-        a.Y = to_out ? out : ws + y.act[l];
-        a.Y2 = to_out && save ? ws + y.act[l] : nullptr;
-        a.y = y.ymap[l];
-        a.w[0] = w[2 * l]; a.bias[0] = w[2 * l + 1];
-        a.B = B; a.G = 1; a.cin = y.cin[l]; a.cout = y.cout[l]; a.H = y.H[l]; a.W = y.W[l]; a.OH = y.OH[l]; a.OW = y.OW[l];
-        a.ks = y.ks[l]; a.stride = y.st[l];
-        RC(nc_conv_fwd_launch(a, st));
+        RC(conv_fwd(y.c[l], ws + y.act[l - 1], to_out ? out : ws + y.act[l], to_out && save ? ws + y.act[l] : nullptr, w + 2 * l, 0, B, 1, st));
     }
     if (rep_dim == 0) return 0;
     float* lo = save ? ws + y.lin : out;
@@ -105,33 +84,14 @@ int ocrl_pool_cnn_bwd(const float* tokens, const float* dout, const float* const
     OCRL_REQUIRE(tokens && dout && w && dw && ws, "ocrl_pool_cnn_bwd: null argument");
     RC(check_pc(B, H, W, D, rep_dim));
     const PcLay y = pc_layout(B, H, W, D, rep_dim);
-    OCRL_REQUIRE(ws_floats >= y.total, "ocrl_pool_cnn_bwd: workspace too small (%zu < %zu floats)", ws_floats, y.total);
+    RC(ws_check("ocrl_pool_cnn_bwd", ws_floats, y.total));
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (rep_dim == 0) {
-        RC(nc_relu_mask_launch(dout, ws + y.act[2], ws + y.dact[2], (long long)B * y.nflat, st));      // tokens: same layout as out
-    } else {
-        RC(nc_relu_mask_launch(dout, ws + y.lin, ws + y.dz, (long long)B * rep_dim, st));
-        const float* flat = ws + y.act[2];
-        // dW = dz^T flat, db = column sums of dz (B rows: no split-k scratch); d flat = (dz W) * (flat > 0)
-        RC(lin_bwd_w(ws + y.dz, rep_dim, flat, y.nflat, dw[6], dw[7], B, rep_dim, y.nflat, 1.f, nullptr, 0, st));
-        RC(lin_bwd_x(ws + y.dz, rep_dim, w[6], ws + y.dact[2], y.nflat, B, rep_dim, y.nflat, flat, y.nflat, nullptr, 0, st));
-    }
+    if (rep_dim == 0) RC(nc_relu_mask_launch(dout, ws + y.act[2], ws + y.dact[2], (long long)B * y.nflat, st));      // tokens: same layout as out
+    else RC(nc_tail_bwd(dout, ws + y.lin, ws + y.dz, ws + y.act[2], ws + y.dact[2], w + 6, dw + 6, 0, B, 1, rep_dim, y.nflat, st));
     NcReduceArgs r;
-    r.nlayers = 2;
     for (int l = 2; l >= 1; --l) {
-        NcBwdArgs a;
-        a.X = ws + y.act[l - 1]; a.x = y.ymap[l - 1];
-        a.dY = ws + y.dact[l]; a.dy = y.ymap[l];
-        a.dX = ws + y.dact[l - 1];
-        a.part = ws + y.part[l]; a.slabs = y.slabs[l]; a.slab_rows = y.slab_rows[l];
-        a.w[0] = w[2 * l];
-        a.B = B; a.G = 1; a.cin = y.cin[l]; a.cout = y.cout[l]; a.H = y.H[l]; a.W = y.W[l]; a.OH = y.OH[l]; a.OW = y.OW[l];
-        a.ks = y.ks[l]; a.stride = y.st[l];
-        RC(nc_conv_bwd_launch(a, st));
-        NcReduceLayer& q = r.L[l - 1];
-        q.part = ws + y.part[l]; q.slabs = y.slabs[l]; q.G = 1; q.cout = y.cout[l]; q.K = y.cin[l] * y.ks[l] * y.ks[l];
-        q.n = (long long)q.cout * (q.K + 1);
-        r.dw[l - 1][0] = dw[2 * l]; r.db[l - 1][0] = dw[2 * l + 1];
+        RC(conv_bwd(y.c[l], ws + y.act[l - 1], ws + y.dact[l], ws + y.dact[l - 1], ws + y.part[l], w + 2 * l, 0, B, 1, st));
+        conv_reduce_add(r, l - 1, y.c[l], ws + y.part[l], dw + 2 * l, 0, 1);
     }
     RC(nc_dw_reduce_launch(r, st));
     // first layer: ws.dact[0] is the gradient of its pre-activation (layer 2's dX applies the mask of act[0])

@@ -1,15 +1,15 @@
 // C ABI of the slot property probe (include/ocrl_hip.h: ocrl_probe_*): utils/property_predictor.py:12-189 of the reference.
 // Head: nl Linear layers with LeakyReLU between them (model_type linear: nl = 1; mlp3: nl = 4, hidden width 256) on the encoder rows
 // ([B K, D] slot rows, or [B, D] rows whose K O outputs are read as K pseudo-slots: the VAE branch), on the library's GEMM.  The input
-// width and the last layer's output width are zero-padded to multiples of 4 (the last layer is 15 wide for the default schema; the pad
-// rows of its weight are zero, so are the pad columns of d out).  Then probe.hip: cost matrix, exact assignment, loss, metrics, d out.
-// Stateless like the pooling heads: the caller owns parameters, gradients and the workspace; forward leaves what backward needs in `ws`
-// (the activations and the unscaled d loss / d out), backward scales by the incoming d loss and walks the layers down.  The rows get
-// no gradient: the probe reads a detached encoder.
+// width is padded as unit_base.h says; the last layer's output width is zero-padded to a multiple of 4 here (it is 15 wide for the
+// default schema; the pad rows of its weight are zero, so are the pad columns of d out).  Then probe.hip: cost matrix, exact
+// assignment, loss, metrics, d out.  Stateless: the caller owns parameters, gradients and the workspace; forward leaves what backward
+// needs in `ws` (the activations and the unscaled d loss / d out), backward scales by the incoming d loss and walks the layers down.
+// The rows get no gradient: the probe reads a detached encoder.
 #include <hip/hip_runtime.h>
 
 #include "../../include/ocrl_hip.h"
-#include "kernels.h"
+#include "unit_base.h"
 
 namespace {
 struct ProbeLay {
@@ -24,8 +24,8 @@ int check_head(int B, int K, int D, int O, int slot_rows, int nl, const int* dim
         OCRL_REQUIRE(dims[l] >= 4 && dims[l] % 4 == 0, "probe: hidden width dims[%d] = %d is not a positive multiple of 4", l, dims[l]);
     const long long want = slot_rows ? O : (long long)K * O;
     OCRL_REQUIRE(dims[nl - 1] == want, "probe: the last layer is %d wide, the schema needs %lld", dims[nl - 1], want);
-    long long wmax = (D + 3) & ~3;
-    for (int l = 0; l < nl; ++l) wmax = dims[l] + 3 > wmax ? ((dims[l] + 3) & ~3) : wmax;
+    long long wmax = pad4(D);
+    for (int l = 0; l < nl; ++l) wmax = dims[l] + 3 > wmax ? pad4(dims[l]) : wmax;
     OCRL_REQUIRE((long long)B * (slot_rows ? K : 1) * wmax < (1LL << 31), "probe: %d images exceed the int32 range of one call", B);
     return 0;
 }
@@ -33,14 +33,14 @@ int check_head(int B, int K, int D, int O, int slot_rows, int nl, const int* dim
 ProbeLay probe_layout(int B, int K, int N, int D, int slot_rows, int nl, const int* dims, int P) {
     ProbeLay y;
     WsTake take;
-    y.Dp = (D + 3) & ~3;
-    y.Hp = (dims[nl - 1] + 3) & ~3;
+    y.Dp = pad4(D);
+    y.Hp = pad4(dims[nl - 1]);
     y.M = slot_rows ? B * K : B;
     const size_t M = y.M, kin_last = nl > 1 ? dims[nl - 2] : y.Dp;
-    y.xp = take(y.Dp != D ? M * y.Dp : 0);
+    y.xp = take(pad4_floats(M, D));
     y.wl = take((size_t)y.Hp * kin_last); y.bl = take(y.Hp);
     y.dwl = take((size_t)y.Hp * kin_last); y.dbl = take(y.Hp);
-    y.dw0 = take(y.Dp != D && nl > 1 ? (size_t)dims[0] * y.Dp : 0);
+    y.dw0 = take(nl > 1 ? pad4_floats(dims[0], D) : 0);
     size_t wmax = y.Hp, slab = (size_t)y.Hp * kin_last;
     for (int l = 0; l < nl; ++l) {
         const size_t wl = l == nl - 1 ? y.Hp : dims[l], kin = l ? dims[l - 1] : y.Dp;
@@ -51,9 +51,7 @@ ProbeLay probe_layout(int B, int K, int N, int D, int slot_rows, int nl, const i
     y.gout = take(M * y.Hp);
     y.gA = take(M * wmax); y.gB = take(M * wmax);
     y.part = take((size_t)B * (P + 2));
-    size_t splits = M / 256;                               // split-k slabs of the weight gradients (the rows are their k dimension)
-    if (splits > 32) splits = 32;
-    y.sk_floats = splits > 1 ? splits * (slab + wmax + 4) : 0;
+    y.sk_floats = splitk_scratch_floats(M, slab + wmax + 4);      // the head rows are the k dimension of the weight gradients
     y.sk = take(y.sk_floats);
     y.total = take.end;
     return y;
@@ -87,7 +85,7 @@ int ocrl_probe_match(const float* out, int ld_row, long long ld_img, const float
     OCRL_REQUIRE(out && y && metrics && ws, "ocrl_probe_match: null argument");
     ProbeSchema sc;
     RC(make_schema(P, tgt_range, out_range, kind, &sc));
-    OCRL_REQUIRE(ws_floats >= (size_t)B * (P + 2), "ocrl_probe_match: workspace too small (%zu < %zu floats)", ws_floats, (size_t)B * (P + 2));
+    RC(ws_check("ocrl_probe_match", ws_floats, (size_t)B * (P + 2)));
     return probe_match_launch(out, ld_row, ld_img, y, dloss, cost, col, ws, metrics, dout, B, K, N, T, O, sc, static_cast<hipStream_t>(stream));
 }
 
@@ -106,15 +104,12 @@ int ocrl_probe_fwd(const float* rows, const float* const* w, const float* y, flo
     RC(make_schema(P, tgt_range, out_range, kind, &sc));
     RC(probe_schema_check(sc, T, O));
     const ProbeLay L = probe_layout(B, K, N, D, slot_rows, nl, dims, P);
-    OCRL_REQUIRE(ws_floats >= L.total, "ocrl_probe_fwd: workspace too small (%zu < %zu floats)", ws_floats, L.total);
+    RC(ws_check("ocrl_probe_fwd", ws_floats, L.total));
     hipStream_t st = static_cast<hipStream_t>(stream);
     const long long M = L.M;
     const int H = dims[nl - 1], Hp = L.Hp, kin_last = nl > 1 ? dims[nl - 2] : L.Dp;
-    const float* x = rows;
-    if (L.Dp != D) {                                       // zero-padded stride-4 copy of the rows
-        RC(pool_cols_launch(rows, D, ws + L.xp, L.Dp, M, L.Dp, D, st));
-        x = ws + L.xp;
-    }
+    const float* x;
+    RC(pad4_view(rows, D, ws + L.xp, M, &x, st));
     // the last layer's weight padded to Hp output rows (and, as the only layer, to Dp input columns)
     const int kin_real = nl > 1 ? dims[nl - 2] : D;
     OCRL_HIP(hipMemsetAsync(ws + L.wl, 0, (size_t)Hp * kin_last * sizeof(float), st));
@@ -125,10 +120,7 @@ int ocrl_probe_fwd(const float* rows, const float* const* w, const float* y, flo
         const int kin = l ? dims[l - 1] : L.Dp, wout = last ? Hp : dims[l];
         const float* W = last ? ws + L.wl : w[2 * l];
         const float* bias = last ? ws + L.bl : w[2 * l + 1];
-        if (l == 0 && !last && L.Dp != D) {                // first of several layers with a padded input: its weight padded in dw0's place
-            RC(pool_cols_launch(w[0], D, ws + L.dw0, L.Dp, dims[0], L.Dp, D, st));
-            W = ws + L.dw0;
-        }
+        if (l == 0 && !last) RC(pad4_view(w[0], D, ws + L.dw0, dims[0], &W, st));      // first of several layers: its weight padded in dw0's place
         RC(lin_fwd(l ? ws + L.h[l - 1] : x, kin, W, bias, ws + L.h[l], wout, M, wout, kin, 0, nullptr, 0, st));
         if (!last) RC(probe_leaky_fwd_launch(ws + L.h[l], M * wout, slope, st));
     }
@@ -147,32 +139,31 @@ int ocrl_probe_bwd(const float* rows, const float* dloss, const float* const* w,
     RC(probe_match_check(B, K, N, 1, O));
     OCRL_REQUIRE(P >= 1 && P <= OCRL_PROBE_MAX_PROPS, "ocrl_probe_bwd: 1 <= properties <= %d (got %d)", OCRL_PROBE_MAX_PROPS, P);
     const ProbeLay L = probe_layout(B, K, N, D, slot_rows, nl, dims, P);
-    OCRL_REQUIRE(ws_floats >= L.total, "ocrl_probe_bwd: workspace too small (%zu < %zu floats)", ws_floats, L.total);
+    RC(ws_check("ocrl_probe_bwd", ws_floats, L.total));
     hipStream_t st = static_cast<hipStream_t>(stream);
     const long long M = L.M;
     const int H = dims[nl - 1], Hp = L.Hp;
-    const float* x = L.Dp != D ? ws + L.xp : rows;         // the padded copy the forward left in ws
+    const float* x = pad4_sel<const float>(rows, D, ws + L.xp);      // the padded copy the forward left in ws
     float *gc = ws + L.gA, *gn = ws + L.gB;
     RC(vae_scale_launch(ws + L.gout, gc, dloss, M * Hp, st));
     for (int l = nl - 1; l >= 0; --l) {
         const bool last = l == nl - 1;
         const int kin = l ? dims[l - 1] : L.Dp, wout = last ? Hp : dims[l];
         const float* xin = l ? ws + L.h[l - 1] : x;
-        const bool pad_in = l == 0 && L.Dp != D;
         // padded gradients land in ws first: the last layer's pad rows, the first layer's pad columns
-        float* dW = last ? ws + L.dwl : (pad_in ? ws + L.dw0 : dw[2 * l]);
+        float* dW = last ? ws + L.dwl : (l ? dw[2 * l] : pad4_sel(dw[0], D, ws + L.dw0));
         float* db = last ? ws + L.dbl : dw[2 * l + 1];
         if (l > 0) RC(lin_bwd_x(gc, wout, last ? ws + L.wl : w[2 * l], gn, kin, M, wout, kin, nullptr, 0, nullptr, 0, st));
         RC(lin_bwd_w(gc, wout, xin, kin, dW, db, M, wout, kin, 1.f, ws + L.sk, L.sk_floats, st));
         if (last) {
             RC(pool_cols_launch(ws + L.dwl, kin, dw[2 * l], l ? kin : D, H, l ? kin : D, l ? kin : D, st));
             RC(copy_launch(ws + L.dbl, dw[2 * l + 1], H, st));
-        } else if (pad_in) {
-            RC(pool_cols_launch(ws + L.dw0, L.Dp, dw[0], D, dims[0], D, D, st));
+        } else if (l == 0) {
+            RC(pad4_unpad(ws + L.dw0, D, dw[0], dims[0], st));
         }
         if (l > 0) {
             RC(probe_leaky_bwd_launch(gn, ws + L.h[l - 1], M * kin, slope, st));
-            float* t = gc; gc = gn; gn = t;
+            std::swap(gc, gn);
         }
     }
     return 0;

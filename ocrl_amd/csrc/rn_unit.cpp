@@ -1,12 +1,12 @@
 // C ABI of the Relation Network pooling head (include/ocrl_hip.h: ocrl_pool_rn_*): poolings/rn/rn_module.py:8-59.
 // g = [Linear, ReLU] x ng on every ordered slot pair cat(s_i, s_j), summed over the pairs, then f = [Linear, ReLU] x nf.
 // The first g layer is factored: its weight W1 [g1, 2D] splits into U = W1[:, :D] and V = W1[:, D:], and pair row (i, j) is
-// relu(U s_i + V s_j + b1).  Both halves are stacked into W1s = [U; V] ([2 g1, Dp], rep_dim zero-padded to a multiple of 4), so one
+// relu(U s_i + V s_j + b1).  Both halves are stacked into W1s = [U; V] ([2 g1, Dp], Dp = pad4(rep_dim): unit_base.h), so one
 // GEMM over the B K slot rows gives AB = [A | Bq] and rn_pair_fwd expands the pairs with an addition.  The other layers run on the
-// library's GEMM (bias and ReLU in the epilogue; the ReLU mask of the backward in the dX epilogue).  Stateless like the Transformer
-// head: the caller owns parameters, gradients and the workspace; forward leaves what backward needs in `ws`.
+// library's GEMM (bias and ReLU in the epilogue; the ReLU mask of the backward in the dX epilogue).  Stateless: the caller owns
+// parameters, gradients and the workspace; forward leaves what backward needs in `ws`.
 #include "../../include/ocrl_hip.h"
-#include "kernels.h"
+#include "unit_base.h"
 
 namespace {
 struct RnLay {
@@ -27,7 +27,7 @@ int check_rn(int B, int K, int D, int ng, const int* g_dims, int nf, const int* 
         OCRL_REQUIRE(f_dims[l] >= 4 && f_dims[l] % 4 == 0, "pool_rn: f_dims[%d] = %d is not a positive multiple of 4", l, f_dims[l]);
     // every GEMM extent and element count must stay in the int32 range of the kernels: the pair rows (B K (K-1)) times the widest g
     // layer bound them (a CNN feature map as "slots", K = 4096, is 16.8 M pairs per image and is rejected here)
-    const long long BK = (long long)B * K, Dp = (D + 3) & ~3;
+    const long long BK = (long long)B * K, Dp = pad4(D);
     const long long pairs = BK * (K - 1);
     OCRL_REQUIRE(pairs * gmax < (1LL << 31) && BK * 2 * g_dims[0] < (1LL << 31) && BK * Dp < (1LL << 31),
                  "pool_rn: %lld pair rows of width %lld exceed the int32 range of one call (batch %d, %d slots)", pairs, gmax, B, K);
@@ -37,14 +37,13 @@ int check_rn(int B, int K, int D, int ng, const int* g_dims, int nf, const int* 
 RnLay rn_layout(int B, int K, int D, int ng, const int* g_dims, int nf, const int* f_dims) {
     RnLay y;
     WsTake take;
-    y.Dp = (D + 3) & ~3;
+    y.Dp = pad4(D);
     y.P = K * (K - 1);
     const size_t BK = (size_t)B * K, BP = (size_t)B * y.P, g1 = g_dims[0], gL = g_dims[ng - 1];
-    const bool pad = y.Dp != D;
     y.gmax = 0; y.fmax = (int)gL;
     for (int l = 0; l < ng; ++l) y.gmax = g_dims[l] > y.gmax ? g_dims[l] : y.gmax;
     for (int l = 0; l < nf; ++l) y.fmax = f_dims[l] > y.fmax ? f_dims[l] : y.fmax;
-    y.sp = take(pad ? BK * y.Dp : 0); y.dsp = take(pad ? BK * y.Dp : 0);
+    y.sp = take(pad4_floats(BK, D)); y.dsp = take(pad4_floats(BK, D));
     y.w1s = take(2 * g1 * y.Dp); y.dw1s = take(2 * g1 * y.Dp); y.db1s = take(2 * g1);
     y.ab = take(BK * 2 * g1); y.dab = take(BK * 2 * g1);
     for (int l = 0; l < ng; ++l) y.h[l] = take(BP * g_dims[l]);
@@ -52,15 +51,13 @@ RnLay rn_layout(int B, int K, int D, int ng, const int* g_dims, int nf, const in
     for (int l = 0; l < nf; ++l) y.f[l] = take((size_t)B * f_dims[l]);
     y.gA = take(BP * y.gmax); y.gB = take(BP * y.gmax);
     y.fA = take((size_t)B * y.fmax); y.fB = take((size_t)B * y.fmax);
-    // split-k slabs of the weight-gradient GEMMs (the pair rows are their k dimension): up to 32 slabs of the largest weight
+    // split-k scratch of the weight gradients: the pair rows are their k dimension; the largest weight and the widest bias
     size_t slab = 2 * g1 * y.Dp, bslab = 2 * g1;
     for (int l = 1; l < ng; ++l) slab = (size_t)g_dims[l] * g_dims[l - 1] > slab ? (size_t)g_dims[l] * g_dims[l - 1] : slab;
     for (int l = 0; l < nf; ++l) slab = (size_t)f_dims[l] * (l ? f_dims[l - 1] : gL) > slab ? (size_t)f_dims[l] * (l ? f_dims[l - 1] : gL) : slab;
     if ((size_t)y.gmax > bslab) bslab = y.gmax;
     if ((size_t)y.fmax > bslab) bslab = y.fmax;
-    size_t splits = BP / 256;
-    if (splits > 32) splits = 32;
-    y.sk_floats = splits > 1 ? splits * (slab + bslab + 4) : 0;
+    y.sk_floats = splitk_scratch_floats(BP, slab + bslab + 4);
     y.sk = take(y.sk_floats);
     y.total = take.end;
     return y;
@@ -79,15 +76,12 @@ int ocrl_pool_rn_fwd(const float* slots, const float* const* w, float* out, int 
     OCRL_REQUIRE(slots && w && out && ws, "ocrl_pool_rn_fwd: null argument");
     RC(check_rn(B, K, D, ng, g_dims, nf, f_dims));
     const RnLay y = rn_layout(B, K, D, ng, g_dims, nf, f_dims);
-    OCRL_REQUIRE(ws_floats >= y.total, "ocrl_pool_rn_fwd: workspace too small (%zu < %zu floats)", ws_floats, y.total);
+    RC(ws_check("ocrl_pool_rn_fwd", ws_floats, y.total));
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int Dp = y.Dp, g1 = g_dims[0], gL = g_dims[ng - 1];
     const long long BK = (long long)B * K, BP = (long long)B * y.P;
-    const float* xs = slots;
-    if (Dp != D) {                                      // zero-padded stride-4 copy of the slots
-        RC(pool_cols_launch(slots, D, ws + y.sp, Dp, BK, Dp, D, st));
-        xs = ws + y.sp;
-    }
+    const float* xs;
+    RC(pad4_view(slots, D, ws + y.sp, BK, &xs, st));
     RC(pool_cols_launch(w[0], 2 * D, ws + y.w1s, Dp, g1, Dp, D, st));                              // U = W1[:, :D]
     RC(pool_cols_launch(w[0] + D, 2 * D, ws + y.w1s + (size_t)g1 * Dp, Dp, g1, Dp, D, st));        // V = W1[:, D:]
     RC(lin_fwd(xs, Dp, ws + y.w1s, nullptr, ws + y.ab, 2 * g1, BK, 2 * g1, Dp, 0, nullptr, 0, st));   // [A | Bq] on the slot rows
@@ -108,7 +102,7 @@ int ocrl_pool_rn_bwd(const float* slots, const float* dout, const float* const* 
     OCRL_REQUIRE(slots && dout && w && dw && ws, "ocrl_pool_rn_bwd: null argument");
     RC(check_rn(B, K, D, ng, g_dims, nf, f_dims));
     const RnLay y = rn_layout(B, K, D, ng, g_dims, nf, f_dims);
-    OCRL_REQUIRE(ws_floats >= y.total, "ocrl_pool_rn_bwd: workspace too small (%zu < %zu floats)", ws_floats, y.total);
+    RC(ws_check("ocrl_pool_rn_bwd", ws_floats, y.total));
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int Dp = y.Dp, g1 = g_dims[0], gL = g_dims[ng - 1];
     const long long BK = (long long)B * K, BP = (long long)B * y.P;
@@ -122,7 +116,7 @@ int ocrl_pool_rn_bwd(const float* slots, const float* dout, const float* const* 
         const int kin = l ? f_dims[l - 1] : gL;
         RC(lin_bwd_w(fc, f_dims[l], l ? ws + y.f[l - 1] : ws + y.y, kin, dwf[2 * l], dwf[2 * l + 1], B, f_dims[l], kin, 1.f, sk, y.sk_floats, st));
         RC(lin_bwd_x(fc, f_dims[l], wf[2 * l], fn, kin, B, f_dims[l], kin, l ? ws + y.f[l - 1] : nullptr, kin, nullptr, 0, st));
-        float* t = fc; fc = fn; fn = t;
+        std::swap(fc, fn);
     }
     // fc = d loss / d (pair sum); g: broadcast over the pairs under the last layer's ReLU, then layer by layer down to the first
     float *gc = ws + y.gA, *gn = ws + y.gB;
@@ -130,18 +124,18 @@ int ocrl_pool_rn_bwd(const float* slots, const float* dout, const float* const* 
     for (int l = ng - 1; l >= 1; --l) {
         RC(lin_bwd_w(gc, g_dims[l], ws + y.h[l - 1], g_dims[l - 1], dw[2 * l], dw[2 * l + 1], BP, g_dims[l], g_dims[l - 1], 1.f, sk, y.sk_floats, st));
         RC(lin_bwd_x(gc, g_dims[l], w[2 * l], gn, g_dims[l - 1], BP, g_dims[l], g_dims[l - 1], ws + y.h[l - 1], g_dims[l - 1], nullptr, 0, st));
-        float* t = gc; gc = gn; gn = t;
+        std::swap(gc, gn);
     }
     // the factored first layer: pair gradients -> [dA | dBq] on the slot rows -> dW1 = [dA^T s | dBq^T s], db1 = sum dA, dslots
     RC(rn_pair_bwd_launch(gc, ws + y.dab, B, K, g1, st));
-    const float* xs = Dp != D ? ws + y.sp : slots;      // the padded copy the forward left in ws
+    const float* xs = pad4_sel<const float>(slots, D, ws + y.sp);      // the padded copy the forward left in ws
     RC(lin_bwd_w(ws + y.dab, 2 * g1, xs, Dp, ws + y.dw1s, ws + y.db1s, BK, 2 * g1, Dp, 1.f, sk, y.sk_floats, st));
     RC(pool_cols_launch(ws + y.dw1s, Dp, dw[0], 2 * D, g1, D, D, st));
     RC(pool_cols_launch(ws + y.dw1s + (size_t)g1 * Dp, Dp, dw[0] + D, 2 * D, g1, D, D, st));
     RC(copy_launch(ws + y.db1s, dw[1], g1, st));
     if (dslots) {
-        RC(lin_bwd_x(ws + y.dab, 2 * g1, ws + y.w1s, Dp != D ? ws + y.dsp : dslots, Dp, BK, 2 * g1, Dp, nullptr, 0, nullptr, 0, st));
-        if (Dp != D) RC(pool_cols_launch(ws + y.dsp, Dp, dslots, D, BK, D, D, st));
+        RC(lin_bwd_x(ws + y.dab, 2 * g1, ws + y.w1s, pad4_sel(dslots, D, ws + y.dsp), Dp, BK, 2 * g1, Dp, nullptr, 0, nullptr, 0, st));
+        RC(pad4_unpad(ws + y.dsp, D, dslots, BK, st));
     }
     return 0;
 }

@@ -10,34 +10,21 @@
 // Stateless: the caller owns the parameters (read in torch's layout, packed per call into ws), the gradients and the workspace; the
 // forward leaves in ws everything the backward reads.  Sums run in orders fixed by the shapes (no atomics).
 #include "../../include/ocrl_hip.h"
-#include "kernels.h"
+#include "unit_base.h"
 
 namespace {
 constexpr int CONV_HIP_MIN = 32;      // decoder 3 x 3 maps from this size on run conv.hip's 4 x 32 pixel tiles; smaller ones naturecnn.hip's
 constexpr size_t SK_FLOATS = (size_t)1 << 22;
 
-struct Slab { int slabs = 1, rows = 4; size_t floats = 0; };
-// the weight gradient of an implicit-GEMM conv reduces over the B OH OW rows: up to 64 slabs of >= 64 rows (as naturecnn_unit.cpp)
-Slab slab_of(long long M, int cout, int K) {
-    Slab s;
-    long long n = (M + 63) / 64;
-    if (n > 64) n = 64;
-    const long long rows = ((M + n - 1) / n + 3) & ~3LL;
-    s.rows = (int)rows;
-    s.slabs = (int)((M + rows - 1) / rows);
-    s.floats = (size_t)s.slabs * cout * (K + 1);
-    return s;
-}
-
 struct VaeLay {
     int n = 0, f = 0, S = 0, C = 0, L = 0, B = 0, full = 0, cnn = 0;
     size_t ea[OCRL_VAE_MAX_STAGES][4] = {}, epart[OCRL_VAE_MAX_STAGES] = {}, e = 0;
-    Slab eslab[OCRL_VAE_MAX_STAGES];
+    ConvLayer ec[OCRL_VAE_MAX_STAGES];             // the 2 x 2 stride 2 encoder convs
     size_t ml = 0, lat = 0, klp = 0, msews = 0, Wml = 0, bml = 0, Win = 0, bin = 0, Wo4 = 0, bo4 = 0;
     size_t hin = 0, d0 = 0, x3[OCRL_VAE_MAX_STAGES] = {}, y1[OCRL_VAE_MAX_STAGES] = {}, y2[OCRL_VAE_MAX_STAGES] = {},
            y4[OCRL_VAE_MAX_STAGES] = {}, ps[OCRL_VAE_MAX_STAGES] = {}, dpart[OCRL_VAE_MAX_STAGES] = {}, pkf[OCRL_VAE_MAX_STAGES] = {},
            pkb[OCRL_VAE_MAX_STAGES] = {};
-    Slab dslab[OCRL_VAE_MAX_STAGES];
+    ConvLayer dc[OCRL_VAE_MAX_STAGES];             // the 3 x 3 pad 1 decoder convs below CONV_HIP_MIN
     size_t r4 = 0, dr4 = 0, drs = 0, ge = 0;
     size_t gA = 0, gB = 0, dml = 0, dlat = 0, dWml = 0, dbml = 0, dWin = 0, dbin = 0, dWo4 = 0, dbo4 = 0, sk = 0, sk_floats = 0;
     size_t total = 0;
@@ -72,6 +59,10 @@ int check_vae(int B, int S, int C, int f, int L) {
     return 0;
 }
 
+NcMap nhwc(long long s, int c) { NcMap m; m.sN = s * s * c; m.sG = 0; m.sC = 1; m.sH = s * c; m.sW = c; return m; }
+NcMap nchw(long long s, int c) { NcMap m; m.sN = (long long)c * s * s; m.sG = 0; m.sC = s * s; m.sH = s; m.sW = 1; return m; }
+size_t part_floats(const ConvLayer& c) { return (size_t)c.slab.slabs * c.cout * (c.K() + 1); }
+
 VaeLay vae_layout(int B, int S, int C, int f, int L, int cnn, int full) {
     VaeLay y;
     WsTake take;
@@ -81,8 +72,9 @@ VaeLay vae_layout(int B, int S, int C, int f, int L, int cnn, int full) {
     for (int i = 0; i < y.n; ++i) {
         const long long s = S >> (i + 1), M = (long long)B * s * s;
         for (int j = 0; j < 4; ++j) y.ea[i][j] = take((size_t)M * 64);
-        y.eslab[i] = slab_of(M, 64, (i ? 64 : C) * 4);
-        y.epart[i] = take(y.eslab[i].floats);
+        y.ec[i] = conv_layer(B, i ? 64 : C, 64, 2, 2, 0, 2 * (int)s, 2 * (int)s);
+        y.ec[i].x = i ? nhwc(2 * s, 64) : nchw(2 * s, C); y.ec[i].y = nhwc(s, 64);
+        y.epart[i] = take(part_floats(y.ec[i]));
         if ((size_t)M * 64 > gmax) gmax = (size_t)M * 64;
     }
     y.e = take((size_t)B * F);
@@ -98,8 +90,9 @@ VaeLay vae_layout(int B, int S, int C, int f, int L, int cnn, int full) {
             const long long s = (long long)f << i, M = (long long)B * s * s;
             y.x3[i] = take(M * 64); y.y1[i] = take(M * 64); y.y2[i] = take(M * 64); y.y4[i] = take(M * 256); y.ps[i] = take(M * 256);
             if (s < CONV_HIP_MIN) {
-                y.dslab[i] = slab_of(M, 64, 64 * 9);
-                y.dpart[i] = take(y.dslab[i].floats);
+                y.dc[i] = conv_layer(B, 64, 64, 3, 1, 1, (int)s, (int)s);
+                y.dc[i].x = y.dc[i].y = nhwc(s, 64);
+                y.dpart[i] = take(part_floats(y.dc[i]));
             } else {
                 y.pkf[i] = take(9 * 64 * 64); y.pkb[i] = take(9 * 64 * 64);
                 const size_t wg = conv_wgrad_ws_floats(B, (int)s, (int)s, 3, 64);
@@ -118,28 +111,13 @@ VaeLay vae_layout(int B, int S, int C, int f, int L, int cnn, int full) {
     return y;
 }
 
-NcMap nhwc(long long s, int c) { NcMap m; m.sN = s * s * c; m.sG = 0; m.sC = 1; m.sH = s * c; m.sW = c; return m; }
-NcMap nchw(long long s, int c) { NcMap m; m.sN = (long long)c * s * s; m.sG = 0; m.sC = s * s; m.sH = s; m.sW = 1; return m; }
-
-// implicit-GEMM conv of naturecnn.hip: relu(conv(x) + b), x and y in the given layouts
-int nc_fwd(const float* x, NcMap xm, float* yv, NcMap ym, const float* w, const float* b, int B, int cin, int H, int OH, int ks, int stride,
-           int pad, hipStream_t st) {
-    NcFwdArgs a;
-    a.X = x; a.x = xm; a.Y = yv; a.y = ym; a.w[0] = w; a.bias[0] = b;
-    a.B = B; a.G = 1; a.cin = cin; a.cout = 64; a.H = H; a.W = H; a.OH = OH; a.OW = OH; a.ks = ks; a.stride = stride; a.pad = pad;
-    return nc_conv_fwd_launch(a, st);
-}
-// its backward: dW, db (through the slab partials and one reduce) and, when dx, the gradient masked by x > 0
-int nc_bwd(const float* x, NcMap xm, const float* dy, NcMap dym, float* dx, const float* w, float* dw, float* db, float* part, const Slab& sl,
-           int B, int cin, int H, int OH, int ks, int stride, int pad, hipStream_t st) {
-    NcBwdArgs a;
-    a.X = x; a.x = xm; a.dY = dy; a.dy = dym; a.dX = dx; a.part = part; a.slabs = sl.slabs; a.slab_rows = sl.rows; a.w[0] = w;
-    a.B = B; a.G = 1; a.cin = cin; a.cout = 64; a.H = H; a.W = H; a.OH = OH; a.OW = OH; a.ks = ks; a.stride = stride; a.pad = pad;
-    RC(nc_conv_bwd_launch(a, st));
+// backward of an implicit-GEMM conv layer (wb / dwb: its weight, the bias follows): dW, db through the slab partials and one reduce and,
+// when dx, the gradient masked by x > 0
+int nc_bwd(const ConvLayer& c, const float* x, const float* dy, float* dx, const float* const* wb, float* const* dwb, float* part, int B,
+           hipStream_t st) {
+    RC(conv_bwd(c, x, dy, dx, part, wb, 0, B, 1, st));
     NcReduceArgs r;
-    r.nlayers = 1;
-    r.L[0].part = part; r.L[0].slabs = sl.slabs; r.L[0].G = 1; r.L[0].cout = 64; r.L[0].K = cin * ks * ks; r.L[0].n = (long long)64 * (r.L[0].K + 1);
-    r.dw[0][0] = dw; r.db[0][0] = db;
+    conv_reduce_add(r, 0, c, part, dwb, 0, 1);
     return nc_dw_reduce_launch(r, st);
 }
 
@@ -172,10 +150,10 @@ int zero_decoder_grads(float* const* dw, const VaeLay& y, hipStream_t st) {
 int enc_fwd(const float* obs, const float* const* w, float* emap, const VaeLay& y, float* ws, hipStream_t st) {
     const int B = y.B;
     for (int i = 0; i < y.n; ++i) {
-        const int H = y.S >> i, s = H / 2;
+        const int s = y.S >> (i + 1);
         const long long M = (long long)B * s * s;
         const float* x = i ? ws + y.ea[i - 1][3] : obs;
-        RC(nc_fwd(x, i ? nhwc(H, 64) : nchw(H, y.C), ws + y.ea[i][0], nhwc(s, 64), w[y.enc(i, 0)], w[y.enc(i, 0) + 1], B, i ? 64 : y.C, H, s, 2, 2, 0, st));
+        RC(conv_fwd(y.ec[i], x, ws + y.ea[i][0], nullptr, w + y.enc(i, 0), 0, B, 1, st));
         for (int j = 1; j < 4; ++j)
             RC(lin_fwd(ws + y.ea[i][j - 1], 64, w[y.enc(i, j)], w[y.enc(i, j) + 1], ws + y.ea[i][j], 64, M, 64, 64, 1, nullptr, 0, st));
     }
@@ -190,17 +168,16 @@ int enc_bwd(const float* obs, const float* const* w, float* const* dw, const flo
     const float* last = ws + y.ea[y.n - 1][3];
     RC(lin_bwd(ge, last, w[y.enc_last()], dw[y.enc_last()], dw[y.enc_last() + 1], gb, (long long)B * y.f * y.f, 64, 64, last, nullptr, y, ws, st));
     for (int i = y.n - 1; i >= 0; --i) {
-        const int H = y.S >> i, s = H / 2;
+        const int s = y.S >> (i + 1);
         const long long M = (long long)B * s * s;
         for (int j = 3; j >= 1; --j) {                 // gb = d pre-activation of block j
             const float* x = ws + y.ea[i][j - 1];
             RC(lin_bwd(gb, x, w[y.enc(i, j)], dw[y.enc(i, j)], dw[y.enc(i, j) + 1], ga, M, 64, 64, x, nullptr, y, ws, st));
-            float* t = ga; ga = gb; gb = t;
+            std::swap(ga, gb);
         }
         const float* x = i ? ws + y.ea[i - 1][3] : obs;
-        RC(nc_bwd(x, i ? nhwc(H, 64) : nchw(H, y.C), gb, nhwc(s, 64), i ? ga : nullptr, w[y.enc(i, 0)], dw[y.enc(i, 0)], dw[y.enc(i, 0) + 1],
-                  ws + y.epart[i], y.eslab[i], B, i ? 64 : y.C, H, s, 2, 2, 0, st));
-        float* t = ga; ga = gb; gb = t;
+        RC(nc_bwd(y.ec[i], x, gb, i ? ga : nullptr, w + y.enc(i, 0), dw + y.enc(i, 0), ws + y.epart[i], B, st));
+        std::swap(ga, gb);
     }
     return 0;
 }
@@ -219,7 +196,7 @@ int ocrl_vae_fwd(const float* obs, const float* const* w, const float* eps, floa
     OCRL_REQUIRE(obs && w && rep && ws && (!full || (eps && metrics)), "ocrl_vae_fwd: null argument");
     RC(check_vae(B, obs_size, obs_channels, cnn_feat_size, latent_dim));
     const VaeLay y = vae_layout(B, obs_size, obs_channels, cnn_feat_size, latent_dim, use_cnn_feat, full);
-    OCRL_REQUIRE(ws_floats >= y.total, "ocrl_vae_fwd: workspace too small (%zu < %zu floats)", ws_floats, y.total);
+    RC(ws_check("ocrl_vae_fwd", ws_floats, y.total));
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int L = y.L, f = y.f, HW = f * f, F = 64 * HW, S = y.S;
     RC(enc_fwd(obs, w, ws + y.e, y, ws, st));
@@ -246,7 +223,7 @@ int ocrl_vae_fwd(const float* obs, const float* const* w, const float* eps, floa
         const long long M = (long long)B * s * s;
         const int l3 = y.dec(i, 0);
         if (s < CONV_HIP_MIN) {
-            RC(nc_fwd(x, nhwc(s, 64), ws + y.x3[i], nhwc(s, 64), w[l3], w[l3 + 1], B, 64, s, s, 3, 1, 1, st));
+            RC(conv_fwd(y.dc[i], x, ws + y.x3[i], nullptr, w + l3, 0, B, 1, st));
         } else {
             RC(conv_pack_launch(w[l3], ws + y.pkf[i], ws + y.pkb[i], 3, 64, 64, 64, st));
             ConvArgs a;
@@ -275,7 +252,7 @@ int ocrl_vae_bwd(const float* obs, const float* eps, const float* const* w, cons
     OCRL_REQUIRE(obs && w && dw && ws && (!full || eps) && (full || drep), "ocrl_vae_bwd: null argument");
     RC(check_vae(B, obs_size, obs_channels, cnn_feat_size, latent_dim));
     const VaeLay y = vae_layout(B, obs_size, obs_channels, cnn_feat_size, latent_dim, use_cnn_feat, full);
-    OCRL_REQUIRE(ws_floats >= y.total, "ocrl_vae_bwd: workspace too small (%zu < %zu floats)", ws_floats, y.total);
+    RC(ws_check("ocrl_vae_bwd", ws_floats, y.total));
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int L = y.L, f = y.f, HW = f * f, F = 64 * HW, S = y.S;
     if (!full) {
@@ -308,7 +285,7 @@ int ocrl_vae_bwd(const float* obs, const float* eps, const float* const* w, cons
             const float* x = i ? ws + y.ps[i - 1] : ws + y.d0;
             const int l3 = y.dec(i, 0);
             if (s < CONV_HIP_MIN) {
-                RC(nc_bwd(x, nhwc(s, 64), ga, nhwc(s, 64), gb, w[l3], dw[l3], dw[l3 + 1], ws + y.dpart[i], y.dslab[i], B, 64, s, s, 3, 1, 1, st));
+                RC(nc_bwd(y.dc[i], x, ga, gb, w + l3, dw + l3, ws + y.dpart[i], B, st));
             } else {
                 WgradArgs wa;
                 wa.X = x; wa.dY = ga; wa.part = ws + y.sk; wa.B = B; wa.H = s; wa.W = s;
@@ -318,7 +295,7 @@ int ocrl_vae_bwd(const float* obs, const float* eps, const float* const* w, cons
                 a.X = ga; a.Wp = ws + y.pkb[i]; a.Y = gb; a.B = B; a.H = s; a.W = s; a.mask = x;
                 RC(conv_fwd_launch(a, 3, 64, 64, st));
             }
-            float* t = ga; ga = gb; gb = t;
+            std::swap(ga, gb);
         }
         // ga = d d0 (masked); the decoder's input block, _in_dec, the reparameterisation and KL, _mu / _var
         RC(lin_bwd(ga, ws + y.hin, w[y.dec0()], dw[y.dec0()], dw[y.dec0() + 1], gb, (long long)B * HW, 64, 64, nullptr, nullptr, y, ws, st));
