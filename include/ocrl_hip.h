@@ -170,7 +170,10 @@ int ocrl_layernorm_bwd(const float* dy, const float* x, const float* mean, const
 
 /* Causal multi-head self-attention core of MultiHeadAttention.forward (ocrs/common/transformer.py:31-47): q,k,v are the
  * projected [B,T,d] tensors (row stride ld >= d, heads side by side, q unscaled); o = dropout(softmax(mask(q k^T / sqrt(dh)))) v
- * as [B,T,d]; lse [B,h,T] is saved for the backward.  Dropout decisions come from (seed, site) as in ocrl_slate_forward. */
+ * as [B,T,d]; lse [B,h,T] is saved for the backward.  Dropout decisions come from (seed, site) as in ocrl_slate_forward: the
+ * probability of (b, head, query, key) is element ((b*h + head)*T + query)*T4 + key of the site's stream, T4 = T rounded up to a
+ * multiple of 4 (the site's mask dump is [B,h,T,T4], of which [..., :T] is used; dense [B,h,T,T] when T % 4 == 0).
+ * Every output element is written, none is read: o, lse, dq, dk, dv and delta need no initialisation. */
 int ocrl_attention_fwd(const float* q, const float* k, const float* v, float* o, float* lse, int B, int T, int d, int h, int ld,
                        float p, unsigned long long seed, unsigned site, void* stream);
 /* gradients dq,dk,dv (row stride ld) from dO [B,T,d]; delta is scratch [B,h,T]. */

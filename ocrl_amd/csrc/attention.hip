@@ -1,7 +1,8 @@
 // Causal multi-head self-attention of the SLATE transformer decoder (reference:
 // ocrs/common/transformer.py:23-50), flash-style: scores are never written to HBM.
 // fp32 on v_mfma_f32_16x16x4_f32; softmax statistics online; dropout on the probabilities from the
-// stateless counter RNG (identical decisions in forward and backward, index = ((b*h+head)*T+q)*T+key).
+// stateless counter RNG (identical decisions in forward and backward, index = ((b*h+head)*T+q)*T4+key with T4 = T rounded up to
+// a multiple of 4: common.h attn_drop_ld).
 //
 // Orientation trick (no LDS round trip for P): the forward and the dQ kernel compute S^T = K Q^T, so a lane
 // holds, for its query (lane & 15), the four consecutive keys 4*(lane>>4)+r in accumulator registers r = 0..3 —
@@ -95,7 +96,7 @@ __global__ __launch_bounds__(256, 4) void attn_fwd_kernel(AttnArgs p) {
     bid = FA_LPT ? bid % nbh : bid / nqb;
     const int hd = bid % p.h;
     const long long b = bid / p.h;
-    const int T = p.T, d = p.ld, hoff = hd * DH;
+    const int T = p.T, T4 = attn_drop_ld(p.T), d = p.ld, hoff = hd * DH;
     const long long bt0 = b * T;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int li = lane & 15, g = lane >> 4;
@@ -183,7 +184,7 @@ __global__ __launch_bounds__(256, 4) void attn_fwd_kernel(AttnArgs p) {
         if (p.p > 0.f) {
 #pragma unroll
             for (int st = 0; st < 4; ++st) {
-                const uint64_t idx = ((uint64_t)bh * T + (uint64_t)(q_abs < T ? q_abs : 0)) * T + (uint64_t)(kt * FA_BLK + 16 * st + 4 * g);
+                const uint64_t idx = ((uint64_t)bh * T + (uint64_t)(q_abs < T ? q_abs : 0)) * T4 + (uint64_t)(kt * FA_BLK + 16 * st + 4 * g);
                 const uint2 bits = rng_bits4(p.seed, p.site, idx >> 2);
 #pragma unroll
                 for (int r = 0; r < 4; ++r) s[st][r] = rng_keep(bits, r, thr) ? s[st][r] * dsc : 0.f;
@@ -262,7 +263,7 @@ __global__ __launch_bounds__(256, FA_BWD_WGS) void attn_bwd_kv_kernel(AttnArgs p
     bid = FA_LPT ? bid % nbh : bid / nkb;
     const int hd = bid % p.h;
     const long long b = bid / p.h;
-    const int T = p.T, d = p.ld, hoff = hd * DH;
+    const int T = p.T, T4 = attn_drop_ld(p.T), d = p.ld, hoff = hd * DH;
     const long long bt0 = b * T;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int li = lane & 15, g = lane >> 4;
@@ -327,7 +328,7 @@ __global__ __launch_bounds__(256, FA_BWD_WGS) void attn_bwd_kv_kernel(AttnArgs p
             uint2 hb = make_uint2(0u, 0u);
             if (p.p > 0.f) {
                 const int qh = qt * FA_BLK + 16 * sq + 4 * g + (li & 3);
-                const uint64_t idx = ((uint64_t)bh * T + (uint64_t)(qh < T ? qh : 0)) * T + (uint64_t)(k_abs < T ? k_abs : 0);
+                const uint64_t idx = ((uint64_t)bh * T + (uint64_t)(qh < T ? qh : 0)) * T4 + (uint64_t)(k_abs < T4 ? k_abs : 0);
                 hb = rng_bits4(p.seed, p.site, idx >> 2);
             }
             uint2 hq[4];
@@ -392,7 +393,7 @@ __global__ __launch_bounds__(256, FA_BWD_WGS) void attn_bwd_q_kernel(AttnArgs p)
     bid = FA_LPT ? bid % nbh : bid / nqb;
     const int hd = bid % p.h;
     const long long b = bid / p.h;
-    const int T = p.T, d = p.ld, hoff = hd * DH;
+    const int T = p.T, T4 = attn_drop_ld(p.T), d = p.ld, hoff = hd * DH;
     const long long bt0 = b * T;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int li = lane & 15, g = lane >> 4;
@@ -456,7 +457,7 @@ __global__ __launch_bounds__(256, FA_BWD_WGS) void attn_bwd_q_kernel(AttnArgs p)
             const int key0 = kt * FA_BLK + 16 * st + 4 * g;
             uint2 bits = make_uint2(0u, 0u);
             if (p.p > 0.f) {
-                const uint64_t idx = ((uint64_t)bh * T + (uint64_t)(q_abs < T ? q_abs : 0)) * T + (uint64_t)key0;
+                const uint64_t idx = ((uint64_t)bh * T + (uint64_t)(q_abs < T ? q_abs : 0)) * T4 + (uint64_t)key0;
                 bits = rng_bits4(p.seed, p.site, idx >> 2);
             }
 #pragma unroll
@@ -517,7 +518,7 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_fused_kernel(AttnArgs p) {
     __shared__ float Ls[FA_BLK], Ds[FA_BLK];
     const int hd = blockIdx.x % p.h;
     const long long b = blockIdx.x / p.h;
-    const int T = p.T, d = p.ld, hoff = hd * DH;
+    const int T = p.T, T4 = attn_drop_ld(p.T), d = p.ld, hoff = hd * DH;
     const long long bt0 = b * T;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int li = lane & 15, g = lane >> 4;
@@ -590,7 +591,7 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_fused_kernel(AttnArgs p) {
                 uint2 hb = make_uint2(0u, 0u);
                 if (p.p > 0.f) {
                     const int qh = qt * FA_BLK + 16 * sq + 4 * g + (li & 3);
-                    const uint64_t idx = ((uint64_t)bh * T + (uint64_t)(qh < T ? qh : 0)) * T + (uint64_t)(k_abs < T ? k_abs : 0);
+                    const uint64_t idx = ((uint64_t)bh * T + (uint64_t)(qh < T ? qh : 0)) * T4 + (uint64_t)(k_abs < T4 ? k_abs : 0);
                     hb = rng_bits4(p.seed, p.site, idx >> 2);
                 }
                 uint2 hq[4];

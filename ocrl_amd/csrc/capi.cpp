@@ -83,6 +83,14 @@ int ocrl_slate_create(const ocrl_slate_config* c, ocrl_slate** out) {
         ocrl_set_error("ocrl_slate_create: invalid configuration");
         return 1;
     }
+    // T = (obs_size / 4)^2 tokens; the step's kernels are written for T % 4 == 0 (SlateModel::bind checks the same): refuse here,
+    // before anything is allocated, instead of at bind time
+    if (c->obs_size % 8) {
+        const int e = c->obs_size / 4;
+        ocrl_set_error("ocrl_slate_create: obs_size %d gives %d tokens per image; the token count must be a multiple of 4 (obs_size a multiple of 8)",
+                       c->obs_size, e * e);
+        return 1;
+    }
     SlateConfig k;
     k.obs_size = c->obs_size; k.obs_channels = c->obs_channels; k.vocab = c->vocab_size; k.d_model = c->d_model;
     k.cnn_hidden = c->cnn_hidden; k.num_slots = c->num_slots; k.num_iters = c->num_iterations; k.slot_size = c->slot_size;

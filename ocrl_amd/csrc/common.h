@@ -112,6 +112,14 @@ enum : uint32_t {
     SITE_SLOT_NOISE = 202,
 };
 
+// Dropout index contract of the causal self-attention probabilities (site SITE_BLK_BASE + 8 * block + 0; csrc/attention.hip):
+// the keep decision of (image b, head, query q, key) is element
+//     i = ((b * h + head) * T + q) * T4 + key,     T4 = attn_drop_ld(T) = T rounded up to a multiple of 4,
+// i.e. group i >> 2, slot i & 3 = key & 3 of the site's stream.  Every row starts on a group boundary, so the four kernels (which
+// draw one group per four consecutive keys) and the mask dump agree for every T; the dump of the site is [B, h, T, T4], of which
+// [..., :T] is the mask.  For T % 4 == 0 this is the dense index ((b * h + head) * T + q) * T + key.
+__host__ __device__ inline int attn_drop_ld(int T) { return (T + 3) & ~3; }
+
 __device__ inline float wave_sum(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

@@ -86,6 +86,24 @@ def test_invalid_config_is_rejected_with_message():
     assert b"invalid" in L.ocrl_last_error()
 
 
+@pytest.mark.parametrize("obs_size,ok", [(12, False), (20, False), (28, False), (16, True), (24, True)])
+def test_token_counts_off_the_group_size_are_refused(obs_size, ok):
+    """T = (obs_size/4)^2 must be a multiple of 4 (the step's kernels assume it; self-attention dropout alone is defined for every T,
+    tests/test_gpu_attention_edges.py): obs_size 12, 20, 28 would give T = 9, 25, 49 and are refused at create time with the reason"""
+    from ocrl_amd import _lib
+    L = _lib.lib()
+    c = _lib.SlateConfig(obs_size, 3, 256, 192, 64, 3, 2, 192, 192, 1, 4, 0.1, 1, 0)
+    h = ctypes.c_void_p()
+    rc = L.ocrl_slate_create(ctypes.byref(c), ctypes.byref(h))
+    if ok:
+        assert rc == 0, L.ocrl_last_error()
+        L.ocrl_slate_destroy(h)
+    else:
+        assert rc != 0
+        msg = L.ocrl_last_error().decode()
+        assert f"obs_size {obs_size}" in msg and f"{(obs_size // 4) ** 2} tokens" in msg and "multiple of 8" in msg
+
+
 def test_engine_refuses_cpu_device():
     from ocrl_amd.engine import SlateEngine
     from tests.gpu_util import dims_from_cfg

@@ -48,7 +48,7 @@ def site_masks(eng, cfg, B):
     M = {"z_pos": eng.dropout_mask(1, (B, T + 1, d)).cpu()}
     for b in range(cfg.num_dec_blocks):
         s = 16 + 8 * b
-        M[f"blk{b}.self.attn"] = eng.dropout_mask(s + 0, (B, h, T, T)).cpu()
+        M[f"blk{b}.self.attn"] = eng.dropout_mask(s + 0, (B, h, T, (T + 3) & ~3))[..., :T].cpu()      # key stride T4: csrc/common.h attn_drop_ld
         M[f"blk{b}.self.out"] = eng.dropout_mask(s + 1, (B, T, d)).cpu()
         M[f"blk{b}.cross.attn"] = eng.dropout_mask(s + 2, (B, h, T, K)).cpu()
         M[f"blk{b}.cross.out"] = eng.dropout_mask(s + 3, (B, T, d)).cpu()
@@ -149,6 +149,15 @@ def test_forward_backward_eval(tag, over, B):
     torch.cuda.synchronize()
     worst, rows = compare_grads(tag, eng, tr, cfg, P, obs, noise, step)
     assert worst < GRAD_TOL, rows[:5]
+
+
+@pytest.mark.parametrize("dropout", [0.0, 0.1])
+def test_odd_token_count_is_refused(dropout):
+    """obs_size = 12 (T = 9 tokens): outside self-attention the step's kernels assume T % 4 == 0, so the configuration is refused with
+    the reason when the engine is created -- with and without dropout -- instead of being computed wrong"""
+    cfg = O.default_cfg(obs_size=12, vocab_size=256, num_slots=3, num_iterations=2, num_dec_blocks=1, dropout=dropout)
+    with pytest.raises(RuntimeError, match="obs_size 12 gives 9 tokens.*multiple of 8"):
+        make_engine(cfg, 2)
 
 
 @pytest.mark.parametrize("over", [SMALL, LONG])
