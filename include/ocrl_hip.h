@@ -163,6 +163,32 @@ int ocrl_conv2d_bwd_data(const float* dy, const float* w, const float* mask, flo
 size_t ocrl_conv2d_wgrad_ws_floats(int B, int H, int W, int ks, int cin_pad);
 int ocrl_conv2d_bwd_weight(const float* x, const float* dy, float* dw, float* db, int B, int H, int W, int cin, int cin_pad, int ks,
                            float* ws, size_t ws_floats, void* stream);
+/* The same convolution kernels with every argument they take (unit tests of each instantiation and epilogue; csrc/kernels.h ConvArgs
+ * documents the fields).  x [B,H,W,cin_pad], y [B,H,W,64] NHWC, w [64,cin,ks,ks] in the reference layout; (ks, cin_pad) is (5, 64),
+ * (5, 8) or (3, 64).  Epilogue in this order: + bias[co]; relu = 1 ReLU, 2 ELU; + posmap [H,W,64]; mask [B,H,W,64]: v where m > 0,
+ * else 0, or v * (m + 1) with mask_elu (m = the ELU output of the layer below, so m + 1 = ELU'(pre-activation)).  transposed = 1 packs
+ * the flipped taps with ci / co swapped, the backward-data form (x = dy, y = dx; needs cin = cin_pad = 64).  low_latency = 1 asks for the
+ * k-split kernel, which serves 5x5 / 64 channels, relu <= 1, no mask, at most 160 tiles; every other request runs the throughput kernel.
+ * ws: ks*ks*cin_pad*64 floats, twice that when transposed (the packs, laid out as ocrl_conv2d_fwd / ocrl_conv2d_bwd_data lay them out).
+ * Every pointer 16-byte aligned; fields left zero by memset are "absent".  An unsupported combination is an error, never another kernel. */
+typedef struct ocrl_conv_desc {
+    const float* x; const float* w; float* y;
+    int B, H, W, cin, cin_pad, ks;
+    const float* bias; int relu;
+    const float* posmap; const float* mask; int mask_elu;
+    int transposed, low_latency;
+} ocrl_conv_desc;
+size_t ocrl_conv_desc_size(void);
+int ocrl_conv2d_ex(const ocrl_conv_desc* d, float* ws, size_t ws_floats, void* stream);
+/* ocrl_conv2d_bwd_weight with the accumulate switch of the model paths: accumulate = 1 gives dw += and db += (IODINE sums the decoder's
+ * weight gradients over its refinement iterations), 0 overwrites.  db may be NULL; ws from ocrl_conv2d_wgrad_ws_floats. */
+typedef struct ocrl_conv_wgrad_desc {
+    const float* x; const float* dy; float* dw; float* db;
+    int B, H, W, cin, cin_pad, ks;
+    int accumulate;
+} ocrl_conv_wgrad_desc;
+size_t ocrl_conv_wgrad_desc_size(void);
+int ocrl_conv2d_bwd_weight_ex(const ocrl_conv_wgrad_desc* d, float* ws, size_t ws_floats, void* stream);
 /* nn.LayerNorm(F) forward / backward over R rows (F in {64,128,192,256}); dgb = [dgamma | dbeta]. */
 int ocrl_layernorm_fwd(const float* x, const float* gamma, const float* beta, float* y, float* mean, float* rstd, long long R, int F, void* stream);
 int ocrl_layernorm_bwd(const float* dy, const float* x, const float* mean, const float* rstd, const float* gamma, float* dx, float* dgb,

@@ -36,6 +36,20 @@ class GemmDesc(ctypes.Structure):
                 ("force_tile", c_int), ("force_sb", c_int)]
 
 
+class ConvDesc(ctypes.Structure):
+    """mirror of ocrl_conv_desc (include/ocrl_hip.h); make one with conv_desc()"""
+    _fields_ = [("x", c_void_p), ("w", c_void_p), ("y", c_void_p)] + \
+               [(n, c_int) for n in ("B", "H", "W", "cin", "cin_pad", "ks")] + \
+               [("bias", c_void_p), ("relu", c_int), ("posmap", c_void_p), ("mask", c_void_p), ("mask_elu", c_int),
+                ("transposed", c_int), ("low_latency", c_int)]
+
+
+class ConvWgradDesc(ctypes.Structure):
+    """mirror of ocrl_conv_wgrad_desc (include/ocrl_hip.h); make one with conv_wgrad_desc()"""
+    _fields_ = [("x", c_void_p), ("dy", c_void_p), ("dw", c_void_p), ("db", c_void_p)] + \
+               [(n, c_int) for n in ("B", "H", "W", "cin", "cin_pad", "ks", "accumulate")]
+
+
 class AcnetDesc(ctypes.Structure):
     """mirror of ocrl_acnet_desc (include/ocrl_hip.h); make one with acnet_desc()"""
     _fields_ = [("B", c_int), ("F", c_int), ("A", c_int), ("n", c_int * 3), ("dims", (c_int * 8) * 3), ("acts", (c_int * 8) * 3)]
@@ -56,6 +70,23 @@ def acnet_desc(B, F, A, dims, acts):
 def gemm_desc(**kw):
     """GemmDesc with the defaults of GemmArgs (alpha = 1, one batch, no split, the dispatch rule) and the given fields"""
     d = GemmDesc(batch=1, batch_inner=1, splitk=1, alpha=1.0, x_scale=1.0, e_scale=1.0, force_sb=-1)
+    for k, v in kw.items():
+        setattr(d, k, v)
+    return d
+
+
+def conv_desc(**kw):
+    """ConvDesc with the given fields; every other field is zero (no bias, no activation, no posmap, no mask, the forward pack, the
+    throughput kernel)"""
+    d = ConvDesc()
+    for k, v in kw.items():
+        setattr(d, k, v)
+    return d
+
+
+def conv_wgrad_desc(**kw):
+    """ConvWgradDesc with the given fields; every other field is zero (no bias gradient, overwrite)"""
+    d = ConvWgradDesc()
     for k, v in kw.items():
         setattr(d, k, v)
     return d
@@ -121,6 +152,14 @@ def lib():
     L.ocrl_conv2d_wgrad_ws_floats.argtypes = [c_int, c_int, c_int, c_int, c_int]
     L.ocrl_conv2d_wgrad_ws_floats.restype = c_size_t
     L.ocrl_conv2d_bwd_weight.argtypes = [p, p, p, p, c_int, c_int, c_int, c_int, c_int, c_int, p, c_size_t, p]
+    L.ocrl_conv_desc_size.restype = c_size_t
+    L.ocrl_conv_wgrad_desc_size.restype = c_size_t
+    for name, cls in (("ocrl_conv_desc", ConvDesc), ("ocrl_conv_wgrad_desc", ConvWgradDesc)):
+        n = getattr(L, name + "_size")()
+        if n != ctypes.sizeof(cls):
+            raise RuntimeError(f"libocrl_hip.so: {name} is {n} bytes, this binding's {cls.__name__} {ctypes.sizeof(cls)}")
+    L.ocrl_conv2d_ex.argtypes = [POINTER(ConvDesc), p, c_size_t, p]
+    L.ocrl_conv2d_bwd_weight_ex.argtypes = [POINTER(ConvWgradDesc), p, c_size_t, p]
     L.ocrl_layernorm_fwd.argtypes = [p, p, p, p, p, p, c_longlong, c_int, p]
     L.ocrl_layernorm_bwd.argtypes = [p, p, p, p, p, p, p, c_longlong, c_int, p, c_size_t, p]
     L.ocrl_attention_fwd.argtypes = [p, p, p, p, p, c_int, c_int, c_int, c_int, c_int, c_float, c_ulonglong, c_uint, p]

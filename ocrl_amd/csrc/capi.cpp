@@ -1,5 +1,6 @@
 // extern "C" boundary of libocrl_hip.so (see include/ocrl_hip.h).
 #include <stdarg.h>
+#include <stdint.h>
 #include <string.h>
 
 #include <new>
@@ -251,6 +252,46 @@ int ocrl_conv2d_bwd_weight_x3(const float* x, const float* dy, float* dw, int B,
     WgradArgs a;
     a.X = x; a.dY = dy; a.part = ws; a.B = B; a.H = H; a.W = W;
     return conv_wgrad_launch(a, ks, 64, 64, 64, dw, 0, ST(stream), 1);
+}
+static bool conv_kernel_built(int ks, int cin_pad) { return (ks == 5 && (cin_pad == 64 || cin_pad == 8)) || (ks == 3 && cin_pad == 64); }
+static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+size_t ocrl_conv_desc_size(void) { return sizeof(ocrl_conv_desc); }
+int ocrl_conv2d_ex(const ocrl_conv_desc* d, float* ws, size_t ws_floats, void* stream) {
+    if (!d) { ocrl_set_error("ocrl_conv2d_ex: null descriptor"); return 1; }
+    if (!d->x || !d->w || !d->y || !ws || d->B < 1 || d->H < 1 || d->W < 1) { ocrl_set_error("ocrl_conv2d_ex: x, w, y, ws and a non-empty image are required"); return 1; }
+    if (!conv_kernel_built(d->ks, d->cin_pad)) { ocrl_set_error("ocrl_conv2d_ex: no kernel for ks=%d cin_pad=%d (built: 5/64, 5/8, 3/64)", d->ks, d->cin_pad); return 1; }
+    if (d->cin < 1 || d->cin > d->cin_pad) { ocrl_set_error("ocrl_conv2d_ex: cin %d outside 1 .. cin_pad %d", d->cin, d->cin_pad); return 1; }
+    if (d->relu < 0 || d->relu > 2) { ocrl_set_error("ocrl_conv2d_ex: relu must be 0, 1 (ReLU) or 2 (ELU), got %d", d->relu); return 1; }
+    if (d->mask_elu && !d->mask) { ocrl_set_error("ocrl_conv2d_ex: mask_elu needs a mask"); return 1; }
+    if (d->transposed && (d->cin != 64 || d->cin_pad != 64)) { ocrl_set_error("ocrl_conv2d_ex: the transposed (backward-data) form needs cin = cin_pad = 64"); return 1; }
+    if (!aligned16(d->x) || !aligned16(d->y) || !aligned16(ws) || !aligned16(d->bias) || !aligned16(d->posmap) || !aligned16(d->mask)) {
+        ocrl_set_error("ocrl_conv2d_ex: x, y, ws, bias, posmap and mask must be 16-byte aligned");
+        return 1;
+    }
+    const size_t pack = (size_t)d->ks * d->ks * d->cin_pad * 64, need = d->transposed ? 2 * pack : pack;
+    if (ws_floats < need) { ocrl_set_error("ocrl_conv2d_ex: workspace of %zu floats, %zu needed", ws_floats, need); return 1; }
+    float* bw = d->transposed ? ws + pack : nullptr;
+    if (conv_pack_launch(d->w, ws, bw, d->ks, d->cin_pad, 64, d->cin, ST(stream))) return 1;
+    ConvArgs a;
+    a.X = d->x; a.Wp = bw ? bw : ws; a.Y = d->y; a.B = d->B; a.H = d->H; a.W = d->W; a.bias = d->bias; a.relu = d->relu;
+    a.posmap = d->posmap; a.mask = d->mask; a.mask_elu = d->mask_elu ? 1 : 0;
+    return conv_fwd_launch(a, d->ks, d->cin_pad, 64, ST(stream), d->low_latency ? 1 : 0);
+}
+size_t ocrl_conv_wgrad_desc_size(void) { return sizeof(ocrl_conv_wgrad_desc); }
+int ocrl_conv2d_bwd_weight_ex(const ocrl_conv_wgrad_desc* d, float* ws, size_t ws_floats, void* stream) {
+    if (!d) { ocrl_set_error("ocrl_conv2d_bwd_weight_ex: null descriptor"); return 1; }
+    if (!d->x || !d->dy || !d->dw || !ws || d->B < 1 || d->H < 1 || d->W < 1) { ocrl_set_error("ocrl_conv2d_bwd_weight_ex: x, dy, dw, ws and a non-empty image are required"); return 1; }
+    if (!conv_kernel_built(d->ks, d->cin_pad)) { ocrl_set_error("ocrl_conv2d_bwd_weight_ex: no kernel for ks=%d cin_pad=%d (built: 5/64, 5/8, 3/64)", d->ks, d->cin_pad); return 1; }
+    if (d->cin < 1 || d->cin > d->cin_pad) { ocrl_set_error("ocrl_conv2d_bwd_weight_ex: cin %d outside 1 .. cin_pad %d", d->cin, d->cin_pad); return 1; }
+    if (!aligned16(d->x) || !aligned16(d->dy) || !aligned16(ws)) { ocrl_set_error("ocrl_conv2d_bwd_weight_ex: x, dy and ws must be 16-byte aligned"); return 1; }
+    const size_t need = ocrl_conv2d_wgrad_ws_floats(d->B, d->H, d->W, d->ks, d->cin_pad);
+    if (ws_floats < need) { ocrl_set_error("ocrl_conv2d_bwd_weight_ex: workspace of %zu floats, %zu needed", ws_floats, need); return 1; }
+    const int acc = d->accumulate ? 1 : 0;
+    WgradArgs a;
+    a.X = d->x; a.dY = d->dy; a.part = ws; a.B = d->B; a.H = d->H; a.W = d->W;
+    if (conv_wgrad_launch(a, d->ks, d->cin_pad, 64, d->cin, d->dw, acc, ST(stream), 0)) return 1;
+    if (d->db) return colsum_launch(d->dy, 64, d->db, (long long)d->B * d->H * d->W, 64, acc, 1.f, ws, ws_floats, ST(stream));
+    return 0;
 }
 int ocrl_layernorm_fwd(const float* x, const float* g, const float* b, float* y, float* mean, float* rstd, long long R, int F, void* stream) {
     return layernorm_fwd_launch(x, g, b, y, mean, rstd, R, F, ST(stream));

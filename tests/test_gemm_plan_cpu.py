@@ -31,16 +31,72 @@ def mm(akc, bkc, M, N, K, **kw):
     return dict(akc=akc, bkc=bkc, M=M, N=N, K=K, lda=K if akc else M, ldb=K if bkc else N, ldc=N, **kw)
 
 
-def test_desc_struct_matches_the_header(L):
+def header_fields(struct):
+    """field names and C types of a descriptor struct of include/ocrl_hip.h, in declaration order"""
     hdr = open(os.path.join(ROOT, "include", "ocrl_hip.h")).read()
-    body = re.search(r"typedef struct ocrl_gemm_desc \{(.*?)\} ocrl_gemm_desc;", hdr, re.S).group(1)
-    fields = []
+    body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (struct, struct), hdr, re.S).group(1)
+    names, types = [], []
     for decl in body.split(";"):
         decl = decl.strip()
         if decl:
-            fields += [re.search(r"(\w+)$", f.strip()).group(1) for f in decl.split(",")]
+            parts = [f.strip() for f in decl.split(",")]
+            ctype = re.match(r"(.*?)(\w+)$", parts[0]).group(1).strip()
+            for f in parts:
+                names.append(re.search(r"(\w+)$", f).group(1))
+                types.append(ctype)
+    return names, types
+
+
+def test_desc_struct_matches_the_header(L):
+    fields, _ = header_fields("ocrl_gemm_desc")
     assert [n for n, _ in L.GemmDesc._fields_] == fields
     assert L.lib().ocrl_gemm_desc_size() == ctypes.sizeof(L.GemmDesc)
+
+
+@pytest.mark.parametrize("struct,cls,size_fn", [("ocrl_conv_desc", "ConvDesc", "ocrl_conv_desc_size"),
+                                                ("ocrl_conv_wgrad_desc", "ConvWgradDesc", "ocrl_conv_wgrad_desc_size")])
+def test_conv_desc_structs_match_the_header(L, struct, cls, size_fn):
+    fields, types = header_fields(struct)
+    mirror = getattr(L, cls)
+    assert [n for n, _ in mirror._fields_] == fields
+    # pointers mirror pointers, ints mirror ints: equal sizes alone would not show an int where a 4-byte float is declared
+    for (n, t), c in zip(mirror._fields_, types):
+        assert t is (ctypes.c_void_p if c.endswith("*") else {"int": ctypes.c_int}[c]), (n, c)
+    assert getattr(L.lib(), size_fn)() == ctypes.sizeof(mirror)
+
+
+def test_conv_desc_makers_default_to_absent():
+    from ocrl_amd import _lib
+    d = _lib.conv_desc(B=2, ks=5, relu=2, x=FAKE)
+    assert (d.B, d.ks, d.relu, d.x) == (2, 5, 2, FAKE)
+    assert (d.bias, d.posmap, d.mask, d.mask_elu, d.transposed, d.low_latency) == (None, None, None, 0, 0, 0)
+    g = _lib.conv_wgrad_desc(cin=3, cin_pad=8, accumulate=1)
+    assert (g.cin, g.cin_pad, g.accumulate, g.db) == (3, 8, 1, None)
+
+
+@pytest.mark.parametrize("kw,msg", [
+    (dict(ks=4, cin=64, cin_pad=64), "no kernel"),
+    (dict(ks=3, cin=3, cin_pad=8), "no kernel"),
+    (dict(ks=5, cin=9, cin_pad=8), "cin"),
+    (dict(ks=5, cin=64, cin_pad=64, relu=3), "relu"),
+    (dict(ks=5, cin=64, cin_pad=64, mask_elu=1), "mask_elu"),
+    (dict(ks=5, cin=3, cin_pad=8, transposed=1), "transposed"),
+    (dict(ks=5, cin=64, cin_pad=64, bias=FAKE + 4), "aligned"),
+    (dict(ks=5, cin=64, cin_pad=64, B=0), "non-empty"),
+    (dict(ks=5, cin=64, cin_pad=64, transposed=1, ws_floats=25 * 64 * 64), "workspace"),
+])
+def test_unsupported_convolutions_are_refused_before_any_launch(L, kw, msg):
+    """ocrl_conv2d_ex returns 1 with a message for what no kernel serves; the checks come before the first launch, so the fake
+    addresses are never touched"""
+    kw = dict(kw)
+    ws_floats = kw.pop("ws_floats", 1 << 20)
+    base = dict(x=FAKE, w=FAKE, y=FAKE, B=1, H=4, W=4)
+    base.update(kw)
+    assert L.lib().ocrl_conv2d_ex(L.conv_desc(**base), FAKE, ws_floats, None) == 1
+    assert msg in L.lib().ocrl_last_error().decode()
+    if not {"relu", "mask_elu", "transposed", "bias"} & set(kw):
+        g = dict(x=FAKE, dy=FAKE, dw=FAKE, B=base["B"], H=4, W=4, ks=base["ks"], cin=base["cin"], cin_pad=base["cin_pad"])
+        assert L.lib().ocrl_conv2d_bwd_weight_ex(L.conv_wgrad_desc(**g), FAKE, 16, None) == 1
 
 
 def rule(akc, bkc, M, N, K):

@@ -176,6 +176,8 @@ def test_conv_split_precision_exploratory(L, B, H, W, ks):
         f"weight gradient {ew:.2e} ({ew0:.2e}) vs fp64")
     assert torch.isfinite(y).all() and torch.isfinite(dx).all() and torch.isfinite(dw).all()
     assert e < TOL and eb < TOL and ew < TOL
+    assert e0 < TOL and eb0 < TOL and ew0 < TOL          # the default fp32 kernels at the same (ragged) shapes
+    assert torch.isfinite(dw0).all()
 
 
 @pytest.mark.parametrize("B,S,ks", [(2, 16, 5), (2, 32, 5), (2, 12, 3)])
