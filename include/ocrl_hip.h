@@ -442,6 +442,15 @@ int ocrl_ari_counts(const float* truth, long long t_sb, long long t_sc, long lon
  * _ppo_fwd_bwd: the whole minibatch step.  actions: int64 [B] in [0, A) (clamped into the range); scalars [6] = loss, policy_loss,
  *   value_loss, entropy_loss, approx_kl, clip_fraction; dw, dfeatures = gradients of `loss`.  With normalize_advantage the advantages
  *   become (adv - mean) / (std + 1e-8), unbiased std; B == 1 is then rejected.  At most three launches.
+ * _act: the rollout's step: _fwd (save = 0, no workspace) with the action and its log-probability in the same single launch.  Needs the
+ *   heads (A >= 1; A == 0 is rejected).  actions int64 [B], values [B], log_prob [B]; logits [B, A] may be NULL.  The sampling rule:
+ *     u in [0, 1) is a 24-bit uniform (k / 2^24): uniforms[r] when `uniforms` is given, else a pure function of (seed, row_offset + r)
+ *       from the library's counter RNG, so a row's result depends neither on B nor on its position in the batch;
+ *     lse = max + log(sum_j exp(logits_j - max)), p_j = exp(logits_j - lse), c_a = p_0 + ... + p_a, all fp32, summed in index order;
+ *     action = the number of a in [0, A - 2] with c_a <= u: the last action absorbs the rounding of the sum, the result is in [0, A);
+ *     deterministic != 0: action = the lowest index of the maximum logit (torch.argmax), no draw;
+ *     log_prob = logits[action] - lse either way.
+ *   _act_uniforms writes out[i] = the uniform of row row_offset + i of the stream `seed`, i < n: exactly what _act draws.
  * Bit-reproducible: no atomics; per-tile partial gradients are summed in a fixed order; a row's outputs do not depend on its position. */
 #define OCRL_ACNET_MAX_LAYERS 8
 typedef struct {
@@ -460,10 +469,24 @@ int ocrl_acnet_ppo_fwd_bwd(const ocrl_acnet_desc* d, const float* features, cons
                            const float* old_log_prob, const float* advantages, const float* returns, float clip_range, float vf_coef,
                            float ent_coef, int normalize_advantage, float* scalars, float* dfeatures, float* const* dw, float* ws,
                            size_t ws_floats, void* stream);
+int ocrl_acnet_act(const ocrl_acnet_desc* d, const float* features, const float* const* w, unsigned long long seed,
+                   unsigned long long row_offset, const float* uniforms /* NULL = draw */, int deterministic, long long* actions, float* values,
+                   float* log_prob, float* logits /* may be NULL */, void* stream);
+int ocrl_acnet_act_uniforms(unsigned long long seed, unsigned long long row_offset, long long n, float* out, void* stream);
 /* Generalised advantage estimation as stable-baselines3's RolloutBuffer.compute_returns_and_advantage: rewards, values, episode_starts
  * [T, E], last_values, dones [E] -> advantages, returns [T, E]; one thread per environment walks T backwards. */
 int ocrl_gae(const float* rewards, const float* values, const float* episode_starts, const float* last_values, const float* dones,
              float* advantages, float* returns, int T, int E, float gamma, float gae_lambda, void* stream);
+
+/* ---- L2 gradient clip + Adam on caller-owned flat fp32 buffers p, g, m, v [n] (16-byte aligned), as PPO.train applies
+ *      torch.nn.utils.clip_grad_norm_ and torch.optim.Adam to the policy.  Stateless, no host synchronisation, no atomics:
+ *      norm = ||g||_2 over the whole buffer (per-block sums of squares folded in a fixed order; written to norm_out, 1 device float),
+ *      coef = min(1, max_norm / (norm + 1e-6)) (max_norm <= 0: no clipping; norm_out is still written), then the bias-corrected Adam
+ *      update of p, m, v with g * coef; `step` counts from 1.  n >= 1, any tail; ws: ocrl_flat_clip_adam_ws_floats() floats.
+ *      Four small launches (three of the norm, one update), five when n is not a multiple of 4. */
+size_t ocrl_flat_clip_adam_ws_floats(void);
+int ocrl_flat_clip_adam_l2(float* p, const float* g, float* m, float* v, long long n, float max_norm, float lr, float beta1, float beta2,
+                           float eps, int step, float* norm_out /* device, 1 float */, float* ws, size_t ws_floats, void* stream);
 
 /* ---- IODINE (ocrs/iodine/iodine_module.py:14-271, ocrs/iodine/iodine.py:4-14, ocrs/base.py:60-74): SURVEY.md §8 row a20 ----
  * Same conventions as the SLATE handle: flat fp32 parameter / gradient / Adam buffers in the reference's

@@ -6,6 +6,7 @@
 #define ACNET_MAX_WIDTH 256     // of a trunk layer
 #define ACNET_MAX_ACTIONS 64
 #define ACNET_MAX_SLABS 64      // partial-gradient slabs: workgroup s walks the row tiles s, s + S, ...
+#define SITE_ACNET_ACT 400u     // rng site of the action draw (common.h keeps the encoder's sites below 300, pool_unit.cpp 300 .. 399)
 #define ACNET_NPARAM (2 * (3 * ACNET_MAX_LAYERS + 2))
 
 // trunks: 0 = shared, 1 = policy, 2 = value.  act: 0 none, 1 ReLU, 2 tanh.  Every pointer is fp32 device memory.
@@ -32,6 +33,15 @@ struct AcnetArgs {
     float* scal_slab;                                 // [S][8] partial sums of the six scalars
 };
 
+// the sampling tail of acnet_act: row r draws from (seed, row_offset + r) unless `uniforms` [B] is given
+struct AcnetActArgs {
+    unsigned long long seed, row_offset;
+    const float* uniforms;
+    int deterministic;                                // the lowest index of the maximum logit instead of a draw
+    long long* actions;                               // [B]
+    float* log_prob;                                  // [B] log-probability of the action taken
+};
+
 struct AcnetReduceArgs {
     const float* slab;
     long long stride, total, off[ACNET_NPARAM + 1];   // parameter q covers [off[q], off[q + 1]) of a slab
@@ -43,6 +53,8 @@ struct AcnetReduceArgs {
 };
 
 int acnet_fwd_launch(const AcnetArgs& a, hipStream_t st);
+int acnet_act_launch(const AcnetArgs& a, const AcnetActArgs& s, hipStream_t st);
+int acnet_act_uniforms_launch(unsigned long long seed, unsigned long long row_offset, long long n, float* out, hipStream_t st);
 int acnet_bwd_launch(const AcnetArgs& a, hipStream_t st);
 int acnet_ppo_launch(const AcnetArgs& a, hipStream_t st);
 int acnet_reduce_launch(const AcnetReduceArgs& r, hipStream_t st);

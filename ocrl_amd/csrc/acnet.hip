@@ -9,6 +9,8 @@
 //   acnet_bwd        cotangents of latents / logits / values -> per-slab partial dW, db and dfeatures
 //   acnet_ppo        forward, log-softmax, log-prob gather, entropy, ratio, clipping, the loss sums and their gradient, and the
 //                    backward, per row tile in one kernel; logits, probabilities and layer cotangents never leave LDS
+//   acnet_act        the forward with the rollout's tail in the same launch: log-softmax, the action (drawn from one 24-bit uniform
+//                    per row, or the argmax) and its log-probability; one lane owns a row's tail (include/ocrl_hip.h ocrl_acnet_act)
 //   acnet_reduce     dw = sum of the slabs in slab order; the six PPO scalars from their partial sums
 //   acnet_adv_stats  mean and 1 / (std + 1e-8) (unbiased std) of the advantages, one workgroup, fixed order
 //   gae              generalised advantage estimation, one thread per environment walking T backwards
@@ -280,6 +282,51 @@ __global__ __launch_bounds__(256) void acnet_fwd_kernel(AcnetArgs p) {
     fwd_tile(p, row0, rows, buf, lg, vl);
 }
 
+// the uniform of global row `idx` of a sampling stream: the top 24 bits of one counter draw, in [0, 1)
+__host__ __device__ inline float act_uniform(unsigned long long seed, unsigned long long idx) {
+    const uint32_t key = rng_key(seed, SITE_ACNET_ACT, (uint32_t)(idx >> 32));
+    return (float)(rng_bits1_keyed(key, (uint32_t)idx) >> 8) * (1.f / 16777216.f);
+}
+
+// Forward of a tile, then lane r < rows finishes row r from the logits and the value in LDS (A <= 64: the tail is serial in a).
+__global__ __launch_bounds__(256) void acnet_act_kernel(AcnetArgs p, AcnetActArgs s) {
+    __shared__ __attribute__((aligned(16))) float buf[3 * TR * LD];
+    __shared__ __attribute__((aligned(16))) float lg[TR * LA];
+    __shared__ float vl[TR];
+    const long long row0 = (long long)blockIdx.x * TR;
+    const int rows = p.B - row0 < TR ? (int)(p.B - row0) : TR;
+    fwd_tile(p, row0, rows, buf, lg, vl);               // ends on a barrier: lg and vl are complete
+    const int r = threadIdx.x;
+    if (r >= rows) return;
+    const long long row = row0 + r;
+    const float* z = lg + r * LA;
+    const int A = p.A;
+    float m = z[0];
+    int best = 0;
+    for (int a = 1; a < A; ++a)
+        if (z[a] > m) { m = z[a]; best = a; }           // strict: the lowest index of the maximum
+    float se = 0.f;
+    for (int a = 0; a < A; ++a) se += expf(z[a] - m);
+    const float lse = m + logf(se);
+    int act = best;
+    if (!s.deterministic) {
+        const float u = s.uniforms ? s.uniforms[row] : act_uniform(s.seed, s.row_offset + (unsigned long long)row);
+        float c = 0.f;
+        act = 0;
+        for (int a = 0; a + 1 < A; ++a) {
+            c += expf(z[a] - lse);
+            act += c <= u ? 1 : 0;
+        }
+    }
+    s.actions[row] = act;
+    s.log_prob[row] = z[act] - lse;
+}
+
+__global__ __launch_bounds__(256) void acnet_act_uniforms_kernel(unsigned long long seed, unsigned long long row_offset, long long n, float* __restrict__ out) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) out[i] = act_uniform(seed, row_offset + (unsigned long long)i);
+}
+
 __global__ __launch_bounds__(256) void acnet_bwd_kernel(AcnetArgs p) {
     __shared__ __attribute__((aligned(16))) float buf[3 * TR * LD];
     __shared__ __attribute__((aligned(16))) float lg[TR * LA];
@@ -437,6 +484,16 @@ __global__ __launch_bounds__(64) void gae_kernel(const float* __restrict__ rw, c
 int acnet_fwd_launch(const AcnetArgs& a, hipStream_t st) {
     hipLaunchKernelGGL(acnet_fwd_kernel, dim3(cdiv(a.B, TR)), dim3(256), 0, st, a);
     OCRL_CHECK_LAUNCH("acnet_fwd");
+    return 0;
+}
+int acnet_act_launch(const AcnetArgs& a, const AcnetActArgs& s, hipStream_t st) {
+    hipLaunchKernelGGL(acnet_act_kernel, dim3(cdiv(a.B, TR)), dim3(256), 0, st, a, s);
+    OCRL_CHECK_LAUNCH("acnet_act");
+    return 0;
+}
+int acnet_act_uniforms_launch(unsigned long long seed, unsigned long long row_offset, long long n, float* out, hipStream_t st) {
+    hipLaunchKernelGGL(acnet_act_uniforms_kernel, dim3(cdiv(n, 256)), dim3(256), 0, st, seed, row_offset, n, out);
+    OCRL_CHECK_LAUNCH("acnet_act_uniforms");
     return 0;
 }
 int acnet_bwd_launch(const AcnetArgs& a, hipStream_t st) {

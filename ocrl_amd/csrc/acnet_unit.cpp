@@ -123,6 +123,25 @@ int ocrl_acnet_fwd(const ocrl_acnet_desc* d, const float* features, const float*
     return acnet_fwd_launch(a, static_cast<hipStream_t>(stream));
 }
 
+int ocrl_acnet_act(const ocrl_acnet_desc* d, const float* features, const float* const* w, unsigned long long seed, unsigned long long row_offset,
+                   const float* uniforms, int deterministic, long long* actions, float* values, float* log_prob, float* logits, void* stream) {
+    RC(check_acnet(d, "ocrl_acnet_act"));
+    OCRL_REQUIRE(d->A >= 1, "ocrl_acnet_act: acting needs the heads (1 <= n_actions <= %d, got 0)", ACNET_MAX_ACTIONS);
+    const AcLay y = ac_layout(d);
+    OCRL_REQUIRE(features && w && actions && values && log_prob, "ocrl_acnet_act: null argument");
+    RC(check_ptrs(w, y.np, "ocrl_acnet_act"));
+    AcnetArgs a;
+    fill_args(a, d, y, features, w, nullptr, false);
+    a.logits = logits; a.values = values;
+    AcnetActArgs s{seed, row_offset, uniforms, deterministic ? 1 : 0, actions, log_prob};
+    return acnet_act_launch(a, s, static_cast<hipStream_t>(stream));
+}
+
+int ocrl_acnet_act_uniforms(unsigned long long seed, unsigned long long row_offset, long long n, float* out, void* stream) {
+    OCRL_REQUIRE(out && n >= 1, "ocrl_acnet_act_uniforms: null output or n < 1 (got %lld)", n);
+    return acnet_act_uniforms_launch(seed, row_offset, n, out, static_cast<hipStream_t>(stream));
+}
+
 int ocrl_acnet_bwd(const ocrl_acnet_desc* d, const float* features, const float* const* w, const float* dlatent_pi, const float* dlatent_vf,
                    const float* dlogits, const float* dvalues, float* dfeatures, float* const* dw, float* ws, size_t ws_floats, void* stream) {
     RC(check_acnet(d, "ocrl_acnet_bwd"));

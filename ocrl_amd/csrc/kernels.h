@@ -427,6 +427,9 @@ int absmax_launch(const float* g, long long n, float* out, float* ws, size_t ws_
 // g is first scaled by gscale (1/world for data parallel mean), then clipped by the inf-norm in norm[0]*gscale
 int clip_adam_launch(float* p, const float* g, float* m, float* v, long long n, const float* norm, float clip, float lr, double b1,
                      double b2, double eps, int step, float gscale, hipStream_t st);
+// the same update on 1 .. 3 trailing elements (any alignment)
+int clip_adam_tail_launch(float* p, const float* g, float* m, float* v, int n, const float* norm, float clip, float lr, double b1, double b2,
+                          double eps, int step, float gscale, hipStream_t st);
 int store_u64_launch(unsigned long long* dst, unsigned long long v, hipStream_t st);
 int slot_init_launch(const float* mu, const float* logsig, const float* noise, float* slots0, int BK, int D, unsigned long long seed, hipStream_t st,
                      const unsigned long long* seed_dev = nullptr);

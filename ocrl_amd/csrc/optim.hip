@@ -38,30 +38,47 @@ __global__ void absmax_final_kernel(const float* __restrict__ part, int n, float
 // (torch.clamp(max=1) does; fminf would return 1), so a NaN norm reaches every weight.  omb1 / omb2 are 1 - beta and bc1 /
 // bc2_sqrt the bias corrections, all computed in double from the decimal betas and rounded once: 1.f - 0.999f is 1.3e-5 away from
 // 0.001 (the rounding of 0.999f, small against 1, is 2^-14 of the difference), and 1 - 0.999f^t carries the same error at small t.
-__global__ __launch_bounds__(256) void clip_adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                       float* __restrict__ v, long long n4, const float* __restrict__ norm, float clip,
-                                                       float lr, float omb1, float b2, float omb2, float eps, float bc1, float bc2_sqrt, float gscale) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n4) return;
+__device__ __forceinline__ float clip_coef(const float* __restrict__ norm, float clip, float gscale) {
     float coef = gscale;
     if (clip > 0.f) {
         const float c = clip / (norm[0] * gscale + 1e-6f);
         coef *= c > 1.0f ? 1.0f : c;
     }
+    return coef;
+}
+// one element of the update; step = lr / bc1
+__device__ __forceinline__ void adam_upd(float gg, float& mm, float& vq, float& pp, float coef, float step, float omb1, float b2, float omb2,
+                                         float eps, float bc2_sqrt) {
+    gg *= coef;
+    mm = mm + (gg - mm) * omb1;                        // exp_avg.lerp_(grad, 1 - beta1)
+    vq = vq * b2 + omb2 * gg * gg;
+    const float denom = sqrtf(vq) / bc2_sqrt + eps;
+    pp -= step * (mm / denom);
+}
+__global__ __launch_bounds__(256) void clip_adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                       float* __restrict__ v, long long n4, const float* __restrict__ norm, float clip,
+                                                       float lr, float omb1, float b2, float omb2, float eps, float bc1, float bc2_sqrt, float gscale) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n4) return;
+    const float coef = clip_coef(norm, clip, gscale);
     const float4 gv = reinterpret_cast<const float4*>(g)[i];
     float4 mv = reinterpret_cast<float4*>(m)[i], vv = reinterpret_cast<float4*>(v)[i], pv = reinterpret_cast<float4*>(p)[i];
     const float step = lr / bc1;
-    auto upd = [&](float gg, float& mm, float& vq, float& pp) {
-        gg *= coef;
-        mm = mm + (gg - mm) * omb1;                        // exp_avg.lerp_(grad, 1 - beta1)
-        vq = vq * b2 + omb2 * gg * gg;
-        const float denom = sqrtf(vq) / bc2_sqrt + eps;
-        pp -= step * (mm / denom);
-    };
+    auto upd = [&](float gg, float& mm, float& vq, float& pp) { adam_upd(gg, mm, vq, pp, coef, step, omb1, b2, omb2, eps, bc2_sqrt); };
     upd(gv.x, mv.x, vv.x, pv.x); upd(gv.y, mv.y, vv.y, pv.y); upd(gv.z, mv.z, vv.z, pv.z); upd(gv.w, mv.w, vv.w, pv.w);
     reinterpret_cast<float4*>(m)[i] = mv;
     reinterpret_cast<float4*>(v)[i] = vv;
     reinterpret_cast<float4*>(p)[i] = pv;
+}
+// the same update on the n < 4 elements a buffer's length leaves past its last group of four (ocrl_flat_clip_adam_l2)
+__global__ __launch_bounds__(64) void clip_adam_tail_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                           float* __restrict__ v, int n, const float* __restrict__ norm, float clip, float lr,
+                                                           float omb1, float b2, float omb2, float eps, float bc1, float bc2_sqrt, float gscale) {
+    const int i = threadIdx.x;
+    if (i >= n) return;
+    float mm = m[i], vq = v[i], pp = p[i];
+    adam_upd(g[i], mm, vq, pp, clip_coef(norm, clip, gscale), lr / bc1, omb1, b2, omb2, eps, bc2_sqrt);
+    m[i] = mm; v[i] = vq; p[i] = pp;
 }
 
 int absmax_launch(const float* g, long long n, float* out, float* ws, size_t ws_floats, hipStream_t st) {
@@ -81,5 +98,14 @@ int clip_adam_launch(float* p, const float* g, float* m, float* v, long long n, 
     hipLaunchKernelGGL(clip_adam_kernel, dim3(cdiv(n / 4, 256)), dim3(256), 0, st, p, g, m, v, n / 4, norm, clip, lr,
                        (float)(1.0 - b1), (float)b2, (float)(1.0 - b2), (float)eps, (float)bc1, (float)sqrt(bc2), gscale);
     OCRL_CHECK_LAUNCH("clip_adam");
+    return 0;
+}
+int clip_adam_tail_launch(float* p, const float* g, float* m, float* v, int n, const float* norm, float clip, float lr, double b1, double b2,
+                          double eps, int step, float gscale, hipStream_t st) {
+    OCRL_REQUIRE(n >= 1 && n < 4 && step >= 1, "clip_adam_tail: 1 <= n <= 3 and step >= 1");
+    const double bc1 = 1.0 - pow(b1, step), bc2 = 1.0 - pow(b2, step);
+    hipLaunchKernelGGL(clip_adam_tail_kernel, dim3(1), dim3(64), 0, st, p, g, m, v, n, norm, clip, lr, (float)(1.0 - b1), (float)b2,
+                       (float)(1.0 - b2), (float)eps, (float)bc1, (float)sqrt(bc2), gscale);
+    OCRL_CHECK_LAUNCH("clip_adam_tail");
     return 0;
 }

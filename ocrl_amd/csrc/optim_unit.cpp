@@ -1,0 +1,45 @@
+// C ABI of the stateless optimiser step (include/ocrl_hip.h: ocrl_flat_clip_adam_*): torch.nn.utils.clip_grad_norm_ (L2) followed by
+// torch.optim.Adam on caller-owned flat fp32 buffers, as PPO.train applies them to the policy.  Nothing new is computed here: the norm is
+// IODINE's io_l2norm_launch (iodine.hip: per-block sums of squares, folded in a fixed order) and the update optim.hip's clip_adam kernels.
+#include "../../include/ocrl_hip.h"
+#include "common.h"
+#include "kernels.h"
+#include <cstdio>
+#include <cstdlib>
+
+namespace {
+constexpr size_t WS_FLOATS = 1024;      // io_l2norm's per-block partial sums
+bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+// The decimal a float argument stands for: the shortest one that rounds to it (0.999f -> 0.999, not 0.99900001287).  optim.hip takes
+// 1 - beta and the bias corrections in double from the decimal betas, as torch.optim.Adam does; 1 - 0.999f is 4.7e-5 off 0.001.
+double decimal(float x) {
+    char buf[32];
+    for (int digits = 1; digits <= 9; ++digits) {
+        snprintf(buf, sizeof buf, "%.*g", digits, (double)x);
+        if (strtof(buf, nullptr) == x) return strtod(buf, nullptr);
+    }
+    return (double)x;
+}
+}  // namespace
+
+extern "C" {
+
+size_t ocrl_flat_clip_adam_ws_floats(void) { return WS_FLOATS; }
+
+int ocrl_flat_clip_adam_l2(float* p, const float* g, float* m, float* v, long long n, float max_norm, float lr, float beta1, float beta2, float eps,
+                           int step, float* norm_out, float* ws, size_t ws_floats, void* stream) {
+    OCRL_REQUIRE(p && g && m && v && norm_out && ws, "ocrl_flat_clip_adam_l2: null argument");
+    OCRL_REQUIRE(n >= 1, "ocrl_flat_clip_adam_l2: n >= 1 (got %lld)", n);
+    OCRL_REQUIRE(step >= 1, "ocrl_flat_clip_adam_l2: step counts from 1 (got %d)", step);
+    OCRL_REQUIRE(ws_floats >= WS_FLOATS, "ocrl_flat_clip_adam_l2: workspace too small (%zu < %zu floats)", ws_floats, WS_FLOATS);
+    OCRL_REQUIRE(aligned16(p) && aligned16(g) && aligned16(m) && aligned16(v), "ocrl_flat_clip_adam_l2: p, g, m and v must be 16-byte aligned");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    RC(io_l2norm_launch(g, n, norm_out, ws, ws_floats, st));
+    const double b1 = decimal(beta1), b2 = decimal(beta2), e = decimal(eps);
+    const long long n4 = n & ~3LL;
+    if (n4) RC(clip_adam_launch(p, g, m, v, n4, norm_out, max_norm, lr, b1, b2, e, step, 1.f, st));
+    if (n > n4) RC(clip_adam_tail_launch(p + n4, g + n4, m + n4, v + n4, (int)(n - n4), norm_out, max_norm, lr, b1, b2, e, step, 1.f, st));
+    return 0;
+}
+
+}  // extern "C"

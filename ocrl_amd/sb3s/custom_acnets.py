@@ -224,7 +224,42 @@ else:
             dims, acts, A, params = self._head_args()
             return _AcnetFn.apply(features, dims, acts, A, *params)
 
+        _sample_seed = None                                   # set_sampling(): forward then samples inside the head's launch
+        _sample_rows = 0
+
+        def set_sampling(self, seed):
+            """give the policy a sampling stream: ``forward`` then acts through ``ocrl_acnet_act`` (one launch after the extractor), row
+            r of the n-th call drawing from (seed, rows of the earlier calls + r); ``None`` returns to torch's sampler"""
+            self._sample_seed = None if seed is None else int(seed) & (2 ** 64 - 1)
+            self._sample_rows = 0
+
+        def act(self, features, row_offset=None, uniforms=None, deterministic: bool = False):
+            """(actions int64 [B], values [B], log_prob [B]) of a feature batch in one kernel launch, detached (the rollout's step; the
+            sampling rule is include/ocrl_hip.h's).  Row r draws from (the set_sampling seed, row_offset + r); ``row_offset=None`` takes and
+            advances the policy's own row counter.  ``uniforms`` [B] in [0, 1) replaces the draw."""
+            dims, acts, A, params = self._head_args()
+            x, ps = _bridge.inputs(_WHO, features.detach(), params)
+            B, F = x.shape
+            if uniforms is not None:
+                uniforms = uniforms.to(device=x.device, dtype=torch.float32).reshape(-1).contiguous()
+                if uniforms.numel() != B:
+                    raise ValueError(f"{_WHO}.act: {uniforms.numel()} uniforms for a batch of {B}")
+            elif not deterministic and self._sample_seed is None:
+                raise RuntimeError(f"{_WHO}.act: no sampling stream: call policy.set_sampling(seed) or pass uniforms")
+            if row_offset is None:
+                row_offset = self._sample_rows
+                self._sample_rows += B
+            d, _ = _desc(B, F, A, dims, acts, x.device, keep=False)
+            actions = torch.empty(B, device=x.device, dtype=torch.int64)
+            values, logp = torch.empty(B, device=x.device), torch.empty(B, device=x.device)
+            _bridge.launch(x.device, _lib.lib().ocrl_acnet_act, ctypes.byref(d), _lib.ptr(x), _lib.ptrs(ps), self._sample_seed or 0, int(row_offset),
+                           _lib.ptr(uniforms), int(bool(deterministic)), _lib.ptr(actions), _lib.ptr(values), _lib.ptr(logp), None)
+            return actions, values, logp
+
         def forward(self, obs, deterministic: bool = False):
+            if self._sample_seed is not None:
+                actions, values, logp = self.act(self.extract_features(obs), deterministic=deterministic)
+                return actions, values.unsqueeze(-1), logp
             logits, values = self.logits_values(self.extract_features(obs))
             logp = torch.log_softmax(logits, dim=-1)
             actions = logits.argmax(dim=-1) if deterministic else torch.multinomial(logp.exp(), 1).squeeze(-1)
