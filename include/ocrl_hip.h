@@ -238,6 +238,12 @@ int ocrl_slot_attention_mh_fwd(const float* x, const float* slots0, const float*
                                int H, int I, int heads, float* ws, size_t ws_floats, void* stream);
 int ocrl_slot_attention_mh_bwd(const float* x, const float* dslots, float* dx, float* dslots0, float* const* dw, int B, int N, int K, int D, int H,
                                int I, int heads, float* ws, size_t ws_floats, void* stream);
+/* the form _fwd / _bwd run for these sizes, from the host function their launch path dispatches on (no device needed):
+ * out = {G images per slot-side workgroup, NB row blocks, KB rows per block, dynamic LDS bytes of the forward slot-side kernel, of the
+ * backward one, KS = heads * K soft-max columns of the streaming kernels}.  heads = 1, K <= 8: G = 16 / K while both LDS requests fit
+ * the 163,584 bytes a workgroup may take, else G = 1 (KB = G * K rows fill the 16-row matrix tile); K > 8: G = 1, NB = 2 blocks of
+ * KB = (K + 1) / 2 rows; heads > 1: G = 1, KB = K.  Non-zero, with ocrl_last_error(), for sizes _fwd / _bwd refuse. */
+int ocrl_slot_attention_plan(int K, int D, int H, int heads, int* out6);
 
 /* ---- slot-set pooling head: poolings/common/transformer.py:9-33 (Transformer: Linear -> [CLS; tokens] (+pos) ->
  * nn.TransformerEncoder of post-norm ReLU layers -> CLS row), as built by poolings/transformer/transformer_module.py:27-117 with its

@@ -192,6 +192,7 @@ def lib():
     L.ocrl_slot_attention_mh_ws_floats.restype = c_size_t
     L.ocrl_slot_attention_mh_fwd.argtypes = [p, p, POINTER(p), p, p] + [c_int] * 7 + [p, c_size_t, p]
     L.ocrl_slot_attention_mh_bwd.argtypes = [p, p, p, p, POINTER(p)] + [c_int] * 7 + [p, c_size_t, p]
+    L.ocrl_slot_attention_plan.argtypes = [c_int, c_int, c_int, c_int, POINTER(c_int * 6)]
     L.ocrl_pool_transformer_ws_floats.argtypes = [c_int, c_int, c_int, c_int, c_int, c_int]
     L.ocrl_pool_transformer_ws_floats.restype = c_size_t
     L.ocrl_pool_transformer_fwd.argtypes = [p, POINTER(p), p, p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_ulonglong, p, c_size_t, p]

@@ -416,6 +416,11 @@ struct SlotAttnArgs {
 };
 size_t sa_xchg_floats_host(int K, int D);      // per image; K = num_slots * heads
 size_t sa_parts_floats_host(int B, int K);     // K = num_slots * heads
+// what slot_attn_launch runs for (num_slots, slot size, MLP size, heads): G images per slot-side workgroup, NB row blocks of KB rows, the
+// dynamic LDS bytes of the forward / backward slot-side kernels, KS = heads * num_slots streaming columns.  Needs no device; non-zero
+// (with the error text) for arguments slot_attn_launch refuses.
+struct SaPlan { int G, NB, KB, KS; size_t smem_fwd, smem_bwd; };
+int sa_plan(int K, int D, int H, int NH, SaPlan* plan);
 int slot_attn_launch(const SlotAttnArgs& a, int backward, hipStream_t st);
 
 // generic gather/transposing pack: entry e copies src[rows][cols] to dst + dst_off (transposed if requested)

@@ -41,6 +41,14 @@ size_t ocrl_slot_attention_mh_ws_floats(int B, int N, int K, int D, int H, int I
     return layout(B, K, D, H, I, heads).total + (heads > 1 ? (size_t)B * N * K * heads : 0);
 }
 
+int ocrl_slot_attention_plan(int K, int D, int H, int heads, int* out6) {
+    OCRL_REQUIRE(out6, "ocrl_slot_attention_plan: null argument");
+    SaPlan pl;
+    RC(sa_plan(K, D, H, heads, &pl));
+    out6[0] = pl.G; out6[1] = pl.NB; out6[2] = pl.KB; out6[3] = (int)pl.smem_fwd; out6[4] = (int)pl.smem_bwd; out6[5] = pl.KS;
+    return 0;
+}
+
 int ocrl_slot_attention_fwd(const float* x, const float* slots0, const float* const* w, float* slots, float* attn, int B, int N, int K, int D, int H, int I,
                             float* ws, size_t ws_floats, void* stream) {
     return ocrl_slot_attention_mh_fwd(x, slots0, w, slots, attn, B, N, K, D, H, I, 1, ws, ws_floats, stream);

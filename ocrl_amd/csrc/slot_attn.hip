@@ -1241,6 +1241,33 @@ static size_t sa_bwd_smem(int K, int G, int D, int H, int NH = 1) {
     return (size_t)(KP * D * 2 + KB * D * 2 + KB * 3 * D * 2 + KB * H + NH * KP * SA_C * 5 + 80 + 4 * D + 2 * SA_C) * 4;
 }
 #define SA_LDS_MAX (160 * 1024 - 256)       // dynamic LDS available to a workgroup (the kernels hold 128 bytes of static LDS)
+// The form slot_attn_launch runs for (num_slots K, slot size D, MLP size H, NH heads): the checks of those four arguments and the choice
+// of the images per slot-side workgroup.  slot_attn_launch dispatches on this plan and ocrl_slot_attention_plan (sa_unit.cpp) reports it.
+// Single head, K <= 8: G = 16 / K images per workgroup as long as both directions' LDS requests fit SA_LDS_MAX (OCRL_SA_GROUP=0, read
+// once: one image per workgroup, a development comparison), else one image; K > 8: one image in two row blocks of (K + 1) / 2 rows.
+// Several heads: one image per workgroup, the streaming kernels of KS = NH * K columns.
+int sa_plan(int K, int D, int H, int NH, SaPlan* pl) {
+    OCRL_REQUIRE(K >= 1 && K <= 16, "slot_attn: 1 <= num_slots <= 16 supported (got %d)", K);
+    OCRL_REQUIRE(D > 0 && H > 0 && D % 64 == 0 && H % 64 == 0 && D <= 256 && H <= 256,
+                 "slot_attn: slot/mlp size must be multiples of 64, <= 256 (got %d / %d)", D, H);
+    OCRL_REQUIRE(NH >= 1 && D % NH == 0, "slot_attn: the slot size %d does not divide into %d heads", D, NH);
+    if (NH > 1)
+        OCRL_REQUIRE(K <= 8 && NH * K <= 16 && (D / NH) % 16 == 0,
+                     "slot_attn: with %d heads, heads * num_slots <= 16 and a head width that is a multiple of 16 are supported (num_slots %d, slot size %d)", NH, K, D);
+    int G = 1;
+    if (NH == 1 && K <= 8 && 16 / K > 1) {
+        // images per slot-side workgroup: as many as fill the 16 MFMA rows, unless the group's rows do not fit the LDS (wide slots)
+        static int gmode = -1;
+        if (gmode < 0) { const char* e = getenv("OCRL_SA_GROUP"); gmode = e ? atoi(e) : 1; }      // 0: one image per workgroup (development comparison)
+        const int GM = 16 / K;
+        if (gmode && sa_fwd_smem(K, GM, D, H) <= SA_LDS_MAX && sa_bwd_smem(K, GM, D, H) <= SA_LDS_MAX) G = GM;
+    }
+    pl->G = G; pl->NB = K > 8 ? 2 : 1; pl->KB = K > 8 ? (K + 1) / 2 : G * K; pl->KS = NH * K;
+    pl->smem_fwd = sa_fwd_smem(K, G, D, H, NH); pl->smem_bwd = sa_bwd_smem(K, G, D, H, NH);
+    OCRL_REQUIRE(pl->smem_fwd <= SA_LDS_MAX && pl->smem_bwd <= SA_LDS_MAX, "slot_attn: LDS request %zu / %zu too large (num_slots %d, heads %d, slot size %d, mlp size %d)",
+                 pl->smem_fwd, pl->smem_bwd, K, NH, D, H);
+    return 0;
+}
 size_t sa_xchg_floats_host(int K, int D) {
     const size_t f = sa_xchg_floats(K, D), g = sa_xchg_bwd_floats(K, D);
     return f > g ? f : g;
@@ -1272,10 +1299,10 @@ static int sa_splits(int B, int N, int per_cu) {
 }
 
 template <int K, int G>
-static int sa_launch_kg(const SlotAttnArgs& a, int backward, hipStream_t st) {
+static int sa_launch_kg(const SlotAttnArgs& a, const SaPlan& pl, int backward, hipStream_t st) {
     constexpr int KP = SaBlk<K>::KP;
-    const size_t smem = backward ? sa_bwd_smem(K, G, a.D, a.H) : sa_fwd_smem(K, G, a.D, a.H);
-    OCRL_REQUIRE(smem <= SA_LDS_MAX, "slot_attn: LDS request %zu too large (num_slots %d, slot size %d)", smem, K, a.D);
+    static_assert(SaGeo<K, G>::NB == (K > 8 ? 2 : 1) && SaGeo<K, G>::KB == (K > 8 ? (K + 1) / 2 : G * K), "sa_plan states the kernels' geometry");
+    const size_t smem = backward ? pl.smem_bwd : pl.smem_fwd;
     static_assert((SA_TS / 64) * 16 * SA_TLD >= (SA_TS / 64) * 16 * (SA_C + 1), "streaming workgroup: partial scratch must fit the tile region");
     const SaWts wo = sa_wts_layout(a.C, a.D, a.H);
     const SaSave so = sa_save_layout(a.C, a.D, a.H);
@@ -1366,10 +1393,9 @@ __global__ void sa_attn_heads_sum_kernel(const float* __restrict__ in, float* __
     }
 }
 template <int K>
-static int sa_launch_heads(const SlotAttnArgs& a0, int backward, hipStream_t st) {
-    const int NH = a0.NH, KS = NH * K, KPS = sa_ki(KS);
-    const size_t smem = backward ? sa_bwd_smem(K, 1, a0.D, a0.H, NH) : sa_fwd_smem(K, 1, a0.D, a0.H, NH);
-    OCRL_REQUIRE(smem <= SA_LDS_MAX, "slot_attn: LDS request %zu too large (num_slots %d, heads %d, slot size %d)", smem, K, NH, a0.D);
+static int sa_launch_heads(const SlotAttnArgs& a0, const SaPlan& pl, int backward, hipStream_t st) {
+    const int NH = a0.NH, KS = pl.KS, KPS = sa_ki(KS);
+    const size_t smem = backward ? pl.smem_bwd : pl.smem_fwd;
     OCRL_REQUIRE(!a0.attn || a0.attn_heads, "slot_attn: the per-head attention scratch is missing");
     SlotAttnArgs a = a0;
     if (a.attn) a.attn = a0.attn_heads;          // the streaming kernel writes [B,N,KS]
@@ -1406,39 +1432,33 @@ static int sa_launch_heads(const SlotAttnArgs& a0, int backward, hipStream_t st)
 }
 
 template <int K>
-static int sa_launch_k(const SlotAttnArgs& a, int backward, hipStream_t st) {
+static int sa_launch_k(const SlotAttnArgs& a, const SaPlan& pl, int backward, hipStream_t st) {
     OCRL_REQUIRE(a.xchg && a.parts, "slot_attn: exchange / partial buffers missing");
-    // images per slot-side workgroup: as many as fill the 16 MFMA rows, unless the group's rows do not fit the LDS (wide slots)
     constexpr int GM = K <= 8 ? 16 / K : 1;
-    static int gmode = -1;
-    if (gmode < 0) { const char* e = getenv("OCRL_SA_GROUP"); gmode = e ? atoi(e) : 1; }      // 0: one image per workgroup (development comparison)
-    if (GM > 1 && gmode && sa_fwd_smem(K, GM, a.D, a.H) <= SA_LDS_MAX && sa_bwd_smem(K, GM, a.D, a.H) <= SA_LDS_MAX) return sa_launch_kg<K, GM>(a, backward, st);
-    return sa_launch_kg<K, 1>(a, backward, st);
+    if (GM > 1 && pl.G == GM) return sa_launch_kg<K, GM>(a, pl, backward, st);
+    return sa_launch_kg<K, 1>(a, pl, backward, st);
 }
 
 int slot_attn_launch(const SlotAttnArgs& a, int backward, hipStream_t st) {
     OCRL_REQUIRE(a.C == SA_C, "slot_attn: input width must be %d (got %d)", SA_C, a.C);
-    OCRL_REQUIRE(a.K >= 1 && a.K <= 16, "slot_attn: 1 <= num_slots <= 16 supported (got %d)", a.K);
-    OCRL_REQUIRE(a.D % 64 == 0 && a.H % 64 == 0 && a.D <= 256 && a.H <= 256, "slot_attn: slot/mlp size must be multiples of 64, <= 256");
+    SaPlan pl;
+    RC(sa_plan(a.K, a.D, a.H, a.NH, &pl));
     OCRL_REQUIRE(a.B > 0 && a.N > 0 && a.I >= 1, "slot_attn: empty problem");
     OCRL_REQUIRE((long long)a.N * 16 < (1ll << 31), "slot_attn: N too large for 32-bit row offsets");
     OCRL_REQUIRE(a.x && a.wts && ((uintptr_t)a.x & 15) == 0, "slot_attn: x/wts missing or x not 16-byte aligned");
     if (backward) OCRL_REQUIRE(a.dx && ((uintptr_t)a.dx & 15) == 0 && a.save && a.grows && a.dslots && a.dslots0 && a.g_small, "slot_attn bwd: missing buffers");
     else OCRL_REQUIRE(a.slots0 && a.slots, "slot_attn fwd: missing buffers");
     OCRL_REQUIRE(a.xchg && a.parts && ((uintptr_t)a.xchg & 15) == 0, "slot_attn: exchange / partial buffers missing or xchg not 16-byte aligned");
-    OCRL_REQUIRE(a.NH >= 1 && a.D % a.NH == 0, "slot_attn: the slot size %d does not divide into %d heads", a.D, a.NH);
     if (a.NH > 1) {
-        OCRL_REQUIRE(a.K <= 8 && a.NH * a.K <= 16 && (a.D / a.NH) % 16 == 0,
-                     "slot_attn: with %d heads, heads * num_slots <= 16 and a head width that is a multiple of 16 are supported (num_slots %d, slot size %d)", a.NH, a.K, a.D);
         switch (a.K) {
-#define SA_CASE(k) case k: return sa_launch_heads<k>(a, backward, st);
+#define SA_CASE(k) case k: return sa_launch_heads<k>(a, pl, backward, st);
             SA_CASE(1) SA_CASE(2) SA_CASE(3) SA_CASE(4) SA_CASE(5) SA_CASE(6) SA_CASE(7) SA_CASE(8)
 #undef SA_CASE
         }
         return -1;
     }
     switch (a.K) {
-#define SA_CASE(k) case k: return sa_launch_k<k>(a, backward, st);
+#define SA_CASE(k) case k: return sa_launch_k<k>(a, pl, backward, st);
         SA_CASE(1) SA_CASE(2) SA_CASE(3) SA_CASE(4) SA_CASE(5) SA_CASE(6) SA_CASE(7) SA_CASE(8)
         SA_CASE(9) SA_CASE(10) SA_CASE(11) SA_CASE(12) SA_CASE(13) SA_CASE(14) SA_CASE(15) SA_CASE(16)
 #undef SA_CASE
