@@ -194,6 +194,19 @@ int ocrl_layernorm_fwd(const float* x, const float* gamma, const float* beta, fl
 int ocrl_layernorm_bwd(const float* dy, const float* x, const float* mean, const float* rstd, const float* gamma, float* dx, float* dgb,
                        long long R, int F, float* ws, size_t ws_floats, void* stream);
 
+/* The slot-attention input chain x = W2 relu(W0 LN(e4) + b0) + b2 over R rows of 64 (SlotAttentionModule: layer_norm, mlp), one kernel per
+ * direction.  Forward: mean, rstd [R], h1, x [R,64] are bitwise what ocrl_layernorm_fwd followed by two ocrl_gemm_ex (bias, ReLU) give.
+ * Backward: de4 is bitwise the unfused chain's; dW0, db0, dW2, db2, dgamma, dbeta are written from one partial slab per workgroup, summed
+ * in a fixed order (no atomics).  ws: workgroups * slab floats, both reported by ocrl_sa_input_plan, out = {tile rows, workgroups of the
+ * backward at max_wgs = 0 (one slab each), slab floats}; max_wgs > 0 caps the workgroups of either direction (they walk the tiles with
+ * that stride).  All tensors 16-byte aligned. */
+int ocrl_sa_input_plan(long long R, int out[3]);
+int ocrl_sa_input_fwd(const float* e4, const float* gamma, const float* beta, const float* W0, const float* b0, const float* W2, const float* b2,
+                      float* mean, float* rstd, float* h1, float* x, long long R, int max_wgs, void* stream);
+int ocrl_sa_input_bwd(const float* dx, const float* h1, const float* e4, const float* mean, const float* rstd, const float* gamma, const float* beta,
+                      const float* W0, const float* W2, float* de4, float* dW0, float* db0, float* dW2, float* db2, float* dgamma, float* dbeta,
+                      long long R, int max_wgs, float* ws, size_t ws_floats, void* stream);
+
 /* Causal multi-head self-attention core of MultiHeadAttention.forward (ocrs/common/transformer.py:31-47): q,k,v are the
  * projected [B,T,d] tensors (row stride ld >= d, heads side by side, q unscaled); o = dropout(softmax(mask(q k^T / sqrt(dh)))) v
  * as [B,T,d]; lse [B,h,T] is saved for the backward.  Dropout decisions come from (seed, site) as in ocrl_slate_forward: the

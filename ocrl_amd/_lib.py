@@ -162,6 +162,9 @@ def lib():
     L.ocrl_conv2d_bwd_weight_ex.argtypes = [POINTER(ConvWgradDesc), p, c_size_t, p]
     L.ocrl_layernorm_fwd.argtypes = [p, p, p, p, p, p, c_longlong, c_int, p]
     L.ocrl_layernorm_bwd.argtypes = [p, p, p, p, p, p, p, c_longlong, c_int, p, c_size_t, p]
+    L.ocrl_sa_input_plan.argtypes = [c_longlong, POINTER(c_int * 3)]
+    L.ocrl_sa_input_fwd.argtypes = [p] * 11 + [c_longlong, c_int, p]
+    L.ocrl_sa_input_bwd.argtypes = [p] * 16 + [c_longlong, c_int, p, c_size_t, p]
     L.ocrl_attention_fwd.argtypes = [p, p, p, p, p, c_int, c_int, c_int, c_int, c_int, c_float, c_ulonglong, c_uint, p]
     L.ocrl_attention_bwd.argtypes = [p, p, p, p, p, p, p, p, p, p, c_int, c_int, c_int, c_int, c_int, c_float, c_ulonglong, c_uint, p]
     L.ocrl_obs_u8_to_f32.argtypes = [p, p, c_int, c_int, c_int, c_int, p]

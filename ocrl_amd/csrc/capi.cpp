@@ -301,6 +301,22 @@ int ocrl_layernorm_bwd(const float* dy, const float* x, const float* mean, const
     return layernorm_bwd_launch(dy, x, mean, rstd, g, dx, dgb, R, F, 0, 0, ws, ws_floats, ST(stream));
 }
 
+int ocrl_sa_input_plan(long long R, int out[3]) {
+    if (!out || R <= 0) { ocrl_set_error("ocrl_sa_input_plan: needs R > 0 and an output array"); return 1; }
+    sa_input_plan(R, 0, out);
+    return 0;
+}
+int ocrl_sa_input_fwd(const float* e4, const float* gamma, const float* beta, const float* W0, const float* b0, const float* W2, const float* b2,
+                      float* mean, float* rstd, float* h1, float* x, long long R, int max_wgs, void* stream) {
+    return sa_input_fwd_launch(e4, gamma, beta, W0, b0, W2, b2, mean, rstd, nullptr, h1, x, R, max_wgs, ST(stream));
+}
+int ocrl_sa_input_bwd(const float* dx, const float* h1, const float* e4, const float* mean, const float* rstd, const float* gamma, const float* beta,
+                      const float* W0, const float* W2, float* de4, float* dW0, float* db0, float* dW2, float* db2, float* dgamma, float* dbeta,
+                      long long R, int max_wgs, float* ws, size_t ws_floats, void* stream) {
+    return sa_input_bwd_launch(dx, h1, e4, mean, rstd, gamma, beta, W0, W2, de4, dW0, db0, dW2, db2, dgamma, dbeta, R, max_wgs, ws, ws_floats,
+                               ST(stream));
+}
+
 int ocrl_attention_fwd(const float* q, const float* k, const float* v, float* o, float* lse, int B, int T, int d, int h, int ld, float p,
                        unsigned long long seed, unsigned site, void* stream) {
     AttnArgs a;

@@ -295,6 +295,18 @@ int layernorm_fwd_launch(const float* x, const float* g, const float* b, float* 
 int layernorm_bwd_launch(const float* dy, const float* x, const float* mean, const float* rstd, const float* g, float* dx,
                          float* dgb, long long R, int F, int accumulate_dx, int accumulate_dgb, float* ws, size_t ws_floats, hipStream_t st);
 int colsum_launch(const float* X, long long ld, float* out, long long R, int F, int accumulate, float scale, float* ws, size_t ws_floats, hipStream_t st);
+
+// ------------------------------------------------------------------ sa_input.hip
+// x = W2 relu(W0 LN(e4) + b0) + b2 over [R,64] rows, one kernel per direction (64-row tiles, persistent workgroups, max_wgs 0 = default).
+// Forward: mean, rstd, h1, x bitwise as layernorm_fwd_launch + two lin_fwd give them; ln0 (may be null) receives LN(e4).  Backward: de4
+// bitwise as the unfused chain's; the six parameter gradients are written (not accumulated) from one partial slab per workgroup in ws.
+#define SA_INPUT_SLAB (2 * 4096 + 4 * 64)
+void sa_input_plan(long long R, int max_wgs, int out[3]);        // {tile rows, workgroups of the backward (one slab each), slab floats}
+int sa_input_fwd_launch(const float* e4, const float* gamma, const float* beta, const float* W0, const float* b0, const float* W2, const float* b2,
+                        float* mean, float* rstd, float* ln0, float* h1, float* x, long long R, int max_wgs, hipStream_t st);
+int sa_input_bwd_launch(const float* dx, const float* h1, const float* e4, const float* mean, const float* rstd, const float* gamma, const float* beta,
+                        const float* W0, const float* W2, float* de4, float* dW0, float* db0, float* dW2, float* db2, float* dgamma, float* dbeta,
+                        long long R, int max_wgs, float* ws, size_t ws_floats, hipStream_t st);
 int reduce_partials_launch(const float* part, int n, float* out, float scale, int accumulate, hipStream_t st);
 int mse_launch(const float* obs, const float* recon, float* drecon, float* out, int B, int C, int H, int W, float* ws, size_t ws_floats, hipStream_t st);
 int gumbel_softmax_launch(const float* raw, const float* e1, const float* e2, float* z, int* tokens, long long R, int V, float tau,

@@ -287,6 +287,12 @@ int SlateModel::bind(float* p, float* g, float* m, float* v, void* ws, size_t ws
         }
     }
     {
+        // OCRL_SA_INPUT (default 1): the slot-attention input LayerNorm + MLP as one kernel per direction (csrc/sa_input.hip);
+        //   0 = the unfused chain (LayerNorm, two GEMMs; five launches and their reduction tails backward), 2 = fused forward only
+        const char* e = getenv("OCRL_SA_INPUT");
+        sa_input_ = e ? atoi(e) : 1;
+    }
+    {
         const char* e = getenv("OCRL_XATTN");
         xattn_ = !cfg.use_bcdec && xattn_supported(K, d, NH) && (e ? atoi(e) != 0 : true);
         if (!cfg.use_bcdec && xa_zero_floats_) OCRL_HIP(hipMemset(xa_zero_base_, 0, xa_zero_floats_ * sizeof(float)));      // padding columns of the folded operands
@@ -412,9 +418,17 @@ int SlateModel::fwd_encoder(const StepInputs& in, hipStream_t st, int fork_dvae)
     RC(conv_layer_fwd(e2_, cw_fwd_[2], P("_enc._encoder.2.m.bias"), e3_, B, S, S, 5, 64, 1, nullptr, nullptr, st));
     RC(conv_layer_fwd(e3_, cw_fwd_[3], P("_enc._encoder.3.bias"), e4_, B, S, S, 5, 64, 0, posmap_, nullptr, st));
     if (fork_dvae == 3) RC(fork_here());
-    RC(layernorm_fwd_launch(e4_, P("_slotattn.layer_norm.weight"), P("_slotattn.layer_norm.bias"), ln0_, ln0_mean_, ln0_rstd_, BN, C, st));
-    RC(lin_fwd(ln0_, C, P("_slotattn.mlp.0.weight"), P("_slotattn.mlp.0.bias"), h1_, C, BN, C, C, 1, nullptr, 0, 0.f, 0, st));
-    RC(lin_fwd(h1_, C, P("_slotattn.mlp.2.weight"), P("_slotattn.mlp.2.bias"), x_, C, BN, C, C, 0, nullptr, 0, 0.f, 0, st));
+    if (sa_input_ && C == 64 && !(conv_lowlat_ && frozen_)) {
+        // LayerNorm and both Linear layers in one pass over the rows (csrc/sa_input.hip): e4 is read, h1 and x are written; the fused
+        // backward rebuilds LN(e4) from e4, mean and rstd, so ln0_ is written only for the unfused backward (OCRL_SA_INPUT=2)
+        RC(sa_input_fwd_launch(e4_, P("_slotattn.layer_norm.weight"), P("_slotattn.layer_norm.bias"), P("_slotattn.mlp.0.weight"),
+                               P("_slotattn.mlp.0.bias"), P("_slotattn.mlp.2.weight"), P("_slotattn.mlp.2.bias"), ln0_mean_, ln0_rstd_,
+                               sa_input_ == 2 ? ln0_ : nullptr, h1_, x_, BN, 0, st));
+    } else {
+        RC(layernorm_fwd_launch(e4_, P("_slotattn.layer_norm.weight"), P("_slotattn.layer_norm.bias"), ln0_, ln0_mean_, ln0_rstd_, BN, C, st));
+        RC(lin_fwd(ln0_, C, P("_slotattn.mlp.0.weight"), P("_slotattn.mlp.0.bias"), h1_, C, BN, C, C, 1, nullptr, 0, 0.f, 0, st));
+        RC(lin_fwd(h1_, C, P("_slotattn.mlp.2.weight"), P("_slotattn.mlp.2.bias"), x_, C, BN, C, C, 0, nullptr, 0, 0.f, 0, st));
+    }
     if (fork_dvae == 1) RC(fork_here());
     a.phase = 2;
     RC(slot_attn_launch(a, 0, st));
@@ -948,6 +962,7 @@ int SlateModel::bwd_encoder(hipStream_t st, bool fork_dvae) {
     const bool side_w = side_ && overlap_mode_ >= 3 && !cfg.use_bcdec && !fork_dvae;
     hipStream_t sw = side_w ? side_ : st;
     if (side_w) { RC(fork_side(st)); std::swap(scratch_, scratch2_); }
+    const bool sa_in_bwd = sa_input_ == 1 && C == 64;          // the input LayerNorm + MLP backward as one kernel on the main stream
     auto sa_weight_grads = [&]() -> int {
     // weight gradients: contract the emitted gradient rows with the saved activations over (image, iteration, slot)
     RC(lin_bwd_w(sa_grows_ + go.out, go.ld, sa_save_ + so.hid, so.ld, G(sa + "mlp.2.weight"), G(sa + "mlp.2.bias"), R, D, H, 1.f, sw));
@@ -966,7 +981,7 @@ int SlateModel::bwd_encoder(hipStream_t st, bool fork_dvae) {
     RC(slot_init_bwd_launch(gslots0_, P("_slotattn.slot_log_sigma"), last_.noise_slots, G("_slotattn.slot_mu"), G("_slotattn.slot_log_sigma"),
                             B * K, D, last_.seed, sw));
     // ---- input MLP: x = W2 relu(W0 LN(e4) + b0) + b2 ; gA = dx
-    RC(lin_bwd_w(gA_, C, h1_, C, G("_slotattn.mlp.2.weight"), G("_slotattn.mlp.2.bias"), BN, C, C, 1.f, sw));
+    if (!sa_in_bwd) RC(lin_bwd_w(gA_, C, h1_, C, G("_slotattn.mlp.2.weight"), G("_slotattn.mlp.2.bias"), BN, C, C, 1.f, sw));
     // the first convolution's weight gradient is a product with im2col(obs): the patch matrix only needs the observation
     if (side_w) RC(im2col5_launch(obs8_, col0_, BN, S, S, cfg.obs_channels, (25 * cfg.obs_channels + 3) & ~3, sw));
     return 0;
@@ -976,13 +991,23 @@ int SlateModel::bwd_encoder(hipStream_t st, bool fork_dvae) {
         if (side_w) std::swap(scratch_, scratch2_);
         RC(rc);
     }
-    RC(lin_bwd_x(gA_, C, P("_slotattn.mlp.2.weight"), gB_, C, BN, C, C, h1_, C, nullptr, 0, st));              // gB = d h1 (pre-relu)
-    RC(lin_bwd_w(gB_, C, ln0_, C, G("_slotattn.mlp.0.weight"), G("_slotattn.mlp.0.bias"), BN, C, C, 1.f, st));
-    // d ln0 goes to gC_ when the side stream may still be reading gA_ (= dx) for the second layer's weight gradient
-    float* gL = side_w ? gC_ : gA_;
-    RC(lin_bwd_x(gB_, C, P("_slotattn.mlp.0.weight"), gL, C, BN, C, C, nullptr, 0, nullptr, 0, st));            // gL = d ln0
-    RC(layernorm_bwd_launch(gL, e4_, ln0_mean_, ln0_rstd_, P("_slotattn.layer_norm.weight"), gB_, G("_slotattn.layer_norm.weight"), BN, C, 0, 0,
-                            scratch_, scratch_floats_, st));                                                      // gB = d e4
+    if (sa_in_bwd) {
+        // reads dx (gA_), h1, e4; writes d e4 (gB_) and the six parameter gradients from one partial slab per workgroup (csrc/sa_input.hip)
+        const size_t slabs = scratch_floats_ / SA_INPUT_SLAB;
+        OCRL_REQUIRE(slabs >= 1, "bwd_encoder: scratch too small for the input-chain slabs");
+        RC(sa_input_bwd_launch(gA_, h1_, e4_, ln0_mean_, ln0_rstd_, P("_slotattn.layer_norm.weight"), P("_slotattn.layer_norm.bias"),
+                               P("_slotattn.mlp.0.weight"), P("_slotattn.mlp.2.weight"), gB_, G("_slotattn.mlp.0.weight"), G("_slotattn.mlp.0.bias"),
+                               G("_slotattn.mlp.2.weight"), G("_slotattn.mlp.2.bias"), G("_slotattn.layer_norm.weight"), G("_slotattn.layer_norm.bias"),
+                               BN, slabs < 512 ? (int)slabs : 0, scratch_, scratch_floats_, st));
+    } else {
+        RC(lin_bwd_x(gA_, C, P("_slotattn.mlp.2.weight"), gB_, C, BN, C, C, h1_, C, nullptr, 0, st));              // gB = d h1 (pre-relu)
+        RC(lin_bwd_w(gB_, C, ln0_, C, G("_slotattn.mlp.0.weight"), G("_slotattn.mlp.0.bias"), BN, C, C, 1.f, st));
+        // d ln0 goes to gC_ when the side stream may still be reading gA_ (= dx) for the second layer's weight gradient
+        float* gL = side_w ? gC_ : gA_;
+        RC(lin_bwd_x(gB_, C, P("_slotattn.mlp.0.weight"), gL, C, BN, C, C, nullptr, 0, nullptr, 0, st));            // gL = d ln0
+        RC(layernorm_bwd_launch(gL, e4_, ln0_mean_, ln0_rstd_, P("_slotattn.layer_norm.weight"), gB_, G("_slotattn.layer_norm.weight"), BN, C, 0, 0,
+                                scratch_, scratch_floats_, st));                                                      // gB = d e4
+    }
     // ---- positional embedding (added to every image): d map = sum over images
     RC(colsum_launch(gB_, (long long)N * C, gmap_, B, N * C, 0, 1.f, scratch_, scratch_floats_, st));
     RC(lin_bwd_w(gmap_, C, gridT_, 4, G("_enc_pos.channels_map.weight"), G("_enc_pos.channels_map.bias"), N, C, 4, 1.f, st));

@@ -129,6 +129,7 @@ private:
         float *ln3, *ln3_mean, *ln3_rstd, *f1, *x3;
         float *xaAb, *xaAbT, *xaVo, *xaVoT;       // folded cross-attention operands per image (xattn.hip): [B,NC,d], [B,d,NC], [B,NC,d], [B,d,NC]
     };
+    int sa_input_ = 1;                    // OCRL_SA_INPUT (default 1): 1 fused input LayerNorm + MLP both ways, 2 forward only, 0 the unfused chain
     bool xattn_ = false;                  // OCRL_XATTN (default 1): cross attention in its folded form (one launch per block and direction)
     float *xa_dAb_ = nullptr, *xa_dVo_ = nullptr, *xa_pq_ = nullptr, *xa_po_ = nullptr;
     size_t xa_zero_floats_ = 0;           // the per-block operand buffers form one contiguous region that bind() zeroes (padding columns)
