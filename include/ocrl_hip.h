@@ -497,6 +497,64 @@ int ocrl_acnet_act_uniforms(unsigned long long seed, unsigned long long row_offs
 int ocrl_gae(const float* rewards, const float* values, const float* episode_starts, const float* last_values, const float* dones,
              float* advantages, float* returns, int T, int E, float gamma, float gae_lambda, void* stream);
 
+/* ---- sprite environments: the Target task (envs/synthetic_envs/base.py:81-151, 291-360 and target.py:16-57, restated) as a vectorised
+ *      environment whose state, transition, reward, auto-reset and frames stay on the device.  Stateless: the caller owns `state`
+ *      (ocrl_sprite_env_state_floats floats, 256-byte aligned, zero before the first reset) and every output; everything is enqueued on
+ *      `stream` with no host synchronisation, no atomics and no unbounded loop; reset and step run one thread per environment.
+ * desc: E environments, H x H frames (H a multiple of 4 in [8, 512]); num_objects_range [lo, hi], 1 <= lo <= hi <= 15 (easy mode: within
+ *   [2, 4]; normal mode: [4, 4], the modes' boxes); colour ids 0..6 = blue, green, yellow, red, cyan, pink, brown; shape ids 0..3 = square,
+ *   triangle, star_4, circle (the other names of the reference's list are not drawn and are rejected); scales in (0, 1).  Anything else
+ *   is rejected: state_floats == 0, the other entry points return non-zero, with a message.
+ * state: rows [E, hi + 1, 5] fp32 = (colour id, shape id, scale, x, y): objects 0..n-1, the agent in row n, zero rows after it; then,
+ *   at the next multiple of 64 floats, 8 int32 words per environment: n, target index, step_count, episode index, episode length, 0, and
+ *   the episode's return so far as one double.
+ * The draws.  u(seed, e, k, j) = the top 24 bits of the library's counter RNG at site 500 and counter (e << 44) | ((k mod 2^24) << 20) | j:
+ *   draw j of episode k of environment e is a function of (seed, e, k, j) alone, whatever E is and whenever the episode began.  An integer
+ *   in [0, m) is (bits24 * m) >> 24; a position in [a, b] is a + (b - a) * (bits24 / 2^24), each operation rounded to fp32 (no FMA).
+ *   An episode draws, with j counting up from 0: n in [lo, hi]; the target index in [0, n); for every other object in index order its
+ *   (colour, shape, scale) as indices into the desc's lists, redrawn while the triple equals the target's (after 64 tries the last one
+ *   stands); then positions for i = 0..n-1, x then y: uniform in [lo_i + r + dist_wall, hi_i - r - dist_wall] of the object's box (easy
+ *   mode: [lo_i, hi_i]; an interval with lo_i == hi_i yields lo_i without a draw), r = scale / 2, rejected while the centre is closer than
+ *   a threshold to an object placed before it (r + r_j + dist_objs) or to the agent (r + r_agent + dist_agent), 0.15 for both with
+ *   `occlusion`.  An object takes at most 256 candidates; then the whole placement starts over on the draws that follow, at most 8
+ *   times, and on the last attempt the 256th candidate stands.  The agent starts at agent_x, agent_y (hard mode) or (0.5, 0.5).
+ * _reset: every environment, or those with mask[e] != 0.  episode >= 0 starts that episode index, -1 the one after the state's own.
+ * _step: actions int64 [E]: 0 y += step_size, 1 x -= step_size, 2 y -= step_size, 3 x += step_size, anything else no move; x, y clipped
+ *   to [r_agent, 1 - r_agent]; step_count + 1 >= max_steps ends the episode; rew_type 2 (dense) pays +-0.01 by whether the distance to the
+ *   target shrank; the first object in index order whose centre is closer than agent_scale ends it: reward 1 and success for the target,
+ *   else 0.1 under rew_type 1 (normal) and 0 otherwise.  rewards fp32, dones and success bytes, ep_return (double; the rewards summed in
+ *   double in step order) and ep_length of the episode that ended with this step (0 elsewhere), all [E].  A finished environment starts
+ *   its next episode in the same launch.
+ * _render: rows [E, R, 5] of any origin, R <= 16, painted in row order (a later row overwrites; colour -1, an unknown id or scale <= 0:
+ *   not drawn) on black with the shape predicates of the pre-training scenes, pixel centre (i + 0.5) / H, the row index growing with y.
+ *   mode 0: uint8 [E, 3, H, W]; 1: [E, H, W, 3]; 2: masks [E, R + 1, H, W, 1] of 0 / 1: each row alone and unoccluded, the background
+ *   (no row covers the pixel) last.
+ * _uniforms: out [n_envs, n] = bits24 / 2^24 of draws first .. first + n - 1 of episode `episode` of environments env0 .. */
+#define OCRL_SPRITE_MAX_OBJECTS 15
+typedef struct {
+    int E, H;
+    int lo, hi;
+    int mode;                                   /* 0 easy, 1 normal, 2 hard */
+    int rew_type;                               /* 0 sparse, 1 normal, 2 dense */
+    int occlusion, max_steps;
+    int n_colors, n_shapes, n_scales;
+    int colors[8], shapes[8];
+    float scales[8];
+    int target_color, target_shape;
+    float target_scale;
+    int agent_color, agent_shape;
+    float agent_scale, agent_x, agent_y;
+    float step_size, dist_agent, dist_objs, dist_wall;
+} ocrl_sprite_env_desc;
+size_t ocrl_sprite_env_desc_size(void);
+size_t ocrl_sprite_env_state_floats(const ocrl_sprite_env_desc* d);
+int ocrl_sprite_env_reset(const ocrl_sprite_env_desc* d, float* state, unsigned long long seed, const unsigned char* mask /* [E] or NULL */,
+                          long long episode, void* stream);
+int ocrl_sprite_env_step(const ocrl_sprite_env_desc* d, float* state, unsigned long long seed, const long long* actions, float* rewards,
+                         unsigned char* dones, unsigned char* success, double* ep_return, int* ep_length, void* stream);
+int ocrl_sprite_render(const float* rows, int E, int R, int H, int mode, unsigned char* out, void* stream);
+int ocrl_sprite_env_uniforms(unsigned long long seed, long long env0, int n_envs, long long episode, int first, int n, float* out, void* stream);
+
 /* ---- L2 gradient clip + Adam on caller-owned flat fp32 buffers p, g, m, v [n] (16-byte aligned), as PPO.train applies
  *      torch.nn.utils.clip_grad_norm_ and torch.optim.Adam to the policy.  Stateless, no host synchronisation, no atomics:
  *      norm = ||g||_2 over the whole buffer (per-block sums of squares folded in a fixed order; written to norm_out, 1 device float),

@@ -55,6 +55,14 @@ class AcnetDesc(ctypes.Structure):
     _fields_ = [("B", c_int), ("F", c_int), ("A", c_int), ("n", c_int * 3), ("dims", (c_int * 8) * 3), ("acts", (c_int * 8) * 3)]
 
 
+class SpriteEnvDesc(ctypes.Structure):
+    """mirror of ocrl_sprite_env_desc (include/ocrl_hip.h); ocrl_amd.envs fills it from an env config"""
+    _fields_ = [(n, c_int) for n in ("E", "H", "lo", "hi", "mode", "rew_type", "occlusion", "max_steps", "n_colors", "n_shapes", "n_scales")] + \
+               [("colors", c_int * 8), ("shapes", c_int * 8), ("scales", c_float * 8), ("target_color", c_int), ("target_shape", c_int),
+                ("target_scale", c_float), ("agent_color", c_int), ("agent_shape", c_int)] + \
+               [(n, c_float) for n in ("agent_scale", "agent_x", "agent_y", "step_size", "dist_agent", "dist_objs", "dist_wall")]
+
+
 def acnet_desc(B, F, A, dims, acts):
     """AcnetDesc of three trunks: dims / acts = (shared, policy, value) sequences of widths / activation codes (0 none, 1 relu, 2 tanh)"""
     d = AcnetDesc(B=B, F=F, A=A)
@@ -250,6 +258,16 @@ def lib():
     L.ocrl_flat_clip_adam_ws_floats.restype = c_size_t
     L.ocrl_flat_clip_adam_l2.argtypes = [p, p, p, p, c_longlong, c_float, c_float, c_float, c_float, c_float, c_int, p, p, c_size_t, p]
     L.ocrl_gae.argtypes = [p, p, p, p, p, p, p, c_int, c_int, c_float, c_float, p]
+    L.ocrl_sprite_env_desc_size.restype = c_size_t
+    if L.ocrl_sprite_env_desc_size() != ctypes.sizeof(SpriteEnvDesc):
+        raise RuntimeError(f"libocrl_hip.so: ocrl_sprite_env_desc is {L.ocrl_sprite_env_desc_size()} bytes, this binding's SpriteEnvDesc "
+                           f"{ctypes.sizeof(SpriteEnvDesc)}")
+    L.ocrl_sprite_env_state_floats.argtypes = [POINTER(SpriteEnvDesc)]
+    L.ocrl_sprite_env_state_floats.restype = c_size_t
+    L.ocrl_sprite_env_reset.argtypes = [POINTER(SpriteEnvDesc), p, c_ulonglong, p, c_longlong, p]
+    L.ocrl_sprite_env_step.argtypes = [POINTER(SpriteEnvDesc), p, c_ulonglong, p, p, p, p, p, p, p]
+    L.ocrl_sprite_render.argtypes = [p, c_int, c_int, c_int, c_int, p, p]
+    L.ocrl_sprite_env_uniforms.argtypes = [c_ulonglong, c_longlong, c_int, c_longlong, c_int, c_int, p, p]
     L.ocrl_comm_unique_id.argtypes = [p, c_size_t]
     L.ocrl_comm_init.argtypes = [POINTER(p), c_int, c_int, p]
     L.ocrl_comm_allreduce.argtypes = [p, p, c_longlong, p]

@@ -1,0 +1,295 @@
+// The Target sprite task (envs/synthetic_envs/{base,target}.py restated) as a vectorised environment: state, transition, reward, auto-reset
+// and rendering on the device.  reset / step: one thread per environment (an episode's draws are a serial rejection chain).  render: the
+// only part with bytes to move; a workgroup takes a row band of one environment, keeps the sprite table in LDS and writes 4 pixels of a
+// channel plane per 32-bit store.  No atomics; every loop is bounded.  Compiled with -ffp-contract=off: each position is the written
+// sequence of fp32 roundings, so a numpy fp32 restatement (tests/sprite_env_ref.py) follows it bit for bit.
+#include "sprite_env.h"
+
+#pragma clang fp contract(off)
+
+namespace {
+
+// ---------------------------------------------------------------------------------------------------------------- the draws
+// 24 random bits of draw j of episode k of environment e: counter (e << 44) | ((k mod 2^24) << 20) | j of the site's stream
+__host__ __device__ inline uint32_t env_bits24(unsigned long long seed, uint32_t e, uint32_t k, uint32_t j) {
+    const uint64_t c = ((uint64_t)e << 44) | ((uint64_t)(k & 0xFFFFFFu) << 20) | (uint64_t)j;
+    return rng_bits1_keyed(rng_key(seed, SITE_SPRITE_ENV, (uint32_t)(c >> 32)), (uint32_t)c) >> 8;
+}
+
+struct Stream {
+    unsigned long long seed;
+    uint32_t e, k, j;
+    __device__ uint32_t bits() { return env_bits24(seed, e, k, j++); }
+    __device__ int below(int m) { return (int)((bits() * (uint32_t)m) >> 24); }            // uniform in [0, m), m <= 256
+    __device__ float u01() { return (float)bits() * (1.f / 16777216.f); }                  // k / 2^24 in [0, 1)
+};
+
+// [x_min, x_max, y_min, y_max] of object i (base.py:158-219)
+__device__ inline void obj_box(int mode, int n, int i, float* b) {
+    if (mode == 2) { b[0] = 0.f; b[1] = 1.f; b[2] = 0.f; b[3] = 1.f; return; }
+    const bool left = i < 2, low = i == 1 || i == 2;
+    if (mode == 1) {
+        b[0] = left ? 0.f : 0.5f; b[1] = left ? 0.5f : 1.f;
+        b[2] = low ? 0.f : 0.5f;  b[3] = low ? 0.5f : 1.f;
+        return;
+    }
+    if (n == 4) {
+        b[0] = left ? 0.2f : 0.7f; b[1] = left ? 0.3f : 0.8f;
+        b[2] = low ? 0.2f : 0.7f;  b[3] = low ? 0.3f : 0.8f;
+    } else {
+        b[0] = left ? 0.15f : 0.65f; b[1] = left ? 0.35f : 0.85f;
+        b[2] = low ? 0.15f : 0.65f;  b[3] = low ? 0.35f : 0.85f;
+    }
+}
+
+__device__ inline float draw_pos(Stream& s, int mode, float lo, float hi, float r, float wall) {
+    if (lo == hi) return lo;                                   // a degenerate interval takes no draw
+    float a = lo, b = hi;
+    if (mode != 0) { a = (lo + r) + wall; b = (hi - r) - wall; }
+    const float w = b - a;
+    const float p = w * s.u01();
+    return a + p;
+}
+
+__device__ inline float dist2d(float ax, float ay, float bx, float by) {
+    const float dx = ax - bx, dy = ay - by;
+    const float xx = dx * dx, yy = dy * dy;
+    return sqrtf(xx + yy);
+}
+
+// a new episode of environment e into its rows (R x 5) and aux words
+__device__ void new_episode(const ocrl_sprite_env_desc& d, float* __restrict__ q, int* __restrict__ aux, unsigned long long seed, uint32_t e, uint32_t k) {
+    const int R = d.hi + 1;
+    Stream s{seed, e, k, 0u};
+    const int n = d.lo + s.below(d.hi - d.lo + 1);
+    const int target = s.below(n);
+    float col[SPRITE_MAX_ROWS], shp[SPRITE_MAX_ROWS], scl[SPRITE_MAX_ROWS], px[SPRITE_MAX_ROWS], py[SPRITE_MAX_ROWS];
+    for (int i = 0; i < n; ++i) {
+        int c = d.target_color, h = d.target_shape;
+        float z = d.target_scale;
+        if (i != target) {
+            for (int t = 0; t < SPRITE_TRIPLE_TRIES; ++t) {
+                c = d.colors[s.below(d.n_colors)];
+                h = d.shapes[s.below(d.n_shapes)];
+                z = d.scales[s.below(d.n_scales)];
+                if (!(c == d.target_color && h == d.target_shape && z == d.target_scale)) break;
+            }
+        }
+        col[i] = (float)c; shp[i] = (float)h; scl[i] = z; px[i] = 0.f; py[i] = 0.f;
+    }
+    const float ax = d.mode == 2 ? d.agent_x : 0.5f, ay = d.mode == 2 ? d.agent_y : 0.5f;
+    const float ra = d.agent_scale * 0.5f;
+    for (int attempt = 0; attempt <= SPRITE_RESTARTS; ++attempt) {
+        bool dead = false;
+        for (int i = 0; i < n && !dead; ++i) {
+            float b[4];
+            obj_box(d.mode, n, i, b);
+            const float r = scl[i] * 0.5f;
+            bool ok = false;
+            float x = 0.f, y = 0.f;
+            for (int c = 0; c < SPRITE_CANDIDATES && !ok; ++c) {
+                x = draw_pos(s, d.mode, b[0], b[1], r, d.dist_wall);
+                y = draw_pos(s, d.mode, b[2], b[3], r, d.dist_wall);
+                ok = true;
+                for (int j = 0; j < i; ++j) {
+                    const float thr = d.occlusion ? 0.15f : (r + scl[j] * 0.5f) + d.dist_objs;
+                    if (dist2d(px[j], py[j], x, y) < thr) ok = false;
+                }
+                const float thr = d.occlusion ? 0.15f : (r + ra) + d.dist_agent;
+                if (dist2d(ax, ay, x, y) < thr) ok = false;
+            }
+            px[i] = x; py[i] = y;
+            if (!ok && attempt < SPRITE_RESTARTS) dead = true;  // restart the whole placement on fresh draws; on the last attempt the candidate stands
+        }
+        if (!dead) break;
+    }
+    for (int i = 0; i < R; ++i) {
+        float v[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
+        if (i < n) { v[0] = col[i]; v[1] = shp[i]; v[2] = scl[i]; v[3] = px[i]; v[4] = py[i]; }
+        else if (i == n) { v[0] = (float)d.agent_color; v[1] = (float)d.agent_shape; v[2] = d.agent_scale; v[3] = ax; v[4] = ay; }
+        for (int c = 0; c < 5; ++c) q[i * 5 + c] = v[c];
+    }
+    aux[0] = n; aux[1] = target; aux[2] = 0; aux[3] = (int)k; aux[4] = 0; aux[5] = 0;
+    *reinterpret_cast<double*>(aux + 6) = 0.0;
+}
+
+__global__ __launch_bounds__(64) void sprite_env_reset_kernel(ocrl_sprite_env_desc d, float* __restrict__ rows, int* __restrict__ aux, unsigned long long seed,
+                                                              const unsigned char* __restrict__ mask, long long episode) {
+    const int e = blockIdx.x * 64 + threadIdx.x;
+    if (e >= d.E) return;
+    if (mask && !mask[e]) return;
+    int* a = aux + (size_t)e * SPRITE_AUX;
+    const uint32_t k = episode >= 0 ? (uint32_t)episode : (uint32_t)a[3] + 1u;
+    new_episode(d, rows + (size_t)e * (d.hi + 1) * 5, a, seed, (uint32_t)e, k);
+}
+
+__global__ __launch_bounds__(64) void sprite_env_step_kernel(ocrl_sprite_env_desc d, float* __restrict__ rows, int* __restrict__ aux, unsigned long long seed,
+                                                             const long long* __restrict__ actions, SpriteStepOut o) {
+    const int e = blockIdx.x * 64 + threadIdx.x;
+    if (e >= d.E) return;
+    const int R = d.hi + 1;
+    float* q = rows + (size_t)e * R * 5;
+    int* a = aux + (size_t)e * SPRITE_AUX;
+    int n = a[0], target = a[1];
+    n = n < 1 ? 1 : (n > d.hi ? d.hi : n);                                   // a hand-set state cannot index outside the rows
+    target = target < 0 ? 0 : (target >= n ? n - 1 : target);
+    float x = q[n * 5 + 3], y = q[n * 5 + 4];
+    const float tx = q[target * 5 + 3], ty = q[target * 5 + 4];
+    const float before = dist2d(tx, ty, x, y);
+    const long long act = actions[e];
+    if (act == 0) y = y + d.step_size;
+    else if (act == 1) x = x - d.step_size;
+    else if (act == 2) y = y - d.step_size;
+    else if (act == 3) x = x + d.step_size;                                  // anything else leaves the agent where it is
+    const float ra = d.agent_scale * 0.5f, top = 1.0f - ra;
+    x = fminf(fmaxf(x, ra), top);
+    y = fminf(fmaxf(y, ra), top);
+    q[n * 5 + 3] = x; q[n * 5 + 4] = y;
+    const int steps = a[2] + 1;
+    bool done = steps >= d.max_steps, success = false;
+    float reward = 0.f;
+    if (d.rew_type == 2) reward = dist2d(tx, ty, x, y) < before ? 0.01f : -0.01f;
+    for (int i = 0; i < n; ++i) {
+        if (dist2d(q[i * 5 + 3], q[i * 5 + 4], x, y) < d.agent_scale) {
+            if (i == target) { reward = 1.0f; success = true; }
+            else reward = d.rew_type == 1 ? 0.1f : 0.f;
+            done = true;
+            break;
+        }
+    }
+    double* ret = reinterpret_cast<double*>(a + 6);
+    const double total = *ret + (double)reward;
+    const int len = a[4] + 1;
+    o.rewards[e] = reward;
+    o.dones[e] = done ? 1 : 0;
+    o.success[e] = success ? 1 : 0;
+    o.ep_return[e] = done ? total : 0.0;
+    o.ep_length[e] = done ? len : 0;
+    if (done) new_episode(d, q, a, seed, (uint32_t)e, (uint32_t)a[3] + 1u);
+    else { a[2] = steps; a[4] = len; *ret = total; }
+}
+
+__global__ __launch_bounds__(256) void sprite_env_uniforms_kernel(unsigned long long seed, long long env0, int n_envs, long long episode, int first, int n,
+                                                                  float* __restrict__ out) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long long)n_envs * n) return;
+    const uint32_t e = (uint32_t)(env0 + i / n), j = (uint32_t)(first + i % n);
+    out[i] = (float)env_bits24(seed, e, (uint32_t)episode, j) * (1.f / 16777216.f);
+}
+
+// ---------------------------------------------------------------------------------------------------------------- the renderer
+// the predicates of ocrl_amd/utils/data.py:_mask in fp32; (dx, dy) = pixel centre - sprite centre, r = scale / 2
+__device__ inline bool sprite_covers(int shape, float dx, float dy, float r) {
+    const float ax = fabsf(dx), ay = fabsf(dy);
+    if (shape == 0) return ax <= r && ay <= r;
+    if (shape == 1) {
+        const float t = (dy + r) / (2.f * r);
+        return t >= 0.f && t <= 1.f && ax <= r * t;
+    }
+    if (shape == 2) return sqrtf(ax) + sqrtf(ay) <= sqrtf(r) * 1.25f;
+    const float xx = dx * dx, yy = dy * dy;
+    return xx + yy <= r * r;
+}
+
+__constant__ uint32_t SPRITE_RGB[7] = {0xFF0000u, 0x00FF00u, 0x00FFFFu, 0x0000FFu, 0xFFFF00u, 0xCBC0FFu, 0x2A2AA5u};       // byte 0 = red
+
+// mode 0: [E, 3, H, W]; 1: [E, H, W, 3]; 2: masks [E, R + 1, H, W, 1] (row j alone and unoccluded; the background last)
+__global__ __launch_bounds__(256) void sprite_render_kernel(const float* __restrict__ rows, int R, int H, int band_rows, int bands, int mode,
+                                                            unsigned char* __restrict__ out) {
+    __shared__ float s_cx[SPRITE_MAX_ROWS], s_cy[SPRITE_MAX_ROWS], s_r[SPRITE_MAX_ROWS];
+    __shared__ int s_shape[SPRITE_MAX_ROWS];                                 // -1: not drawn
+    __shared__ uint32_t s_rgb[SPRITE_MAX_ROWS];
+    const int e = blockIdx.x / bands, band = blockIdx.x % bands;
+    if (threadIdx.x < SPRITE_MAX_ROWS) {
+        const int j = threadIdx.x;
+        int shape = -1;
+        uint32_t rgb = 0;
+        float cx = 0.f, cy = 0.f, r = 0.f;
+        if (j < R) {
+            const float* q = rows + ((size_t)e * R + j) * 5;
+            const float c = q[0], h = q[1], z = q[2];
+            if (c >= 0.f && c < 7.f && h >= 0.f && h < 4.f && z > 0.f) {     // colour -1, an unknown id or an empty row: not drawn
+                shape = (int)h; rgb = SPRITE_RGB[(int)c]; r = z * 0.5f; cx = q[3]; cy = q[4];
+            }
+        }
+        s_shape[j] = shape; s_rgb[j] = rgb; s_cx[j] = cx; s_cy[j] = cy; s_r[j] = r;
+    }
+    __syncthreads();
+    const int W = H, W4 = W / 4;
+    const int y0 = band * band_rows, y1 = y0 + band_rows < H ? y0 + band_rows : H;
+    const int groups = (y1 - y0) * W4;
+    const float fH = (float)H;
+    for (int g = threadIdx.x; g < groups; g += 256) {
+        const int y = y0 + g / W4, x4 = (g % W4) * 4;
+        const float py = ((float)y + 0.5f) / fH;
+        if (mode == 2) {
+            uint32_t any = 0;
+            for (int j = 0; j < R; ++j) {
+                uint32_t m = 0;
+                if (s_shape[j] >= 0) {
+                    const float dy = py - s_cy[j];
+#pragma unroll
+                    for (int p = 0; p < 4; ++p) {
+                        const float dx = ((float)(x4 + p) + 0.5f) / fH - s_cx[j];
+                        if (sprite_covers(s_shape[j], dx, dy, s_r[j])) m |= 1u << (8 * p);
+                    }
+                }
+                any |= m;
+                *reinterpret_cast<uint32_t*>(out + (((size_t)e * (R + 1) + j) * H + y) * W + x4) = m;
+            }
+            *reinterpret_cast<uint32_t*>(out + (((size_t)e * (R + 1) + R) * H + y) * W + x4) = any ^ 0x01010101u;
+            continue;
+        }
+        uint32_t px[4] = {0u, 0u, 0u, 0u};
+        for (int j = 0; j < R; ++j) {                                        // painter's order: a later row overwrites
+            if (s_shape[j] < 0) continue;
+            const float dy = py - s_cy[j];
+#pragma unroll
+            for (int p = 0; p < 4; ++p) {
+                const float dx = ((float)(x4 + p) + 0.5f) / fH - s_cx[j];
+                if (sprite_covers(s_shape[j], dx, dy, s_r[j])) px[p] = s_rgb[j];
+            }
+        }
+        if (mode == 0) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const uint32_t w = ((px[0] >> (8 * c)) & 0xFFu) | (((px[1] >> (8 * c)) & 0xFFu) << 8) | (((px[2] >> (8 * c)) & 0xFFu) << 16) |
+                                   (((px[3] >> (8 * c)) & 0xFFu) << 24);
+                *reinterpret_cast<uint32_t*>(out + (((size_t)e * 3 + c) * H + y) * W + x4) = w;
+            }
+        } else {                                                             // 12 bytes r g b r g b ... as three words
+            uint32_t* dst = reinterpret_cast<uint32_t*>(out + (((size_t)e * H + y) * W + x4) * 3);
+            dst[0] = (px[0] & 0xFFFFFFu) | ((px[1] & 0xFFu) << 24);
+            dst[1] = ((px[1] >> 8) & 0xFFFFu) | ((px[2] & 0xFFFFu) << 16);
+            dst[2] = ((px[2] >> 16) & 0xFFu) | ((px[3] & 0xFFFFFFu) << 8);
+        }
+    }
+}
+
+}  // namespace
+
+int sprite_env_reset_launch(const ocrl_sprite_env_desc& d, float* rows, int* aux, unsigned long long seed, const unsigned char* mask, long long episode,
+                            hipStream_t st) {
+    hipLaunchKernelGGL(sprite_env_reset_kernel, dim3(cdiv(d.E, 64)), dim3(64), 0, st, d, rows, aux, seed, mask, episode);
+    OCRL_CHECK_LAUNCH("sprite_env_reset");
+    return 0;
+}
+int sprite_env_step_launch(const ocrl_sprite_env_desc& d, float* rows, int* aux, unsigned long long seed, const long long* actions, const SpriteStepOut& o,
+                           hipStream_t st) {
+    hipLaunchKernelGGL(sprite_env_step_kernel, dim3(cdiv(d.E, 64)), dim3(64), 0, st, d, rows, aux, seed, actions, o);
+    OCRL_CHECK_LAUNCH("sprite_env_step");
+    return 0;
+}
+int sprite_render_launch(const float* rows, int E, int R, int H, int mode, unsigned char* out, hipStream_t st) {
+    int band_rows = 1024 / H;                                                // about 256 groups of four pixels, one per thread, to a workgroup
+    band_rows = band_rows < 1 ? 1 : (band_rows > H ? H : band_rows);
+    const int bands = cdiv(H, band_rows);
+    hipLaunchKernelGGL(sprite_render_kernel, dim3((unsigned)((long long)E * bands)), dim3(256), 0, st, rows, R, H, band_rows, bands, mode, out);
+    OCRL_CHECK_LAUNCH("sprite_render");
+    return 0;
+}
+int sprite_env_uniforms_launch(unsigned long long seed, long long env0, int n_envs, long long episode, int first, int n, float* out, hipStream_t st) {
+    hipLaunchKernelGGL(sprite_env_uniforms_kernel, dim3(cdiv((long long)n_envs * n, 256)), dim3(256), 0, st, seed, env0, n_envs, episode, first, n, out);
+    OCRL_CHECK_LAUNCH("sprite_env_uniforms");
+    return 0;
+}

@@ -143,6 +143,7 @@ class PPO:
         self._last_obs, self._last_starts = None, None
         self._ep_ret, self._ep_len = np.zeros(self.n_envs), np.zeros(self.n_envs, dtype=np.int64)
         self._episodes = collections.deque(maxlen=100)
+        self._successes = collections.deque(maxlen=100)               # is_success of the same episodes (the on-device path fills it)
 
     # ---- the optimiser's view of the policy: one flat buffer each for parameters, gradients and Adam's two moments
     def _flatten_parameters(self):
@@ -190,7 +191,10 @@ class PPO:
         self._ep_ret[:], self._ep_len[:] = 0.0, 0
 
     def collect_rollouts(self):
-        """n_steps steps of every environment into a fresh buffer, then its returns and advantages"""
+        """n_steps steps of every environment into a fresh buffer, then its returns and advantages.  An environment with ``on_device``
+        set (ocrl_amd.envs) is stepped through ``step_device`` and nothing is read from the device between the steps."""
+        if getattr(self.env, "on_device", False):
+            return self._collect_rollouts_on_device()
         if self._last_obs is None:
             self._reset_env()
         if self.rollout_buffer is None:
@@ -219,6 +223,36 @@ class PPO:
         buf.compute_returns_and_advantage(last_values, self._last_starts)
         return buf
 
+    def _collect_rollouts_on_device(self):
+        """the same rollout with rewards, dones and the episode statistics left on the device: ``step_device`` returns tensors, the buffer
+        takes them as they are, and the finished episodes of the whole rollout are read in one copy at its end, in (step, environment)
+        order, so the 100-episode window fills as on the host path.  Such an environment ends its own episodes (no TimeLimit.truncated)."""
+        T, E = self.n_steps, self.n_envs
+        if self._last_obs is None:
+            self._last_obs = _tensor(self.env.reset(), self.device)
+            self._last_starts = torch.ones(E, device=self.device)
+        if self.rollout_buffer is None:
+            self.rollout_buffer = RolloutBuffer(T, E, self._obs_shape, self.device, self.gamma, self.gae_lambda, self._last_obs.dtype)
+        buf = self.rollout_buffer
+        buf.reset()
+        stats = torch.zeros(T, 4, E, device=self.device, dtype=torch.float64)      # done, success, return, length of the episodes each step ended
+        self.policy.eval()
+        with torch.no_grad():
+            for t in range(T):
+                actions, values, log_probs = self.policy(self._obs(self._last_obs))
+                new_obs, rewards, dones, extras = self.env.step_device(actions)
+                self.num_timesteps += E
+                buf.add(self._last_obs, actions, rewards, self._last_starts, values, log_probs)
+                stats[t, 0], stats[t, 1], stats[t, 2], stats[t, 3] = dones, extras["is_success"], extras["episode_return"], extras["episode_length"]
+                self._last_obs, self._last_starts = new_obs, dones.float()
+            last_values = self.policy.predict_values(self._obs(self._last_obs))[:, 0]
+        buf.compute_returns_and_advantage(last_values, self._last_starts)
+        host = stats.cpu().numpy()                                    # the rollout's one read
+        for t, e in zip(*np.nonzero(host[:, 0])):
+            self._episodes.append((float(host[t, 2, e]), int(host[t, 3, e])))
+            self._successes.append(bool(host[t, 1, e]))
+        return buf
+
     def _track_episodes(self, rewards, dones):
         self._ep_ret += rewards
         self._ep_len += 1
@@ -233,6 +267,11 @@ class PPO:
     @property
     def ep_len_mean(self):
         return float(np.mean([n for _, n in self._episodes])) if self._episodes else float("nan")
+
+    @property
+    def success_rate(self):
+        """share of successes among the last 100 finished episodes (of an on-device environment)"""
+        return float(np.mean(self._successes)) if self._successes else float("nan")
 
     # ---- the update
     def train(self, perms=None):
