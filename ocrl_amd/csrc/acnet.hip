@@ -441,10 +441,7 @@ __global__ __launch_bounds__(256) void acnet_reduce_kernel(AcnetReduceArgs r) {
 __device__ float block_sum256(float v, float* sh) {
     sh[threadIdx.x] = v;
     __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
-        __syncthreads();
-    }
+    block_tree_sum<256>(sh);
     const float s = sh[0];
     __syncthreads();
     return s;

@@ -406,8 +406,6 @@ __global__ __launch_bounds__(256) void bc_mix_kernel(const float* __restrict__ o
 }
 
 // ================================================================== launchers
-#define GRID1D(n) dim3(cdiv((n), 256)), dim3(256)
-
 int bc_compose_launch(const float* W1, const float* Wpos, const float* bpos, float* Wc, float* W1r, int D, hipStream_t st) {
     hipLaunchKernelGGL(bc_compose_kernel, GRID1D(25 * 64), 0, st, W1, Wpos, bpos, Wc, W1r, D);
     OCRL_CHECK_LAUNCH("bc_compose");

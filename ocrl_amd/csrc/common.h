@@ -130,3 +130,51 @@ __device__ inline float wave_max(float v) {
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
     return v;
 }
+
+// ---- reductions whose order is part of the result.  The library is tested to the bit (two-run determinism, fused == unfused, fixture
+// replays), so each order is written once, here; wave_sum / wave_max above run their xor-shuffle stages 32 -> 1.
+//
+// Sum over an aligned group of 16 lanes: xor-shuffle stages 1, 2, 4, 8.  Not wave_sum cut short: that runs the stages downwards, which
+// is another association of the same sum.
+__device__ __forceinline__ float group16_sum(float v) {
+#pragma unroll
+    for (int o = 1; o < 16; o <<= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+// Arg-max over a wave, stages 32 -> 1: the other lane's pair is taken when its value is greater, or equal with a smaller index -- the
+// first index wins ties, like torch.argmax on the CPU.  Every lane ends with the wave's pair.
+__device__ __forceinline__ void wave_argmax(float& best, int& idx) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float ob = __shfl_xor(best, o, 64);
+        const int oi = __shfl_xor(idx, o, 64);
+        if (ob > best || (ob == best && oi < idx)) { best = ob; idx = oi; }
+    }
+}
+// Fixed halving tree over red[0 .. N) in LDS, N = the workgroup's size, filled and synchronised by the caller: level o = N/2, N/4, .. 1
+// does red[t] (op)= red[t + o] for t < o, with a barrier after every level.  The result is red[0], valid for every thread on return; a
+// caller that goes on to overwrite `red` puts its own barrier after reading it.
+template <int N>
+__device__ __forceinline__ void block_tree_sum(float* red) {
+    const int t = threadIdx.x;
+    for (int o = N / 2; o > 0; o >>= 1) {
+        if (t < o) red[t] += red[t + o];
+        __syncthreads();
+    }
+}
+template <int N>
+__device__ __forceinline__ void block_tree_max(float* red) {
+    const int t = threadIdx.x;
+    for (int o = N / 2; o > 0; o >>= 1) {
+        if (t < o) red[t] = fmaxf(red[t], red[t + o]);
+        __syncthreads();
+    }
+}
+
+// ---- host side (the launchers)
+// every pointer 16-byte aligned (float4 access); a null pointer, an optional tensor left out, counts as aligned (uintptr_t: <stdint.h> above)
+template <typename... P>
+static inline bool aligned16(const P*... p) { return ((... | (uintptr_t)p) & 15) == 0; }
+
+// one thread per element, 256 to a workgroup
+#define GRID1D(n) dim3(cdiv((n), 256)), dim3(256)

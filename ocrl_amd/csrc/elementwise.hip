@@ -3,6 +3,7 @@
 // All fp32; rows are processed by whole waves / workgroups with coalesced float4 access.
 #include "common.h"
 #include "kernels.h"
+#include "layernorm16.h"
 
 #define TINYF 1.17549435e-38f
 
@@ -157,34 +158,39 @@ __global__ void layernorm_bwd_kernel(const float* __restrict__ dy, const float* 
         part[(size_t)blockIdx.x * 2 * F + c] = red[0][c] + red[1][c] + red[2][c] + red[3][c];
 }
 
-// 64-wide rows (the slot-attention input norm over B*H*W positions): one wave per row meant one 4-byte load per lane and two full wave
-// reductions per 256 bytes -- latency-bound at 2.4 TB/s.  Here 16 lanes own a row (float4 each), a wave works on 4 rows per pass and
-// has 4 passes (16 rows) in flight; the reductions are four xor-shuffles inside the 16-lane group.
-__device__ __forceinline__ float group16_sum(float v) {
-#pragma unroll
-    for (int o = 1; o < 16; o <<= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__global__ __launch_bounds__(256) void layernorm_fwd64_kernel(const float* __restrict__ x, const float* __restrict__ g, const float* __restrict__ bta,
+// The 16-lane form (layernorm16.h holds the row arithmetic): 16 lanes own a row, NV float4 each (F = 64 * NV), a wave works on 4 rows
+// per pass and keeps NP passes in flight, and the reductions are four xor-shuffles inside the 16-lane group.
+//   <1, 4>, 64-wide rows (the slot-attention input norm over B*H*W positions): one wave per row meant one 4-byte load per lane and two
+//     full wave reductions per 256 bytes -- latency-bound at 2.4 TB/s.  4 passes = 16 rows per wave in flight.
+//   <3, 2>, 192-wide rows (the transformer decoder's d_model): the one-wave-per-row kernels keep one row of 4-byte loads in flight per
+//     wave and need every wave slot of the machine to reach HBM speed -- alone they do (4.7-5.3 TB/s), but on the step's main stream
+//     they share the CUs with the weight-gradient and dVAE streams and ran 2-4x longer (layernorm_bwd 243 vs 64 us, 13 launches per
+//     step on the critical path).  2 passes = 8 rows, 6 KB per wave in flight.
+template <int NV, int NP>   // a workgroup takes 16 * NP rows
+__global__ __launch_bounds__(256) void layernorm16_fwd_kernel(const float* __restrict__ x, const float* __restrict__ g, const float* __restrict__ bta,
                                                               float* __restrict__ y, float* __restrict__ mean, float* __restrict__ rstd, long long R) {
+    constexpr int F = 64 * NV;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, c4 = lane & 15, rsub = lane >> 4;
-    const long long row0 = ((long long)blockIdx.x * 4 + wv) * 16 + rsub;
-    float4 v[4];
+    const long long row0 = ((long long)blockIdx.x * 4 + wv) * (4 * NP) + rsub;
+    float4 v[NP][NV];
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const long long row = row0 + 4 * i;
-        v[i] = row < R ? *reinterpret_cast<const float4*>(x + row * 64 + c4 * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-    const float4 gg = *reinterpret_cast<const float4*>(g + c4 * 4), bb = *reinterpret_cast<const float4*>(bta + c4 * 4);
+    for (int i = 0; i < NP; ++i)
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
+        for (int k = 0; k < NV; ++k) {
+            const long long row = row0 + 4 * i;
+            v[i][k] = row < R ? *reinterpret_cast<const float4*>(x + row * F + (k * 16 + c4) * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+    float4 gg[NV], bb[NV];
+#pragma unroll
+    for (int k = 0; k < NV; ++k) { gg[k] = *reinterpret_cast<const float4*>(g + (k * 16 + c4) * 4); bb[k] = *reinterpret_cast<const float4*>(bta + (k * 16 + c4) * 4); }
+#pragma unroll
+    for (int i = 0; i < NP; ++i) {
         const long long row = row0 + 4 * i;
-        const float mu = group16_sum((v[i].x + v[i].y) + (v[i].z + v[i].w)) * (1.0f / 64);
-        const float4 dd = make_float4(v[i].x - mu, v[i].y - mu, v[i].z - mu, v[i].w - mu);
-        const float rs = rsqrtf(group16_sum((dd.x * dd.x + dd.y * dd.y) + (dd.z * dd.z + dd.w * dd.w)) * (1.0f / 64) + 1e-5f);
+        float mu, rs;
+        layernorm16_row_fwd<NV>(v[i], mu, rs);
         if (row < R) {
-            *reinterpret_cast<float4*>(y + row * 64 + c4 * 4) =
-                make_float4(dd.x * rs * gg.x + bb.x, dd.y * rs * gg.y + bb.y, dd.z * rs * gg.z + bb.z, dd.w * rs * gg.w + bb.w);
+#pragma unroll
+            for (int k = 0; k < NV; ++k) *reinterpret_cast<float4*>(y + row * F + (k * 16 + c4) * 4) = layernorm16_affine(v[i][k], rs, gg[k], bb[k]);
             if (c4 == 0) {
                 if (mean) mean[row] = mu;
                 if (rstd) rstd[row] = rs;
@@ -192,146 +198,42 @@ __global__ __launch_bounds__(256) void layernorm_fwd64_kernel(const float* __res
         }
     }
 }
-// backward, same layout; a block walks 64-row groups with stride gridDim.x and leaves its dgamma | dbeta partial in part[blk][128]
-__global__ __launch_bounds__(256) void layernorm_bwd64_kernel(const float* __restrict__ dy, const float* __restrict__ x, const float* __restrict__ mean,
+// backward, same layout; a block walks groups of 16 * NP rows with stride gridDim.x and leaves its dgamma | dbeta partial in part[blk][2F]
+template <int NV, int NP>
+__global__ __launch_bounds__(256) void layernorm16_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ x, const float* __restrict__ mean,
                                                               const float* __restrict__ rstd, const float* __restrict__ g, float* __restrict__ dx,
                                                               float* __restrict__ part, long long R, int accumulate) {
-    __shared__ float4 red[2][16][16];
+    constexpr int F = 64 * NV;
+    __shared__ float4 red[2][16][16 * NV];       // [dgamma | dbeta][wave * 4 + row group][float4 column]
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, c4 = lane & 15, rsub = lane >> 4;
-    const float4 gg = *reinterpret_cast<const float4*>(g + c4 * 4);
-    float4 dg = make_float4(0.f, 0.f, 0.f, 0.f), db = dg;
-    for (long long grp = blockIdx.x; grp * 64 < R; grp += gridDim.x) {
-        const long long row0 = (grp * 4 + wv) * 16 + rsub;
-        float4 xv[4], yv[4];
-        float mu[4], rs[4];
+    float4 gg[NV], dg[NV], db[NV];
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const long long row = row0 + 4 * i;
-            const bool ok = row < R;
-            xv[i] = ok ? *reinterpret_cast<const float4*>(x + row * 64 + c4 * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
-            yv[i] = ok ? *reinterpret_cast<const float4*>(dy + row * 64 + c4 * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
-            mu[i] = ok ? mean[row] : 0.f;
-            rs[i] = ok ? rstd[row] : 0.f;
-        }
+    for (int k = 0; k < NV; ++k) { gg[k] = *reinterpret_cast<const float4*>(g + (k * 16 + c4) * 4); dg[k] = make_float4(0.f, 0.f, 0.f, 0.f); db[k] = dg[k]; }
+    for (long long grp = blockIdx.x; grp * (16 * NP) < R; grp += gridDim.x) {
+        const long long row0 = (grp * 4 + wv) * (4 * NP) + rsub;
+        float4 xv[NP][NV], yv[NP][NV];
+        float mu[NP], rs[NP];
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const long long row = row0 + 4 * i;
-            const float4 xh = make_float4((xv[i].x - mu[i]) * rs[i], (xv[i].y - mu[i]) * rs[i], (xv[i].z - mu[i]) * rs[i], (xv[i].w - mu[i]) * rs[i]);
-            dg.x += yv[i].x * xh.x; dg.y += yv[i].y * xh.y; dg.z += yv[i].z * xh.z; dg.w += yv[i].w * xh.w;
-            db.x += yv[i].x; db.y += yv[i].y; db.z += yv[i].z; db.w += yv[i].w;
-            const float4 d4 = make_float4(yv[i].x * gg.x, yv[i].y * gg.y, yv[i].z * gg.z, yv[i].w * gg.w);
-            const float s1 = group16_sum((d4.x + d4.y) + (d4.z + d4.w)) * (1.0f / 64);
-            const float s2 = group16_sum((d4.x * xh.x + d4.y * xh.y) + (d4.z * xh.z + d4.w * xh.w)) * (1.0f / 64);
-            if (row < R) {
-                float4 o = make_float4(rs[i] * (d4.x - s1 - xh.x * s2), rs[i] * (d4.y - s1 - xh.y * s2), rs[i] * (d4.z - s1 - xh.z * s2),
-                                       rs[i] * (d4.w - s1 - xh.w * s2));
-                float* dp = dx + row * 64 + c4 * 4;
-                if (accumulate) { const float4 a = *reinterpret_cast<const float4*>(dp); o.x += a.x; o.y += a.y; o.z += a.z; o.w += a.w; }
-                *reinterpret_cast<float4*>(dp) = o;
-            }
-        }
-    }
-    red[0][wv * 4 + rsub][c4] = dg;
-    red[1][wv * 4 + rsub][c4] = db;
-    __syncthreads();
-    if (threadIdx.x < 32) {
-        const int which = threadIdx.x >> 4, c = threadIdx.x & 15;
-        float4 a = red[which][0][c];
-#pragma unroll
-        for (int k = 1; k < 16; ++k) { const float4 t = red[which][k][c]; a.x += t.x; a.y += t.y; a.z += t.z; a.w += t.w; }
-        *reinterpret_cast<float4*>(part + (size_t)blockIdx.x * 128 + which * 64 + c * 4) = a;
-    }
-}
-
-// 192-wide rows (the transformer decoder's d_model): the one-wave-per-row kernels keep one row of 4-byte loads in flight per wave and
-// need every wave slot of the machine to reach HBM speed -- alone they do (4.7-5.3 TB/s), but on the step's main stream they share the
-// CUs with the weight-gradient and dVAE streams and ran 2-4x longer (layernorm_bwd 243 vs 64 us, 13 launches per step on the critical
-// path).  Here 16 lanes own a row (three float4 each), a wave works on 4 rows per pass and keeps 2 passes (8 rows, 6 KB) in flight.
-__global__ __launch_bounds__(256) void layernorm_fwd192_kernel(const float* __restrict__ x, const float* __restrict__ g, const float* __restrict__ bta,
-                                                               float* __restrict__ y, float* __restrict__ mean, float* __restrict__ rstd, long long R) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, c4 = lane & 15, rsub = lane >> 4;
-    const long long row0 = ((long long)blockIdx.x * 4 + wv) * 8 + rsub;
-    float4 v[2][3];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            const long long row = row0 + 4 * i;
-            v[i][k] = row < R ? *reinterpret_cast<const float4*>(x + row * 192 + (k * 16 + c4) * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-    float4 gg[3], bb[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) { gg[k] = *reinterpret_cast<const float4*>(g + (k * 16 + c4) * 4); bb[k] = *reinterpret_cast<const float4*>(bta + (k * 16 + c4) * 4); }
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        const long long row = row0 + 4 * i;
-        float s = 0.f;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) s += (v[i][k].x + v[i][k].y) + (v[i][k].z + v[i][k].w);
-        const float mu = group16_sum(s) * (1.0f / 192);
-        float q = 0.f;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            v[i][k].x -= mu; v[i][k].y -= mu; v[i][k].z -= mu; v[i][k].w -= mu;
-            q += (v[i][k].x * v[i][k].x + v[i][k].y * v[i][k].y) + (v[i][k].z * v[i][k].z + v[i][k].w * v[i][k].w);
-        }
-        const float rs = rsqrtf(group16_sum(q) * (1.0f / 192) + 1e-5f);
-        if (row < R) {
-#pragma unroll
-            for (int k = 0; k < 3; ++k)
-                *reinterpret_cast<float4*>(y + row * 192 + (k * 16 + c4) * 4) = make_float4(v[i][k].x * rs * gg[k].x + bb[k].x, v[i][k].y * rs * gg[k].y + bb[k].y,
-                                                                                            v[i][k].z * rs * gg[k].z + bb[k].z, v[i][k].w * rs * gg[k].w + bb[k].w);
-            if (c4 == 0) { if (mean) mean[row] = mu; if (rstd) rstd[row] = rs; }
-        }
-    }
-}
-__global__ __launch_bounds__(256) void layernorm_bwd192_kernel(const float* __restrict__ dy, const float* __restrict__ x, const float* __restrict__ mean,
-                                                               const float* __restrict__ rstd, const float* __restrict__ g, float* __restrict__ dx,
-                                                               float* __restrict__ part, long long R, int accumulate) {
-    __shared__ float4 red[2][16][48];            // [dgamma | dbeta][wave * 4 + row group][float4 column]
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, c4 = lane & 15, rsub = lane >> 4;
-    float4 gg[3], dg[3], db[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) { gg[k] = *reinterpret_cast<const float4*>(g + (k * 16 + c4) * 4); dg[k] = make_float4(0.f, 0.f, 0.f, 0.f); db[k] = dg[k]; }
-    for (long long grp = blockIdx.x; grp * 32 < R; grp += gridDim.x) {         // 32 rows per workgroup and pass
-        const long long row0 = (grp * 4 + wv) * 8 + rsub;
-        float4 xv[2][3], yv[2][3];
-        float mu[2], rs[2];
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
+        for (int i = 0; i < NP; ++i) {
             const long long row = row0 + 4 * i;
             const bool ok = row < R;
 #pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                xv[i][k] = ok ? *reinterpret_cast<const float4*>(x + row * 192 + (k * 16 + c4) * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
-                yv[i][k] = ok ? *reinterpret_cast<const float4*>(dy + row * 192 + (k * 16 + c4) * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
+            for (int k = 0; k < NV; ++k) {
+                xv[i][k] = ok ? *reinterpret_cast<const float4*>(x + row * F + (k * 16 + c4) * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
+                yv[i][k] = ok ? *reinterpret_cast<const float4*>(dy + row * F + (k * 16 + c4) * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
             }
             mu[i] = ok ? mean[row] : 0.f;
             rs[i] = ok ? rstd[row] : 0.f;
         }
 #pragma unroll
-        for (int i = 0; i < 2; ++i) {
+        for (int i = 0; i < NP; ++i) {
             const long long row = row0 + 4 * i;
-            float4 xh[3], d4[3];
-            float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                xh[k] = make_float4((xv[i][k].x - mu[i]) * rs[i], (xv[i][k].y - mu[i]) * rs[i], (xv[i][k].z - mu[i]) * rs[i], (xv[i][k].w - mu[i]) * rs[i]);
-                const float4 yy = yv[i][k];
-                dg[k].x += yy.x * xh[k].x; dg[k].y += yy.y * xh[k].y; dg[k].z += yy.z * xh[k].z; dg[k].w += yy.w * xh[k].w;
-                db[k].x += yy.x; db[k].y += yy.y; db[k].z += yy.z; db[k].w += yy.w;
-                d4[k] = make_float4(yy.x * gg[k].x, yy.y * gg[k].y, yy.z * gg[k].z, yy.w * gg[k].w);
-                s1 += (d4[k].x + d4[k].y) + (d4[k].z + d4[k].w);
-                s2 += (d4[k].x * xh[k].x + d4[k].y * xh[k].y) + (d4[k].z * xh[k].z + d4[k].w * xh[k].w);
-            }
-            s1 = group16_sum(s1) * (1.0f / 192);
-            s2 = group16_sum(s2) * (1.0f / 192);
+            const Ln16Bwd<NV> r = layernorm16_row_bwd<NV>(xv[i], yv[i], mu[i], rs[i], gg, dg, db);
             if (row < R) {
 #pragma unroll
-                for (int k = 0; k < 3; ++k) {
-                    float4 o = make_float4(rs[i] * (d4[k].x - s1 - xh[k].x * s2), rs[i] * (d4[k].y - s1 - xh[k].y * s2), rs[i] * (d4[k].z - s1 - xh[k].z * s2),
-                                           rs[i] * (d4[k].w - s1 - xh[k].w * s2));
-                    float* dp = dx + row * 192 + (k * 16 + c4) * 4;
+                for (int k = 0; k < NV; ++k) {
+                    float4 o = layernorm16_row_dx(r, rs[i], k);
+                    float* dp = dx + row * F + (k * 16 + c4) * 4;
                     if (accumulate) { const float4 a = *reinterpret_cast<const float4*>(dp); o.x += a.x; o.y += a.y; o.z += a.z; o.w += a.w; }
                     *reinterpret_cast<float4*>(dp) = o;
                 }
@@ -339,14 +241,14 @@ __global__ __launch_bounds__(256) void layernorm_bwd192_kernel(const float* __re
         }
     }
 #pragma unroll
-    for (int k = 0; k < 3; ++k) { red[0][wv * 4 + rsub][k * 16 + c4] = dg[k]; red[1][wv * 4 + rsub][k * 16 + c4] = db[k]; }
+    for (int k = 0; k < NV; ++k) { red[0][wv * 4 + rsub][k * 16 + c4] = dg[k]; red[1][wv * 4 + rsub][k * 16 + c4] = db[k]; }
     __syncthreads();
-    if (threadIdx.x < 96) {                      // fixed order over the 16 (wave, row group) partials
-        const int which = threadIdx.x / 48, c = threadIdx.x % 48;
+    if (threadIdx.x < 32 * NV) {                 // fixed order over the 16 (wave, row group) partials
+        const int which = threadIdx.x / (16 * NV), c = threadIdx.x % (16 * NV);
         float4 a = red[which][0][c];
 #pragma unroll
         for (int k = 1; k < 16; ++k) { const float4 t = red[which][k][c]; a.x += t.x; a.y += t.y; a.z += t.z; a.w += t.w; }
-        *reinterpret_cast<float4*>(part + (size_t)blockIdx.x * 384 + which * 192 + c * 4) = a;
+        *reinterpret_cast<float4*>(part + (size_t)blockIdx.x * (2 * F) + which * F + c * 4) = a;
     }
 }
 
@@ -523,12 +425,7 @@ __global__ __launch_bounds__(256) void gumbel_softmax_kernel(const float* __rest
 #pragma unroll
         for (int i = 0; i < GS_MAXPT; ++i)
             if (i < npt && u[i] > b1) { b1 = u[i]; b1i = i * 256 + threadIdx.x; }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const float ob = __shfl_xor(b1, o, 64);
-            const int oi = __shfl_xor(b1i, o, 64);
-            if (ob > b1 || (ob == b1 && oi < b1i)) { b1 = ob; b1i = oi; }
-        }
+        wave_argmax(b1, b1i);
         __shared__ float hv[4];
         __shared__ int hi[4];
         if ((threadIdx.x & 63) == 0) { hv[threadIdx.x >> 6] = b1; hi[threadIdx.x >> 6] = b1i; }
@@ -544,12 +441,7 @@ __global__ __launch_bounds__(256) void gumbel_softmax_kernel(const float* __rest
             }
     }
     // argmax (first index wins ties, like torch.argmax on CPU)
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ob = __shfl_xor(best, o, 64);
-        const int oi = __shfl_xor(besti, o, 64);
-        if (ob > best || (ob == best && oi < besti)) { best = ob; besti = oi; }
-    }
+    wave_argmax(best, besti);
     const int w = threadIdx.x >> 6;
     if ((threadIdx.x & 63) == 0) { redv[w] = best; redi[w] = besti; }
     __syncthreads();
@@ -581,44 +473,6 @@ __global__ __launch_bounds__(256) void softmax_bwd_rows_kernel(const float* __re
         if (i < npt) d[row * V + i * 256 + threadIdx.x] = zz[i] * (dd[i] - s) * scale;
 }
 
-// cross entropy with hard targets, one workgroup per row: part[row] = lse - pred[tok];
-// pred <- (softmax(pred) - onehot(tok)) * inv_b   (in place gradient)
-template <int NPT>
-__global__ __launch_bounds__(256) void ce_kernel(float* __restrict__ pred, const int* __restrict__ tokens, float* __restrict__ part,
-                                                 int V, float inv_b, int write_grad) {
-    __shared__ float red[4];
-    const long long row = blockIdx.x;
-    float* r = pred + row * V;
-    const int tok = tokens[row];
-    const int npt = NPT ? NPT : V / 256;                 // V % 256 == 0, V <= 256 * GS_MAXPT: the row lives in registers (one read, one exp, one write)
-    float x[GS_MAXPT];
-    float mx = -INFINITY, rt = 0.f;
-#pragma unroll
-    for (int i = 0; i < GS_MAXPT; ++i)
-        if (i < npt) {
-            x[i] = r[i * 256 + threadIdx.x];
-            mx = fmaxf(mx, x[i]);
-            if (i * 256 + (int)threadIdx.x == tok) rt = x[i];
-        }
-    mx = block_max(mx, red);
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < GS_MAXPT; ++i)
-        if (i < npt) { x[i] = __expf(x[i] - mx); s += x[i]; }
-    s = block_sum(s, red);
-    rt = block_sum(rt, red);                 // exactly one thread holds the target logit
-    if (threadIdx.x == 0) part[row] = (mx + __logf(s)) - rt;
-    if (write_grad) {
-        const float inv = 1.0f / s;
-#pragma unroll
-        for (int i = 0; i < GS_MAXPT; ++i)
-            if (i < npt) {
-                const int v = i * 256 + threadIdx.x;
-                r[v] = (x[i] * inv - (v == tok ? 1.f : 0.f)) * inv_b;
-            }
-    }
-}
-
 // ------------------------------------------------------------------ soft-max heads fused into the vocabulary GEMMs (gemm.hip, epi_mode 1-3)
 // One wave per row, lane = 64-column segment: combines the per-segment (max, sum-exp) pairs the GEMM epilogue left in `stat` into
 // lse[row]; optionally picks the hard Gumbel sample (first maximum over the segment maxima -> tokens[row]) and the cross-entropy term
@@ -647,20 +501,14 @@ __global__ __launch_bounds__(1024) void softmax_stat_combine_kernel(const float*
     if (row < R) {
         float m = -INFINITY, sv = 0.f;
         if (lane < nseg) { m = stat[((size_t)row * nseg + lane) * 2]; sv = stat[((size_t)row * nseg + lane) * 2 + 1]; }
-        float mx = m;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
-        float t = m > -INFINITY ? sv * __expf(m - mx) : 0.f;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o, 64);
+        const float mx = wave_max(m);
+        const float t = wave_sum(m > -INFINITY ? sv * __expf(m - mx) : 0.f);
         const float l = mx + __logf(t);
         if (lane == 0) lse[row] = l;
         if (hstat && cdf.scores) {
             float hm = -INFINITY, hsum = 0.f;
             if (lane < nseg) { hm = hstat[(size_t)row * nseg + lane]; hsum = __builtin_bit_cast(float, hidx[(size_t)row * nseg + lane]); }
-            float M = hm;
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) M = fmaxf(M, __shfl_xor(M, o, 64));
+            const float M = wave_max(hm);
             const float w = hm > -INFINITY ? hsum * __expf(hm - M) : 0.f;
             const float cw = wave_incl_scan(w, lane);
             const float tot = __shfl(cw, 63, 64);
@@ -690,12 +538,7 @@ __global__ __launch_bounds__(1024) void softmax_stat_combine_kernel(const float*
             float b = -INFINITY;
             int bi = 0x7fffffff;
             if (lane < nseg) { b = hstat[(size_t)row * nseg + lane]; bi = hidx[(size_t)row * nseg + lane]; }
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) {
-                const float ob = __shfl_xor(b, o, 64);
-                const int oi = __shfl_xor(bi, o, 64);
-                if (ob > b || (ob == b && oi < bi)) { b = ob; bi = oi; }
-            }
+            wave_argmax(b, bi);
             if (lane == 0) tokens[row] = bi;
         }
         if (part && lane == 0) loss = l - pred[(size_t)row * ldp + tok[row]];
@@ -1355,12 +1198,7 @@ __global__ __launch_bounds__(256) void argmax_pos_kernel(const float* __restrict
     float best = -INFINITY;
     int bi = 0;
     for (int v = threadIdx.x; v < V; v += 256) { const float x = r[v]; if (x > best) { best = x; bi = v; } }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ob = __shfl_xor(best, o, 64);
-        const int oi = __shfl_xor(bi, o, 64);
-        if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
-    }
+    wave_argmax(best, bi);
     if ((threadIdx.x & 63) == 0) { rv[threadIdx.x >> 6] = best; ri[threadIdx.x >> 6] = bi; }
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -1405,14 +1243,14 @@ __global__ __launch_bounds__(256) void decode_attn_kernel(const float* __restric
     }
     red[tid] = mx;
     __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) { if (tid < o) red[tid] = fmaxf(red[tid], red[tid + o]); __syncthreads(); }
+    block_tree_max<256>(red);
     mx = red[0];
     __syncthreads();
     float sum = 0.f;
     for (int j = tid; j < nk; j += 256) { const float e = __expf(sc[j] - mx); sc[j] = e; sum += e; }
     red[tid] = sum;
     __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) { if (tid < o) red[tid] += red[tid + o]; __syncthreads(); }
+    block_tree_sum<256>(red);
     const float inv = 1.0f / red[0];
     __syncthreads();
     const int nsl = 256 / dh, c = tid % dh, sl = tid / dh;
@@ -1436,8 +1274,6 @@ __global__ void onehot_kernel(const int* __restrict__ tokens, float* __restrict_
 }
 
 // ================================================================== launchers
-#define GRID1D(n) dim3(cdiv((n), 256)), dim3(256)
-
 int nchw_to_nhwc8_launch(const float* in, float* out, int B, int C, int H, int W, hipStream_t st) {
     OCRL_REQUIRE(C <= 8, "nchw_to_nhwc8: C must be <= 8");
     const long long n = (long long)B * H * W;
@@ -1461,15 +1297,15 @@ int pixel_shuffle_launch(const float* in, float* out, int B, int h, int w, int C
 int layernorm_fwd_launch(const float* x, const float* g, const float* b, float* y, float* mean, float* rstd, long long R, int F, hipStream_t st) {
     OCRL_REQUIRE(F % 64 == 0 && F >= 64 && F <= 256, "layernorm: F must be 64..256, multiple of 64 (got %d)", F);
     dim3 grid(cdiv(R, 4)), blk(256);
-    const bool al16 = (((uintptr_t)x | (uintptr_t)y | (uintptr_t)g | (uintptr_t)b) & 15) == 0;
+    const bool al16 = aligned16(x, y, g, b);
     switch (F / 64) {
         case 1:
-            if (al16) hipLaunchKernelGGL(layernorm_fwd64_kernel, dim3((unsigned)cdiv(R, 64)), blk, 0, st, x, g, b, y, mean, rstd, R);
+            if (al16) hipLaunchKernelGGL((layernorm16_fwd_kernel<1, 4>), dim3((unsigned)cdiv(R, 64)), blk, 0, st, x, g, b, y, mean, rstd, R);
             else hipLaunchKernelGGL(layernorm_fwd_kernel<1>, grid, blk, 0, st, x, g, b, y, mean, rstd, R);
             break;
         case 2: hipLaunchKernelGGL(layernorm_fwd_kernel<2>, grid, blk, 0, st, x, g, b, y, mean, rstd, R); break;
         case 3:
-            if (al16) hipLaunchKernelGGL(layernorm_fwd192_kernel, dim3((unsigned)cdiv(R, 32)), blk, 0, st, x, g, b, y, mean, rstd, R);
+            if (al16) hipLaunchKernelGGL((layernorm16_fwd_kernel<3, 2>), dim3((unsigned)cdiv(R, 32)), blk, 0, st, x, g, b, y, mean, rstd, R);
             else hipLaunchKernelGGL(layernorm_fwd_kernel<3>, grid, blk, 0, st, x, g, b, y, mean, rstd, R);
             break;
         default: hipLaunchKernelGGL(layernorm_fwd_kernel<4>, grid, blk, 0, st, x, g, b, y, mean, rstd, R); break;
@@ -1514,16 +1350,15 @@ int layernorm_bwd_launch(const float* dy, const float* x, const float* mean, con
     const size_t need = (size_t)nblk * 2 * F;
     OCRL_REQUIRE(need + (size_t)8 * 2 * F <= ws_floats, "layernorm bwd: workspace too small");
     dim3 grid(nblk), blk(256);
+    const bool al16 = aligned16(x, dy, dx, g, ws);
     switch (F / 64) {
         case 1:
-            if (((((uintptr_t)x | (uintptr_t)dy | (uintptr_t)dx | (uintptr_t)g) & 15) == 0) && (((uintptr_t)ws) & 15) == 0)
-                hipLaunchKernelGGL(layernorm_bwd64_kernel, grid, blk, 0, st, dy, x, mean, rstd, g, dx, ws, R, accumulate_dx);
+            if (al16) hipLaunchKernelGGL((layernorm16_bwd_kernel<1, 4>), grid, blk, 0, st, dy, x, mean, rstd, g, dx, ws, R, accumulate_dx);
             else hipLaunchKernelGGL(layernorm_bwd_kernel<1>, grid, blk, 0, st, dy, x, mean, rstd, g, dx, ws, R, accumulate_dx);
             break;
         case 2: hipLaunchKernelGGL(layernorm_bwd_kernel<2>, grid, blk, 0, st, dy, x, mean, rstd, g, dx, ws, R, accumulate_dx); break;
         case 3:
-            if (((((uintptr_t)x | (uintptr_t)dy | (uintptr_t)dx | (uintptr_t)g) & 15) == 0) && (((uintptr_t)ws) & 15) == 0)
-                hipLaunchKernelGGL(layernorm_bwd192_kernel, grid, blk, 0, st, dy, x, mean, rstd, g, dx, ws, R, accumulate_dx);
+            if (al16) hipLaunchKernelGGL((layernorm16_bwd_kernel<3, 2>), grid, blk, 0, st, dy, x, mean, rstd, g, dx, ws, R, accumulate_dx);
             else hipLaunchKernelGGL(layernorm_bwd_kernel<3>, grid, blk, 0, st, dy, x, mean, rstd, g, dx, ws, R, accumulate_dx);
             break;
         default: hipLaunchKernelGGL(layernorm_bwd_kernel<4>, grid, blk, 0, st, dy, x, mean, rstd, g, dx, ws, R, accumulate_dx); break;
@@ -1562,14 +1397,6 @@ int softmax_bwd_rows_launch(const float* z, float* d, long long R, int V, float 
     else hipLaunchKernelGGL(softmax_bwd_rows_kernel<0>, dim3((unsigned)R), dim3(256), 0, st, z, d, V, scale);
     OCRL_CHECK_LAUNCH("softmax_bwd_rows");
     return 0;
-}
-int ce_launch(float* pred, const int* tokens, float* out, long long R, int V, int B, int write_grad, float* ws, size_t ws_floats, hipStream_t st) {
-    OCRL_REQUIRE(ws_floats >= (size_t)R, "ce: workspace too small");
-    OCRL_REQUIRE(V % 256 == 0 && V <= 256 * GS_MAXPT, "ce: V must be a multiple of 256, <= %d", 256 * GS_MAXPT);
-    if (V == 4096) hipLaunchKernelGGL(ce_kernel<16>, dim3((unsigned)R), dim3(256), 0, st, pred, tokens, ws, V, 1.0f / B, write_grad);
-    else hipLaunchKernelGGL(ce_kernel<0>, dim3((unsigned)R), dim3(256), 0, st, pred, tokens, ws, V, 1.0f / B, write_grad);
-    OCRL_CHECK_LAUNCH("ce");
-    return reduce_partials_launch(ws, (int)R, out, 1.0f / B, 0, st);
 }
 // lse [R]; tokens (with hstat / hidx) and the cross-entropy sum (with pred / tok; out[0] = scale * sum, ws >= ceil(R/16) floats) are optional
 int softmax_stat_combine_launch(const float* stat, int nseg, long long R, float* lse, const float* hstat, const int* hidx, int* tokens,

@@ -49,7 +49,7 @@ __global__ __launch_bounds__(1024) void io_ordered_sum_kernel(const float* __res
     for (long long i = threadIdx.x; i < n; i += 1024) a += x[i * stride];
     red[threadIdx.x] = a;
     __syncthreads();
-    for (int o = 512; o > 0; o >>= 1) { if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o]; __syncthreads(); }
+    block_tree_sum<1024>(red);
     if (threadIdx.x == 0) out[0] = red[0];
 }
 

@@ -317,7 +317,6 @@ int softmax_stat_combine_launch(const float* stat, int nseg, long long R, float*
                                 const float* cdf_scores = nullptr, int cdf_V = 0, float cdf_tau = 1.f, unsigned long long cdf_seed = 0);
 int exp_rows_launch(const float* y, const float* lse, float* z, long long R, int V, hipStream_t st);
 int rowdot_bias64_launch(const float* g, const float* act, const float* bias, long long R, float* out, hipStream_t st);
-int ce_launch(float* pred, const int* tokens, float* out, long long R, int V, int B, int write_grad, float* ws, size_t ws_floats, hipStream_t st);
 int embed_fwd_launch(const int* tokens, const float* dict, const float* bos, const float* pe, float* out, int B, int T, int d, float p,
                      unsigned long long seed, hipStream_t st);
 size_t embed_bwd_ws_floats(long long BT, int V, int d);

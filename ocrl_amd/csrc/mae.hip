@@ -271,10 +271,7 @@ __global__ __launch_bounds__(256) void mae_loss_kernel(const float* __restrict__
     if (!part) return;
     red[tid] = s;
     __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {                // fixed tree
-        if (tid < w) red[tid] += red[tid + w];
-        __syncthreads();
-    }
+    block_tree_sum<256>(red);
     if (tid == 0) part[(long long)b * L + l] = m * red[0] / (float)P;
 }
 
@@ -285,18 +282,11 @@ __global__ __launch_bounds__(256) void mae_loss_final_kernel(const float* __rest
     for (long long i = threadIdx.x; i < n; i += 256) s += part[i];
     red[threadIdx.x] = s;
     __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-        __syncthreads();
-    }
+    block_tree_sum<256>(red);
     if (threadIdx.x == 0) out[0] = out[1] = red[0] * scale;
 }
 
-inline bool al16(const void* a) { return (((uintptr_t)a) & 15) == 0; }
-
 }  // namespace
-
-#define GRID1D(n) dim3(cdiv((n), 256)), dim3(256)
 
 int mae_rank_launch(const float* noise, int* restore, int* keep, float* mask, int* restore_out, float* mask_out, int B, int L, int len_keep,
                     hipStream_t st) {
@@ -309,7 +299,7 @@ int mae_rank_launch(const float* noise, int* restore, int* keep, float* mask, in
 
 int mae_patch_gather_launch(const float* obs, const int* ids, float* out, int B, int n, int S, int p, hipStream_t st) {
     OCRL_REQUIRE(p >= 1 && S % p == 0 && n >= 1 && n <= (S / p) * (S / p), "mae_patch_gather: bad shape (S %d, patch %d, n %d)", S, p, n);
-    if (p % 4 == 0 && al16(obs) && al16(out)) {
+    if (p % 4 == 0 && aligned16(obs, out)) {
         const long long total = (long long)B * n * 3 * p * (p / 4);
         hipLaunchKernelGGL(mae_patch_gather_kernel<4>, GRID1D(total), 0, st, obs, ids, out, total, n, S, p);
     } else {
@@ -321,7 +311,7 @@ int mae_patch_gather_launch(const float* obs, const int* ids, float* out, int B,
 }
 
 int mae_tokens_fwd_launch(const float* embed, const float* cls, const float* pos, const int* ids, float* x0, int B, int n, int D, hipStream_t st) {
-    OCRL_REQUIRE(D % 4 == 0 && al16(embed) && al16(cls) && al16(pos) && al16(x0), "mae_tokens: D %% 4 == 0 and 16-byte aligned rows (D = %d)", D);
+    OCRL_REQUIRE(D % 4 == 0 && aligned16(embed, cls, pos, x0), "mae_tokens: D %% 4 == 0 and 16-byte aligned rows (D = %d)", D);
     const long long total = (long long)B * (n + 1) * (D / 4);
     hipLaunchKernelGGL(mae_tokens_fwd_kernel, GRID1D(total), 0, st, embed, cls, pos, ids, x0, total, n, D / 4);
     OCRL_CHECK_LAUNCH("mae_tokens_fwd");
@@ -335,7 +325,7 @@ int mae_rowsum_launch(const float* src, long long ld, float* out, int n, int F, 
 }
 
 int mae_tokens_bwd_launch(const float* dx0, float* dembed, float* dcls, int B, int n, int D, hipStream_t st) {
-    OCRL_REQUIRE(D % 4 == 0 && al16(dx0) && al16(dembed), "mae_tokens: D %% 4 == 0 and 16-byte aligned rows (D = %d)", D);
+    OCRL_REQUIRE(D % 4 == 0 && aligned16(dx0, dembed), "mae_tokens: D %% 4 == 0 and 16-byte aligned rows (D = %d)", D);
     const long long total = (long long)B * n * (D / 4);
     hipLaunchKernelGGL(mae_rows_kernel, GRID1D(total), 0, st, dx0, (const int*)nullptr, dembed, total, n, n, D / 4, 0);
     OCRL_CHECK_LAUNCH("mae_tokens_bwd");
@@ -344,7 +334,7 @@ int mae_tokens_bwd_launch(const float* dx0, float* dembed, float* dcls, int B, i
 
 int mae_unshuffle_fwd_launch(const float* e, const float* mtok, const float* dpos, const int* restore, float* xd, int B, int L, int len_keep, int Dd,
                              hipStream_t st) {
-    OCRL_REQUIRE(Dd % 4 == 0 && al16(e) && al16(mtok) && al16(dpos) && al16(xd), "mae_unshuffle: width %% 4 == 0 and 16-byte aligned rows (%d)", Dd);
+    OCRL_REQUIRE(Dd % 4 == 0 && aligned16(e, mtok, dpos, xd), "mae_unshuffle: width %% 4 == 0 and 16-byte aligned rows (%d)", Dd);
     const long long total = (long long)B * (L + 1) * (Dd / 4);
     hipLaunchKernelGGL(mae_unshuffle_fwd_kernel, GRID1D(total), 0, st, e, mtok, dpos, restore, xd, total, L, len_keep, Dd / 4);
     OCRL_CHECK_LAUNCH("mae_unshuffle_fwd");
@@ -353,7 +343,7 @@ int mae_unshuffle_fwd_launch(const float* e, const float* mtok, const float* dpo
 
 int mae_unshuffle_bwd_launch(const float* dxd, const int* keep, const float* mask, float* de, float* dmtok, float* part, int B, int L, int len_keep,
                              int Dd, hipStream_t st) {
-    OCRL_REQUIRE(Dd % 4 == 0 && al16(dxd) && al16(de), "mae_unshuffle: width %% 4 == 0 and 16-byte aligned rows (%d)", Dd);
+    OCRL_REQUIRE(Dd % 4 == 0 && aligned16(dxd, de), "mae_unshuffle: width %% 4 == 0 and 16-byte aligned rows (%d)", Dd);
     const long long total = (long long)B * (len_keep + 1) * (Dd / 4);
     hipLaunchKernelGGL(mae_rows_kernel, GRID1D(total), 0, st, dxd, keep, de, total, len_keep, L, Dd / 4, 1);
     OCRL_CHECK_LAUNCH("mae_unshuffle_bwd");
@@ -363,21 +353,21 @@ int mae_unshuffle_bwd_launch(const float* dxd, const int* keep, const float* mas
 }
 
 int mae_gelu_fwd_launch(const float* pre, float* y, long long n, hipStream_t st) {
-    OCRL_REQUIRE(n % 4 == 0 && al16(pre) && al16(y), "mae_gelu: n %% 4 == 0 and 16-byte aligned buffers");
+    OCRL_REQUIRE(n % 4 == 0 && aligned16(pre, y), "mae_gelu: n %% 4 == 0 and 16-byte aligned buffers");
     hipLaunchKernelGGL(mae_gelu_fwd_kernel, GRID1D(n / 4), 0, st, pre, y, n / 4);
     OCRL_CHECK_LAUNCH("mae_gelu_fwd");
     return 0;
 }
 
 int mae_gelu_bwd_launch(const float* dy, const float* pre, float* dpre, long long n, hipStream_t st) {
-    OCRL_REQUIRE(n % 4 == 0 && al16(pre) && al16(dy) && al16(dpre), "mae_gelu: n %% 4 == 0 and 16-byte aligned buffers");
+    OCRL_REQUIRE(n % 4 == 0 && aligned16(pre, dy, dpre), "mae_gelu: n %% 4 == 0 and 16-byte aligned buffers");
     hipLaunchKernelGGL(mae_gelu_bwd_kernel, GRID1D(n / 4), 0, st, dy, pre, dpre, n / 4);
     OCRL_CHECK_LAUNCH("mae_gelu_bwd");
     return 0;
 }
 
 int mae_ln_fwd_launch(const float* x, const float* g, const float* b, float* y, float* mean, float* rstd, long long R, int F, float eps, hipStream_t st) {
-    OCRL_REQUIRE(F >= 4 && F % 4 == 0 && al16(x) && al16(g) && al16(b) && al16(y), "mae_ln: F %% 4 == 0 and 16-byte aligned rows (F = %d)", F);
+    OCRL_REQUIRE(F >= 4 && F % 4 == 0 && aligned16(x, g, b, y), "mae_ln: F %% 4 == 0 and 16-byte aligned rows (F = %d)", F);
     hipLaunchKernelGGL(mae_ln_fwd_kernel, dim3(cdiv(R, 4)), dim3(256), 0, st, x, g, b, y, mean, rstd, R, F / 4, eps);
     OCRL_CHECK_LAUNCH("mae_ln_fwd");
     return 0;
@@ -392,7 +382,7 @@ int mae_ln_chunks(long long R) {
 
 int mae_ln_bwd_launch(const float* dy, const float* x, const float* mean, const float* rstd, const float* g, const float* resid, float* dx, float* dg,
                       float* db, float* part, long long R, int F, hipStream_t st) {
-    OCRL_REQUIRE(F >= 4 && F % 4 == 0 && al16(x) && al16(g) && al16(dy) && al16(dx) && (!resid || al16(resid)),
+    OCRL_REQUIRE(F >= 4 && F % 4 == 0 && aligned16(x, g, dy, dx, resid),
                  "mae_ln: F %% 4 == 0 and 16-byte aligned rows (F = %d)", F);
     hipLaunchKernelGGL(mae_ln_bwd_kernel, dim3(cdiv(R, 4)), dim3(256), 0, st, dy, x, mean, rstd, g, resid, dx, R, F / 4);
     OCRL_CHECK_LAUNCH("mae_ln_bwd");

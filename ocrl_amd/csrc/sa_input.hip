@@ -4,8 +4,9 @@
 // reduction tails backward (12 passes).  Here a workgroup walks 64-row tiles: the forward reads e4 and writes h1 and x (3 passes), the
 // backward reads dx, h1, e4 and writes d e4 (4 passes); LN(e4) is rebuilt from e4, mean and rstd, and d h1 / d LN never leave LDS.
 //
-// Bitwise contract.  mean, rstd, h1, x and d e4 equal what layernorm_fwd64_kernel / gemm_kernel / layernorm_bwd64_kernel produce:
-//   * the LayerNorm arithmetic is theirs (16 lanes per row, float4 per lane, the xor-shuffle sum inside the group, the same expressions);
+// Bitwise contract.  mean, rstd, h1, x and d e4 equal what layernorm16_fwd_kernel<1, 4> / gemm_kernel / layernorm16_bwd_kernel<1, 4> produce:
+//   * the LayerNorm arithmetic is theirs: the same 16 lanes per row and float4 per lane, and the row functions of layernorm16.h that
+//     those kernels call are the ones called here;
 //   * every product is a K = 64 dot product accumulated from zero on v_mfma_f32_32x32x2_f32 over chunks c = 0..7 and steps s = 0..3,
 //     MFMA step (c, s) taking k = 8c + s from lanes 0..31 and k = 8c + 4 + s from lanes 32..63 -- gemm_kernel's order, in which the tile
 //     shape does not enter -- followed by gemm_kernel's epilogue expressions.
@@ -18,17 +19,12 @@
 // leaves them as one slab of SA_INPUT_SLAB floats per workgroup; sa_input_reduce_kernel sums the slabs in a fixed order (no atomics).
 #include "common.h"
 #include "kernels.h"
+#include "layernorm16.h"
 
 #define SAI_TR 64                 // rows per tile
 #define SAI_LD 68                 // LDS row stride of a tile: float4 rows stay aligned, 8 consecutive rows cover the banks
 #define SAI_MAX_WGS 512           // backward: two workgroups on each of the 256 CUs (256 VGPRs, 75 KB of LDS)
 #define SAI_FWD_MAX_WGS 768       // forward: three (168 VGPRs, 34 KB)
-
-__device__ __forceinline__ float sai_group16_sum(float v) {
-#pragma unroll
-    for (int o = 1; o < 16; o <<= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 // float4 c4 of row `row` of a [R,64] tensor, zero past the end.  The load itself is unconditional (from the last row when past the end):
 // a branch around it would keep the prefetch registers of the callers in scratch memory.
@@ -96,15 +92,14 @@ __global__ __launch_bounds__(256, 3) void sa_input_fwd_kernel(const float* __res
     for (int i = 0; i < 4; ++i) v[i] = sai_ld4(e4, (long long)blockIdx.x * SAI_TR + lr0 + 4 * i, R, c4);
     for (long long tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         const long long r0 = tile * SAI_TR;
-        // ---- LayerNorm (layernorm_fwd64_kernel's arithmetic) -> At
+        // ---- LayerNorm -> At
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int lr = lr0 + 4 * i;
             const long long row = r0 + lr;
-            const float mu = sai_group16_sum((v[i].x + v[i].y) + (v[i].z + v[i].w)) * (1.0f / 64);
-            const float4 dd = make_float4(v[i].x - mu, v[i].y - mu, v[i].z - mu, v[i].w - mu);
-            const float rs = rsqrtf(sai_group16_sum((dd.x * dd.x + dd.y * dd.y) + (dd.z * dd.z + dd.w * dd.w)) * (1.0f / 64) + 1e-5f);
-            const float4 y = make_float4(dd.x * rs * gg.x + bb.x, dd.y * rs * gg.y + bb.y, dd.z * rs * gg.z + bb.z, dd.w * rs * gg.w + bb.w);
+            float mu, rs;
+            layernorm16_row_fwd<1>(&v[i], mu, rs);
+            const float4 y = layernorm16_affine(v[i], rs, gg, bb);
             *reinterpret_cast<float4*>(At + lr * SAI_LD + c4 * 4) = y;
             if (row < R) {
                 if (ln0) *reinterpret_cast<float4*>(ln0 + row * 64 + c4 * 4) = y;
@@ -249,8 +244,7 @@ __global__ __launch_bounds__(256, 2) void sa_input_bwd_kernel(const float* __res
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const float4 dd = make_float4(xe[i].x - mu[i], xe[i].y - mu[i], xe[i].z - mu[i], xe[i].w - mu[i]);
-            *reinterpret_cast<float4*>(T1 + (lr0 + 4 * i) * SAI_LD + c4 * 4) =
-                make_float4(dd.x * rs[i] * gg.x + bb.x, dd.y * rs[i] * gg.y + bb.y, dd.z * rs[i] * gg.z + bb.z, dd.w * rs[i] * gg.w + bb.w);
+            *reinterpret_cast<float4*>(T1 + (lr0 + 4 * i) * SAI_LD + c4 * 4) = layernorm16_affine(dd, rs[i], gg, bb);
         }
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[r] = 0.f;
@@ -268,23 +262,14 @@ __global__ __launch_bounds__(256, 2) void sa_input_bwd_kernel(const float* __res
         __syncthreads();
         // ---- dW0 += d h1^T ln0
         sai_mma_rows(T2 + wm0, T1 + wn0, dW0a);
-        // ---- d e4 (layernorm_bwd64_kernel's arithmetic)
+        // ---- d e4
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int lr = lr0 + 4 * i;
             const long long row = r0 + lr;
             const float4 yv = *reinterpret_cast<const float4*>(T0 + lr * SAI_LD + c4 * 4);
-            const float4 xh = make_float4((xe[i].x - mu[i]) * rs[i], (xe[i].y - mu[i]) * rs[i], (xe[i].z - mu[i]) * rs[i], (xe[i].w - mu[i]) * rs[i]);
-            dg.x += yv.x * xh.x; dg.y += yv.y * xh.y; dg.z += yv.z * xh.z; dg.w += yv.w * xh.w;
-            db.x += yv.x; db.y += yv.y; db.z += yv.z; db.w += yv.w;
-            const float4 d4 = make_float4(yv.x * gg.x, yv.y * gg.y, yv.z * gg.z, yv.w * gg.w);
-            const float s1 = sai_group16_sum((d4.x + d4.y) + (d4.z + d4.w)) * (1.0f / 64);
-            const float s2 = sai_group16_sum((d4.x * xh.x + d4.y * xh.y) + (d4.z * xh.z + d4.w * xh.w)) * (1.0f / 64);
-            if (row < R) {
-                const float4 o = make_float4(rs[i] * (d4.x - s1 - xh.x * s2), rs[i] * (d4.y - s1 - xh.y * s2), rs[i] * (d4.z - s1 - xh.z * s2),
-                                             rs[i] * (d4.w - s1 - xh.w * s2));
-                *reinterpret_cast<float4*>(de4 + row * 64 + c4 * 4) = o;
-            }
+            const Ln16Bwd<1> r = layernorm16_row_bwd<1>(&xe[i], &yv, mu[i], rs[i], &gg, &dg, &db);
+            if (row < R) *reinterpret_cast<float4*>(de4 + row * 64 + c4 * 4) = layernorm16_row_dx(r, rs[i], 0);
         }
     }
     // ---- the workgroup's slab
@@ -336,8 +321,6 @@ __global__ __launch_bounds__(256) void sa_input_reduce_kernel(const float* __res
     }
 }
 
-static bool sai_al16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
-
 void sa_input_plan(long long R, int max_wgs, int out[3]) {
     const long long ntiles = (R + SAI_TR - 1) / SAI_TR;
     long long wgs = max_wgs > 0 && max_wgs < SAI_MAX_WGS ? max_wgs : SAI_MAX_WGS;
@@ -349,8 +332,7 @@ int sa_input_fwd_launch(const float* e4, const float* gamma, const float* beta, 
                         float* mean, float* rstd, float* ln0, float* h1, float* x, long long R, int max_wgs, hipStream_t st) {
     OCRL_REQUIRE(R > 0, "sa_input_fwd: no rows");
     OCRL_REQUIRE(e4 && gamma && beta && W0 && b0 && W2 && b2 && mean && rstd && h1 && x, "sa_input_fwd: null argument");
-    OCRL_REQUIRE(sai_al16(e4) && sai_al16(gamma) && sai_al16(beta) && sai_al16(W0) && sai_al16(W2) && sai_al16(ln0) && sai_al16(h1) && sai_al16(x),
-                 "sa_input_fwd: tensors must be 16-byte aligned");
+    OCRL_REQUIRE(aligned16(e4, gamma, beta, W0, W2, ln0, h1, x), "sa_input_fwd: tensors must be 16-byte aligned");
     const long long ntiles = (R + SAI_TR - 1) / SAI_TR;
     long long wgs = max_wgs > 0 && max_wgs < SAI_FWD_MAX_WGS ? max_wgs : SAI_FWD_MAX_WGS;
     if (wgs > ntiles) wgs = ntiles;
@@ -365,8 +347,7 @@ int sa_input_bwd_launch(const float* dx, const float* h1, const float* e4, const
     OCRL_REQUIRE(R > 0, "sa_input_bwd: no rows");
     OCRL_REQUIRE(dx && h1 && e4 && mean && rstd && gamma && beta && W0 && W2 && de4 && dW0 && db0 && dW2 && db2 && dgamma && dbeta && ws,
                  "sa_input_bwd: null argument");
-    OCRL_REQUIRE(sai_al16(dx) && sai_al16(h1) && sai_al16(e4) && sai_al16(gamma) && sai_al16(beta) && sai_al16(W0) && sai_al16(de4) && sai_al16(ws),
-                 "sa_input_bwd: tensors must be 16-byte aligned");
+    OCRL_REQUIRE(aligned16(dx, h1, e4, gamma, beta, W0, de4, ws), "sa_input_bwd: tensors must be 16-byte aligned");
     int plan[3];
     sa_input_plan(R, max_wgs, plan);
     OCRL_REQUIRE((size_t)plan[1] * SA_INPUT_SLAB <= ws_floats, "sa_input_bwd: workspace too small (%d slabs of %d floats)", plan[1], SA_INPUT_SLAB);

@@ -62,10 +62,7 @@ __global__ __launch_bounds__(256) void vae_kl_fwd_kernel(const float* __restrict
     }
     red[threadIdx.x] = s;
     __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {                               // fixed tree
-        if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-        __syncthreads();
-    }
+    block_tree_sum<256>(red);
     if (threadIdx.x == 0) part[b] = -0.5f * red[0];
 }
 

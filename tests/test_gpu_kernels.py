@@ -220,8 +220,24 @@ def test_conv_bwd_weight(L, B, S, cin, ks):
     assert e < TOL and eb < TOL
 
 
-@pytest.mark.parametrize("R,Fd", [(1000, 64), (517, 192), (12, 192), (4096, 128)])
-def test_layernorm(L, R, Fd):
+def off_view(t, off):
+    """a copy of t on the GPU that starts `off` floats into its allocation (off = 1: 4-byte aligned only)"""
+    buf = torch.empty(t.numel() + off, device="cuda")
+    v = buf[off:].view(t.shape)
+    v.copy_(t)
+    return v
+
+
+# the 16-lane kernels take 64 rows (F = 64) or 32 rows (F = 192) per workgroup and pass: row counts on both sides of one; 256 is the
+# width only the one-wave-per-row form serves; "unaligned": x, y, dy, dx start one float into their allocation, for which the launchers
+# are written to take the one-wave-per-row form at 64 and 192 too.  The case checks the result at such pointers against fp64 at the same
+# bar (the two forms sum in different orders, so they are not compared bitwise); it cannot tell which kernel the launcher picked.
+LAYERNORM_CASES = [(1000, 64, 0), (517, 192, 0), (12, 192, 0), (4096, 128, 0),
+                   (1, 64, 0), (63, 64, 0), (65, 64, 0), (1, 192, 0), (31, 192, 0), (33, 192, 0), (5, 256, 0), (65, 64, 1), (33, 192, 1)]
+
+
+@pytest.mark.parametrize("R,Fd,off", LAYERNORM_CASES, ids=[f"{r}-{f}" + ("-unaligned" if o else "") for r, f, o in LAYERNORM_CASES])
+def test_layernorm(L, R, Fd, off):
     g = torch.Generator().manual_seed(R + Fd)
     x = (torch.randn(R, Fd, generator=g) * 2 + 0.5).double().requires_grad_(True)
     gam = (1 + 0.2 * torch.randn(Fd, generator=g)).double().requires_grad_(True)
@@ -229,18 +245,19 @@ def test_layernorm(L, R, Fd):
     dy = torch.randn(R, Fd, generator=g)
     y = F.layer_norm(x, (Fd,), gam, bet)
     y.backward(dy.double())
-    xd, gd, bd, dyd = dev(x.detach().float()), dev(gam.detach().float()), dev(bet.detach().float()), dev(dy)
-    yo = torch.empty(R, Fd, device="cuda")
+    xd, gd, bd, dyd = off_view(x.detach().float(), off), dev(gam.detach().float()), dev(bet.detach().float()), off_view(dy, off)
+    yo = off_view(torch.zeros(R, Fd), off)
     mean = torch.empty(R, device="cuda")
     rstd = torch.empty(R, device="cuda")
+    assert all(t.data_ptr() % 16 == 4 * off for t in (xd, dyd, yo))
     L.check(L.lib().ocrl_layernorm_fwd(P(xd), P(gd), P(bd), P(yo), P(mean), P(rstd), R, Fd, None))
-    dx = torch.empty(R, Fd, device="cuda")
+    dx = off_view(torch.zeros(R, Fd), off)
     dgb = torch.empty(2 * Fd, device="cuda")
     ws = torch.empty(1 << 20, device="cuda")
     L.check(L.lib().ocrl_layernorm_bwd(P(dyd), P(xd), P(mean), P(rstd), P(gd), P(dx), P(dgb), R, Fd, P(ws), ws.numel(), None))
     torch.cuda.synchronize()
     e = [relerr(yo.cpu(), y), relerr(dx.cpu(), x.grad), relerr(dgb[:Fd].cpu(), gam.grad), relerr(dgb[Fd:].cpu(), bet.grad)]
-    log(f"layernorm R{R} F{Fd}: y {e[0]:.2e} dx {e[1]:.2e} dgamma {e[2]:.2e} dbeta {e[3]:.2e}")
+    log(f"layernorm R{R} F{Fd} off{off}: y {e[0]:.2e} dx {e[1]:.2e} dgamma {e[2]:.2e} dbeta {e[3]:.2e}")
     assert max(e) < TOL
 
 
