@@ -497,8 +497,8 @@ int ocrl_acnet_act_uniforms(unsigned long long seed, unsigned long long row_offs
 int ocrl_gae(const float* rewards, const float* values, const float* episode_starts, const float* last_values, const float* dones,
              float* advantages, float* returns, int T, int E, float gamma, float gae_lambda, void* stream);
 
-/* ---- sprite environments: the Target task (envs/synthetic_envs/base.py:81-151, 291-360 and target.py:16-57, restated) as a vectorised
- *      environment whose state, transition, reward, auto-reset and frames stay on the device.  Stateless: the caller owns `state`
+/* ---- sprite environments: the Target and Odd-One-Out tasks (envs/synthetic_envs/base.py:81-151, 291-360, target.py:16-57 and
+ *      oddoneout.py:19-126, restated) as a vectorised environment whose state, transition, reward, auto-reset and frames stay on the device.  Stateless: the caller owns `state`
  *      (ocrl_sprite_env_state_floats floats, 256-byte aligned, zero before the first reset) and every output; everything is enqueued on
  *      `stream` with no host synchronisation, no atomics and no unbounded loop; reset and step run one thread per environment.
  * desc: E environments, H x H frames (H a multiple of 4 in [8, 512]); num_objects_range [lo, hi], 1 <= lo <= hi <= 15 (easy mode: within
@@ -506,8 +506,9 @@ int ocrl_gae(const float* rewards, const float* values, const float* episode_sta
  *   triangle, star_4, circle (the other names of the reference's list are not drawn and are rejected); scales in (0, 1).  Anything else
  *   is rejected: state_floats == 0, the other entry points return non-zero, with a message.
  * state: rows [E, hi + 1, 5] fp32 = (colour id, shape id, scale, x, y): objects 0..n-1, the agent in row n, zero rows after it; then,
- *   at the next multiple of 64 floats, 8 int32 words per environment: n, target index, step_count, episode index, episode length, 0, and
- *   the episode's return so far as one double.
+ *   at the next multiple of 64 floats, 8 int32 words per environment: n, target index, step_count, episode index, episode length, the
+ *   unique property kind of an Odd-One-Out episode (0 colour, 1 shape, 2 scale; 0 for Target), and the episode's return so far as one
+ *   double.
  * The draws.  u(seed, e, k, j) = the top 24 bits of the library's counter RNG at site 500 and counter (e << 44) | ((k mod 2^24) << 20) | j:
  *   draw j of episode k of environment e is a function of (seed, e, k, j) alone, whatever E is and whenever the episode began.  An integer
  *   in [0, m) is (bits24 * m) >> 24; a position in [a, b] is a + (b - a) * (bits24 / 2^24), each operation rounded to fp32 (no FMA).
@@ -518,6 +519,24 @@ int ocrl_gae(const float* rewards, const float* values, const float* episode_sta
  *   a threshold to an object placed before it (r + r_j + dist_objs) or to the agent (r + r_agent + dist_agent), 0.15 for both with
  *   `occlusion`.  An object takes at most 256 candidates; then the whole placement starts over on the draws that follow, at most 8
  *   times, and on the last attempt the 256th candidate stands.  The agent starts at agent_x, agent_y (hard mode) or (0.5, 0.5).
+ * The Odd-One-Out episode (task 1; target_* is ignored).  One object, `target`, carries a value u of one property kind T that no other
+ *   object has; every other value of every kind is shared by at least two objects.  below(m) is the integer draw in [0, m) above and takes
+ *   exactly one draw, also when m = 1; list_K / n_K are the desc's COLORS, SHAPES, SCALES in the order colour, shape, scale.  The draws:
+ *   1. n = lo + below(hi - lo + 1).
+ *   2. target = below(n); in an unseen mode target = 0 and no draw is taken.
+ *   3. kinds = the K with n_K > 1, in order; T = kinds[below(len(kinds))].
+ *   4. u = list_T[below(n_T)]; in unseen test mode u = unseen_colors[below(2)].  Object `target` gets u in kind T.
+ *   5. with obj_comp: for each K != T in order, v_K = list_K[below(n_K)] is given to all n objects.
+ *   6. for K = colour, shape, scale: fill the objects without a value of kind K: for K = T all but `target`; for K != T all n, or none
+ *      under obj_comp (no draw then).  The admissible list A is list_K in desc order; for K = T without u, in unseen train mode with u
+ *      one of the two unseen colours also without the other one, and in unseen test mode exactly the other one.  While z objects are
+ *      unfilled, z > 0: v = A[below(len(A))], g = 2 + below(z - 1), then g times v goes to the below(z')-th still unfilled object in
+ *      index order (z' the count at that moment); if exactly one object is then left, it takes v too, without a draw.
+ *   7. positions exactly as in the Target episode.
+ *   These are the reference's distributions with its rejection loops written as draws from the admissible set, so every loop is bounded
+ *   (at most 6 + 6 n draws before the positions).  Rejected for task 1: lo < 3, no list with more than one entry, equal entries within a
+ *   list; for an unseen mode also n_shapes != 1, n_scales != 1, n_colors < 3, and unseen colours that are equal or not both in COLORS
+ *   (the reference's unseen modes do not terminate when the unique kind is not the colour).  Task 0 takes no obj_comp or unseen_mode.
  * _reset: every environment, or those with mask[e] != 0.  episode >= 0 starts that episode index, -1 the one after the state's own.
  * _step: actions int64 [E]: 0 y += step_size, 1 x -= step_size, 2 y -= step_size, 3 x += step_size, anything else no move; x, y clipped
  *   to [r_agent, 1 - r_agent]; step_count + 1 >= max_steps ends the episode; rew_type 2 (dense) pays +-0.01 by whether the distance to the
@@ -545,6 +564,10 @@ typedef struct {
     int agent_color, agent_shape;
     float agent_scale, agent_x, agent_y;
     float step_size, dist_agent, dist_objs, dist_wall;
+    int task;                                   /* 0 Target, 1 Odd-One-Out; a zeroed tail from here on is the Target task */
+    int obj_comp;                               /* Odd-One-Out: the kinds other than the unique one are constant over the objects */
+    int unseen_mode;                            /* 0 none, 1 train (never the unseen pair), 2 test (always the unseen pair) */
+    int unseen_colors[2];                       /* colour ids of the unseen combination */
 } ocrl_sprite_env_desc;
 size_t ocrl_sprite_env_desc_size(void);
 size_t ocrl_sprite_env_state_floats(const ocrl_sprite_env_desc* d);

@@ -60,7 +60,8 @@ class SpriteEnvDesc(ctypes.Structure):
     _fields_ = [(n, c_int) for n in ("E", "H", "lo", "hi", "mode", "rew_type", "occlusion", "max_steps", "n_colors", "n_shapes", "n_scales")] + \
                [("colors", c_int * 8), ("shapes", c_int * 8), ("scales", c_float * 8), ("target_color", c_int), ("target_shape", c_int),
                 ("target_scale", c_float), ("agent_color", c_int), ("agent_shape", c_int)] + \
-               [(n, c_float) for n in ("agent_scale", "agent_x", "agent_y", "step_size", "dist_agent", "dist_objs", "dist_wall")]
+               [(n, c_float) for n in ("agent_scale", "agent_x", "agent_y", "step_size", "dist_agent", "dist_objs", "dist_wall")] + \
+               [("task", c_int), ("obj_comp", c_int), ("unseen_mode", c_int), ("unseen_colors", c_int * 2)]
 
 
 def acnet_desc(B, F, A, dims, acts):

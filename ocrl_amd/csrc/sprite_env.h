@@ -5,11 +5,11 @@
 
 #define SITE_SPRITE_ENV 500u        // rng site of an episode's draws (acnet.h has 400, pool_unit.cpp 300 .. 399)
 #define SPRITE_MAX_ROWS (OCRL_SPRITE_MAX_OBJECTS + 1)
-#define SPRITE_AUX 8                // int32 words per environment after the rows: n, target, step_count, episode, ep_length, -, ep_return (double)
+#define SPRITE_AUX 8                // int32 words per environment after the rows: n, target, step_count, episode, ep_length, unique kind, ep_return (double)
 #define SPRITE_TRIPLE_TRIES 64      // redraws of a non-target's (colour, shape, scale) before the last one stands
 #define SPRITE_CANDIDATES 256       // position candidates per object
 #define SPRITE_RESTARTS 8           // whole-placement restarts before a dead-ended object keeps its last candidate
-#define SPRITE_MAX_DRAWS (1 << 20)  // draw indices of one episode: 2 + 15 * 64 * 3 + 9 * 15 * 256 * 2 = 72 002 are ever used
+#define SPRITE_MAX_DRAWS (1 << 20)  // draw indices of one episode: 2 + 15 * 64 * 3 + 9 * 15 * 256 * 2 = 72 002 are ever used (Odd-One-Out: fewer)
 
 // where the pieces of a state buffer lie (floats from its start)
 struct SpriteLay {

@@ -1,5 +1,5 @@
-// The Target sprite task (envs/synthetic_envs/{base,target}.py restated) as a vectorised environment: state, transition, reward, auto-reset
-// and rendering on the device.  reset / step: one thread per environment (an episode's draws are a serial rejection chain).  render: the
+// The Target and Odd-One-Out sprite tasks (envs/synthetic_envs/{base,target,oddoneout}.py restated) as a vectorised environment: state,
+// transition, reward, auto-reset and rendering on the device; the tasks differ in how an episode's objects are made, nothing else.  reset / step: one thread per environment (an episode's draws are a serial rejection chain).  render: the
 // only part with bytes to move; a workgroup takes a row band of one environment, keeps the sprite table in LDS and writes 4 pixels of a
 // channel plane per 32-bit store.  No atomics; every loop is bounded.  Compiled with -ffp-contract=off: each position is the written
 // sequence of fp32 roundings, so a numpy fp32 restatement (tests/sprite_env_ref.py) follows it bit for bit.
@@ -57,13 +57,9 @@ __device__ inline float dist2d(float ax, float ay, float bx, float by) {
     return sqrtf(xx + yy);
 }
 
-// a new episode of environment e into its rows (R x 5) and aux words
-__device__ void new_episode(const ocrl_sprite_env_desc& d, float* __restrict__ q, int* __restrict__ aux, unsigned long long seed, uint32_t e, uint32_t k) {
-    const int R = d.hi + 1;
-    Stream s{seed, e, k, 0u};
-    const int n = d.lo + s.below(d.hi - d.lo + 1);
+// the Target episode's objects: the target index, then every other object's triple, redrawn while it equals the target's -> target
+__device__ int target_objects(const ocrl_sprite_env_desc& d, Stream& s, int n, float* col, float* shp, float* scl) {
     const int target = s.below(n);
-    float col[SPRITE_MAX_ROWS], shp[SPRITE_MAX_ROWS], scl[SPRITE_MAX_ROWS], px[SPRITE_MAX_ROWS], py[SPRITE_MAX_ROWS];
     for (int i = 0; i < n; ++i) {
         int c = d.target_color, h = d.target_shape;
         float z = d.target_scale;
@@ -75,8 +71,80 @@ __device__ void new_episode(const ocrl_sprite_env_desc& d, float* __restrict__ q
                 if (!(c == d.target_color && h == d.target_shape && z == d.target_scale)) break;
             }
         }
-        col[i] = (float)c; shp[i] = (float)h; scl[i] = z; px[i] = 0.f; py[i] = 0.f;
+        col[i] = (float)c; shp[i] = (float)h; scl[i] = z;
     }
+    return target;
+}
+
+// rule 6 of the Odd-One-Out episode: the objects of `todo` (a bit each) take values of A in groups of at least two
+__device__ inline void ooo_fill(Stream& s, uint32_t todo, const float* A, int nA, float* out) {
+    int z = __popc(todo);
+    while (z > 0) {                                            // every round fills at least two objects, or the last one
+        const float v = A[s.below(nA)];
+        int g = 2 + s.below(z - 1);
+        g = g > z ? z : g;                                     // z == 1 cannot begin a round (lo >= 3); it must not index outside either
+        for (; g > 0; --g, --z) {
+            uint32_t m = todo;
+            for (int r = s.below(z); r > 0; --r) m &= m - 1;   // the r-th object still unfilled, in index order
+            const int i = __ffs(m) - 1;
+            out[i] = v;
+            todo &= ~(1u << i);
+        }
+        if (z == 1) { out[__ffs(todo) - 1] = v; todo = 0u; z = 0; }
+    }
+}
+
+// the Odd-One-Out episode's objects (oddoneout.py:19-126 as the header's rules 2 to 6) -> target; prop = colour, shape, scale rows
+__device__ int ooo_objects(const ocrl_sprite_env_desc& d, Stream& s, int n, int& kind, float (*prop)[SPRITE_MAX_ROWS]) {
+    float list[3][8];
+    const int cnt[3] = {d.n_colors, d.n_shapes, d.n_scales};
+    for (int i = 0; i < 8; ++i) { list[0][i] = (float)d.colors[i]; list[1][i] = (float)d.shapes[i]; list[2][i] = d.scales[i]; }
+    const int target = d.unseen_mode ? 0 : s.below(n);
+    int kinds[3] = {0, 0, 0}, nk = 0;
+    for (int K = 0; K < 3; ++K)
+        if (cnt[K] > 1) kinds[nk++] = K;
+    const int T = kinds[s.below(nk)];
+    const float u = d.unseen_mode == 2 ? (float)d.unseen_colors[s.below(2)] : list[T][s.below(cnt[T])];
+    prop[T][target] = u;
+    if (d.obj_comp)
+        for (int K = 0; K < 3; ++K) {
+            if (K == T) continue;
+            const float v = list[K][s.below(cnt[K])];
+            for (int i = 0; i < n; ++i) prop[K][i] = v;
+        }
+    const uint32_t all = (1u << n) - 1u;
+    const float c0 = (float)d.unseen_colors[0], c1 = (float)d.unseen_colors[1];
+    const bool paired = d.unseen_mode != 0 && T == 0 && (u == c0 || u == c1);
+    const float other = u == c0 ? c1 : c0;
+    for (int K = 0; K < 3; ++K) {
+        if (K != T) {
+            if (!d.obj_comp) ooo_fill(s, all, list[K], cnt[K], prop[K]);
+            continue;
+        }
+        float A[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        int nA = 0;
+        for (int i = 0; i < cnt[K]; ++i) {
+            const float v = list[K][i];
+            bool ok = v != u;
+            if (paired) ok = ok && (d.unseen_mode == 1 ? v != other : v == other);
+            if (ok) A[nA++] = v;
+        }
+        ooo_fill(s, all & ~(1u << target), A, nA, prop[K]);
+    }
+    kind = T;
+    return target;
+}
+
+// a new episode of environment e into its rows (R x 5) and aux words
+__device__ void new_episode(const ocrl_sprite_env_desc& d, float* __restrict__ q, int* __restrict__ aux, unsigned long long seed, uint32_t e, uint32_t k) {
+    const int R = d.hi + 1;
+    Stream s{seed, e, k, 0u};
+    const int n = d.lo + s.below(d.hi - d.lo + 1);
+    float prop[3][SPRITE_MAX_ROWS], px[SPRITE_MAX_ROWS], py[SPRITE_MAX_ROWS];
+    float *col = prop[0], *shp = prop[1], *scl = prop[2];
+    int kind = 0;
+    const int target = d.task == 1 ? ooo_objects(d, s, n, kind, prop) : target_objects(d, s, n, col, shp, scl);
+    for (int i = 0; i < n; ++i) { px[i] = 0.f; py[i] = 0.f; }
     const float ax = d.mode == 2 ? d.agent_x : 0.5f, ay = d.mode == 2 ? d.agent_y : 0.5f;
     const float ra = d.agent_scale * 0.5f;
     for (int attempt = 0; attempt <= SPRITE_RESTARTS; ++attempt) {
@@ -109,7 +177,7 @@ __device__ void new_episode(const ocrl_sprite_env_desc& d, float* __restrict__ q
         else if (i == n) { v[0] = (float)d.agent_color; v[1] = (float)d.agent_shape; v[2] = d.agent_scale; v[3] = ax; v[4] = ay; }
         for (int c = 0; c < 5; ++c) q[i * 5 + c] = v[c];
     }
-    aux[0] = n; aux[1] = target; aux[2] = 0; aux[3] = (int)k; aux[4] = 0; aux[5] = 0;
+    aux[0] = n; aux[1] = target; aux[2] = 0; aux[3] = (int)k; aux[4] = 0; aux[5] = kind;
     *reinterpret_cast<double*>(aux + 6) = 0.0;
 }
 

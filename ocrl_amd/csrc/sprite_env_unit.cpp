@@ -1,10 +1,11 @@
-// C ABI of the sprite environments (include/ocrl_hip.h: ocrl_sprite_*): the Target task of envs/synthetic_envs/{base,target}.py as a
-// vectorised environment.  Stateless: the caller owns the state buffer (ocrl_sprite_env_state_floats floats) and every output.
+// C ABI of the sprite environments (include/ocrl_hip.h: ocrl_sprite_*): the Target and Odd-One-Out tasks of
+// envs/synthetic_envs/{base,target,oddoneout}.py as a vectorised environment.  Stateless: the caller owns the state buffer (ocrl_sprite_env_state_floats floats) and every output.
 #include "sprite_env.h"
 
 namespace {
 int check_env(const ocrl_sprite_env_desc* d, const char* who) {
     OCRL_REQUIRE(d, "%s: null descriptor", who);
+    OCRL_REQUIRE(d->task >= 0 && d->task <= 1, "%s: task 0 (Target) or 1 (Odd-One-Out) (got %d)", who, d->task);
     OCRL_REQUIRE(d->E >= 1 && d->E < (1 << 20), "%s: 1 <= environments < 2^20 (got %d)", who, d->E);
     OCRL_REQUIRE(d->H >= 8 && d->H <= 512 && d->H % 4 == 0, "%s: obs_size must be a multiple of 4 in [8, 512] (got %d)", who, d->H);
     OCRL_REQUIRE(d->lo >= 1 && d->lo <= d->hi && d->hi <= OCRL_SPRITE_MAX_OBJECTS, "%s: num_objects_range [lo, hi] needs 1 <= lo <= hi <= %d (got [%d, %d])",
@@ -16,21 +17,48 @@ int check_env(const ocrl_sprite_env_desc* d, const char* who) {
     OCRL_REQUIRE(d->max_steps >= 1, "%s: max_steps >= 1 (got %d)", who, d->max_steps);
     OCRL_REQUIRE(d->n_colors >= 1 && d->n_colors <= 8 && d->n_shapes >= 1 && d->n_shapes <= 8 && d->n_scales >= 1 && d->n_scales <= 8,
                  "%s: 1 to 8 COLORS, SHAPES and SCALES each (got %d, %d, %d)", who, d->n_colors, d->n_shapes, d->n_scales);
+    const bool targeted = d->task != 1;                          // the Odd-One-Out task ignores target_*
     for (int i = 0; i < d->n_colors + 2; ++i) {
+        if (i == d->n_colors && !targeted) continue;
         const int c = i < d->n_colors ? d->colors[i] : (i == d->n_colors ? d->target_color : d->agent_color);
         OCRL_REQUIRE(c >= 0 && c < 7, "%s: colour id %d is not one of the 7 colours", who, c);
     }
     for (int i = 0; i < d->n_shapes + 2; ++i) {
+        if (i == d->n_shapes && !targeted) continue;
         const int s = i < d->n_shapes ? d->shapes[i] : (i == d->n_shapes ? d->target_shape : d->agent_shape);
         OCRL_REQUIRE(s >= 0 && s < 4, "%s: shape id %d is not drawn (0 square, 1 triangle, 2 star_4, 3 circle)", who, s);
     }
     for (int i = 0; i < d->n_scales + 2; ++i) {
+        if (i == d->n_scales && !targeted) continue;
         const float z = i < d->n_scales ? d->scales[i] : (i == d->n_scales ? d->target_scale : d->agent_scale);
         OCRL_REQUIRE(z > 0.f && z < 1.f, "%s: scales lie in (0, 1) (got %g)", who, (double)z);
     }
     OCRL_REQUIRE(d->agent_x >= 0.f && d->agent_x <= 1.f && d->agent_y >= 0.f && d->agent_y <= 1.f, "%s: agent_pos lies in [0, 1]^2", who);
     OCRL_REQUIRE(d->step_size > 0.f && d->dist_agent >= 0.f && d->dist_objs >= 0.f && d->dist_wall >= 0.f,
                  "%s: moving_step_size > 0 and the three distances >= 0", who);
+    OCRL_REQUIRE(d->unseen_mode >= 0 && d->unseen_mode <= 2, "%s: unseen_mode 0 (none), 1 (train) or 2 (test) (got %d)", who, d->unseen_mode);
+    if (d->task == 0) {
+        OCRL_REQUIRE(d->obj_comp == 0 && d->unseen_mode == 0, "%s: obj_comp and unseen_mode belong to task 1 (Odd-One-Out) (got %d, %d with task 0)", who,
+                     d->obj_comp, d->unseen_mode);
+        return 0;
+    }
+    OCRL_REQUIRE(d->lo >= 3, "%s: Odd-One-Out needs num_objects_range lo >= 3, two others must share a value (got %d)", who, d->lo);
+    OCRL_REQUIRE(d->n_colors > 1 || d->n_shapes > 1 || d->n_scales > 1,
+                 "%s: Odd-One-Out needs more than one entry in COLORS, SHAPES or SCALES to pick the odd value from", who);
+    for (int i = 0; i < 8; ++i)
+        for (int j = 0; j < i; ++j)
+            OCRL_REQUIRE(!(i < d->n_colors && d->colors[i] == d->colors[j]) && !(i < d->n_shapes && d->shapes[i] == d->shapes[j]) &&
+                             !(i < d->n_scales && d->scales[i] == d->scales[j]),
+                         "%s: Odd-One-Out needs distinct entries in COLORS, SHAPES and SCALES (entries %d and %d are equal)", who, j, i);
+    if (d->unseen_mode != 0) {
+        OCRL_REQUIRE(d->n_shapes == 1 && d->n_scales == 1, "%s: an unseen_mode needs one entry each in SHAPES and SCALES, the odd kind must be the colour (got %d, %d)",
+                     who, d->n_shapes, d->n_scales);
+        OCRL_REQUIRE(d->n_colors >= 3, "%s: an unseen_mode needs 3 or more COLORS (got %d)", who, d->n_colors);
+        int found = 0;
+        for (int i = 0; i < d->n_colors; ++i) found |= (d->colors[i] == d->unseen_colors[0] ? 1 : 0) | (d->colors[i] == d->unseen_colors[1] ? 2 : 0);
+        OCRL_REQUIRE(d->unseen_colors[0] != d->unseen_colors[1] && found == 3, "%s: unseen_colors must be two different entries of COLORS (got %d, %d)", who,
+                     d->unseen_colors[0], d->unseen_colors[1]);
+    }
     return 0;
 }
 }  // namespace

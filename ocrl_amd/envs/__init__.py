@@ -1,7 +1,7 @@
-"""Environments of the RL side (the reference's ``envs`` package): built here is the Target sprite task, vectorised on the GPU."""
-from .sprite import COLORS, SHAPES, TargetEnv, env_desc, sprite_env_uniforms
+"""Environments of the RL side (the reference's ``envs`` package): built here are the Target and Odd-One-Out sprite tasks, vectorised on the GPU."""
+from .sprite import COLORS, SHAPES, OddOneOutEnv, SpriteEnv, TargetEnv, env_desc, sprite_env_uniforms
 
-_ENVS = {"TargetEnv": TargetEnv}
+_ENVS = {"TargetEnv": TargetEnv, "OddOneOutEnv": OddOneOutEnv}
 
 
 def make_env(config, num_envs=None, seed=None, device=None):
@@ -14,4 +14,4 @@ def make_env(config, num_envs=None, seed=None, device=None):
                        config.device if device is None else device)
 
 
-__all__ = ["TargetEnv", "make_env", "env_desc", "sprite_env_uniforms", "COLORS", "SHAPES"]
+__all__ = ["TargetEnv", "OddOneOutEnv", "SpriteEnv", "make_env", "env_desc", "sprite_env_uniforms", "COLORS", "SHAPES"]

@@ -1,8 +1,8 @@
-"""The sprite tasks as vectorised environments that live on the GPU (the reference's envs/synthetic_envs/{base,target}.py run one
-spriteworld / PIL environment per host process).  State, transition, reward, auto-reset and frames are the library's
-(``ocrl_sprite_env_*`` / ``ocrl_sprite_render``, include/ocrl_hip.h: the rules are written there); this module checks the config, owns
-the buffers and offers both calling conventions: ``step`` (gym / VecEnv style, host rewards and infos) and ``step_device`` (device
-tensors only, no host read: what ``PPO.collect_rollouts`` uses)."""
+"""The sprite tasks (Target, Odd-One-Out) as vectorised environments that live on the GPU (the reference's
+envs/synthetic_envs/{base,target,oddoneout}.py run one spriteworld / PIL environment per host process).  State, transition, reward,
+auto-reset and frames are the library's (``ocrl_sprite_env_*`` / ``ocrl_sprite_render``, include/ocrl_hip.h: the rules are written
+there); this module checks the config, owns the buffers and offers both calling conventions: ``step`` (gym / VecEnv style, host rewards
+and infos) and ``step_device`` (device tensors only, no host read: what ``PPO.collect_rollouts`` uses)."""
 import ctypes
 
 import numpy as np
@@ -16,6 +16,8 @@ DRAWN_SHAPES = SHAPES[:4]                       # the predicates of ocrl_amd.uti
 COLOR_BYTES = ((0, 0, 255), (0, 255, 0), (255, 255, 0), (255, 0, 0), (0, 255, 255), (255, 192, 203), (165, 42, 42))
 MODES, REW_TYPES = ("easy", "normal", "hard"), ("sparse", "normal", "dense")
 RENDER_MODES = {"image": 0, "rgb_array": 1, "mask": 2}
+TASKS = {"TargetEnv": 0, "OddOneOutEnv": 1}     # config.env -> ocrl_sprite_env_desc.task
+UNSEEN_MODES = (None, "train", "test")
 
 try:                                            # gym's spaces when importable
     from gym.spaces import Box, Discrete
@@ -46,6 +48,10 @@ def env_desc(config, num_envs):
     """SpriteEnvDesc of an env config (configs/env/*.yaml).  Raises NotImplementedError, naming the key, for what is not built and
     ValueError for a name or a value outside the task's lists; touches neither the library nor the GPU."""
     who = "ocrl_amd.envs"
+    name = getattr(config, "env", "TargetEnv")
+    if name not in TASKS:
+        raise NotImplementedError(f"{who}: env: {name} is not built (built: {', '.join(TASKS)})")
+    task = TASKS[name]
     if getattr(config, "agent_pos", None) is None:
         raise NotImplementedError(f"{who}: agent_pos: null (a randomly placed agent) is not built; give agent_pos: [x, y]")
     for key in ("skewed", "wo_agent"):
@@ -76,7 +82,17 @@ def env_desc(config, num_envs):
     for i, v in enumerate(scales):
         d.scales[i] = v
     d.n_colors, d.n_shapes, d.n_scales = len(config.COLORS), len(config.SHAPES), len(scales)
-    d.target_color, d.target_shape, d.target_scale = _index(COLORS, config.target[0], "colour"), _index(SHAPES, config.target[1], "shape", DRAWN_SHAPES), float(config.target[2])
+    d.task = task
+    obj_comp, unseen = bool(getattr(config, "obj_comp", False)), getattr(config, "unseen_combi_mode", None)
+    if unseen not in UNSEEN_MODES:
+        raise ValueError(f"{who}: unseen_combi_mode {unseen!r} is not one of null, train, test")
+    if task == 0:
+        if obj_comp or unseen is not None:
+            raise ValueError(f"{who}: obj_comp and unseen_combi_mode belong to env: OddOneOutEnv, not to env: {name}")
+        d.target_color, d.target_shape, d.target_scale = (_index(COLORS, config.target[0], "colour"), _index(SHAPES, config.target[1], "shape", DRAWN_SHAPES),
+                                                          float(config.target[2]))
+    else:
+        _odd_one_out_fields(d, config, obj_comp, unseen, scales)
     d.agent_color, d.agent_shape, d.agent_scale = _index(COLORS, config.AGENT[0], "colour"), _index(SHAPES, config.AGENT[1], "shape", DRAWN_SHAPES), float(config.AGENT[2])
     d.agent_x, d.agent_y = float(config.agent_pos[0]), float(config.agent_pos[1])
     d.step_size, d.dist_agent, d.dist_objs, d.dist_wall = (float(config.moving_step_size), float(config.distance_to_agent), float(config.distance_to_objs),
@@ -84,24 +100,51 @@ def env_desc(config, num_envs):
     return d
 
 
-class TargetEnv:
-    """``num_envs`` Target tasks (reach the object that carries ``config.target``) stepping together on ``device``.  Observations are
+def _odd_one_out_fields(d, config, obj_comp, unseen, scales):
+    """the Odd-One-Out part of env_desc: obj_comp, the unseen mode and its two colours, with the library's rejections by config key"""
+    who = "ocrl_amd.envs"
+    if d.lo < 3:
+        raise ValueError(f"{who}: num_objects_range: OddOneOutEnv needs at least 3 objects, two others must share a value (got [{d.lo}, {d.hi}])")
+    if max(d.n_colors, d.n_shapes, d.n_scales) < 2:
+        raise ValueError(f"{who}: OddOneOutEnv needs more than one entry in COLORS, SHAPES or SCALES to pick the odd value from")
+    for key, vals in (("COLORS", list(config.COLORS)), ("SHAPES", list(config.SHAPES)), ("SCALES", scales)):
+        if len(set(vals)) != len(vals):
+            raise ValueError(f"{who}: {key}: OddOneOutEnv needs distinct entries (got {vals})")
+    d.obj_comp, d.unseen_mode = int(obj_comp), UNSEEN_MODES.index(unseen)
+    if unseen is None:
+        return
+    if d.n_shapes != 1 or d.n_scales != 1:
+        raise ValueError(f"{who}: unseen_combi_mode: {unseen} needs one entry each in SHAPES and SCALES, the odd kind must be the colour "
+                         f"(got {d.n_shapes}, {d.n_scales})")
+    if d.n_colors < 3:
+        raise ValueError(f"{who}: unseen_combi_mode: {unseen} needs 3 or more COLORS (got {d.n_colors})")
+    pair = list(getattr(config, "unseen_combi", None) or [])
+    if len(pair) != 2 or pair[0] == pair[1] or any(c not in list(config.COLORS) for c in pair):
+        raise ValueError(f"{who}: unseen_combi must be two different entries of COLORS (got {pair})")
+    d.unseen_colors[0], d.unseen_colors[1] = COLORS.index(pair[0]), COLORS.index(pair[1])
+
+
+class SpriteEnv:
+    """``num_envs`` sprite tasks stepping together on ``device``; a subclass names the task (``TASK``, a key of TASKS).  Observations are
     uint8 frames [E, 3, H, W] (what stable-baselines3 hands the policy after its image transpose); actions 0..3 = up, left, down, right.
     A finished environment starts its next episode inside the step that finished it: the observation returned for it is the new
     episode's first frame, and the finished episode's return and length come back with that step."""
     on_device = True
+    TASK = None
 
     def __init__(self, config_env, num_envs, seed=0, device="cuda"):
         self.config, self.num_envs, self.seed = config_env, int(num_envs), int(seed)
         self._desc = env_desc(config_env, num_envs)               # refusals first: nothing below runs for a config that is not built
         d = self._desc
+        if d.task != TASKS[self.TASK]:
+            raise ValueError(f"ocrl_amd.envs.{self.TASK}: the config's env: {getattr(config_env, 'env', 'TargetEnv')} is another task")
         self.obs_size, self.rows = d.H, d.hi + 1
         self.observation_space = Box(0, 255, (3, d.H, d.H), np.uint8)
         self.action_space = Discrete(4)
         self.render_mode = getattr(config_env, "render_mode", "image")
         self.device = torch.device(device)
         if self.device.type != "cuda":
-            raise RuntimeError(f"ocrl_amd.envs.TargetEnv runs on the GPU (device={device!r}); there is no CPU fallback")
+            raise RuntimeError(f"ocrl_amd.envs.{self.TASK} runs on the GPU (device={device!r}); there is no CPU fallback")
         if self.device.index is None:
             self.device = torch.device("cuda", torch.cuda.current_device())
         L = _lib.lib()
@@ -141,7 +184,7 @@ class TargetEnv:
         """actions int64 [E] on the device -> (frames, rewards fp32, dones bool, extras) as fresh device tensors; extras has ``is_success``
         (bool), ``episode_return`` (float64) and ``episode_length`` (int32) of the episodes this step finished.  No host read."""
         if not self._started:
-            raise RuntimeError("ocrl_amd.envs.TargetEnv: step before reset()")
+            raise RuntimeError(f"ocrl_amd.envs.{self.TASK}: step before reset()")
         E = self.num_envs
         a = actions.to(device=self.device, dtype=torch.int64).reshape(E).contiguous()
         rewards = torch.empty(E, device=self.device)
@@ -184,7 +227,8 @@ class TargetEnv:
     _AUX = {"n": 0, "target": 1, "step_count": 2, "episode": 3, "episode_length": 4}
 
     def get_state(self):
-        """copies: rows [E, hi + 1, 5], n, target, step_count, episode, episode_length (int32 [E]) and episode_return (float64 [E])"""
+        """copies: rows [E, hi + 1, 5], n, target, step_count, episode, episode_length (int32 [E]; an OddOneOutEnv adds unique_kind) and
+        episode_return (float64 [E])"""
         out = {"rows": self._rows.clone(), "episode_return": self._ret.clone()}
         out.update({k: self._aux[:, i].clone() for k, i in self._AUX.items()})
         return out
@@ -200,11 +244,23 @@ class TargetEnv:
             elif k in self._AUX:
                 self._aux[:, self._AUX[k]].copy_(v.to(self.device, torch.int32))
             else:
-                raise KeyError(f"ocrl_amd.envs.TargetEnv.set_state: no field {k!r}")
+                raise KeyError(f"ocrl_amd.envs.{self.TASK}.set_state: no field {k!r}")
         self._started = True
 
     def close(self):
         pass
+
+
+class TargetEnv(SpriteEnv):
+    """the Target task: reach the object that carries ``config.target``"""
+    TASK = "TargetEnv"
+
+
+class OddOneOutEnv(SpriteEnv):
+    """the Odd-One-Out task: reach the object that alone carries some value of one property kind (``unique_kind``: 0 colour, 1 shape,
+    2 scale), with ``obj_comp`` and the unseen-combination train / test modes of the reference"""
+    TASK = "OddOneOutEnv"
+    _AUX = dict(SpriteEnv._AUX, unique_kind=5)
 
 
 def sprite_env_uniforms(seed, env0, n_envs, episode, first, n, device="cuda"):
