@@ -442,10 +442,10 @@ int ocrl_probe_match(const float* out, int ld_row, long long ld_img, const float
 int ocrl_ari_counts(const float* truth, long long t_sb, long long t_sc, long long t_sn, int Ct, const float* pred, long long p_sb,
                     long long p_sc, long long p_sn, int Cp, int fuse_fg, int B, long long N, int* table, long long* sums, void* stream);
 
-/* ---- actor-critic head and PPO minibatch step: sb3s/custom_acnets.py:8-96 (CustomNetwork: shared_net, then policy_net and value_net,
+/* ---- actor-critic head, PPO minibatch step and A2C step: sb3s/custom_acnets.py:8-96 (CustomNetwork: shared_net, then policy_net and value_net,
  *      each [Linear, ReLU | Tanh] x n, the configs/sb3_acnet files) with the heads its ActorCriticPolicy (custom_acnets.py:99-128) inherits
  *      from stable-baselines3: action_net = Linear(latent_dim_pi, A), value_net = Linear(latent_dim_vf, 1), a categorical distribution,
- *      and the loss of PPO.train (configs/sb3/ppo.yaml; clip_range_vf = None).  The heads and the loss are restated from the published
+ *      and the losses of PPO.train (configs/sb3/ppo.yaml; clip_range_vf = None) and A2C.train (configs/sb3/a2c.yaml).  The heads and the losses are restated from the published
  *      algorithm, not from an import.
  * Stateless; fp32 device pointers; everything is enqueued on `stream` with no host synchronisation.
  * desc: B rows of F features, A actions (A == 0: the trunks alone, no heads), trunk t = 0 shared, 1 policy, 2 value with n[t] layers of
@@ -461,6 +461,12 @@ int ocrl_ari_counts(const float* truth, long long t_sb, long long t_sc, long lon
  * _ppo_fwd_bwd: the whole minibatch step.  actions: int64 [B] in [0, A) (clamped into the range); scalars [6] = loss, policy_loss,
  *   value_loss, entropy_loss, approx_kl, clip_fraction; dw, dfeatures = gradients of `loss`.  With normalize_advantage the advantages
  *   become (adv - mean) / (std + 1e-8), unbiased std; B == 1 is then rejected.  At most three launches.
+ * _a2c_fwd_bwd: the whole-batch A2C step with the same descriptor, w / dw order, workspace and reduction.  Per row, with lse, q_a =
+ *   exp(z_a - lse) and H = -sum_a q_a (z_a - lse) computed as in _ppo_fwd_bwd: policy_loss = -mean(adv * log_prob), value_loss =
+ *   mean((values - returns)^2), entropy_loss = -mean(H), loss = policy_loss + ent_coef * entropy_loss + vf_coef * value_loss;
+ *   scalars [4] = loss, policy_loss, value_loss, entropy_loss; dw, dfeatures (may be NULL) = gradients of `loss`.  actions are clamped
+ *   into [0, A); normalize_advantage as above (B == 1 is then rejected); A == 0 is rejected.  At most three launches (the advantage
+ *   statistics run only with normalize_advantage).
  * _act: the rollout's step: _fwd (save = 0, no workspace) with the action and its log-probability in the same single launch.  Needs the
  *   heads (A >= 1; A == 0 is rejected).  actions int64 [B], values [B], log_prob [B]; logits [B, A] may be NULL.  The sampling rule:
  *     u in [0, 1) is a 24-bit uniform (k / 2^24): uniforms[r] when `uniforms` is given, else a pure function of (seed, row_offset + r)
@@ -488,6 +494,9 @@ int ocrl_acnet_ppo_fwd_bwd(const ocrl_acnet_desc* d, const float* features, cons
                            const float* old_log_prob, const float* advantages, const float* returns, float clip_range, float vf_coef,
                            float ent_coef, int normalize_advantage, float* scalars, float* dfeatures, float* const* dw, float* ws,
                            size_t ws_floats, void* stream);
+int ocrl_acnet_a2c_fwd_bwd(const ocrl_acnet_desc* d, const float* features, const float* const* w, const long long* actions,
+                           const float* advantages, const float* returns, float vf_coef, float ent_coef, int normalize_advantage,
+                           float* scalars, float* dfeatures, float* const* dw, float* ws, size_t ws_floats, void* stream);
 int ocrl_acnet_act(const ocrl_acnet_desc* d, const float* features, const float* const* w, unsigned long long seed,
                    unsigned long long row_offset, const float* uniforms /* NULL = draw */, int deterministic, long long* actions, float* values,
                    float* log_prob, float* logits /* may be NULL */, void* stream);
@@ -587,6 +596,18 @@ int ocrl_sprite_env_uniforms(unsigned long long seed, long long env0, int n_envs
 size_t ocrl_flat_clip_adam_ws_floats(void);
 int ocrl_flat_clip_adam_l2(float* p, const float* g, float* m, float* v, long long n, float max_norm, float lr, float beta1, float beta2,
                            float eps, int step, float* norm_out /* device, 1 float */, float* ws, size_t ws_floats, void* stream);
+
+/* ---- L2 gradient clip + TF-style RMSprop on caller-owned flat fp32 buffers p, g, sq [n] (16-byte aligned), as A2C.train applies
+ *      torch.nn.utils.clip_grad_norm_ and stable-baselines3's RMSpropTFLike (momentum 0, not centred, no weight decay) to the policy.
+ *      norm and coef exactly as in ocrl_flat_clip_adam_l2 (a NaN norm reaches every weight); with g' = coef * g:
+ *        sq <- alpha * sq + (1 - alpha) * g'^2,   p <- p - lr * g' / sqrt(sq + eps)
+ *      Two things set this apart from torch.optim.RMSprop: the epsilon is INSIDE the square root, and the caller initialises sq to
+ *      ONES, not zeros.  1 - alpha is taken in double from the decimal `alpha` stands for and rounded once.  Rejected before any launch:
+ *      null arguments, n < 1, misaligned p / g / sq, ws_floats < ocrl_flat_clip_rmsprop_ws_floats(), alpha outside (0, 1), eps <= 0.
+ *      Four small launches (three of the norm, one update), five when n is not a multiple of 4. */
+size_t ocrl_flat_clip_rmsprop_ws_floats(void);
+int ocrl_flat_clip_rmsprop_l2(float* p, const float* g, float* sq, long long n, float max_norm, float lr, float alpha, float eps,
+                              float* norm_out /* device, 1 float */, float* ws, size_t ws_floats, void* stream);
 
 /* ---- IODINE (ocrs/iodine/iodine_module.py:14-271, ocrs/iodine/iodine.py:4-14, ocrs/base.py:60-74): SURVEY.md §8 row a20 ----
  * Same conventions as the SLATE handle: flat fp32 parameter / gradient / Adam buffers in the reference's

@@ -253,11 +253,15 @@ def lib():
     L.ocrl_acnet_fwd.argtypes = [POINTER(AcnetDesc), p, POINTER(p), p, p, p, p, c_int, p, c_size_t, p]
     L.ocrl_acnet_bwd.argtypes = [POINTER(AcnetDesc), p, POINTER(p), p, p, p, p, p, POINTER(p), p, c_size_t, p]
     L.ocrl_acnet_ppo_fwd_bwd.argtypes = [POINTER(AcnetDesc), p, POINTER(p), p, p, p, p, c_float, c_float, c_float, c_int, p, p, POINTER(p), p, c_size_t, p]
+    L.ocrl_acnet_a2c_fwd_bwd.argtypes = [POINTER(AcnetDesc), p, POINTER(p), p, p, p, c_float, c_float, c_int, p, p, POINTER(p), p, c_size_t, p]
     L.ocrl_acnet_act.argtypes = [POINTER(AcnetDesc), p, POINTER(p), c_ulonglong, c_ulonglong, p, c_int, p, p, p, p, p]
     L.ocrl_acnet_act_uniforms.argtypes = [c_ulonglong, c_ulonglong, c_longlong, p, p]
     L.ocrl_flat_clip_adam_ws_floats.argtypes = []
     L.ocrl_flat_clip_adam_ws_floats.restype = c_size_t
     L.ocrl_flat_clip_adam_l2.argtypes = [p, p, p, p, c_longlong, c_float, c_float, c_float, c_float, c_float, c_int, p, p, c_size_t, p]
+    L.ocrl_flat_clip_rmsprop_ws_floats.argtypes = []
+    L.ocrl_flat_clip_rmsprop_ws_floats.restype = c_size_t
+    L.ocrl_flat_clip_rmsprop_l2.argtypes = [p, p, p, c_longlong, c_float, c_float, c_float, c_float, p, p, c_size_t, p]
     L.ocrl_gae.argtypes = [p, p, p, p, p, p, p, c_int, c_int, c_float, c_float, p]
     L.ocrl_sprite_env_desc_size.restype = c_size_t
     if L.ocrl_sprite_env_desc_size() != ctypes.sizeof(SpriteEnvDesc):

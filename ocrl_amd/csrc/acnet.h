@@ -25,12 +25,12 @@ struct AcnetArgs {
     float* slab;                                      // [S][slab_stride] partial parameter gradients
     long long slab_stride, off_w[3][ACNET_MAX_LAYERS], off_b[3][ACNET_MAX_LAYERS], off_wa, off_ba, off_wv, off_bv;
     int S, ntiles;
-    // PPO
+    // PPO and A2C (A2C reads neither old_logp nor clip)
     const long long* actions;
     const float *old_logp, *adv, *ret, *stats;        // stats: {mean, 1 / (std + 1e-8)} of the advantages
     float clip, vf_coef, ent_coef;
     int norm;
-    float* scal_slab;                                 // [S][8] partial sums of the six scalars
+    float* scal_slab;                                 // [S][8] partial sums of the scalars (PPO five, A2C three)
 };
 
 // the sampling tail of acnet_act: row r draws from (seed, row_offset + r) unless `uniforms` [B] is given
@@ -48,7 +48,8 @@ struct AcnetReduceArgs {
     float* dst[ACNET_NPARAM];
     int S, np, B;
     const float* scal_slab;                           // null: no scalars
-    float* scal_out;                                  // {loss, policy_loss, value_loss, entropy_loss, approx_kl, clip_fraction}
+    int nsum;                                         // partial sums per slab: 5 (PPO) or 3 (A2C)
+    float* scal_out;                                  // {loss, policy_loss, value_loss, entropy_loss} and for PPO {approx_kl, clip_fraction}
     float vf_coef, ent_coef;
 };
 
@@ -57,6 +58,7 @@ int acnet_act_launch(const AcnetArgs& a, const AcnetActArgs& s, hipStream_t st);
 int acnet_act_uniforms_launch(unsigned long long seed, unsigned long long row_offset, long long n, float* out, hipStream_t st);
 int acnet_bwd_launch(const AcnetArgs& a, hipStream_t st);
 int acnet_ppo_launch(const AcnetArgs& a, hipStream_t st);
+int acnet_a2c_launch(const AcnetArgs& a, hipStream_t st);
 int acnet_reduce_launch(const AcnetReduceArgs& r, hipStream_t st);
 int acnet_adv_stats_launch(const float* adv, int B, float* stats, hipStream_t st);
 int acnet_gae_launch(const float* rewards, const float* values, const float* starts, const float* last_values, const float* dones, float* adv, float* ret,

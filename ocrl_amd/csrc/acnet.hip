@@ -9,9 +9,10 @@
 //   acnet_bwd        cotangents of latents / logits / values -> per-slab partial dW, db and dfeatures
 //   acnet_ppo        forward, log-softmax, log-prob gather, entropy, ratio, clipping, the loss sums and their gradient, and the
 //                    backward, per row tile in one kernel; logits, probabilities and layer cotangents never leave LDS
+//   acnet_a2c        the same for A2C's loss (no ratio, no clipping): -adv log_prob, the squared value error and the entropy
 //   acnet_act        the forward with the rollout's tail in the same launch: log-softmax, the action (drawn from one 24-bit uniform
 //                    per row, or the argmax) and its log-probability; one lane owns a row's tail (include/ocrl_hip.h ocrl_acnet_act)
-//   acnet_reduce     dw = sum of the slabs in slab order; the six PPO scalars from their partial sums
+//   acnet_reduce     dw = sum of the slabs in slab order; the six PPO (four A2C) scalars from their partial sums
 //   acnet_adv_stats  mean and 1 / (std + 1e-8) (unbiased std) of the advantages, one workgroup, fixed order
 //   gae              generalised advantage estimation, one thread per environment walking T backwards
 // Order of every sum: a layer output is acc0 + acc1 + bias with acc0 / acc1 the MFMA chains over the even / odd 16-wide k chunks in
@@ -416,6 +417,73 @@ __global__ __launch_bounds__(256) void acnet_ppo_kernel(AcnetArgs p) {
     }
 }
 
+// The A2C step of one tile after its forward, in the shape of ppo_rows: lse, q_a and H are computed by the same operations.  Replaces
+// the logits in lg by dL/dlogits and the values in vl by dL/dvalues and adds the row's three terms (-adv log_prob, (v - ret)^2, -H) to the
+// slab's partial sums.
+__device__ void a2c_rows(const AcnetArgs& p, long long row0, int rows, bool first, float* lg, float* vl, float (*rs)[3]) {
+    const int r = threadIdx.x;
+    if (r < TR) {
+        float t[3] = {0.f, 0.f, 0.f};
+        float* z = lg + r * LA;
+        if (r < rows) {
+            const long long row = row0 + r;
+            const int A = p.A;
+            float m = z[0];
+            for (int a = 1; a < A; ++a) m = fmaxf(m, z[a]);
+            float se = 0.f;
+            for (int a = 0; a < A; ++a) se += expf(z[a] - m);
+            const float lse = m + logf(se);
+            float H = 0.f;
+            for (int a = 0; a < A; ++a) { const float lq = z[a] - lse; H -= expf(lq) * lq; }
+            long long act = p.actions[row];
+            act = act < 0 ? 0 : act >= A ? A - 1 : act;
+            const float logp = z[act] - lse;
+            float adv = p.adv[row];
+            if (p.norm) adv = (adv - p.stats[0]) * p.stats[1];
+            const float v = vl[r], dv = v - p.ret[row], invB = 1.f / (float)p.B;
+            t[0] = -(adv * logp); t[1] = dv * dv; t[2] = -H;
+            for (int a = 0; a < A; ++a) {
+                const float lq = z[a] - lse, q = expf(lq);
+                const float dlogp = (a == act ? 1.f : 0.f) - q;
+                z[a] = invB * (-adv * dlogp + p.ent_coef * q * (lq + H));
+            }
+            vl[r] = invB * p.vf_coef * 2.f * dv;
+        } else {
+            for (int a = 0; a < p.A; ++a) z[a] = 0.f;
+            vl[r] = 0.f;
+        }
+#pragma unroll
+        for (int j = 0; j < 3; ++j) rs[r][j] = t[j];
+    }
+    __syncthreads();
+    if (threadIdx.x < 3) {
+        float s = 0.f;
+#pragma unroll
+        for (int q = 0; q < TR; ++q) s += rs[q][threadIdx.x];
+        float* d = p.scal_slab + (long long)blockIdx.x * 8 + threadIdx.x;
+        *d = first ? s : *d + s;
+    }
+    __syncthreads();
+}
+
+__global__ __launch_bounds__(256) void acnet_a2c_kernel(AcnetArgs p) {
+    __shared__ __attribute__((aligned(16))) float buf[3 * TR * LD];
+    __shared__ __attribute__((aligned(16))) float lg[TR * LA];
+    __shared__ float vl[TR];
+    __shared__ float rs[TR][3];
+    for (int tile = blockIdx.x; tile < p.ntiles; tile += p.S) {
+        const long long row0 = (long long)tile * TR;
+        const int rows = p.B - row0 < TR ? (int)(p.B - row0) : TR;
+        const bool first = tile == (int)blockIdx.x;
+        fwd_tile(p, row0, rows, buf, lg, vl);
+        a2c_rows(p, row0, rows, first, lg, vl, rs);
+        bwd_tile(p, row0, rows, first, buf, lg, vl);
+        __syncthreads();
+    }
+}
+
+// scalars: the first three partial sums are policy, value and entropy terms for both losses; PPO carries two more (nsum = 5: approx_kl
+// and the clip fraction, outputs 4 and 5), A2C none (nsum = 3: four outputs)
 __global__ __launch_bounds__(256) void acnet_reduce_kernel(AcnetReduceArgs r) {
     const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
     if (e < r.total) {
@@ -427,13 +495,14 @@ __global__ __launch_bounds__(256) void acnet_reduce_kernel(AcnetReduceArgs r) {
     }
     if (r.scal_slab && blockIdx.x == 0 && threadIdx.x == 0) {
         float t[5];
-        for (int j = 0; j < 5; ++j) {
+        for (int j = 0; j < r.nsum; ++j) {
             float s = 0.f;
             for (int k = 0; k < r.S; ++k) s += r.scal_slab[k * 8 + j];
             t[j] = s / (float)r.B;
         }
         r.scal_out[0] = t[0] + r.ent_coef * t[2] + r.vf_coef * t[1];
-        r.scal_out[1] = t[0]; r.scal_out[2] = t[1]; r.scal_out[3] = t[2]; r.scal_out[4] = t[3]; r.scal_out[5] = t[4];
+        r.scal_out[1] = t[0]; r.scal_out[2] = t[1]; r.scal_out[3] = t[2];
+        for (int j = 3; j < r.nsum; ++j) r.scal_out[j + 1] = t[j];
     }
 }
 
@@ -501,6 +570,11 @@ int acnet_bwd_launch(const AcnetArgs& a, hipStream_t st) {
 int acnet_ppo_launch(const AcnetArgs& a, hipStream_t st) {
     hipLaunchKernelGGL(acnet_ppo_kernel, dim3(a.S), dim3(256), 0, st, a);
     OCRL_CHECK_LAUNCH("acnet_ppo");
+    return 0;
+}
+int acnet_a2c_launch(const AcnetArgs& a, hipStream_t st) {
+    hipLaunchKernelGGL(acnet_a2c_kernel, dim3(a.S), dim3(256), 0, st, a);
+    OCRL_CHECK_LAUNCH("acnet_a2c");
     return 0;
 }
 int acnet_reduce_launch(const AcnetReduceArgs& r, hipStream_t st) {

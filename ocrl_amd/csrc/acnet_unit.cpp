@@ -1,5 +1,6 @@
 // C ABI of the actor-critic head (include/ocrl_hip.h: ocrl_acnet_*, ocrl_gae): sb3s/custom_acnets.py:8-96 (CustomNetwork) with the
-// action_net / value_net heads of its ActorCriticPolicy and the PPO minibatch loss (configs/sb3/ppo.yaml).  Stateless: the caller owns
+// action_net / value_net heads of its ActorCriticPolicy, the PPO minibatch loss (configs/sb3/ppo.yaml) and the A2C loss
+// (configs/sb3/a2c.yaml).  Stateless: the caller owns
 // parameters, gradients and the workspace.  Parameter order (w, dw): state_dict order of the trunks, shared_net, policy_net, value_net,
 // (weight, bias) per layer, then with heads (A > 0) action_net.weight, action_net.bias, value_net.weight, value_net.bias.
 #include "../../include/ocrl_hip.h"
@@ -185,7 +186,32 @@ int ocrl_acnet_ppo_fwd_bwd(const ocrl_acnet_desc* d, const float* features, cons
     RC(acnet_ppo_launch(a, st));
     AcnetReduceArgs r;
     fill_reduce(r, a, y, dw);
-    r.scal_slab = a.scal_slab; r.scal_out = scalars; r.vf_coef = vf_coef; r.ent_coef = ent_coef;
+    r.scal_slab = a.scal_slab; r.nsum = 5; r.scal_out = scalars; r.vf_coef = vf_coef; r.ent_coef = ent_coef;
+    return acnet_reduce_launch(r, st);
+}
+
+int ocrl_acnet_a2c_fwd_bwd(const ocrl_acnet_desc* d, const float* features, const float* const* w, const long long* actions, const float* advantages,
+                           const float* returns, float vf_coef, float ent_coef, int normalize_advantage, float* scalars, float* dfeatures,
+                           float* const* dw, float* ws, size_t ws_floats, void* stream) {
+    RC(check_acnet(d, "ocrl_acnet_a2c_fwd_bwd"));
+    OCRL_REQUIRE(d->A >= 1, "ocrl_acnet_a2c_fwd_bwd: the loss needs the heads (1 <= n_actions <= %d, got 0)", ACNET_MAX_ACTIONS);
+    OCRL_REQUIRE(!(normalize_advantage && d->B < 2), "ocrl_acnet_a2c_fwd_bwd: normalize_advantage needs batch >= 2 (the std of one advantage is undefined)");
+    const AcLay y = ac_layout(d);
+    OCRL_REQUIRE(features && w && actions && advantages && returns && scalars && dw && ws, "ocrl_acnet_a2c_fwd_bwd: null argument");
+    RC(check_ptrs(w, y.np, "ocrl_acnet_a2c_fwd_bwd"));
+    RC(check_ptrs(dw, y.np, "ocrl_acnet_a2c_fwd_bwd"));
+    OCRL_REQUIRE(ws_floats >= y.total, "ocrl_acnet_a2c_fwd_bwd: workspace too small (%zu < %zu floats)", ws_floats, y.total);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    AcnetArgs a;
+    fill_args(a, d, y, features, w, ws, true);
+    a.actions = actions; a.adv = advantages; a.ret = returns;
+    a.vf_coef = vf_coef; a.ent_coef = ent_coef; a.norm = normalize_advantage ? 1 : 0;
+    a.dx = dfeatures;
+    if (a.norm) RC(acnet_adv_stats_launch(advantages, d->B, ws + y.stats, st));
+    RC(acnet_a2c_launch(a, st));
+    AcnetReduceArgs r;
+    fill_reduce(r, a, y, dw);
+    r.scal_slab = a.scal_slab; r.nsum = 3; r.scal_out = scalars; r.vf_coef = vf_coef; r.ent_coef = ent_coef;
     return acnet_reduce_launch(r, st);
 }
 

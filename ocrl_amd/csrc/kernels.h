@@ -446,6 +446,11 @@ int clip_adam_launch(float* p, const float* g, float* m, float* v, long long n, 
 // the same update on 1 .. 3 trailing elements (any alignment)
 int clip_adam_tail_launch(float* p, const float* g, float* m, float* v, int n, const float* norm, float clip, float lr, double b1, double b2,
                           double eps, int step, float gscale, hipStream_t st);
+// L2-clipped TF-style RMSprop (eps inside the root, sq starts at ones): norm[0] holds ||g||_2; n a multiple of 4, and the 1 .. 3 element tail
+int clip_rmsprop_launch(float* p, const float* g, float* sq, long long n, const float* norm, float clip, float lr, double alpha, double eps,
+                        hipStream_t st);
+int clip_rmsprop_tail_launch(float* p, const float* g, float* sq, int n, const float* norm, float clip, float lr, double alpha, double eps,
+                             hipStream_t st);
 int store_u64_launch(unsigned long long* dst, unsigned long long v, hipStream_t st);
 int slot_init_launch(const float* mu, const float* logsig, const float* noise, float* slots0, int BK, int D, unsigned long long seed, hipStream_t st,
                      const unsigned long long* seed_dev = nullptr);

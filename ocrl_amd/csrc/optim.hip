@@ -1,5 +1,5 @@
 // Global inf-norm gradient clip + Adam on flat fp32 buffers (reference: ocrs/base.py:65-72,
-// torch.nn.utils.clip_grad_norm_(…, "inf") and torch.optim.Adam defaults).
+// torch.nn.utils.clip_grad_norm_(…, "inf") and torch.optim.Adam defaults), and the TF-style RMSprop update A2C takes after the same clip.
 #include "common.h"
 #include "kernels.h"
 
@@ -81,6 +81,35 @@ __global__ __launch_bounds__(64) void clip_adam_tail_kernel(float* __restrict__ 
     m[i] = mm; v[i] = vq; p[i] = pp;
 }
 
+// One element of the TF-style RMSprop update (stable-baselines3's RMSpropTFLike: momentum 0, not centred, no weight decay): the epsilon
+// sits inside the square root, and the caller starts sq at ones.  oma = 1 - alpha, taken in double from the decimal alpha.
+__device__ __forceinline__ void rmsprop_upd(float gg, float& sq, float& pp, float coef, float lr, float alpha, float oma, float eps) {
+    gg *= coef;
+    sq = alpha * sq + oma * gg * gg;
+    pp -= lr * (gg / sqrtf(sq + eps));
+}
+__global__ __launch_bounds__(256) void clip_rmsprop_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ sq, long long n4,
+                                                          const float* __restrict__ norm, float clip, float lr, float alpha, float oma, float eps) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n4) return;
+    const float coef = clip_coef(norm, clip, 1.f);
+    const float4 gv = reinterpret_cast<const float4*>(g)[i];
+    float4 sv = reinterpret_cast<float4*>(sq)[i], pv = reinterpret_cast<float4*>(p)[i];
+    rmsprop_upd(gv.x, sv.x, pv.x, coef, lr, alpha, oma, eps); rmsprop_upd(gv.y, sv.y, pv.y, coef, lr, alpha, oma, eps);
+    rmsprop_upd(gv.z, sv.z, pv.z, coef, lr, alpha, oma, eps); rmsprop_upd(gv.w, sv.w, pv.w, coef, lr, alpha, oma, eps);
+    reinterpret_cast<float4*>(sq)[i] = sv;
+    reinterpret_cast<float4*>(p)[i] = pv;
+}
+// the same update on the n < 4 elements a buffer's length leaves past its last group of four
+__global__ __launch_bounds__(64) void clip_rmsprop_tail_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ sq, int n,
+                                                              const float* __restrict__ norm, float clip, float lr, float alpha, float oma, float eps) {
+    const int i = threadIdx.x;
+    if (i >= n) return;
+    float s = sq[i], pp = p[i];
+    rmsprop_upd(g[i], s, pp, clip_coef(norm, clip, 1.f), lr, alpha, oma, eps);
+    sq[i] = s; p[i] = pp;
+}
+
 int absmax_launch(const float* g, long long n, float* out, float* ws, size_t ws_floats, hipStream_t st) {
     OCRL_REQUIRE(n % 4 == 0 && ws_floats >= 1024, "absmax: n %% 4 != 0 or workspace too small");
     int nblk = cdiv(n / 4, 256);
@@ -107,5 +136,20 @@ int clip_adam_tail_launch(float* p, const float* g, float* m, float* v, int n, c
     hipLaunchKernelGGL(clip_adam_tail_kernel, dim3(1), dim3(64), 0, st, p, g, m, v, n, norm, clip, lr, (float)(1.0 - b1), (float)b2,
                        (float)(1.0 - b2), (float)eps, (float)bc1, (float)sqrt(bc2), gscale);
     OCRL_CHECK_LAUNCH("clip_adam_tail");
+    return 0;
+}
+int clip_rmsprop_launch(float* p, const float* g, float* sq, long long n, const float* norm, float clip, float lr, double alpha, double eps,
+                        hipStream_t st) {
+    OCRL_REQUIRE(n >= 4 && n % 4 == 0, "clip_rmsprop: n %% 4 != 0 or n < 4");
+    hipLaunchKernelGGL(clip_rmsprop_kernel, dim3(cdiv(n / 4, 256)), dim3(256), 0, st, p, g, sq, n / 4, norm, clip, lr, (float)alpha,
+                       (float)(1.0 - alpha), (float)eps);
+    OCRL_CHECK_LAUNCH("clip_rmsprop");
+    return 0;
+}
+int clip_rmsprop_tail_launch(float* p, const float* g, float* sq, int n, const float* norm, float clip, float lr, double alpha, double eps,
+                             hipStream_t st) {
+    OCRL_REQUIRE(n >= 1 && n < 4, "clip_rmsprop_tail: 1 <= n <= 3");
+    hipLaunchKernelGGL(clip_rmsprop_tail_kernel, dim3(1), dim3(64), 0, st, p, g, sq, n, norm, clip, lr, (float)alpha, (float)(1.0 - alpha), (float)eps);
+    OCRL_CHECK_LAUNCH("clip_rmsprop_tail");
     return 0;
 }

@@ -1,6 +1,7 @@
-// C ABI of the stateless optimiser step (include/ocrl_hip.h: ocrl_flat_clip_adam_*): torch.nn.utils.clip_grad_norm_ (L2) followed by
-// torch.optim.Adam on caller-owned flat fp32 buffers, as PPO.train applies them to the policy.  Nothing new is computed here: the norm is
-// IODINE's io_l2norm_launch (iodine.hip: per-block sums of squares, folded in a fixed order) and the update optim.hip's clip_adam kernels.
+// C ABI of the stateless optimiser steps (include/ocrl_hip.h: ocrl_flat_clip_adam_*, ocrl_flat_clip_rmsprop_*):
+// torch.nn.utils.clip_grad_norm_ (L2) followed by torch.optim.Adam, as PPO.train applies them to the policy, or by the TF-style RMSprop
+// of A2C.train, on caller-owned flat fp32 buffers.  The norm is IODINE's io_l2norm_launch (iodine.hip: per-block sums of squares, folded
+// in a fixed order) and the updates optim.hip's clip_adam / clip_rmsprop kernels.
 #include "../../include/ocrl_hip.h"
 #include "common.h"
 #include "kernels.h"
@@ -39,6 +40,25 @@ int ocrl_flat_clip_adam_l2(float* p, const float* g, float* m, float* v, long lo
     const long long n4 = n & ~3LL;
     if (n4) RC(clip_adam_launch(p, g, m, v, n4, norm_out, max_norm, lr, b1, b2, e, step, 1.f, st));
     if (n > n4) RC(clip_adam_tail_launch(p + n4, g + n4, m + n4, v + n4, (int)(n - n4), norm_out, max_norm, lr, b1, b2, e, step, 1.f, st));
+    return 0;
+}
+
+size_t ocrl_flat_clip_rmsprop_ws_floats(void) { return WS_FLOATS; }
+
+int ocrl_flat_clip_rmsprop_l2(float* p, const float* g, float* sq, long long n, float max_norm, float lr, float alpha, float eps, float* norm_out,
+                              float* ws, size_t ws_floats, void* stream) {
+    OCRL_REQUIRE(p && g && sq && norm_out && ws, "ocrl_flat_clip_rmsprop_l2: null argument (p, g, sq, norm_out or ws)");
+    OCRL_REQUIRE(n >= 1, "ocrl_flat_clip_rmsprop_l2: n >= 1 (got %lld)", n);
+    OCRL_REQUIRE(alpha > 0.f && alpha < 1.f, "ocrl_flat_clip_rmsprop_l2: alpha must lie in (0, 1) (got %g)", (double)alpha);
+    OCRL_REQUIRE(eps > 0.f, "ocrl_flat_clip_rmsprop_l2: eps must be positive (got %g)", (double)eps);
+    OCRL_REQUIRE(ws_floats >= WS_FLOATS, "ocrl_flat_clip_rmsprop_l2: workspace too small (%zu < %zu floats)", ws_floats, WS_FLOATS);
+    OCRL_REQUIRE(aligned16(p) && aligned16(g) && aligned16(sq), "ocrl_flat_clip_rmsprop_l2: p, g and sq must be 16-byte aligned");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    RC(io_l2norm_launch(g, n, norm_out, ws, ws_floats, st));
+    const double a = decimal(alpha), e = decimal(eps);
+    const long long n4 = n & ~3LL;
+    if (n4) RC(clip_rmsprop_launch(p, g, sq, n4, norm_out, max_norm, lr, a, e, st));
+    if (n > n4) RC(clip_rmsprop_tail_launch(p + n4, g + n4, sq + n4, (int)(n - n4), norm_out, max_norm, lr, a, e, st));
     return 0;
 }
 

@@ -1,5 +1,6 @@
-from .custom_acnets import CustomActorCriticPolicy, CustomNetwork, compute_gae, ppo_loss
+from .a2c import A2C
+from .custom_acnets import CustomActorCriticPolicy, CustomNetwork, a2c_loss, compute_gae, ppo_loss
 from .ocr_extractor import OCRExtractor
 from .ppo import PPO, RolloutBuffer
 
-__all__ = ["OCRExtractor", "CustomNetwork", "CustomActorCriticPolicy", "ppo_loss", "compute_gae", "PPO", "RolloutBuffer"]
+__all__ = ["OCRExtractor", "CustomNetwork", "CustomActorCriticPolicy", "ppo_loss", "a2c_loss", "compute_gae", "PPO", "A2C", "RolloutBuffer"]

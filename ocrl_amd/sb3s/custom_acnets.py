@@ -1,4 +1,4 @@
-"""Actor-critic network of the RL agent (sb3s/custom_acnets.py:8-128) and the PPO minibatch loss it is trained with.
+"""Actor-critic network of the RL agent (sb3s/custom_acnets.py:8-128) and the PPO and A2C losses it is trained with.
 
 ``CustomNetwork`` holds the parameters in the reference's containers (``shared_net`` / ``policy_net`` / ``value_net``: nn.Sequential
 of [nn.Linear, nn.ReLU | nn.Tanh] pairs), so ``state_dict()`` keys, shapes and initialisation are the reference's and its checkpoints
@@ -8,7 +8,7 @@ row tile in one kernel) under a ``torch.autograd.Function``.  No CPU fallback: a
 ``CustomActorCriticPolicy`` subclasses stable-baselines3's ``ActorCriticPolicy`` as the reference does when that package is
 installed.  Without it, it is a plain nn.Module with the heads that base class adds (``action_net``, ``value_net``, a categorical
 distribution), restated from the published algorithm; ``ppo_loss`` is the loss of ``PPO.train`` (clip_range_vf = None) through
-``ocrl_acnet_ppo_fwd_bwd`` and ``compute_gae`` the rollout buffer's advantage estimation through ``ocrl_gae``."""
+``ocrl_acnet_ppo_fwd_bwd``, ``a2c_loss`` the loss of ``A2C.train`` through ``ocrl_acnet_a2c_fwd_bwd`` and ``compute_gae`` the rollout buffer's advantage estimation through ``ocrl_gae``."""
 import ctypes
 import math
 import numbers
@@ -21,6 +21,7 @@ from .. import _bridge, _lib
 _WHO = "ocrl_amd.sb3s"
 _ACT_CODE = {nn.ReLU: 1, nn.Tanh: 2}
 PPO_SCALARS = ("loss", "policy_loss", "value_loss", "entropy_loss", "approx_kl", "clip_fraction")
+A2C_SCALARS = PPO_SCALARS[:4]
 
 
 def _desc(B, F, A, dims, acts, dev, keep=True):
@@ -96,6 +97,37 @@ class _PPOFn(torch.autograd.Function):
     def backward(ctx, gloss, _gscal):
         dx = None if ctx.dx is None else ctx.dx * gloss
         return (dx, None, None, None, None, None, None, None, None, *[g * gloss for g in ctx.gs])
+
+
+class _A2CFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, features, actions, advantages, returns, hyper, dims, acts, A, *params):
+        x, ps = _bridge.inputs(_WHO, features, params)
+        dev = x.device
+        B, F = x.shape
+        vf_coef, ent_coef, normalize = hyper
+        if normalize and B < 2:
+            raise ValueError(f"{_WHO}.a2c_loss: normalize_advantage needs a batch of at least 2 (the std of one advantage is undefined)")
+        vec = lambda t, dt: t.to(device=dev, dtype=dt).reshape(-1).contiguous()
+        actions, advantages, returns = vec(actions, torch.int64), vec(advantages, torch.float32), vec(returns, torch.float32)
+        for name, t in (("actions", actions), ("advantages", advantages), ("returns", returns)):
+            if t.numel() != B:
+                raise ValueError(f"{_WHO}.a2c_loss: {name} has {t.numel()} entries for a batch of {B}")
+        d, ws = _desc(B, F, A, dims, acts, dev)
+        scal = torch.empty(4, device=dev, dtype=torch.float32)
+        gs = [torch.empty_like(p) for p in ps]
+        dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+        _bridge.launch(dev, _lib.lib().ocrl_acnet_a2c_fwd_bwd, ctypes.byref(d), _lib.ptr(x), _lib.ptrs(ps), _lib.ptr(actions), _lib.ptr(advantages),
+                       _lib.ptr(returns), float(vf_coef), float(ent_coef), int(bool(normalize)), _lib.ptr(scal), _lib.ptr(dx), _lib.ptrs(gs),
+                       _lib.ptr(ws), ws.numel())
+        ctx.gs, ctx.dx = gs, dx              # as in _PPOFn: the gradients are the forward's own outputs
+        ctx.mark_non_differentiable(scal)
+        return scal[0].clone(), scal
+
+    @staticmethod
+    def backward(ctx, gloss, _gscal):
+        dx = None if ctx.dx is None else ctx.dx * gloss
+        return (dx, None, None, None, None, None, None, None, *[g * gloss for g in ctx.gs])
 
 
 def _mlp(in_dim, cfg):
@@ -284,6 +316,16 @@ def ppo_loss(policy, features, actions, old_log_prob, advantages, returns, clip_
     loss, scal = _PPOFn.apply(features, actions, old_log_prob, advantages, returns, (clip_range, vf_coef, ent_coef, normalize_advantage), dims, acts,
                               policy.action_net.out_features, *params)
     return loss, {k: scal[i] for i, k in enumerate(PPO_SCALARS)}
+
+
+def a2c_loss(policy, features, actions, advantages, returns, vf_coef, ent_coef, normalize_advantage=False):
+    """A2C's loss of ``policy`` on a feature batch [B, F]: (loss, metrics), attached to autograd as ``ppo_loss`` is.  ``metrics`` maps
+    A2C_SCALARS to detached 0-d tensors."""
+    dims, acts = policy.mlp_extractor._layout()
+    params = policy.mlp_extractor._param_list() + [policy.action_net.weight, policy.action_net.bias, policy.value_net.weight, policy.value_net.bias]
+    loss, scal = _A2CFn.apply(features, actions, advantages, returns, (vf_coef, ent_coef, normalize_advantage), dims, acts,
+                              policy.action_net.out_features, *params)
+    return loss, {k: scal[i] for i, k in enumerate(A2C_SCALARS)}
 
 
 def compute_gae(rewards, values, episode_starts, last_values, dones, gamma, gae_lambda):

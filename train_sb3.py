@@ -1,15 +1,17 @@
-"""RL entry point with the reference's command line (train_sb3.py:22-120, on this project's config resolver and its own PPO):
+"""RL entry point with the reference's command line (train_sb3.py:22-120, on this project's config resolver and its own PPO and A2C;
+``sb3=ppo`` or ``sb3=a2c`` chooses, as the reference's ``getattr(sb3, config.sb3.name)``):
 
     python train_sb3.py ocr=slate pooling=transformer sb3=ppo sb3_acnet=mlp env=target-N4C4S3S1 num_envs=16 device=cuda:0 \
         pooling.ocr_checkpoint.local_file=outputs/train_ocr/SLATE-RandomN5C4S4S2/checkpoints/model_best.pth
 
 Builds the vectorised environment (ocrl_amd.envs: state, step and frames stay on the GPU), the OCRExtractor policy over the pre-trained
-encoder and PPO with ``n_steps = sb3.algo_kwargs.n_steps // num_envs``, then alternates rollouts and updates until ``max_steps``.  Whenever
-``num_timesteps`` passes a multiple of ``eval.freq`` the policy plays ``eval.n_episodes`` episodes (sampled actions, as the reference's
+encoder and the algorithm with ``n_steps = max(1, sb3.algo_kwargs.n_steps // num_envs)``, then alternates rollouts and updates until
+``max_steps``.  Whenever ``num_timesteps`` passes a multiple of ``eval.freq`` the policy plays ``eval.n_episodes`` episodes (sampled actions, as the reference's
 EvalCallback with deterministic=False) on a separate environment seeded ``seed + num_envs``.  ``run_dir`` receives metrics.jsonl (one line
 per iteration: the train() statistics, the rollout's episode window, and the evaluation when one ran) and checkpoints/model_latest.pth,
-model_best.pth (PPO.save).  No video and no wandb.  A SLATE / IODINE encoder needs its pre-trained checkpoint
-(pooling.ocr_checkpoint.local_file, no finetuning): PPO refuses to step such an encoder itself; NatureCNN / MultipleCNN train from scratch.
+model_best.pth (PPO.save / A2C.save).  No video and no wandb.  A SLATE / IODINE encoder needs its pre-trained checkpoint
+(pooling.ocr_checkpoint.local_file, no finetuning): PPO and A2C refuse to step such an encoder themselves; NatureCNN / MultipleCNN train
+from scratch.
 """
 import json
 import logging
@@ -26,13 +28,14 @@ from ocrl_amd import envs, sb3s  # noqa: E402
 from ocrl_amd.utils.config import compose  # noqa: E402
 
 log = logging.getLogger("train_sb3")
+ALGOS = {"PPO": sb3s.PPO, "A2C": sb3s.A2C}
 EVAL_ROW_OFFSET = 1 << 40          # the evaluation samples from its own rows of the policy's stream: training draws do not move
 
 
 def build(config):
     """(env, eval_env, model) of a composed train_sb3 config"""
-    if config.sb3.name != "PPO":
-        raise NotImplementedError(f"train_sb3: sb3: {config.sb3.name} is not built (built: PPO)")
+    if config.sb3.name not in ALGOS:
+        raise NotImplementedError(f"train_sb3: sb3: {config.sb3.name} is not built (built: {', '.join(ALGOS)})")
     if config.ocr.name == "GT":
         raise NotImplementedError("train_sb3: ocr: GT (ground-truth states as observations) is not built")
     env = envs.make_env(config)
@@ -43,7 +46,7 @@ def build(config):
         kwargs.update(config.sb3.algo_kwargs.to_dict())
     if "n_steps" in kwargs:
         kwargs["n_steps"] = max(1, kwargs["n_steps"] // config.num_envs)
-    return env, eval_env, sb3s.PPO(sb3s.CustomActorCriticPolicy, env, **kwargs)
+    return env, eval_env, ALGOS[config.sb3.name](sb3s.CustomActorCriticPolicy, env, **kwargs)
 
 
 def evaluate(model, env, n_episodes, calls):
