@@ -37,6 +37,12 @@ static int h_create(const C& k, H** out) {
     if (!h) { ocrl_set_error("out of memory"); return 1; }
     h->m = new (std::nothrow) typename H::Model(k);
     if (!h->m) { delete h; ocrl_set_error("out of memory"); return 1; }
+    if (!h->m->create_error().empty()) {       // a name the constructor could not resolve
+        ocrl_set_error("create: %s", h->m->create_error().c_str());
+        delete h->m;
+        delete h;
+        return 1;
+    }
     *out = h;
     return 0;
 }

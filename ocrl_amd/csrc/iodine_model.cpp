@@ -40,6 +40,14 @@ IodineModel::IodineModel(const IodineConfig& c) : cfg(c) {
     }
     add_param("decoder.conv.weight", {4, 64, 3, 3}); add_param("decoder.conv.bias", {4});
     finish_params();
+    w_.mean_init = ref("slot_mean_init"); w_.logsig_init = ref("slot_logsig_init");
+    w_.skip_begin = ref("slot_init").off; w_.skip_end = w_.skip_begin + padded(L);
+    for (int l = 0; l < 4; ++l) { w_.ref_conv[l] = ref_pair(ifmt("refine.mlc.layers.%d", l)); w_.dec_conv[l] = ref_pair(ifmt("decoder.mlc.layers.%d", l)); }
+    w_.ref_mlp = ref_pair("refine.mlp.layers.0");
+    w_.lstm_wih = ref("refine.lstm.weight_ih"); w_.lstm_whh = ref("refine.lstm.weight_hh");
+    w_.lstm_bih = ref("refine.lstm.bias_ih"); w_.lstm_bhh = ref("refine.lstm.bias_hh");
+    w_.mean_update = ref_pair("refine.mean_update"); w_.logsig_update = ref_pair("refine.logsig_update");
+    w_.dec_out = ref_pair("decoder.conv");
     layout_workspace(false);
 }
 
@@ -117,13 +125,13 @@ int IodineModel::bind(float* p, float* g, float* m, float* v, void* ws, size_t w
 }
 
 int IodineModel::pack_weights(hipStream_t st) {
-    RC(io_w1_pack_launch(P("decoder.mlc.layers.0.weight"), W1r_, Wxy_, L, st));
-    RC(io_p1_launch(Wxy_, P("decoder.mlc.layers.0.bias"), P1_, S, st));
-    for (int l = 0; l < 3; ++l) RC(conv_pack_launch(P(ifmt("decoder.mlc.layers.%d.weight", l + 1)), pk_[l], pkb_[l], 3, 64, 64, 64, st));
+    RC(io_w1_pack_launch(P(w_.dec_conv[0].w), W1r_, Wxy_, L, st));
+    RC(io_p1_launch(Wxy_, P(w_.dec_conv[0].b), P1_, S, st));
+    for (int l = 0; l < 3; ++l) RC(conv_pack_launch(P(w_.dec_conv[l + 1].w), pk_[l], pkb_[l], 3, 64, 64, 64, st));
     if (conv_x3_ > 0)
-        for (int l = 0; l < 3; ++l) RC(conv_pack_x3_launch(P(ifmt("decoder.mlc.layers.%d.weight", l + 1)), pk3_[l], pkb3_[l], st, 3));
-    RC(bc_c4_pack_launch(P("decoder.conv.weight"), Wk4_, Wb4_, 4, st));
-    for (int l = 0; l < 4; ++l) RC(io_refw_pack_launch(P(ifmt("refine.mlc.layers.%d.weight", l)), Wp_[l], l ? 64 : 17, ldc_[l], st));
+        for (int l = 0; l < 3; ++l) RC(conv_pack_x3_launch(P(w_.dec_conv[l + 1].w), pk3_[l], pkb3_[l], st, 3));
+    RC(bc_c4_pack_launch(P(w_.dec_out.w), Wk4_, Wb4_, 4, st));
+    for (int l = 0; l < 4; ++l) RC(io_refw_pack_launch(P(w_.ref_conv[l].w), Wp_[l], l ? 64 : 17, ldc_[l], st));
     return 0;
 }
 
@@ -135,11 +143,11 @@ int IodineModel::decoder_fwd(int i, hipStream_t st) {
     for (int l = 0; l < 3; ++l) {
         ConvArgs a;
         a.X = c_[l][i]; a.Wp = pk_[l]; a.Y = c_[l + 1][i]; a.B = (int)BK; a.H = S; a.W = S; a.relu = 2;
-        a.bias = P(ifmt("decoder.mlc.layers.%d.bias", l + 1));
+        a.bias = P(w_.dec_conv[l + 1].b);
         if (conv_x3_ > 0) RC(conv_x3_launch(a, pk3_[l], st, 3)); else
         RC(conv_fwd_launch(a, 3, 64, 64, st));
     }
-    RC(bc_c4_fwd_launch(c_[3][i], Wk4_, P("decoder.conv.bias"), out4_[i], (int)BK, S, st));
+    RC(bc_c4_fwd_launch(c_[3][i], Wk4_, P(w_.dec_out.b), out4_[i], (int)BK, S, st));
     return 0;
 }
 
@@ -149,8 +157,8 @@ int IodineModel::decoder_bwd(int i, const float* dout4, bool weights, hipStream_
     if (weights) {
         const int nb = bc_c4_wgrad_blocks((int)BK, S);
         RC(bc_c4_wgrad_launch(c_[3][i], dout4, scratch_, (int)BK, S, st));
-        RC(colsum_launch(scratch_, 2304, G("decoder.conv.weight"), nb, 2304, 1, 1.f, scratch_ + (size_t)nb * 2304, scratch_floats_ - (size_t)nb * 2304, st));
-        RC(colsum_launch(dout4, 4, G("decoder.conv.bias"), BKN, 4, 1, 1.f, scratch_, scratch_floats_, st));
+        RC(colsum_launch(scratch_, 2304, G(w_.dec_out.w), nb, 2304, 1, 1.f, scratch_ + (size_t)nb * 2304, scratch_floats_ - (size_t)nb * 2304, st));
+        RC(colsum_launch(dout4, 4, G(w_.dec_out.b), BKN, 4, 1, 1.f, scratch_, scratch_floats_, st));
     }
     RC(bc_c4_bwd_data_launch(dout4, Wb4_, c_[3][i], gA_, (int)BK, S, st, 1));                        // gA = d pre-activation of layer 3
     float* cur = gA_;
@@ -160,8 +168,8 @@ int IodineModel::decoder_bwd(int i, const float* dout4, bool weights, hipStream_
             WgradArgs w;
             w.X = c_[l][i]; w.dY = cur; w.part = scratch_; w.B = (int)BK; w.H = S; w.W = S;
             OCRL_REQUIRE(conv_wgrad_ws_floats((int)BK, S, S, 3, 64) <= scratch_floats_, "conv wgrad: scratch too small");
-            RC(conv_wgrad_launch(w, 3, 64, 64, 64, G(ifmt("decoder.mlc.layers.%d.weight", l + 1)), 1, st, conv_x3_ > 0 ? 1 : 0));
-            RC(colsum_launch(cur, 64, G(ifmt("decoder.mlc.layers.%d.bias", l + 1)), BKN, 64, 1, 1.f, scratch_, scratch_floats_, st));
+            RC(conv_wgrad_launch(w, 3, 64, 64, 64, G(w_.dec_conv[l + 1].w), 1, st, conv_x3_ > 0 ? 1 : 0));
+            RC(colsum_launch(cur, 64, G(w_.dec_conv[l + 1].b), BKN, 64, 1, 1.f, scratch_, scratch_floats_, st));
         }
         ConvArgs a;
         a.X = cur; a.Wp = pkb_[l]; a.Y = nxt; a.B = (int)BK; a.H = S; a.W = S; a.mask = c_[l][i]; a.mask_elu = 1;
@@ -186,20 +194,20 @@ int IodineModel::refine_fwd(int i, hipStream_t st) {
     for (int l = 0; l < 4; ++l) {
         const int C = l ? 64 : 17, so = rs_[l + 1];
         RC(io_im2col_launch(x, col_, BK, C, rs_[l], rs_[l], ldc_[l], st));
-        RC(lin_fwd(col_, ldc_[l], Wp_[l], P(ifmt("refine.mlc.layers.%d.bias", l)), r_[l][i], 64, BK * so * so, 64, ldc_[l], 2, nullptr, 0, st));
+        RC(lin_fwd(col_, ldc_[l], Wp_[l], P(w_.ref_conv[l].b), r_[l][i], 64, BK * so * so, 64, ldc_[l], 2, nullptr, 0, st));
         x = r_[l][i];
     }
     RC(io_pool_launch(r_[3][i], pool_[i], BK, rs_[4] * rs_[4], st));
-    RC(lin_fwd(pool_[i], 64, P("refine.mlp.layers.0.weight"), P("refine.mlp.layers.0.bias"), mlpa_[i], Hm, BK, Hm, 64, 0, nullptr, 0, st));
+    RC(lin_fwd(pool_[i], 64, P(w_.ref_mlp.w), P(w_.ref_mlp.b), mlpa_[i], Hm, BK, Hm, 64, 0, nullptr, 0, st));
     RC(io_elu2_launch(mlpa_[i], Hm, xin_[i], XW, BK, Hm, nullptr, 0, st));
     const float* hp = i ? hst_[i - 1] : zero_state_;
     const float* cp = i ? cst_[i - 1] : zero_state_;
-    RC(lin_fwd(xin_[i], XW, P("refine.lstm.weight_ih"), P("refine.lstm.bias_ih"), gates_, 4 * Hm, BK, 4 * Hm, XW, 0, nullptr, 0, st));
-    RC(lin_fwd(hp, Hm, P("refine.lstm.weight_hh"), P("refine.lstm.bias_hh"), gates_, 4 * Hm, BK, 4 * Hm, Hm, 0, gates_, 4 * Hm, st));
+    RC(lin_fwd(xin_[i], XW, P(w_.lstm_wih), P(w_.lstm_bih), gates_, 4 * Hm, BK, 4 * Hm, XW, 0, nullptr, 0, st));
+    RC(lin_fwd(hp, Hm, P(w_.lstm_whh), P(w_.lstm_bhh), gates_, 4 * Hm, BK, 4 * Hm, Hm, 0, gates_, 4 * Hm, st));
     RC(io_lstm_fwd_launch(gates_, cp, acts_[i], cst_[i], hst_[i], BK, Hm, st));
     // the reference binds the LSTMCell outputs as (c, h): the update heads read the CELL state (iodine_module.py:418-422)
-    RC(lin_fwd(cst_[i], Hm, P("refine.mean_update.weight"), P("refine.mean_update.bias"), mu_[i + 1], L, BK, L, Hm, 0, mu_[i], L, st));
-    RC(lin_fwd(cst_[i], Hm, P("refine.logsig_update.weight"), P("refine.logsig_update.bias"), ls_[i + 1], L, BK, L, Hm, 0, ls_[i], L, st));
+    RC(lin_fwd(cst_[i], Hm, P(w_.mean_update.w), P(w_.mean_update.b), mu_[i + 1], L, BK, L, Hm, 0, mu_[i], L, st));
+    RC(lin_fwd(cst_[i], Hm, P(w_.logsig_update.w), P(w_.logsig_update.b), ls_[i + 1], L, BK, L, Hm, 0, ls_[i], L, st));
     return 0;
 }
 
@@ -211,8 +219,8 @@ int IodineModel::forward(const float* obs, int B, unsigned long long seed, const
     RC(pack_weights(st));
     RC(fill_launch(parts_, I * 4, 0.f, st));
     // posterior initialisation: every (image, slot) row starts from the shared init vectors (pad_cols with ldi = 0 broadcasts a row)
-    RC(pad_cols_launch(P("slot_mean_init"), 0, mu_[0], L, BK, L, L, st));
-    RC(pad_cols_launch(P("slot_logsig_init"), 0, ls_[0], L, BK, L, L, st));
+    RC(pad_cols_launch(P(w_.mean_init), 0, mu_[0], L, BK, L, L, st));
+    RC(pad_cols_launch(P(w_.logsig_init), 0, ls_[0], L, BK, L, L, st));
     for (int i = 0; i < I; ++i) {
         const bool last = i == I - 1;
         RC(io_sample_launch(mu_[i], ls_[i], noise ? noise + (size_t)i * BK * L : nullptr, eps_[i], slots_[i], parts_ + i * 4 + 2, BK * L, seed,
@@ -239,26 +247,26 @@ int IodineModel::refine_bwd(int i, hipStream_t st) {
     const long long BK = (long long)B_ * K;
     const bool top = i == I - 2;                  // the last refinement step has no successor: no carried state gradients
     // heads: mu[i+1] = mu[i] + c W_m^T + b_m (same for logsig)
-    RC(lin_bwd_x(gmu_, L, P("refine.mean_update.weight"), dcH_, Hm, BK, L, Hm, nullptr, 0, top ? nullptr : dc_, Hm, st));
-    RC(lin_bwd_x(gls_, L, P("refine.logsig_update.weight"), dcH_, Hm, BK, L, Hm, nullptr, 0, dcH_, Hm, st));
-    RC(lin_bwd_w(gmu_, L, cst_[i], Hm, G("refine.mean_update.weight"), nullptr, BK, L, Hm, 1.f, scratch_, scratch_floats_, st, Drop(), Xf(), 1));
-    RC(colsum_launch(gmu_, L, G("refine.mean_update.bias"), BK, L, 1, 1.f, scratch_, scratch_floats_, st));
-    RC(lin_bwd_w(gls_, L, cst_[i], Hm, G("refine.logsig_update.weight"), nullptr, BK, L, Hm, 1.f, scratch_, scratch_floats_, st, Drop(), Xf(), 1));
-    RC(colsum_launch(gls_, L, G("refine.logsig_update.bias"), BK, L, 1, 1.f, scratch_, scratch_floats_, st));
+    RC(lin_bwd_x(gmu_, L, P(w_.mean_update.w), dcH_, Hm, BK, L, Hm, nullptr, 0, top ? nullptr : dc_, Hm, st));
+    RC(lin_bwd_x(gls_, L, P(w_.logsig_update.w), dcH_, Hm, BK, L, Hm, nullptr, 0, dcH_, Hm, st));
+    RC(lin_bwd_w(gmu_, L, cst_[i], Hm, G(w_.mean_update.w), nullptr, BK, L, Hm, 1.f, scratch_, scratch_floats_, st, Drop(), Xf(), 1));
+    RC(colsum_launch(gmu_, L, G(w_.mean_update.b), BK, L, 1, 1.f, scratch_, scratch_floats_, st));
+    RC(lin_bwd_w(gls_, L, cst_[i], Hm, G(w_.logsig_update.w), nullptr, BK, L, Hm, 1.f, scratch_, scratch_floats_, st, Drop(), Xf(), 1));
+    RC(colsum_launch(gls_, L, G(w_.logsig_update.b), BK, L, 1, 1.f, scratch_, scratch_floats_, st));
     const float* hp = i ? hst_[i - 1] : zero_state_;
     const float* cp = i ? cst_[i - 1] : zero_state_;
     RC(io_lstm_bwd_launch(acts_[i], cp, cst_[i], top ? nullptr : dh_, dcH_, dgates_, dc_, BK, Hm, st));     // dc_ = gradient wrt c_{i-1}
-    RC(lin_bwd_x(dgates_, 4 * Hm, P("refine.lstm.weight_ih"), dxin_, XW, BK, 4 * Hm, XW, nullptr, 0, nullptr, 0, st));
-    RC(lin_bwd_x(dgates_, 4 * Hm, P("refine.lstm.weight_hh"), dh_, Hm, BK, 4 * Hm, Hm, nullptr, 0, nullptr, 0, st));  // dh_ = gradient wrt h_{i-1}
-    RC(lin_bwd_w(dgates_, 4 * Hm, xin_[i], XW, G("refine.lstm.weight_ih"), nullptr, BK, 4 * Hm, XW, 1.f, scratch_, scratch_floats_, st, Drop(), Xf(), 1));
-    RC(colsum_launch(dgates_, 4 * Hm, G("refine.lstm.bias_ih"), BK, 4 * Hm, 1, 1.f, scratch_, scratch_floats_, st));
-    RC(lin_bwd_w(dgates_, 4 * Hm, hp, Hm, G("refine.lstm.weight_hh"), nullptr, BK, 4 * Hm, Hm, 1.f, scratch_, scratch_floats_, st, Drop(), Xf(), 1));
-    RC(colsum_launch(dgates_, 4 * Hm, G("refine.lstm.bias_hh"), BK, 4 * Hm, 1, 1.f, scratch_, scratch_floats_, st));
+    RC(lin_bwd_x(dgates_, 4 * Hm, P(w_.lstm_wih), dxin_, XW, BK, 4 * Hm, XW, nullptr, 0, nullptr, 0, st));
+    RC(lin_bwd_x(dgates_, 4 * Hm, P(w_.lstm_whh), dh_, Hm, BK, 4 * Hm, Hm, nullptr, 0, nullptr, 0, st));  // dh_ = gradient wrt h_{i-1}
+    RC(lin_bwd_w(dgates_, 4 * Hm, xin_[i], XW, G(w_.lstm_wih), nullptr, BK, 4 * Hm, XW, 1.f, scratch_, scratch_floats_, st, Drop(), Xf(), 1));
+    RC(colsum_launch(dgates_, 4 * Hm, G(w_.lstm_bih), BK, 4 * Hm, 1, 1.f, scratch_, scratch_floats_, st));
+    RC(lin_bwd_w(dgates_, 4 * Hm, hp, Hm, G(w_.lstm_whh), nullptr, BK, 4 * Hm, Hm, 1.f, scratch_, scratch_floats_, st, Drop(), Xf(), 1));
+    RC(colsum_launch(dgates_, 4 * Hm, G(w_.lstm_bhh), BK, 4 * Hm, 1, 1.f, scratch_, scratch_floats_, st));
     // MLP with the double ELU
     RC(io_elu2_launch(mlpa_[i], Hm, da_, Hm, BK, Hm, dxin_, XW, st));
-    RC(lin_bwd_x(da_, Hm, P("refine.mlp.layers.0.weight"), dpool_, 64, BK, Hm, 64, nullptr, 0, nullptr, 0, st));
-    RC(lin_bwd_w(da_, Hm, pool_[i], 64, G("refine.mlp.layers.0.weight"), nullptr, BK, Hm, 64, 1.f, scratch_, scratch_floats_, st, Drop(), Xf(), 1));
-    RC(colsum_launch(da_, Hm, G("refine.mlp.layers.0.bias"), BK, Hm, 1, 1.f, scratch_, scratch_floats_, st));
+    RC(lin_bwd_x(da_, Hm, P(w_.ref_mlp.w), dpool_, 64, BK, Hm, 64, nullptr, 0, nullptr, 0, st));
+    RC(lin_bwd_w(da_, Hm, pool_[i], 64, G(w_.ref_mlp.w), nullptr, BK, Hm, 64, 1.f, scratch_, scratch_floats_, st, Drop(), Xf(), 1));
+    RC(colsum_launch(da_, Hm, G(w_.ref_mlp.b), BK, Hm, 1, 1.f, scratch_, scratch_floats_, st));
     // stride-2 convolutions, last to first
     float* dpre = dr_[0];
     float* other = dr_[1];
@@ -269,7 +277,7 @@ int IodineModel::refine_bwd(int i, hipStream_t st) {
         const float* x = l ? r_[l - 1][i] : enc_[i];
         RC(io_im2col_launch(x, col_, BK, C, rs_[l], rs_[l], ldc_[l], st));
         RC(lin_bwd_w(dpre, 64, col_, ldc_[l], dWp_[l], nullptr, rows, 64, ldc_[l], 1.f, scratch_, scratch_floats_, st, Drop(), Xf(), 1));
-        RC(colsum_launch(dpre, 64, G(ifmt("refine.mlc.layers.%d.bias", l)), rows, 64, 1, 1.f, scratch_, scratch_floats_, st));
+        RC(colsum_launch(dpre, 64, G(w_.ref_conv[l].b), rows, 64, 1, 1.f, scratch_, scratch_floats_, st));
         RC(lin_bwd_x(dpre, 64, Wp_[l], dcol_, ldc_[l], rows, 64, ldc_[l], nullptr, 0, nullptr, 0, st));
         if (l) {
             RC(io_col2im_launch(dcol_, r_[l - 1][i], other, BK, 64, rs_[l], rs_[l], ldc_[l], st));
@@ -298,10 +306,10 @@ int IodineModel::backward(hipStream_t st) {
         RC(decoder_bwd(i, dout4_, true, st));
         RC(io_post_grad_launch(mu_[i], ls_[i], eps_[i], dslots_, last ? nullptr : dxin_ + Hm, XW, w * cfg.beta / (float)B_, gmu_, gls_, BK, L, st));
     }
-    RC(colsum_launch(gmu_, L, G("slot_mean_init"), BK, L, 0, 1.f, scratch_, scratch_floats_, st));
-    RC(colsum_launch(gls_, L, G("slot_logsig_init"), BK, L, 0, 1.f, scratch_, scratch_floats_, st));
-    RC(io_w1_grad_launch(dW1r_, G1_, G("decoder.mlc.layers.0.weight"), G("decoder.mlc.layers.0.bias"), S, L, st));
-    for (int l = 0; l < 4; ++l) RC(io_refw_unpack_launch(dWp_[l], G(ifmt("refine.mlc.layers.%d.weight", l)), l ? 64 : 17, ldc_[l], st));
+    RC(colsum_launch(gmu_, L, G(w_.mean_init), BK, L, 0, 1.f, scratch_, scratch_floats_, st));
+    RC(colsum_launch(gls_, L, G(w_.logsig_init), BK, L, 0, 1.f, scratch_, scratch_floats_, st));
+    RC(io_w1_grad_launch(dW1r_, G1_, G(w_.dec_conv[0].w), G(w_.dec_conv[0].b), S, L, st));
+    for (int l = 0; l < 4; ++l) RC(io_refw_unpack_launch(dWp_[l], G(w_.ref_conv[l].w), l ? 64 : 17, ldc_[l], st));
     have_fwd_ = false;
     return 0;
 }
@@ -313,8 +321,7 @@ int IodineModel::grad_norm(hipStream_t st) { return io_l2norm_launch(g_, flat_si
 int IodineModel::clip_adam(float lr, float clip, int step, float gscale, hipStream_t st) {
     OCRL_REQUIRE(m_ && v_, "clip_adam: optimiser state not bound");
     RC(grad_norm(st));
-    const ParamInfo& skip = param("slot_init");
-    const long long a1 = skip.offset, b0 = skip.offset + padded(skip.numel);
+    const long long a1 = w_.skip_begin, b0 = w_.skip_end;
     RC(clip_adam_launch(p_, g_, m_, v_, a1, metrics_ + 3, clip, lr, 0.9, 0.999, 1e-8, step, gscale, st));
     RC(clip_adam_launch(p_ + b0, g_ + b0, m_ + b0, v_ + b0, flat_size_ - b0, metrics_ + 3, clip, lr, 0.9, 0.999, 1e-8, step, gscale, st));
     return 0;

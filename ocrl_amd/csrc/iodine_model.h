@@ -35,6 +35,13 @@ private:
     int refine_fwd(int i, hipStream_t st);
     int refine_bwd(int i, hipStream_t st);                                         // -> denc_, dxin_ (latent part)
 
+    // parameters, resolved once by the constructor
+    struct Weights {
+        ParamRef mean_init, logsig_init, lstm_wih, lstm_whh, lstm_bih, lstm_bhh;
+        ParamPair ref_conv[4], ref_mlp, mean_update, logsig_update, dec_conv[4], dec_out;
+        long long skip_begin = 0, skip_end = 0;       // `slot_init`, which the optimiser leaves alone
+    } w_;
+
     int S, N, K, I, L, Hm, Bmax, XW;          // XW = Hm + 4L (LSTM input width)
     int rs_[5];                               // spatial side of the refinement feature maps: S, S/2, ...
     int B_ = 0;

@@ -19,6 +19,11 @@ struct ParamInfo {
     int group = 0;          // optimiser group (SLATE: 0 dvae, 1 slot-attention side, 2 transformer decoder; IODINE has one)
 };
 
+// A parameter resolved by name once, when the model is created: its element offset into the flat buffers.  An offset, not a pointer:
+// bind() may be called again with other buffers.  ModelBase::P / G turn it into the parameter / gradient pointer of the current binding.
+struct ParamRef { long long off = 0; };
+struct ParamPair { ParamRef w, b; };       // "<prefix>.weight" and "<prefix>.bias" of one layer
+
 class ModelBase {
 public:
     ModelBase(const ModelBase&) = delete;
@@ -27,6 +32,9 @@ public:
     long long flat_size() const { return flat_size_; }
     size_t workspace_bytes() const { return ws_bytes_; }
     float* metrics() const { return metrics_; }                 // device float[8], carved by the model's layout
+    // empty, or what made the constructor's resolve fail (the first name that is not in the parameter table): the create entry point
+    // reports it and discards the model
+    const std::string& create_error() const { return create_error_; }
     int tensor(const char* name, float** ptr, long long* count) const {
         auto it = named_.find(name);
         if (it == named_.end()) {
@@ -67,9 +75,17 @@ protected:
         while (g < groups) group_begin[++g] = off;
         flat_size_ = off;
     }
-    const ParamInfo& param(const std::string& n) const { return params_[index_.at(n)]; }
-    float* P(const std::string& n) const { return p_ + param(n).offset; }
-    float* G(const std::string& n) const { return g_ + param(n).offset; }
+    // by-name lookup for the constructors only (after finish_params()): the step path holds ParamRefs, so a misspelt name fails the
+    // create call whatever branch would have used it, and no launch builds a string or searches the index
+    ParamRef ref(const std::string& n) {
+        auto it = index_.find(n);
+        if (it != index_.end()) return ParamRef{params_[it->second].offset};
+        if (create_error_.empty()) create_error_ = "unknown parameter '" + n + "'";
+        return ParamRef();
+    }
+    ParamPair ref_pair(const std::string& prefix) { return ParamPair{ref(prefix + ".weight"), ref(prefix + ".bias")}; }
+    float* P(ParamRef r) const { return p_ + r.off; }
+    float* G(ParamRef r) const { return g_ + r.off; }
 
     // ---- workspace: a layout pass is begin_layout(), the model's carve() calls in a fixed order (the order is the layout),
     // end_layout().  The constructor runs it without a buffer (commit = false) to size the workspace, bind() on the caller's.
@@ -107,4 +123,5 @@ protected:
     bool ws_commit_ = false;
     std::map<std::string, std::pair<float*, size_t>> named_;
     float* metrics_ = nullptr;
+    std::string create_error_;
 };

@@ -1,5 +1,5 @@
 // SLATE training-step orchestration over the HIP kernels (host code).  One object per process
-// per GPU; not thread-safe; every launch goes to the caller's stream.
+// per GPU; not thread-safe; every launch goes to the caller's stream or to a side stream ordered against it (Lane).
 #pragma once
 #include <map>
 #include <string>
@@ -31,6 +31,16 @@ struct StepInputs {
     const unsigned long long* seed_dev = nullptr;   // internal: the slot-noise seed read from device memory (captured encode graphs)
 };
 
+// A lane is a stream together with the transient scratch (split-k slabs, column-sum partials, wgrad slabs) that launches on it may
+// use: lanes run concurrently, so each has a region of its own, and every launcher that needs scratch takes it from the lane it
+// launches on.  Passed where a launcher expects the stream.
+struct Lane {
+    hipStream_t st = nullptr;
+    float* scratch = nullptr;
+    size_t scratch_floats = 0;
+    operator hipStream_t() const { return st; }
+};
+
 class SlateModel : public ModelBase {
 public:
     explicit SlateModel(const SlateConfig& c);
@@ -55,32 +65,70 @@ public:
 
 private:
     void layout_workspace(bool commit);
-    // the Linear helpers of gemm.hip with this step's dropout seed and the current scratch (lin_bwd_x is used as it is)
+    // the Linear helpers of gemm.hip with this step's dropout seed and the lane's scratch (lin_bwd_x is used as it is)
     int lin_fwd(const float* x, int ldx, const float* W, const float* b, float* y, int ldy, long long M, int N, int K, int relu,
                 const float* resid, int ldr, float drop_p, unsigned site, hipStream_t st) {
         return ::lin_fwd(x, ldx, W, b, y, ldy, M, N, K, relu, resid, ldr, st, Drop{drop_p, last_.seed, site});
     }
     int lin_bwd_w(const float* dy, int ld_dy, const float* x, int ldx, float* dW, float* db, long long M, int N_out, int K_in,
-                  float alpha, hipStream_t st, Xf xf = Xf()) {
-        return ::lin_bwd_w(dy, ld_dy, x, ldx, dW, db, M, N_out, K_in, alpha, scratch_, scratch_floats_, st, Drop(), xf);
+                  float alpha, const Lane& L, Xf xf = Xf()) {
+        return ::lin_bwd_w(dy, ld_dy, x, ldx, dW, db, M, N_out, K_in, alpha, L.scratch, L.scratch_floats, L.st, Drop(), xf);
     }
     // the Gumbel / cross-entropy soft-max heads live in the vocabulary GEMMs (soft samples; the straight-through `hard` form keeps z)
     bool fused_heads() const { return !cfg.hard; }
     int conv_layer_fwd(const float* x, const float* pack, const float* bias, float* y, int Bn, int Hh, int Ww, int KS, int CIN, int relu,
-                       const float* posmap, const float* mask, hipStream_t st);
+                       const float* posmap, const float* mask, const Lane& L);
     int conv_layer_wgrad(const float* x, const float* dy, float* dW, float* db, int Bn, int Hh, int Ww, int KS, int CIN, int cin_real,
-                         hipStream_t st);
-    int pack_weights(hipStream_t st, bool encoder_only = false);
-    int fwd_encoder(const StepInputs& in, hipStream_t st, int fork_dvae = 0);
-    int fwd_dvae(const StepInputs& in, hipStream_t st);
-    int fwd_decoder(hipStream_t st, bool with_ce = true);
-    int dvae_decode(int B, float* drecon, hipStream_t st, const float* zin = nullptr);
-    int bwd_decoder(hipStream_t st);
-    int bwd_encoder(hipStream_t st, bool fork_dvae = false);
-    int bwd_dvae(hipStream_t st);
-    int pack_bcdec(hipStream_t st);
-    int fwd_bcdec(hipStream_t st);
-    int bwd_bcdec(hipStream_t st);
+                         const Lane& L);
+    int pack_weights(const Lane& L, bool encoder_only = false);
+    int fwd_encoder(const StepInputs& in, const Lane& L, int fork_dvae = 0);
+    int fwd_dvae(const StepInputs& in, const Lane& L);
+    int fwd_decoder(const Lane& L, bool with_ce = true);
+    int dvae_decode(int B, float* drecon, const Lane& L, const float* zin = nullptr);
+    int bwd_decoder(const Lane& L);
+    int bwd_encoder(const Lane& L, bool fork_dvae = false);
+    int bwd_dvae(const Lane& L);
+    int pack_bcdec(const Lane& L);
+    int fwd_bcdec(const Lane& L);
+    int bwd_bcdec(const Lane& L);
+    AttnArgs self_attn_args(int b) const;          // the fields of block b's causal self attention that forward and backward share
+    XaHost xattn_args(int b) const;                // the same for its folded cross attention
+
+    // ---- the three lanes.  The scratch pointers are assigned in layout_workspace and nowhere else.
+    Lane main_lane(hipStream_t st) const { return Lane{st, scratch_, scratch_floats_}; }      // the caller's stream
+    Lane dvae_lane() const { return Lane{side_, scratch2_, scratch_floats_}; }                // the dVAE branch (under use_bcdec, which has none, scratch2_ == scratch_)
+    // The decoder's weight-gradient products: a stream of their own (OCRL_DW_SIDE=2), the dVAE lane (1) or the main lane (0).  The
+    // operands such a product reads are never rewritten by the main stream during this backward: saved activations, and the per-block
+    // gradient temporaries bg_[b] (bwd_decoder selects bg_[b] when this lane is not the main one, bg_[0] otherwise).
+    Lane dw_lane(const Lane& main) const { return dw_mode_ == 2 ? Lane{side2_, scratch3_, scratch_floats_} : dw_mode_ ? dvae_lane() : main; }
+    // The one ordering primitive: everything enqueued on `producer` so far happens before whatever is enqueued on `waiter` from now
+    // on (records `ev` on producer.st, makes waiter.st wait for it; nothing when both are the same stream).  Each call site passes the
+    // event object it has always used -- ev_fork_ (main -> dVAE lane), ev_join_ (dVAE lane -> main), ev_join2_ (weight-gradient stream
+    // -> main), the ring (main -> weight-gradient lane, and back at the end of bwd_decoder) -- so a step issues the same record / wait
+    // pairs in the same order as when they were written out at each site (one record moved: the cross-attention fold's ev_join2_ is
+    // recorded where it is awaited, in fwd_decoder, not right after the fold -- nothing is enqueued on that stream in between, so it
+    // marks the same point).  ev_tokens_ alone is recorded in one place (fwd_dvae, in the middle of the dVAE lane's work) and awaited
+    // in another (forward).
+    int after(const Lane& waiter, const Lane& producer, hipEvent_t ev);
+    hipEvent_t ring_event() { return ev_dw_[ev_dw_next_++ & 7]; }
+
+    // ---- parameters, resolved once by the constructor (resolve_params)
+    struct DecBlockW { ParamPair ln1, ln2, ln3, ffn0, ffn2; ParamRef qkv, o, cq, ck, cv, co; };     // qkv: proj_q, with proj_k / proj_v behind it
+    struct SlotAttnW {
+        ParamRef mu, log_sigma, q, k, v, gru_wih, gru_whh, gru_bih, gru_bhh;
+        ParamPair ln, mlp0, mlp2, norm_inputs, norm_slots, norm_mlp, m0, m2;          // ln / mlp0 / mlp2: the input LayerNorm + MLP
+    };
+    struct Weights {
+        ParamPair dvae_enc[8], dvae_dec[12];       // by the reference's Sequential index (decoder 5 and 10 are pixel shuffles)
+        ParamPair enc[4], enc_pos;                 // CNN encoder, positional map
+        SlotAttnW sa;
+        ParamPair bc[4], bc_pos;                   // broadcast decoder (use_bcdec)
+        ParamRef slotproj, dict, bos, pe, out;
+        ParamPair lnf;
+        std::vector<DecBlockW> blk;
+        long long enc_grads_end = 0;               // encode_backward() fills [group_begin(1), enc_grads_end): group 1 up to the slot projection / broadcast decoder
+    } w_;
+    void resolve_params();
 
     long long group_begin_[4] = {0, 0, 0, 0};
 
@@ -98,14 +146,12 @@ private:
     bool have_scores_ = false;        // zraw_ holds the Gumbel scores of last_ (not yet overwritten by their gradient)
 
     // ---- workspace tensors
-    float *scratch_ = nullptr;            // transient: split-k slabs, column-sum partials, wgrad slabs
+    float *scratch_ = nullptr;            // transient: split-k slabs, column-sum partials, wgrad slabs (main lane)
     size_t scratch_floats_ = 0;
-    float* scratch2_ = nullptr;           // scratch of the dVAE branch when it runs on the side stream
+    float* scratch2_ = nullptr;           // scratch of the dVAE lane
     int overlap_mode_ = 0;                // OCRL_OVERLAP 0..5 (default 5), described where it is read in SlateModel::bind
     hipStream_t side_ = nullptr;          // dVAE forward / backward overlap the encoder + decoder work (independent branches)
     hipEvent_t ev_fork_ = nullptr, ev_join_ = nullptr, ev_tokens_ = nullptr;
-    int fork_side(hipStream_t st);
-    int join_side(hipStream_t st);
     float *zstat_ = nullptr, *zhstat_ = nullptr, *zlse_ = nullptr, *zdot_ = nullptr, *cestat_ = nullptr, *celse_ = nullptr, *cepart_ = nullptr;
     int* zhidx_ = nullptr;
     float *obs8_, *patches_, *de_[7], *zraw_, *z_, *zdec_;      // zdec_: what the dVAE decoder consumes (z_ or its straight-through form)
@@ -151,7 +197,7 @@ private:
     unsigned long long* seed_dev_ = nullptr;
     int dw_mode_ = 0;                     // OCRL_DW_SIDE: 0 weight gradients of the decoder on the main stream, 1 on the dVAE side stream, 2 on a stream of their own
     hipStream_t side2_ = nullptr;
-    float* scratch3_ = nullptr;
+    float* scratch3_ = nullptr;           // scratch of the weight-gradient stream
     hipEvent_t ev_dw_[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     hipEvent_t ev_join2_ = nullptr;
     int ev_dw_next_ = 0;

@@ -492,6 +492,57 @@ def test_execution_switches_agree(monkeypatch):
             assert 0.0 < d < 2e-5, (env, d)          # a different kernel really ran, and agrees
 
 
+STREAM_MODES = [     # (OCRL_OVERLAP, OCRL_DW_SIDE, OCRL_SA_INPUT, OCRL_TOKENS_LATE or None)
+    ("mid", MID, [("5", "2", "1", None), ("5", "1", "1", None), ("5", "0", "0", None), ("3", "2", "2", None), ("4", "1", "1", "1"),
+                  ("2", "2", "1", None), ("1", "2", "0", None)]),       # overlap 2 keeps the weight gradients on the main stream
+    ("bc32", BC32, [("0", "2", "1", None), ("3", "2", "1", None), ("5", "2", "1", None)]),    # the dVAE side's scratch is the main one's
+]
+
+
+@pytest.mark.parametrize("tag,over,modes", STREAM_MODES, ids=[m[0] for m in STREAM_MODES])
+def test_stream_modes_keep_every_bit(tag, over, modes, monkeypatch):
+    """The stream switches in combination, and under use_bcdec (the two tests above vary one switch at a time under the default of the
+    others): which stream a launch goes to, and which scratch region it is handed with it, changes no bit of the losses or of the flat
+    gradient against the single-stream engine (OCRL_OVERLAP=0).  OCRL_SA_INPUT is no stream switch -- the fused backward sums six
+    gradients in another order -- so each combination is held against the single-stream engine with its own
+    OCRL_SA_INPUT.  B = 3 leaves the image-pair grouping of the slot side a ragged group; two steps per engine, because the buffers are
+    reused across steps.  OCRL_XATTN / OCRL_CONV_X3 change the summation order too and stay pinned."""
+    cfg = O.default_cfg(**over)
+    B = 3
+    P = O.formula_params(cfg)
+    obs = torch.rand(B, 3, cfg.obs_size, cfg.obs_size, generator=torch.Generator().manual_seed(3)).cuda()
+    noise = O.make_noise(cfg, B, 9)
+    noise = dict(slots=noise["slots"].contiguous().cuda()) if over.get("use_bcdec") else dev_noise(cfg, noise)
+    monkeypatch.setenv("OCRL_XATTN", "1")
+    monkeypatch.setenv("OCRL_CONV_X3", "0")
+
+    def run(overlap, dw, sa_in, late):
+        monkeypatch.setenv("OCRL_OVERLAP", overlap)
+        monkeypatch.setenv("OCRL_DW_SIDE", dw)
+        monkeypatch.setenv("OCRL_SA_INPUT", sa_in)
+        if late is None:
+            monkeypatch.delenv("OCRL_TOKENS_LATE", raising=False)
+        else:
+            monkeypatch.setenv("OCRL_TOKENS_LATE", late)
+        eng = make_engine(cfg, B)
+        load_params(eng, P)
+        for _ in range(2):
+            eng.forward(obs, 0.9, train=True, seed=5, noise=noise)
+            eng.backward()
+        torch.cuda.synchronize()
+        return eng.metrics.cpu()[:3].clone(), eng.flat_g.cpu().clone()
+
+    single = {}        # OCRL_SA_INPUT -> the single-stream engine's result
+    for mode in modes:
+        sa_in = mode[2]
+        if sa_in not in single:
+            single[sa_in] = run("0", "2", sa_in, None)
+            assert float(single[sa_in][1].abs().max()) > 0.0
+        m, g = run(*mode)
+        assert torch.equal(m, single[sa_in][0]), mode
+        assert torch.equal(g, single[sa_in][1]), mode
+
+
 def test_full_size_batch_additivity():
     """BASELINE config A shapes (128x128, 6 slots, 3 iterations, vocab 4096, 4 decoder blocks) are beyond the CPU oracle's reach in
     a test; the domain's size-independent property is additivity over images: every loss is sum/B and no operator mixes images, so
