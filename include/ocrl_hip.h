@@ -159,7 +159,8 @@ int ocrl_conv2d_bwd_data_x3(const float* dy, const float* w, const float* mask, 
 int ocrl_conv2d_bwd_weight_x3(const float* x, const float* dy, float* dw, int B, int H, int W, int ks, float* ws, size_t ws_floats, void* stream);
 /* grad wrt input of the same conv (square 64->64 layers): dx = conv_transpose(dy, w) * (mask > 0 if mask). ws: 2*ks*ks*64*64 floats. */
 int ocrl_conv2d_bwd_data(const float* dy, const float* w, const float* mask, float* dx, int B, int H, int W, int ks, float* ws, void* stream);
-/* grad wrt weight (reference layout [64,cin,ks,ks]) and bias [64] (may be NULL); ws from ocrl_conv2d_wgrad_ws_floats. */
+/* grad wrt weight (reference layout [64,cin,ks,ks]) and bias [64] (may be NULL); ws from ocrl_conv2d_wgrad_ws_floats: the kernel's
+ * partial dW slabs, then 65536 floats that hold its bias partials (64 per slab). */
 size_t ocrl_conv2d_wgrad_ws_floats(int B, int H, int W, int ks, int cin_pad);
 int ocrl_conv2d_bwd_weight(const float* x, const float* dy, float* dw, float* db, int B, int H, int W, int cin, int cin_pad, int ks,
                            float* ws, size_t ws_floats, void* stream);
@@ -189,6 +190,16 @@ typedef struct ocrl_conv_wgrad_desc {
 } ocrl_conv_wgrad_desc;
 size_t ocrl_conv_wgrad_desc_size(void);
 int ocrl_conv2d_bwd_weight_ex(const ocrl_conv_wgrad_desc* d, float* ws, size_t ws_floats, void* stream);
+/* The encoder's first layer alone: 5x5, 3 -> 64 channels, stride 1, padding 2, on the NCHW observation obs [B,3,H,W] (no channel padding,
+ * no NHWC copy).  y [B,H,W,64] = conv(obs, w [64,3,5,5]) + bias (may be NULL), ReLU if relu = 1.  An image's result does not depend on B. */
+size_t ocrl_conv2d_first_fwd_ws_floats(void);
+int ocrl_conv2d_first_fwd(const float* obs, const float* w, const float* bias, float* y, int B, int H, int W, int relu, float* ws, size_t ws_floats,
+                          void* stream);
+/* its weight gradient dw [64,3,5,5] and bias gradient db [64] (may be NULL) from dy [B,H,W,64], without a patch matrix; accumulate = 1 adds
+ * to dw / db.  The workspace holds one partial of 64 * 96 + 64 floats per worker (at most 512, one per 4 x 32 pixel tile below that). */
+size_t ocrl_conv2d_first_wgrad_ws_floats(int B, int H, int W);
+int ocrl_conv2d_first_bwd_weight(const float* obs, const float* dy, float* dw, float* db, int B, int H, int W, int accumulate, float* ws, size_t ws_floats,
+                                 void* stream);
 /* nn.LayerNorm(F) forward / backward over R rows (F in {64,128,192,256}); dgb = [dgamma | dbeta]. */
 int ocrl_layernorm_fwd(const float* x, const float* gamma, const float* beta, float* y, float* mean, float* rstd, long long R, int F, void* stream);
 int ocrl_layernorm_bwd(const float* dy, const float* x, const float* mean, const float* rstd, const float* gamma, float* dx, float* dgb,

@@ -169,6 +169,11 @@ def lib():
             raise RuntimeError(f"libocrl_hip.so: {name} is {n} bytes, this binding's {cls.__name__} {ctypes.sizeof(cls)}")
     L.ocrl_conv2d_ex.argtypes = [POINTER(ConvDesc), p, c_size_t, p]
     L.ocrl_conv2d_bwd_weight_ex.argtypes = [POINTER(ConvWgradDesc), p, c_size_t, p]
+    L.ocrl_conv2d_first_fwd_ws_floats.restype = c_size_t
+    L.ocrl_conv2d_first_fwd.argtypes = [p, p, p, p, c_int, c_int, c_int, c_int, p, c_size_t, p]
+    L.ocrl_conv2d_first_wgrad_ws_floats.argtypes = [c_int, c_int, c_int]
+    L.ocrl_conv2d_first_wgrad_ws_floats.restype = c_size_t
+    L.ocrl_conv2d_first_bwd_weight.argtypes = [p, p, p, p, c_int, c_int, c_int, c_int, p, c_size_t, p]
     L.ocrl_layernorm_fwd.argtypes = [p, p, p, p, p, p, c_longlong, c_int, p]
     L.ocrl_layernorm_bwd.argtypes = [p, p, p, p, p, p, p, c_longlong, c_int, p, c_size_t, p]
     L.ocrl_sa_input_plan.argtypes = [c_longlong, POINTER(c_int * 3)]

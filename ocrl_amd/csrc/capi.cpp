@@ -242,22 +242,24 @@ int ocrl_conv2d_bwd_data(const float* dy, const float* w, const float* mask, flo
     a.X = dy; a.Wp = bw; a.Y = dx; a.B = B; a.H = H; a.W = W; a.mask = mask;
     return conv_fwd_launch(a, ks, 64, 64, ST(stream));
 }
-size_t ocrl_conv2d_wgrad_ws_floats(int B, int H, int W, int ks, int cin_pad) { return conv_wgrad_ws_floats(B, H, W, ks, cin_pad) + (1 << 16); }
+// the dW slabs plus 65536 floats, which hold the bias partials (64 per slab, at most 204 slabs)
+size_t ocrl_conv2d_wgrad_ws_floats(int B, int H, int W, int ks, int cin_pad) {
+    const size_t slabs = (size_t)conv_wgrad_slabs(B, H, W, ks, cin_pad);
+    return slabs * ks * ks * 64 * cin_pad + (1 << 16);
+}
 int ocrl_conv2d_bwd_weight(const float* x, const float* dy, float* dw, float* db, int B, int H, int W, int cin, int cin_pad, int ks, float* ws,
                            size_t ws_floats, void* stream) {
     if (ws_floats < ocrl_conv2d_wgrad_ws_floats(B, H, W, ks, cin_pad)) { ocrl_set_error("ocrl_conv2d_bwd_weight: workspace too small"); return 1; }
     WgradArgs a;
     a.X = x; a.dY = dy; a.part = ws; a.B = B; a.H = H; a.W = W;
-    if (conv_wgrad_launch(a, ks, cin_pad, 64, cin, dw, 0, ST(stream), 0)) return 1;
-    if (db) return colsum_launch(dy, 64, db, (long long)B * H * W, 64, 0, 1.f, ws, ws_floats, ST(stream));
-    return 0;
+    return conv_wgrad_launch(a, ks, cin_pad, 64, cin, dw, db, 0, ST(stream), 0);
 }
 int ocrl_conv2d_bwd_weight_x3(const float* x, const float* dy, float* dw, int B, int H, int W, int ks, float* ws, size_t ws_floats, void* stream) {
     if (ks != 3 && ks != 5) { ocrl_set_error("ocrl_conv2d_bwd_weight_x3: ks must be 3 or 5"); return 1; }
     if (ws_floats < ocrl_conv2d_wgrad_ws_floats(B, H, W, ks, 64)) { ocrl_set_error("ocrl_conv2d_bwd_weight_x3: workspace too small"); return 1; }
     WgradArgs a;
     a.X = x; a.dY = dy; a.part = ws; a.B = B; a.H = H; a.W = W;
-    return conv_wgrad_launch(a, ks, 64, 64, 64, dw, 0, ST(stream), 1);
+    return conv_wgrad_launch(a, ks, 64, 64, 64, dw, nullptr, 0, ST(stream), 1);
 }
 static bool conv_kernel_built(int ks, int cin_pad) { return (ks == 5 && (cin_pad == 64 || cin_pad == 8)) || (ks == 3 && cin_pad == 64); }
 static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
@@ -295,9 +297,24 @@ int ocrl_conv2d_bwd_weight_ex(const ocrl_conv_wgrad_desc* d, float* ws, size_t w
     const int acc = d->accumulate ? 1 : 0;
     WgradArgs a;
     a.X = d->x; a.dY = d->dy; a.part = ws; a.B = d->B; a.H = d->H; a.W = d->W;
-    if (conv_wgrad_launch(a, d->ks, d->cin_pad, 64, d->cin, d->dw, acc, ST(stream), 0)) return 1;
-    if (d->db) return colsum_launch(d->dy, 64, d->db, (long long)d->B * d->H * d->W, 64, acc, 1.f, ws, ws_floats, ST(stream));
-    return 0;
+    return conv_wgrad_launch(a, d->ks, d->cin_pad, 64, d->cin, d->dw, d->db, acc, ST(stream), 0);
+}
+size_t ocrl_conv2d_first_fwd_ws_floats(void) { return conv_first_pack_floats(); }
+int ocrl_conv2d_first_fwd(const float* obs, const float* w, const float* bias, float* y, int B, int H, int W, int relu, float* ws, size_t ws_floats,
+                          void* stream) {
+    if (!obs || !w || !y || !ws || B < 1 || H < 1 || W < 1) { ocrl_set_error("ocrl_conv2d_first_fwd: obs, w, y, ws and a non-empty image are required"); return 1; }
+    if (relu < 0 || relu > 1) { ocrl_set_error("ocrl_conv2d_first_fwd: relu must be 0 or 1, got %d", relu); return 1; }
+    if (ws_floats < conv_first_pack_floats()) { ocrl_set_error("ocrl_conv2d_first_fwd: workspace of %zu floats, %zu needed", ws_floats, conv_first_pack_floats()); return 1; }
+    if (conv_first_pack_launch(w, ws, ST(stream))) return 1;
+    return conv_first_fwd_launch(obs, ws, bias, y, B, H, W, relu, ST(stream));
+}
+size_t ocrl_conv2d_first_wgrad_ws_floats(int B, int H, int W) { return conv_first_wgrad_ws_floats(B, H, W); }
+int ocrl_conv2d_first_bwd_weight(const float* obs, const float* dy, float* dw, float* db, int B, int H, int W, int accumulate, float* ws, size_t ws_floats,
+                                 void* stream) {
+    if (!obs || !dy || !dw || !ws || B < 1 || H < 1 || W < 1) { ocrl_set_error("ocrl_conv2d_first_bwd_weight: obs, dy, dw, ws and a non-empty image are required"); return 1; }
+    const size_t need = conv_first_wgrad_ws_floats(B, H, W);
+    if (ws_floats < need) { ocrl_set_error("ocrl_conv2d_first_bwd_weight: workspace of %zu floats, %zu needed", ws_floats, need); return 1; }
+    return conv_first_wgrad_launch(obs, dy, ws, dw, db, B, H, W, accumulate ? 1 : 0, ST(stream));
 }
 int ocrl_layernorm_fwd(const float* x, const float* g, const float* b, float* y, float* mean, float* rstd, long long R, int F, void* stream) {
     return layernorm_fwd_launch(x, g, b, y, mean, rstd, R, F, ST(stream));

@@ -10,7 +10,9 @@
 // conv_wgrad_kernel — dW[tap][co][ci] = sum_pixels dY[p][co] * X[p+tap][ci]: pixels are the
 //     MFMA k dimension; grid = (chunks, KS) so one workgroup owns one kernel row (KS taps) and
 //     keeps KS 32x32 accumulators per wave across all its tiles; partial slabs are reduced (and
-//     permuted to the reference [co][ci][ky][kx] layout) by conv_wgrad_reduce_kernel.
+//     permuted to the reference [co][ci][ky][kx] layout) by conv_wgrad_reduce_kernel.  The bias gradient db[co] = sum_pixels dY[p][co]
+//     rides along: the ky == 0 workgroups sum the dY fragment they feed to the MFMAs and leave one 64-float partial per slab behind
+//     the dW slabs; the reduce kernel adds those in slab order.
 #include "common.h"
 #include "kernels.h"
 #include <stdlib.h>
@@ -336,6 +338,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(WgradArgs p) {
     for (int k = 0; k < KS; ++k)
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[k][r] = 0.f;
+    float bsum = 0.f;       // this lane's channel (coh * 32 + li) of dY summed over the pixels of parity lh: the bias gradient's share
 
     // global -> register staging of one tile (dY tile + X rows shifted by this workgroup's ky): the loads of tile t+1
     // are in flight while tile t's MFMAs run; the registers are written to LDS after the barrier that retires tile t.
@@ -391,6 +394,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(WgradArgs p) {
 #pragma unroll 4
             for (int xx = 0; xx < TW; xx += 2) {
                 const float a = ay[xx * COUT];
+                bsum += a;
 #pragma unroll
                 for (int kx = 0; kx < KS; ++kx) {
                     const float bb = bx[(xx + kx) * CIN];
@@ -411,14 +415,27 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(WgradArgs p) {
                 out[((size_t)kx * COUT + co) * CIN + cih * 32 + li] = acc[kx][r];
             }
     }
+    // ---- bias partial [slab][co]: one wave per output-channel half of the ky == 0 workgroup (the ci halves of CIN == 64 read the same
+    // dY); even pixels + odd pixels, in that order
+    const float bodd = __shfl_down(bsum, 32);
+    if (p.bpart && ky == 0 && cih == 0 && lh == 0) p.bpart[(size_t)slab * COUT + coh * 32 + li] = bsum + bodd;
 }
 
-// dW[co][ci][ky][kx] (reference layout, cin_real channels) = sum_slabs part[slab][tap][co][ci]
+// dW[co][ci][ky][kx] (reference layout, cin_real channels) = sum_slabs part[slab][tap][co][ci]; db[co] = sum_slabs bpart[slab][co] (the
+// COUT threads behind the dW ones, when db is given)
 __global__ void conv_wgrad_reduce_kernel(const float* __restrict__ part, float* __restrict__ dW, int nslab,
-                                         int KS, int CIN, int COUT, int cin_real, int accumulate) {
+                                         int KS, int CIN, int COUT, int cin_real, int accumulate,
+                                         const float* __restrict__ bpart, float* __restrict__ db) {
     const int n = KS * KS * COUT * CIN;
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
+    if (i >= n) {
+        if (db && i < n + COUT) {
+            float s = 0.f;
+            for (int k = 0; k < nslab; ++k) s += bpart[(size_t)k * COUT + (i - n)];
+            db[i - n] = accumulate ? db[i - n] + s : s;
+        }
+        return;
+    }
     const int ci = i % CIN, co = (i / CIN) % COUT, tap = i / (CIN * COUT);
     if (ci >= cin_real) return;
     float s = 0.f;
@@ -507,17 +524,22 @@ int conv_wgrad_chunks(int B, int H, int W, int KS) {
     int n = (2 * 256) / KS;          // all workgroups co-resident (2 per CU): no straggler round
     return n < ntiles ? n : ntiles;
 }
-size_t conv_wgrad_ws_floats(int B, int H, int W, int KS, int CIN) {
-    const int ks = CIN == 64 ? 1 : 2;
-    return (size_t)conv_wgrad_chunks(B, H, W, KS) * ks * KS * KS * 64 * CIN;
+int conv_wgrad_slabs(int B, int H, int W, int KS, int CIN) { return conv_wgrad_chunks(B, H, W, KS) * (CIN == 64 ? 1 : 2); }
+// partial slabs of dW, then (for a launch that is given db) one 64-float bias partial per slab
+size_t conv_wgrad_ws_floats(int B, int H, int W, int KS, int CIN, bool with_db) {
+    return (size_t)conv_wgrad_slabs(B, H, W, KS, CIN) * (KS * KS * 64 * CIN + (with_db ? 64 : 0));
 }
 
-int conv_wgrad_launch(const WgradArgs& a, int KS, int CIN, int COUT, int cin_real, float* dW, int accumulate, hipStream_t st, int x3) {
+int conv_wgrad_launch(const WgradArgs& a_in, int KS, int CIN, int COUT, int cin_real, float* dW, float* db, int accumulate, hipStream_t st, int x3) {
     OCRL_REQUIRE(COUT == 64, "conv wgrad: COUT must be 64 (got %d)", COUT);
-    const int nchunk = conv_wgrad_chunks(a.B, a.H, a.W, KS);
+    const int nchunk = conv_wgrad_chunks(a_in.B, a_in.H, a_in.W, KS);
+    const int nslab = nchunk * (CIN == 64 ? 1 : 2);
+    WgradArgs a = a_in;
+    a.bpart = db ? a.part + (size_t)nslab * KS * KS * COUT * CIN : nullptr;
     static int x3_env = -1;
     if (x3_env < 0) { const char* e = getenv("OCRL_CONV_X3"); x3_env = e ? atoi(e) : 0; }
     if (x3 < 0) x3 = x3_env;
+    OCRL_REQUIRE(!(db && x3 > 0), "conv wgrad: the split-precision stage leaves no bias partials (take the column sum of dY instead)");
     int rc;
     if ((KS == 5 || KS == 3) && CIN == 64 && x3 > 0) rc = conv_wgrad_x3_stage(a, nchunk, st, KS);
     else if (KS == 5 && CIN == 64) rc = conv_wgrad_cfg<5, 64>(a, nchunk, st);
@@ -525,9 +547,9 @@ int conv_wgrad_launch(const WgradArgs& a, int KS, int CIN, int COUT, int cin_rea
     else if (KS == 3 && CIN == 64) rc = conv_wgrad_cfg<3, 64>(a, nchunk, st);
     else { ocrl_set_error("conv wgrad: unsupported KS=%d CIN=%d", KS, CIN); return 1; }
     if (rc) return rc;
-    const int nslab = nchunk * (CIN == 64 ? 1 : 2);
     const int n = KS * KS * COUT * CIN;
-    hipLaunchKernelGGL(conv_wgrad_reduce_kernel, dim3(cdiv(n, 256)), dim3(256), 0, st, a.part, dW, nslab, KS, CIN, COUT, cin_real, accumulate);
+    hipLaunchKernelGGL(conv_wgrad_reduce_kernel, dim3(cdiv(n + (db ? COUT : 0), 256)), dim3(256), 0, st, a.part, dW, nslab, KS, CIN, COUT, cin_real, accumulate,
+                       a.bpart, db);
     OCRL_CHECK_LAUNCH("conv_wgrad_reduce");
     return 0;
 }

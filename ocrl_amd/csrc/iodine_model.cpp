@@ -168,7 +168,7 @@ int IodineModel::decoder_bwd(int i, const float* dout4, bool weights, hipStream_
             WgradArgs w;
             w.X = c_[l][i]; w.dY = cur; w.part = scratch_; w.B = (int)BK; w.H = S; w.W = S;
             OCRL_REQUIRE(conv_wgrad_ws_floats((int)BK, S, S, 3, 64) <= scratch_floats_, "conv wgrad: scratch too small");
-            RC(conv_wgrad_launch(w, 3, 64, 64, 64, G(w_.dec_conv[l + 1].w), 1, st, conv_x3_ > 0 ? 1 : 0));
+            RC(conv_wgrad_launch(w, 3, 64, 64, 64, G(w_.dec_conv[l + 1].w), nullptr, 1, st, conv_x3_ > 0 ? 1 : 0));
             RC(colsum_launch(cur, 64, G(w_.dec_conv[l + 1].b), BKN, 64, 1, 1.f, scratch_, scratch_floats_, st));
         }
         ConvArgs a;

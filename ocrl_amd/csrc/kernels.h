@@ -278,14 +278,27 @@ struct WgradArgs {
     const float* dY = nullptr;      // [B,H,W,COUT]
     float* part = nullptr;          // workspace, conv_wgrad_ws_floats()
     int B = 0, H = 0, W = 0;
+    float* bpart = nullptr;         // bias partials [slab][64] behind the dW slabs (set by conv_wgrad_launch when db is asked for)
 };
 // low_latency: the caller's grid is small (inference at a few images): 5x5 / 64-channel forward layers whose throughput grid would leave
 // most CUs idle go to the k-split kernel (conv_lat_kernel); results differ from the throughput kernel by fp32 summation order
 int conv_fwd_launch(const ConvArgs& a, int KS, int CIN, int COUT, hipStream_t st, int low_latency = 0);
 // x3: 1 = the split-precision first stage for the 5x5 / 64-channel layer (exploratory), 0 = fp32 MFMA, -1 = by OCRL_CONV_X3
-int conv_wgrad_launch(const WgradArgs& a, int KS, int CIN, int COUT, int cin_real, float* dW, int accumulate, hipStream_t st, int x3 = -1);
-size_t conv_wgrad_ws_floats(int B, int H, int W, int KS, int CIN);
+// db (may be null): the bias gradient, summed inside the fp32 kernel from the dY fragments it stages anyway (not with x3 > 0)
+int conv_wgrad_launch(const WgradArgs& a, int KS, int CIN, int COUT, int cin_real, float* dW, float* db, int accumulate, hipStream_t st, int x3 = -1);
+int conv_wgrad_slabs(int B, int H, int W, int KS, int CIN);       // partial slabs the launch writes (workers, x2 for CIN == 8)
+size_t conv_wgrad_ws_floats(int B, int H, int W, int KS, int CIN, bool with_db = true);
 int conv_pack_launch(const float* W, float* fwd, float* bwd, int KS, int CIN, int COUT, int cin_real, hipStream_t st);
+
+// ------------------------------------------------------------------ conv_first.hip
+// the 5x5 / 3 -> 64 layer on the NCHW observation [B,3,H,W]: Y [B,H,W,64] = relu?(conv + bias) with the weights packed as [76][64]
+size_t conv_first_pack_floats();
+int conv_first_pack_launch(const float* W, float* pack, hipStream_t st);                       // W [64][3][5][5]
+int conv_first_fwd_launch(const float* obs, const float* pack, const float* bias, float* Y, int B, int H, int W, int relu, hipStream_t st);
+// its weight gradient dW [64][3][5][5] and bias gradient db [64] (may be null) from dY [B,H,W,64]; ws: conv_first_wgrad_ws_floats()
+int conv_first_wgrad_workers(int B, int H, int W);
+size_t conv_first_wgrad_ws_floats(int B, int H, int W);
+int conv_first_wgrad_launch(const float* obs, const float* dY, float* ws, float* dW, float* db, int B, int H, int W, int accumulate, hipStream_t st);
 
 // ------------------------------------------------------------------ elementwise.hip
 int nchw_to_nhwc8_launch(const float* in, float* out, int B, int C, int H, int W, hipStream_t st);

@@ -144,6 +144,7 @@ void SlateModel::layout_workspace(bool commit) {
     scratch_floats_ = 0;
     {
         size_t need = conv_wgrad_ws_floats((int)(B * (cfg.use_bcdec ? K : 1)), S, S, 5, 64) + (size_t)512 * 2304 * 2;
+        if (conv_first_wgrad_ws_floats((int)B, S, S) > need) need = conv_first_wgrad_ws_floats((int)B, S, S);
         size_t sk = (size_t)32 * V * d + (size_t)(1 << 20);        // split-k slabs ([V,d] weights x16; 170 slabs of the [4d,d] FFN weights)
         if (sk > need) need = sk;
         size_t cs = (size_t)N * C * 8 + (size_t)T * d * 8 + (1 << 20);   // column-sum partials (pos map / pe)
@@ -156,7 +157,10 @@ void SlateModel::layout_workspace(bool commit) {
     }
     scratch_ = carve(nullptr, scratch_floats_);
     scratch2_ = cfg.use_bcdec ? scratch_ : carve(nullptr, scratch_floats_);
-    obs8_ = carve("obs8", BN * 8);
+    // three channels: the first layer reads the NCHW observation itself (csrc/conv_first.hip); obs_keep_ is the copy its weight gradient
+    // reads in the backward, so the caller's buffer is free again once the forward has run.  Other channel counts: the NHWC8 copy.
+    obs8_ = first_direct() ? nullptr : carve("obs8", BN * 8);
+    obs_keep_ = first_direct() ? carve(nullptr, BN * cfg.obs_channels) : nullptr;
     obs_stage_ = carve(nullptr, (B < 32 ? B : 32) * (size_t)cfg.obs_channels * N);
     seed_dev_ = reinterpret_cast<unsigned long long*>(carve(nullptr, 64));
     e1_ = carve("enc1", BN * 64); e2_ = carve("enc2", BN * 64); e3_ = carve("enc3", BN * 64); e4_ = carve("feats", BN * 64);
@@ -278,7 +282,8 @@ void SlateModel::layout_workspace(bool commit) {
     gmem_ = carve(nullptr, BK * d); gck_ = carve(nullptr, BK * d); gcv_ = carve(nullptr, BK * d);
     gdA_ = carve(nullptr, BN * 64); gdB_ = carve(nullptr, BN * 64);
     }
-    {
+    col0_ = dw0p_ = nullptr;
+    if (!first_direct()) {      // the first layer's weight gradient as a product with the patch matrix
         const int ldc0 = (25 * cfg.obs_channels + 3) & ~3;
         col0_ = carve(nullptr, BN * ldc0); dw0p_ = carve(nullptr, (size_t)64 * ldc0);
     }
@@ -390,13 +395,17 @@ int SlateModel::conv_layer_wgrad(const float* x, const float* dy, float* dW, flo
     WgradArgs a;
     a.X = x; a.dY = dy; a.part = L.scratch; a.B = Bn; a.H = Hh; a.W = Ww;
     OCRL_REQUIRE(conv_wgrad_ws_floats(Bn, Hh, Ww, KS, CIN) <= L.scratch_floats, "conv wgrad: scratch too small");
-    RC(conv_wgrad_launch(a, KS, CIN, 64, cin_real, dW, 0, L, conv_x3_ > 0 ? 1 : 0));
-    if (db) RC(colsum_launch(dy, 64, db, (long long)Bn * Hh * Ww, 64, 0, 1.f, L.scratch, L.scratch_floats, L));
+    // the bias gradient comes out of the weight-gradient kernel (it sums the dY fragments it feeds to the MFMAs); the exploratory
+    // split-precision stage has no such sum and keeps the column-sum pass over dY
+    const bool x3 = conv_x3_ > 0 && CIN == 64;
+    RC(conv_wgrad_launch(a, KS, CIN, 64, cin_real, dW, x3 ? nullptr : db, 0, L, x3 ? 1 : 0));
+    if (db && x3) RC(colsum_launch(dy, 64, db, (long long)Bn * Hh * Ww, 64, 0, 1.f, L.scratch, L.scratch_floats, L));
     return 0;
 }
 
 int SlateModel::pack_weights(const Lane& L, bool encoder_only) {
-    RC(conv_pack_launch(P(w_.enc[0].w), cw_fwd_[0], nullptr, 5, 8, 64, cfg.obs_channels, L));
+    if (first_direct()) RC(conv_first_pack_launch(P(w_.enc[0].w), cw_fwd_[0], L));
+    else RC(conv_pack_launch(P(w_.enc[0].w), cw_fwd_[0], nullptr, 5, 8, 64, cfg.obs_channels, L));
     RC(conv_pack_launch(P(w_.enc[1].w), cw_fwd_[1], cw_bwd_[1], 5, 64, 64, 64, L));
     RC(conv_pack_launch(P(w_.enc[2].w), cw_fwd_[2], cw_bwd_[2], 5, 64, 64, 64, L));
     RC(conv_pack_launch(P(w_.enc[3].w), cw_fwd_[3], cw_bwd_[3], 5, 64, 64, 64, L));
@@ -445,8 +454,14 @@ int SlateModel::fwd_encoder(const StepInputs& in, const Lane& L, int fork_dvae) 
     a.phase = 1;
     RC(slot_attn_launch(a, 0, L));
     if (fork_dvae == 2) RC(fork_here());
-    RC(nchw_to_nhwc8_launch(in.obs, obs8_, B, cfg.obs_channels, S, S, L));
-    RC(conv_layer_fwd(obs8_, cw_fwd_[0], P(w_.enc[0].b), e1_, B, S, S, 5, 8, 1, nullptr, nullptr, L));
+    if (first_direct()) {
+        RC(conv_first_fwd_launch(in.obs, cw_fwd_[0], P(w_.enc[0].b), e1_, B, S, S, 1, L));
+        if (!(conv_lowlat_ && frozen_))       // a backward may follow: it reads the observation again
+            OCRL_HIP(hipMemcpyAsync(obs_keep_, in.obs, (size_t)BN * cfg.obs_channels * sizeof(float), hipMemcpyDeviceToDevice, L));
+    } else {
+        RC(nchw_to_nhwc8_launch(in.obs, obs8_, B, cfg.obs_channels, S, S, L));
+        RC(conv_layer_fwd(obs8_, cw_fwd_[0], P(w_.enc[0].b), e1_, B, S, S, 5, 8, 1, nullptr, nullptr, L));
+    }
     RC(conv_layer_fwd(e1_, cw_fwd_[1], P(w_.enc[1].b), e2_, B, S, S, 5, 64, 1, nullptr, nullptr, L));
     RC(conv_layer_fwd(e2_, cw_fwd_[2], P(w_.enc[2].b), e3_, B, S, S, 5, 64, 1, nullptr, nullptr, L));
     RC(conv_layer_fwd(e3_, cw_fwd_[3], P(w_.enc[3].b), e4_, B, S, S, 5, 64, 0, posmap_, nullptr, L));
@@ -985,7 +1000,7 @@ int SlateModel::bwd_encoder(const Lane& L, bool fork_dvae) {
     // ---- input MLP: x = W2 relu(W0 LN(e4) + b0) + b2 ; gA = dx
     if (!sa_in_bwd) RC(lin_bwd_w(gA_, C, h1_, C, G(w_.sa.mlp2.w), G(w_.sa.mlp2.b), BN, C, C, 1.f, W));
     // the first convolution's weight gradient is a product with im2col(obs): the patch matrix only needs the observation
-    if (side_w) RC(im2col5_launch(obs8_, col0_, BN, S, S, cfg.obs_channels, (25 * cfg.obs_channels + 3) & ~3, W));
+    if (side_w && !first_direct()) RC(im2col5_launch(obs8_, col0_, BN, S, S, cfg.obs_channels, (25 * cfg.obs_channels + 3) & ~3, W));
     if (sa_in_bwd) {
         // reads dx (gA_), h1, e4; writes d e4 (gB_) and the six parameter gradients from one partial slab per workgroup (csrc/sa_input.hip)
         const size_t slabs = L.scratch_floats / SA_INPUT_SLAB;
@@ -1018,9 +1033,12 @@ int SlateModel::bwd_encoder(const Lane& L, bool fork_dvae) {
     RC(conv_layer_fwd(gA_, cw_bwd_[2], nullptr, gB_, B, S, S, 5, 64, 0, nullptr, e2_, L));
     RC(conv_layer_wgrad(e1_, gB_, G(w_.enc[1].w), G(w_.enc[1].b), B, S, S, 5, 64, 64, L));
     RC(conv_layer_fwd(gB_, cw_bwd_[1], nullptr, gA_, B, S, S, 5, 64, 0, nullptr, e1_, L));
-    // first layer (3 input channels): on the conv wgrad kernel its 8-of-64 useful MFMA columns cost 1.5 ms; as
-    // dW = dY^T im2col(obs) it is one [64 x 75] split-K product over the B*N pixels
-    {
+    // first layer: three channels go through the kernel that gathers the patches from the observation's halo tiles and sums the bias
+    // gradient on the way (csrc/conv_first.hip); any other count as dW = dY^T im2col(obs), one [64 x 25 ch] split-K product over the pixels
+    if (first_direct()) {
+        OCRL_REQUIRE(conv_first_wgrad_ws_floats(B, S, S) <= L.scratch_floats, "first conv wgrad: scratch too small");
+        RC(conv_first_wgrad_launch(obs_keep_, gA_, L.scratch, G(w_.enc[0].w), G(w_.enc[0].b), B, S, S, 0, L));
+    } else {
         const int ch = cfg.obs_channels, ldc0 = (25 * ch + 3) & ~3;
         if (!side_w) RC(im2col5_launch(obs8_, col0_, BN, S, S, ch, ldc0, L));
         RC(lin_bwd_w(gA_, 64, col0_, ldc0, dw0p_, G(w_.enc[0].b), BN, 64, ldc0, 1.f, L));

@@ -95,7 +95,7 @@ VaeLay vae_layout(int B, int S, int C, int f, int L, int cnn, int full) {
                 y.dpart[i] = take(part_floats(y.dc[i]));
             } else {
                 y.pkf[i] = take(9 * 64 * 64); y.pkb[i] = take(9 * 64 * 64);
-                const size_t wg = conv_wgrad_ws_floats(B, (int)s, (int)s, 3, 64);
+                const size_t wg = conv_wgrad_ws_floats(B, (int)s, (int)s, 3, 64, false);        // db comes from the unit's own column sums
                 if (wg > y.sk_floats) y.sk_floats = wg;
             }
             if ((size_t)M * 256 > gmax) gmax = (size_t)M * 256;
@@ -289,7 +289,7 @@ int ocrl_vae_bwd(const float* obs, const float* eps, const float* const* w, cons
             } else {
                 WgradArgs wa;
                 wa.X = x; wa.dY = ga; wa.part = ws + y.sk; wa.B = B; wa.H = s; wa.W = s;
-                RC(conv_wgrad_launch(wa, 3, 64, 64, 64, dw[l3], 0, st, 0));
+                RC(conv_wgrad_launch(wa, 3, 64, 64, 64, dw[l3], nullptr, 0, st, 0));
                 RC(colsum_launch(ga, 64, dw[l3 + 1], M, 64, 0, 1.f, ws + y.sk, y.sk_floats, st));
                 ConvArgs a;                                // d x = conv(d y, flipped W) masked by x > 0
                 a.X = ga; a.Wp = ws + y.pkb[i]; a.Y = gb; a.B = B; a.H = s; a.W = s; a.mask = x;
