@@ -568,6 +568,9 @@ int ocrl_gae(const float* rewards, const float* values, const float* episode_sta
  *   not drawn) on black with the shape predicates of the pre-training scenes, pixel centre (i + 0.5) / H, the row index growing with y.
  *   mode 0: uint8 [E, 3, H, W]; 1: [E, H, W, 3]; 2: masks [E, R + 1, H, W, 1] of 0 / 1: each row alone and unoccluded, the background
  *   (no row covers the pixel) last.
+ * _state_obs: the observation of render_mode "state" (base.py:365-394) of rows [E, R, 5], R <= 16 -> out fp32 [E, R, 5]: columns 0, 1, 3, 4
+ *   copied; column 2 the index of the scale in the reference's global list [0.15, 0.22]: 0 for (float)0.15 and for an all-zero row (the
+ *   padding), 1 for (float)0.22, -1 for any other scale; a row whose colour is -1 becomes (-1, -1, -1, 0, 0).  One thread per row.
  * _uniforms: out [n_envs, n] = bits24 / 2^24 of draws first .. first + n - 1 of episode `episode` of environments env0 .. */
 #define OCRL_SPRITE_MAX_OBJECTS 15
 typedef struct {
@@ -596,7 +599,26 @@ int ocrl_sprite_env_reset(const ocrl_sprite_env_desc* d, float* state, unsigned 
 int ocrl_sprite_env_step(const ocrl_sprite_env_desc* d, float* state, unsigned long long seed, const long long* actions, float* rewards,
                          unsigned char* dones, unsigned char* success, double* ep_return, int* ep_length, void* stream);
 int ocrl_sprite_render(const float* rows, int E, int R, int H, int mode, unsigned char* out, void* stream);
+int ocrl_sprite_state_obs(const float* rows, int E, int R, float* out, void* stream);
 int ocrl_sprite_env_uniforms(unsigned long long seed, long long env0, int n_envs, long long episode, int first, int n, float* out, void* stream);
+
+/* ---- the per-object MLP of the ground-truth-state encoder (ocrs/gt/gt_module.py:14-27): x [M, D] through nl layers
+ *      h_l = act_l(h_{l-1} W_l^T + b_l), W_l [dims[l], dims[l-1]] (torch layout), acts[l] != 0: ReLU, 0: none.  M = batch x objects rows
+ *      (1 <= M < 2^22), 1 <= D <= 64, 1 <= nl <= 4, every dims[l] a multiple of 4 in 4 .. 256; anything else: ws_floats == 0 and the
+ *      other entries return non-zero, with a message.  w = {W_0, b_0, W_1, b_1, ..}, dw likewise.  Stateless: the caller owns parameters,
+ *      gradients and `ws` (ocrl_gt_mlp_ws_floats floats, 256-byte aligned); _fwd leaves every layer's output there and _bwd reads them
+ *      (the ReLU mask is output > 0), so `ws` lives from the one to the other.
+ * _fwd: one launch; a workgroup takes 16 rows, the activations stay in LDS from layer to layer.  out [M, dims[nl-1]].
+ * _bwd: dout [M, dims[nl-1]] -> dw (written, not accumulated) and, when dx is not NULL, dx [M, D].  One launch down the chain: the
+ *   16-row tiles are split into at most 64 slabs, a workgroup adds its slab's tiles in order into the slab's partial; a second launch
+ *   sums the partials in slab order (none when M <= 16 rows make one slab).  No atomics: the result depends on the inputs and M alone
+ *   and is the same bit for bit from run to run. */
+#define OCRL_GT_MLP_MAX_LAYERS 4
+size_t ocrl_gt_mlp_ws_floats(int M, int D, int nl, const int* dims);
+int ocrl_gt_mlp_fwd(const float* x, const float* const* w, float* out, int M, int D, int nl, const int* dims, const int* acts, float* ws,
+                    size_t ws_floats, void* stream);
+int ocrl_gt_mlp_bwd(const float* x, const float* dout, const float* const* w, float* dx /* may be NULL */, float* const* dw, int M, int D, int nl,
+                    const int* dims, const int* acts, float* ws, size_t ws_floats, void* stream);
 
 /* ---- L2 gradient clip + Adam on caller-owned flat fp32 buffers p, g, m, v [n] (16-byte aligned), as PPO.train applies
  *      torch.nn.utils.clip_grad_norm_ and torch.optim.Adam to the policy.  Stateless, no host synchronisation, no atomics:

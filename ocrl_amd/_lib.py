@@ -277,6 +277,11 @@ def lib():
     L.ocrl_sprite_env_reset.argtypes = [POINTER(SpriteEnvDesc), p, c_ulonglong, p, c_longlong, p]
     L.ocrl_sprite_env_step.argtypes = [POINTER(SpriteEnvDesc), p, c_ulonglong, p, p, p, p, p, p, p]
     L.ocrl_sprite_render.argtypes = [p, c_int, c_int, c_int, c_int, p, p]
+    L.ocrl_sprite_state_obs.argtypes = [p, c_int, c_int, p, p]
+    L.ocrl_gt_mlp_ws_floats.argtypes = [c_int, c_int, c_int, POINTER(c_int)]
+    L.ocrl_gt_mlp_ws_floats.restype = c_size_t
+    L.ocrl_gt_mlp_fwd.argtypes = [p, POINTER(p), p, c_int, c_int, c_int, POINTER(c_int), POINTER(c_int), p, c_size_t, p]
+    L.ocrl_gt_mlp_bwd.argtypes = [p, p, POINTER(p), p, POINTER(p), c_int, c_int, c_int, POINTER(c_int), POINTER(c_int), p, c_size_t, p]
     L.ocrl_sprite_env_uniforms.argtypes = [c_ulonglong, c_longlong, c_int, c_longlong, c_int, c_int, p, p]
     L.ocrl_comm_unique_id.argtypes = [p, c_size_t]
     L.ocrl_comm_init.argtypes = [POINTER(p), c_int, c_int, p]

@@ -39,3 +39,4 @@ int sprite_env_step_launch(const ocrl_sprite_env_desc& d, float* rows, int* aux,
                            hipStream_t st);
 int sprite_render_launch(const float* rows, int E, int R, int H, int mode, unsigned char* out, hipStream_t st);
 int sprite_env_uniforms_launch(unsigned long long seed, long long env0, int n_envs, long long episode, int first, int n, float* out, hipStream_t st);
+int sprite_state_obs_launch(const float* rows, long long n, float* out, hipStream_t st);

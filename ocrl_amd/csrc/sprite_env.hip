@@ -245,6 +245,23 @@ __global__ __launch_bounds__(256) void sprite_env_uniforms_kernel(unsigned long 
     out[i] = (float)env_bits24(seed, e, (uint32_t)episode, j) * (1.f / 16777216.f);
 }
 
+// ---------------------------------------------------------------------------------------------------------------- state observations
+// render(mode="state") of the reference (base.py:365-394), one thread per row: the scale becomes its index in the global SCALES list
+// [0.15, 0.22] (-1: neither; an all-zero row, the padding after the agent, stays zero), a colour of -1 gives (-1, -1, -1, 0, 0)
+__global__ __launch_bounds__(256) void sprite_state_obs_kernel(const float* __restrict__ rows, long long n, float* __restrict__ out) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const float* r = rows + i * 5;
+    const float c = r[0], s = r[1], z = r[2], x = r[3], y = r[4];
+    float* o = out + i * 5;
+    if (c == -1.f) {
+        o[0] = -1.f; o[1] = -1.f; o[2] = -1.f; o[3] = 0.f; o[4] = 0.f;
+        return;
+    }
+    const bool empty = c == 0.f && s == 0.f && z == 0.f && x == 0.f && y == 0.f;
+    o[0] = c; o[1] = s; o[2] = (z == 0.15f || empty) ? 0.f : (z == 0.22f ? 1.f : -1.f); o[3] = x; o[4] = y;
+}
+
 // ---------------------------------------------------------------------------------------------------------------- the renderer
 // the predicates of ocrl_amd/utils/data.py:_mask in fp32; (dx, dy) = pixel centre - sprite centre, r = scale / 2
 __device__ inline bool sprite_covers(int shape, float dx, float dy, float r) {
@@ -359,5 +376,10 @@ int sprite_render_launch(const float* rows, int E, int R, int H, int mode, unsig
 int sprite_env_uniforms_launch(unsigned long long seed, long long env0, int n_envs, long long episode, int first, int n, float* out, hipStream_t st) {
     hipLaunchKernelGGL(sprite_env_uniforms_kernel, dim3(cdiv((long long)n_envs * n, 256)), dim3(256), 0, st, seed, env0, n_envs, episode, first, n, out);
     OCRL_CHECK_LAUNCH("sprite_env_uniforms");
+    return 0;
+}
+int sprite_state_obs_launch(const float* rows, long long n, float* out, hipStream_t st) {
+    hipLaunchKernelGGL(sprite_state_obs_kernel, GRID1D(n), 0, st, rows, n, out);
+    OCRL_CHECK_LAUNCH("sprite_state_obs");
     return 0;
 }

@@ -99,6 +99,12 @@ int ocrl_sprite_render(const float* rows, int E, int R, int H, int mode, unsigne
     return sprite_render_launch(rows, E, R, H, mode, out, static_cast<hipStream_t>(stream));
 }
 
+int ocrl_sprite_state_obs(const float* rows, int E, int R, float* out, void* stream) {
+    OCRL_REQUIRE(rows && out, "ocrl_sprite_state_obs: null argument");
+    OCRL_REQUIRE(E >= 1 && R >= 1 && R <= SPRITE_MAX_ROWS, "ocrl_sprite_state_obs: environments >= 1 and 1 <= rows <= %d (got %d, %d)", SPRITE_MAX_ROWS, E, R);
+    return sprite_state_obs_launch(rows, (long long)E * R, out, static_cast<hipStream_t>(stream));
+}
+
 int ocrl_sprite_env_uniforms(unsigned long long seed, long long env0, int n_envs, long long episode, int first, int n, float* out, void* stream) {
     OCRL_REQUIRE(out && n >= 1 && n_envs >= 1, "ocrl_sprite_env_uniforms: null output, n < 1 or n_envs < 1");
     OCRL_REQUIRE(env0 >= 0 && env0 + n_envs <= (1 << 20) && episode >= 0 && episode < (1LL << 24) && first >= 0 && (long long)first + n <= SPRITE_MAX_DRAWS,

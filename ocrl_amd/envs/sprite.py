@@ -18,6 +18,7 @@ MODES, REW_TYPES = ("easy", "normal", "hard"), ("sparse", "normal", "dense")
 RENDER_MODES = {"image": 0, "rgb_array": 1, "mask": 2}
 TASKS = {"TargetEnv": 0, "OddOneOutEnv": 1}     # config.env -> ocrl_sprite_env_desc.task
 UNSEEN_MODES = (None, "train", "test")
+STATE_SCALES = (0.15, 0.22)                     # the reference's global SCALES list: a state observation carries a scale as its index here
 
 try:                                            # gym's spaces when importable
     from gym.spaces import Box, Discrete
@@ -124,9 +125,21 @@ def _odd_one_out_fields(d, config, obj_comp, unseen, scales):
     d.unseen_colors[0], d.unseen_colors[1] = COLORS.index(pair[0]), COLORS.index(pair[1])
 
 
+def _check_state_scales(config, task):
+    """render_mode: state writes every scale as its index in STATE_SCALES; the reference raises from list.index at the first render of
+    another one, here the config is refused by key"""
+    known = [np.float32(v) for v in STATE_SCALES]
+    keys = [("SCALES", list(config.SCALES)), ("AGENT", [config.AGENT[2]])] + ([("target", [config.target[2]])] if task == 0 else [])
+    for key, vals in keys:
+        for v in vals:
+            if np.float32(float(v)) not in known:
+                raise ValueError(f"ocrl_amd.envs: {key}: scale {v} has no index in the state observation (render_mode: state knows {list(STATE_SCALES)})")
+
+
 class SpriteEnv:
     """``num_envs`` sprite tasks stepping together on ``device``; a subclass names the task (``TASK``, a key of TASKS).  Observations are
-    uint8 frames [E, 3, H, W] (what stable-baselines3 hands the policy after its image transpose); actions 0..3 = up, left, down, right.
+    uint8 frames [E, 3, H, W] (what stable-baselines3 hands the policy after its image transpose), or with ``render_mode: state`` the
+    reference's state observation, fp32 [E, hi + 1, 5] (ocrl_sprite_state_obs; no frame is rendered); actions 0..3 = up, left, down, right.
     A finished environment starts its next episode inside the step that finished it: the observation returned for it is the new
     episode's first frame, and the finished episode's return and length come back with that step."""
     on_device = True
@@ -139,9 +152,14 @@ class SpriteEnv:
         if d.task != TASKS[self.TASK]:
             raise ValueError(f"ocrl_amd.envs.{self.TASK}: the config's env: {getattr(config_env, 'env', 'TargetEnv')} is another task")
         self.obs_size, self.rows = d.H, d.hi + 1
-        self.observation_space = Box(0, 255, (3, d.H, d.H), np.uint8)
-        self.action_space = Discrete(4)
         self.render_mode = getattr(config_env, "render_mode", "image")
+        self._state_obs = self.render_mode == "state"
+        if self._state_obs:
+            _check_state_scales(config_env, d.task)
+            self.observation_space = Box(0, 1, (d.hi + 1, 5), np.float32)       # the reference's space, bounds included (base.py)
+        else:
+            self.observation_space = Box(0, 255, (3, d.H, d.H), np.uint8)
+        self.action_space = Discrete(4)
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise RuntimeError(f"ocrl_amd.envs.{self.TASK} runs on the GPU (device={device!r}); there is no CPU fallback")
@@ -155,6 +173,7 @@ class SpriteEnv:
         self._state = torch.zeros(n, device=self.device)
         off = (E * R * 5 + 63) & ~63
         self._rows = self._state[:E * R * 5].view(E, R, 5)
+        self._rows_ptr = _lib.ptr(self._rows)
         self._aux = self._state[off:off + 8 * E].view(torch.int32).view(E, 8)
         self._ret = self._state[off:off + 8 * E].view(torch.float64).view(E, 4)[:, 3]
         self._started = False
@@ -172,16 +191,31 @@ class SpriteEnv:
         self._call(_lib.lib().ocrl_sprite_render, _lib.ptr(rows), E, R, H, mode, _lib.ptr(out))
         return out
 
+    def state_obs(self, rows):
+        """the state observation (render(mode="state") of the reference) of hand-made rows [E', R, 5], R <= 16"""
+        rows = rows.to(device=self.device, dtype=torch.float32).contiguous()
+        out = torch.empty_like(rows)
+        self._call(_lib.lib().ocrl_sprite_state_obs, _lib.ptr(rows), rows.shape[0], rows.shape[1], _lib.ptr(out))
+        return out
+
+    def observe(self):
+        """the observation of the current state in the environment's mode, a fresh tensor: what reset and the steps return"""
+        if not self._state_obs:
+            return self._frames()
+        out = torch.empty_like(self._rows)
+        self._call(_lib.lib().ocrl_sprite_state_obs, self._rows_ptr, self.num_envs, self.rows, _lib.ptr(out))
+        return out
+
     def reset(self, mask=None):
-        """new episodes for every environment (or those ``mask`` [E] selects) -> frames [E, 3, H, W].  The first reset starts episode 0
+        """new episodes for every environment (or those ``mask`` [E] selects) -> observations.  The first reset starts episode 0
         of every environment's stream; later ones the episode after the current one."""
         m = None if mask is None else torch.as_tensor(mask).to(device=self.device).ne(0).to(torch.uint8).contiguous()
         self._call(_lib.lib().ocrl_sprite_env_reset, ctypes.byref(self._desc), _lib.ptr(self._state), self.seed, _lib.ptr(m), -1 if self._started else 0)
         self._started = True
-        return self._frames()
+        return self.observe()
 
     def step_device(self, actions):
-        """actions int64 [E] on the device -> (frames, rewards fp32, dones bool, extras) as fresh device tensors; extras has ``is_success``
+        """actions int64 [E] on the device -> (observations, rewards fp32, dones bool, extras) as fresh device tensors; extras has ``is_success``
         (bool), ``episode_return`` (float64) and ``episode_length`` (int32) of the episodes this step finished.  No host read."""
         if not self._started:
             raise RuntimeError(f"ocrl_amd.envs.{self.TASK}: step before reset()")
@@ -194,10 +228,10 @@ class SpriteEnv:
         self._call(_lib.lib().ocrl_sprite_env_step, ctypes.byref(self._desc), _lib.ptr(self._state), self.seed, _lib.ptr(a), _lib.ptr(rewards),
                    _lib.ptr(flags[0]), _lib.ptr(flags[1]), _lib.ptr(ret), _lib.ptr(length))
         flags = flags.view(torch.bool)
-        return self._frames(), rewards, flags[0], {"is_success": flags[1], "episode_return": ret, "episode_length": length}
+        return self.observe(), rewards, flags[0], {"is_success": flags[1], "episode_return": ret, "episode_length": length}
 
     def step(self, actions):
-        """the gym-style call: actions as a numpy array or a tensor -> (frames tensor, rewards, dones as numpy arrays, infos)"""
+        """the gym-style call: actions as a numpy array or a tensor -> (observations tensor, rewards, dones as numpy arrays, infos)"""
         a = actions.detach().cpu().numpy() if isinstance(actions, torch.Tensor) else np.asarray(actions)
         a = a.reshape(self.num_envs)
         if ((a < 0) | (a > 3)).any() or not np.issubdtype(a.dtype, np.integer):

@@ -11,7 +11,8 @@ EvalCallback with deterministic=False) on a separate environment seeded ``seed +
 per iteration: the train() statistics, the rollout's episode window, and the evaluation when one ran) and checkpoints/model_latest.pth,
 model_best.pth (PPO.save / A2C.save).  No video and no wandb.  A SLATE / IODINE encoder needs its pre-trained checkpoint
 (pooling.ocr_checkpoint.local_file, no finetuning): PPO and A2C refuse to step such an encoder themselves; NatureCNN / MultipleCNN train
-from scratch.
+from scratch.  ``ocr=gt`` is the ground-truth-state baseline: the environments hand out their state rows (render_mode: state) and no
+frame is rendered.
 """
 import json
 import logging
@@ -37,7 +38,7 @@ def build(config):
     if config.sb3.name not in ALGOS:
         raise NotImplementedError(f"train_sb3: sb3: {config.sb3.name} is not built (built: {', '.join(ALGOS)})")
     if config.ocr.name == "GT":
-        raise NotImplementedError("train_sb3: ocr: GT (ground-truth states as observations) is not built")
+        config.env.render_mode = "state"          # train_sb3.py:41-42, 72-73: the GT encoder reads the state rows, not frames
     env = envs.make_env(config)
     eval_env = envs.make_env(config, num_envs=min(config.num_envs, config.eval.n_episodes), seed=config.seed + config.num_envs)
     kwargs = dict(device=config.device, seed=config.seed,
