@@ -63,7 +63,7 @@ def main(argv=None):
     os.makedirs(config.run_dir, exist_ok=True)
     np.random.seed(config.seed)
     torch.manual_seed(config.seed)
-    _, val_dl = get_dataloaders(config.dataset, config.batch_size, config.num_workers, seed=config.seed)
+    _, val_dl = get_dataloaders(config.dataset, config.batch_size, config.num_workers, seed=config.seed, device=config.device)
     ocr = getattr(ocrs, config.ocr.name)(config.ocr, config.dataset)
     if not hasattr(ocr._module, "last_ari"):
         raise RuntimeError(f"ocr={config.ocr.name} produces no slot maps: the ARI is defined for SLATE, Slot-Attention and IODINE")

@@ -602,6 +602,38 @@ int ocrl_sprite_render(const float* rows, int E, int R, int H, int mode, unsigne
 int ocrl_sprite_state_obs(const float* rows, int E, int R, float* out, void* stream);
 int ocrl_sprite_env_uniforms(unsigned long long seed, long long env0, int n_envs, long long episode, int first, int n, float* out, void* stream);
 
+/* ---- pre-training scenes: the RandomObjs episode of the pre-training dataset (ocrl_amd/utils/data.py:random_sprite_scenes: K sprites on
+ *      black, occlusion allowed, no agent) made on the device, batch by batch.  Scene i of a seed is a function of (seed, i) alone: the
+ *      same whichever batch it is in, at whichever position, and whichever outputs are asked for.  Stateless: the caller owns every
+ *      buffer (obs and masks 16-byte aligned, obs_u8 4-byte aligned); everything is enqueued on `stream` with no host synchronisation, no
+ *      atomics and no unbounded loop.  One launch per call.
+ * desc: H x H frames, H a multiple of 4 in [8, 512]; K objects, 1 <= K <= 15.  indices: device int64 [B], B >= 1, the scene indices
+ *   of the batch; an index outside [0, 2^40) is masked to its low 40 bits inside the kernel.  Rejected, non-zero with a message: a null
+ *   descriptor, H or K outside their ranges, B < 1, null indices, all four outputs null, misaligned outputs, a batch beyond the grid limit.
+ * The draws.  u(seed, i, j) = the top 24 bits of the library's counter RNG at site 510 and counter (i << 16) | j.  below(m) =
+ *   (bits24 * m) >> 24 and u01() = bits24 / 2^24 as in the sprite environments.  Scene i takes j = 0, 1, .. in order; for k = 0 .. K-1:
+ *   1. s = below(2); r = SCALES[s] * 0.5f, SCALES = {0.15f, 0.22f}.
+ *   2. a = r + 0.08f; b = (1.0f - r) - 0.08f.  At most 64 candidates, each x = a + (b - a) * u01(), then y likewise, every operation
+ *      rounded to fp32 (no FMA); a candidate is rejected when its distance (sqrtf(dx * dx + dy * dy)) to (0.5, 0.5) or to an earlier
+ *      object's centre is < 0.15f.  The 64th candidate stands whatever it is.
+ *   3. shape = below(4): square, triangle, star_4, circle.
+ *   4. colour = below(4): blue, green, yellow, red.
+ *   This is the distribution and the draw order of random_sprite_scenes, not numpy's bit stream.
+ * The pixels are those of ocrl_sprite_render: pixel centre (i + 0.5) / H, its shape predicates with r = scale / 2, object k + 1 painted
+ *   over object k, on black.
+ * Outputs, each may be NULL: obs_u8 [B, H, W, 3] the bytes; obs [B, 3, H, W] what ocrl_obs_u8_to_f32 gives for them (0.0f or 1.0f:
+ *   only the bytes 0 and 255 occur); masks [B, K + 1, H, W]: plane k is 1.0f where object k is the last one covering the pixel, plane K
+ *   where none does, 0.0f elsewhere; objs [B, K, 5] = (colour index, shape index, scale index, x, y).
+ * _uniforms: out [n] = bits24 / 2^24 of draws first .. first + n - 1 (all below 2^16) of scene `index` (masked as above). */
+typedef struct {
+    int H;
+    int K;
+} ocrl_scenes_desc;
+int ocrl_scenes_batch(const ocrl_scenes_desc* d, unsigned long long seed, const long long* indices /* device int64 [B] */, int B,
+                      float* obs /* [B,3,H,W] or NULL */, unsigned char* obs_u8 /* [B,H,W,3] or NULL */, float* masks /* [B,K+1,H,W] or NULL */,
+                      float* objs /* [B,K,5] or NULL */, void* stream);
+int ocrl_scenes_uniforms(unsigned long long seed, long long index, int first, int n, float* out /* [n] */, void* stream);
+
 /* ---- the per-object MLP of the ground-truth-state encoder (ocrs/gt/gt_module.py:14-27): x [M, D] through nl layers
  *      h_l = act_l(h_{l-1} W_l^T + b_l), W_l [dims[l], dims[l-1]] (torch layout), acts[l] != 0: ReLU, 0: none.  M = batch x objects rows
  *      (1 <= M < 2^22), 1 <= D <= 64, 1 <= nl <= 4, every dims[l] a multiple of 4 in 4 .. 256; anything else: ws_floats == 0 and the

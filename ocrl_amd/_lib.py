@@ -64,6 +64,11 @@ class SpriteEnvDesc(ctypes.Structure):
                [("task", c_int), ("obj_comp", c_int), ("unseen_mode", c_int), ("unseen_colors", c_int * 2)]
 
 
+class ScenesDesc(ctypes.Structure):
+    """mirror of ocrl_scenes_desc (include/ocrl_hip.h)"""
+    _fields_ = [("H", c_int), ("K", c_int)]
+
+
 def acnet_desc(B, F, A, dims, acts):
     """AcnetDesc of three trunks: dims / acts = (shared, policy, value) sequences of widths / activation codes (0 none, 1 relu, 2 tanh)"""
     d = AcnetDesc(B=B, F=F, A=A)
@@ -283,6 +288,8 @@ def lib():
     L.ocrl_gt_mlp_fwd.argtypes = [p, POINTER(p), p, c_int, c_int, c_int, POINTER(c_int), POINTER(c_int), p, c_size_t, p]
     L.ocrl_gt_mlp_bwd.argtypes = [p, p, POINTER(p), p, POINTER(p), c_int, c_int, c_int, POINTER(c_int), POINTER(c_int), p, c_size_t, p]
     L.ocrl_sprite_env_uniforms.argtypes = [c_ulonglong, c_longlong, c_int, c_longlong, c_int, c_int, p, p]
+    L.ocrl_scenes_batch.argtypes = [POINTER(ScenesDesc), c_ulonglong, p, c_int, p, p, p, p, p]
+    L.ocrl_scenes_uniforms.argtypes = [c_ulonglong, c_longlong, c_int, c_int, p, p]
     L.ocrl_comm_unique_id.argtypes = [p, c_size_t]
     L.ocrl_comm_init.argtypes = [POINTER(p), c_int, c_int, p]
     L.ocrl_comm_allreduce.argtypes = [p, p, c_longlong, p]

@@ -4,6 +4,7 @@
 // channel plane per 32-bit store.  No atomics; every loop is bounded.  Compiled with -ffp-contract=off: each position is the written
 // sequence of fp32 roundings, so a numpy fp32 restatement (tests/sprite_env_ref.py) follows it bit for bit.
 #include "sprite_env.h"
+#include "sprite_shapes.h"
 
 #pragma clang fp contract(off)
 
@@ -49,12 +50,6 @@ __device__ inline float draw_pos(Stream& s, int mode, float lo, float hi, float 
     const float w = b - a;
     const float p = w * s.u01();
     return a + p;
-}
-
-__device__ inline float dist2d(float ax, float ay, float bx, float by) {
-    const float dx = ax - bx, dy = ay - by;
-    const float xx = dx * dx, yy = dy * dy;
-    return sqrtf(xx + yy);
 }
 
 // the Target episode's objects: the target index, then every other object's triple, redrawn while it equals the target's -> target
@@ -263,21 +258,7 @@ __global__ __launch_bounds__(256) void sprite_state_obs_kernel(const float* __re
 }
 
 // ---------------------------------------------------------------------------------------------------------------- the renderer
-// the predicates of ocrl_amd/utils/data.py:_mask in fp32; (dx, dy) = pixel centre - sprite centre, r = scale / 2
-__device__ inline bool sprite_covers(int shape, float dx, float dy, float r) {
-    const float ax = fabsf(dx), ay = fabsf(dy);
-    if (shape == 0) return ax <= r && ay <= r;
-    if (shape == 1) {
-        const float t = (dy + r) / (2.f * r);
-        return t >= 0.f && t <= 1.f && ax <= r * t;
-    }
-    if (shape == 2) return sqrtf(ax) + sqrtf(ay) <= sqrtf(r) * 1.25f;
-    const float xx = dx * dx, yy = dy * dy;
-    return xx + yy <= r * r;
-}
-
-__constant__ uint32_t SPRITE_RGB[7] = {0xFF0000u, 0x00FF00u, 0x00FFFFu, 0x0000FFu, 0xFFFF00u, 0xCBC0FFu, 0x2A2AA5u};       // byte 0 = red
-
+// (the shape predicates and the colour table: sprite_shapes.h)
 // mode 0: [E, 3, H, W]; 1: [E, H, W, 3]; 2: masks [E, R + 1, H, W, 1] (row j alone and unoccluded; the background last)
 __global__ __launch_bounds__(256) void sprite_render_kernel(const float* __restrict__ rows, int R, int H, int band_rows, int bands, int mode,
                                                             unsigned char* __restrict__ out) {

@@ -2,7 +2,8 @@
 the background last).  Reads the reference's HDF5 when h5py and the file are available, otherwise generates random-N5C4S4S2-style
 scenes deterministically per index.  With raw_uint8 (the default of get_dataloaders) a sample carries the image as the dataset stores
 it — "obss_u8", uint8 HWC — and the permute + /255 of utils/datasets.py:17 runs on the GPU (ocrl_obs_u8_to_f32) after a 4x smaller
-upload; raw_uint8=False gives the reference's float CHW "obss"."""
+upload; raw_uint8=False gives the reference's float CHW "obss".  With dataset.on_device the synthetic scenes never exist on the host:
+device_scenes.py makes each batch on the GPU."""
 import os
 
 import numpy as np
@@ -67,9 +68,26 @@ class H5DataSet(Dataset):
         return self._num_samples
 
 
-def get_dataloaders(config, batch_size, num_workers, rank=0, world=1, seed=0, raw_uint8=True):
-    """utils/tools.py:155-178 without the wandb download path"""
+def _device_loaders(config, batch_size, rank, world, seed, device, datafile):
+    """dataset.on_device: the synthetic scenes made on `device` batch by batch (device_scenes.py); no worker, no upload"""
+    from .device_scenes import DeviceScenes
+    if datafile and os.path.isfile(datafile):
+        raise ValueError(f"dataset.on_device generates the scenes, but dataset.datadir {datafile} exists: unset one of the two keys")
+    if device is None or torch.device(device).type != "cuda":
+        raise ValueError(f"dataset.on_device needs the CUDA device the model trains on (got device={device!r})")
+    kw = dict(num_objs=5, with_masks=bool(config.get("with_masks", False)), with_objs=bool(config.get("with_objs", False)))
+    train = DeviceScenes(config.get("synthetic_train", 100000), config.obs_size, seed * 2 + 1, batch_size, device, shuffle=True, drop_last=True,
+                         rank=rank, world=world, **kw)
+    val = DeviceScenes(config.get("synthetic_val", 1000), config.obs_size, seed * 2 + 2, batch_size, device, **kw)
+    return train, val
+
+
+def get_dataloaders(config, batch_size, num_workers, rank=0, world=1, seed=0, raw_uint8=True, device=None):
+    """utils/tools.py:155-178 without the wandb download path; with dataset.on_device the scenes are made on `device` and num_workers
+    is ignored"""
     datafile = config.datadir if config.get("datadir") else None
+    if config.get("on_device", False):
+        return _device_loaders(config, batch_size, rank, world, seed, device, datafile)
     if datafile and os.path.isfile(datafile):
         try:
             import h5py

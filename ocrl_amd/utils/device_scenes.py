@@ -1,0 +1,102 @@
+"""The pre-training scenes made on the GPU (include/ocrl_hip.h: ocrl_scenes_*): a loader with a DataLoader's surface whose batches never
+exist on the host.  Scene i of a seed is a function of (seed, i) alone, so an epoch is a list of indices: the host shuffles and shards
+integers (``epoch_indices``, pure torch), uploads them once per epoch, and every batch is one ocrl_scenes_batch call on the current
+stream.  Nothing is read back.  Same distribution and draw order as ocrl_amd/utils/data.py:random_sprite_scenes, not numpy's bit stream:
+dataset.on_device=True trains on other scenes of the same kind than the host loader does."""
+import torch
+
+from .. import _bridge, _lib
+
+
+def _rank_indices(n, seed, epoch, rank, world, shuffle):
+    """the scene indices rank `rank` of `world` sees in epoch `epoch`, in order: elements rank::world of the first n - n % world of the
+    epoch's permutation (shuffle: torch.randperm from a CPU generator seeded by (seed, epoch); else arange)"""
+    n, world, rank = int(n), int(world), int(rank)
+    if n < 1 or world < 1 or not 0 <= rank < world:
+        raise ValueError(f"epoch_indices: n >= 1 and 0 <= rank < world (got n {n}, rank {rank}, world {world})")
+    if shuffle:
+        g = torch.Generator()
+        g.manual_seed((int(seed) * 1000003 + int(epoch)) & 0x7FFFFFFFFFFFFFFF)
+        order = torch.randperm(n, generator=g)
+    else:
+        order = torch.arange(n, dtype=torch.int64)
+    return order[:n - n % world][rank::world].contiguous()
+
+
+def epoch_indices(n, seed, epoch, rank, world, batch_size, shuffle, drop_last=True):
+    """-> CPU int64 [batches, batch_size]: the batches of one rank's epoch, the incomplete last one dropped.  drop_last=False keeps it:
+    then a list of 1-D tensors, the last of which may be shorter"""
+    idx, bs = _rank_indices(n, seed, epoch, rank, world, shuffle), int(batch_size)
+    if bs < 1:
+        raise ValueError(f"epoch_indices: batch_size >= 1 (got {bs})")
+    if drop_last:
+        return idx[:len(idx) - len(idx) % bs].view(-1, bs)
+    return list(idx.split(bs))
+
+
+class _Scenes:
+    """the `.dataset` of a DeviceScenes: scene i of the seed, as a one-scene batch without its batch dimension"""
+
+    def __init__(self, loader):
+        self._loader = loader
+
+    def __len__(self):
+        return self._loader.n
+
+    def __getitem__(self, i):
+        i = int(i)
+        if not -self._loader.n <= i < self._loader.n:
+            raise IndexError(f"scene {i} of {self._loader.n}")
+        idx = torch.tensor([i % self._loader.n], dtype=torch.int64).to(self._loader.device)
+        return {k: v[0] for k, v in self._loader.batch(idx).items()}
+
+
+class DeviceScenes:
+    """an iterable of batches {"obss": fp32 [B,3,H,W], "masks": [B,K+1,H,W,1] (with_masks), "objs": [B,K,5] (with_objs)} of fresh
+    tensors on `device`, with the surface train_ocr.py uses of a DataLoader: len() = batches, .dataset, .sampler.set_epoch"""
+
+    def __init__(self, n, size, seed, batch_size, device, num_objs=5, with_masks=False, with_objs=False, shuffle=False, drop_last=False,
+                 rank=0, world=1):
+        self.device = torch.device(device) if device is not None else None
+        if self.device is None or self.device.type != "cuda":
+            raise ValueError(f"DeviceScenes: the scenes are made on a CUDA device (got device={device!r})")
+        self.n, self.size, self.seed, self.batch_size, self.num_objs = int(n), int(size), int(seed), int(batch_size), int(num_objs)
+        self.with_masks, self.with_objs, self.shuffle, self.drop_last = bool(with_masks), bool(with_objs), bool(shuffle), bool(drop_last)
+        self.rank, self.world, self.epoch = int(rank), int(world), 0
+        if not (8 <= self.size <= 512 and self.size % 4 == 0 and 1 <= self.num_objs <= 15):
+            raise ValueError(f"DeviceScenes: obs_size a multiple of 4 in [8, 512] and 1 to 15 objects (got {self.size}, {self.num_objs})")
+        _rank_indices(self.n, 0, 0, self.rank, self.world, False)            # the same refusals as an epoch's, before the first one
+        if self.batch_size < 1:
+            raise ValueError(f"DeviceScenes: batch_size >= 1 (got {self.batch_size})")
+        self._desc = _lib.ScenesDesc(H=self.size, K=self.num_objs)
+        self.dataset, self.sampler = _Scenes(self), self
+
+    def set_epoch(self, epoch):
+        self.epoch = int(epoch)
+
+    def __len__(self):
+        per_rank = (self.n - self.n % self.world) // self.world
+        return per_rank // self.batch_size if self.drop_last else -(-per_rank // self.batch_size)
+
+    def batch(self, idx):
+        """the scenes of idx (int64 [B] on the device, contiguous) as one ocrl_scenes_batch call on the current stream"""
+        B, H, K = idx.shape[0], self.size, self.num_objs
+        obs = torch.empty(B, 3, H, H, dtype=torch.float32, device=self.device)
+        masks = torch.empty(B, K + 1, H, H, dtype=torch.float32, device=self.device) if self.with_masks else None
+        objs = torch.empty(B, K, 5, dtype=torch.float32, device=self.device) if self.with_objs else None
+        _bridge.launch(self.device, _lib.lib().ocrl_scenes_batch, self._desc, self.seed & 0xFFFFFFFFFFFFFFFF, _lib.ptr(idx), B, _lib.ptr(obs), None,
+                       _lib.ptr(masks), _lib.ptr(objs))
+        out = {"obss": obs}
+        if masks is not None:
+            out["masks"] = masks.unsqueeze(-1)
+        if objs is not None:
+            out["objs"] = objs
+        return out
+
+    def __iter__(self):
+        idx = _rank_indices(self.n, self.seed, self.epoch, self.rank, self.world, self.shuffle).to(self.device)    # one upload per epoch
+        if self.shuffle:
+            self.epoch += 1                # a pass that no set_epoch precedes takes the next order, as a shuffling DataLoader's would
+        bs = self.batch_size
+        for b in range(len(self)):
+            yield self.batch(idx[b * bs:(b + 1) * bs])

@@ -108,7 +108,7 @@ def main(argv=None):
 
     np.random.seed(config.seed)
     torch.manual_seed(config.seed)      # identical initial weights on every rank
-    train_dl, val_dl = get_dataloaders(config.dataset, config.batch_size, config.num_workers, rank, world, config.seed)
+    train_dl, val_dl = get_dataloaders(config.dataset, config.batch_size, config.num_workers, rank, world, config.seed, device=config.device)
     model = getattr(ocrs, config.ocr.name)(config.ocr, config.dataset)
     model._module._max_batch = config.batch_size
     model.to(config.device)

@@ -53,7 +53,7 @@ def main(argv=None):
 
     np.random.seed(config.seed)
     torch.manual_seed(config.seed)
-    train_dl, val_dl = get_dataloaders(config.dataset, config.batch_size, config.num_workers, seed=config.seed)
+    train_dl, val_dl = get_dataloaders(config.dataset, config.batch_size, config.num_workers, seed=config.seed, device=config.device)
     ocr = getattr(ocrs, config.ocr.name)(config.ocr, config.dataset)
     if hasattr(ocr._module, "_max_batch"):
         ocr._module._max_batch = config.batch_size
