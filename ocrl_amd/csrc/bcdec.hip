@@ -1,23 +1,17 @@
 // Spatial-broadcast decoder of the Slot-Attention configuration (reference: ocrs/common/models.py:110-141,
 // ocrs/slate/slate_module.py:218-225).
 //
-// First layer without the broadcast tensor: the 5x5 / 192->64 convolution runs on  s[bk,:] + posmap[y,x,:]
-// (spatially constant per slot plus a batch-independent map).  A convolution is linear, so
-//     c1[bk,y,x,:] = relu( conv(posmap)[y,x,:] + sum_{taps valid at (y,x)} W_tap s[bk,:] + b )
-// i.e. one tiny GEMM  M[bk, tap, :] = W_tap s  plus 25 border classes (5 row x 5 column classes of valid taps):
-// 82 % of the configuration's forward FLOPs disappear.  The position-map term is folded through
-// the 4-channel ramp grid: conv(posmap) = sum_taps (Wc[tap,:,0..3] . grid(y+dy,x+dx) + Wc[tap,:,4]).
-// Layers 2-3 reuse conv.hip; the 64->4 output convolution and the slot mixture have their own kernels here.
+// The first layer (5x5 / 192->64 on the broadcast slots plus the position map) never builds the broadcast tensor: it runs through
+// the shortcut of bcast_l1.hip, c1 = relu(conv(posmap) + sum_{taps valid at (y,x)} W_tap s + b) with 25 border classes: 82 % of the
+// configuration's forward FLOPs disappear.  The position-map term is folded through the 4-channel ramp grid:
+// conv(posmap) = sum_taps (Wc[tap,:,0..3] . grid(y+dy,x+dx) + Wc[tap,:,4]); this file composes Wc (and takes its gradient apart).
+// Layers 2-3 reuse conv.hip; the 64->4 output convolution (shared with IODINE) and the slot mixture have their own kernels here.
 #include "common.h"
 #include "kernels.h"
 #include <stdlib.h>
 
 #define BT_H 4
 #define BT_W 32
-
-__device__ inline int bc_class(int y, int S) { return y < 2 ? y : (y >= S - 2 ? 4 - (S - 1 - y) : 2); }
-// tap row ky (0..4) is inside the image for row class rc
-__device__ inline bool bc_valid(int rc, int ky) { return rc == 0 ? ky >= 2 : rc == 1 ? ky >= 1 : rc == 3 ? ky <= 3 : rc == 4 ? ky <= 2 : true; }
 
 // Wc[tap][co][0..3] = sum_ci W1[co][ci][tap] Wpos[ci][j];  Wc[tap][co][4] = sum_ci W1[co][ci][tap] bpos[ci]
 // W1r[tap][co][ci] = W1[co][ci][tap]
@@ -36,121 +30,6 @@ __global__ void bc_compose_kernel(const float* __restrict__ W1, const float* __r
     }
 #pragma unroll
     for (int j = 0; j < 5; ++j) Wc[i * 5 + j] = a[j];
-}
-
-__device__ inline void bc_grid(int y, int x, int S, float (&g)[5]) {
-    const float east = S > 1 ? (float)x / (float)(S - 1) : 0.f, south = S > 1 ? (float)y / (float)(S - 1) : 0.f;
-    g[0] = 1.f - south; g[1] = south; g[2] = 1.f - east; g[3] = east; g[4] = 1.f;
-}
-
-// P1[y][x][co] = sum over taps inside the image of Wc[tap][co][:] . (grid(y+dy, x+dx), 1)
-__global__ void bc_posconv_kernel(const float* __restrict__ Wc, float* __restrict__ P1, int S) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= S * S * 64) return;
-    const int co = i % 64, x = (i / 64) % S, y = i / (64 * S);
-    float a = 0.f;
-    for (int ky = 0; ky < 5; ++ky)
-        for (int kx = 0; kx < 5; ++kx) {
-            const int yy = y + ky - 2, xx = x + kx - 2;
-            if (yy < 0 || yy >= S || xx < 0 || xx >= S) continue;
-            float g[5];
-            bc_grid(yy, xx, S, g);
-            const float* w = Wc + ((ky * 5 + kx) * 64 + co) * 5;
-            a += w[0] * g[0] + w[1] * g[1] + w[2] * g[2] + w[3] * g[3] + w[4];
-        }
-    P1[i] = a;
-}
-
-// forward: Tc[bk][cls][co] = sum_{taps valid in cls} M[bk][tap][co];  backward (transpose): dM[bk][tap][co] = sum_{cls valid} dT
-__global__ void bc_class_sum_kernel(const float* __restrict__ in, float* __restrict__ out, int BK, int forward) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= BK * 25 * 64) return;
-    const int co = i % 64, a = (i / 64) % 25;
-    const long long bk = i / (64 * 25);
-    float s = 0.f;
-    for (int b = 0; b < 25; ++b) {
-        const int cls = forward ? a : b, tap = forward ? b : a;
-        if (bc_valid(cls / 5, tap / 5) && bc_valid(cls % 5, tap % 5)) s += in[(bk * 25 + b) * 64 + co];
-    }
-    out[i] = s;
-}
-
-// c1[bk][y][x][co] = relu(P1[y][x][co] + Tc[bk][cls(y,x)][co] + b1[co])
-__global__ void bc_layer1_kernel(const float* __restrict__ P1, const float* __restrict__ Tc, const float* __restrict__ b1,
-                                 float* __restrict__ c1, int BK, int S) {
-    const long long n4 = (long long)BK * S * S * 16;
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n4) return;
-    const int c4 = i % 16;
-    const long long pix = i / 16;
-    const int x = pix % S, y = (pix / S) % S;
-    const long long bk = pix / ((long long)S * S);
-    const int cls = bc_class(y, S) * 5 + bc_class(x, S);
-    const float4 p = *reinterpret_cast<const float4*>(P1 + ((size_t)y * S + x) * 64 + c4 * 4);
-    const float4 t = *reinterpret_cast<const float4*>(Tc + (bk * 25 + cls) * 64 + c4 * 4);
-    const float4 b = *reinterpret_cast<const float4*>(b1 + c4 * 4);
-    *reinterpret_cast<float4*>(c1 + i * 4) = make_float4(fmaxf(p.x + t.x + b.x, 0.f), fmaxf(p.y + t.y + b.y, 0.f),
-                                                        fmaxf(p.z + t.z + b.z, 0.f), fmaxf(p.w + t.w + b.w, 0.f));
-}
-
-// rowpart[bk][y][k][co] = sum over the pixels of row y in column class k of g[bk][y][x][co]   (one block per (bk, y));
-// bc_layer1_reduce_kernel then sums the rows of each row class in row order (no float atomics: bitwise reproducible)
-__global__ __launch_bounds__(256) void bc_layer1_bwd_kernel(const float* __restrict__ g, float* __restrict__ rowpart, int S) {
-    __shared__ float red[4][5][64];
-    const int y = blockIdx.x % S;
-    const long long bk = blockIdx.x / S;
-    const int co = threadIdx.x & 63, xl = threadIdx.x >> 6;
-    float a[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
-    const float* row = g + ((bk * S + y) * S) * 64;
-    for (int x = xl; x < S; x += 4) {
-        const float v = row[(size_t)x * 64 + co];
-        const int cc = bc_class(x, S);
-#pragma unroll
-        for (int k = 0; k < 5; ++k) a[k] += (cc == k) ? v : 0.f;
-    }
-#pragma unroll
-    for (int k = 0; k < 5; ++k) red[xl][k][co] = a[k];
-    __syncthreads();
-    if (xl == 0) {
-#pragma unroll
-        for (int k = 0; k < 5; ++k) rowpart[((bk * S + y) * 5 + k) * 64 + co] = (red[0][k][co] + red[1][k][co]) + (red[2][k][co] + red[3][k][co]);
-    }
-}
-// dT[bk][rc*5+k][co] = sum over the rows y of row class rc of rowpart[bk][y][k][co]
-__global__ void bc_layer1_reduce_kernel(const float* __restrict__ rowpart, float* __restrict__ dT, long long n, int S) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;      // over [BK][25][64]
-    if (i >= n) return;
-    const int co = i & 63, cls = (i >> 6) % 25;
-    const long long bk = i / (25 * 64);
-    const int rc = cls / 5, k = cls - rc * 5;
-    const int y0 = rc < 2 ? rc : (rc == 2 ? 2 : S - 2 + (rc - 3)), y1 = rc == 2 ? S - 2 : y0 + 1;
-    float a = 0.f;
-    for (int y = y0; y < y1; ++y) a += rowpart[((bk * S + y) * 5 + k) * 64 + co];
-    dT[i] = a;
-}
-
-// dWc[tap][co][j] = sum_{y,x : tap inside} G[y][x][co] * (grid_j(y+dy, x+dx) | 1)     (one block per tap, G = sum over bk)
-__global__ __launch_bounds__(256) void bc_posconv_bwd_kernel(const float* __restrict__ G, float* __restrict__ dWc, int S) {
-    __shared__ float red[4][5][64];
-    const int tap = blockIdx.x, ky = tap / 5, kx = tap % 5;
-    const int co = threadIdx.x & 63, pl = threadIdx.x >> 6;
-    float a[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
-    for (int pix = pl; pix < S * S; pix += 4) {
-        const int x = pix % S, y = pix / S;
-        const int yy = y + ky - 2, xx = x + kx - 2;
-        if (yy < 0 || yy >= S || xx < 0 || xx >= S) continue;
-        float gr[5];
-        bc_grid(yy, xx, S, gr);
-        const float v = G[(size_t)pix * 64 + co];
-#pragma unroll
-        for (int j = 0; j < 5; ++j) a[j] += v * gr[j];
-    }
-#pragma unroll
-    for (int j = 0; j < 5; ++j) red[pl][j][co] = a[j];
-    __syncthreads();
-    if (pl == 0)
-#pragma unroll
-        for (int j = 0; j < 5; ++j) dWc[(tap * 64 + co) * 5 + j] = red[0][j][co] + red[1][j][co] + red[2][j][co] + red[3][j][co];
 }
 
 // dW1[co][ci][tap] = dW1r[tap][co][ci] + sum_j dWc[tap][co][j] Wpos[ci][j] + dWc[tap][co][4] bpos[ci]
@@ -409,38 +288,6 @@ __global__ __launch_bounds__(256) void bc_mix_kernel(const float* __restrict__ o
 int bc_compose_launch(const float* W1, const float* Wpos, const float* bpos, float* Wc, float* W1r, int D, hipStream_t st) {
     hipLaunchKernelGGL(bc_compose_kernel, GRID1D(25 * 64), 0, st, W1, Wpos, bpos, Wc, W1r, D);
     OCRL_CHECK_LAUNCH("bc_compose");
-    return 0;
-}
-int bc_posconv_launch(const float* Wc, float* P1, int S, hipStream_t st) {
-    OCRL_REQUIRE(S >= 5, "broadcast decoder needs obs_size >= 5");
-    hipLaunchKernelGGL(bc_posconv_kernel, GRID1D(S * S * 64), 0, st, Wc, P1, S);
-    OCRL_CHECK_LAUNCH("bc_posconv");
-    return 0;
-}
-int bc_class_sum_launch(const float* in, float* out, int BK, int forward, hipStream_t st) {
-    hipLaunchKernelGGL(bc_class_sum_kernel, GRID1D((long long)BK * 25 * 64), 0, st, in, out, BK, forward);
-    OCRL_CHECK_LAUNCH("bc_class_sum");
-    return 0;
-}
-int bc_layer1_launch(const float* P1, const float* Tc, const float* b1, float* c1, int BK, int S, hipStream_t st) {
-    hipLaunchKernelGGL(bc_layer1_kernel, GRID1D((long long)BK * S * S * 16), 0, st, P1, Tc, b1, c1, BK, S);
-    OCRL_CHECK_LAUNCH("bc_layer1");
-    return 0;
-}
-size_t bc_layer1_bwd_ws_floats(int BK, int S) { return (size_t)BK * S * 5 * 64; }
-// dT [BK][25][64] is written (not accumulated); ws: bc_layer1_bwd_ws_floats() floats of scratch
-int bc_layer1_bwd_launch(const float* g, float* dT, int BK, int S, float* ws, size_t ws_floats, hipStream_t st) {
-    OCRL_REQUIRE(S >= 5 && ws && ws_floats >= bc_layer1_bwd_ws_floats(BK, S), "bc_layer1_bwd: S < 5 or scratch too small");
-    hipLaunchKernelGGL(bc_layer1_bwd_kernel, dim3(BK * S), dim3(256), 0, st, g, ws, S);
-    OCRL_CHECK_LAUNCH("bc_layer1_bwd");
-    const long long n = (long long)BK * 25 * 64;
-    hipLaunchKernelGGL(bc_layer1_reduce_kernel, dim3(cdiv(n, 256)), dim3(256), 0, st, ws, dT, n, S);
-    OCRL_CHECK_LAUNCH("bc_layer1_reduce");
-    return 0;
-}
-int bc_posconv_bwd_launch(const float* G, float* dWc, int S, hipStream_t st) {
-    hipLaunchKernelGGL(bc_posconv_bwd_kernel, dim3(25), dim3(256), 0, st, G, dWc, S);
-    OCRL_CHECK_LAUNCH("bc_posconv_bwd");
     return 0;
 }
 int bc_compose_bwd_launch(const float* W1, const float* Wpos, const float* bpos, const float* dWc, const float* dW1r, float* dW1,

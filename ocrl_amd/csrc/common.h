@@ -131,6 +131,10 @@ __device__ inline float wave_max(float v) {
     return v;
 }
 
+__device__ inline float elu_(float v) { return v > 0.f ? v : expf(v) - 1.f; }
+// coordinate i of S evenly spaced points over [-1, 1] (IODINE's coordinate channels)
+__device__ inline float io_lin(int i, int S) { return S > 1 ? -1.f + 2.f * (float)i / (float)(S - 1) : -1.f; }
+
 // ---- reductions whose order is part of the result.  The library is tested to the bit (two-run determinism, fused == unfused, fixture
 // replays), so each order is written once, here; wave_sum / wave_max above run their xor-shuffle stages 32 -> 1.
 //

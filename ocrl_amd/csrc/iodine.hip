@@ -1,9 +1,9 @@
 // IODINE-specific kernels (reference: ocrs/iodine/iodine_module.py).  The 3x3 / 64-channel decoder convolutions and every
 // dense contraction (linears, LSTM, stride-2 refinement convolutions as im2col GEMMs) run on conv.hip / gemm.hip; this
 // file holds what is particular to the model:
-//   * the decoder's first layer on the spatial broadcast (iodine_module.py:438-470): a convolution of a per-slot
-//     constant plus two coordinate channels is  P1[y,x,:] + T[bk, class(y,x), :]  — one [BK,64]x[64,576] GEMM and 9 border
-//     classes instead of a 66-channel convolution over every pixel;
+//   * the weight packing of the decoder's first layer on the spatial broadcast (iodine_module.py:438-470): a convolution of a
+//     per-slot constant plus two coordinate channels is  P1[y,x,:] + T[bk, class(y,x), :]  — one [BK,64]x[64,576] GEMM and 9 border
+//     classes instead of a 66-channel convolution over every pixel; the layer itself is bcast_l1.hip, shared with bcdec.hip;
 //   * the mixture likelihood / ELBO, its in-forward gradients and the 17-channel refinement encoding (:92-229) with the
 //     reference's non-affine layer norms (:307-330), forward and backward;
 //   * im2col / col2im for the stride-2 refinement convolutions, pooling, the double ELU, the LSTM cell, the latent vector.
@@ -12,13 +12,6 @@
 #include "kernels.h"
 
 #define IO_ENC 17
-
-__device__ inline float elu_(float v) { return v > 0.f ? v : expf(v) - 1.f; }
-__device__ inline float io_lin(int i, int S) { return S > 1 ? -1.f + 2.f * (float)i / (float)(S - 1) : -1.f; }
-// border class of a coordinate for a 3x3 "same" convolution: 0 first row/column, 2 last, 1 interior
-__device__ inline int io_cls(int i, int S) { return i == 0 ? 0 : (i == S - 1 ? 2 : 1); }
-// tap offset k (0..2) stays inside the image for class c
-__device__ inline bool io_valid(int c, int k) { return !(c == 0 && k == 0) && !(c == 2 && k == 2); }
 
 // ------------------------------------------------------------------------------------------- sampling + KL
 // slots = mu + exp(ls) * eps (eps injected or drawn: Box-Muller on the counter RNG, stored for the backward);
@@ -63,108 +56,6 @@ __global__ void io_w1_pack_kernel(const float* __restrict__ W1, float* __restric
     const float v = W1[((size_t)co * (L + 2) + ci) * 9 + tap];
     if (ci < L) W1r[((size_t)tap * 64 + co) * L + ci] = v;
     else Wxy[(tap * 64 + co) * 2 + (ci - L)] = v;
-}
-// P1[y][x][co] = b1[co] + sum over taps inside the image of Wxy[tap][co][0] * xx(x+dx) + Wxy[tap][co][1] * yy(y+dy)
-__global__ void io_p1_kernel(const float* __restrict__ Wxy, const float* __restrict__ b1, float* __restrict__ P1, int S) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= S * S * 64) return;
-    const int co = i & 63, x = (i >> 6) % S, y = (i >> 6) / S;
-    float a = b1[co];
-    for (int ky = 0; ky < 3; ++ky)
-        for (int kx = 0; kx < 3; ++kx) {
-            const int yy = y + ky - 1, xx = x + kx - 1;
-            if (yy < 0 || yy >= S || xx < 0 || xx >= S) continue;
-            const float* w = Wxy + ((ky * 3 + kx) * 64 + co) * 2;
-            a += w[0] * io_lin(xx, S) + w[1] * io_lin(yy, S);
-        }
-    P1[i] = a;
-}
-// forward: T[bk][cls][co] = sum_{taps valid in cls} M[bk][tap][co];  backward: dM[bk][tap][co] = sum_{cls valid for tap} dT[bk][cls][co]
-__global__ void io_class_sum_kernel(const float* __restrict__ in, float* __restrict__ out, long long BK, int forward) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= BK * 9 * 64) return;
-    const int co = i & 63, j = (i >> 6) % 9;
-    const long long bk = i / (9 * 64);
-    const int j0 = j / 3, j1 = j % 3;
-    float a = 0.f;
-    for (int q = 0; q < 9; ++q) {
-        const int q0 = q / 3, q1 = q % 3;
-        // forward: j = class, q = tap; backward: j = tap, q = class
-        const bool ok = forward ? (io_valid(j0, q0) && io_valid(j1, q1)) : (io_valid(q0, j0) && io_valid(q1, j1));
-        if (ok) a += in[(bk * 9 + q) * 64 + co];
-    }
-    out[i] = a;
-}
-// c1[bk][y][x][co] = elu(P1[y][x][co] + T[bk][cls(y,x)][co])
-__global__ void io_layer1_kernel(const float* __restrict__ P1, const float* __restrict__ T, float* __restrict__ c1, long long BK, int S) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;      // float4 index
-    const long long n4 = BK * S * S * 16;
-    if (i >= n4) return;
-    const int c4 = i & 15;
-    const long long pix = (i >> 4) % ((long long)S * S), bk = (i >> 4) / ((long long)S * S);
-    const int x = pix % S, y = pix / S;
-    const float4 p = *reinterpret_cast<const float4*>(P1 + pix * 64 + c4 * 4);
-    const float4 t = *reinterpret_cast<const float4*>(T + (bk * 9 + io_cls(y, S) * 3 + io_cls(x, S)) * 64 + c4 * 4);
-    *reinterpret_cast<float4*>(c1 + i * 4) = make_float4(elu_(p.x + t.x), elu_(p.y + t.y), elu_(p.z + t.z), elu_(p.w + t.w));
-}
-// rowpart[bk][y][c][co] = sum over the pixels of row y in column class c of g[bk][y][x][co]   (one block per (bk, y));
-// io_layer1_reduce_kernel sums the rows of each row class in row order (no float atomics: bitwise reproducible)
-__global__ __launch_bounds__(256) void io_layer1_bwd_kernel(const float* __restrict__ g, float* __restrict__ rowpart, int S) {
-    __shared__ float red[4][3][64];
-    const long long bk = blockIdx.x / S;
-    const int y = blockIdx.x % S;
-    const int co = threadIdx.x & 63, part = threadIdx.x >> 6;
-    float a[3] = {0.f, 0.f, 0.f};
-    const float* row = g + ((bk * S + y) * S) * 64 + co;
-    for (int x = part; x < S; x += 4) a[io_cls(x, S)] += row[(size_t)x * 64];
-    for (int c = 0; c < 3; ++c) red[part][c][co] = a[c];
-    __syncthreads();
-    if (part == 0) {
-        for (int c = 0; c < 3; ++c) rowpart[((bk * S + y) * 3 + c) * 64 + co] = (red[0][c][co] + red[1][c][co]) + (red[2][c][co] + red[3][c][co]);
-    }
-}
-// dT[bk][rc*3+c][co] = sum over the rows y of row class rc of rowpart[bk][y][c][co]
-__global__ void io_layer1_reduce_kernel(const float* __restrict__ rowpart, float* __restrict__ dT, long long n, int S) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;      // over [BK][9][64]
-    if (i >= n) return;
-    const int co = i & 63, cls = (i >> 6) % 9;
-    const long long bk = i / (9 * 64);
-    const int rc = cls / 3, c = cls - rc * 3;
-    const int y0 = rc == 0 ? 0 : (rc == 1 ? 1 : S - 1), y1 = rc == 1 ? S - 1 : y0 + 1;
-    float a = 0.f;
-    for (int y = y0; y < y1; ++y) a += rowpart[((bk * S + y) * 3 + c) * 64 + co];
-    dT[i] = a;
-}
-// Weight gradient of layer 1 from the accumulated pieces: dW1[co][ci<L][tap] = dW1r[tap][co][ci];
-// dW1[co][L+j][tap] = sum_{pixels where tap is inside} G[y][x][co] * coord_j;  db1[co] = sum G   (one block per tap)
-__global__ __launch_bounds__(256) void io_w1_grad_kernel(const float* __restrict__ dW1r, const float* __restrict__ G, float* __restrict__ dW1,
-                                                         float* __restrict__ db1, int S, int L) {
-    __shared__ float red[4][3][64];
-    const int tap = blockIdx.x, ky = tap / 3, kx = tap % 3;
-    const int co = threadIdx.x & 63, part = threadIdx.x >> 6;
-    float ax = 0.f, ay = 0.f, ab = 0.f;
-    for (int pix = part; pix < S * S; pix += 4) {
-        const int x = pix % S, y = pix / S;
-        const int yy = y + ky - 1, xx = x + kx - 1;
-        if (yy < 0 || yy >= S || xx < 0 || xx >= S) continue;
-        const float v = G[(size_t)pix * 64 + co];
-        ax += v * io_lin(xx, S);
-        ay += v * io_lin(yy, S);
-        ab += v;
-    }
-    red[part][0][co] = ax; red[part][1][co] = ay; red[part][2][co] = ab;
-    __syncthreads();
-    if (part == 0) {
-        float s[3];
-        for (int c = 0; c < 3; ++c) s[c] = red[0][c][co] + red[1][c][co] + red[2][c][co] + red[3][c][co];
-        dW1[((size_t)co * (L + 2) + L) * 9 + tap] = s[0];
-        dW1[((size_t)co * (L + 2) + L + 1) * 9 + tap] = s[1];
-        if (tap == 4) db1[co] = s[2];
-    }
-    for (int i = threadIdx.x; i < 64 * L; i += 256) {
-        const int ci = i % L, c2 = i / L;
-        dW1[((size_t)c2 * (L + 2) + ci) * 9 + tap] = dW1r[((size_t)tap * 64 + c2) * L + ci];
-    }
 }
 
 // ------------------------------------------------------------------------------------------- mixture likelihood / encoding
@@ -701,35 +592,6 @@ int io_sample_launch(const float* mu, const float* ls, const float* noise, float
 int io_w1_pack_launch(const float* W1, float* W1r, float* Wxy, int L, hipStream_t st) {
     hipLaunchKernelGGL(io_w1_pack_kernel, IO_GRID(9 * 64 * (L + 2)), 0, st, W1, W1r, Wxy, L);
     OCRL_CHECK_LAUNCH("io_w1_pack");
-    return 0;
-}
-int io_p1_launch(const float* Wxy, const float* b1, float* P1, int S, hipStream_t st) {
-    hipLaunchKernelGGL(io_p1_kernel, IO_GRID((long long)S * S * 64), 0, st, Wxy, b1, P1, S);
-    OCRL_CHECK_LAUNCH("io_p1");
-    return 0;
-}
-int io_class_sum_launch(const float* in, float* out, long long BK, int forward, hipStream_t st) {
-    hipLaunchKernelGGL(io_class_sum_kernel, IO_GRID(BK * 9 * 64), 0, st, in, out, BK, forward);
-    OCRL_CHECK_LAUNCH("io_class_sum");
-    return 0;
-}
-int io_layer1_launch(const float* P1, const float* T, float* c1, long long BK, int S, hipStream_t st) {
-    hipLaunchKernelGGL(io_layer1_kernel, IO_GRID(BK * S * S * 16), 0, st, P1, T, c1, BK, S);
-    OCRL_CHECK_LAUNCH("io_layer1");
-    return 0;
-}
-// dT [BK][9][64] is written (not accumulated); ws: BK*S*3*64 floats of scratch
-int io_layer1_bwd_launch(const float* g, float* dT, long long BK, int S, float* ws, size_t ws_floats, hipStream_t st) {
-    OCRL_REQUIRE(S >= 3 && ws && ws_floats >= (size_t)BK * S * 3 * 64, "io_layer1_bwd: S < 3 or scratch too small");
-    hipLaunchKernelGGL(io_layer1_bwd_kernel, dim3((unsigned)(BK * S)), dim3(256), 0, st, g, ws, S);
-    const long long n = BK * 9 * 64;
-    hipLaunchKernelGGL(io_layer1_reduce_kernel, IO_GRID(n), 0, st, ws, dT, n, S);
-    OCRL_CHECK_LAUNCH("io_layer1_bwd");
-    return 0;
-}
-int io_w1_grad_launch(const float* dW1r, const float* G, float* dW1, float* db1, int S, int L, hipStream_t st) {
-    hipLaunchKernelGGL(io_w1_grad_kernel, dim3(9), dim3(256), 0, st, dW1r, G, dW1, db1, S, L);
-    OCRL_CHECK_LAUNCH("io_w1_grad");
     return 0;
 }
 // st1 [B*K][4] is written when enc is given; part[0..1] += (log-likelihood, squared error) totals; ws: (B*S*S/256) * 66 floats of scratch

@@ -63,7 +63,7 @@ void IodineModel::layout_workspace(bool commit) {
         if (sk > need) need = sk;
         const size_t cs = (size_t)N * 64 * 4 + (1 << 20);
         if (cs > need) need = cs;
-        const size_t rp = BK * (size_t)S * 3 * 64;        // row partials of the first decoder layer's backward
+        const size_t rp = bcast_l1_bwd_ws_floats((long long)BK, S, 3);        // row partials of the first decoder layer's backward
         if (rp > need) need = rp;
         scratch_floats_ = need + (1 << 20);
     }
@@ -73,7 +73,7 @@ void IodineModel::layout_workspace(bool commit) {
     for (int i = 0; i < I; ++i) {
         mu_[i] = carve(nullptr, BK * L); ls_[i] = carve(nullptr, BK * L); eps_[i] = carve(nullptr, BK * L);
         slots_[i] = carve(i == I - 1 ? "slots" : nullptr, BK * L);
-        for (int l = 0; l < 4; ++l) c_[l][i] = carve(nullptr, BKN * 64);
+        for (int l = 0; l < 4; ++l) c_[l][i] = carve(i == I - 1 && l == 0 ? "dec_c1" : nullptr, BKN * 64);
         out4_[i] = carve(i == I - 1 ? "out4" : nullptr, BKN * 4);
     }
     const int R = I > 1 ? I - 1 : 0;
@@ -138,8 +138,8 @@ int IodineModel::pack_weights(hipStream_t st) {
 int IodineModel::decoder_fwd(int i, hipStream_t st) {
     const long long BK = (long long)B_ * K;
     RC(lin_fwd(slots_[i], L, W1r_, nullptr, M_, 576, BK, 576, L, 0, nullptr, 0, st));          // M[bk][tap][co] = W_tap s
-    RC(io_class_sum_launch(M_, T_, BK, 1, st));
-    RC(io_layer1_launch(P1_, T_, c_[0][i], BK, S, st));
+    RC(bcast_l1_class_sum_launch(M_, T_, BK, 3, 1, st));
+    RC(bcast_l1_fwd_launch(P1_, T_, nullptr, c_[0][i], BK, S, 3, BCAST_L1_ELU, st));       // the bias is folded into P1
     for (int l = 0; l < 3; ++l) {
         ConvArgs a;
         a.X = c_[l][i]; a.Wp = pk_[l]; a.Y = c_[l + 1][i]; a.B = (int)BK; a.H = S; a.W = S; a.relu = 2;
@@ -178,8 +178,8 @@ int IodineModel::decoder_bwd(int i, const float* dout4, bool weights, hipStream_
         float* t = cur; cur = nxt; nxt = t;
     }
     // first layer through the broadcast shortcut (cur = d pre-activation of layer 0)
-    RC(io_layer1_bwd_launch(cur, T_, BK, S, scratch_, scratch_floats_, st));
-    RC(io_class_sum_launch(T_, M_, BK, 0, st));
+    RC(bcast_l1_bwd_launch(cur, T_, BK, S, 3, scratch_, scratch_floats_, st));
+    RC(bcast_l1_class_sum_launch(T_, M_, BK, 3, 0, st));
     RC(lin_bwd_x(M_, 576, W1r_, dslots_, L, BK, 576, L, nullptr, 0, nullptr, 0, st));
     if (weights) {
         RC(lin_bwd_w(M_, 576, slots_[i], L, dW1r_, nullptr, BK, 576, L, 1.f, scratch_, scratch_floats_, st, Drop(), Xf(), 1));

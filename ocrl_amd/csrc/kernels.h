@@ -489,14 +489,19 @@ struct AttnArgs {
 };
 int attn_launch(const AttnArgs& a, int mode, hipStream_t st);
 
+// ------------------------------------------------------------------ bcast_l1.hip (first layer of both broadcast decoders: ks = 5 SLATE, 3 IODINE)
+enum { BCAST_L1_RELU = 0, BCAST_L1_ELU = 1 };
+int bcast_l1_class_sum_launch(const float* in, float* out, long long BK, int ks, int forward, hipStream_t st);
+int bcast_l1_fwd_launch(const float* P1, const float* T, const float* bias, float* c1, long long BK, int S, int ks, int act, hipStream_t st);
+size_t bcast_l1_bwd_ws_floats(long long BK, int S, int ks);
+int bcast_l1_bwd_launch(const float* g, float* dT, long long BK, int S, int ks, float* ws, size_t ws_floats, hipStream_t st);
+int bc_posconv_launch(const float* Wc, float* P1, int S, hipStream_t st);
+int bc_posconv_bwd_launch(const float* G, float* dWc, int S, hipStream_t st);
+int io_p1_launch(const float* Wxy, const float* b1, float* P1, int S, hipStream_t st);
+int io_w1_grad_launch(const float* dW1r, const float* G, float* dW1, float* db1, int S, int L, hipStream_t st);
+
 // ------------------------------------------------------------------ bcdec.hip (Slot-Attention broadcast decoder)
 int bc_compose_launch(const float* W1, const float* Wpos, const float* bpos, float* Wc, float* W1r, int D, hipStream_t st);
-int bc_posconv_launch(const float* Wc, float* P1, int S, hipStream_t st);
-int bc_class_sum_launch(const float* in, float* out, int BK, int forward, hipStream_t st);
-int bc_layer1_launch(const float* P1, const float* Tc, const float* b1, float* c1, int BK, int S, hipStream_t st);
-size_t bc_layer1_bwd_ws_floats(int BK, int S);
-int bc_layer1_bwd_launch(const float* g, float* dT, int BK, int S, float* ws, size_t ws_floats, hipStream_t st);
-int bc_posconv_bwd_launch(const float* G, float* dWc, int S, hipStream_t st);
 int bc_compose_bwd_launch(const float* W1, const float* Wpos, const float* bpos, const float* dWc, const float* dW1r, float* dW1,
                           float* dWpos, float* dbpos, int D, hipStream_t st);
 int bc_c4_pack_launch(const float* W, float* Wk, float* Wb, int co_n, hipStream_t st);
@@ -511,11 +516,6 @@ int bc_mix_launch(const float* out4, const float* obs, float* recon, float* dout
 int io_sample_launch(const float* mu, const float* ls, const float* noise, float* eps_out, float* slots, float* kl_out, long long n,
                      unsigned long long seed, unsigned site, float* ws, size_t ws_floats, hipStream_t st);
 int io_w1_pack_launch(const float* W1, float* W1r, float* Wxy, int L, hipStream_t st);
-int io_p1_launch(const float* Wxy, const float* b1, float* P1, int S, hipStream_t st);
-int io_class_sum_launch(const float* in, float* out, long long BK, int forward, hipStream_t st);
-int io_layer1_launch(const float* P1, const float* T, float* c1, long long BK, int S, hipStream_t st);
-int io_layer1_bwd_launch(const float* g, float* dT, long long BK, int S, float* ws, size_t ws_floats, hipStream_t st);
-int io_w1_grad_launch(const float* dW1r, const float* G, float* dW1, float* db1, int S, int L, hipStream_t st);
 int io_elbo_launch(const float* out4, const float* obs, int B, int K, int S, float sigma, float* enc, float* st1, float* dout4, float* part,
                    float* masks_out, float* recon_out, float* rmasked_out, float* ws, size_t ws_floats, hipStream_t st);
 int io_enc_norm_launch(float* enc, const float* st1, float* st2, long long BK, int N, float* ws, size_t ws_floats, hipStream_t st);

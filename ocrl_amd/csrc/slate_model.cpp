@@ -149,7 +149,7 @@ void SlateModel::layout_workspace(bool commit) {
         if (sk > need) need = sk;
         size_t cs = (size_t)N * C * 8 + (size_t)T * d * 8 + (1 << 20);   // column-sum partials (pos map / pe)
         if (cs > need) need = cs;
-        if (cfg.use_bcdec && bc_layer1_bwd_ws_floats((int)(B * K), S) > need) need = bc_layer1_bwd_ws_floats((int)(B * K), S);
+        if (cfg.use_bcdec && bcast_l1_bwd_ws_floats((long long)BK, S, 5) > need) need = bcast_l1_bwd_ws_floats((long long)BK, S, 5);
         const size_t ca = cross_attn_bwd_ws_floats((int)B, T, K, d, NH), eb = embed_bwd_ws_floats((long long)B * T, V, d);
         if (ca > need) need = ca;
         if (eb > need) need = eb;
@@ -1207,8 +1207,8 @@ int SlateModel::fwd_bcdec(const Lane& L) {
     const int B = last_.B, BK = B * K;
     RC(bc_posconv_launch(bc_Wc_, bc_P1_, S, L));
     RC(lin_fwd(slots_, D, bc_W1r_, nullptr, bc_M_, 1600, BK, 1600, D, 0, nullptr, 0, 0.f, 0, L));       // M[bk][tap][co] = W_tap s
-    RC(bc_class_sum_launch(bc_M_, bc_T_, BK, 1, L));
-    RC(bc_layer1_launch(bc_P1_, bc_T_, P(w_.bc[0].b), bc_c1_, BK, S, L));
+    RC(bcast_l1_class_sum_launch(bc_M_, bc_T_, BK, 5, 1, L));
+    RC(bcast_l1_fwd_launch(bc_P1_, bc_T_, P(w_.bc[0].b), bc_c1_, BK, S, 5, BCAST_L1_RELU, L));
     RC(conv_layer_fwd(bc_c1_, bc_pk_[0], P(w_.bc[1].b), bc_c2_, BK, S, S, 5, 64, 1, nullptr, nullptr, L));
     RC(conv_layer_fwd(bc_c2_, bc_pk_[1], P(w_.bc[2].b), bc_c3_, BK, S, S, 5, 64, 1, nullptr, nullptr, L));
     RC(bc_c4_fwd_launch(bc_c3_, bc_Wk4_, P(w_.bc[3].b), bc_out4_, BK, S, L));
@@ -1230,9 +1230,9 @@ int SlateModel::bwd_bcdec(const Lane& L) {
     RC(conv_layer_wgrad(bc_c1_, bc_gB_, G(w_.bc[1].w), G(w_.bc[1].b), BK, S, S, 5, 64, 64, L));
     RC(conv_layer_fwd(bc_gB_, bc_pkb_[0], nullptr, bc_gA_, BK, S, S, 5, 64, 0, nullptr, bc_c1_, L));               // gA = d c1 (pre-relu)
     // first layer through the shortcut
-    RC(bc_layer1_bwd_launch(bc_gA_, bc_dT_, BK, S, L.scratch, L.scratch_floats, L));
+    RC(bcast_l1_bwd_launch(bc_gA_, bc_dT_, BK, S, 5, L.scratch, L.scratch_floats, L));
     RC(colsum_launch(bc_dT_, 64, G(w_.bc[0].b), (long long)BK * 25, 64, 0, 1.f, L.scratch, L.scratch_floats, L));
-    RC(bc_class_sum_launch(bc_dT_, bc_dM_, BK, 0, L));
+    RC(bcast_l1_class_sum_launch(bc_dT_, bc_dM_, BK, 5, 0, L));
     RC(lin_bwd_x(bc_dM_, 1600, bc_W1r_, gslots_, D, BK, 1600, D, nullptr, 0, nullptr, 0, L));                      // d slots
     RC(lin_bwd_w(bc_dM_, 1600, slots_, D, bc_dW1r_, nullptr, BK, 1600, D, 1.f, L));
     RC(colsum_launch(bc_gA_, (long long)N * 64, bc_G1_, BK, N * 64, 0, 1.f, L.scratch, L.scratch_floats, L));        // sum over (image, slot)
