@@ -231,6 +231,53 @@ int ocrl_attention_bwd(const float* q, const float* k, const float* v, const flo
                        float* dq, float* dk, float* dv, float* delta, int B, int T, int d, int h, int ld,
                        float p, unsigned long long seed, unsigned site, void* stream);
 
+/* ---- Cross attention of a decoder block to the K projected slots (MultiHeadAttention.forward, ocrs/common/transformer.py:23-50, as
+ * TransformerDecoderBlock.forward :181-185 calls it with k = v = the slot memory), in the two forms the decoder runs.
+ *
+ * Folded form (csrc/xattn.hip): y = resid + dropout_o(softmax_dropout_p(x Wq^T (mem Wk^T)^T / sqrt(d/h)) (mem Wv^T) Wo^T) with the two
+ * projections around the attention folded into per-image operands.  ocrl_xattn_plan reports the form a shape runs, host only:
+ * out = {supported (0/1), KP, NC, NM, dynamic LDS bytes of the forward / backward kernel}.  Supported: 1 <= K <= 16, d in {64, 128, 192,
+ * 256}, h | d, (d/h) % 4 == 0 and NC = h * KP in {16, 32, 64}, where KP (slots per head after padding) is 8 for K <= 8 and h > 1, else
+ * 16; NM = d / 16.  That is h in {1, 2, 4, 8} at K <= 8 and h in {1, 2, 4} at K > 8; an unsupported shape gives out = {0, 0, 0, 0, 0} (the
+ * model then runs the plain form), and _fwd / _bwd refuse it with a message and launch nothing.
+ * Column layout of the padded operands: col = head * KP + slot.
+ *   ocrl_xattn_fwd: the fold (ck, cv [B,K,d] = mem Wk^T, mem Wv^T; Ab [B,NC,d], AbT [B,d,NC], Vo [B,NC,d], VoT [B,d,NC]), then the
+ *     attention: y [B,T,d] and P [B,h,T,K] (probabilities before dropout).  ck, cv, y, P are written in full and need no initialisation.
+ *     Of Ab / AbT / Vo / VoT only the columns of real slots are written: the CALLER ZEROES these four buffers once, and the padding columns
+ *     (slot >= K of every head) stay zero through every call.
+ *   ocrl_xattn_bwd (after _fwd, same descriptor): from gd [B,T,d], the gradient wrt the attention branch's output after the output
+ *     dropout's backward (gd = dy * keep_o / (1 - p)), it writes Pd [B*T,NC] = P * keep_p / (1 - p) and dS [B*T,NC] (score gradients;
+ *     padding columns of both are written as zero), dx [B,T,d] (gradient wrt x through the attention branch only), the per-image sums
+ *     dVo, dAb [B,NC,d], then dck, dcv [B,K,d], the per-image partials pq, po [B,d,d] and dWq, dWo [d,d] (the partials summed over the
+ *     images in a fixed order).  Every one of them is written, none is added to.  cs_ws: scratch of cs_ws_floats >= d * d floats; B <= 64.
+ * Dropout index contract (seed as in ocrl_slate_forward): the keep decision of probability (b, head, t, slot) is element
+ * ((b*h + head)*T + t)*K + slot of site_p's stream (K % 4 != 0 included: rows then start off the group of four); that of output element
+ * (b, t, o) is element (b*T + t)*d + o of site_o's stream.  Results are bitwise reproducible, and an image's results do not depend on B. */
+typedef struct ocrl_xattn_desc {
+    const float* x; const float* resid; const float* mem;            /* [B,T,d] LN output, [B,T,d] residual stream, [B,K,d] projected slots */
+    const float* Wq; const float* Wk; const float* Wv; const float* Wo;      /* [d,d] (out, in) */
+    float* ck; float* cv; float* Ab; float* AbT; float* Vo; float* VoT; float* y; float* P;
+    const float* gd;
+    float* Pd; float* dS; float* dx; float* dAb; float* dVo; float* dck; float* dcv; float* dWq; float* dWo;
+    float* pq; float* po; float* cs_ws; size_t cs_ws_floats;
+    int B, T, K, d, h;
+    float p; unsigned long long seed; unsigned site_p, site_o;
+} ocrl_xattn_desc;
+size_t ocrl_xattn_desc_size(void);
+int ocrl_xattn_plan(int K, int d, int h, int out[5]);
+int ocrl_xattn_fwd(const ocrl_xattn_desc* d, void* stream);
+int ocrl_xattn_bwd(const ocrl_xattn_desc* d, void* stream);
+/* Plain form (csrc/elementwise.hip), the attention core alone: Q [B,T,d] (projected, unscaled), Km, Vm [B,K,d], heads side by side;
+ * O [B,T,d] = dropout(softmax(Q Km^T / sqrt(d/h))) Vm and P [B,h,T,K] (before dropout) are written.  1 <= K <= 16 (K <= 8 and K > 8 run
+ * different instantiations), (d/h) % 4 == 0, d/h <= 64.  Dropout as site_p above.  _bwd writes dQ [B,T,d], dKm, dVm [B,K,d] (none is
+ * added to); ws: ocrl_cross_attn_bwd_ws_floats floats (one partial per (image, head, block of 256 queries), summed in a fixed order). */
+int ocrl_cross_attn_fwd(const float* Q, const float* Km, const float* Vm, float* O, float* P, int B, int T, int K, int d, int h, float p,
+                        unsigned long long seed, unsigned site, void* stream);
+size_t ocrl_cross_attn_bwd_ws_floats(int B, int T, int K, int d, int h);
+int ocrl_cross_attn_bwd(const float* dO, const float* Q, const float* Km, const float* Vm, const float* P, float* dQ, float* dKm, float* dVm,
+                        int B, int T, int K, int d, int h, float p, unsigned long long seed, unsigned site, float* ws, size_t ws_floats,
+                        void* stream);
+
 /* ---- optional HIP-event timing of kernel families on the launch stream (bench.py's roofline line).
  * tag bits: 0 conv5x5/64ch fwd+bwd-data, 1 other convs, 2 conv weight-grad, 3 gemm, 4 slot-attn fwd, 5 slot-attn bwd,
  * 6 self-attention fwd, 7 self-attention bwd.

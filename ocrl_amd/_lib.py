@@ -50,6 +50,14 @@ class ConvWgradDesc(ctypes.Structure):
                [(n, c_int) for n in ("B", "H", "W", "cin", "cin_pad", "ks", "accumulate")]
 
 
+class XattnDesc(ctypes.Structure):
+    """mirror of ocrl_xattn_desc (include/ocrl_hip.h)"""
+    _fields_ = [(n, c_void_p) for n in ("x", "resid", "mem", "Wq", "Wk", "Wv", "Wo", "ck", "cv", "Ab", "AbT", "Vo", "VoT", "y", "P", "gd",
+                                        "Pd", "dS", "dx", "dAb", "dVo", "dck", "dcv", "dWq", "dWo", "pq", "po", "cs_ws")] + \
+               [("cs_ws_floats", c_size_t)] + [(n, c_int) for n in ("B", "T", "K", "d", "h")] + \
+               [("p", c_float), ("seed", c_ulonglong), ("site_p", c_uint), ("site_o", c_uint)]
+
+
 class AcnetDesc(ctypes.Structure):
     """mirror of ocrl_acnet_desc (include/ocrl_hip.h); make one with acnet_desc()"""
     _fields_ = [("B", c_int), ("F", c_int), ("A", c_int), ("n", c_int * 3), ("dims", (c_int * 8) * 3), ("acts", (c_int * 8) * 3)]
@@ -186,6 +194,16 @@ def lib():
     L.ocrl_sa_input_bwd.argtypes = [p] * 16 + [c_longlong, c_int, p, c_size_t, p]
     L.ocrl_attention_fwd.argtypes = [p, p, p, p, p, c_int, c_int, c_int, c_int, c_int, c_float, c_ulonglong, c_uint, p]
     L.ocrl_attention_bwd.argtypes = [p, p, p, p, p, p, p, p, p, p, c_int, c_int, c_int, c_int, c_int, c_float, c_ulonglong, c_uint, p]
+    L.ocrl_xattn_desc_size.restype = c_size_t
+    if L.ocrl_xattn_desc_size() != ctypes.sizeof(XattnDesc):
+        raise RuntimeError(f"libocrl_hip.so: ocrl_xattn_desc is {L.ocrl_xattn_desc_size()} bytes, this binding's XattnDesc {ctypes.sizeof(XattnDesc)}")
+    L.ocrl_xattn_plan.argtypes = [c_int, c_int, c_int, POINTER(c_int * 5)]
+    L.ocrl_xattn_fwd.argtypes = [POINTER(XattnDesc), p]
+    L.ocrl_xattn_bwd.argtypes = [POINTER(XattnDesc), p]
+    L.ocrl_cross_attn_fwd.argtypes = [p, p, p, p, p, c_int, c_int, c_int, c_int, c_int, c_float, c_ulonglong, c_uint, p]
+    L.ocrl_cross_attn_bwd_ws_floats.argtypes = [c_int] * 5
+    L.ocrl_cross_attn_bwd_ws_floats.restype = c_size_t
+    L.ocrl_cross_attn_bwd.argtypes = [p] * 8 + [c_int] * 5 + [c_float, c_ulonglong, c_uint, p, c_size_t, p]
     L.ocrl_obs_u8_to_f32.argtypes = [p, p, c_int, c_int, c_int, c_int, p]
     L.ocrl_prof_enable.argtypes = [c_uint]
     L.ocrl_prof_collect.argtypes = [POINTER(ctypes.c_double * 8), POINTER(c_longlong * 8), c_int]

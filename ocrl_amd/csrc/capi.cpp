@@ -355,6 +355,71 @@ int ocrl_attention_bwd(const float* q, const float* k, const float* v, const flo
     return attn_launch(a, 1, ST(stream));
 }
 
+// ---- cross attention to the slots: the folded form (xattn.hip) and the plain kernels (elementwise.hip), as the decoder runs them
+int ocrl_xattn_plan(int K, int d, int h, int out[5]) {
+    if (!out) { ocrl_set_error("ocrl_xattn_plan: null argument"); return 1; }
+    XaPlan p;
+    if (!xattn_plan(K, d, h, &p)) ocrl_set_error("ocrl_xattn_plan: no folded form for K %d, d %d, heads %d", K, d, h);
+    out[0] = p.supported ? 1 : 0; out[1] = p.KP; out[2] = p.NC; out[3] = p.NM; out[4] = (int)p.lds;
+    return 0;
+}
+size_t ocrl_xattn_desc_size(void) { return sizeof(ocrl_xattn_desc); }
+static XaHost xattn_host(const ocrl_xattn_desc& d) {
+    XaHost hx;
+    hx.x = d.x; hx.P = d.P; hx.Ab = d.Ab; hx.AbT = d.AbT; hx.Vo = d.Vo; hx.VoT = d.VoT;
+    hx.B = d.B; hx.T = d.T; hx.K = d.K; hx.d = d.d; hx.h = d.h; hx.p = d.p; hx.seed = d.seed; hx.site_p = d.site_p; hx.site_o = d.site_o;
+    return hx;
+}
+int ocrl_xattn_fwd(const ocrl_xattn_desc* d, void* stream) {
+    if (!d) { ocrl_set_error("ocrl_xattn_fwd: null descriptor"); return 1; }
+    if (!xattn_supported(d->K, d->d, d->h)) { ocrl_set_error("ocrl_xattn_fwd: no folded form for K %d, d %d, heads %d", d->K, d->d, d->h); return 1; }
+    if (d->B < 1 || d->T < 1 || !d->x || !d->resid || !d->mem || !d->Wq || !d->Wk || !d->Wv || !d->Wo || !d->ck || !d->cv || !d->Ab || !d->AbT ||
+        !d->Vo || !d->VoT || !d->y || !d->P) {
+        ocrl_set_error("ocrl_xattn_fwd: null buffer or empty shape");
+        return 1;
+    }
+    XaFoldHost f;
+    f.mem = d->mem; f.B = d->B; f.K = d->K; f.d = d->d; f.h = d->h; f.nblk = 1;
+    f.Wq[0] = d->Wq; f.Wk[0] = d->Wk; f.Wv[0] = d->Wv; f.Wo[0] = d->Wo;
+    f.ck[0] = d->ck; f.cv[0] = d->cv; f.Ab[0] = d->Ab; f.AbT[0] = d->AbT; f.Vo[0] = d->Vo; f.VoT[0] = d->VoT;
+    if (xattn_fold_fwd_launch(f, ST(stream))) return 1;
+    XaHost hx = xattn_host(*d);
+    hx.resid = d->resid; hx.y = d->y;
+    return xattn_launch(hx, 0, ST(stream));
+}
+int ocrl_xattn_bwd(const ocrl_xattn_desc* d, void* stream) {
+    if (!d) { ocrl_set_error("ocrl_xattn_bwd: null descriptor"); return 1; }
+    if (!xattn_supported(d->K, d->d, d->h)) { ocrl_set_error("ocrl_xattn_bwd: no folded form for K %d, d %d, heads %d", d->K, d->d, d->h); return 1; }
+    if (d->B < 1 || d->T < 1 || !d->x || !d->Wq || !d->Wo || !d->ck || !d->cv || !d->Ab || !d->AbT || !d->Vo || !d->VoT || !d->P || !d->gd || !d->Pd ||
+        !d->dS || !d->dx || !d->dAb || !d->dVo || !d->dck || !d->dcv || !d->dWq || !d->dWo || !d->pq || !d->po || !d->cs_ws) {
+        ocrl_set_error("ocrl_xattn_bwd: null buffer or empty shape");
+        return 1;
+    }
+    if (d->cs_ws_floats < (size_t)d->d * d->d || d->B > 64) { ocrl_set_error("ocrl_xattn_bwd: needs B <= 64 and a column-sum workspace of d * d floats"); return 1; }
+    XaHost hx = xattn_host(*d);
+    hx.y = d->dx; hx.gd = d->gd; hx.Pd = d->Pd; hx.dS = d->dS;
+    if (xattn_launch(hx, 1, ST(stream))) return 1;
+    XaFoldBwdHost f;
+    f.Pd = d->Pd; f.dS = d->dS; f.gd = d->gd; f.x = d->x; f.Wq = d->Wq; f.Wo = d->Wo; f.ck = d->ck; f.cv = d->cv;
+    f.dVo = d->dVo; f.dAb = d->dAb; f.dck = d->dck; f.dcv = d->dcv; f.pq = d->pq; f.po = d->po; f.dWq = d->dWq; f.dWo = d->dWo;
+    f.ws = d->cs_ws; f.ws_floats = d->cs_ws_floats; f.B = d->B; f.T = d->T; f.K = d->K; f.d = d->d; f.h = d->h;
+    return xattn_fold_bwd_launch(f, ST(stream));
+}
+int ocrl_cross_attn_fwd(const float* Q, const float* Km, const float* Vm, float* O, float* P, int B, int T, int K, int d, int h, float p,
+                        unsigned long long seed, unsigned site, void* stream) {
+    if (!Q || !Km || !Vm || !O || !P || B < 1 || T < 1 || h < 1) { ocrl_set_error("ocrl_cross_attn_fwd: null buffer or empty shape"); return 1; }
+    return cross_attn_fwd_launch(Q, Km, Vm, O, P, B, T, K, d, h, p, seed, site, ST(stream));
+}
+size_t ocrl_cross_attn_bwd_ws_floats(int B, int T, int K, int d, int h) {
+    if (B < 1 || T < 1 || K < 1 || d < 1 || h < 1 || d % h) { ocrl_set_error("ocrl_cross_attn_bwd_ws_floats: invalid shape"); return 0; }
+    return cross_attn_bwd_ws_floats(B, T, K, d, h);
+}
+int ocrl_cross_attn_bwd(const float* dO, const float* Q, const float* Km, const float* Vm, const float* P, float* dQ, float* dKm, float* dVm, int B,
+                        int T, int K, int d, int h, float p, unsigned long long seed, unsigned site, float* ws, size_t ws_floats, void* stream) {
+    if (!dO || !Q || !Km || !Vm || !P || !dQ || !dKm || !dVm || B < 1 || T < 1 || h < 1) { ocrl_set_error("ocrl_cross_attn_bwd: null buffer or empty shape"); return 1; }
+    return cross_attn_bwd_launch(dO, Q, Km, Vm, P, dQ, dKm, dVm, B, T, K, d, h, p, seed, site, ws, ws_floats, ST(stream));
+}
+
 
 // ---------------------------------------------------------------- IODINE
 int ocrl_iodine_create(const ocrl_iodine_config* c, ocrl_iodine** out) {

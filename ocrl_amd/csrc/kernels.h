@@ -353,6 +353,11 @@ int unpack5_launch(const float* dWp, float* dW, int C, int ldc, hipStream_t st);
 int pad_cols_launch(const float* in, int ldi, float* out, int ldo, long long R, int C, int Cout, hipStream_t st);
 
 // ------------------------------------------------------------------ xattn.hip: cross attention to the slots, folded (transformer.py:23-50,181-185)
+// The folded form's shape rule (host only; the launchers below call it, so what it reports is what runs): KP slots per head after
+// padding (8 or 16), NC = h * KP columns, NM = d / 16, lds = dynamic LDS bytes of xattn_launch's kernels.  Returns `supported`;
+// an unsupported shape leaves every field zero.
+struct XaPlan { bool supported = false; int KP = 0, NC = 0, NM = 0; size_t lds = 0; };
+bool xattn_plan(int K, int d, int h, XaPlan* out);
 bool xattn_supported(int K, int d, int h);
 int xattn_kp(int K, int h);                       // slots per head after padding (8 or 16); columns NC = h * KP
 struct XaFoldHost {                               // per-image operands of all decoder blocks from the projected slots, one launch
@@ -375,6 +380,19 @@ struct XaHost {
     float p = 0.f; unsigned long long seed = 0; unsigned site_p = 0, site_o = 0;
 };
 int xattn_launch(const XaHost& h, int backward, hipStream_t st);
+struct XaFoldBwdHost {                            // backward of the fold, after xattn_launch(.., 1) of the same block
+    const float *Pd = nullptr, *dS = nullptr;     // [B*T,NC] what xattn_launch(.., 1) wrote
+    const float *gd = nullptr, *x = nullptr;      // [B,T,d] gradient wrt out; the attention input
+    const float *Wq = nullptr, *Wo = nullptr;     // [d,d] (out, in)
+    const float *ck = nullptr, *cv = nullptr;     // [B,K,d] from the fold
+    float *dVo = nullptr, *dAb = nullptr;         // [B,NC,d] per-image sums over the tokens (written)
+    float *dck = nullptr, *dcv = nullptr;         // [B,K,d] (written)
+    float *pq = nullptr, *po = nullptr;           // [B,d,d] per-image partials of d Wq / d Wo (written)
+    float *dWq = nullptr, *dWo = nullptr;         // [d,d] (written: the partials summed over the images in a fixed order)
+    float* ws = nullptr; size_t ws_floats = 0;    // column-sum scratch (colsum_launch: d*d floats serve B <= 64)
+    int B = 0, T = 0, K = 0, d = 0, h = 0;
+};
+int xattn_fold_bwd_launch(const XaFoldBwdHost& f, hipStream_t st);
 
 
 // ------------------------------------------------------------------ slot_attn.hip

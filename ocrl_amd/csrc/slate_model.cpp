@@ -815,7 +815,6 @@ int SlateModel::bwd_decoder(const Lane& L) {
     const int B = last_.B;
     const long long BT = (long long)B * T, BK = (long long)B * K;
     const float p = pdrop_;
-    const float scale = 1.0f / sqrtf((float)DH);
     // The weight-gradient products go to their own lane W (OCRL_DW_SIDE, dw_lane): after(W, L, ..) makes it wait for everything the main
     // stream has enqueued so far.  Without OCRL_DW_SIDE W is the main lane and the ordering calls do nothing.
     const Lane W = dw_lane(L);
@@ -860,51 +859,16 @@ int SlateModel::bwd_decoder(const Lane& L) {
             // folded backward (xattn.hip): d probabilities, soft-max backward and d LN(x) in one launch; the per-image sums
             // d Vo_b = Pd^T d out and d A_b = dS^T LN(x) are two batched products; a per-image kernel takes them back to the projection
             // weights (partials summed over the images in a fixed order) and to d ck / d cv
-            const int NC = NH * xattn_kp(K, NH);
             XaHost hx = xattn_args(b);
             hx.y = gt1_; hx.gd = gd_co; hx.Pd = q.xaPd; hx.dS = q.xaDs;
             RC(xattn_launch(hx, 1, L));                                                                                  // gt1 = d ln2
             // everything below feeds weight gradients and d mem only: it runs on the weight-gradient stream lane (W), in order
             RC(after(W, L, ring_event()));
-            {
-                const int KP = xattn_kp(K, NH), dh = DH;
-                const float* Wq = P(bw.cq);
-                const float* Wo = P(bw.co);
-                GemmArgs ga;      // per-image sums over the tokens: d Vo_b = Pd^T d out,  d A_b = dS^T LN(x)      [NC, d] each
-                ga.M = NC; ga.N = d; ga.K = T; ga.lda = NC; ga.ldb = d; ga.ldc = d; ga.akc = 0; ga.bkc = 0; ga.batch = B;
-                ga.sA = (long long)T * NC; ga.sB = (long long)T * d; ga.sC = (long long)NC * d;
-                ga.A = q.xaPd; ga.B = gd_co; ga.C = xa_dVo_;
-                RC(gemm_launch(ga, W));
-                ga.A = q.xaDs; ga.B = k.ln2; ga.C = xa_dAb_;
-                RC(gemm_launch(ga, W));
-                // back through the fold, batched over (image, head):
-                GemmArgs gb;      // d ck[k, h dh + j] = scale sum_e dA_b[(h,k), e] Wq[h dh + j, e]
-                gb.M = K; gb.N = dh; gb.K = d; gb.akc = 1; gb.bkc = 1; gb.lda = d; gb.ldb = d; gb.ldc = d; gb.batch = B * NH; gb.batch_inner = NH; gb.alpha = scale;
-                gb.A = xa_dAb_; gb.sA = (long long)NC * d; gb.sAi = (long long)KP * d;
-                gb.B = Wq; gb.sB = 0; gb.sBi = (long long)dh * d;
-                gb.C = gck_; gb.sC = (long long)K * d; gb.sCi = dh;
-                RC(gemm_launch(gb, W));
-                GemmArgs gc;      // d cv[k, h dh + j] = sum_o dVo_b[(h,k), o] Wo[o, h dh + j]
-                gc.M = K; gc.N = dh; gc.K = d; gc.akc = 1; gc.bkc = 0; gc.lda = d; gc.ldb = d; gc.ldc = d; gc.batch = B * NH; gc.batch_inner = NH;
-                gc.A = xa_dVo_; gc.sA = (long long)NC * d; gc.sAi = (long long)KP * d;
-                gc.B = Wo; gc.sB = 0; gc.sBi = dh;
-                gc.C = gcv_; gc.sC = (long long)K * d; gc.sCi = dh;
-                RC(gemm_launch(gc, W));
-                GemmArgs gq;      // this image's d Wq[h dh + j, e] = scale sum_k ck[k, h dh + j] dA_b[(h,k), e]
-                gq.M = dh; gq.N = d; gq.K = K; gq.akc = 0; gq.bkc = 0; gq.lda = d; gq.ldb = d; gq.ldc = d; gq.batch = B * NH; gq.batch_inner = NH; gq.alpha = scale;
-                gq.A = k.ck; gq.sA = (long long)K * d; gq.sAi = dh;
-                gq.B = xa_dAb_; gq.sB = (long long)NC * d; gq.sBi = (long long)KP * d;
-                gq.C = xa_pq_; gq.sC = (long long)d * d; gq.sCi = (long long)dh * d;
-                RC(gemm_launch(gq, W));
-                GemmArgs go;      // this image's d Wo[o, h dh + j] = sum_k dVo_b[(h,k), o] cv[k, h dh + j]
-                go.M = d; go.N = dh; go.K = K; go.akc = 0; go.bkc = 0; go.lda = d; go.ldb = d; go.ldc = d; go.batch = B * NH; go.batch_inner = NH;
-                go.A = xa_dVo_; go.sA = (long long)NC * d; go.sAi = (long long)KP * d;
-                go.B = k.cv; go.sB = (long long)K * d; go.sBi = dh;
-                go.C = xa_po_; go.sC = (long long)d * d; go.sCi = dh;
-                RC(gemm_launch(go, W));
-                RC(colsum_launch(xa_pq_, (long long)d * d, G(bw.cq), B, d * d, 0, 1.f, W.scratch, W.scratch_floats, W));
-                RC(colsum_launch(xa_po_, (long long)d * d, G(bw.co), B, d * d, 0, 1.f, W.scratch, W.scratch_floats, W));
-            }
+            XaFoldBwdHost f;      // the per-image sums, back through the fold to d ck / d cv, and the images' d Wq / d Wo partials summed
+            f.Pd = q.xaPd; f.dS = q.xaDs; f.gd = gd_co; f.x = k.ln2; f.Wq = P(bw.cq); f.Wo = P(bw.co); f.ck = k.ck; f.cv = k.cv;
+            f.dVo = xa_dVo_; f.dAb = xa_dAb_; f.dck = gck_; f.dcv = gcv_; f.pq = xa_pq_; f.po = xa_po_; f.dWq = G(bw.cq); f.dWo = G(bw.co);
+            f.ws = W.scratch; f.ws_floats = W.scratch_floats; f.B = B; f.T = T; f.K = K; f.d = d; f.h = NH;
+            RC(xattn_fold_bwd_launch(f, W));
         } else {
         RC(lin_bwd_x(gd, d, P(bw.co), gt1_, d, BT, d, d, nullptr, 0, nullptr, 0, L));   // d cao
         RC(cross_attn_bwd_launch(gt1_, k.cq, k.ck, k.cv, k.cP, q.gt2, gck_, gcv_, B, T, K, d, NH, p, last_.seed, site + 2, L.scratch, L.scratch_floats, L));   // gt2 = d cq

@@ -8,7 +8,7 @@
 // output projection (2 x 2 d^2 FLOP per token become 2 x 2 d h K) -- it reads LN(x) and the residual once and writes the new
 // residual stream once.  The backward mirrors it: d Pd = d out Vo^T, soft-max backward per head, d LN(x) = d scores A^T in one
 // launch; the per-image sums d Vo_b = Pd^T d out and d A_b = d scores^T LN(x) are two batched products of the GEMM family, and four
-// more (batched over image and head, slate_model.cpp) take them back to Wq, Wo, ck, cv.  Only the summation order differs from the reference's three products.
+// more (batched over image and head, xattn_fold_bwd_launch below) take them back to Wq, Wo, ck, cv.  Only the summation order differs from the reference's three products.
 //
 // Column layout: col = head * KP + slot with the heads padded to KP = 8 (K <= 8) or 16 slots, so that on the matrix cores
 // (scores^T = A^T x^T: accumulator lane = (token li, column group g'), register r = column 16 tt + 4 g' + r) a head is two (KP = 8)
@@ -363,7 +363,7 @@ __global__ __launch_bounds__(XA_T, 3) void xattn_bwd_kernel(XaArgs a) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 pdp[r] = pr[tt][r] * keep[r];
-                dsp[r] = pr[tt][r] * (dpr[r] - dot);
+                dsp[r] = slot0 + r < K ? pr[tt][r] * (dpr[r] - dot) : 0.f;      // padding: +0, not 0 * (negative) = -0
                 ds[tt][r] = dsp[r];
             }
             if (live) {
@@ -400,17 +400,32 @@ __global__ __launch_bounds__(XA_T, 3) void xattn_bwd_kernel(XaArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------- launchers
-bool xattn_supported(int K, int d, int h) {
-    if (K < 1 || K > 16 || d % 16 || d > 256 || h < 1 || d % h || (d / h) % 4) return false;
-    const int KP = (K <= 8 && h > 1) ? 8 : 16, NC = h * KP;
-    return NC == 16 || NC == 32 || NC == 64;
+// The shape rule of the folded form, in one place (host only): xattn_supported, the fold and xattn_launch all read it, so what it
+// reports is what runs.  KP: slots per head after padding; NC = h * KP columns (one, two or four 16-column tiles); NM = d / 16 row
+// tiles (64-, 128-, 192- and 256-wide kernels are built); lds: dynamic LDS bytes of the forward / backward kernel (both operands,
+// row strides padded by 4).
+bool xattn_plan(int K, int d, int h, XaPlan* out) {
+    XaPlan p;
+    if (K >= 1 && K <= 16 && d >= 64 && d <= 256 && d % 64 == 0 && h >= 1 && d % h == 0 && (d / h) % 4 == 0) {
+        p.KP = (K <= 8 && h > 1) ? 8 : 16;
+        p.NC = h * p.KP;
+        p.NM = d / 16;
+        p.lds = (size_t)(p.NC * (d + 4) + d * (p.NC + 4)) * sizeof(float);
+        p.supported = p.NC == 16 || p.NC == 32 || p.NC == 64;
+    }
+    if (!p.supported) p = XaPlan();
+    if (out) *out = p;
+    return p.supported;
 }
+bool xattn_supported(int K, int d, int h) { return xattn_plan(K, d, h, nullptr); }
 int xattn_kp(int K, int h) { return (K <= 8 && h > 1) ? 8 : 16; }
 
 int xattn_fold_fwd_launch(const XaFoldHost& f, hipStream_t st) {
     OCRL_REQUIRE(xattn_supported(f.K, f.d, f.h) && f.nblk >= 1 && f.nblk <= 8, "xattn_fold: unsupported shape");
     XaFoldArgs a;
-    a.mem = f.mem; a.B = f.B; a.K = f.K; a.d = f.d; a.h = f.h; a.KP = xattn_kp(f.K, f.h); a.NC = f.h * a.KP;
+    XaPlan pl;
+    xattn_plan(f.K, f.d, f.h, &pl);
+    a.mem = f.mem; a.B = f.B; a.K = f.K; a.d = f.d; a.h = f.h; a.KP = pl.KP; a.NC = pl.NC;
     for (int i = 0; i < f.nblk; ++i) {
         a.Wq[i] = f.Wq[i]; a.Wk[i] = f.Wk[i]; a.Wv[i] = f.Wv[i]; a.Wo[i] = f.Wo[i];
         a.ck[i] = f.ck[i]; a.cv[i] = f.cv[i]; a.Ab[i] = f.Ab[i]; a.AbT[i] = f.AbT[i]; a.Vo[i] = f.Vo[i]; a.VoT[i] = f.VoT[i];
@@ -431,9 +446,7 @@ static int xa_splits(int B, int T) {
 }
 
 template <int NM, int NT, int KP>
-static int xattn_launch_t(XaArgs& a, int backward, hipStream_t st) {
-    constexpr int D = 16 * NM, NC = 16 * NT;
-    const size_t smem = (size_t)(NC * (D + 4) + D * (NC + 4)) * sizeof(float);
+static int xattn_launch_t(XaArgs& a, size_t smem, int backward, hipStream_t st) {
     static bool attr[2] = {false, false};
     if (!attr[backward]) {
         if (backward) OCRL_HIP(hipFuncSetAttribute((const void*)xattn_bwd_kernel<NM, NT, KP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
@@ -447,17 +460,20 @@ static int xattn_launch_t(XaArgs& a, int backward, hipStream_t st) {
     return 0;
 }
 template <int NM>
-static int xattn_launch_m(XaArgs& a, int KP, int NC, int backward, hipStream_t st) {
-    if (KP == 8 && NC == 16) return xattn_launch_t<NM, 1, 8>(a, backward, st);
-    if (KP == 8 && NC == 32) return xattn_launch_t<NM, 2, 8>(a, backward, st);
-    if (KP == 8 && NC == 64) return xattn_launch_t<NM, 4, 8>(a, backward, st);
-    if (KP == 16 && NC == 16) return xattn_launch_t<NM, 1, 16>(a, backward, st);
-    if (KP == 16 && NC == 32) return xattn_launch_t<NM, 2, 16>(a, backward, st);
-    if (KP == 16 && NC == 64) return xattn_launch_t<NM, 4, 16>(a, backward, st);
+static int xattn_launch_m(XaArgs& a, const XaPlan& pl, int backward, hipStream_t st) {
+    const int KP = pl.KP, NC = pl.NC;
+    if (KP == 8 && NC == 16) return xattn_launch_t<NM, 1, 8>(a, pl.lds, backward, st);
+    if (KP == 8 && NC == 32) return xattn_launch_t<NM, 2, 8>(a, pl.lds, backward, st);
+    if (KP == 8 && NC == 64) return xattn_launch_t<NM, 4, 8>(a, pl.lds, backward, st);
+    if (KP == 16 && NC == 16) return xattn_launch_t<NM, 1, 16>(a, pl.lds, backward, st);
+    if (KP == 16 && NC == 32) return xattn_launch_t<NM, 2, 16>(a, pl.lds, backward, st);
+    if (KP == 16 && NC == 64) return xattn_launch_t<NM, 4, 16>(a, pl.lds, backward, st);
     OCRL_REQUIRE(false, "xattn: unsupported column count %d", NC);
 }
 int xattn_launch(const XaHost& h, int backward, hipStream_t st) {
-    OCRL_REQUIRE(xattn_supported(h.K, h.d, h.h), "xattn: unsupported shape (K %d, d %d, heads %d)", h.K, h.d, h.h);
+    XaPlan pl;
+    OCRL_REQUIRE(xattn_plan(h.K, h.d, h.h, &pl), "xattn: unsupported shape (K %d, d %d, heads %d)", h.K, h.d, h.h);
+    OCRL_REQUIRE(h.B >= 1 && h.T >= 1, "xattn: empty batch or sequence");
     OCRL_REQUIRE(h.x && h.y && h.P && h.Ab && h.AbT && h.Vo && h.VoT, "xattn: missing buffers");
     OCRL_REQUIRE((long long)h.B * h.T * h.d < (1ll << 40), "xattn: too large");
     XaArgs a;
@@ -465,12 +481,58 @@ int xattn_launch(const XaHost& h, int backward, hipStream_t st) {
     a.B = h.B; a.T = h.T; a.K = h.K; a.d = h.d; a.h = h.h; a.p = h.p; a.seed = h.seed; a.site_p = h.site_p; a.site_o = h.site_o; a.NS = 1;
     if (backward) OCRL_REQUIRE(h.gd && h.Pd && h.dS, "xattn backward: missing buffers");
     else OCRL_REQUIRE(h.resid, "xattn forward: missing residual");
-    const int KP = xattn_kp(h.K, h.h), NC = h.h * KP;
-    switch (h.d / 16) {
-        case 4: return xattn_launch_m<4>(a, KP, NC, backward, st);
-        case 8: return xattn_launch_m<8>(a, KP, NC, backward, st);
-        case 12: return xattn_launch_m<12>(a, KP, NC, backward, st);
-        case 16: return xattn_launch_m<16>(a, KP, NC, backward, st);
+    switch (pl.NM) {
+        case 4: return xattn_launch_m<4>(a, pl, backward, st);
+        case 8: return xattn_launch_m<8>(a, pl, backward, st);
+        case 12: return xattn_launch_m<12>(a, pl, backward, st);
+        case 16: return xattn_launch_m<16>(a, pl, backward, st);
         default: OCRL_REQUIRE(false, "xattn: d_model %d not built (64, 128, 192, 256)", h.d);
     }
+}
+
+// Backward of the fold: from the per-token operands of xattn_launch(.., 1) (Pd, dS) to d ck, d cv and the two projection weight
+// gradients.  Two per-image sums over the tokens, four products batched over (image, head), two sums over the images in a fixed order.
+int xattn_fold_bwd_launch(const XaFoldBwdHost& f, hipStream_t st) {
+    XaPlan pl;
+    OCRL_REQUIRE(xattn_plan(f.K, f.d, f.h, &pl), "xattn_fold_bwd: unsupported shape (K %d, d %d, heads %d)", f.K, f.d, f.h);
+    OCRL_REQUIRE(f.B >= 1 && f.T >= 1, "xattn_fold_bwd: empty batch or sequence");
+    OCRL_REQUIRE(f.Pd && f.dS && f.gd && f.x && f.Wq && f.Wo && f.ck && f.cv && f.dVo && f.dAb && f.dck && f.dcv && f.pq && f.po && f.dWq && f.dWo && f.ws,
+                 "xattn_fold_bwd: missing buffers");
+    const int B = f.B, T = f.T, K = f.K, d = f.d, NH = f.h, KP = pl.KP, NC = pl.NC, dh = d / NH;
+    const float scale = 1.0f / sqrtf((float)dh);
+    GemmArgs ga;      // per-image sums over the tokens: d Vo_b = Pd^T d out,  d A_b = dS^T LN(x)      [NC, d] each
+    ga.M = NC; ga.N = d; ga.K = T; ga.lda = NC; ga.ldb = d; ga.ldc = d; ga.akc = 0; ga.bkc = 0; ga.batch = B;
+    ga.sA = (long long)T * NC; ga.sB = (long long)T * d; ga.sC = (long long)NC * d;
+    ga.A = f.Pd; ga.B = f.gd; ga.C = f.dVo;
+    RC(gemm_launch(ga, st));
+    ga.A = f.dS; ga.B = f.x; ga.C = f.dAb;
+    RC(gemm_launch(ga, st));
+    // back through the fold, batched over (image, head):
+    GemmArgs gb;      // d ck[k, h dh + j] = scale sum_e dA_b[(h,k), e] Wq[h dh + j, e]
+    gb.M = K; gb.N = dh; gb.K = d; gb.akc = 1; gb.bkc = 1; gb.lda = d; gb.ldb = d; gb.ldc = d; gb.batch = B * NH; gb.batch_inner = NH; gb.alpha = scale;
+    gb.A = f.dAb; gb.sA = (long long)NC * d; gb.sAi = (long long)KP * d;
+    gb.B = f.Wq; gb.sB = 0; gb.sBi = (long long)dh * d;
+    gb.C = f.dck; gb.sC = (long long)K * d; gb.sCi = dh;
+    RC(gemm_launch(gb, st));
+    GemmArgs gc;      // d cv[k, h dh + j] = sum_o dVo_b[(h,k), o] Wo[o, h dh + j]
+    gc.M = K; gc.N = dh; gc.K = d; gc.akc = 1; gc.bkc = 0; gc.lda = d; gc.ldb = d; gc.ldc = d; gc.batch = B * NH; gc.batch_inner = NH;
+    gc.A = f.dVo; gc.sA = (long long)NC * d; gc.sAi = (long long)KP * d;
+    gc.B = f.Wo; gc.sB = 0; gc.sBi = dh;
+    gc.C = f.dcv; gc.sC = (long long)K * d; gc.sCi = dh;
+    RC(gemm_launch(gc, st));
+    GemmArgs gq;      // this image's d Wq[h dh + j, e] = scale sum_k ck[k, h dh + j] dA_b[(h,k), e]
+    gq.M = dh; gq.N = d; gq.K = K; gq.akc = 0; gq.bkc = 0; gq.lda = d; gq.ldb = d; gq.ldc = d; gq.batch = B * NH; gq.batch_inner = NH; gq.alpha = scale;
+    gq.A = f.ck; gq.sA = (long long)K * d; gq.sAi = dh;
+    gq.B = f.dAb; gq.sB = (long long)NC * d; gq.sBi = (long long)KP * d;
+    gq.C = f.pq; gq.sC = (long long)d * d; gq.sCi = (long long)dh * d;
+    RC(gemm_launch(gq, st));
+    GemmArgs go;      // this image's d Wo[o, h dh + j] = sum_k dVo_b[(h,k), o] cv[k, h dh + j]
+    go.M = d; go.N = dh; go.K = K; go.akc = 0; go.bkc = 0; go.lda = d; go.ldb = d; go.ldc = d; go.batch = B * NH; go.batch_inner = NH;
+    go.A = f.dVo; go.sA = (long long)NC * d; go.sAi = (long long)KP * d;
+    go.B = f.cv; go.sB = (long long)K * d; go.sBi = dh;
+    go.C = f.po; go.sC = (long long)d * d; go.sCi = dh;
+    RC(gemm_launch(go, st));
+    RC(colsum_launch(f.pq, (long long)d * d, f.dWq, B, d * d, 0, 1.f, f.ws, f.ws_floats, st));
+    RC(colsum_launch(f.po, (long long)d * d, f.dWo, B, d * d, 0, 1.f, f.ws, f.ws_floats, st));
+    return 0;
 }
