@@ -681,6 +681,30 @@ int ocrl_scenes_batch(const ocrl_scenes_desc* d, unsigned long long seed, const 
                       float* objs /* [B,K,5] or NULL */, void* stream);
 int ocrl_scenes_uniforms(unsigned long long seed, long long index, int first, int n, float* out /* [n] */, void* stream);
 
+/* ---- task scenes: the first frames of the sprite tasks' episodes as a pre-training dataset (the reference collects its target-* and
+ *      odd-one-out-* datasets from the environments with only_initial: True), made on the device, batch by batch.  Scene i of a seed is a
+ *      function of (desc, seed, i) alone, and it is the environment's own episode: the kernel runs the episode function of
+ *      ocrl_sprite_env_reset.  Stateless: the caller owns every buffer (obs and masks 16-byte aligned, obs_u8 4-byte aligned); everything
+ *      is enqueued on `stream` with no host synchronisation, no atomics and no unbounded loop.  One launch per call.
+ * desc: a sprite environment's descriptor, validated exactly as by ocrl_sprite_env_reset (tasks 0 and 1); E and max_steps are not used
+ *   but must be valid; frames are H x H.  indices: device int64 [B], B >= 1.  An index is masked to its low 44 bits inside the kernel:
+ *   scene i is episode k = i & 0xFFFFFF of environment e = i >> 24 of the site-500 stream ("The draws" above), so scene (e << 24) | k
+ *   under a seed is what an environment of that seed shows when its environment e starts its episode k, and a plain dataset index
+ *   i < 2^24 is episode i of environment 0.
+ * Outputs, each may be NULL.  With R = hi + 1 rows (objects 0..n-1, the agent in row n, zero rows after it):
+ *   obs_u8 [B, H, W, 3]: the pixels of ocrl_sprite_render mode 1 of the rows: painter's order over rows 0..hi, the agent included, on black;
+ *   obs [B, 3, H, W] fp32: byte / 255.0f, what ocrl_obs_u8_to_f32 gives for those bytes;
+ *   masks [B, R + 1, H, W] fp32 of 0 / 1: ocrl_sprite_render mode 2 (the reference's render(mode="mask") with its zero padding): plane j is
+ *     row j alone and unoccluded, the planes of empty rows are zero, the last plane is 1 where no row covers the pixel.  (Not the
+ *     "last object covering" planes of ocrl_scenes_batch: where sprites overlap, the planes here overlap too.)
+ *   objs [B, R, 5] fp32: what ocrl_sprite_state_obs gives for the rows, the scale as its index in [0.15, 0.22];
+ *   labels [B] int64: the target's row index.
+ * Rejected, non-zero with a message: a null or invalid descriptor, B < 1, null indices, all five outputs null, misaligned outputs, a
+ *   batch beyond the grid limit. */
+int ocrl_task_scenes_batch(const ocrl_sprite_env_desc* d, unsigned long long seed, const long long* indices /* device int64 [B] */, int B,
+                           float* obs /* [B,3,H,W] or NULL */, unsigned char* obs_u8 /* [B,H,W,3] or NULL */, float* masks /* [B,hi+2,H,W] or NULL */,
+                           float* objs /* [B,hi+1,5] or NULL */, long long* labels /* [B] or NULL */, void* stream);
+
 /* ---- the per-object MLP of the ground-truth-state encoder (ocrs/gt/gt_module.py:14-27): x [M, D] through nl layers
  *      h_l = act_l(h_{l-1} W_l^T + b_l), W_l [dims[l], dims[l-1]] (torch layout), acts[l] != 0: ReLU, 0: none.  M = batch x objects rows
  *      (1 <= M < 2^22), 1 <= D <= 64, 1 <= nl <= 4, every dims[l] a multiple of 4 in 4 .. 256; anything else: ws_floats == 0 and the

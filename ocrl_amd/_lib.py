@@ -308,6 +308,7 @@ def lib():
     L.ocrl_sprite_env_uniforms.argtypes = [c_ulonglong, c_longlong, c_int, c_longlong, c_int, c_int, p, p]
     L.ocrl_scenes_batch.argtypes = [POINTER(ScenesDesc), c_ulonglong, p, c_int, p, p, p, p, p]
     L.ocrl_scenes_uniforms.argtypes = [c_ulonglong, c_longlong, c_int, c_int, p, p]
+    L.ocrl_task_scenes_batch.argtypes = [POINTER(SpriteEnvDesc), c_ulonglong, p, c_int, p, p, p, p, p, p]
     L.ocrl_comm_unique_id.argtypes = [p, c_size_t]
     L.ocrl_comm_init.argtypes = [POINTER(p), c_int, c_int, p]
     L.ocrl_comm_allreduce.argtypes = [p, p, c_longlong, p]

@@ -33,6 +33,17 @@ struct SpriteStepOut {
     int* ep_length;                 // [E]
 };
 
+#define TASK_SCENES_INDEX_BITS 44   // a task scene's index is taken modulo 2^44: environment (20 bits) << 24 | episode (24 bits)
+
+struct TaskScenesOut {              // task_scenes.hip; any of them may be null
+    float* obs;                     // [B, 3, H, W]
+    unsigned char* obs_u8;          // [B, H, W, 3]
+    float* masks;                   // [B, hi + 2, H, W]
+    float* objs;                    // [B, hi + 1, 5]
+    long long* labels;              // [B]
+};
+
+int task_scenes_batch_launch(const ocrl_sprite_env_desc& d, unsigned long long seed, const long long* indices, int B, const TaskScenesOut& o, hipStream_t st);
 int sprite_env_reset_launch(const ocrl_sprite_env_desc& d, float* rows, int* aux, unsigned long long seed, const unsigned char* mask, long long episode,
                             hipStream_t st);
 int sprite_env_step_launch(const ocrl_sprite_env_desc& d, float* rows, int* aux, unsigned long long seed, const long long* actions, const SpriteStepOut& o,

@@ -1,5 +1,6 @@
 // C ABI of the sprite environments (include/ocrl_hip.h: ocrl_sprite_*): the Target and Odd-One-Out tasks of
 // envs/synthetic_envs/{base,target,oddoneout}.py as a vectorised environment.  Stateless: the caller owns the state buffer (ocrl_sprite_env_state_floats floats) and every output.
+#include "scenes.h"
 #include "sprite_env.h"
 
 namespace {
@@ -103,6 +104,18 @@ int ocrl_sprite_state_obs(const float* rows, int E, int R, float* out, void* str
     OCRL_REQUIRE(rows && out, "ocrl_sprite_state_obs: null argument");
     OCRL_REQUIRE(E >= 1 && R >= 1 && R <= SPRITE_MAX_ROWS, "ocrl_sprite_state_obs: environments >= 1 and 1 <= rows <= %d (got %d, %d)", SPRITE_MAX_ROWS, E, R);
     return sprite_state_obs_launch(rows, (long long)E * R, out, static_cast<hipStream_t>(stream));
+}
+
+int ocrl_task_scenes_batch(const ocrl_sprite_env_desc* d, unsigned long long seed, const long long* indices, int B, float* obs, unsigned char* obs_u8,
+                           float* masks, float* objs, long long* labels, void* stream) {
+    RC(check_env(d, "ocrl_task_scenes_batch"));
+    OCRL_REQUIRE(B >= 1, "ocrl_task_scenes_batch: batch >= 1 (got %d)", B);
+    OCRL_REQUIRE(indices, "ocrl_task_scenes_batch: null indices");
+    OCRL_REQUIRE(obs || obs_u8 || masks || objs || labels, "ocrl_task_scenes_batch: no output requested (obs, obs_u8, masks, objs and labels are all null)");
+    OCRL_REQUIRE(((uintptr_t)obs | (uintptr_t)masks) % 16 == 0 && (uintptr_t)obs_u8 % 4 == 0,
+                 "ocrl_task_scenes_batch: obs and masks must be 16-byte aligned, obs_u8 4-byte aligned");
+    OCRL_REQUIRE((long long)B * cdiv(d->H, scenes_band_rows(d->H)) < (1LL << 31), "ocrl_task_scenes_batch: %d scenes of %d rows exceed one launch", B, d->H);
+    return task_scenes_batch_launch(*d, seed, indices, B, TaskScenesOut{obs, obs_u8, masks, objs, labels}, static_cast<hipStream_t>(stream));
 }
 
 int ocrl_sprite_env_uniforms(unsigned long long seed, long long env0, int n_envs, long long episode, int first, int n, float* out, void* stream) {

@@ -3,7 +3,8 @@
     python train_ocr.py ocr=slate ocr.slotattr.num_slots=6 dataset=random-N5C4S4S2 device=cuda:0 tags="slate"
 
 Supported: `defaults:` lists with `_self_`, relative group files (`- _base`), group selection (`- ocr: ???` is
-mandatory, chosen on the command line as `ocr=slate`), dotted `key=value` overrides with YAML-typed values,
+mandatory, chosen on the command line as `ocr=slate`), an absolute group under a package key (`- /env@task: target-N4C4S3S1` in a
+dataset file puts configs/env/target-N4C4S3S1.yaml under `task`), dotted `key=value` overrides with YAML-typed values,
 `+key=value` additions, and `${a.b}` interpolation of scalar values.  The result is an attribute namespace that
 supports `hasattr` probes the way the reference uses its DictConfig (ocrs/base.py:21-22,65-66)."""
 import copy
@@ -99,6 +100,13 @@ def _compose_file(config_dir, rel, choices, top):
             _merge(out, _compose_file(config_dir, os.path.join(group_dir, item), choices, False))
         elif isinstance(item, dict):
             (group, choice), = item.items()
+            if str(group).startswith("/"):                 # `- /env@task: name`: a group from the root, merged under the package key
+                group, _, package = str(group)[1:].partition("@")
+                if choice == "???" or choice is None:
+                    raise ValueError(f"{rel}.yaml: '/{group}' needs an option (available: {available(config_dir, group)})")
+                sub = _compose_file(config_dir, os.path.join(group, str(choice)), choices, False)
+                _merge(out.setdefault(package or group, {}), sub)
+                continue
             choice = choices.get(group, choice) if top else choice
             if choice == "???" or choice is None:
                 raise ValueError(f"You must specify '{group}', e.g. {group}=<option> (available: {available(config_dir, group)})")

@@ -3,7 +3,8 @@ the background last).  Reads the reference's HDF5 when h5py and the file are ava
 scenes deterministically per index.  With raw_uint8 (the default of get_dataloaders) a sample carries the image as the dataset stores
 it — "obss_u8", uint8 HWC — and the permute + /255 of utils/datasets.py:17 runs on the GPU (ocrl_obs_u8_to_f32) after a 4x smaller
 upload; raw_uint8=False gives the reference's float CHW "obss".  With dataset.on_device the synthetic scenes never exist on the host:
-device_scenes.py makes each batch on the GPU."""
+device_scenes.py makes each batch on the GPU; so it does the task datasets (target-*, odd-one-out-*), the first frames of the sprite
+tasks' episodes, which exist on the device only."""
 import os
 
 import numpy as np
@@ -75,6 +76,8 @@ def _device_loaders(config, batch_size, rank, world, seed, device, datafile):
         raise ValueError(f"dataset.on_device generates the scenes, but dataset.datadir {datafile} exists: unset one of the two keys")
     if device is None or torch.device(device).type != "cuda":
         raise ValueError(f"dataset.on_device needs the CUDA device the model trains on (got device={device!r})")
+    if config.get("task") is not None:
+        return _task_loaders(config, batch_size, rank, world, seed, device)
     kw = dict(num_objs=5, with_masks=bool(config.get("with_masks", False)), with_objs=bool(config.get("with_objs", False)))
     train = DeviceScenes(config.get("synthetic_train", 100000), config.obs_size, seed * 2 + 1, batch_size, device, shuffle=True, drop_last=True,
                          rank=rank, world=world, **kw)
@@ -82,12 +85,30 @@ def _device_loaders(config, batch_size, rank, world, seed, device, datafile):
     return train, val
 
 
+def _task_loaders(config, batch_size, rank, world, seed, device):
+    """a dataset config with a `task` mapping (an env config): the first frames of that task's episodes (device_scenes.py:
+    DeviceTaskScenes).  The descriptor is the environment's, so every refusal of ocrl_amd.envs applies; the frame size is the dataset's"""
+    from ..envs import env_desc
+    from .device_scenes import DeviceTaskScenes
+    desc = env_desc(config.task, 1)
+    desc.H = int(config.obs_size)
+    kw = dict(with_masks=bool(config.get("with_masks", False)), with_objs=bool(config.get("with_objs", False)))
+    train = DeviceTaskScenes(desc, config.get("synthetic_train", 100000), seed * 2 + 1, batch_size, device, shuffle=True, drop_last=True, rank=rank,
+                             world=world, **kw)
+    val = DeviceTaskScenes(desc, config.get("synthetic_val", 1000), seed * 2 + 2, batch_size, device, **kw)
+    return train, val
+
+
 def get_dataloaders(config, batch_size, num_workers, rank=0, world=1, seed=0, raw_uint8=True, device=None):
     """utils/tools.py:155-178 without the wandb download path; with dataset.on_device the scenes are made on `device` and num_workers
-    is ignored"""
+    is ignored.  A config with a `task` mapping (configs/dataset/target-*.yaml, odd-one-out-*.yaml) is a sprite task's first frames: made
+    on the device, or read from its datadir file; there is no host generator for them"""
     datafile = config.datadir if config.get("datadir") else None
     if config.get("on_device", False):
         return _device_loaders(config, batch_size, rank, world, seed, device, datafile)
+    if config.get("task") is not None and not (datafile and os.path.isfile(datafile)):
+        raise ValueError(f"dataset {config.get('name')}: a task's frames are made on the GPU only: set dataset.on_device=True, or dataset.datadir to "
+                         "an existing HDF5 file")
     if datafile and os.path.isfile(datafile):
         try:
             import h5py

@@ -51,25 +51,26 @@ class _Scenes:
         return {k: v[0] for k, v in self._loader.batch(idx).items()}
 
 
-class DeviceScenes:
-    """an iterable of batches {"obss": fp32 [B,3,H,W], "masks": [B,K+1,H,W,1] (with_masks), "objs": [B,K,5] (with_objs)} of fresh
-    tensors on `device`, with the surface train_ocr.py uses of a DataLoader: len() = batches, .dataset, .sampler.set_epoch"""
+class _DeviceLoader:
+    """what the on-device loaders share: the surface train_ocr.py uses of a DataLoader (len() = batches, .dataset, .sampler.set_epoch) and
+    an epoch as a list of indices, shuffled and sharded on the host, uploaded once, one ``batch(idx)`` call per batch"""
 
-    def __init__(self, n, size, seed, batch_size, device, num_objs=5, with_masks=False, with_objs=False, shuffle=False, drop_last=False,
-                 rank=0, world=1):
+    def __init__(self, n, size, seed, batch_size, device, with_masks, with_objs, shuffle, drop_last, rank, world):
+        who = type(self).__name__
         self.device = torch.device(device) if device is not None else None
         if self.device is None or self.device.type != "cuda":
-            raise ValueError(f"DeviceScenes: the scenes are made on a CUDA device (got device={device!r})")
-        self.n, self.size, self.seed, self.batch_size, self.num_objs = int(n), int(size), int(seed), int(batch_size), int(num_objs)
+            raise ValueError(f"{who}: the scenes are made on a CUDA device (got device={device!r})")
+        self.n, self.size, self.seed, self.batch_size = int(n), int(size), int(seed), int(batch_size)
         self.with_masks, self.with_objs, self.shuffle, self.drop_last = bool(with_masks), bool(with_objs), bool(shuffle), bool(drop_last)
         self.rank, self.world, self.epoch = int(rank), int(world), 0
-        if not (8 <= self.size <= 512 and self.size % 4 == 0 and 1 <= self.num_objs <= 15):
-            raise ValueError(f"DeviceScenes: obs_size a multiple of 4 in [8, 512] and 1 to 15 objects (got {self.size}, {self.num_objs})")
+        self._check()
         _rank_indices(self.n, 0, 0, self.rank, self.world, False)            # the same refusals as an epoch's, before the first one
         if self.batch_size < 1:
-            raise ValueError(f"DeviceScenes: batch_size >= 1 (got {self.batch_size})")
-        self._desc = _lib.ScenesDesc(H=self.size, K=self.num_objs)
+            raise ValueError(f"{who}: batch_size >= 1 (got {self.batch_size})")
         self.dataset, self.sampler = _Scenes(self), self
+
+    def _check(self):
+        """the subclass's own refusals, raised before the index rules'"""
 
     def set_epoch(self, epoch):
         self.epoch = int(epoch)
@@ -77,6 +78,29 @@ class DeviceScenes:
     def __len__(self):
         per_rank = (self.n - self.n % self.world) // self.world
         return per_rank // self.batch_size if self.drop_last else -(-per_rank // self.batch_size)
+
+    def __iter__(self):
+        idx = _rank_indices(self.n, self.seed, self.epoch, self.rank, self.world, self.shuffle).to(self.device)    # one upload per epoch
+        if self.shuffle:
+            self.epoch += 1                # a pass that no set_epoch precedes takes the next order, as a shuffling DataLoader's would
+        bs = self.batch_size
+        for b in range(len(self)):
+            yield self.batch(idx[b * bs:(b + 1) * bs])
+
+
+class DeviceScenes(_DeviceLoader):
+    """an iterable of batches {"obss": fp32 [B,3,H,W], "masks": [B,K+1,H,W,1] (with_masks), "objs": [B,K,5] (with_objs)} of fresh
+    tensors on `device`, with the surface train_ocr.py uses of a DataLoader: len() = batches, .dataset, .sampler.set_epoch"""
+
+    def __init__(self, n, size, seed, batch_size, device, num_objs=5, with_masks=False, with_objs=False, shuffle=False, drop_last=False,
+                 rank=0, world=1):
+        self.num_objs = int(num_objs)
+        super().__init__(n, size, seed, batch_size, device, with_masks, with_objs, shuffle, drop_last, rank, world)
+        self._desc = _lib.ScenesDesc(H=self.size, K=self.num_objs)
+
+    def _check(self):
+        if not (8 <= self.size <= 512 and self.size % 4 == 0 and 1 <= self.num_objs <= 15):
+            raise ValueError(f"DeviceScenes: obs_size a multiple of 4 in [8, 512] and 1 to 15 objects (got {self.size}, {self.num_objs})")
 
     def batch(self, idx):
         """the scenes of idx (int64 [B] on the device, contiguous) as one ocrl_scenes_batch call on the current stream"""
@@ -93,10 +117,39 @@ class DeviceScenes:
             out["objs"] = objs
         return out
 
-    def __iter__(self):
-        idx = _rank_indices(self.n, self.seed, self.epoch, self.rank, self.world, self.shuffle).to(self.device)    # one upload per epoch
-        if self.shuffle:
-            self.epoch += 1                # a pass that no set_epoch precedes takes the next order, as a shuffling DataLoader's would
-        bs = self.batch_size
-        for b in range(len(self)):
-            yield self.batch(idx[b * bs:(b + 1) * bs])
+
+class DeviceTaskScenes(_DeviceLoader):
+    """the first frames of a sprite task's episodes (ocrl_task_scenes_batch; ``desc`` from ocrl_amd.envs.env_desc, its H the frame size):
+    batches {"obss": fp32 [B,3,H,W], "masks": [B,hi+2,H,W,1] (with_masks: each row alone, the agent's after the objects', the background
+    last), "objs": [B,hi+1,5] and "labels": int64 [B,1], the target's row (with_objs)}.  Scene i is episode i of environment 0 of the
+    seed's streams: what a vectorised environment of that seed shows when it starts that episode."""
+
+    def __init__(self, desc, n, seed, batch_size, device, with_masks=False, with_objs=False, shuffle=False, drop_last=False, rank=0, world=1):
+        self._desc = desc
+        super().__init__(n, desc.H, seed, batch_size, device, with_masks, with_objs, shuffle, drop_last, rank, world)
+
+    def _check(self):
+        d = self._desc
+        if not (8 <= self.size <= 512 and self.size % 4 == 0):
+            raise ValueError(f"DeviceTaskScenes: obs_size a multiple of 4 in [8, 512] (got {self.size})")
+        if self.with_objs and d.lo != d.hi:
+            raise ValueError(f"DeviceTaskScenes: with_objs needs num_objects_range [lo, hi] with lo == hi (got [{d.lo}, {d.hi}]): the zero row "
+                             "after the agent of a smaller episode would be matched as an object")
+        if self.n > 1 << 24:
+            raise ValueError(f"DeviceTaskScenes: at most 2^24 scenes, the episodes of one environment's stream (got {self.n})")
+
+    def batch(self, idx):
+        """the scenes of idx (int64 [B] on the device, contiguous) as one ocrl_task_scenes_batch call on the current stream"""
+        B, H, R = idx.shape[0], self.size, self._desc.hi + 1
+        obs = torch.empty(B, 3, H, H, dtype=torch.float32, device=self.device)
+        masks = torch.empty(B, R + 1, H, H, dtype=torch.float32, device=self.device) if self.with_masks else None
+        objs = torch.empty(B, R, 5, dtype=torch.float32, device=self.device) if self.with_objs else None
+        labels = torch.empty(B, 1, dtype=torch.int64, device=self.device) if self.with_objs else None
+        _bridge.launch(self.device, _lib.lib().ocrl_task_scenes_batch, self._desc, self.seed & 0xFFFFFFFFFFFFFFFF, _lib.ptr(idx), B,
+                       _lib.ptr(obs), None, _lib.ptr(masks), _lib.ptr(objs), _lib.ptr(labels))
+        out = {"obss": obs}
+        if masks is not None:
+            out["masks"] = masks.unsqueeze(-1)
+        if objs is not None:
+            out["objs"], out["labels"] = objs, labels
+        return out
