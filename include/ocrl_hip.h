@@ -745,6 +745,25 @@ size_t ocrl_flat_clip_rmsprop_ws_floats(void);
 int ocrl_flat_clip_rmsprop_l2(float* p, const float* g, float* sq, long long n, float max_norm, float lr, float alpha, float eps,
                               float* norm_out /* device, 1 float */, float* ws, size_t ws_floats, void* stream);
 
+/* ---- The same two steps over several flat buffers at once, as stable-baselines3 clips and steps a policy whose encoder keeps its
+ *      parameters in a buffer of its own: the semantics are those of ocrl_flat_clip_adam_l2 / ocrl_flat_clip_rmsprop_l2 applied to the
+ *      concatenation of the segments.  norm = ||g||_2 over every segment's g together (written to norm_out), one coef for all, then the
+ *      same update of every segment; a NaN norm reaches every weight of every segment; g is never written.  No atomics, no host
+ *      synchronisation: block partial sums of squares are folded in a fixed order (segment order, then block order), so the result is a
+ *      function of the inputs and the segment lengths alone, the same bit for bit from run to run.  `seg` is HOST memory, read during the
+ *      call and handed to the kernels by value: no upload, copy or allocation.  Three launches whatever nseg is (partial sums, their
+ *      fold, the update); a segment's last n % 4 elements are taken inside them.  p, g, s0, s1 16-byte aligned; n >= 1, any tail.
+ *      A segment whose g is all zero and whose m = v = 0 comes back with p, m, v unchanged bit for bit (Adam).
+ *      Rejected before any launch: nseg outside [1, OCRL_FLAT_MAX_SEGMENTS]; a null seg, p, g, s0 (s1 for Adam), norm_out or ws;
+ *      n < 1; a misaligned pointer; ws_floats < ocrl_flat_clip_multi_ws_floats(); step < 1; alpha outside (0, 1) or eps <= 0 (RMSprop). */
+#define OCRL_FLAT_MAX_SEGMENTS 8
+typedef struct { float* p; const float* g; float* s0; float* s1; long long n; } ocrl_flat_segment;   /* s0, s1: m, v (Adam); sq, unused (RMSprop) */
+size_t ocrl_flat_clip_multi_ws_floats(void);
+int ocrl_flat_clip_adam_l2_multi(const ocrl_flat_segment* seg, int nseg, float max_norm, float lr, float beta1, float beta2, float eps,
+                                 int step, float* norm_out /* device, 1 float */, float* ws, size_t ws_floats, void* stream);
+int ocrl_flat_clip_rmsprop_l2_multi(const ocrl_flat_segment* seg, int nseg, float max_norm, float lr, float alpha, float eps,
+                                    float* norm_out /* device, 1 float */, float* ws, size_t ws_floats, void* stream);
+
 /* ---- IODINE (ocrs/iodine/iodine_module.py:14-271, ocrs/iodine/iodine.py:4-14, ocrs/base.py:60-74): SURVEY.md §8 row a20 ----
  * Same conventions as the SLATE handle: flat fp32 parameter / gradient / Adam buffers in the reference's
  * _module.parameters() order and state_dict names, adopted from the caller; one workspace; all work on the caller's stream. */

@@ -77,6 +77,21 @@ class ScenesDesc(ctypes.Structure):
     _fields_ = [("H", c_int), ("K", c_int)]
 
 
+FLAT_MAX_SEGMENTS = 8            # OCRL_FLAT_MAX_SEGMENTS
+
+
+class FlatSegment(ctypes.Structure):
+    """mirror of ocrl_flat_segment (include/ocrl_hip.h); make a table with flat_segments()"""
+    _fields_ = [("p", c_void_p), ("g", c_void_p), ("s0", c_void_p), ("s1", c_void_p), ("n", c_longlong)]
+
+
+def flat_segments(segs):
+    """the host table ocrl_flat_clip_*_l2_multi read: one (p, g, s0, s1, n) per segment; p, g, s0, s1 are device addresses as integers
+    or ptr()'s result, None for a null pointer"""
+    addr = lambda a: a.value if isinstance(a, c_void_p) else a
+    return (FlatSegment * len(segs))(*[FlatSegment(addr(p), addr(g), addr(s0), addr(s1), int(n)) for p, g, s0, s1, n in segs])
+
+
 def acnet_desc(B, F, A, dims, acts):
     """AcnetDesc of three trunks: dims / acts = (shared, policy, value) sequences of widths / activation codes (0 none, 1 relu, 2 tanh)"""
     d = AcnetDesc(B=B, F=F, A=A)
@@ -290,6 +305,10 @@ def lib():
     L.ocrl_flat_clip_rmsprop_ws_floats.argtypes = []
     L.ocrl_flat_clip_rmsprop_ws_floats.restype = c_size_t
     L.ocrl_flat_clip_rmsprop_l2.argtypes = [p, p, p, c_longlong, c_float, c_float, c_float, c_float, p, p, c_size_t, p]
+    L.ocrl_flat_clip_multi_ws_floats.argtypes = []
+    L.ocrl_flat_clip_multi_ws_floats.restype = c_size_t
+    L.ocrl_flat_clip_adam_l2_multi.argtypes = [POINTER(FlatSegment), c_int, c_float, c_float, c_float, c_float, c_float, c_int, p, p, c_size_t, p]
+    L.ocrl_flat_clip_rmsprop_l2_multi.argtypes = [POINTER(FlatSegment), c_int, c_float, c_float, c_float, c_float, p, p, c_size_t, p]
     L.ocrl_gae.argtypes = [p, p, p, p, p, p, p, c_int, c_int, c_float, c_float, p]
     L.ocrl_sprite_env_desc_size.restype = c_size_t
     if L.ocrl_sprite_env_desc_size() != ctypes.sizeof(SpriteEnvDesc):

@@ -482,6 +482,23 @@ int clip_rmsprop_launch(float* p, const float* g, float* sq, long long n, const 
                         hipStream_t st);
 int clip_rmsprop_tail_launch(float* p, const float* g, float* sq, int n, const float* norm, float clip, float lr, double alpha, double eps,
                              hipStream_t st);
+// The L2 clip + update over up to FLAT_MAX_SEG flat buffers in three launches (partial sums of squares, their fold, the update): the norm
+// is that of all the gradients together.  The table travels by value as a kernel argument; the launchers fill blk0 (the prefix of each
+// segment's block count, at most FLAT_SEG_BLOCKS each).  s0, s1: m, v (Adam); sq, unused (RMSprop).  Any n >= 1; ws: blk0[nseg] floats,
+// at most FLAT_MAX_SEG * FLAT_SEG_BLOCKS.
+constexpr int FLAT_MAX_SEG = 8, FLAT_SEG_BLOCKS = 1024;
+struct FlatSegs {
+    float* p[FLAT_MAX_SEG];
+    const float* g[FLAT_MAX_SEG];
+    float* s0[FLAT_MAX_SEG];
+    float* s1[FLAT_MAX_SEG];
+    long long n[FLAT_MAX_SEG];
+    int blk0[FLAT_MAX_SEG + 1];
+    int nseg;
+};
+int multi_clip_adam_launch(FlatSegs t, float* norm, float clip, float lr, double b1, double b2, double eps, int step, float* ws, size_t ws_floats,
+                           hipStream_t st);
+int multi_clip_rmsprop_launch(FlatSegs t, float* norm, float clip, float lr, double alpha, double eps, float* ws, size_t ws_floats, hipStream_t st);
 int store_u64_launch(unsigned long long* dst, unsigned long long v, hipStream_t st);
 int slot_init_launch(const float* mu, const float* logsig, const float* noise, float* slots0, int BK, int D, unsigned long long seed, hipStream_t st,
                      const unsigned long long* seed_dev = nullptr);

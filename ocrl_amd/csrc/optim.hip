@@ -1,5 +1,6 @@
 // Global inf-norm gradient clip + Adam on flat fp32 buffers (reference: ocrs/base.py:65-72,
-// torch.nn.utils.clip_grad_norm_(…, "inf") and torch.optim.Adam defaults), and the TF-style RMSprop update A2C takes after the same clip.
+// torch.nn.utils.clip_grad_norm_(…, "inf") and torch.optim.Adam defaults), the TF-style RMSprop update A2C takes after the same clip, and
+// the L2 clip + either update over several flat buffers under one joint norm (multi_*, at the end).
 #include "common.h"
 #include "kernels.h"
 
@@ -151,5 +152,122 @@ int clip_rmsprop_tail_launch(float* p, const float* g, float* sq, int n, const f
     OCRL_REQUIRE(n >= 1 && n < 4, "clip_rmsprop_tail: 1 <= n <= 3");
     hipLaunchKernelGGL(clip_rmsprop_tail_kernel, dim3(1), dim3(64), 0, st, p, g, sq, n, norm, clip, lr, (float)alpha, (float)(1.0 - alpha), (float)eps);
     OCRL_CHECK_LAUNCH("clip_rmsprop_tail");
+    return 0;
+}
+
+// ---- the same clip + update over up to FLAT_MAX_SEG flat buffers at once (ocrl_flat_clip_*_l2_multi): the norm is that of all the
+// gradients together.  The segment table is a kernel argument, passed by value: nothing is uploaded.  Segment s owns the blocks
+// [blk0[s], blk0[s + 1]) of the partial-sum launch and of the update launch alike; a block finds s from blockIdx alone, so s is uniform
+// across it, and walks its segment's groups of four floats grid-stride.  The n % 4 floats a segment's length leaves past its last
+// group of four are taken element by element inside the same launches.
+static_assert(FLAT_MAX_SEG == 8, "seg_of compares against seven boundaries");
+__device__ __forceinline__ int seg_of(const FlatSegs& t) {
+    const int b = blockIdx.x;
+    int s = 0;
+#pragma unroll
+    for (int i = 1; i < FLAT_MAX_SEG; ++i) s += (i < t.nseg && b >= t.blk0[i]) ? 1 : 0;
+    return s;
+}
+// part[blk] = the block's share of its segment's sum of squares
+__global__ __launch_bounds__(256) void multi_sumsq_kernel(const FlatSegs t, float* __restrict__ part) {
+    __shared__ float red[4];
+    const int s = seg_of(t), lb = blockIdx.x - t.blk0[s], nb = t.blk0[s + 1] - t.blk0[s];
+    const float* __restrict__ g = t.g[s];
+    const long long n = t.n[s], n4 = n >> 2;
+    float a = 0.f;
+    for (long long i = (long long)lb * 256 + threadIdx.x; i < n4; i += (long long)nb * 256) {
+        const float4 v = reinterpret_cast<const float4*>(g)[i];
+        a += (v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w);
+    }
+    if (lb == nb - 1 && (long long)threadIdx.x < n - 4 * n4) { const float x = g[4 * n4 + threadIdx.x]; a += x * x; }
+    a = wave_sum(a);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = a;
+    __syncthreads();
+    if (threadIdx.x == 0) part[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+// norm[0] = sqrt of the sum of the partials, which lie in segment order, then block order: thread j adds part[j], part[j + 256], ... in
+// that order, then the fixed tree of the block.  One block of 256 threads.
+__global__ __launch_bounds__(256) void multi_norm_kernel(const float* __restrict__ part, int n, float* __restrict__ norm) {
+    __shared__ float red[4];
+    float a = 0.f;
+    for (int i = threadIdx.x; i < n; i += 256) a += part[i];
+    a = wave_sum(a);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = a;
+    __syncthreads();
+    if (threadIdx.x == 0) norm[0] = sqrtf((red[0] + red[1]) + (red[2] + red[3]));
+}
+// ADAM: s0 = m, s1 = v and (c0 .. c5) = (lr / bc1, 1 - beta1, beta2, 1 - beta2, eps, sqrt(bc2)); else s0 = sq and (c0 .. c3) = (lr, alpha,
+// 1 - alpha, eps)
+template <bool ADAM>
+__global__ __launch_bounds__(256) void multi_update_kernel(const FlatSegs t, const float* __restrict__ norm, float clip, float c0, float c1,
+                                                          float c2, float c3, float c4, float c5) {
+    const int s = seg_of(t), lb = blockIdx.x - t.blk0[s], nb = t.blk0[s + 1] - t.blk0[s];
+    float* __restrict__ p = t.p[s];
+    const float* __restrict__ g = t.g[s];
+    float* __restrict__ s0 = t.s0[s];
+    float* __restrict__ s1 = t.s1[s];
+    const long long n = t.n[s], n4 = n >> 2;
+    const float coef = clip_coef(norm, clip, 1.f);
+    auto upd = [&](float gg, float& a, float& b, float& pp) {
+        if (ADAM) adam_upd(gg, a, b, pp, coef, c0, c1, c2, c3, c4, c5);
+        else rmsprop_upd(gg, a, pp, coef, c0, c1, c2, c3);
+    };
+    for (long long i = (long long)lb * 256 + threadIdx.x; i < n4; i += (long long)nb * 256) {
+        const float4 gv = reinterpret_cast<const float4*>(g)[i];
+        float4 av = reinterpret_cast<float4*>(s0)[i], pv = reinterpret_cast<float4*>(p)[i], bv = av;
+        if (ADAM) bv = reinterpret_cast<float4*>(s1)[i];
+        upd(gv.x, av.x, bv.x, pv.x); upd(gv.y, av.y, bv.y, pv.y); upd(gv.z, av.z, bv.z, pv.z); upd(gv.w, av.w, bv.w, pv.w);
+        reinterpret_cast<float4*>(s0)[i] = av;
+        if (ADAM) reinterpret_cast<float4*>(s1)[i] = bv;
+        reinterpret_cast<float4*>(p)[i] = pv;
+    }
+    if (lb == nb - 1 && (long long)threadIdx.x < n - 4 * n4) {
+        const long long i = 4 * n4 + threadIdx.x;
+        float a = s0[i], b = ADAM ? s1[i] : 0.f, pp = p[i];
+        upd(g[i], a, b, pp);
+        s0[i] = a;
+        if (ADAM) s1[i] = b;
+        p[i] = pp;
+    }
+}
+
+// blk0: each segment gets one block per 256 groups of four floats, at least one and at most FLAT_SEG_BLOCKS
+static void flat_segs_blocks(FlatSegs& t) {
+    t.blk0[0] = 0;
+    for (int s = 0; s < FLAT_MAX_SEG; ++s) {
+        int nb = 0;
+        if (s < t.nseg) {
+            const long long want = (t.n[s] / 4 + 255) / 256;
+            nb = want < 1 ? 1 : want > FLAT_SEG_BLOCKS ? FLAT_SEG_BLOCKS : (int)want;
+        }
+        t.blk0[s + 1] = t.blk0[s] + nb;
+    }
+}
+static int multi_norm_launch(const FlatSegs& t, float* norm, float* ws, size_t ws_floats, hipStream_t st) {
+    const int nblk = t.blk0[t.nseg];
+    OCRL_REQUIRE(t.nseg >= 1 && t.nseg <= FLAT_MAX_SEG && nblk >= 1 && ws && ws_floats >= (size_t)nblk, "flat multi: bad segment table or scratch");
+    hipLaunchKernelGGL(multi_sumsq_kernel, dim3(nblk), dim3(256), 0, st, t, ws);
+    OCRL_CHECK_LAUNCH("multi_sumsq");
+    hipLaunchKernelGGL(multi_norm_kernel, dim3(1), dim3(256), 0, st, ws, nblk, norm);
+    OCRL_CHECK_LAUNCH("multi_norm");
+    return 0;
+}
+int multi_clip_adam_launch(FlatSegs t, float* norm, float clip, float lr, double b1, double b2, double eps, int step, float* ws, size_t ws_floats,
+                           hipStream_t st) {
+    OCRL_REQUIRE(step >= 1, "multi_clip_adam: step < 1");
+    flat_segs_blocks(t);
+    RC(multi_norm_launch(t, norm, ws, ws_floats, st));
+    const double bc1 = 1.0 - pow(b1, step), bc2 = 1.0 - pow(b2, step);      // as clip_adam_launch takes them
+    hipLaunchKernelGGL(multi_update_kernel<true>, dim3(t.blk0[t.nseg]), dim3(256), 0, st, t, norm, clip, lr / (float)bc1, (float)(1.0 - b1),
+                       (float)b2, (float)(1.0 - b2), (float)eps, (float)sqrt(bc2));
+    OCRL_CHECK_LAUNCH("multi_clip_adam");
+    return 0;
+}
+int multi_clip_rmsprop_launch(FlatSegs t, float* norm, float clip, float lr, double alpha, double eps, float* ws, size_t ws_floats, hipStream_t st) {
+    flat_segs_blocks(t);
+    RC(multi_norm_launch(t, norm, ws, ws_floats, st));
+    hipLaunchKernelGGL(multi_update_kernel<false>, dim3(t.blk0[t.nseg]), dim3(256), 0, st, t, norm, clip, lr, (float)alpha, (float)(1.0 - alpha),
+                       (float)eps, 0.f, 0.f);
+    OCRL_CHECK_LAUNCH("multi_clip_rmsprop");
     return 0;
 }

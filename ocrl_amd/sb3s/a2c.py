@@ -37,22 +37,36 @@ class A2C(OnPolicyAlgorithm):
         if not self.use_rms_prop:
             return self._init_adam()
         self.square_avg = torch.ones_like(self.flat_p)
+        self.enc_sq = self._new_encoder_state(1.0)               # a trainable encoder's range: its own square average, at ones too
         self.rmsprop_step = 0
-        self._ws = torch.empty(_lib.lib().ocrl_flat_clip_rmsprop_ws_floats(), device=self.device)
+        L = _lib.lib()
+        self._ws = torch.empty(L.ocrl_flat_clip_rmsprop_ws_floats() if self._encoder is None else L.ocrl_flat_clip_multi_ws_floats(), device=self.device)
 
     def _optimizer_step(self):
-        """L2 clip of the whole gradient to max_grad_norm, then the TF-style RMSprop step: one C call, no host synchronisation"""
+        """L2 clip of the whole gradient to max_grad_norm, then the TF-style RMSprop step: one C call, no host synchronisation.  With a
+        trainable encoder the norm is the joint one and the one call steps the policy's and the encoder's segments."""
         if not self.use_rms_prop:
             return self._adam_step()
         self.rmsprop_step += 1
         with torch.cuda.device(self.device):
+            if self._encoder is not None:
+                seg = self._segments(self.square_avg, None, self.enc_sq, None)
+                _lib.check(_lib.lib().ocrl_flat_clip_rmsprop_l2_multi(seg, len(seg), self.max_grad_norm, self.learning_rate, RMSPROP_ALPHA,
+                                                                      self.rms_prop_eps, _lib.ptr(self._norm), _lib.ptr(self._ws), self._ws.numel(),
+                                                                      _lib.stream(self.device)))
+                return
             _lib.check(_lib.lib().ocrl_flat_clip_rmsprop_l2(_lib.ptr(self.flat_p), _lib.ptr(self.flat_g), _lib.ptr(self.square_avg),
                                                             self.flat_p.numel(), self.max_grad_norm, self.learning_rate, RMSPROP_ALPHA,
                                                             self.rms_prop_eps, _lib.ptr(self._norm), _lib.ptr(self._ws), self._ws.numel(),
                                                             _lib.stream(self.device)))
 
     def _optimizer_state(self):
-        return {"square_avg": self.square_avg, "step": self.rmsprop_step} if self.use_rms_prop else self._adam_state()
+        if not self.use_rms_prop:
+            return self._adam_state()
+        out = {"square_avg": self.square_avg, "step": self.rmsprop_step}
+        if self._encoder is not None:
+            out["enc_sq"] = self.enc_sq
+        return out
 
     def _load_optimizer_state(self, opt):
         if not self.use_rms_prop:
@@ -61,7 +75,10 @@ class A2C(OnPolicyAlgorithm):
             n = opt["square_avg"].numel() if "square_avg" in opt else "no"
             raise ValueError(f"{self._who}.load: the checkpoint's optimiser state has {n} RMSprop entries, this policy's {self.square_avg.numel()} "
                              "(use_rms_prop and the policy layout must be those of the run that saved it)")
+        self._check_encoder_state(opt, ("enc_sq",))
         self.square_avg.copy_(opt["square_avg"])
+        if self._encoder is not None:
+            self.enc_sq.copy_(opt["enc_sq"])
         self.rmsprop_step = int(opt["step"])
 
     # ---- the update

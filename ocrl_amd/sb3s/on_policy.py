@@ -6,7 +6,10 @@ add their ``train()`` and their hyper-parameters.
 ``RolloutBuffer`` and ``OnPolicyAlgorithm`` restate stable-baselines3 1.5's classes of the same names from the published algorithms: none
 of their text is copied.  The GPU work is the library's: acting is ``CustomActorCriticPolicy.forward`` with a sampling stream
 (``ocrl_acnet_act``: one launch after the extractor), advantages are ``compute_gae`` and the Adam update ``ocrl_flat_clip_adam_l2`` on one
-flat parameter buffer.  Where this departs from stable-baselines3 is listed in DESIGN.md §7."""
+flat parameter buffer.  A trainable SLATE / Slot-Attention encoder behind the extractor keeps its parameters in its engine's flat buffer;
+the update then is ``ocrl_flat_clip_adam_l2_multi`` / ``ocrl_flat_clip_rmsprop_l2_multi`` over two segments, the policy's buffer and the
+encoder's range, as stable-baselines3 clips and steps all of ``policy.parameters()`` together.  Where this departs from
+stable-baselines3 is listed in DESIGN.md §7."""
 import collections
 import numbers
 
@@ -19,6 +22,7 @@ from .custom_acnets import _n_actions, compute_gae
 
 ALGOS = ("PPO", "A2C")          # the classes built on OnPolicyAlgorithm; a checkpoint names the one that wrote it
 ADAM_EPS = 1e-5                 # stable-baselines3's ActorCriticPolicy builds Adam with eps = 1e-5
+ENCODER_TENSORS = ("_enc.", "_enc_pos.", "_slotattn.")        # what ocrl_slate_encode_backward writes: SLATE's group 1 up to the slot projection
 RolloutBatch = collections.namedtuple("RolloutBatch", "observations actions old_values old_log_prob advantages returns")
 
 
@@ -137,10 +141,18 @@ class OnPolicyAlgorithm:
         if not hasattr(policy, "set_sampling"):
             raise TypeError(f"{_WHO}: policy must be an ocrl_amd.sb3s.CustomActorCriticPolicy (or the class), got {type(policy).__name__}")
         self.policy = policy.to(self.device)
+        self._encoder = None
         for m in self.policy.modules():
             if isinstance(m, FlatParamModule):
-                raise NotImplementedError(f"{_WHO}: a trainable {m.backend} encoder behind the extractor keeps its own flat buffers and optimiser "
-                                          f"step; stepping it from {self.ALGO} is not built: give the extractor a pre-trained, frozen encoder")
+                if self._encoder is not None or m.backend != "SLATE" or not getattr(m, "finetune_through_slots", False):
+                    raise NotImplementedError(f"{_WHO}: a trainable {m.backend} encoder behind the extractor keeps its own flat buffers and optimiser "
+                                              f"step; stepping it from {self.ALGO} is not built: give the extractor a pre-trained, frozen encoder")
+                self._encoder = m
+        if self._encoder is not None:
+            # sized once for the rollouts and the minibatches alike: no rebuild, and so no re-seating of its flat buffers, inside learn()
+            if getattr(self._encoder, "_device", None) is None:
+                self._encoder.to(self.device)
+            self._encoder._ensure_engine(max(self.n_envs, self.batch_size))
         self.policy.set_sampling(self.seed)
         self.generator = torch.Generator(device=self.device).manual_seed(self.seed)
         self._flatten_parameters()
@@ -157,8 +169,11 @@ class OnPolicyAlgorithm:
     def _flatten_parameters(self):
         """re-seat every trainable parameter as a view of ``flat_p`` and its .grad as a view of ``flat_g`` (each starts on a multiple of
         4 floats; the padding stays zero).  state_dict() keeps its keys and shapes and reads the same memory the optimiser writes.  The
-        optimiser's own state is the subclass's (``_init_optimizer``)."""
-        params = [p for p in self.policy.parameters() if p.requires_grad]
+        optimiser's own state is the subclass's (``_init_optimizer``).  A trainable SLATE encoder's parameters are left where they are:
+        views of its engine's flat buffer, which the HIP model is bound to; the step reaches them as a second segment
+        (``_encoder_range``)."""
+        own = set() if self._encoder is None else {id(p) for p in self._encoder.parameters()}
+        params = [p for p in self.policy.parameters() if p.requires_grad and id(p) not in own]
         for p in params:
             if p.dtype != torch.float32 or p.device != self.device:
                 raise RuntimeError(f"{self._who}: parameters must be float32 on {self.device} (got {p.dtype} on {p.device})")
@@ -175,18 +190,70 @@ class OnPolicyAlgorithm:
             p.grad = self.flat_g[o:o + p.numel()].view(p.shape)
         self._params = params
         self._norm = torch.zeros(1, device=self.device)
+        self._enc_range = self._encoder_range()
         self._init_optimizer()
 
+    # ---- a trainable SLATE encoder: the second segment of the step
+    def _encoder_range(self):
+        """(first float, length) of the smallest contiguous range of the encoder engine's flat buffer that covers the tensors
+        ocrl_slate_encode_backward writes (ENCODER_TENSORS), from the engine's own parameter table; None without such an encoder.  The
+        16-byte gaps between the tensors are zero in every buffer and stay so under the step."""
+        if self._encoder is None:
+            return None
+        eng = self._encoder.engine
+        live = [p for p in eng.params if p.name.startswith(ENCODER_TENSORS)]
+        lo, hi = min((p.offset for p in live), default=0), max((p.offset + p.numel for p in live), default=0)
+        other = [p.name for p in eng.params if not p.name.startswith(ENCODER_TENSORS) and p.offset < hi and p.offset + p.numel > lo]
+        if not live or other or lo % 4:
+            raise RuntimeError(f"{self._who}: the encoder's tensors do not form one 16-byte aligned range of its flat buffer ({lo}..{hi}, {other})")
+        return lo, hi - lo
+
+    def _new_encoder_state(self, value):
+        """a fresh optimiser-state buffer for the encoder's range (the reference builds a fresh optimiser over policy.parameters(): the
+        engine's flat_m / flat_v belong to the pre-training optimiser and are neither read nor written here); None without an encoder"""
+        return None if self._enc_range is None else torch.full((self._enc_range[1],), float(value), device=self.device)
+
+    def _segments(self, s0, s1, enc_s0, enc_s1):
+        """the two segments of one step, policy then encoder; the encoder's pointers are resolved from its engine at every step"""
+        eng, (lo, n) = self._encoder.engine, self._enc_range
+        if eng.device != self.device:
+            raise RuntimeError(f"{self._who}: the encoder lives on {eng.device}, the policy on {self.device}")
+        return _lib.flat_segments([(_lib.ptr(self.flat_p), _lib.ptr(self.flat_g), _lib.ptr(s0), _lib.ptr(s1), self.flat_p.numel()),
+                                   (_lib.ptr(eng.flat_p[lo:lo + n]), _lib.ptr(eng.flat_g[lo:lo + n]), _lib.ptr(enc_s0), _lib.ptr(enc_s1), n)])
+
+    def _check_encoder_state(self, opt, keys):
+        """load(): the checkpoint carries the encoder's optimiser state exactly when this policy has such an encoder, at its length"""
+        have = [k for k in keys if k in opt]
+        if self._enc_range is None:
+            if have:
+                raise ValueError(f"{self._who}.load: the checkpoint carries a trainable encoder's optimiser state ({', '.join(have)}), this policy "
+                                 "has no such encoder")
+            return
+        n = self._enc_range[1]
+        for k in keys:
+            if k not in opt or opt[k].numel() != n:
+                got = opt[k].numel() if k in opt else "no"
+                raise ValueError(f"{self._who}.load: the checkpoint's optimiser state has {got} {k} entries, this policy's encoder range {n}")
+
     def _init_adam(self):
-        """Adam's two moments beside flat_p, the step counter and the step's workspace"""
+        """Adam's two moments beside flat_p (and the encoder range's own), the step counter and the step's workspace"""
         self.flat_m, self.flat_v = (torch.zeros_like(self.flat_p) for _ in range(2))
+        self.enc_m, self.enc_v = self._new_encoder_state(0.0), self._new_encoder_state(0.0)
         self.adam_step = 0
-        self._ws = torch.empty(_lib.lib().ocrl_flat_clip_adam_ws_floats(), device=self.device)
+        L = _lib.lib()
+        self._ws = torch.empty(L.ocrl_flat_clip_adam_ws_floats() if self._encoder is None else L.ocrl_flat_clip_multi_ws_floats(), device=self.device)
 
     def _adam_step(self):
-        """L2 clip of the whole gradient to max_grad_norm, then Adam (eps 1e-5): one C call, no host synchronisation"""
+        """L2 clip of the whole gradient to max_grad_norm, then Adam (eps 1e-5): one C call, no host synchronisation.  With a trainable
+        encoder the norm is the joint one of the policy's and the encoder's gradients and the one call steps both segments."""
         self.adam_step += 1
         with torch.cuda.device(self.device):
+            if self._encoder is not None:
+                seg = self._segments(self.flat_m, self.flat_v, self.enc_m, self.enc_v)
+                _lib.check(_lib.lib().ocrl_flat_clip_adam_l2_multi(seg, len(seg), self.max_grad_norm, self.learning_rate, 0.9, 0.999, ADAM_EPS,
+                                                                   self.adam_step, _lib.ptr(self._norm), _lib.ptr(self._ws), self._ws.numel(),
+                                                                   _lib.stream(self.device)))
+                return
             _lib.check(_lib.lib().ocrl_flat_clip_adam_l2(_lib.ptr(self.flat_p), _lib.ptr(self.flat_g), _lib.ptr(self.flat_m), _lib.ptr(self.flat_v),
                                                          self.flat_p.numel(), self.max_grad_norm, self.learning_rate, 0.9, 0.999, ADAM_EPS,
                                                          self.adam_step, _lib.ptr(self._norm), _lib.ptr(self._ws), self._ws.numel(),
@@ -321,20 +388,30 @@ class OnPolicyAlgorithm:
         return {k: getattr(self, k) for k in self.HYPER + ("seed", "num_timesteps", "iteration")}
 
     def _adam_state(self):
-        return {"m": self.flat_m, "v": self.flat_v, "step": self.adam_step}
+        out = {"m": self.flat_m, "v": self.flat_v, "step": self.adam_step}
+        if self._encoder is not None:
+            out.update(enc_m=self.enc_m, enc_v=self.enc_v)
+        return out
 
     def _load_adam_state(self, opt):
         if "m" not in opt or opt["m"].shape != self.flat_m.shape:
             n = opt["m"].numel() if "m" in opt else "no"
             raise ValueError(f"{self._who}.load: the checkpoint's optimiser state has {n} Adam entries, this policy's {self.flat_m.numel()}")
+        self._check_encoder_state(opt, ("enc_m", "enc_v"))
         self.flat_m.copy_(opt["m"])
         self.flat_v.copy_(opt["v"])
+        if self._encoder is not None:
+            self.enc_m.copy_(opt["enc_m"])
+            self.enc_v.copy_(opt["enc_v"])
         self.adam_step = int(opt["step"])
 
     def save(self, path):
         opt = dict(self._optimizer_state())
         opt["sampling_rows"] = self.policy._sample_rows
-        torch.save({"algo": self.ALGO, "policy": self.policy.state_dict(), "optimizer": opt, "hyper": self._hyper()}, path)
+        if self._encoder is not None:
+            opt["enc_step_seed"] = self._encoder._step_seed          # where the encoder's slot-noise stream stands: a resumed run goes on from it
+        torch.save({"algo": self.ALGO, "policy": self.policy.state_dict(), "optimizer": opt, "hyper": self._hyper(),
+                    "generator": self.generator.get_state()}, path)     # where the minibatch permutations' stream stands
 
     def load(self, path):
         """restore policy, optimiser state and hyper-parameters saved by ``save`` into this instance (same algorithm and policy layout);
@@ -347,8 +424,13 @@ class OnPolicyAlgorithm:
         self._load_optimizer_state(ck["optimizer"])                     # checks the layout before anything is changed
         self.policy.load_state_dict(ck["policy"])                       # copies in place: the parameters stay views of flat_p
         self.policy._sample_rows = int(ck["optimizer"]["sampling_rows"])
+        if self._encoder is not None:
+            self._encoder._step_seed = int(ck["optimizer"].get("enc_step_seed", self._encoder._step_seed))
         for k, v in ck["hyper"].items():
             setattr(self, k, v)
+        if "generator" in ck:                                           # a resumed learn() draws the permutations and the actions the saved
+            self.generator.set_state(ck["generator"].cpu())             # run would have drawn next; older files leave both streams alone
+            self.policy._sample_seed = int(self.seed) & (2 ** 64 - 1)
         return self
 
 

@@ -1,8 +1,9 @@
 """PPO's update on the shared on-policy loop (on_policy.py: rollout buffer, rollout collection, the flat buffers, ``learn``).
 
 ``PPO`` restates stable-baselines3 1.5's ``PPO`` from the published algorithm (the footing of ``ppo_loss``): none of its text is copied.
-A minibatch is ``ppo_loss`` (one fused forward + backward) and the update ``ocrl_flat_clip_adam_l2`` on one flat parameter buffer.  Where
-this departs from stable-baselines3 is listed in DESIGN.md §7."""
+A minibatch is ``ppo_loss`` (one fused forward + backward) and the update ``ocrl_flat_clip_adam_l2`` on one flat parameter buffer; with a
+trainable SLATE encoder behind the extractor ``ocrl_flat_clip_adam_l2_multi`` on that buffer and the encoder's range of its engine's, under
+one joint norm (on_policy.py).  Where this departs from stable-baselines3 is listed in DESIGN.md §7."""
 import torch
 
 from .custom_acnets import PPO_SCALARS, CustomActorCriticPolicy, ppo_loss

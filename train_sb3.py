@@ -9,10 +9,11 @@ encoder and the algorithm with ``n_steps = max(1, sb3.algo_kwargs.n_steps // num
 ``max_steps``.  Whenever ``num_timesteps`` passes a multiple of ``eval.freq`` the policy plays ``eval.n_episodes`` episodes (sampled actions, as the reference's
 EvalCallback with deterministic=False) on a separate environment seeded ``seed + num_envs``.  ``run_dir`` receives metrics.jsonl (one line
 per iteration: the train() statistics, the rollout's episode window, and the evaluation when one ran) and checkpoints/model_latest.pth,
-model_best.pth (PPO.save / A2C.save).  No video and no wandb.  A SLATE / IODINE encoder needs its pre-trained checkpoint
-(pooling.ocr_checkpoint.local_file, no finetuning): PPO and A2C refuse to step such an encoder themselves; NatureCNN / MultipleCNN train
-from scratch.  ``ocr=gt`` is the ground-truth-state baseline: the environments hand out their state rows (render_mode: state) and no
-frame is rendered.
+model_best.pth (PPO.save / A2C.save).  No video and no wandb.  ``ocr=slate`` / ``ocr=slotattn`` without a checkpoint train the encoder
+end to end through the agent's loss, and with ``pooling.ocr_checkpoint.finetuning=True`` fine-tune a pre-trained one: PPO and A2C clip
+and step the encoder's slice together with the policy.  An IODINE encoder needs its pre-trained checkpoint
+(pooling.ocr_checkpoint.local_file, no finetuning); NatureCNN / MultipleCNN train from scratch.  ``ocr=gt`` is the ground-truth-state
+baseline: the environments hand out their state rows (render_mode: state) and no frame is rendered.
 """
 import json
 import logging
