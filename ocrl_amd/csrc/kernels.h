@@ -337,12 +337,6 @@ int embed_bwd_launch(float* g, const int* tokens, float* ddict, int B, int T, in
                      size_t ws_floats, hipStream_t st);
 int dropout_apply_launch(const float* x, float* y, long long n, float p, unsigned long long seed, unsigned site, hipStream_t st);
 int dropout_mask_launch(float* y, long long n, float p, unsigned long long seed, unsigned site, hipStream_t st);
-int cross_attn_fwd_launch(const float* Q, const float* Km, const float* Vm, float* O, float* P, int B, int T, int K, int d, int h, float p,
-                          unsigned long long seed, unsigned site, hipStream_t st);
-size_t cross_attn_bwd_ws_floats(int B, int T, int K, int d, int h);
-int cross_attn_bwd_launch(const float* dO, const float* Q, const float* Km, const float* Vm, const float* P, float* dQ, float* dKm, float* dVm,
-                          int B, int T, int K, int d, int h, float p, unsigned long long seed, unsigned site, float* part, size_t part_floats,
-                          hipStream_t st);
 int obs_u8_to_f32_launch(const unsigned char* in, float* out, int B, int H, int W, int C, hipStream_t st);
 int fill_launch(float* x, long long n, float v, hipStream_t st);
 int axpy_launch(const float* x, float* y, long long n, float a, hipStream_t st);
@@ -393,6 +387,13 @@ struct XaFoldBwdHost {                            // backward of the fold, after
     int B = 0, T = 0, K = 0, d = 0, h = 0;
 };
 int xattn_fold_bwd_launch(const XaFoldBwdHost& f, hipStream_t st);
+// the plain form: Q [B,T,d], Km / Vm [B,K,d], P [B,h,T,K] the probabilities before dropout
+int cross_attn_fwd_launch(const float* Q, const float* Km, const float* Vm, float* O, float* P, int B, int T, int K, int d, int h, float p,
+                          unsigned long long seed, unsigned site, hipStream_t st);
+size_t cross_attn_bwd_ws_floats(int B, int T, int K, int d, int h);
+int cross_attn_bwd_launch(const float* dO, const float* Q, const float* Km, const float* Vm, const float* P, float* dQ, float* dKm, float* dVm,
+                          int B, int T, int K, int d, int h, float p, unsigned long long seed, unsigned site, float* part, size_t part_floats,
+                          hipStream_t st);
 
 
 // ------------------------------------------------------------------ slot_attn.hip

@@ -94,12 +94,7 @@ void SlateModel::resolve_params() {
     w.enc_pos = ref_pair("_enc_pos.channels_map");
     w.sa.mu = ref("_slotattn.slot_mu"); w.sa.log_sigma = ref("_slotattn.slot_log_sigma");
     w.sa.ln = ref_pair("_slotattn.layer_norm"); w.sa.mlp0 = ref_pair("_slotattn.mlp.0"); w.sa.mlp2 = ref_pair("_slotattn.mlp.2");
-    const std::string sa = "_slotattn.slot_attention.";
-    w.sa.norm_inputs = ref_pair(sa + "norm_inputs"); w.sa.norm_slots = ref_pair(sa + "norm_slots"); w.sa.norm_mlp = ref_pair(sa + "norm_mlp");
-    w.sa.q = ref(sa + "project_q.weight"); w.sa.k = ref(sa + "project_k.weight"); w.sa.v = ref(sa + "project_v.weight");
-    w.sa.gru_wih = ref(sa + "gru.weight_ih"); w.sa.gru_whh = ref(sa + "gru.weight_hh");
-    w.sa.gru_bih = ref(sa + "gru.bias_ih"); w.sa.gru_bhh = ref(sa + "gru.bias_hh");
-    w.sa.m0 = ref_pair(sa + "mlp.0"); w.sa.m2 = ref_pair(sa + "mlp.2");
+    for (int i = 0; i < SA_NW; ++i) w.sa.w[i] = ref(std::string("_slotattn.slot_attention.") + SA_WEIGHT_NAMES[i]);
     w.slotproj = ref("_slotproj.weight");
     if (cfg.use_bcdec) {
         for (int i = 0; i < 4; ++i) w.bc[i] = ref_pair(fmt(i < 3 ? "_dec._decoder.%d.m" : "_dec._decoder.%d", i));
@@ -169,17 +164,15 @@ void SlateModel::layout_workspace(bool commit) {
     h1_ = carve("sa_mlp_hidden", BN * 64); x_ = carve("sa_inputs", BN * 64);
     slots0_ = carve("slots0", BK * D); slot_noise_ = carve(nullptr, BK * D); slots_ = carve("slots", BK * D);
     attn_ = carve("attn", BN * K);
-    attn_heads_ = SH > 1 ? carve(nullptr, BN * K * SH) : nullptr;
-    const SaSave so = sa_save_layout(C, D, H, SH);
-    const SaGrad go = sa_grad_layout(C, D, H, SH);
-    const SaWts wo = sa_wts_layout(C, D, H);
-    sa_save_ = carve("sa_save", BK * I * so.ld);
-    sa_grows_ = carve(nullptr, BK * I * go.ld);
-    sa_wts_ = carve(nullptr, wo.total);
-    sa_small_ = carve(nullptr, B * (4 * D + 2 * C));
-    sa_xchg_ = carve(nullptr, B * sa_xchg_floats_host(K * SH, D));
-    sa_parts_ = carve(nullptr, sa_parts_floats_host((int)B, K * SH));
-    sa_pack_dev_ = reinterpret_cast<PackEntry*>(carve(nullptr, 64 * sizeof(PackEntry) / 4 + 64));
+    attn_heads_ = SH > 1 ? carve(nullptr, sa_attn_heads_floats(B, N, K, SH)) : nullptr;
+    const SaSizes sz = sa_sizes(B, K, C, D, H, I, SH);
+    sa_save_ = carve("sa_save", sz.save);
+    sa_grows_ = carve(nullptr, sz.grows);
+    sa_wts_ = carve(nullptr, sz.wts);
+    sa_small_ = carve(nullptr, sz.small);
+    sa_xchg_ = carve(nullptr, sz.xchg);
+    sa_parts_ = carve(nullptr, sz.parts);
+    sa_pack_dev_ = reinterpret_cast<PackEntry*>(carve(nullptr, sz.table));
     for (int i = 0; i < 4; ++i) {
         const int cin = i == 0 ? 8 : 64;
         cw_fwd_[i] = carve(nullptr, (size_t)25 * cin * 64);
@@ -344,28 +337,11 @@ int SlateModel::bind(float* p, float* g, float* m, float* v, void* ws, size_t ws
     RC(posgrid_launch(gridT_, S, 0));
     RC(fill_launch(recon_, (long long)Bmax * N * 4, 0.f, 0));
     // slot-attention weight pack table
-    const SaWts wo = sa_wts_layout(C, D, H);
-    const SlotAttnW& sa = w_.sa;
-    std::vector<PackEntry> ent;
-    auto e = [&](ParamRef r, int rows, int cols, int off, int tr) {
-        PackEntry x; x.src = P(r); x.rows = rows; x.cols = cols; x.dst_off = off; x.transpose = tr;
-        ent.push_back(x);
-    };
-    e(sa.norm_inputs.w, 1, C, wo.ln_in_g, 0); e(sa.norm_inputs.b, 1, C, wo.ln_in_b, 0);
-    e(sa.norm_slots.w, 1, D, wo.ln_s_g, 0); e(sa.norm_slots.b, 1, D, wo.ln_s_b, 0);
-    e(sa.norm_mlp.w, 1, D, wo.ln_m_g, 0); e(sa.norm_mlp.b, 1, D, wo.ln_m_b, 0);
-    e(sa.q, D, D, wo.Wq, 2); e(sa.q, D, D, wo.WqT, 3);
-    e(sa.k, D, C, wo.Wk, 2); e(sa.k, D, C, wo.WkT, 3);
-    e(sa.v, D, C, wo.Wv, 2); e(sa.v, D, C, wo.WvT, 3);
-    e(sa.gru_wih, 3 * D, D, wo.Wih, 2); e(sa.gru_wih, 3 * D, D, wo.WihT, 3);
-    e(sa.gru_whh, 3 * D, D, wo.Whh, 2); e(sa.gru_whh, 3 * D, D, wo.WhhT, 3);
-    e(sa.gru_bih, 1, 3 * D, wo.bih, 0); e(sa.gru_bhh, 1, 3 * D, wo.bhh, 0);
-    e(sa.m0.w, H, D, wo.W0, 2); e(sa.m0.w, H, D, wo.W0T, 3); e(sa.m0.b, 1, H, wo.b0, 0);
-    e(sa.m2.w, D, H, wo.W2, 2); e(sa.m2.w, D, H, wo.W2T, 3); e(sa.m2.b, 1, D, wo.b2, 0);
-    sa_pack_n_ = (int)ent.size();
-    sa_pack_max_ = 3 * D * D;
-    OCRL_REQUIRE(sa_pack_n_ <= 64, "pack table overflow");
-    OCRL_HIP(hipMemcpy(sa_pack_dev_, ent.data(), ent.size() * sizeof(PackEntry), hipMemcpyHostToDevice));
+    const float* saw[SA_NW];
+    for (int i = 0; i < SA_NW; ++i) saw[i] = P(w_.sa.w[i]);
+    PackEntry ent[SA_PACK_ENTRIES];
+    sa_pack_n_ = sa_pack_table(saw, C, D, H, ent, &sa_pack_max_);
+    OCRL_HIP(hipMemcpy(sa_pack_dev_, ent, sa_pack_n_ * sizeof(PackEntry), hipMemcpyHostToDevice));
     OCRL_HIP(hipDeviceSynchronize());
     have_fwd_ = false;
     return 0;
@@ -446,8 +422,7 @@ int SlateModel::fwd_encoder(const StepInputs& in, const Lane& L, int fork_dvae) 
     // queue behind the Gumbel head's 32 768 small workgroups on the side stream (measured: 1.46 ms instead of 60 us, on the critical
     // path of the decoder)
     RC(slot_init_launch(P(w_.sa.mu), P(w_.sa.log_sigma), in.noise_slots, slots0_, B * K, D, in.seed, L, in.seed_dev));
-    SlotAttnArgs a;
-    a.B = B; a.N = N; a.C = C; a.K = K; a.D = D; a.H = H; a.I = I; a.NH = SH; a.eps = 1e-8f; a.scale = 1.0f / sqrtf((float)(D / SH));
+    SlotAttnArgs a = sa_args(B, N, K, D, H, I, SH);
     a.x = x_; a.slots0 = slots0_; a.wts = sa_wts_; a.slots = slots_; a.attn = attn_; a.attn_heads = attn_heads_; a.save = sa_save_;
     if (conv_lowlat_ && frozen_) a.save = nullptr;       // encode() of a frozen encoder: no backward can follow, the saved-activation rows are not written
     a.xchg = sa_xchg_; a.parts = sa_parts_;
@@ -735,20 +710,15 @@ int SlateModel::encode(const StepInputs& in, hipStream_t st) {
     return 0;
 }
 
-// SLATE_Module._gen_imgs (slate_module.py:163-179): greedy autoregressive token decode from the projected slots, then the dVAE
-// decoder.  The reference re-runs the whole decoder on the growing prefix for every token (O(T^2) decoder rows); the causal mask makes
-// the rows of earlier positions independent of later tokens, so here every step pushes ONE new row per image through the blocks and
-// attends to the keys / values of the earlier rows kept in the fused q|k|v buffer of each block (KV cache): T steps of B rows instead
-// of T passes of up to B*T rows.  Clobbers the decoder activations: no backward() afterwards.  metrics[4] = mse of the generated image.
-// Fine-tuning the encoder through a downstream loss (poolings/base.py:53-55, learn_downstream_loss: the slots reach the pooling head
-// undetached): d loss / d slots of the last encode() -> gradients of the CNN encoder, the positional embedding and the slot-attention
-// module.  Every other tensor of the flat gradient buffer is zero and is skipped by the next clip_adam(), as torch's Adam skips
-// parameters whose .grad is None.
 void SlateModel::clear_encode_graphs() {
     for (auto& kv : enc_graphs_) if (kv.second.exec) (void)hipGraphExecDestroy(kv.second.exec);
     enc_graphs_.clear();
 }
 
+// Fine-tuning the encoder through a downstream loss (poolings/base.py:53-55, learn_downstream_loss: the slots reach the pooling head
+// undetached): d loss / d slots of the last encode() -> gradients of the CNN encoder, the positional embedding and the slot-attention
+// module.  Every other tensor of the flat gradient buffer is zero and is skipped by the next clip_adam(), as torch's Adam skips
+// parameters whose .grad is None.
 int SlateModel::encode_backward(const float* dslots, hipStream_t st) {
     OCRL_REQUIRE(have_enc_, "encode_backward: call encode first (its activations are what is differentiated)");
     OCRL_REQUIRE(!frozen_, "encode_backward: the weights are frozen (ocrl_slate_freeze_weights): encode() kept no activations");
@@ -762,6 +732,11 @@ int SlateModel::encode_backward(const float* dslots, hipStream_t st) {
     return 0;
 }
 
+// SLATE_Module._gen_imgs (slate_module.py:163-179): greedy autoregressive token decode from the projected slots, then the dVAE
+// decoder.  The reference re-runs the whole decoder on the growing prefix for every token (O(T^2) decoder rows); the causal mask makes
+// the rows of earlier positions independent of later tokens, so here every step pushes ONE new row per image through the blocks and
+// attends to the keys / values of the earlier rows kept in the fused q|k|v buffer of each block (KV cache): T steps of B rows instead
+// of T passes of up to B*T rows.  Clobbers the decoder activations: no backward() afterwards.  metrics[4] = mse of the generated image.
 int SlateModel::generate(hipStream_t st) {
     OCRL_REQUIRE(!cfg.use_bcdec, "generate: the autoregressive decoder is not part of the use_bcdec configuration");
     OCRL_REQUIRE(last_.B > 0 && last_.obs, "generate: run forward or encode first");
@@ -925,11 +900,8 @@ int SlateModel::bwd_decoder(const Lane& L) {
 int SlateModel::bwd_encoder(const Lane& L, bool fork_dvae) {
     const int B = last_.B;
     const long long BN = (long long)B * N, R = (long long)B * I * K;
-    const SaSave so = sa_save_layout(C, D, H, SH);
-    const SaGrad go = sa_grad_layout(C, D, H, SH);
     const SlotAttnW& sa = w_.sa;
-    SlotAttnArgs a;
-    a.B = B; a.N = N; a.C = C; a.K = K; a.D = D; a.H = H; a.I = I; a.NH = SH; a.eps = 1e-8f; a.scale = 1.0f / sqrtf((float)(D / SH));
+    SlotAttnArgs a = sa_args(B, N, K, D, H, I, SH);
     a.x = x_; a.wts = sa_wts_; a.save = sa_save_; a.dslots = gslots_; a.dx = gA_; a.dslots0 = gslots0_; a.grows = sa_grows_; a.g_small = sa_small_;
     a.xchg = sa_xchg_; a.parts = sa_parts_;
     if (fork_dvae) {
@@ -945,20 +917,20 @@ int SlateModel::bwd_encoder(const Lane& L, bool fork_dvae) {
     const Lane W = side_w ? dvae_lane() : L;
     if (side_w) RC(after(W, L, ev_fork_));
     const bool sa_in_bwd = sa_input_ == 1 && C == 64;          // the input LayerNorm + MLP backward as one kernel on the main stream
-    // weight gradients: contract the emitted gradient rows with the saved activations over (image, iteration, slot)
-    RC(lin_bwd_w(sa_grows_ + go.out, go.ld, sa_save_ + so.hid, so.ld, G(sa.m2.w), G(sa.m2.b), R, D, H, 1.f, W));
-    RC(lin_bwd_w(sa_grows_ + go.hid, go.ld, sa_save_ + so.m, so.ld, G(sa.m0.w), G(sa.m0.b), R, H, D, 1.f, W));
-    RC(lin_bwd_w(sa_grows_ + go.gi, go.ld, sa_save_ + so.u, so.ld, G(sa.gru_wih), G(sa.gru_bih), R, 3 * D, D, 1.f, W));
-    RC(lin_bwd_w(sa_grows_ + go.gh, go.ld, sa_save_ + so.sprev, so.ld, G(sa.gru_whh), G(sa.gru_bhh), R, 3 * D, D, 1.f, W));
-    RC(lin_bwd_w(sa_grows_ + go.q, go.ld, sa_save_ + so.sn, so.ld, G(sa.q), nullptr, R, D, D, 1.f, W));
-    for (int h = 0, dh = D / SH; h < SH; ++h) {       // rows of head h of project_v / project_k meet that head's weighted means / folded-query gradients
-        RC(lin_bwd_w(sa_grows_ + go.u + h * dh, go.ld, sa_save_ + so.up + h * C, so.ld, G(sa.v) + (size_t)h * dh * C, nullptr, R, dh, C, 1.f, W));
-        RC(lin_bwd_w(sa_save_ + so.q + h * dh, so.ld, sa_grows_ + go.qp + h * C, go.ld, G(sa.k) + (size_t)h * dh * C, nullptr, R, dh, C, a.scale, W));
+    // weight gradients: contract the emitted gradient rows with the saved activations over (image, iteration, slot), the bias gradient
+    // out of the same product
+    SaWgrad wg[SA_MAX_WGRADS];
+    const int nwg = sa_wgrad_list(C, D, H, SH, a.scale, wg);
+    for (int i = 0; i < nwg; ++i) {
+        const SaWgrad& e = wg[i];
+        RC(lin_bwd_w(e.dy.at(sa_save_, sa_grows_), e.dy.ld, e.x.at(sa_save_, sa_grows_), e.x.ld, G(sa.w[e.w]) + e.w_off,
+                     e.b < 0 ? nullptr : G(sa.w[e.b]), R, e.N_out, e.K_in, e.alpha, W));
     }
+    // LayerNorm gammas / betas: weight and bias are adjacent in the flat buffer, one column sum over each pair
     const int SM = 4 * D + 2 * C;
-    RC(colsum_launch(sa_small_ + 0, SM, G(sa.norm_slots.w), B, 2 * D, 0, 1.f, W.scratch, W.scratch_floats, W));
-    RC(colsum_launch(sa_small_ + 2 * D, SM, G(sa.norm_mlp.w), B, 2 * D, 0, 1.f, W.scratch, W.scratch_floats, W));
-    RC(colsum_launch(sa_small_ + 4 * D, SM, G(sa.norm_inputs.w), B, 2 * C, 0, 1.f, W.scratch, W.scratch_floats, W));
+    RC(colsum_launch(sa_small_ + 0, SM, G(sa.w[SAW_NORM_SLOTS_W]), B, 2 * D, 0, 1.f, W.scratch, W.scratch_floats, W));
+    RC(colsum_launch(sa_small_ + 2 * D, SM, G(sa.w[SAW_NORM_MLP_W]), B, 2 * D, 0, 1.f, W.scratch, W.scratch_floats, W));
+    RC(colsum_launch(sa_small_ + 4 * D, SM, G(sa.w[SAW_NORM_INPUTS_W]), B, 2 * C, 0, 1.f, W.scratch, W.scratch_floats, W));
     RC(slot_init_bwd_launch(gslots0_, P(w_.sa.log_sigma), last_.noise_slots, G(w_.sa.mu), G(w_.sa.log_sigma),
                             B * K, D, last_.seed, W));
     // ---- input MLP: x = W2 relu(W0 LN(e4) + b0) + b2 ; gA = dx

@@ -7,6 +7,7 @@
 
 #include "kernels.h"
 #include "model_base.h"
+#include "slot_attn_host.h"
 
 struct SlateConfig {
     int obs_size = 64, obs_channels = 3, vocab = 4096, d_model = 192, cnn_hidden = 64;
@@ -115,8 +116,9 @@ private:
     // ---- parameters, resolved once by the constructor (resolve_params)
     struct DecBlockW { ParamPair ln1, ln2, ln3, ffn0, ffn2; ParamRef qkv, o, cq, ck, cv, co; };     // qkv: proj_q, with proj_k / proj_v behind it
     struct SlotAttnW {
-        ParamRef mu, log_sigma, q, k, v, gru_wih, gru_whh, gru_bih, gru_bhh;
-        ParamPair ln, mlp0, mlp2, norm_inputs, norm_slots, norm_mlp, m0, m2;          // ln / mlp0 / mlp2: the input LayerNorm + MLP
+        ParamRef mu, log_sigma;
+        ParamPair ln, mlp0, mlp2;          // the input LayerNorm + MLP
+        ParamRef w[SA_NW];                 // the slot-attention module's own weights, by SaWeight (slot_attn_host.h)
     };
     struct Weights {
         ParamPair dvae_enc[8], dvae_dec[12];       // by the reference's Sequential index (decoder 5 and 10 are pixel shuffles)
@@ -161,7 +163,7 @@ private:
     float *slots0_, *slot_noise_, *slots_, *attn_, *sa_save_, *sa_wts_, *sa_grows_, *sa_small_, *sa_xchg_;
     float* attn_heads_ = nullptr;         // [B,N,SH*K] per-head attention maps (SH > 1 only)
     float* sa_parts_;
-    PackEntry* sa_pack_dev_ = nullptr;
+    PackEntry* sa_pack_dev_ = nullptr;    // sa_pack_table on the device
     int sa_pack_n_ = 0, sa_pack_max_ = 0;
     float *cw_fwd_[4], *cw_bwd_[4];       // CNN encoder conv packs
     int conv_x3_ = -1;                    // OCRL_CONV_X3=1 (exploratory): the 5x5 / 64-channel layers on the split-precision bf16 kernel

@@ -14,6 +14,9 @@
 // (scores^T = A^T x^T: accumulator lane = (token li, column group g'), register r = column 16 tt + 4 g' + r) a head is two (KP = 8)
 // or four (KP = 16) consecutive 4-column groups of one 16-column tile: its soft-max is in-lane arithmetic plus one or two cross-row
 // exchanges (v_permlane16/32_swap), and the probabilities are already the B operand of the second product.
+//
+// The plain form (cross_attn_*: the attention alone, between the callers' projections) is at the end of the file: generate() runs
+// it one query row at a time, training with OCRL_XATTN=0 or at a shape the fold does not support.
 #include "common.h"
 #include "kernels.h"
 
@@ -535,4 +538,327 @@ int xattn_fold_bwd_launch(const XaFoldBwdHost& f, hipStream_t st) {
     RC(colsum_launch(f.pq, (long long)d * d, f.dWq, B, d * d, 0, 1.f, f.ws, f.ws_floats, st));
     RC(colsum_launch(f.po, (long long)d * d, f.dWo, B, d * d, 0, 1.f, f.ws, f.ws_floats, st));
     return 0;
+}
+
+// =========================================================================================== the plain form (OCRL_XATTN=0, generate())
+// ------------------------------------------------------------------ cross attention to K (<= 16) slots
+// Q [B,T,d] (projected, unscaled), Km/Vm [B,K,d], heads h, dh = d/h (<= 64).  One thread per (b,head,q).
+// P [B,h,T,K] = softmax (pre-dropout) is saved for the backward.
+// MAXK (8 or 16) is the compile-time slot capacity: per-slot values live in registers.
+#define CA_MAXDH 64
+template <int CA_MAXK>
+__global__ __launch_bounds__(256) void cross_attn_fwd_kernel(const float* __restrict__ Q, const float* __restrict__ Km,
+                                                             const float* __restrict__ Vm, float* __restrict__ O,
+                                                             float* __restrict__ P, int T, int K, int d, int h, float p,
+                                                             unsigned long long seed, unsigned site) {
+    extern __shared__ float sm[];   // Ks [K][dh], Vs [K][dh]
+    const int dh = d / h;
+    const int nqb = (T + 255) / 256;
+    int bid = blockIdx.x;
+    const int qb = bid % nqb; bid /= nqb;
+    const int hd = bid % h;
+    const long long b = bid / h;
+    float* Ks = sm;
+    float* Vs = sm + K * dh;
+    for (int i = threadIdx.x; i < K * dh; i += 256) {
+        const int k = i / dh, c = i % dh;
+        Ks[i] = Km[(b * K + k) * d + hd * dh + c];
+        Vs[i] = Vm[(b * K + k) * d + hd * dh + c];
+    }
+    __syncthreads();
+    const int q = qb * 256 + threadIdx.x;
+    if (q >= T) return;
+    const float scale = rsqrtf((float)dh);
+    float qv[CA_MAXDH];
+    const float* qp = Q + (b * T + q) * d + hd * dh;
+#pragma unroll
+    for (int c = 0; c < CA_MAXDH; c += 4)
+        if (c < dh) {
+            const float4 v = *reinterpret_cast<const float4*>(qp + c);
+            qv[c] = v.x * scale; qv[c + 1] = v.y * scale; qv[c + 2] = v.z * scale; qv[c + 3] = v.w * scale;
+        }
+    float s[CA_MAXK];
+    float mx = -INFINITY;
+#pragma unroll
+    for (int k = 0; k < CA_MAXK; ++k)
+        if (k < K) {
+            float a = 0.f;
+#pragma unroll
+            for (int c = 0; c < CA_MAXDH; c += 4)              // broadcast ds_read_b128: a quarter of the LDS instructions
+                if (c < dh) {
+                    const float4 k4 = *reinterpret_cast<const float4*>(Ks + k * dh + c);
+                    a += (qv[c] * k4.x + qv[c + 1] * k4.y) + (qv[c + 2] * k4.z + qv[c + 3] * k4.w);
+                }
+            s[k] = a;
+            mx = fmaxf(mx, a);
+        }
+    float sum = 0.f;
+#pragma unroll
+    for (int k = 0; k < CA_MAXK; ++k)
+        if (k < K) { s[k] = __expf(s[k] - mx); sum += s[k]; }
+    const float inv = 1.0f / sum;
+    const uint32_t thr = drop_thresh(p);
+    const float sc = p > 0.f ? 1.0f / (1.0f - p) : 1.f;
+    const long long prow = ((b * h + hd) * T + q) * K;
+    float o[CA_MAXDH];
+#pragma unroll
+    for (int c = 0; c < CA_MAXDH; ++c) o[c] = 0.f;
+#pragma unroll
+    for (int k = 0; k < CA_MAXK; ++k)
+        if (k < K) {
+            const float pr = s[k] * inv;
+            P[prow + k] = pr;
+            float pd = pr;
+            if (p > 0.f) {
+                const uint64_t idx = (uint64_t)prow + k;
+                pd = rng_keep(rng_bits4(seed, site, idx >> 2), (int)(idx & 3), thr) ? pr * sc : 0.f;
+            }
+#pragma unroll
+            for (int c = 0; c < CA_MAXDH; c += 4)
+                if (c < dh) {
+                    const float4 v4 = *reinterpret_cast<const float4*>(Vs + k * dh + c);
+                    o[c] += pd * v4.x; o[c + 1] += pd * v4.y; o[c + 2] += pd * v4.z; o[c + 3] += pd * v4.w;
+                }
+        }
+    float* op = O + (b * T + q) * d + hd * dh;
+#pragma unroll
+    for (int c = 0; c < CA_MAXDH; c += 4)
+        if (c < dh) *reinterpret_cast<float4*>(op + c) = make_float4(o[c], o[c + 1], o[c + 2], o[c + 3]);
+}
+
+// backward: dQ [B,T,d] written; the slot-side gradients leave each workgroup as one partial [2][K*dh] (dV, dK) in `part`,
+// summed over the query blocks in a fixed order by cross_attn_reduce_kernel (no float atomics: bitwise reproducible).  The
+// per-query outer products are reduced over the 64 queries of a wave through a wave-private LDS staging tile (queries x (K + dh)),
+// then over the four waves through LDS.
+template <int CA_MAXK>
+__global__ __launch_bounds__(256) void cross_attn_bwd_kernel(const float* __restrict__ dO, const float* __restrict__ Q,
+                                                             const float* __restrict__ Km, const float* __restrict__ Vm,
+                                                             const float* __restrict__ P, float* __restrict__ dQ,
+                                                             float* __restrict__ part, int T, int K, int d,
+                                                             int h, float p, unsigned long long seed, unsigned site) {
+    extern __shared__ float sm[];   // Ks [K][dh], Vs [K][dh], stage [4][64][CA_SW]
+    constexpr int CA_SW = CA_MAXK + CA_MAXDH + 1;
+    float* mypart = part + (size_t)blockIdx.x * 2 * K * (d / h);
+    const int dh = d / h;
+    const int nqb = (T + 255) / 256;
+    int bid = blockIdx.x;
+    const int qb = bid % nqb; bid /= nqb;
+    const int hd = bid % h;
+    const long long b = bid / h;
+    float* Ks = sm;
+    float* Vs = sm + K * dh;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    float* stg = sm + 2 * K * dh + wv * 64 * CA_SW;      // this wave's staging tile
+    for (int i = threadIdx.x; i < K * dh; i += 256) {
+        const int k = i / dh, c = i % dh;
+        Ks[i] = Km[(b * K + k) * d + hd * dh + c];
+        Vs[i] = Vm[(b * K + k) * d + hd * dh + c];
+    }
+    __syncthreads();
+    const int q = qb * 256 + threadIdx.x;
+    const bool act = q < T;
+    const float scale = rsqrtf((float)dh);
+    // The wave's 64 query rows of dO (and later of Q) are fetched as one coalesced tile (consecutive lanes = consecutive 16 bytes of a
+    // row) straight into the staging tile the matrix products read; a thread then takes its own row from LDS.  Thread-per-row global
+    // loads (64 different cache lines per instruction) were what bound this kernel.
+    const int q0 = qb * 256 + wv * 64, dh4 = dh >> 2;
+    // All dh/4 loads of a lane are issued before the first LDS store (a rolled load -> store loop paid one memory round trip per
+    // 16 bytes: 2 x 12 round trips per workgroup, with two workgroups per CU to hide them).  (row, chunk) advance without divisions.
+    const int r_step = 64 / dh4, c_step = 64 - r_step * dh4;
+    auto load_tile = [&](const float* src, float mul) {
+        float4 tmp[CA_MAXDH / 4];
+        int r = lane / dh4, c4 = lane - r * dh4;
+#pragma unroll
+        for (int i = 0; i < CA_MAXDH / 4; ++i) {
+            tmp[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (i < dh4 && q0 + r < T) tmp[i] = *reinterpret_cast<const float4*>(src + (b * T + q0 + r) * d + hd * dh + 4 * c4);
+            r += r_step; c4 += c_step;
+            if (c4 >= dh4) { c4 -= dh4; ++r; }
+        }
+        r = lane / dh4; c4 = lane - r * dh4;
+#pragma unroll
+        for (int i = 0; i < CA_MAXDH / 4; ++i) {
+            if (i < dh4) {
+                float* dst = stg + r * CA_SW + CA_MAXK + 4 * c4;
+                dst[0] = tmp[i].x * mul; dst[1] = tmp[i].y * mul; dst[2] = tmp[i].z * mul; dst[3] = tmp[i].w * mul;
+            }
+            r += r_step; c4 += c_step;
+            if (c4 >= dh4) { c4 -= dh4; ++r; }
+        }
+        __builtin_amdgcn_wave_barrier();
+    };
+    load_tile(dO, 1.f);
+    float go[CA_MAXDH];
+    float pr[CA_MAXK], dp[CA_MAXK], keepv[CA_MAXK];
+#pragma unroll
+    for (int c = 0; c < CA_MAXDH; ++c) go[c] = c < dh ? stg[lane * CA_SW + CA_MAXK + c] : 0.f;
+#pragma unroll
+    for (int k = 0; k < CA_MAXK; ++k) { pr[k] = 0.f; dp[k] = 0.f; keepv[k] = 0.f; }
+    float delta = 0.f;
+    if (act) {
+        const uint32_t thr = drop_thresh(p);
+        const float sc = p > 0.f ? 1.0f / (1.0f - p) : 1.f;
+        const long long prow = ((b * h + hd) * T + q) * K;
+#pragma unroll
+        for (int k = 0; k < CA_MAXK; ++k)
+            if (k < K) {
+                pr[k] = P[prow + k];
+                float keep = 1.f;
+                if (p > 0.f) {
+                    const uint64_t idx = (uint64_t)prow + k;
+                    keep = rng_keep(rng_bits4(seed, site, idx >> 2), (int)(idx & 3), thr) ? sc : 0.f;
+                }
+                keepv[k] = keep;
+                float a = 0.f;
+#pragma unroll
+                for (int c = 0; c < CA_MAXDH; c += 4)          // one broadcast ds_read_b128 per four channels (the per-channel form waited on 576 LDS reads per query)
+                    if (c < dh) {
+                        const float4 v4 = *reinterpret_cast<const float4*>(Vs + k * dh + c);
+                        a += (go[c] * v4.x + go[c + 1] * v4.y) + (go[c + 2] * v4.z + go[c + 3] * v4.w);
+                    }
+                dp[k] = a * keep;
+                delta += pr[k] * dp[k];
+            }
+    }
+    // ---- dV[k][c] += sum_q pd[q][k] * go[q][c]      (go is already in the staging tile)
+#pragma unroll
+    for (int k = 0; k < CA_MAXK; ++k) stg[lane * CA_SW + k] = pr[k] * keepv[k];
+    __syncthreads();
+    // [slots x 64 queries] . [64 queries x dh] on the matrix cores: slots on the 16 MFMA rows, 16-channel tiles on the columns, four
+    // queries per v_mfma_f32_16x16x4_f32 (lane (li, g): A = stage[query 4s+g][slot li], B = stage[query 4s+g][channel 16m+li])
+    const int li = lane & 15, g4 = lane >> 4, nmt = (dh + 15) >> 4;
+    f32x4 acc[CA_MAXDH / 16];
+#pragma unroll
+    for (int m = 0; m < CA_MAXDH / 16; ++m) acc[m] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll 4
+    for (int s16 = 0; s16 < 16; ++s16) {
+        const float* rowp = stg + (4 * s16 + g4) * CA_SW;
+        const float a = li < CA_MAXK ? rowp[li] : 0.f;
+#pragma unroll
+        for (int m = 0; m < CA_MAXDH / 16; ++m)
+            if (m < nmt) acc[m] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, rowp[CA_MAXK + 16 * m + li], acc[m], 0, 0, 0);
+    }
+    __syncthreads();                                       // every wave is done reading its staging tile
+#pragma unroll
+    for (int m = 0; m < CA_MAXDH / 16; ++m)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int k = 4 * g4 + r, c = 16 * m + li;
+            if (m < nmt && k < K && c < dh) stg[k * dh + c] = acc[m][r];
+        }
+    __syncthreads();
+    for (int o = threadIdx.x; o < K * dh; o += 256) {
+        const float* r = sm + 2 * K * dh + o;
+        mypart[o] = (r[0] + r[64 * CA_SW]) + (r[2 * 64 * CA_SW] + r[3 * 64 * CA_SW]);
+    }
+    __syncthreads();
+    // ---- dS, dQ, and dK[k][c] += sum_q ds[q][k] * q'[q][c]
+    float dq[CA_MAXDH];
+#pragma unroll
+    for (int c = 0; c < CA_MAXDH; ++c) dq[c] = 0.f;
+#pragma unroll
+    for (int k = 0; k < CA_MAXK; ++k) {
+        const float ds = (k < K) ? pr[k] * (dp[k] - delta) : 0.f;
+        stg[lane * CA_SW + k] = ds;
+        if (k < K) {
+#pragma unroll
+            for (int c = 0; c < CA_MAXDH; c += 4)
+                if (c < dh) {
+                    const float4 k4 = *reinterpret_cast<const float4*>(Ks + k * dh + c);
+                    dq[c] += ds * k4.x; dq[c + 1] += ds * k4.y; dq[c + 2] += ds * k4.z; dq[c + 3] += ds * k4.w;
+                }
+        }
+    }
+    load_tile(Q, scale);                                   // q' = scale * q of the wave's rows, straight into the staging tile
+    __syncthreads();
+#pragma unroll
+    for (int m = 0; m < CA_MAXDH / 16; ++m) acc[m] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll 4
+    for (int s16 = 0; s16 < 16; ++s16) {
+        const float* rowp = stg + (4 * s16 + g4) * CA_SW;
+        const float a = li < CA_MAXK ? rowp[li] : 0.f;
+#pragma unroll
+        for (int m = 0; m < CA_MAXDH / 16; ++m)
+            if (m < nmt) acc[m] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, rowp[CA_MAXK + 16 * m + li], acc[m], 0, 0, 0);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int m = 0; m < CA_MAXDH / 16; ++m)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int k = 4 * g4 + r, c = 16 * m + li;
+            if (m < nmt && k < K && c < dh) stg[k * dh + c] = acc[m][r];
+        }
+    __syncthreads();
+    for (int o = threadIdx.x; o < K * dh; o += 256) {
+        const float* r = sm + 2 * K * dh + o;
+        mypart[K * dh + o] = (r[0] + r[64 * CA_SW]) + (r[2 * 64 * CA_SW] + r[3 * 64 * CA_SW]);
+    }
+    __syncthreads();                                       // the partials are out: the staging tile carries dQ to a coalesced store
+#pragma unroll
+    for (int c = 0; c < CA_MAXDH; ++c)
+        if (c < dh) stg[lane * CA_SW + CA_MAXK + c] = dq[c] * scale;
+    __builtin_amdgcn_wave_barrier();
+    for (int idx = lane; idx < 64 * dh4; idx += 64) {
+        const int r = idx / dh4, c4 = idx - r * dh4;
+        if (q0 + r < T) {
+            const float* src = stg + r * CA_SW + CA_MAXK + 4 * c4;
+            *reinterpret_cast<float4*>(dQ + (b * T + q0 + r) * d + hd * dh + 4 * c4) = make_float4(src[0], src[1], src[2], src[3]);
+        }
+    }
+}
+
+int cross_attn_fwd_launch(const float* Q, const float* Km, const float* Vm, float* O, float* P, int B, int T, int K, int d, int h, float p,
+                          unsigned long long seed, unsigned site, hipStream_t st) {
+    OCRL_REQUIRE(K >= 1 && K <= 16 && d % h == 0 && (d / h) <= CA_MAXDH && (d / h) % 4 == 0, "cross_attn: unsupported K=%d d=%d h=%d", K, d, h);
+    const int grid = B * h * cdiv(T, 256);
+    if (K <= 8) hipLaunchKernelGGL(cross_attn_fwd_kernel<8>, dim3(grid), dim3(256), 2 * K * (d / h) * 4, st, Q, Km, Vm, O, P, T, K, d, h, p, seed, site);
+    else hipLaunchKernelGGL(cross_attn_fwd_kernel<16>, dim3(grid), dim3(256), 2 * K * (d / h) * 4, st, Q, Km, Vm, O, P, T, K, d, h, p, seed, site);
+    OCRL_CHECK_LAUNCH("cross_attn_fwd");
+    return 0;
+}
+// dKm / dVm [B,K,d] = sum over the query blocks of the per-workgroup partials, in block order
+__global__ void cross_attn_reduce_kernel(const float* __restrict__ part, float* __restrict__ dKm, float* __restrict__ dVm, long long n, int nqb,
+                                         int K, int d, int h) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;      // over [B][K][d]
+    if (i >= n) return;
+    const int dh = d / h;
+    const int col = i % d, k = (i / d) % K;
+    const long long b = i / ((long long)d * K);
+    const int hd = col / dh, c = col - hd * dh;
+    const float* src = part + ((b * h + hd) * nqb) * 2 * K * dh + k * dh + c;
+    float av = 0.f, ak = 0.f;
+    for (int q = 0; q < nqb; ++q) { av += src[(size_t)q * 2 * K * dh]; ak += src[(size_t)q * 2 * K * dh + K * dh]; }
+    dVm[i] = av;
+    dKm[i] = ak;
+}
+
+size_t cross_attn_bwd_ws_floats(int B, int T, int K, int d, int h) { return (size_t)B * h * cdiv(T, 256) * 2 * K * (d / h); }
+
+template <int MAXK>
+static int cross_attn_bwd_launch_k(const float* dO, const float* Q, const float* Km, const float* Vm, const float* P, float* dQ, float* dKm, float* dVm,
+                                   int B, int T, int K, int d, int h, float p, unsigned long long seed, unsigned site, float* part, hipStream_t st) {
+    constexpr int SW = MAXK + CA_MAXDH + 1;
+    const int grid = B * h * cdiv(T, 256);
+    static bool attr_set = false;
+    if (!attr_set) {
+        OCRL_HIP(hipFuncSetAttribute((const void*)cross_attn_bwd_kernel<MAXK>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                     (2 * MAXK * CA_MAXDH + 4 * 64 * SW) * 4));
+        attr_set = true;
+    }
+    hipLaunchKernelGGL(cross_attn_bwd_kernel<MAXK>, dim3(grid), dim3(256), (2 * K * (d / h) + 4 * 64 * SW) * 4, st, dO, Q, Km, Vm, P, dQ, part, T, K, d, h, p, seed, site);
+    OCRL_CHECK_LAUNCH("cross_attn_bwd");
+    const long long n = (long long)B * K * d;
+    hipLaunchKernelGGL(cross_attn_reduce_kernel, GRID1D(n), 0, st, part, dKm, dVm, n, cdiv(T, 256), K, d, h);
+    OCRL_CHECK_LAUNCH("cross_attn_reduce");
+    return 0;
+}
+// dKm / dVm are written (not accumulated); part: cross_attn_bwd_ws_floats() floats of scratch
+int cross_attn_bwd_launch(const float* dO, const float* Q, const float* Km, const float* Vm, const float* P, float* dQ, float* dKm, float* dVm,
+                          int B, int T, int K, int d, int h, float p, unsigned long long seed, unsigned site, float* part, size_t part_floats,
+                          hipStream_t st) {
+    OCRL_REQUIRE(K >= 1 && K <= 16 && d % h == 0 && (d / h) <= CA_MAXDH && (d / h) % 4 == 0, "cross_attn: unsupported K=%d d=%d h=%d", K, d, h);
+    OCRL_REQUIRE(part && part_floats >= cross_attn_bwd_ws_floats(B, T, K, d, h), "cross_attn_bwd: scratch too small");
+    if (K <= 8) return cross_attn_bwd_launch_k<8>(dO, Q, Km, Vm, P, dQ, dKm, dVm, B, T, K, d, h, p, seed, site, part, st);
+    return cross_attn_bwd_launch_k<16>(dO, Q, Km, Vm, P, dQ, dKm, dVm, B, T, K, d, h, p, seed, site, part, st);
 }

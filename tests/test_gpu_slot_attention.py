@@ -121,6 +121,36 @@ def test_image_independence(K):
                 f"K {K}: {k} of image {b} differs between the batch of {c.B} and the image alone by {float((one[k][0] - base[k][b]).abs().max()):.2e}"
 
 
+# ---- the unit entry point against the model: one host description of the module (csrc/slot_attn_host.h) behind both
+@pytest.mark.parametrize("name", ["SMALL", "K11", "HEADS2"])      # one group form, the uneven two-block split, two heads
+def test_unit_entry_equals_the_model(name):
+    """the engine's encode(), then ocrl_slot_attention_mh_fwd on the model's own sa_inputs / slots0 and its 17 weights: the same pack
+    table, arguments and kernels (the model only issues the preparation launch ahead of the rest), so slots and attn are equal bit for bit"""
+    from oracle import slate_oracle as O
+    from ocrl_amd import _lib
+    from tests import test_gpu_slate as S
+    from tests.gpu_util import load_params
+    cfg = O.default_cfg(**getattr(S, name))
+    B, N, K, D, H, I, NH = 3, cfg.obs_size ** 2, cfg.num_slots, cfg.slot_size, cfg.mlp_hidden, cfg.num_iterations, int(getattr(cfg, "num_slot_heads", 1))
+    eng = S.make_engine(cfg, B)
+    load_params(eng, O.formula_params(cfg))
+    eng.encode(torch.rand(B, 3, cfg.obs_size, cfg.obs_size, generator=torch.Generator().manual_seed(11)).cuda(), seed=7)
+    torch.cuda.synchronize()
+    x, s0 = eng.tensor("sa_inputs", (B, N, R.C)), eng.tensor("slots0", (B, K, D))
+    w = [eng.param(R.PRE + n) for n in R.NAMES]
+    assert [tuple(t.shape) for t in w] == R.shapes(D, H)
+    L, p = _lib.lib(), _lib.ptr
+    nan = lambda *shp: torch.full(shp, float("nan"), device="cuda")
+    slots, attn = nan(B, K, D), nan(B, N, K)
+    nws = L.ocrl_slot_attention_mh_ws_floats(B, N, K, D, H, I, NH)
+    ws = nan(nws)
+    _lib.check(L.ocrl_slot_attention_mh_fwd(p(x), p(s0), _lib.ptrs(w), p(slots), p(attn), B, N, K, D, H, I, NH, p(ws), nws, None))
+    torch.cuda.synchronize()
+    for k, got, want in (("slots", slots, eng.tensor("slots", (B, K, D))), ("attn", attn, eng.tensor("attn", (B, N, K)))):
+        log(f"[slot_attention unit == model {name}] {k} max |difference| {float((got - want).abs().max()):.2e}")
+        assert torch.equal(got, want), f"{name}: {k} of the unit entry point differs from the model's"
+
+
 # ---- the development forms, one fresh process each (the knobs are read once per process)
 SETTINGS = [("fwd1-bwd1", dict(OCRL_SA_FWD="1", OCRL_SA_BWD="1")), ("group0", dict(OCRL_SA_GROUP="0"))]
 
