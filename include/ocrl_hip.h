@@ -230,6 +230,16 @@ int ocrl_attention_fwd(const float* q, const float* k, const float* v, float* o,
 int ocrl_attention_bwd(const float* q, const float* k, const float* v, const float* o, const float* lse, const float* dO,
                        float* dq, float* dk, float* dv, float* delta, int B, int T, int d, int h, int ld,
                        float p, unsigned long long seed, unsigned site, void* stream);
+/* The same backward with a dS workspace (hand-off form: the dK/dV kernel stores the score gradients it forms, the dQ kernel is the one
+ * product dS K that reads them; dk and dv are bit for bit those of ocrl_attention_bwd's two-kernel form).  ds is uninitialised scratch,
+ * 16-byte aligned; ocrl_attention_bwd_ds_floats(B, T, h) floats hold the whole batch, a smaller ds_floats makes the call walk the batch
+ * in chunks of floor(ds_floats / ocrl_attention_bwd_ds_floats(1, T, h)) images with the same results, and with room for less than one
+ * image (or ds null) the call is ocrl_attention_bwd's two-kernel form.  OCRL_ATTN_BWD unset or 3 runs this form; 1 and 2 keep their
+ * meanings (the one-pass and the two-kernel form). */
+size_t ocrl_attention_bwd_ds_floats(int B, int T, int h);
+int ocrl_attention_bwd_ws(const float* q, const float* k, const float* v, const float* o, const float* lse, const float* dO,
+                          float* dq, float* dk, float* dv, float* delta, int B, int T, int d, int h, int ld,
+                          float p, unsigned long long seed, unsigned site, float* ds, size_t ds_floats, void* stream);
 
 /* ---- Cross attention of a decoder block to the K projected slots (MultiHeadAttention.forward, ocrs/common/transformer.py:23-50, as
  * TransformerDecoderBlock.forward :181-185 calls it with k = v = the slot memory), in the two forms the decoder runs.

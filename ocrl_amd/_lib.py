@@ -209,6 +209,9 @@ def lib():
     L.ocrl_sa_input_bwd.argtypes = [p] * 16 + [c_longlong, c_int, p, c_size_t, p]
     L.ocrl_attention_fwd.argtypes = [p, p, p, p, p, c_int, c_int, c_int, c_int, c_int, c_float, c_ulonglong, c_uint, p]
     L.ocrl_attention_bwd.argtypes = [p, p, p, p, p, p, p, p, p, p, c_int, c_int, c_int, c_int, c_int, c_float, c_ulonglong, c_uint, p]
+    L.ocrl_attention_bwd_ds_floats.argtypes = [c_int, c_int, c_int]
+    L.ocrl_attention_bwd_ds_floats.restype = c_size_t
+    L.ocrl_attention_bwd_ws.argtypes = L.ocrl_attention_bwd.argtypes[:-1] + [p, c_size_t, p]
     L.ocrl_xattn_desc_size.restype = c_size_t
     if L.ocrl_xattn_desc_size() != ctypes.sizeof(XattnDesc):
         raise RuntimeError(f"libocrl_hip.so: ocrl_xattn_desc is {L.ocrl_xattn_desc_size()} bytes, this binding's XattnDesc {ctypes.sizeof(XattnDesc)}")

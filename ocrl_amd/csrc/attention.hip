@@ -250,7 +250,18 @@ __global__ __launch_bounds__(256) void attn_delta_kernel(const float* __restrict
 }
 
 // ------------------------------------------------------------------------------------------- backward: dK, dV
-template <int DH>
+// dS hand-off (HANDOFF): the score gradients this kernel forms for dK are also what the dQ product needs, so with the flag set it stores
+// them and attn_bwd_dq_kernel reads them back instead of recomputing S and dP (5 product-equivalents per backward instead of 7).
+// Workspace: per (image of the chunk, head) the causal triangle of 64 x 64 tiles, tile (query tile qt, key tile kt <= qt) at index
+// qt (qt + 1) / 2 + kt, each tile [query][key] with the key contiguous (FA_DS_TILE floats).  A lane's value belongs to query
+// 16 sq + 4 g + r and key 16 wv + li, so the 16 li lanes of a store cover 64 contiguous bytes, and the dQ kernel's lane (li, g) reads
+// its four consecutive keys as one 16-byte load that is the B operand as it stands: no transpose through LDS on either side.  Every
+// element of every tile is stored -- above the diagonal, and for queries or keys at and beyond T, pr = 0 makes the value 0 -- because
+// the workspace is uninitialised and the dQ kernel reads whole tiles.  The stores add nothing to the dK / dV arithmetic.
+#define FA_DS_TILE (FA_BLK * FA_BLK)
+__host__ __device__ inline size_t fa_ds_tiles(int nblk) { return (size_t)nblk * (nblk + 1) / 2; }
+
+template <int DH, bool HANDOFF>
 __global__ __launch_bounds__(256, FA_BWD_WGS) void attn_bwd_kv_kernel(AttnArgs p) {
     constexpr int NC = FaCfg<DH>::NC, LD = FaCfg<DH>::LD;
     __shared__ __attribute__((aligned(16))) float Qs[FA_BLK * LD];
@@ -262,7 +273,7 @@ __global__ __launch_bounds__(256, FA_BWD_WGS) void attn_bwd_kv_kernel(AttnArgs p
     const int kb = FA_LPT ? bid / nbh : fa_block_index(bid % nkb, bid / nkb, nkb);
     bid = FA_LPT ? bid % nbh : bid / nkb;
     const int hd = bid % p.h;
-    const long long b = bid / p.h;
+    const long long b = p.b0 + bid / p.h;
     const int T = p.T, T4 = attn_drop_ld(p.T), d = p.ld, hoff = hd * DH;
     const long long bt0 = b * T;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -270,6 +281,8 @@ __global__ __launch_bounds__(256, FA_BWD_WGS) void attn_bwd_kv_kernel(AttnArgs p
     const int k_abs = kb * FA_BLK + wv * 16 + li;                       // this lane's key (column of S)
     const float scale = rsqrtf((float)DH);
     const long long bh = b * p.h + hd;
+    // this lane's element (query 4 g, key 16 wv + li) of tile (0, kb) of the chunk's (image, head) triangle
+    float* const dsw = HANDOFF ? p.ds + ((size_t)bid * fa_ds_tiles(nkb) + kb) * FA_DS_TILE + 4 * g * FA_BLK + wv * 16 + li : nullptr;
 
     float4 kf[NC], vf[NC];
 #pragma unroll
@@ -306,6 +319,7 @@ __global__ __launch_bounds__(256, FA_BWD_WGS) void attn_bwd_kv_kernel(AttnArgs p
         if (threadIdx.x < FA_BLK) { Ls[threadIdx.x] = rl; Ds[threadIdx.x] = rd; }
         __syncthreads();
         if (qt + 1 < nkb) fetch(qt + 1);
+        float* const dst = HANDOFF ? dsw + fa_ds_tiles(qt) * FA_DS_TILE : nullptr;
 #pragma unroll
         for (int sq = 0; sq < 4; ++sq) {
             f32x4_t s = (f32x4_t){0.f, 0.f, 0.f, 0.f}, dp = s;
@@ -347,6 +361,7 @@ __global__ __launch_bounds__(256, FA_BWD_WGS) void attn_bwd_kv_kernel(AttnArgs p
                 if (p.p > 0.f) keep = rng_keep(hq[r], li & 3, thr) ? dsc : 0.f;
                 pd[r] = pr * keep;
                 ds[r] = pr * (dp[r] * keep - Ds[ql]);
+                if (HANDOFF) dst[(16 * sq + r) * FA_BLK] = ds[r];
             }
             // all 8 * NC transposed operands of the sub-tile are requested first, then the 8 * NC MFMAs run (2 * NC independent chains)
             float ag[4][NC], aq[4][NC];
@@ -468,6 +483,81 @@ __global__ __launch_bounds__(256, FA_BWD_WGS) void attn_bwd_q_kernel(AttnArgs p)
                 if (p.p > 0.f) keep = rng_keep(bits, r, thr) ? dsc : 0.f;
                 sS[st][r] = pr * (sP[st][r] * keep - dlt);          // dS^T
             }
+        }
+        float ak[2][4][NC];                              // K^T operands one sub-tile ahead of their MFMAs (see the forward kernel)
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+#pragma unroll
+            for (int c = 0; c < NC; ++c) ak[0][r][c] = Ks[(4 * g + r) * LD + 16 * c + li];
+#pragma unroll
+        for (int st = 0; st < 4; ++st) {
+            if (st + 1 < 4) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+#pragma unroll
+                    for (int c = 0; c < NC; ++c) ak[(st + 1) & 1][r][c] = Ks[(16 * (st + 1) + 4 * g + r) * LD + 16 * c + li];
+            }
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+#pragma unroll
+                for (int c = 0; c < NC; ++c) dq[c] = MFMA16(ak[st & 1][r][c], sS[st][r], dq[c]);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    }
+    if (q_abs < T) {
+#pragma unroll
+        for (int c = 0; c < NC; ++c)
+            *reinterpret_cast<float4*>(p.dq + (bt0 + q_abs) * d + hoff + 16 * c + 4 * g) =
+                make_float4(dq[c][0] * scale, dq[c][1] * scale, dq[c][2] * scale, dq[c][3] * scale);
+    }
+}
+
+// ------------------------------------------------------------------------------------------- backward: dQ from stored dS
+// The hand-off form's dQ kernel: attn_bwd_q_kernel's grid, block order and third phase, with the dS^T operands read from the workspace
+// attn_bwd_kv_kernel<DH, true> filled instead of recomputed (no S, no dP, no soft-max, no RNG; K alone goes through LDS).  Lane (li, g) of
+// wave wv owns query 16 wv + li and loads keys 16 st + 4 g .. + 3 of its row as one 16-byte vector: a row's 256 bytes are consumed by the
+// four g groups over the four st loads.  K and dS of tile kt + 1 are requested before the MFMAs of tile kt.  The accumulation runs over
+// the same operands in the same order as in attn_bwd_q_kernel.
+template <int DH>
+__global__ __launch_bounds__(256, 4) void attn_bwd_dq_kernel(AttnArgs p) {
+    constexpr int NC = FaCfg<DH>::NC, LD = FaCfg<DH>::LD;
+    __shared__ __attribute__((aligned(16))) float Ks[FA_BLK * LD];
+    const int nqb = (p.T + FA_BLK - 1) / FA_BLK;
+    int bid = blockIdx.x;                                   // longest first, as attn_bwd_q_kernel
+    const int nbh = gridDim.x / nqb;
+    const int qb = FA_LPT ? nqb - 1 - bid / nbh : fa_block_index(bid % nqb, bid / nqb, nqb);
+    bid = FA_LPT ? bid % nbh : bid / nqb;
+    const int hd = bid % p.h;
+    const long long b = p.b0 + bid / p.h;
+    const int T = p.T, d = p.ld, hoff = hd * DH;
+    const long long bt0 = b * T;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int li = lane & 15, g = lane >> 4;
+    const int q_abs = qb * FA_BLK + wv * 16 + li;
+    const float scale = rsqrtf((float)DH);
+    // this lane's row of tile (qb, 0): tile kt follows at kt * FA_DS_TILE, sub-tile st at 16 * st
+    const float* const dsr = p.ds + ((size_t)bid * fa_ds_tiles(nqb) + fa_ds_tiles(qb)) * FA_DS_TILE + (wv * 16 + li) * FA_BLK + 4 * g;
+
+    f32x4_t dq[NC];
+#pragma unroll
+    for (int c = 0; c < NC; ++c) dq[c] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+    float4 rk[FaRegs<DH>::N];
+    f32x4_t rs[4];
+    fa_fetch<DH>(rk, p.k, bt0, 0, T, d, hoff);
+#pragma unroll
+    for (int st = 0; st < 4; ++st) rs[st] = *reinterpret_cast<const f32x4_t*>(dsr + 16 * st);
+    for (int kt = 0; kt <= qb; ++kt) {
+        __syncthreads();
+        fa_commit<DH>(Ks, rk, 1.f);
+        __syncthreads();
+        f32x4_t sS[4];
+#pragma unroll
+        for (int st = 0; st < 4; ++st) sS[st] = rs[st];          // dS^T of this tile
+        if (kt < qb) {
+            fa_fetch<DH>(rk, p.k, bt0, (kt + 1) * FA_BLK, T, d, hoff);
+#pragma unroll
+            for (int st = 0; st < 4; ++st) rs[st] = *reinterpret_cast<const f32x4_t*>(dsr + (size_t)(kt + 1) * FA_DS_TILE + 16 * st);
         }
         float ak[2][4][NC];                              // K^T operands one sub-tile ahead of their MFMAs (see the forward kernel)
 #pragma unroll
@@ -687,25 +777,60 @@ static int attn_launch_dh(const AttnArgs& a, int mode, hipStream_t st) {
         hipLaunchKernelGGL((attn_fwd_kernel<DH>), grid, blk, 0, st, a);
         OCRL_CHECK_LAUNCH("attn_fwd");
     } else {
-        const long long BT = (long long)a.B * a.T;
         OCRL_REQUIRE(a.d % 4 == 0 && a.d <= 1024 && (a.d / 4) % a.h == 0, "attention: d must be a multiple of 4*h, <= 1024");
+        // OCRL_ATTN_BWD: 1 = the one-pass form, 2 = the two-kernel form (dK/dV kernel + dQ kernel that recomputes S and dP), 3 = the
+        // hand-off form (the dK/dV kernel stores dS, the dQ kernel is the one product dS K).  Unset: the hand-off form when the caller
+        // gave a dS workspace, the two-kernel form otherwise.  The hand-off form walks the batch in chunks of as many images as the
+        // workspace holds; with room for less than one image it is the two-kernel form.
+        // Measured at B = 128, T = 1024, 4 heads of 48, p = 0.1, the backward alone (tools/bench_attn.py, delta kernel included):
+        //   two-kernel 2.04 ms (7 product-equivalents), one-pass 2.17 ms (5; 222 registers leave one 8-wave workgroup per CU, and what
+        //   the two products save is lost to the lower occupancy), hand-off 1.61 ms (5) with the whole batch as one chunk (1.14 GB of dS),
+        //   1.70 ms in chunks of 32 images (285 MB) and 1.66 ms in chunks of 16 (143 MB): keeping a chunk's round trip near the Infinity
+        //   Cache does not pay for the four or eight smaller launches, so a chunk is as many images as the workspace holds.
+        // Inside the training step (profiles/attn_handoff*_kernel_stats.csv, means over 92 launches): dK/dV kernel 1.58 -> 1.54 ms with the
+        // stores, dQ kernel 1.08 -> 0.37 ms.  dq, dk and dv are bit for bit those of the two-kernel form.
+        const char* fe = getenv("OCRL_ATTN_BWD");
+        const int form = fe ? atoi(fe) : 0;
+        const size_t per_image = attn_bwd_ds_floats(1, a.T, a.h);
+        const size_t room = (a.ds && form != 1 && form != 2) ? a.ds_floats / per_image : 0;
+        if (room >= 1) {
+            OCRL_REQUIRE(((uintptr_t)a.ds & 15) == 0, "attention backward: the dS workspace must be 16-byte aligned");
+            const int chunk = room < (size_t)a.B ? (int)room : a.B;
+            for (int b0 = 0; b0 < a.B; b0 += chunk) {
+                const int nb = a.B - b0 < chunk ? a.B - b0 : chunk;
+                const long long r0 = (long long)b0 * a.T, rows = (long long)nb * a.T;
+                hipLaunchKernelGGL(attn_delta_kernel, dim3(cdiv(rows, 256 / (a.d / 4))), dim3(256), 0, st, a.dO + r0 * a.d, a.o + r0 * a.d,
+                                   a.delta + r0 * a.h, rows, a.T, a.d, a.h);
+                OCRL_CHECK_LAUNCH("attn_delta");
+                AttnArgs c = a;
+                c.b0 = b0;
+                const dim3 cgrid(nb * a.h * nblk);
+                hipLaunchKernelGGL((attn_bwd_kv_kernel<DH, true>), cgrid, blk, 0, st, c);
+                OCRL_CHECK_LAUNCH("attn_bwd_kv");
+                hipLaunchKernelGGL((attn_bwd_dq_kernel<DH>), cgrid, blk, 0, st, c);
+                OCRL_CHECK_LAUNCH("attn_bwd_dq");
+            }
+            return 0;
+        }
+        const long long BT = (long long)a.B * a.T;
         hipLaunchKernelGGL(attn_delta_kernel, dim3(cdiv(BT, 256 / (a.d / 4))), dim3(256), 0, st, a.dO, a.o, a.delta, BT, a.T, a.d, a.h);
         OCRL_CHECK_LAUNCH("attn_delta");
-        // OCRL_ATTN_BWD=1 selects the one-pass form (5 instead of 7 product-equivalents); default: the two-kernel form
-        // (measured at B = 128, T = 1024, 4 heads of 48: 2.21 ms against 2.11 ms -- 222 registers leave one 8-wave workgroup per CU, and
-        // what the two products save is lost to the lower occupancy; kept as a tested alternative, not the default)
-        const char* fe = getenv("OCRL_ATTN_BWD");
-        if (fe && atoi(fe) == 1) {
+        if (form == 1) {
             hipLaunchKernelGGL((attn_bwd_fused_kernel<DH>), dim3(a.B * a.h), dim3(512), 0, st, a);
             OCRL_CHECK_LAUNCH("attn_bwd_fused");
         } else {
-        hipLaunchKernelGGL((attn_bwd_kv_kernel<DH>), grid, blk, 0, st, a);
-        OCRL_CHECK_LAUNCH("attn_bwd_kv");
-        hipLaunchKernelGGL((attn_bwd_q_kernel<DH>), grid, blk, 0, st, a);
-        OCRL_CHECK_LAUNCH("attn_bwd_q");
+            hipLaunchKernelGGL((attn_bwd_kv_kernel<DH, false>), grid, blk, 0, st, a);
+            OCRL_CHECK_LAUNCH("attn_bwd_kv");
+            hipLaunchKernelGGL((attn_bwd_q_kernel<DH>), grid, blk, 0, st, a);
+            OCRL_CHECK_LAUNCH("attn_bwd_q");
         }
     }
     return 0;
+}
+
+size_t attn_bwd_ds_floats(int B, int T, int h) {
+    if (B <= 0 || T <= 0 || h <= 0) return 0;
+    return (size_t)B * h * fa_ds_tiles(cdiv(T, FA_BLK)) * FA_DS_TILE;
 }
 
 // mode 0: forward (q,k,v -> o, lse);  mode 1: backward (q,k,v,o,lse,dO -> dq,dk,dv; delta is scratch [B,h,T])

@@ -354,6 +354,15 @@ int ocrl_attention_bwd(const float* q, const float* k, const float* v, const flo
     a.p = p; a.seed = seed; a.site = site; a.dO = dO; a.dq = dq; a.dk = dk; a.dv = dv; a.delta = delta;
     return attn_launch(a, 1, ST(stream));
 }
+size_t ocrl_attention_bwd_ds_floats(int B, int T, int h) { return attn_bwd_ds_floats(B, T, h); }
+int ocrl_attention_bwd_ws(const float* q, const float* k, const float* v, const float* o, const float* lse, const float* dO, float* dq,
+                          float* dk, float* dv, float* delta, int B, int T, int d, int h, int ld, float p, unsigned long long seed,
+                          unsigned site, float* ds, size_t ds_floats, void* stream) {
+    AttnArgs a;
+    a.q = q; a.k = k; a.v = v; a.o = const_cast<float*>(o); a.lse = const_cast<float*>(lse); a.B = B; a.T = T; a.d = d; a.h = h; a.ld = ld;
+    a.p = p; a.seed = seed; a.site = site; a.dO = dO; a.dq = dq; a.dk = dk; a.dv = dv; a.delta = delta; a.ds = ds; a.ds_floats = ds_floats;
+    return attn_launch(a, 1, ST(stream));
+}
 
 // ---- cross attention to the slots: the folded form (xattn.hip) and the plain kernels (elementwise.hip), as the decoder runs them
 int ocrl_xattn_plan(int K, int d, int h, int out[5]) {

@@ -522,8 +522,15 @@ struct AttnArgs {
     unsigned site = 0;
     const float* dO = nullptr;                              // backward
     float *dq = nullptr, *dk = nullptr, *dv = nullptr, *delta = nullptr;
+    // backward, hand-off form: the dK/dV kernel leaves its dS tiles here and the dQ kernel reads them (uninitialised scratch, 16-byte
+    // aligned; attn_bwd_ds_floats(B, T, h) holds the whole batch, less makes the launcher walk the batch in image chunks, null or less
+    // than one image selects the two-kernel form)
+    float* ds = nullptr;
+    size_t ds_floats = 0;
+    int b0 = 0;                                             // first image of a chunk (set by the launcher: pointers stay those of image 0)
 };
 int attn_launch(const AttnArgs& a, int mode, hipStream_t st);
+size_t attn_bwd_ds_floats(int B, int T, int h);             // 64 x 64 tiles of the causal triangle, per (image, head)
 
 // ------------------------------------------------------------------ bcast_l1.hip (first layer of both broadcast decoders: ks = 5 SLATE, 3 IODINE)
 enum { BCAST_L1_RELU = 0, BCAST_L1_ELU = 1 };

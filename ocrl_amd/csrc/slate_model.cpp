@@ -261,7 +261,22 @@ void SlateModel::layout_workspace(bool commit) {
         xa_pq_ = carve(nullptr, B * (size_t)d * d); xa_po_ = carve(nullptr, B * (size_t)d * d);
     }
     attn_delta_ = carve(nullptr, B * NH * (size_t)T);
-    lnf_ = carve("dec_out", BT * d); lnf_mean_ = carve(nullptr, BT); lnf_rstd_ = carve(nullptr, BT);
+    {
+        // dS workspace of the self-attention backward's hand-off form (csrc/attention.hip), one for the NB blocks, which run in sequence
+        // on the main stream.  OCRL_ATTN_BWD unset or 3: min(whole batch, OCRL_ATTN_DS_MB megabytes, default 2048) -- at T = 1024 the
+        // whole batch of 128 (1.14 GB) is one chunk, at T = 4096 (136 MB per image) a chunk is 15 images; 1 or 2: none
+        if (attn_ds_cap_ < 0) {           // read once: the sizing pass and bind() must lay out the same workspace
+            const char* fe = getenv("OCRL_ATTN_BWD");
+            const char* mb = getenv("OCRL_ATTN_DS_MB");
+            const int form = fe ? atoi(fe) : 0;
+            const long long mbs = mb ? atoll(mb) : 2048;
+            attn_ds_cap_ = (form == 1 || form == 2 || mbs < 0) ? 0 : mbs * (1ll << 20) / (long long)sizeof(float);
+        }
+        const size_t cap = (size_t)attn_ds_cap_, full = attn_bwd_ds_floats((int)B, T, NH);
+        attn_ds_floats_ = full < cap ? full : cap;
+        attn_ds_ = attn_ds_floats_ ? carve(nullptr, attn_ds_floats_) : nullptr;
+    }
+    lnf_ =carve("dec_out", BT * d); lnf_mean_ = carve(nullptr, BT); lnf_rstd_ = carve(nullptr, BT);
     pred_ = carve("pred", BT * V);
     gx_ = carve(nullptr, BT * d); gbr_ = carve(nullptr, BT * d); gt1_ = carve(nullptr, BT * d); gt2_ = carve(nullptr, BT * d);
     gt3_ = carve(nullptr, BT * d); gf1_ = carve(nullptr, BT * 4 * d); gqkv_ = carve(nullptr, BT * 3 * d);
@@ -868,6 +883,7 @@ int SlateModel::bwd_decoder(const Lane& L) {
         {
             AttnArgs a = self_attn_args(b);
             a.dO = gt1_; a.dq = q.gqkv; a.dk = q.gqkv + d; a.dv = q.gqkv + 2 * d; a.delta = attn_delta_;
+            a.ds = attn_ds_; a.ds_floats = attn_ds_floats_;
             RC(attn_launch(a, 1, L));
         }
         // fused [3d, d] weight: dW = [dq|dk|dv]^T ln1 ;  d ln1 = [dq|dk|dv] W

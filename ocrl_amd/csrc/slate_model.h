@@ -204,6 +204,9 @@ private:
     hipEvent_t ev_join2_ = nullptr;
     int ev_dw_next_ = 0;
     float *attn_delta_;                   // [B,h,T] scratch of the attention backward
+    float *attn_ds_ = nullptr;            // dS tiles of its hand-off form (null: the two-kernel form)
+    size_t attn_ds_floats_ = 0;
+    long long attn_ds_cap_ = -1;          // floats; -1: OCRL_ATTN_BWD / OCRL_ATTN_DS_MB not read yet
     float *lnf_, *lnf_mean_, *lnf_rstd_, *pred_;
     // gradient temporaries
     float *gqkv_;                         // [BT, 3d] fused dq|dk|dv
