@@ -21,7 +21,7 @@ from .._bridge import ints as _ints
 
 _WHO = "ocrl_amd.PropertyPredictor"
 SLOT_ENCODERS = ("SLATE", "SlotAttn", "Iodine")
-MAX_SLOTS = 12          # OCRL_PROBE_MAX_SLOTS
+MAX_SLOTS = _lib.CONSTANTS["OCRL_PROBE_MAX_SLOTS"]
 
 
 def property_indices(property_list, properties):

@@ -2,6 +2,8 @@
 import numpy as np
 import torch
 
+from .. import _lib
+
 
 def to_device(batch, device):
     """utils/tools.py:182-191"""
@@ -15,7 +17,6 @@ def to_device(batch, device):
 def obs_from_uint8(u8):
     """uint8 [B,H,W,C] on the GPU -> fp32 [B,C,H,W] in [0,1] (utils/datasets.py:17 + the H2D copy of train_ocr.py:52-53), converted by
     the library's kernel: the host ships a quarter of the bytes and never touches the pixels"""
-    from .. import _lib
     if not (u8.is_cuda and u8.dtype == torch.uint8 and u8.dim() == 4):
         raise RuntimeError("obs_from_uint8: expected a uint8 [B,H,W,C] tensor on the GPU")
     u8 = u8.contiguous()
@@ -78,7 +79,7 @@ def _adjusted_rand_score(a, b):
     return ari_from_pair_sums(comb(cont).sum(), comb(cont.sum(1)).sum(), comb(cont.sum(0)).sum(), n)
 
 
-ARI_MAX_CHANNELS = 32      # OCRL_ARI_MAX_CHANNELS of include/ocrl_hip.h
+ARI_MAX_CHANNELS = _lib.CONSTANTS["OCRL_ARI_MAX_CHANNELS"]
 
 
 def _on_device(*ts):
@@ -89,7 +90,7 @@ def ari_counts(truth, pred, fuse_fg=False):
     """ocrl_ari_counts on the current stream: truth [B, Ct, ...] and pred [B, Cp or K, ...] CUDA fp32 score stacks over the same pixels
     (any strides that flatten(2) can express are read in place).  Returns (table [B, Ct, Cp] int32, sums [B, 3] int64) on the device;
     fuse_fg: pred holds K = Cp - 1 maps and the foreground channel 1 - truth[:, -1] is formed in the kernel."""
-    from .. import _bridge, _lib
+    from .. import _bridge
     t, p = truth.flatten(2), pred.flatten(2)
     B, Ct, N = t.shape
     Cp = p.shape[1] + (1 if fuse_fg else 0)
