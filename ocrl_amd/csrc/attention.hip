@@ -13,7 +13,7 @@
 // One workgroup = 4 waves = 64 queries (or 64 keys); tiles of 64 keys (queries) stream through LDS.
 #include "common.h"
 #include "kernels.h"
-#include <stdlib.h>
+#include "switches.h"
 
 #define FA_BLK 64
 #ifndef FA_LPT
@@ -769,6 +769,9 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_fused_kernel(AttnArgs p) {
 }
 
 // ------------------------------------------------------------------------------------------- launchers
+// OCRL_ATTN_BWD, read at every call (the launcher's comment below describes the forms), and the one reading of "may hand dS off"
+int attn_bwd_form() { return (int)sw::call<sw::OCRL_ATTN_BWD>(); }
+static bool attn_form_hands_off(int form) { return form != 1 && form != 2; }
 template <int DH>
 static int attn_launch_dh(const AttnArgs& a, int mode, hipStream_t st) {
     const int nblk = cdiv(a.T, FA_BLK);
@@ -789,10 +792,9 @@ static int attn_launch_dh(const AttnArgs& a, int mode, hipStream_t st) {
         //   Cache does not pay for the four or eight smaller launches, so a chunk is as many images as the workspace holds.
         // Inside the training step (profiles/attn_handoff*_kernel_stats.csv, means over 92 launches): dK/dV kernel 1.58 -> 1.54 ms with the
         // stores, dQ kernel 1.08 -> 0.37 ms.  dq, dk and dv are bit for bit those of the two-kernel form.
-        const char* fe = getenv("OCRL_ATTN_BWD");
-        const int form = fe ? atoi(fe) : 0;
+        const int form = attn_bwd_form();
         const size_t per_image = attn_bwd_ds_floats(1, a.T, a.h);
-        const size_t room = (a.ds && form != 1 && form != 2) ? a.ds_floats / per_image : 0;
+        const size_t room = (a.ds && attn_form_hands_off(form)) ? a.ds_floats / per_image : 0;
         if (room >= 1) {
             OCRL_REQUIRE(((uintptr_t)a.ds & 15) == 0, "attention backward: the dS workspace must be 16-byte aligned");
             const int chunk = room < (size_t)a.B ? (int)room : a.B;
@@ -831,6 +833,14 @@ static int attn_launch_dh(const AttnArgs& a, int mode, hipStream_t st) {
 size_t attn_bwd_ds_floats(int B, int T, int h) {
     if (B <= 0 || T <= 0 || h <= 0) return 0;
     return (size_t)B * h * fa_ds_tiles(cdiv(T, FA_BLK)) * FA_DS_TILE;
+}
+// what a model that takes the defaults carves for (B, T, h): the whole batch up to OCRL_ATTN_DS_MB megabytes; nothing when the form
+// as the environment has it now would not use it
+size_t attn_bwd_ds_carve_floats(int B, int T, int h) {
+    const long long mb = sw::model<sw::OCRL_ATTN_DS_MB>();
+    if (!attn_form_hands_off(attn_bwd_form()) || mb < 0) return 0;
+    const size_t cap = (size_t)(mb * (1ll << 20) / (long long)sizeof(float)), full = attn_bwd_ds_floats(B, T, h);
+    return full < cap ? full : cap;
 }
 
 // mode 0: forward (q,k,v -> o, lse);  mode 1: backward (q,k,v,o,lse,dO -> dq,dk,dv; delta is scratch [B,h,T])

@@ -8,7 +8,7 @@
 // Layers 2-3 reuse conv.hip; the 64->4 output convolution (shared with IODINE) and the slot mixture have their own kernels here.
 #include "common.h"
 #include "kernels.h"
-#include <stdlib.h>
+#include "switches.h"
 
 #define BT_H 4
 #define BT_W 32
@@ -426,9 +426,7 @@ int bc_c4_wgrad_blocks(int Bn, int S) {
     return nt < 1024 ? nt : 1024;
 }
 int bc_c4_wgrad_launch(const float* X, const float* dY, float* part, int Bn, int S, hipStream_t st) {
-    static int form = -1;
-    if (form < 0) { const char* e = getenv("OCRL_BC_WGRAD"); form = e ? atoi(e) : 2; }       // 1: the VALU form
-    if (form != 1) {
+    if (sw::process<sw::OCRL_BC_WGRAD>() != 1) {       // 1: the VALU form
         hipLaunchKernelGGL(bc_c4_wgrad_mfma_kernel, dim3(bc_c4_wgrad_blocks(Bn, S)), dim3(256), 0, st, X, dY, part, Bn, S);
         OCRL_CHECK_LAUNCH("bc_c4_wgrad_mfma");
         return 0;

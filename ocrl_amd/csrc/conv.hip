@@ -15,7 +15,7 @@
 //     the dW slabs; the reduce kernel adds those in slab order.
 #include "common.h"
 #include "kernels.h"
-#include <stdlib.h>
+#include "switches.h"
 
 #define TH 4
 #define TW 32
@@ -480,9 +480,7 @@ static int conv_fwd_cfg(const ConvArgs& a, hipStream_t st) {
 
 // the low-latency variant pays when the throughput kernel's grid leaves most CUs idle: fewer than ~0.6 workgroups per CU (measured: 64x64, B = 8 = 256 tiles is already faster on the throughput kernel)
 static bool conv_lat_applies(const ConvArgs& a, int KS, int CIN) {
-    static int on = -1;
-    if (on < 0) { const char* e = getenv("OCRL_CONV_LAT"); on = e ? atoi(e) : 1; }
-    return on && KS == 5 && CIN == 64 && !a.mask && a.relu <= 1 && (long long)cdiv(a.W, TW) * cdiv(a.H, TH) * a.B <= 160;
+    return sw::process<sw::OCRL_CONV_LAT>() && KS == 5 && CIN == 64 && !a.mask && a.relu <= 1 && (long long)cdiv(a.W, TW) * cdiv(a.H, TH) * a.B <= 160;
 }
 int conv_fwd_launch(const ConvArgs& a_in, int KS, int CIN, int COUT, hipStream_t st, int low_latency) {
     ConvArgs a = a_in;
@@ -536,9 +534,7 @@ int conv_wgrad_launch(const WgradArgs& a_in, int KS, int CIN, int COUT, int cin_
     const int nslab = nchunk * (CIN == 64 ? 1 : 2);
     WgradArgs a = a_in;
     a.bpart = db ? a.part + (size_t)nslab * KS * KS * COUT * CIN : nullptr;
-    static int x3_env = -1;
-    if (x3_env < 0) { const char* e = getenv("OCRL_CONV_X3"); x3_env = e ? atoi(e) : 0; }
-    if (x3 < 0) x3 = x3_env;
+    if (x3 < 0) x3 = (int)sw::process<sw::OCRL_CONV_X3>();
     OCRL_REQUIRE(!(db && x3 > 0), "conv wgrad: the split-precision stage leaves no bias partials (take the column sum of dY instead)");
     int rc;
     if ((KS == 5 || KS == 3) && CIN == 64 && x3 > 0) rc = conv_wgrad_x3_stage(a, nchunk, st, KS);

@@ -17,7 +17,7 @@
 // their weight gradients over the rows (lin_splitk_count).
 #include "common.h"
 #include "kernels.h"
-#include <stdlib.h>
+#include "switches.h"
 
 int gemm_launch_tt(const GemmArgs& a, const GemmPlan& p, hipStream_t st);
 int gemm_launch_tn(const GemmArgs& a, const GemmPlan& p, hipStream_t st);
@@ -56,22 +56,9 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
     }
 }
 
-// development overrides, read once: OCRL_GEMM_TILE=BMxBN (e.g. 128x64) forces one tile shape where that family builds it;
-// OCRL_GEMM_SB: 0 = the buffering rule, 1 = always single, 2 = always double
-static int env_tile() {
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("OCRL_GEMM_TILE");
-        v = 0;
-        if (e) { int bm = 0, bn = 0; if (sscanf(e, "%dx%d", &bm, &bn) == 2) v = bm * 1000 + bn; }
-    }
-    return v;
-}
-static int env_sb() {
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("OCRL_GEMM_SB"); v = e ? atoi(e) : 0; }
-    return v;
-}
+// development overrides (switches.h): OCRL_GEMM_TILE forces one tile shape where that family builds it, OCRL_GEMM_SB the buffering
+static int env_tile() { return (int)sw::process<sw::OCRL_GEMM_TILE>(); }
+static int env_sb() { return (int)sw::process<sw::OCRL_GEMM_SB>(); }
 // tile shapes instantiated in gemm_impl.h for an operand layout (128x192 only where A is k-contiguous or B is n-contiguous)
 static bool tile_built(int tile, int akc, int bkc) {
     return tile == 128128 || tile == 128064 || tile == 64128 || tile == 64064 || (tile == 128192 && (akc || !bkc));

@@ -6,8 +6,9 @@
 // backward is a plain reverse sweep over the saved activations of every iteration.
 #include "iodine_model.h"
 
+#include "switches.h"
+
 #include <stdarg.h>
-#include <stdlib.h>
 
 static std::string ifmt(const char* f, ...) {
     char buf[128];
@@ -48,6 +49,7 @@ IodineModel::IodineModel(const IodineConfig& c) : cfg(c) {
     w_.lstm_bih = ref("refine.lstm.bias_ih"); w_.lstm_bhh = ref("refine.lstm.bias_hh");
     w_.mean_update = ref_pair("refine.mean_update"); w_.logsig_update = ref_pair("refine.logsig_update");
     w_.dec_out = ref_pair("decoder.conv");
+    conv_x3_ = (int)sw::model<sw::OCRL_CONV_X3>();       // asked once: the sizing pass and every bind() lay out the same blocks
     layout_workspace(false);
 }
 
@@ -90,7 +92,6 @@ void IodineModel::layout_workspace(bool commit) {
     M_ = carve(nullptr, BK * 576); T_ = carve(nullptr, BK * 576);
     P1_ = carve(nullptr, (size_t)N * 64); W1r_ = carve(nullptr, (size_t)576 * L); Wxy_ = carve(nullptr, 576 * 2);
     for (int l = 0; l < 3; ++l) { pk_[l] = carve(nullptr, 9 * 64 * 64); pkb_[l] = carve(nullptr, 9 * 64 * 64); }
-    if (conv_x3_ < 0) { const char* e = getenv("OCRL_CONV_X3"); conv_x3_ = e ? atoi(e) : 0; }
     if (conv_x3_ > 0)
         for (int l = 0; l < 3; ++l) { pk3_[l] = carve(nullptr, conv_x3_pack_floats(3)); pkb3_[l] = carve(nullptr, conv_x3_pack_floats(3)); }
     Wk4_ = carve(nullptr, 9 * 64 * 4); Wb4_ = carve(nullptr, 9 * 4 * 64);

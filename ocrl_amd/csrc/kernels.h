@@ -531,6 +531,10 @@ struct AttnArgs {
 };
 int attn_launch(const AttnArgs& a, int mode, hipStream_t st);
 size_t attn_bwd_ds_floats(int B, int T, int h);             // 64 x 64 tiles of the causal triangle, per (image, head)
+// OCRL_ATTN_BWD as the launcher reads it, at every call: 1 one pass, 2 two kernels, otherwise the hand-off form where a.ds has room
+int attn_bwd_form();
+// dS floats a model may carve for (B, T, h) under the switches as they are now: min(whole batch, OCRL_ATTN_DS_MB), 0 when the form is 1 or 2
+size_t attn_bwd_ds_carve_floats(int B, int T, int h);
 
 // ------------------------------------------------------------------ bcast_l1.hip (first layer of both broadcast decoders: ks = 5 SLATE, 3 IODINE)
 enum { BCAST_L1_RELU = 0, BCAST_L1_ELU = 1 };

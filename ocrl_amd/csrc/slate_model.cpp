@@ -3,7 +3,7 @@
 // Base.update (ocrs/base.py:60-74); maths restated in SURVEY.md Appendix A.
 #include "slate_model.h"
 
-#include <stdlib.h>
+#include "switches.h"
 
 #include <math.h>
 #include <stdarg.h>
@@ -81,6 +81,9 @@ SlateModel::SlateModel(const SlateConfig& c) : cfg(c) {
     finish_params(group_begin_, 3);
     resolve_params();
     blk_.resize(NB);
+    // what sizes the workspace is asked once, here: the sizing pass and every bind() lay out the same blocks
+    conv_x3_ = (int)sw::model<sw::OCRL_CONV_X3>();
+    attn_ds_floats_ = attn_bwd_ds_carve_floats(Bmax, T, NH);
     layout_workspace(false);
 }
 
@@ -177,7 +180,6 @@ void SlateModel::layout_workspace(bool commit) {
         const int cin = i == 0 ? 8 : 64;
         cw_fwd_[i] = carve(nullptr, (size_t)25 * cin * 64);
         cw_bwd_[i] = i == 0 ? nullptr : carve(nullptr, (size_t)25 * 64 * 64);
-        if (conv_x3_ < 0) { const char* e = getenv("OCRL_CONV_X3"); conv_x3_ = e ? atoi(e) : 0; }
         if (conv_x3_ && i > 0) {          // exploratory split-precision packs beside the fp32 ones (csrc/conv_x3.hip)
             float* f3 = carve(nullptr, conv_x3_pack_floats());
             float* b3 = carve(nullptr, conv_x3_pack_floats());
@@ -261,21 +263,10 @@ void SlateModel::layout_workspace(bool commit) {
         xa_pq_ = carve(nullptr, B * (size_t)d * d); xa_po_ = carve(nullptr, B * (size_t)d * d);
     }
     attn_delta_ = carve(nullptr, B * NH * (size_t)T);
-    {
-        // dS workspace of the self-attention backward's hand-off form (csrc/attention.hip), one for the NB blocks, which run in sequence
-        // on the main stream.  OCRL_ATTN_BWD unset or 3: min(whole batch, OCRL_ATTN_DS_MB megabytes, default 2048) -- at T = 1024 the
-        // whole batch of 128 (1.14 GB) is one chunk, at T = 4096 (136 MB per image) a chunk is 15 images; 1 or 2: none
-        if (attn_ds_cap_ < 0) {           // read once: the sizing pass and bind() must lay out the same workspace
-            const char* fe = getenv("OCRL_ATTN_BWD");
-            const char* mb = getenv("OCRL_ATTN_DS_MB");
-            const int form = fe ? atoi(fe) : 0;
-            const long long mbs = mb ? atoll(mb) : 2048;
-            attn_ds_cap_ = (form == 1 || form == 2 || mbs < 0) ? 0 : mbs * (1ll << 20) / (long long)sizeof(float);
-        }
-        const size_t cap = (size_t)attn_ds_cap_, full = attn_bwd_ds_floats((int)B, T, NH);
-        attn_ds_floats_ = full < cap ? full : cap;
-        attn_ds_ = attn_ds_floats_ ? carve(nullptr, attn_ds_floats_) : nullptr;
-    }
+    // dS workspace of the self-attention backward's hand-off form (attn_bwd_ds_carve_floats, csrc/attention.hip), one for the NB blocks,
+    // which run in sequence on the main stream: at T = 1024 the whole batch of 128 (1.14 GB) is one chunk, at T = 4096 (136 MB per
+    // image) a chunk is 15 images
+    attn_ds_ = attn_ds_floats_ ? carve(nullptr, attn_ds_floats_) : nullptr;
     lnf_ =carve("dec_out", BT * d); lnf_mean_ = carve(nullptr, BT); lnf_rstd_ = carve(nullptr, BT);
     pred_ = carve("pred", BT * V);
     gx_ = carve(nullptr, BT * d); gbr_ = carve(nullptr, BT * d); gt1_ = carve(nullptr, BT * d); gt2_ = carve(nullptr, BT * d);
@@ -308,46 +299,27 @@ int SlateModel::bind(float* p, float* g, float* m, float* v, void* ws, size_t ws
     clear_encode_graphs();       // captured against the old buffers
     packs_valid_ = false;
     layout_workspace(true);
-    if (!side_) {
-        // OCRL_OVERLAP (default 5): the dVAE branch (many short 64-wide products that do not fill the machine) runs on a side stream.
-        //   5 = forward forked right after the encoder convolutions (beside the input LayerNorm / MLP and the slot-attention chain),
-        //       backward beside the transformer-decoder backward and joined before the slot-attention backward and the 5x5
-        //       convolutions, so those never share the GPU and their timings stay comparable
-        //   4 = as 5 with the forward forked at the start of the step (beside the encoder convolutions)
-        //   3 = as 5 with the forward forked at the slot-attention launches
-        //   2 = forward and backward beside the slot-attention launches only (round 1's default, when slot attention left half the CUs idle)
-        //   1 = whole dVAE branch beside encoder + decoder (per-kernel timings of both branches stop being comparable); 0 = single stream
-        // In modes 3-5 the main stream waits for the dVAE tokens only (OCRL_TOKENS_LATE=1 restores the full join before the decoder).
-        const char* e = getenv("OCRL_OVERLAP");
-        overlap_mode_ = e ? atoi(e) : 5;
-        if (overlap_mode_) {
+    if (!side_) {       // the first bind (a single-stream plan creates nothing, and is asked for again)
+        plan_ = stream_plan((int)sw::model<sw::OCRL_OVERLAP>(), (int)sw::model<sw::OCRL_DW_SIDE>(), sw::model<sw::OCRL_TOKENS_LATE>() != 0, cfg.use_bcdec);
+        if (plan_.side) {
             OCRL_HIP(hipStreamCreateWithFlags(&side_, hipStreamNonBlocking));
             OCRL_HIP(hipEventCreateWithFlags(&ev_fork_, hipEventDisableTiming));
             OCRL_HIP(hipEventCreateWithFlags(&ev_join_, hipEventDisableTiming));
             OCRL_HIP(hipEventCreateWithFlags(&ev_tokens_, hipEventDisableTiming));
-            // OCRL_DW_SIDE (default 2): the weight-gradient products of the transformer decoder leave the main stream -- nothing later in
-            // the step reads them, while the input-gradient chain they would otherwise interrupt is the step's critical path.
-            //   1 = on the dVAE side stream (behind the dVAE backward), 2 = on a stream of their own, 0 = on the main stream (round 2)
-            const char* w = getenv("OCRL_DW_SIDE");
-            dw_mode_ = (overlap_mode_ >= 3 && !cfg.use_bcdec) ? (w ? atoi(w) : 2) : 0;
-            if (dw_mode_) {
+            // the weight-gradient products of the transformer decoder leave the main stream: nothing later in the step reads them,
+            // while the input-gradient chain they would otherwise interrupt is the step's critical path
+            if (plan_.dw) {
                 for (hipEvent_t& ev : ev_dw_) OCRL_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
                 OCRL_HIP(hipEventCreateWithFlags(&ev_join2_, hipEventDisableTiming));
-                if (dw_mode_ == 2) OCRL_HIP(hipStreamCreateWithFlags(&side2_, hipStreamNonBlocking));
+                if (plan_.dw == 2) OCRL_HIP(hipStreamCreateWithFlags(&side2_, hipStreamNonBlocking));
             }
         }
     }
-    {
-        // OCRL_SA_INPUT (default 1): the slot-attention input LayerNorm + MLP as one kernel per direction (csrc/sa_input.hip);
-        //   0 = the unfused chain (LayerNorm, two GEMMs; five launches and their reduction tails backward), 2 = fused forward only
-        const char* e = getenv("OCRL_SA_INPUT");
-        sa_input_ = e ? atoi(e) : 1;
-    }
-    {
-        const char* e = getenv("OCRL_XATTN");
-        xattn_ = !cfg.use_bcdec && xattn_supported(K, d, NH) && (e ? atoi(e) != 0 : true);
-        if (!cfg.use_bcdec && xa_zero_floats_) OCRL_HIP(hipMemset(xa_zero_base_, 0, xa_zero_floats_ * sizeof(float)));      // padding columns of the folded operands
-    }
+    // the slot-attention input LayerNorm + MLP as one kernel per direction (csrc/sa_input.hip), or the unfused chain: LayerNorm, two
+    // GEMMs; five launches and their reduction tails backward
+    sa_input_ = (int)sw::model<sw::OCRL_SA_INPUT>();
+    xattn_ = !cfg.use_bcdec && xattn_supported(K, d, NH) && sw::model<sw::OCRL_XATTN>() != 0;
+    if (!cfg.use_bcdec && xa_zero_floats_) OCRL_HIP(hipMemset(xa_zero_base_, 0, xa_zero_floats_ * sizeof(float)));      // padding columns of the folded operands
     // static tables
     RC(posgrid_launch(gridT_, S, 0));
     RC(fill_launch(recon_, (long long)Bmax * N * 4, 0.f, 0));
@@ -425,10 +397,11 @@ int SlateModel::pack_weights(const Lane& L, bool encoder_only) {
 
 // ---------------------------------------------------------------------------------------------
 // CNN encoder + slot attention (ocrs/common/models.py:96-107, slot_attn.py:147-161)
-int SlateModel::fwd_encoder(const StepInputs& in, const Lane& L, int fork_dvae) {
+int SlateModel::fwd_encoder(const StepInputs& in, const Lane& L, FwdDvae fork) {
     const int B = in.B;
     const long long BN = (long long)B * N;
-    auto fork_here = [&]() -> int {
+    auto fork_if = [&](FwdDvae here) -> int {
+        if (fork != here) return 0;
         RC(after(dvae_lane(), L, ev_fork_));
         return fwd_dvae(in, dvae_lane());
     };
@@ -443,7 +416,7 @@ int SlateModel::fwd_encoder(const StepInputs& in, const Lane& L, int fork_dvae) 
     a.xchg = sa_xchg_; a.parts = sa_parts_;
     a.phase = 1;
     RC(slot_attn_launch(a, 0, L));
-    if (fork_dvae == 2) RC(fork_here());
+    RC(fork_if(FwdDvae::AtStart));
     if (first_direct()) {
         RC(conv_first_fwd_launch(in.obs, cw_fwd_[0], P(w_.enc[0].b), e1_, B, S, S, 1, L));
         if (!(conv_lowlat_ && frozen_))       // a backward may follow: it reads the observation again
@@ -455,7 +428,7 @@ int SlateModel::fwd_encoder(const StepInputs& in, const Lane& L, int fork_dvae) 
     RC(conv_layer_fwd(e1_, cw_fwd_[1], P(w_.enc[1].b), e2_, B, S, S, 5, 64, 1, nullptr, nullptr, L));
     RC(conv_layer_fwd(e2_, cw_fwd_[2], P(w_.enc[2].b), e3_, B, S, S, 5, 64, 1, nullptr, nullptr, L));
     RC(conv_layer_fwd(e3_, cw_fwd_[3], P(w_.enc[3].b), e4_, B, S, S, 5, 64, 0, posmap_, nullptr, L));
-    if (fork_dvae == 3) RC(fork_here());
+    RC(fork_if(FwdDvae::AfterConvs));
     if (sa_input_ && C == 64 && !(conv_lowlat_ && frozen_)) {
         // LayerNorm and both Linear layers in one pass over the rows (csrc/sa_input.hip): e4 is read, h1 and x are written; the fused
         // backward rebuilds LN(e4) from e4, mean and rstd, so ln0_ is written only for the unfused backward (OCRL_SA_INPUT=2)
@@ -467,7 +440,7 @@ int SlateModel::fwd_encoder(const StepInputs& in, const Lane& L, int fork_dvae) 
         RC(lin_fwd(ln0_, C, P(w_.sa.mlp0.w), P(w_.sa.mlp0.b), h1_, C, BN, C, C, 1, nullptr, 0, 0.f, 0, L));
         RC(lin_fwd(h1_, C, P(w_.sa.mlp2.w), P(w_.sa.mlp2.b), x_, C, BN, C, C, 0, nullptr, 0, 0.f, 0, L));
     }
-    if (fork_dvae == 1) RC(fork_here());
+    RC(fork_if(FwdDvae::AtSlotAttention));
     a.phase = 2;
     RC(slot_attn_launch(a, 0, L));
     return 0;
@@ -563,7 +536,7 @@ int SlateModel::fwd_decoder(const Lane& L, bool with_ce) {
     RC(embed_fwd_launch(tokens_, P(w_.dict), P(w_.bos), P(w_.pe), emb_, B, T, d, p, last_.seed, L));
     // The fold below only needs the projected slots and is first consumed by block 0's cross attention, after the embedding, a LayerNorm,
     // the q|k|v projection and the self attention: on the (idle) weight-gradient stream it runs beside them
-    const Lane F = side2_ ? dw_lane(L) : L;
+    const Lane F = plan_.dw == 2 ? dw_lane(L) : L;
     if (xattn_) {       // per-image cross-attention operands of every block from the projected slots: one launch
         XaFoldHost f;
         f.mem = mem_; f.B = B; f.K = K; f.d = d; f.h = NH; f.nblk = NB;
@@ -642,32 +615,20 @@ int SlateModel::forward(const StepInputs& in, hipStream_t st) {
         have_fwd_ = true;
         return 0;
     }
-    // the dVAE branch (tokens, reconstruction loss) and the CNN encoder + slot attention are independent until the decoder:
-    // the dVAE runs on the side stream, filling the CUs the one-workgroup-per-image slot-attention kernel leaves idle
-    if (side_ && overlap_mode_ >= 2) {
-        // forks the dVAE forward right before the slot-attention launch (modes 2, 3), at the start of the step (4) or after the convolutions (5)
-        RC(fwd_encoder(in, L, overlap_mode_ == 4 ? 2 : (overlap_mode_ == 5 ? 3 : 1)));
-        if (overlap_mode_ >= 3 && !getenv("OCRL_TOKENS_LATE")) {
-            // wait for the tokens only; the rest of the dVAE branch (its decoder, the reconstruction loss) overlaps the transformer decoder
-            OCRL_HIP(hipStreamWaitEvent(L, ev_tokens_, 0));
-            RC(fwd_decoder(L));
-            RC(after(L, dvae_lane(), ev_join_));
-            RC(copy_launch(metrics_ + 0, metrics_ + 2, 1, L));
-            RC(axpy_launch(metrics_ + 1, metrics_ + 2, 1, 1.f, L));      // loss = dvae_mse + cross_entropy
-            have_fwd_ = true;
-            return 0;
-        }
-        RC(after(L, dvae_lane(), ev_join_));
-    } else if (side_) {
+    // the dVAE branch (tokens, reconstruction loss) and the CNN encoder + slot attention are independent until the decoder: on the
+    // side stream the dVAE fills the CUs the one-workgroup-per-image slot-attention kernel leaves idle.  plan_.fwd_dvae says where it
+    // is forked: here, or at one of three points inside the encoder
+    if (plan_.fwd_dvae == FwdDvae::Serial) RC(fwd_dvae(in, L));
+    if (plan_.fwd_dvae == FwdDvae::BesideEncoder) {
         RC(after(dvae_lane(), L, ev_fork_));
         RC(fwd_dvae(in, dvae_lane()));
-        RC(fwd_encoder(in, L));
-        RC(after(L, dvae_lane(), ev_join_));
-    } else {
-        RC(fwd_dvae(in, L));
-        RC(fwd_encoder(in, L));
     }
+    RC(fwd_encoder(in, L, plan_.fwd_dvae));
+    // the decoder needs the tokens only: the rest of the dVAE branch (its decoder, the reconstruction loss) may overlap it
+    if (plan_.tokens_early) OCRL_HIP(hipStreamWaitEvent(L, ev_tokens_, 0));
+    else if (plan_.side) RC(after(L, dvae_lane(), ev_join_));
     RC(fwd_decoder(L));
+    if (plan_.tokens_early) RC(after(L, dvae_lane(), ev_join_));
     RC(copy_launch(metrics_ + 0, metrics_ + 2, 1, L));
     RC(axpy_launch(metrics_ + 1, metrics_ + 2, 1, 1.f, L));      // loss = dvae_mse + cross_entropy
     have_fwd_ = true;
@@ -684,7 +645,7 @@ int SlateModel::encode(const StepInputs& in, hipStream_t st) {
     const Lane L = main_lane(st);
     // measured (tools/bench_encode.py, B = 1 / 8 / 32 at 64x64): 0.457 / 0.483 / 1.006 ms replayed against 0.450 / 0.473 / 0.988 ms eager -- the
     // call is bound by its chain of ~30 dependent small kernels on the GPU, not by the host's launches, so the replay is opt-in
-    if (enc_graph_mode_ < 0) { const char* e = getenv("OCRL_ENCODE_GRAPH"); enc_graph_mode_ = e ? atoi(e) : 0; }
+    if (enc_graph_mode_ < 0) enc_graph_mode_ = (int)sw::model<sw::OCRL_ENCODE_GRAPH>();
     const bool graph = enc_graph_mode_ && in.B <= 32 && !in.noise_slots && obs_stage_;
     // frozen weights (ocrl_slate_freeze_weights: serving with a pre-trained encoder): the derived weight images -- convolution packs,
     // slot-attention block, position map; 8 launches, ~45 us of a 0.47 ms call at B = 1 -- are built once
@@ -808,7 +769,7 @@ int SlateModel::bwd_decoder(const Lane& L) {
     // The weight-gradient products go to their own lane W (OCRL_DW_SIDE, dw_lane): after(W, L, ..) makes it wait for everything the main
     // stream has enqueued so far.  Without OCRL_DW_SIDE W is the main lane and the ordering calls do nothing.
     const Lane W = dw_lane(L);
-    const bool dws = dw_mode_ != 0;
+    const bool dws = plan_.dw != 0;
     // output head: d loss / d pred = (softmax(pred_) - onehot(tokens)) / B, rebuilt from the logits as both products stage their A tiles
     Xf ce; ce.a_mode = 3; ce.lse = celse_; ce.tok = tokens_; ce.scale = 1.0f / last_.B;
     RC(after(W, L, ring_event()));
@@ -913,7 +874,8 @@ int SlateModel::bwd_decoder(const Lane& L) {
     return 0;
 }
 
-int SlateModel::bwd_encoder(const Lane& L, bool fork_dvae) {
+int SlateModel::bwd_encoder(const Lane& L, BwdDvae fork) {
+    const bool fork_dvae = fork == BwdDvae::AtSlotAttention;
     const int B = last_.B;
     const long long BN = (long long)B * N, R = (long long)B * I * K;
     const SlotAttnW& sa = w_.sa;
@@ -929,7 +891,7 @@ int SlateModel::bwd_encoder(const Lane& L, bool fork_dvae) {
     // step -- the slot-side weight gradients, the LayerNorm partials, the slot-initialisation gradients and the weight gradient of the
     // input MLP's second layer -- goes to the side stream; the main stream continues with the input-gradient chain towards the
     // convolutions.  Joined before the convolutions.
-    const bool side_w = side_ && overlap_mode_ >= 3 && !cfg.use_bcdec && !fork_dvae;
+    const bool side_w = plan_.sa_wgrads_on_side;       // never together with fork_dvae: the plan puts the dVAE backward elsewhere then
     const Lane W = side_w ? dvae_lane() : L;
     if (side_w) RC(after(W, L, ev_fork_));
     const bool sa_in_bwd = sa_input_ == 1 && C == 64;          // the input LayerNorm + MLP backward as one kernel on the main stream
@@ -974,7 +936,7 @@ int SlateModel::bwd_encoder(const Lane& L, bool fork_dvae) {
     RC(colsum_launch(gB_, (long long)N * C, gmap_, B, N * C, 0, 1.f, L.scratch, L.scratch_floats, L));
     RC(lin_bwd_w(gmap_, C, gridT_, 4, G(w_.enc_pos.w), G(w_.enc_pos.b), N, C, 4, 1.f, L));
     if (fork_dvae || side_w) RC(after(L, dvae_lane(), ev_join_));      // the side stream has read gA_ (= dx): the convolution chain may reuse it
-    if (dw_mode_ == 2 && side2_) RC(after(L, dw_lane(L), ev_join2_));      // ... and the decoder's weight gradients are done: the convolutions run alone
+    if (plan_.dw == 2) RC(after(L, dw_lane(L), ev_join2_));      // ... and the decoder's weight gradients are done: the convolutions run alone
     // ---- CNN encoder, last layer first
     // the last layer's bias gradient is the column sum of the per-position sums gmap_ just taken for the positional embedding (4 MB),
     // not another pass over the [B*N, 64] gradient (537 MB)
@@ -1082,30 +1044,19 @@ int SlateModel::backward(hipStream_t st) {
         have_fwd_ = false;
         return 0;
     }
-    if (side_ && overlap_mode_ == 2) {
-        RC(bwd_decoder(L));
-        RC(bwd_encoder(L, true));           // forks the dVAE backward at the slot-attention launch, joins before the 5x5 convolutions
-    } else if (side_ && overlap_mode_ >= 3) {
-        // the dVAE backward (many short 64-wide products) runs beside the transformer-decoder backward and is joined before the
-        // slot-attention / convolution kernels, which then have the machine to themselves (their timings stay comparable)
+    // the dVAE backward only needs the forward's reconstruction gradient; plan_.bwd_dvae says what it runs beside
+    const BwdDvae at = plan_.bwd_dvae;
+    if (at == BwdDvae::BesideAll || at == BwdDvae::BesideDecoder) {
         RC(after(dvae_lane(), L, ev_fork_));
         RC(bwd_dvae(dvae_lane()));
-        RC(bwd_decoder(L));
-        // with the decoder's weight gradients on the side stream (OCRL_DW_SIDE) that stream may still be busy: it is joined inside
-        // bwd_encoder, before the convolutions, so the slot-attention backward and the input MLP overlap what is left of it
-        if (!dw_mode_) RC(after(L, dvae_lane(), ev_join_));
-        RC(bwd_encoder(L));
-    } else if (side_) {         // the dVAE backward only needs the forward's reconstruction gradient: it overlaps decoder + encoder
-        RC(after(dvae_lane(), L, ev_fork_));
-        RC(bwd_dvae(dvae_lane()));
-        RC(bwd_decoder(L));
-        RC(bwd_encoder(L));
-        RC(after(L, dvae_lane(), ev_join_));
-    } else {
-        RC(bwd_decoder(L));
-        RC(bwd_encoder(L));
-        RC(bwd_dvae(L));
     }
+    RC(bwd_decoder(L));
+    // with the decoder's weight gradients on lanes of their own the dVAE lane may still be busy: it is joined inside bwd_encoder, before
+    // the convolutions, so the slot-attention backward and the input MLP overlap what is left of it
+    if (at == BwdDvae::BesideDecoder && !plan_.dw) RC(after(L, dvae_lane(), ev_join_));
+    RC(bwd_encoder(L, at));
+    if (at == BwdDvae::BesideAll) RC(after(L, dvae_lane(), ev_join_));
+    if (at == BwdDvae::SerialLast) RC(bwd_dvae(L));
     have_fwd_ = false;
     return 0;
 }

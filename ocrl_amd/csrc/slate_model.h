@@ -8,6 +8,7 @@
 #include "kernels.h"
 #include "model_base.h"
 #include "slot_attn_host.h"
+#include "stream_plan.h"
 
 struct SlateConfig {
     int obs_size = 64, obs_channels = 3, vocab = 4096, d_model = 192, cnn_hidden = 64;
@@ -82,12 +83,14 @@ private:
     int conv_layer_wgrad(const float* x, const float* dy, float* dW, float* db, int Bn, int Hh, int Ww, int KS, int CIN, int cin_real,
                          const Lane& L);
     int pack_weights(const Lane& L, bool encoder_only = false);
-    int fwd_encoder(const StepInputs& in, const Lane& L, int fork_dvae = 0);
+    // fork: the plan's placement of the step's dVAE forward; the three placements inside the encoder fork it there.  encode() and the
+    // use_bcdec step, which run no dVAE branch, leave the default (as do forward()'s own two placements)
+    int fwd_encoder(const StepInputs& in, const Lane& L, FwdDvae fork = FwdDvae::Serial);
     int fwd_dvae(const StepInputs& in, const Lane& L);
     int fwd_decoder(const Lane& L, bool with_ce = true);
     int dvae_decode(int B, float* drecon, const Lane& L, const float* zin = nullptr);
     int bwd_decoder(const Lane& L);
-    int bwd_encoder(const Lane& L, bool fork_dvae = false);
+    int bwd_encoder(const Lane& L, BwdDvae fork = BwdDvae::SerialLast);      // AtSlotAttention forks (and joins) the step's dVAE backward here
     int bwd_dvae(const Lane& L);
     int pack_bcdec(const Lane& L);
     int fwd_bcdec(const Lane& L);
@@ -101,7 +104,7 @@ private:
     // The decoder's weight-gradient products: a stream of their own (OCRL_DW_SIDE=2), the dVAE lane (1) or the main lane (0).  The
     // operands such a product reads are never rewritten by the main stream during this backward: saved activations, and the per-block
     // gradient temporaries bg_[b] (bwd_decoder selects bg_[b] when this lane is not the main one, bg_[0] otherwise).
-    Lane dw_lane(const Lane& main) const { return dw_mode_ == 2 ? Lane{side2_, scratch3_, scratch_floats_} : dw_mode_ ? dvae_lane() : main; }
+    Lane dw_lane(const Lane& main) const { return plan_.dw == 2 ? Lane{side2_, scratch3_, scratch_floats_} : plan_.dw ? dvae_lane() : main; }
     // The one ordering primitive: everything enqueued on `producer` so far happens before whatever is enqueued on `waiter` from now
     // on (records `ev` on producer.st, makes waiter.st wait for it; nothing when both are the same stream).  Each call site passes the
     // event object it has always used -- ev_fork_ (main -> dVAE lane), ev_join_ (dVAE lane -> main), ev_join2_ (weight-gradient stream
@@ -151,7 +154,7 @@ private:
     float *scratch_ = nullptr;            // transient: split-k slabs, column-sum partials, wgrad slabs (main lane)
     size_t scratch_floats_ = 0;
     float* scratch2_ = nullptr;           // scratch of the dVAE lane
-    int overlap_mode_ = 0;                // OCRL_OVERLAP 0..5 (default 5), described where it is read in SlateModel::bind
+    StreamPlan plan_;                     // what OCRL_OVERLAP / OCRL_DW_SIDE / OCRL_TOKENS_LATE decide (stream_plan.h), built where the streams are created: the first bind
     hipStream_t side_ = nullptr;          // dVAE forward / backward overlap the encoder + decoder work (independent branches)
     hipEvent_t ev_fork_ = nullptr, ev_join_ = nullptr, ev_tokens_ = nullptr;
     float *zstat_ = nullptr, *zhstat_ = nullptr, *zlse_ = nullptr, *zdot_ = nullptr, *cestat_ = nullptr, *celse_ = nullptr, *cepart_ = nullptr;
@@ -166,7 +169,7 @@ private:
     PackEntry* sa_pack_dev_ = nullptr;    // sa_pack_table on the device
     int sa_pack_n_ = 0, sa_pack_max_ = 0;
     float *cw_fwd_[4], *cw_bwd_[4];       // CNN encoder conv packs
-    int conv_x3_ = -1;                    // OCRL_CONV_X3=1 (exploratory): the 5x5 / 64-channel layers on the split-precision bf16 kernel
+    int conv_x3_ = 0;                     // OCRL_CONV_X3=1 (exploratory): the 5x5 / 64-channel layers on the split-precision bf16 kernel
     std::map<const float*, const float*> x3_of_;      // fp32 pack -> its split-precision pack
     float *dw_fwd_[2], *dw_bwd_[2];       // dVAE decoder 3x3 conv packs
     float *w11p_;                         // [4,64] padded copy of the dVAE output conv
@@ -197,16 +200,14 @@ private:
     hipStream_t cap_ = nullptr;
     float* obs_stage_ = nullptr;
     unsigned long long* seed_dev_ = nullptr;
-    int dw_mode_ = 0;                     // OCRL_DW_SIDE: 0 weight gradients of the decoder on the main stream, 1 on the dVAE side stream, 2 on a stream of their own
-    hipStream_t side2_ = nullptr;
+    hipStream_t side2_ = nullptr;         // the decoder's weight-gradient products when plan_.dw == 2
     float* scratch3_ = nullptr;           // scratch of the weight-gradient stream
     hipEvent_t ev_dw_[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     hipEvent_t ev_join2_ = nullptr;
     int ev_dw_next_ = 0;
     float *attn_delta_;                   // [B,h,T] scratch of the attention backward
     float *attn_ds_ = nullptr;            // dS tiles of its hand-off form (null: the two-kernel form)
-    size_t attn_ds_floats_ = 0;
-    long long attn_ds_cap_ = -1;          // floats; -1: OCRL_ATTN_BWD / OCRL_ATTN_DS_MB not read yet
+    size_t attn_ds_floats_ = 0;           // attn_bwd_ds_carve_floats at max_batch, asked once by the constructor: the sizing pass and bind() lay out the same workspace
     float *lnf_, *lnf_mean_, *lnf_rstd_, *pred_;
     // gradient temporaries
     float *gqkv_;                         // [BT, 3d] fused dq|dk|dv

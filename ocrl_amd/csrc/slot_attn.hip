@@ -21,9 +21,9 @@
 // (kernels.h: sa_*_layout): few base pointers keep the kernels out of scratch.
 #include "common.h"
 #include "kernels.h"
+#include "switches.h"
 
 #define SA_C 64
-#include <stdlib.h>
 #define SA_TF 1024        // forward threads per workgroup (16 waves)
 #define SA_TB 512         // backward threads per workgroup (8 waves)
 #define SA_TLD 68         // row stride of the per-wave [16 positions][64 channels] LDS tile
@@ -1257,10 +1257,8 @@ int sa_plan(int K, int D, int H, int NH, SaPlan* pl) {
     int G = 1;
     if (NH == 1 && K <= 8 && 16 / K > 1) {
         // images per slot-side workgroup: as many as fill the 16 MFMA rows, unless the group's rows do not fit the LDS (wide slots)
-        static int gmode = -1;
-        if (gmode < 0) { const char* e = getenv("OCRL_SA_GROUP"); gmode = e ? atoi(e) : 1; }      // 0: one image per workgroup (development comparison)
         const int GM = 16 / K;
-        if (gmode && sa_fwd_smem(K, GM, D, H) <= SA_LDS_MAX && sa_bwd_smem(K, GM, D, H) <= SA_LDS_MAX) G = GM;
+        if (sw::process<sw::OCRL_SA_GROUP>() && sa_fwd_smem(K, GM, D, H) <= SA_LDS_MAX && sa_bwd_smem(K, GM, D, H) <= SA_LDS_MAX) G = GM;
     }
     pl->G = G; pl->NB = K > 8 ? 2 : 1; pl->KB = K > 8 ? (K + 1) / 2 : G * K; pl->KS = NH * K;
     pl->smem_fwd = sa_fwd_smem(K, G, D, H, NH); pl->smem_bwd = sa_bwd_smem(K, G, D, H, NH);
@@ -1279,21 +1277,20 @@ size_t sa_parts_floats_host(int B, int K) { return (size_t)(SA_MAX_BLOCKS + B) *
 // bound of 3 with 4 workgroups per CU ran one full round and a second one a third full: the round-2 forward); at least 8 tiles of 16
 // positions per workgroup (2 per wave)
 static int sa_splits(int B, int N, int per_cu) {
-    static int ncu = 0, mult = 0;
+    static int ncu = 0;
     if (!ncu) {
         int dev = 0;
         hipDeviceProp_t prop;
         ncu = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ? prop.multiProcessorCount : 256;
-        const char* e = getenv("OCRL_SA_WGS");          // streaming workgroups per CU per launch (development knob; 0 = the kernel's own)
-        mult = e ? atoi(e) : 0;
     }
+    const int mult = (int)sw::process<sw::OCRL_SA_WGS>();          // streaming workgroups per CU per launch (development knob; 0 = the kernel's own)
     const int ntile = (N + 15) / 16;
     int target = (mult > 0 ? mult : per_cu) * ncu;
     if (target > SA_MAX_BLOCKS) target = SA_MAX_BLOCKS;
     int ns = B <= target ? target / B : 1;              // rounded down: never more workgroups than one full round
     // OCRL_SA_NS (read at every call): a fixed split count, so that a small batch groups its partial sums exactly like a large one --
     // tests/test_gpu_benchshape.py compares a B = 128 step with a B = 1 step of the same image bit for bit
-    if (const char* f = getenv("OCRL_SA_NS")) { const int v = atoi(f); if (v > 0 && (long long)B * v <= SA_MAX_BLOCKS) ns = v; }
+    if (const int v = (int)sw::call<sw::OCRL_SA_NS>(); v > 0 && (long long)B * v <= SA_MAX_BLOCKS) ns = v;
     if (ns > ntile / 8) ns = ntile / 8;
     return ns < 1 ? 1 : ns;
 }
@@ -1316,8 +1313,7 @@ static int sa_launch_kg(const SlotAttnArgs& a, const SaPlan& pl, int backward, h
         OCRL_HIP(hipFuncSetAttribute((const void*)sa_slot_bwd_kernel<K, G>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
         attr_b = smem;
     }
-    static int fwd_form = -1;          // OCRL_SA_FWD=1: the round-2 streaming forward (slots on the lanes); default: positions on the lanes
-    if (fwd_form < 0) { const char* e = getenv("OCRL_SA_FWD"); fwd_form = e ? atoi(e) : 2; }
+    const int fwd_form = (int)sw::process<sw::OCRL_SA_FWD>();          // OCRL_SA_FWD=1: the round-2 streaming forward (slots on the lanes); default: positions on the lanes
     // resident streaming workgroups per CU (launch bounds): forward 4 (3 for the round-2 form), backward 2 -- the backward runs two rounds
     const int NS = sa_splits(a.B, a.N, backward ? 4 : (fwd_form == 1 ? 3 : 4));
     const int ngrp = (a.B + G - 1) / G;
@@ -1331,8 +1327,7 @@ static int sa_launch_kg(const SlotAttnArgs& a, const SaPlan& pl, int backward, h
             hipLaunchKernelGGL((sa_slot_fwd_kernel<K, G>), dim3(ngrp), dim3(SA_TF), smem, st, a, wo, so, t, NS);
         }
     } else {
-        static int bwd_form = -1;          // OCRL_SA_BWD=1: the round-2 streaming backward; default: positions on the lanes
-        if (bwd_form < 0) { const char* e = getenv("OCRL_SA_BWD"); bwd_form = e ? atoi(e) : 2; }
+        const int bwd_form = (int)sw::process<sw::OCRL_SA_BWD>();          // OCRL_SA_BWD=1: the round-2 streaming backward; default: positions on the lanes
         static_assert(16 * SA_WT_LD <= 2 * 16 * SA_WLD, "the weight patch of the second form must fit the first form's two patches");
         const size_t smem_stream = (size_t)(2 * KP * SA_C + 64 + (SA_TS / 64) * (16 * SA_TLD + 2 * 16 * SA_WLD)) * 4;
         hipLaunchKernelGGL((sa_slot_bwd_kernel<K, G>), dim3(ngrp), dim3(SA_TB), smem, st, a, wo, so, go, -1, a.I - 1, NS);
