@@ -11,6 +11,14 @@
 // and feeds P / dS the same way into  dV^T += dO^T P  and  dK^T += Q^T dS.
 //
 // One workgroup = 4 waves = 64 queries (or 64 keys); tiles of 64 keys (queries) stream through LDS.
+//
+// Written once and called by every kernel that needs it: fa_triangle_pos (blockIdx -> block, head, image), fa_fetch / fa_commit,
+// fa_quad_draws, fa_drop_scale, fa_store_row (the query-owning kernels; the two key-owning ones write their dv, dk pair out).  The tile loops, the score products, the transposed accumulate and the key-owning
+// sub-tile step are still written out per kernel, on purpose: each of them, moved into a function, changed the compiler's unswitching,
+// register allocation or spilling in some instantiation (profiles/attn_steps_kernel_table.txt), and these kernels are held
+// to the instruction streams they were measured with.  Whoever edits one of those steps edits its copies: forward <-> attn_bwd_q_kernel
+// (stream, S^T products, accumulate), attn_bwd_q_kernel <-> attn_bwd_dq_kernel (accumulate), attn_bwd_kv_kernel <-> attn_bwd_fused_kernel
+// (fragment loads, sub-tile step, dv / dk stores).
 #include "common.h"
 #include "kernels.h"
 #include "switches.h"
@@ -23,30 +31,15 @@
 #define FA_BWD_WGS 3      // workgroups per CU the backward kernels are compiled for (register budget 512 / FA_BWD_WGS per lane)
 #endif
 
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
-
 template <int DH>
 struct FaCfg {
     static constexpr int NC = DH / 16;       // 16-wide chunks of the head dimension
     static constexpr int LD = DH + 4;        // LDS row stride (floats)
 };
 
-// cooperative load of a [64 x DH] tile (rows row0.., zero beyond T) of one head into LDS, optionally scaled
-template <int DH>
-__device__ inline void fa_load_tile(float* s, const float* __restrict__ g, long long bt0, int row0, int T, int d, int hoff, float scale) {
-    constexpr int F4 = DH / 4;
-    constexpr int LD = FaCfg<DH>::LD;
-    for (int idx = threadIdx.x; idx < FA_BLK * F4; idx += 256) {
-        const int c4 = idx % F4, r = idx / F4;
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (row0 + r < T) v = *reinterpret_cast<const float4*>(g + (bt0 + row0 + r) * d + hoff + c4 * 4);
-        v.x *= scale; v.y *= scale; v.z *= scale; v.w *= scale;
-        *reinterpret_cast<float4*>(s + r * LD + c4 * 4) = v;
-    }
-}
-
-// Register-staged variant: fa_fetch issues the global loads of a tile into registers, fa_commit writes them to LDS one iteration
-// later, so the memory round trip of tile t+1 overlaps the MFMA work on tile t instead of sitting between two barriers.
+// A [64 x DH] tile of one head (rows row0.., zero beyond T) goes to LDS through registers: fa_fetch issues the global loads of a tile,
+// fa_commit writes them to LDS, optionally scaled, one iteration later, so the memory round trip of tile t+1 overlaps the MFMA work on
+// tile t instead of sitting between two barriers.
 template <int DH> struct FaRegs { static constexpr int N = (FA_BLK * (DH / 4) + 255) / 256; };
 template <int DH>
 __device__ inline void fa_fetch(float4 (&r)[FaRegs<DH>::N], const float* __restrict__ g, long long bt0, int row0, int T, int d, int hoff) {
@@ -77,7 +70,53 @@ __device__ inline int fa_block_index(int j, long long bh, int nblk) {
     return (int)((j + rot) % nblk);
 }
 
-#define MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
+// blockIdx -> where a workgroup of the four triangle kernels stands
+struct FaPos {
+    int blk;                 // block of the causal triangle it owns: 64 queries, or 64 keys
+    int pair;                // its (image, head) pair, counted within the launch (the chunk, in the hand-off form)
+    int hd;                  // head
+    long long bt0, bh;       // first token row of its image b (counted over the whole batch), b * h + hd
+};
+// Longest-first dispatch: blockIdx runs over the tile-count classes from the heaviest to the lightest, all (image, head) pairs of a
+// class together, so the launch ends on one-tile blocks instead of on a 16-tile block that started late (with the rotated
+// (image, head)-major order a third of the wave slots sat empty: SQ_WAVE_CYCLES).  Every class has B*h blocks dealt round-robin to the
+// XCDs, so each XCD still gets the same mix.  LAST_HEAVIEST: a query block meets the key tiles up to its own, so the last query block
+// is the heaviest (nblk key tiles); a key block meets the query tiles from its own on, so key block 0 is.  b0: first image of the launch.
+// (int division, and the block index reused as the pair index: the kernels' scalar code is the one this arithmetic gives.)
+template <bool LAST_HEAVIEST>
+__device__ __forceinline__ FaPos fa_triangle_pos(int nblk, const AttnArgs& p, int b0) {
+    FaPos at;
+    int bid = blockIdx.x;
+    const int nbh = gridDim.x / nblk;
+    at.blk = FA_LPT ? (LAST_HEAVIEST ? nblk - 1 - bid / nbh : bid / nbh) : fa_block_index(bid % nblk, bid / nblk, nblk);
+    bid = FA_LPT ? bid % nbh : bid / nblk;
+    at.pair = bid;
+    at.hd = bid % p.h;
+    const long long b = b0 + bid / p.h;
+    at.bt0 = b * p.T;
+    at.bh = b * p.h + at.hd;
+    return at;
+}
+
+// what dropout multiplies a kept probability by
+__device__ __forceinline__ float fa_drop_scale(float p) { return p > 0.f ? 1.0f / (1.0f - p) : 1.f; }
+
+// The key-owning kernels draw once per lane and sub-tile: lane (g, li) draws for query 4g + (li&3) and its key group, and the quad
+// exchanges the draws with DPP broadcasts (quad_perm), hq[j] = the draw of the quad's lane j: 1 hash per lane instead of 4.
+__device__ __forceinline__ void fa_quad_draws(uint2 (&hq)[4], uint2 hb) {
+    hq[0] = make_uint2(__builtin_amdgcn_update_dpp(0, (int)hb.x, 0x00, 0xF, 0xF, false), __builtin_amdgcn_update_dpp(0, (int)hb.y, 0x00, 0xF, 0xF, false));
+    hq[1] = make_uint2(__builtin_amdgcn_update_dpp(0, (int)hb.x, 0x55, 0xF, 0xF, false), __builtin_amdgcn_update_dpp(0, (int)hb.y, 0x55, 0xF, 0xF, false));
+    hq[2] = make_uint2(__builtin_amdgcn_update_dpp(0, (int)hb.x, 0xAA, 0xF, 0xF, false), __builtin_amdgcn_update_dpp(0, (int)hb.y, 0xAA, 0xF, 0xF, false));
+    hq[3] = make_uint2(__builtin_amdgcn_update_dpp(0, (int)hb.x, 0xFF, 0xF, 0xF, false), __builtin_amdgcn_update_dpp(0, (int)hb.y, 0xFF, 0xF, 0xF, false));
+}
+
+// a lane's four accumulator rows of every 16-wide chunk, scaled, to token row `row` of one head (the caller has checked row < T)
+template <int DH>
+__device__ __forceinline__ void fa_store_row(float* __restrict__ dst, long long bt0, int row, int ld, int hoff, int g, const f32x4 (&acc)[FaCfg<DH>::NC], float scale) {
+#pragma unroll
+    for (int c = 0; c < FaCfg<DH>::NC; ++c)
+        *reinterpret_cast<float4*>(dst + (bt0 + row) * ld + hoff + 16 * c + 4 * g) = make_float4(acc[c][0] * scale, acc[c][1] * scale, acc[c][2] * scale, acc[c][3] * scale);
+}
 
 // ------------------------------------------------------------------------------------------- forward
 template <int DH>
@@ -86,23 +125,14 @@ __global__ __launch_bounds__(256, 4) void attn_fwd_kernel(AttnArgs p) {
     __shared__ __attribute__((aligned(16))) float Ks[FA_BLK * LD];
     __shared__ __attribute__((aligned(16))) float Vs[FA_BLK * LD];
     const int nqb = (p.T + FA_BLK - 1) / FA_BLK;
-    // longest-first dispatch: blockIdx runs over the tile-count classes from the heaviest (last query block: nqb key tiles) to the
-    // lightest, all (image, head) pairs of a class together, so the launch ends on one-tile blocks instead of on a 16-tile block
-    // that started late (with the rotated (image, head)-major order a third of the wave slots sat empty: SQ_WAVE_CYCLES).
-    // Every class has B*h blocks dealt round-robin to the XCDs, so each XCD still gets the same mix.
-    int bid = blockIdx.x;
-    const int nbh = gridDim.x / nqb;
-    const int qb = FA_LPT ? nqb - 1 - bid / nbh : fa_block_index(bid % nqb, bid / nqb, nqb);
-    bid = FA_LPT ? bid % nbh : bid / nqb;
-    const int hd = bid % p.h;
-    const long long b = bid / p.h;
+    const FaPos at = fa_triangle_pos<true>(nqb, p, 0);
+    const int qb = at.blk, hd = at.hd;
+    const long long bt0 = at.bt0, bh = at.bh;
     const int T = p.T, T4 = attn_drop_ld(p.T), d = p.ld, hoff = hd * DH;
-    const long long bt0 = b * T;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int li = lane & 15, g = lane >> 4;
     const int q_abs = qb * FA_BLK + wv * 16 + li;            // this lane's query (column of S^T)
     const float scale = rsqrtf((float)DH);
-    const long long bh = b * p.h + hd;
 
     float4 qf[NC];
 #pragma unroll
@@ -111,12 +141,12 @@ __global__ __launch_bounds__(256, 4) void attn_fwd_kernel(AttnArgs p) {
         if (q_abs < T) v = *reinterpret_cast<const float4*>(p.q + (bt0 + q_abs) * d + hoff + 16 * c + 4 * g);
         qf[c] = make_float4(v.x * scale, v.y * scale, v.z * scale, v.w * scale);
     }
-    f32x4_t o[NC];
+    f32x4 o[NC];
 #pragma unroll
-    for (int c = 0; c < NC; ++c) o[c] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+    for (int c = 0; c < NC; ++c) o[c] = (f32x4){0.f, 0.f, 0.f, 0.f};
     float m = -INFINITY, l = 0.f;
     const uint32_t thr = drop_thresh(p.p);
-    const float dsc = p.p > 0.f ? 1.0f / (1.0f - p.p) : 1.f;
+    const float dsc = fa_drop_scale(p.p);
 
     float4 rk[FaRegs<DH>::N], rv[FaRegs<DH>::N];
     fa_fetch<DH>(rk, p.k, bt0, 0, T, d, hoff);
@@ -130,9 +160,9 @@ __global__ __launch_bounds__(256, 4) void attn_fwd_kernel(AttnArgs p) {
             fa_fetch<DH>(rk, p.k, bt0, (kt + 1) * FA_BLK, T, d, hoff);
             fa_fetch<DH>(rv, p.v, bt0, (kt + 1) * FA_BLK, T, d, hoff);
         }
-        f32x4_t s[4];
+        f32x4 s[4];
 #pragma unroll
-        for (int st = 0; st < 4; ++st) s[st] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+        for (int st = 0; st < 4; ++st) s[st] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int c = 0; c < NC; ++c) {
             float4 a[4];
@@ -214,10 +244,7 @@ __global__ __launch_bounds__(256, 4) void attn_fwd_kernel(AttnArgs p) {
         }
     }
     if (q_abs < T) {
-        const float inv = 1.0f / l;
-#pragma unroll
-        for (int c = 0; c < NC; ++c)
-            *reinterpret_cast<float4*>(p.o + (bt0 + q_abs) * p.d + hoff + 16 * c + 4 * g) = make_float4(o[c][0] * inv, o[c][1] * inv, o[c][2] * inv, o[c][3] * inv);
+        fa_store_row<DH>(p.o, bt0, q_abs, p.d, hoff, g, o, 1.0f / l);
         if (g == 0) p.lse[bh * T + q_abs] = m + __logf(l);
     }
 }
@@ -268,21 +295,16 @@ __global__ __launch_bounds__(256, FA_BWD_WGS) void attn_bwd_kv_kernel(AttnArgs p
     __shared__ __attribute__((aligned(16))) float Gs[FA_BLK * LD];      // dO
     __shared__ float Ls[FA_BLK], Ds[FA_BLK];
     const int nkb = (p.T + FA_BLK - 1) / FA_BLK;
-    int bid = blockIdx.x;                                   // longest first: key block 0 meets every query tile
-    const int nbh = gridDim.x / nkb;
-    const int kb = FA_LPT ? bid / nbh : fa_block_index(bid % nkb, bid / nkb, nkb);
-    bid = FA_LPT ? bid % nbh : bid / nkb;
-    const int hd = bid % p.h;
-    const long long b = p.b0 + bid / p.h;
+    const FaPos at = fa_triangle_pos<false>(nkb, p, p.b0);
+    const int kb = at.blk, hd = at.hd;
+    const long long bt0 = at.bt0, bh = at.bh;
     const int T = p.T, T4 = attn_drop_ld(p.T), d = p.ld, hoff = hd * DH;
-    const long long bt0 = b * T;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int li = lane & 15, g = lane >> 4;
     const int k_abs = kb * FA_BLK + wv * 16 + li;                       // this lane's key (column of S)
     const float scale = rsqrtf((float)DH);
-    const long long bh = b * p.h + hd;
     // this lane's element (query 4 g, key 16 wv + li) of tile (0, kb) of the chunk's (image, head) triangle
-    float* const dsw = HANDOFF ? p.ds + ((size_t)bid * fa_ds_tiles(nkb) + kb) * FA_DS_TILE + 4 * g * FA_BLK + wv * 16 + li : nullptr;
+    float* const dsw = HANDOFF ? p.ds + ((size_t)at.pair * fa_ds_tiles(nkb) + kb) * FA_DS_TILE + 4 * g * FA_BLK + wv * 16 + li : nullptr;
 
     float4 kf[NC], vf[NC];
 #pragma unroll
@@ -294,11 +316,11 @@ __global__ __launch_bounds__(256, FA_BWD_WGS) void attn_bwd_kv_kernel(AttnArgs p
             vf[c] = *reinterpret_cast<const float4*>(p.v + (bt0 + k_abs) * d + hoff + 16 * c + 4 * g);
         }
     }
-    f32x4_t dk[NC], dv[NC];
+    f32x4 dk[NC], dv[NC];
 #pragma unroll
-    for (int c = 0; c < NC; ++c) { dk[c] = (f32x4_t){0.f, 0.f, 0.f, 0.f}; dv[c] = dk[c]; }
+    for (int c = 0; c < NC; ++c) { dk[c] = (f32x4){0.f, 0.f, 0.f, 0.f}; dv[c] = dk[c]; }
     const uint32_t thr = drop_thresh(p.p);
-    const float dsc = p.p > 0.f ? 1.0f / (1.0f - p.p) : 1.f;
+    const float dsc = fa_drop_scale(p.p);
 
     float4 rq[FaRegs<DH>::N], rg[FaRegs<DH>::N];
     float rl = 0.f, rd = 0.f;
@@ -322,7 +344,7 @@ __global__ __launch_bounds__(256, FA_BWD_WGS) void attn_bwd_kv_kernel(AttnArgs p
         float* const dst = HANDOFF ? dsw + fa_ds_tiles(qt) * FA_DS_TILE : nullptr;
 #pragma unroll
         for (int sq = 0; sq < 4; ++sq) {
-            f32x4_t s = (f32x4_t){0.f, 0.f, 0.f, 0.f}, dp = s;
+            f32x4 s = (f32x4){0.f, 0.f, 0.f, 0.f}, dp = s;
 #pragma unroll
             for (int c = 0; c < NC; ++c) {
                 const float4 a = *reinterpret_cast<const float4*>(Qs + (16 * sq + li) * LD + 16 * c + 4 * g);
@@ -337,8 +359,7 @@ __global__ __launch_bounds__(256, FA_BWD_WGS) void attn_bwd_kv_kernel(AttnArgs p
                 dp = MFMA16(e.w, vf[c].w, dp);
             }
             // s[r] = S[query 16*sq+4g+r][key k_abs], dp[r] likewise.  Dropout: the decision for (query, key) lives in the
-            // 64-bit draw of (query, key/4); lane (g, li) draws for query 4g + (li&3) and its key group, and the quad
-            // exchanges the draws with DPP broadcasts (1 hash per lane per sub-tile instead of 4).
+            // 64-bit draw of (query, key/4); the lane draws for one query of its four and the quad shares the draws (fa_quad_draws).
             uint2 hb = make_uint2(0u, 0u);
             if (p.p > 0.f) {
                 const int qh = qt * FA_BLK + 16 * sq + 4 * g + (li & 3);
@@ -346,11 +367,8 @@ __global__ __launch_bounds__(256, FA_BWD_WGS) void attn_bwd_kv_kernel(AttnArgs p
                 hb = rng_bits4(p.seed, p.site, idx >> 2);
             }
             uint2 hq[4];
-            hq[0] = make_uint2(__builtin_amdgcn_update_dpp(0, (int)hb.x, 0x00, 0xF, 0xF, false), __builtin_amdgcn_update_dpp(0, (int)hb.y, 0x00, 0xF, 0xF, false));
-            hq[1] = make_uint2(__builtin_amdgcn_update_dpp(0, (int)hb.x, 0x55, 0xF, 0xF, false), __builtin_amdgcn_update_dpp(0, (int)hb.y, 0x55, 0xF, 0xF, false));
-            hq[2] = make_uint2(__builtin_amdgcn_update_dpp(0, (int)hb.x, 0xAA, 0xF, 0xF, false), __builtin_amdgcn_update_dpp(0, (int)hb.y, 0xAA, 0xF, 0xF, false));
-            hq[3] = make_uint2(__builtin_amdgcn_update_dpp(0, (int)hb.x, 0xFF, 0xF, 0xF, false), __builtin_amdgcn_update_dpp(0, (int)hb.y, 0xFF, 0xF, 0xF, false));
-            f32x4_t pd, ds;
+            fa_quad_draws(hq, hb);
+            f32x4 pd, ds;
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int ql = 16 * sq + 4 * g + r;
@@ -398,23 +416,14 @@ __global__ __launch_bounds__(256, FA_BWD_WGS) void attn_bwd_q_kernel(AttnArgs p)
     __shared__ __attribute__((aligned(16))) float Ks[FA_BLK * LD];
     __shared__ __attribute__((aligned(16))) float Vs[FA_BLK * LD];
     const int nqb = (p.T + FA_BLK - 1) / FA_BLK;
-    // longest-first dispatch: blockIdx runs over the tile-count classes from the heaviest (last query block: nqb key tiles) to the
-    // lightest, all (image, head) pairs of a class together, so the launch ends on one-tile blocks instead of on a 16-tile block
-    // that started late (with the rotated (image, head)-major order a third of the wave slots sat empty: SQ_WAVE_CYCLES).
-    // Every class has B*h blocks dealt round-robin to the XCDs, so each XCD still gets the same mix.
-    int bid = blockIdx.x;
-    const int nbh = gridDim.x / nqb;
-    const int qb = FA_LPT ? nqb - 1 - bid / nbh : fa_block_index(bid % nqb, bid / nqb, nqb);
-    bid = FA_LPT ? bid % nbh : bid / nqb;
-    const int hd = bid % p.h;
-    const long long b = bid / p.h;
+    const FaPos at = fa_triangle_pos<true>(nqb, p, 0);
+    const int qb = at.blk, hd = at.hd;
+    const long long bt0 = at.bt0, bh = at.bh;
     const int T = p.T, T4 = attn_drop_ld(p.T), d = p.ld, hoff = hd * DH;
-    const long long bt0 = b * T;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int li = lane & 15, g = lane >> 4;
     const int q_abs = qb * FA_BLK + wv * 16 + li;
     const float scale = rsqrtf((float)DH);
-    const long long bh = b * p.h + hd;
 
     float4 qf[NC], gf[NC];
 #pragma unroll
@@ -429,11 +438,11 @@ __global__ __launch_bounds__(256, FA_BWD_WGS) void attn_bwd_q_kernel(AttnArgs p)
     }
     const float lse = q_abs < T ? p.lse[bh * T + q_abs] : 0.f;
     const float dlt = q_abs < T ? p.delta[bh * T + q_abs] : 0.f;
-    f32x4_t dq[NC];
+    f32x4 dq[NC];
 #pragma unroll
-    for (int c = 0; c < NC; ++c) dq[c] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+    for (int c = 0; c < NC; ++c) dq[c] = (f32x4){0.f, 0.f, 0.f, 0.f};
     const uint32_t thr = drop_thresh(p.p);
-    const float dsc = p.p > 0.f ? 1.0f / (1.0f - p.p) : 1.f;
+    const float dsc = fa_drop_scale(p.p);
 
     float4 rk[FaRegs<DH>::N], rv[FaRegs<DH>::N];
     fa_fetch<DH>(rk, p.k, bt0, 0, T, d, hoff);
@@ -447,9 +456,9 @@ __global__ __launch_bounds__(256, FA_BWD_WGS) void attn_bwd_q_kernel(AttnArgs p)
             fa_fetch<DH>(rk, p.k, bt0, (kt + 1) * FA_BLK, T, d, hoff);
             fa_fetch<DH>(rv, p.v, bt0, (kt + 1) * FA_BLK, T, d, hoff);
         }
-        f32x4_t sS[4], sP[4];
+        f32x4 sS[4], sP[4];
 #pragma unroll
-        for (int st = 0; st < 4; ++st) { sS[st] = (f32x4_t){0.f, 0.f, 0.f, 0.f}; sP[st] = sS[st]; }
+        for (int st = 0; st < 4; ++st) { sS[st] = (f32x4){0.f, 0.f, 0.f, 0.f}; sP[st] = sS[st]; }
 #pragma unroll
         for (int c = 0; c < NC; ++c) {
             float4 a[4], e[4];
@@ -505,12 +514,7 @@ __global__ __launch_bounds__(256, FA_BWD_WGS) void attn_bwd_q_kernel(AttnArgs p)
             __builtin_amdgcn_sched_barrier(0);
         }
     }
-    if (q_abs < T) {
-#pragma unroll
-        for (int c = 0; c < NC; ++c)
-            *reinterpret_cast<float4*>(p.dq + (bt0 + q_abs) * d + hoff + 16 * c + 4 * g) =
-                make_float4(dq[c][0] * scale, dq[c][1] * scale, dq[c][2] * scale, dq[c][3] * scale);
-    }
+    if (q_abs < T) fa_store_row<DH>(p.dq, bt0, q_abs, d, hoff, g, dq, scale);
 }
 
 // ------------------------------------------------------------------------------------------- backward: dQ from stored dS
@@ -524,40 +528,36 @@ __global__ __launch_bounds__(256, 4) void attn_bwd_dq_kernel(AttnArgs p) {
     constexpr int NC = FaCfg<DH>::NC, LD = FaCfg<DH>::LD;
     __shared__ __attribute__((aligned(16))) float Ks[FA_BLK * LD];
     const int nqb = (p.T + FA_BLK - 1) / FA_BLK;
-    int bid = blockIdx.x;                                   // longest first, as attn_bwd_q_kernel
-    const int nbh = gridDim.x / nqb;
-    const int qb = FA_LPT ? nqb - 1 - bid / nbh : fa_block_index(bid % nqb, bid / nqb, nqb);
-    bid = FA_LPT ? bid % nbh : bid / nqb;
-    const int hd = bid % p.h;
-    const long long b = p.b0 + bid / p.h;
+    const FaPos at = fa_triangle_pos<true>(nqb, p, p.b0);
+    const int qb = at.blk, hd = at.hd;
+    const long long bt0 = at.bt0;
     const int T = p.T, d = p.ld, hoff = hd * DH;
-    const long long bt0 = b * T;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int li = lane & 15, g = lane >> 4;
     const int q_abs = qb * FA_BLK + wv * 16 + li;
     const float scale = rsqrtf((float)DH);
     // this lane's row of tile (qb, 0): tile kt follows at kt * FA_DS_TILE, sub-tile st at 16 * st
-    const float* const dsr = p.ds + ((size_t)bid * fa_ds_tiles(nqb) + fa_ds_tiles(qb)) * FA_DS_TILE + (wv * 16 + li) * FA_BLK + 4 * g;
+    const float* const dsr = p.ds + ((size_t)at.pair * fa_ds_tiles(nqb) + fa_ds_tiles(qb)) * FA_DS_TILE + (wv * 16 + li) * FA_BLK + 4 * g;
 
-    f32x4_t dq[NC];
+    f32x4 dq[NC];
 #pragma unroll
-    for (int c = 0; c < NC; ++c) dq[c] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+    for (int c = 0; c < NC; ++c) dq[c] = (f32x4){0.f, 0.f, 0.f, 0.f};
     float4 rk[FaRegs<DH>::N];
-    f32x4_t rs[4];
+    f32x4 rs[4];
     fa_fetch<DH>(rk, p.k, bt0, 0, T, d, hoff);
 #pragma unroll
-    for (int st = 0; st < 4; ++st) rs[st] = *reinterpret_cast<const f32x4_t*>(dsr + 16 * st);
+    for (int st = 0; st < 4; ++st) rs[st] = *reinterpret_cast<const f32x4*>(dsr + 16 * st);
     for (int kt = 0; kt <= qb; ++kt) {
         __syncthreads();
         fa_commit<DH>(Ks, rk, 1.f);
         __syncthreads();
-        f32x4_t sS[4];
+        f32x4 sS[4];
 #pragma unroll
         for (int st = 0; st < 4; ++st) sS[st] = rs[st];          // dS^T of this tile
         if (kt < qb) {
             fa_fetch<DH>(rk, p.k, bt0, (kt + 1) * FA_BLK, T, d, hoff);
 #pragma unroll
-            for (int st = 0; st < 4; ++st) rs[st] = *reinterpret_cast<const f32x4_t*>(dsr + (size_t)(kt + 1) * FA_DS_TILE + 16 * st);
+            for (int st = 0; st < 4; ++st) rs[st] = *reinterpret_cast<const f32x4*>(dsr + (size_t)(kt + 1) * FA_DS_TILE + 16 * st);
         }
         float ak[2][4][NC];                              // K^T operands one sub-tile ahead of their MFMAs (see the forward kernel)
 #pragma unroll
@@ -580,12 +580,7 @@ __global__ __launch_bounds__(256, 4) void attn_bwd_dq_kernel(AttnArgs p) {
             __builtin_amdgcn_sched_barrier(0);
         }
     }
-    if (q_abs < T) {
-#pragma unroll
-        for (int c = 0; c < NC; ++c)
-            *reinterpret_cast<float4*>(p.dq + (bt0 + q_abs) * d + hoff + 16 * c + 4 * g) =
-                make_float4(dq[c][0] * scale, dq[c][1] * scale, dq[c][2] * scale, dq[c][3] * scale);
-    }
+    if (q_abs < T) fa_store_row<DH>(p.dq, bt0, q_abs, d, hoff, g, dq, scale);
 }
 
 // ------------------------------------------------------------------------------------------- backward, one pass: dK, dV and dQ
@@ -616,7 +611,7 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_fused_kernel(AttnArgs p) {
     const float scale = rsqrtf((float)DH);
     const long long bh = b * p.h + hd;
     const uint32_t thr = drop_thresh(p.p);
-    const float dsc = p.p > 0.f ? 1.0f / (1.0f - p.p) : 1.f;
+    const float dsc = fa_drop_scale(p.p);
     const int nqt = (T + FA_BLK - 1) / FA_BLK, nkb = (T + FB_KB - 1) / FB_KB;
     constexpr int F4 = DH / 4;
 #pragma unroll 1
@@ -640,9 +635,9 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_fused_kernel(AttnArgs p) {
 #pragma unroll
             for (int c = 0; c < NC; ++c) kq[s][c] = key < T ? p.k[(bt0 + key) * d + hoff + 16 * c + li] * scale : 0.f;
         }
-        f32x4_t dk[NC], dv[NC];
+        f32x4 dk[NC], dv[NC];
 #pragma unroll
-        for (int c = 0; c < NC; ++c) { dk[c] = (f32x4_t){0.f, 0.f, 0.f, 0.f}; dv[c] = dk[c]; }
+        for (int c = 0; c < NC; ++c) { dk[c] = (f32x4){0.f, 0.f, 0.f, 0.f}; dv[c] = dk[c]; }
 #pragma unroll 1
         for (int qt = (kb * FB_KB) / FA_BLK; qt < nqt; ++qt) {
             __syncthreads();                                  // the previous pair is done with Qs / Gs / Ss / Rs
@@ -664,7 +659,7 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_fused_kernel(AttnArgs p) {
             __syncthreads();
 #pragma unroll
             for (int sq = 0; sq < 4; ++sq) {
-                f32x4_t s = (f32x4_t){0.f, 0.f, 0.f, 0.f}, dp = s;
+                f32x4 s = (f32x4){0.f, 0.f, 0.f, 0.f}, dp = s;
 #pragma unroll
                 for (int c = 0; c < NC; ++c) {
                     const float4 a = *reinterpret_cast<const float4*>(Qs + (16 * sq + li) * LD + 16 * c + 4 * g);
@@ -685,11 +680,8 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_fused_kernel(AttnArgs p) {
                     hb = rng_bits4(p.seed, p.site, idx >> 2);
                 }
                 uint2 hq[4];
-                hq[0] = make_uint2(__builtin_amdgcn_update_dpp(0, (int)hb.x, 0x00, 0xF, 0xF, false), __builtin_amdgcn_update_dpp(0, (int)hb.y, 0x00, 0xF, 0xF, false));
-                hq[1] = make_uint2(__builtin_amdgcn_update_dpp(0, (int)hb.x, 0x55, 0xF, 0xF, false), __builtin_amdgcn_update_dpp(0, (int)hb.y, 0x55, 0xF, 0xF, false));
-                hq[2] = make_uint2(__builtin_amdgcn_update_dpp(0, (int)hb.x, 0xAA, 0xF, 0xF, false), __builtin_amdgcn_update_dpp(0, (int)hb.y, 0xAA, 0xF, 0xF, false));
-                hq[3] = make_uint2(__builtin_amdgcn_update_dpp(0, (int)hb.x, 0xFF, 0xF, 0xF, false), __builtin_amdgcn_update_dpp(0, (int)hb.y, 0xFF, 0xF, 0xF, false));
-                f32x4_t pd, ds;
+                fa_quad_draws(hq, hb);
+                f32x4 pd, ds;
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int ql = 16 * sq + 4 * g + r;
@@ -721,9 +713,9 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_fused_kernel(AttnArgs p) {
             }
             __syncthreads();                                  // dS of the pair is complete
             // ---- dQ[16 queries of qs][DH] over this wave's 64 keys: A = dS[q][key] (four consecutive keys per ds_read_b128), B = kq
-            f32x4_t dq[NC];
+            f32x4 dq[NC];
 #pragma unroll
-            for (int c = 0; c < NC; ++c) dq[c] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+            for (int c = 0; c < NC; ++c) dq[c] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const float4 a4 = *reinterpret_cast<const float4*>(Ss + (16 * qs + li) * SLD + kh * 64 + 16 * j + 4 * g);

@@ -6,6 +6,8 @@
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
+// one v_mfma_f32_16x16x4_f32 step: c += a (16 x 4, one float per lane) * b (4 x 16), c a lane's four accumulator rows
+#define MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
 
 // ---- error convention: every C-ABI entry returns 0 on success; message via ocrl_last_error()
 void ocrl_set_error(const char* fmt, ...);

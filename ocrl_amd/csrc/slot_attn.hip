@@ -30,9 +30,6 @@
 #define SA_WLD 17         // row stride of the per-wave [16 positions][16 slots] LDS tiles
 #define SA_MAX_BLOCKS 2048 // upper bound of streaming workgroups per launch the partial buffer is sized for (plus one per image)
 
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
-#define MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
-
 __device__ inline float sigmoidf_(float x) { return 1.0f / (1.0f + __expf(-x)); }
 // All-reduce over the 16 lanes sharing lane>>4 (one DPP row) by row rotations 8, 4, 2, 1: VALU-speed DPP moves, no trip
 // through the LDS crossbar (ds_bpermute), which is what __shfl_xor costs.
@@ -70,7 +67,7 @@ __device__ __forceinline__ void mv_tile(const MvJob& J, int tile) {
     const float* arow = J.in + (li < K ? li : 0) * J.ldin + 4 * g;
     const int col = tile * 16 + li;
     const float* wrow = J.Wt + ((size_t)(J.t0 + tile) * J.nkt + J.s0) * 256 + lane * 4;
-    f32x4_t acc = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+    f32x4 acc = (f32x4){0.f, 0.f, 0.f, 0.f};
     // the weight row is fetched twelve k-steps (192 values of e) at a time, all loads issued before the first MFMA: one L2 round
     // trip per 192 e instead of one per 16
     for (int s0 = 0; s0 < nks; s0 += 12) {
@@ -227,9 +224,9 @@ __device__ __forceinline__ void sa_stream_fwd(const float4* __restrict__ xb, int
 #pragma unroll
     for (int k = 0; k < 16; ++k) qpr[k] = li < K ? qg[li * SA_C + 16 * (k >> 2) + 4 * g + (k & 3)] : 0.f;
     const float l0 = li < K ? qb[li] : 0.f;
-    f32x4_t acc[4];
+    f32x4 acc[4];
 #pragma unroll
-    for (int m = 0; m < 4; ++m) acc[m] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+    for (int m = 0; m < 4; ++m) acc[m] = (f32x4){0.f, 0.f, 0.f, 0.f};
     float csum = 0.f;
     const int ntile = tile1 < 0 ? (N + 15) / 16 : tile1;      // this workgroup's tiles: [tile0, ntile)
     // two register stages per wave: while tile t is processed, tiles t + nw and t + 2 nw are in flight
@@ -240,13 +237,13 @@ __device__ __forceinline__ void sa_stream_fwd(const float4* __restrict__ xb, int
         float xn[16];
         sa_ln16(cur, xn);
         if (t + 2 * nw < ntile) sa_load_tile(xb, N, t + 2 * nw, li, g, cur);
-        f32x4_t L = (f32x4_t){l0, l0, l0, l0};
+        f32x4 L = (f32x4){l0, l0, l0, l0};
 #pragma unroll
         for (int k = 0; k < 16; ++k) L = MFMA16(xn[k], qpr[k], L);           // L[r] = logits[pos 4g+r][slot li]
 #pragma unroll
         for (int c = 0; c < 4; ++c)
             *reinterpret_cast<float4*>(tile + li * SA_TLD + 16 * c + 4 * g) = make_float4(xn[4 * c], xn[4 * c + 1], xn[4 * c + 2], xn[4 * c + 3]);
-        f32x4_t w;
+        f32x4 w;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const float x = li < K ? L[r] : -INFINITY;
@@ -319,9 +316,9 @@ __device__ __forceinline__ void sa_stream_fwd2(const float4* __restrict__ xb, in
     float qbr[4];                                        // bias of slot 4g + r in log2 units; padding slots sit at -1e30 (their weight is 0)
 #pragma unroll
     for (int r = 0; r < 4; ++r) qbr[r] = 4 * g + r < K ? qb[4 * g + r] * SA_LOG2E : -1e30f;
-    f32x4_t acc[4];
+    f32x4 acc[4];
 #pragma unroll
-    for (int m = 0; m < 4; ++m) acc[m] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+    for (int m = 0; m < 4; ++m) acc[m] = (f32x4){0.f, 0.f, 0.f, 0.f};
     float cs[4] = {0.f, 0.f, 0.f, 0.f};                  // sum over this lane's positions of w[slot 4g + r]
     const int ntile = tile1;
     float4 bufA[4], bufB[4];
@@ -343,7 +340,7 @@ __device__ __forceinline__ void sa_stream_fwd2(const float4* __restrict__ xb, in
         for (int k = 1; k < 8; ++k) q2 = __builtin_elementwise_fma(v2[k], v2[k], q2);
         const float rs = __builtin_amdgcn_rsqf(sa_xrow_sum4(q2.x + q2.y) * (1.0f / SA_C) + 1e-5f);
         // ---- logits^T = q' d^T in two independent chains (the centred x is the B operand: [k = channel group][n = position])
-        f32x4_t La = (f32x4_t){0.f, 0.f, 0.f, 0.f}, Lb = La;
+        f32x4 La = (f32x4){0.f, 0.f, 0.f, 0.f}, Lb = La;
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
             La = MFMA16(qpr[2 * k], v2[k].x, La);
@@ -701,9 +698,9 @@ __device__ __forceinline__ void sa_stream_bwd(const float4* __restrict__ xb, flo
         }
     const float icv = li < K ? 1.0f / cs[li] : 0.f, udv = li < K ? ud[li] : 0.f;
     const float l0 = li < K ? qb[li] : 0.f, d0 = li < K ? dub[li] : 0.f;
-    f32x4_t acc[4];
+    f32x4 acc[4];
 #pragma unroll
-    for (int m = 0; m < 4; ++m) acc[m] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+    for (int m = 0; m < 4; ++m) acc[m] = (f32x4){0.f, 0.f, 0.f, 0.f};
     float sdl = 0.f;
     const int ntile = tile1 < 0 ? (N + 15) / 16 : tile1;      // this workgroup's tiles: [tile0, ntile)
     float4 cur[4];
@@ -721,13 +718,13 @@ __device__ __forceinline__ void sa_stream_bwd(const float4* __restrict__ xb, flo
 #pragma unroll
             for (int c = 0; c < 4; ++c) od[c] = pos0 < N ? dxb[pos0 * 16 + 4 * c + g] : make_float4(0.f, 0.f, 0.f, 0.f);
         }
-        f32x4_t L = (f32x4_t){l0, l0, l0, l0}, DA = (f32x4_t){d0, d0, d0, d0};
+        f32x4 L = (f32x4){l0, l0, l0, l0}, DA = (f32x4){d0, d0, d0, d0};
 #pragma unroll
         for (int k = 0; k < 16; ++k) { L = MFMA16(xn[k], qpr[k], L); DA = MFMA16(xn[k], dur[k], DA); }
 #pragma unroll
         for (int c = 0; c < 4; ++c)
             *reinterpret_cast<float4*>(tile + li * SA_TLD + 16 * c + 4 * g) = make_float4(xn[4 * c], xn[4 * c + 1], xn[4 * c + 2], xn[4 * c + 3]);
-        f32x4_t dl, wn;
+        f32x4 dl, wn;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const float x = li < K ? L[r] : -INFINITY;
@@ -748,9 +745,9 @@ __device__ __forceinline__ void sa_stream_bwd(const float4* __restrict__ xb, flo
         for (int r = 0; r < 4; ++r)
 #pragma unroll
             for (int m = 0; m < 4; ++m) acc[m] = MFMA16(tile[(4 * g + r) * SA_TLD + 16 * m + li], dl[r], acc[m]);   // sum_n dl xn^T: [ch][slot]
-        f32x4_t Dx[4];
+        f32x4 Dx[4];
 #pragma unroll
-        for (int m = 0; m < 4; ++m) Dx[m] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+        for (int m = 0; m < 4; ++m) Dx[m] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int s = 0; s < NS; ++s) {
             const float wa = wt0[li * SA_WLD + 4 * s + g], da2 = wt1[li * SA_WLD + 4 * s + g];     // A layout: [pos li][slot 4s+g]
@@ -838,9 +835,9 @@ __device__ __forceinline__ void sa_stream_bwd2(const float4* __restrict__ xb, fl
         icr[r] = slot < K ? 1.0f / cs[slot] : 0.f;
         dbr[r] = slot < K ? dub[slot] - ud[slot] : 0.f;
     }
-    f32x4_t acc[4];
+    f32x4 acc[4];
 #pragma unroll
-    for (int m = 0; m < 4; ++m) acc[m] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+    for (int m = 0; m < 4; ++m) acc[m] = (f32x4){0.f, 0.f, 0.f, 0.f};
     float sdl[4] = {0.f, 0.f, 0.f, 0.f};
     const int ntile = tile1;
     float4 cur[4];
@@ -869,7 +866,7 @@ __device__ __forceinline__ void sa_stream_bwd2(const float4* __restrict__ xb, fl
         for (int k = 1; k < 8; ++k) q2 = __builtin_elementwise_fma(v2[k], v2[k], q2);
         const float rs = __builtin_amdgcn_rsqf(sa_xrow_sum4(q2.x + q2.y) * (1.0f / SA_C) + 1e-5f);
         // ---- logits^T and (d attn)^T: four independent chains
-        f32x4_t La = (f32x4_t){0.f, 0.f, 0.f, 0.f}, Lb = La, Da = La, Db = La;
+        f32x4 La = (f32x4){0.f, 0.f, 0.f, 0.f}, Lb = La, Da = La, Db = La;
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
             La = MFMA16(qpr[2 * k], v2[k].x, La);
@@ -920,9 +917,9 @@ __device__ __forceinline__ void sa_stream_bwd2(const float4* __restrict__ xb, fl
 #pragma unroll
             for (int m = 0; m < 4; ++m) acc[m] = MFMA16(tile[(4 * g + r) * SA_TLD + 16 * m + li], wb[r], acc[m]);   // sum_n dl xn^T: [ch][slot]
         // ---- d xn^T[ch][pos] = sum_slot dug[slot][ch] wn[pos][slot] + qg[slot][ch] dl[pos][slot]
-        f32x4_t Dx[4];
+        f32x4 Dx[4];
 #pragma unroll
-        for (int m = 0; m < 4; ++m) Dx[m] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+        for (int m = 0; m < 4; ++m) Dx[m] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int r = 0; r < 4; ++r)
 #pragma unroll

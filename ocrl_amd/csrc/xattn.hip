@@ -20,8 +20,6 @@
 #include "common.h"
 #include "kernels.h"
 
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
-#define MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
 #define XA_T 256          // threads per workgroup (4 waves, 16 tokens each per step)
 
 __device__ __forceinline__ float xa_xrow16(float v, bool is_max) {
@@ -187,9 +185,9 @@ __global__ __launch_bounds__(XA_T, 3) void xattn_fwd_kernel(XaArgs a) {
 #pragma unroll
         for (int c = 0; c < NM; ++c) xv[c] = live ? *reinterpret_cast<const float4*>(a.x + row + 16 * c + 4 * g) : make_float4(0.f, 0.f, 0.f, 0.f);
         // ---- scores^T[col][tok] = A_b^T x^T
-        f32x4_t s[NT];
+        f32x4 s[NT];
 #pragma unroll
-        for (int tt = 0; tt < NT; ++tt) s[tt] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+        for (int tt = 0; tt < NT; ++tt) s[tt] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int c = 0; c < NM; ++c) {
             float4 av[NT];
@@ -206,7 +204,7 @@ __global__ __launch_bounds__(XA_T, 3) void xattn_fwd_kernel(XaArgs a) {
             if ((c & 1) == 1) __builtin_amdgcn_sched_barrier(0);
         }
         // ---- soft-max over the slots of each head, dropout
-        f32x4_t pd[NT];
+        f32x4 pd[NT];
 #pragma unroll
         for (int tt = 0; tt < NT; ++tt) {
             const int head = (16 * tt + 4 * g) / KP;
@@ -237,9 +235,9 @@ __global__ __launch_bounds__(XA_T, 3) void xattn_fwd_kernel(XaArgs a) {
             }
         }
         // ---- out^T[o][tok] = Vo_b^T Pd^T
-        f32x4_t o[NM];
+        f32x4 o[NM];
 #pragma unroll
-        for (int m = 0; m < NM; ++m) o[m] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+        for (int m = 0; m < NM; ++m) o[m] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int tt = 0; tt < NT; ++tt) {
 #pragma unroll
@@ -323,9 +321,9 @@ __global__ __launch_bounds__(XA_T, 3) void xattn_bwd_kernel(XaArgs a) {
             for (int r = 0; r < 4; ++r) pr[tt][r] = (live && slot0 + r < K) ? a.P[prow + slot0 + r] : 0.f;
         }
         // ---- d Pd^T[col][tok] = Vo_b gd^T
-        f32x4_t dp[NT];
+        f32x4 dp[NT];
 #pragma unroll
-        for (int tt = 0; tt < NT; ++tt) dp[tt] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+        for (int tt = 0; tt < NT; ++tt) dp[tt] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int c = 0; c < NM; ++c) {
             float4 av[NT];
@@ -342,7 +340,7 @@ __global__ __launch_bounds__(XA_T, 3) void xattn_bwd_kernel(XaArgs a) {
             if ((c & 1) == 1) __builtin_amdgcn_sched_barrier(0);
         }
         // ---- dropout backward, soft-max backward per head
-        f32x4_t ds[NT];
+        f32x4 ds[NT];
 #pragma unroll
         for (int tt = 0; tt < NT; ++tt) {
             const int head = (16 * tt + 4 * g) / KP;
@@ -375,9 +373,9 @@ __global__ __launch_bounds__(XA_T, 3) void xattn_bwd_kernel(XaArgs a) {
             }
         }
         // ---- d x^T[e][tok] = A_b dS^T
-        f32x4_t o[NM];
+        f32x4 o[NM];
 #pragma unroll
-        for (int m = 0; m < NM; ++m) o[m] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+        for (int m = 0; m < NM; ++m) o[m] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int tt = 0; tt < NT; ++tt) {
 #pragma unroll

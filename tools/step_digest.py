@@ -1,7 +1,8 @@
 """sha256 digests of what a named case computes, one JSON line: two forward / backward / clip_adam steps from fixed formula parameters
 (losses, the flat gradient after each step, the flat parameters at the end); with --encode three encode() calls (eager, capture and
 replay under OCRL_ENCODE_GRAPH=1), encode_backward() and the encoder-only update; with --generate the generated tokens.  The case
-`sa_unit` is the slot-attention unit entry points instead: every output and weight gradient at three shapes.  Two builds of
+`sa_unit` is the slot-attention unit entry points instead: every output and weight gradient at three shapes; `attn_unit` the causal
+self-attention entry points: the forward and the three backward forms at four head widths, with and without dropout.  Two builds of
 the library (OCRL_HIP_LIB) that issue the same launches print the same line under every OCRL_* switch: a host-side refactor is held to
 that, since the suite's fixture comparisons have tolerances."""
 import argparse
@@ -93,12 +94,56 @@ def sa_unit():
     return out
 
 
+def attn_unit():
+    """the causal self-attention entry points on q, k, v as column blocks of one packed [B, T, 3d] buffer: o and lse of
+    ocrl_attention_fwd; dq, dk, dv of ocrl_attention_bwd under OCRL_ATTN_BWD=2 and =1 and of ocrl_attention_bwd_ws under =3 with a
+    workspace for the whole batch and (B = 3) for two images, i.e. chunks of 2 + 1"""
+    import ctypes
+    from ocrl_amd import _lib
+    L = _lib.lib()
+    P = lambda t: ctypes.c_void_p(t.data_ptr())
+    out = {}
+    for B_, T, h in ATTN_UNIT_SHAPES:
+        for dh in (16, 32, 48, 64):
+            d = dh * h
+            gen = torch.Generator().manual_seed(1000 * T + dh)
+            qkv = torch.randn(B_, T, 3 * d, generator=gen).cuda()
+            dO = torch.randn(B_, T, d, generator=gen).cuda()
+            q, k, v = qkv[..., :d], qkv[..., d:2 * d], qkv[..., 2 * d:]
+            o, lse, delta = torch.empty(B_, T, d, device="cuda"), torch.empty(B_, h, T, device="cuda"), torch.empty(B_, h, T, device="cuda")
+            per_image = L.ocrl_attention_bwd_ds_floats(1, T, h)
+            ds = torch.empty(B_ * per_image, device="cuda")
+            for p in (0.0, 0.1):
+                tag = f"B{B_}T{T}h{h}dh{dh}p{p}"
+                _lib.check(L.ocrl_attention_fwd(P(q), P(k), P(v), P(o), P(lse), B_, T, d, h, 3 * d, p, 7, 16, None))
+                out[f"{tag}.o"], out[f"{tag}.lse"] = digest(o), digest(lse)
+                forms = [("2", None), ("1", None), ("3", B_)] + ([("3", 2)] if B_ == 3 else [])
+                for form, images in forms:
+                    os.environ["OCRL_ATTN_BWD"] = form
+                    g = torch.full_like(qkv, float("nan"))
+                    gq, gk, gv = g[..., :d], g[..., d:2 * d], g[..., 2 * d:]
+                    if images is None:
+                        _lib.check(L.ocrl_attention_bwd(P(q), P(k), P(v), P(o), P(lse), P(dO), P(gq), P(gk), P(gv), P(delta), B_, T, d, h, 3 * d, p, 7, 16, None))
+                    else:
+                        ds.fill_(float("nan"))
+                        _lib.check(L.ocrl_attention_bwd_ws(P(q), P(k), P(v), P(o), P(lse), P(dO), P(gq), P(gk), P(gv), P(delta), B_, T, d, h, 3 * d, p, 7, 16,
+                                                           P(ds), images * per_image, None))
+                    for n, t in (("dq", gq), ("dk", gk), ("dv", gv)):
+                        out[f"{tag}.bwd{form}" + (f"ws{images}" if images else "") + "." + n] = digest(t)
+    os.environ.pop("OCRL_ATTN_BWD", None)
+    return out
+
+
+# (B, T, h): two tiles with a one-row ragged tail; three tiles, T4 != T; the one-pass form's two 128-key blocks over four query tiles
+ATTN_UNIT_SHAPES = [(2, 65, 2), (3, 129, 2), (2, 200, 3)]
+UNITS = {"iodine": iodine, "sa_unit": sa_unit, "attn_unit": attn_unit}
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser(description=__doc__)
-    ap.add_argument("case", choices=sorted(SLATE_CASES) + ["iodine", "sa_unit"])
+    ap.add_argument("case", choices=sorted(SLATE_CASES) + sorted(UNITS))
     ap.add_argument("--encode", action="store_true")
     ap.add_argument("--generate", action="store_true")
     ap.add_argument("--tag", default="", help="copied into the output line (the switch combination of the run)")
     a = ap.parse_args()
-    res = iodine() if a.case == "iodine" else sa_unit() if a.case == "sa_unit" else slate(SLATE_CASES[a.case], a.encode, a.generate)
+    res = UNITS[a.case]() if a.case in UNITS else slate(SLATE_CASES[a.case], a.encode, a.generate)
     print(json.dumps(dict(case=a.case, tag=a.tag, **res)))
