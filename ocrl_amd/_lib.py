@@ -1,4 +1,4 @@
-"""ctypes binding of libocrl_hip.so, derived from include/ocrl_hip.h (_abi.py reads it: the struct classes, the constants and every
+"""ctypes binding of libocrl_hip.so, derived from include/ocrl_hip.h and include/ocrl_hip_dqn.h (_abi.py reads them: the struct classes, the constants and every
 entry point's argtypes / restype come from the header's own declarations).  Fails loudly when the library is not built."""
 import ctypes
 import os
@@ -9,6 +9,7 @@ from . import _abi
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("OCRL_HIP_LIB") or os.path.join(_HERE, "libocrl_hip.so")      # OCRL_HIP_LIB: development builds
 HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "ocrl_hip.h")
+DQN_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "ocrl_hip_dqn.h")      # the DQN entry points: a second, self-contained header
 _lib = None
 
 if not os.path.exists(HEADER_PATH):
@@ -22,6 +23,12 @@ SlateConfig, IodineConfig, GemmDesc, ConvDesc, ConvWgradDesc, XattnDesc, AcnetDe
     ABI.structs["ocrl_" + n] for n in ("slate_config", "iodine_config", "gemm_desc", "conv_desc", "conv_wgrad_desc", "xattn_desc", "acnet_desc",
                                        "sprite_env_desc", "scenes_desc", "flat_segment"))
 FLAT_MAX_SEGMENTS = CONSTANTS["OCRL_FLAT_MAX_SEGMENTS"]
+if not os.path.exists(DQN_HEADER_PATH):
+    raise RuntimeError(f"{DQN_HEADER_PATH} is missing: ocrl_amd derives its binding of libocrl_hip.so from the header and runs from the source tree.")
+with open(DQN_HEADER_PATH) as _f:
+    ABI_DQN = _abi.read(_f.read())                      # a table of its own: ABI stays what ocrl_hip.h declares
+QnetDesc = ABI_DQN.structs["ocrl_qnet_desc"]
+QNET_MAX_LAYERS = len(QnetDesc().dims)
 
 
 def flat_segments(segs):
@@ -40,6 +47,16 @@ def acnet_desc(B, F, A, dims, acts):
         d.n[t] = len(dims[t])
         for l, (w, a) in enumerate(zip(dims[t], acts[t])):
             d.dims[t][l], d.acts[t][l] = int(w), int(a)
+    return d
+
+
+def qnet_desc(B, F, A, dims, acts):
+    """QnetDesc of a Q head: dims / acts = the hidden layers' widths / activation codes (0 none, 1 relu, 2 tanh)"""
+    if len(dims) > QNET_MAX_LAYERS or len(acts) != len(dims):
+        raise ValueError(f"ocrl_amd: at most {QNET_MAX_LAYERS} hidden layers, one activation code each (got {len(dims)}, {len(acts)})")
+    d = QnetDesc(B=B, F=F, A=A, n=len(dims))
+    for l, (w, a) in enumerate(zip(dims, acts)):
+        d.dims[l], d.acts[l] = int(w), int(a)
     return d
 
 
@@ -81,13 +98,14 @@ def lib():
     # when it was loaded before torch)
     import torch  # noqa: F401
     L = ctypes.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in ABI.functions.items():
-        f = getattr(L, name)
-        f.argtypes = argtypes
-        if restype is not ctypes.c_int:         # ctypes' default
-            f.restype = restype
-    for name, cls in ABI.structs.items():       # every struct whose size the library reports
-        if name + "_size" in ABI.functions and getattr(L, name + "_size")() != ctypes.sizeof(cls):
+    for abi in (ABI, ABI_DQN):
+        for name, (restype, argtypes) in abi.functions.items():
+            f = getattr(L, name)
+            f.argtypes = argtypes
+            if restype is not ctypes.c_int:     # ctypes' default
+                f.restype = restype
+    for name, cls in {**ABI.structs, **ABI_DQN.structs}.items():        # every struct whose size the library reports
+        if name + "_size" in {**ABI.functions, **ABI_DQN.functions} and getattr(L, name + "_size")() != ctypes.sizeof(cls):
             raise RuntimeError(f"libocrl_hip.so: {name} is {getattr(L, name + '_size')()} bytes, this binding's {cls.__name__} {ctypes.sizeof(cls)}")
     if L.ocrl_abi_version() != CONSTANTS["OCRL_ABI_VERSION"]:
         raise RuntimeError(f"libocrl_hip.so ABI version mismatch: the library is {L.ocrl_abi_version()}, include/ocrl_hip.h {CONSTANTS['OCRL_ABI_VERSION']}")

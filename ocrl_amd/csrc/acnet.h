@@ -15,7 +15,7 @@ struct AcnetArgs {
     int n[3], dim[3][ACNET_MAX_LAYERS], act[3][ACNET_MAX_LAYERS];
     const float* w[3][ACNET_MAX_LAYERS];
     const float* b[3][ACNET_MAX_LAYERS];
-    const float *wa, *ba, *wv, *bv;                   // action_net [A, latent_pi], value_net [1, latent_vf]
+    const float *wa, *ba, *wv, *bv;                   // action_net [A, latent_pi], value_net [1, latent_vf] (wv null: no value head, dqn.h)
     const float* x;                                   // features [B, F]
     float *logits, *values, *lat_pi, *lat_vf;         // forward outputs (each may be null)
     float* saved[3][ACNET_MAX_LAYERS];                // layer outputs [B, dim] in the workspace (null: not kept)

@@ -1,6 +1,9 @@
 from .a2c import A2C
 from .custom_acnets import CustomActorCriticPolicy, CustomNetwork, a2c_loss, compute_gae, ppo_loss
+from .dqn import DQN, DQNPolicy, QNetwork, dqn_loss
 from .ocr_extractor import OCRExtractor
 from .ppo import PPO, RolloutBuffer
+from .replay import ReplayBuffer
 
-__all__ = ["OCRExtractor", "CustomNetwork", "CustomActorCriticPolicy", "ppo_loss", "a2c_loss", "compute_gae", "PPO", "A2C", "RolloutBuffer"]
+__all__ = ["OCRExtractor", "CustomNetwork", "CustomActorCriticPolicy", "ppo_loss", "a2c_loss", "compute_gae", "PPO", "A2C", "RolloutBuffer",
+           "DQN", "DQNPolicy", "QNetwork", "dqn_loss", "ReplayBuffer"]

@@ -1,0 +1,476 @@
+"""DQN on the GPU: what the reference would select with ``sb3=dqn`` (configs/sb3/dqn.yaml), the value-based baseline on the same
+Discrete sprite tasks and the same ``OCRExtractor``.
+
+``DQNPolicy`` and ``DQN`` restate stable-baselines3 1.5's classes of the same names from the published algorithm (Mnih et al. 2015) with
+that package's hyper-parameter names and defaults: none of its text is copied.  The GPU work is the library's (include/ocrl_hip_dqn.h):
+acting is ``ocrl_dqn_act`` (the Q head's forward and the epsilon-greedy choice in one launch after the extractor), the replay buffer
+(replay.py) samples and reads a batch in two launches, the loss is ``dqn_loss`` (``ocrl_dqn_td_fwd_bwd``: the TD target, the Huber loss
+and the head's gradient, fused) and the update ``ocrl_flat_clip_adam_l2`` on one flat parameter buffer.  Where this departs from
+stable-baselines3 is listed in DESIGN.md §7."""
+import collections
+import copy
+import ctypes
+import math
+
+import numpy as np
+import torch
+from torch import nn
+
+from .. import _bridge, _lib
+from ..ocrs.flat_module import FlatParamModule
+from .custom_acnets import _n_actions
+from .on_policy import OnPolicyAlgorithm, _check_constant, _tensor
+from .replay import ReplayBuffer
+
+_WHO = "ocrl_amd.sb3s"
+_ACT = {"relu": (nn.ReLU, 1), "tanh": (nn.Tanh, 2)}
+ADAM_EPS = 1e-8                 # stable-baselines3's DQNPolicy builds torch's default Adam (the actor-critic policy: 1e-5)
+DQN_SCALARS = ("loss", "mean_q", "mean_target")
+
+
+def _desc(B, F, A, dims, acts, dev, keep=True):
+    """(descriptor, workspace) of a call"""
+    d = _lib.qnet_desc(B, F, A, dims, acts)
+    return d, _bridge.workspace(_WHO, _lib.lib().ocrl_qnet_ws_floats(ctypes.byref(d)), dev,
+                                f"batch {B}, feature_dim {F}, {A} actions, hidden widths {list(dims)}", keep)
+
+
+class _QnetFn(torch.autograd.Function):
+    """q [B, A] of a feature batch"""
+
+    @staticmethod
+    def forward(ctx, features, dims, acts, A, *params):
+        x, ps = _bridge.inputs(_WHO, features, params)
+        dev = x.device
+        B, F = x.shape
+        need_grad = any(ctx.needs_input_grad)
+        d, ws = _desc(B, F, A, dims, acts, dev, need_grad)
+        q = torch.empty(B, A, device=dev)
+        _bridge.launch(dev, _lib.lib().ocrl_qnet_fwd, ctypes.byref(d), _lib.ptr(x), _lib.ptrs(ps), _lib.ptr(q), int(need_grad),
+                       _lib.ptr(ws) if need_grad else None, ws.numel())
+        ctx.save_for_backward(x, *ps)
+        ctx.d, ctx.ws = d, ws
+        return q
+
+    @staticmethod
+    def backward(ctx, dq):
+        x, *ps = ctx.saved_tensors
+        dq = _bridge.cotangent(dq)
+        gs = [torch.empty_like(p) for p in ps]
+        dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+        _bridge.launch(x.device, _lib.lib().ocrl_qnet_bwd, ctypes.byref(ctx.d), _lib.ptr(x), _lib.ptrs(ps), _lib.ptr(dq), _lib.ptr(dx), _lib.ptrs(gs),
+                       _lib.ptr(ctx.ws), ctx.ws.numel())
+        return (dx, None, None, None, *gs)
+
+
+class _DqnFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, features, next_q, actions, rewards, dones, gamma, dims, acts, A, *params):
+        x, ps = _bridge.inputs(_WHO, features, params)
+        dev = x.device
+        B, F = x.shape
+        vec = lambda t, dt: t.to(device=dev, dtype=dt).reshape(-1).contiguous()
+        actions, rewards, dones = vec(actions, torch.int64), vec(rewards, torch.float32), vec(dones, torch.uint8)
+        next_q = next_q.detach().to(device=dev, dtype=torch.float32).contiguous()
+        for name, t, n in (("actions", actions, B), ("rewards", rewards, B), ("dones", dones, B), ("next_q", next_q, B * A)):
+            if t.numel() != n:
+                raise ValueError(f"{_WHO}.dqn_loss: {name} has {t.numel()} entries for a batch of {B} and {A} actions")
+        d, ws = _desc(B, F, A, dims, acts, dev)
+        scal = torch.empty(3, device=dev, dtype=torch.float32)
+        gs = [torch.empty_like(p) for p in ps]
+        dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+        _bridge.launch(dev, _lib.lib().ocrl_dqn_td_fwd_bwd, ctypes.byref(d), _lib.ptr(x), _lib.ptrs(ps), _lib.ptr(next_q), _lib.ptr(actions),
+                       _lib.ptr(rewards), _lib.ptr(dones), float(gamma), _lib.ptr(scal), _lib.ptr(dx), _lib.ptrs(gs), _lib.ptr(ws), ws.numel())
+        ctx.gs, ctx.dx = gs, dx              # the gradients are the forward's own outputs: the backward reads nothing else again
+        ctx.mark_non_differentiable(scal)
+        return scal[0].clone(), scal
+
+    @staticmethod
+    def backward(ctx, gloss, _gscal):
+        dx = None if ctx.dx is None else ctx.dx * gloss
+        return (dx, None, None, None, None, None, None, None, None, *[g * gloss for g in ctx.gs])
+
+
+class QNetwork(nn.Module):
+    """features [B, F] -> len(net_arch) x [Linear, activation] -> Linear(last, n_actions).  The parameters sit in ``q_net``, an
+    nn.Sequential whose ``state_dict()`` keys are ``q_net.{2i}.weight|bias``; the container's ``forward`` is never called: the arithmetic
+    is ``ocrl_qnet_fwd`` / ``ocrl_qnet_bwd`` under a ``torch.autograd.Function``.  No CPU fallback: a CPU tensor raises."""
+
+    def __init__(self, features_dim, n_actions, net_arch=(64, 64), activation="relu"):
+        super().__init__()
+        if activation not in _ACT:
+            raise ValueError(f"{_WHO}.QNetwork: activation {activation!r} is not one of {', '.join(_ACT)}")
+        self.n_actions, self._dims, self._act = int(n_actions), tuple(int(w) for w in net_arch), _ACT[activation][1]
+        layers, in_dim = [], int(features_dim)
+        for w in self._dims:
+            layers += [nn.Linear(in_dim, w), _ACT[activation][0]()]
+            in_dim = w
+        self.q_net = nn.Sequential(*layers, nn.Linear(in_dim, self.n_actions))
+
+    def _layout(self):
+        """(hidden widths, activation codes), as the C ABI takes them"""
+        return self._dims, (self._act,) * len(self._dims)
+
+    def _param_list(self):
+        return [p for m in self.q_net if isinstance(m, nn.Linear) for p in (m.weight, m.bias)]
+
+    def forward(self, features):
+        return _QnetFn.apply(features, *self._layout(), self.n_actions, *self._param_list())
+
+
+class DQNPolicy(nn.Module):
+    """features_extractor -> QNetwork.  ``features_extractor`` is a module with ``features_dim`` (an OCRExtractor), or
+    ``features_extractor_class(observation_space, **features_extractor_kwargs)``; without either the observations are flattened.
+    ``exploration_rate`` is the epsilon ``act`` explores with (DQN sets it before every step); the target network is a second DQNPolicy
+    (DQN builds it)."""
+
+    def __init__(self, observation_space, action_space, lr_schedule=None, config=None, features_extractor=None, features_extractor_class=None,
+                 features_extractor_kwargs=None, net_arch=(64, 64), activation="relu", **kwargs):
+        super().__init__()
+        self._config = config
+        self.observation_space, self.action_space = observation_space, action_space
+        n = _n_actions(action_space)                          # Discrete only, with the actor-critic policy's message
+        if features_extractor is None and features_extractor_class is not None:
+            features_extractor = features_extractor_class(observation_space, **(features_extractor_kwargs or {}))
+        if features_extractor is None:
+            features_extractor = nn.Flatten()
+            self.features_dim = int(math.prod(observation_space.shape))
+        else:
+            self.features_dim = int(features_extractor.features_dim)
+        self.features_extractor = features_extractor
+        self.q_net = QNetwork(self.features_dim, n, net_arch, activation)
+        self.exploration_rate = 0.0
+
+    def extract_features(self, obs):
+        return self.features_extractor(obs)
+
+    def q_values(self, obs):
+        """q [B, n] of an observation batch, attached to autograd"""
+        return self.q_net(self.extract_features(obs))
+
+    _sample_seed = None                                       # set_sampling(): the stream of the exploration coin and the random action
+    _sample_rows = 0
+
+    def set_sampling(self, seed):
+        """give the policy its exploration stream: row r of the n-th ``act`` call draws from (seed, rows of the earlier calls + r)"""
+        self._sample_seed = None if seed is None else int(seed) & (2 ** 64 - 1)
+        self._sample_rows = 0
+
+    def act(self, features, row_offset=None, deterministic: bool = False, uniforms=None, epsilon=None):
+        """(actions int64 [B], q [B, n], None) of a feature batch in one kernel launch, detached (the collection step; the rule is
+        include/ocrl_hip_dqn.h's).  Each row flips its own coin: with probability ``epsilon`` (``None``: ``exploration_rate``;
+        ``deterministic``: 0) a uniform random action, otherwise the lowest index of the maximum Q.  Row r draws from (the set_sampling
+        seed, row_offset + r); ``row_offset=None`` takes and advances the policy's own row counter.  ``uniforms`` [B, 2] in [0, 1)
+        replaces the draw."""
+        dims, acts = self.q_net._layout()
+        x, ps = _bridge.inputs(_WHO, features.detach(), self.q_net._param_list())
+        B, F = x.shape
+        eps = 0.0 if deterministic else float(self.exploration_rate if epsilon is None else epsilon)
+        if uniforms is not None:
+            uniforms = uniforms.to(device=x.device, dtype=torch.float32).reshape(-1).contiguous()
+            if uniforms.numel() != 2 * B:
+                raise ValueError(f"{_WHO}.DQNPolicy.act: {uniforms.numel()} uniforms for a batch of {B} (two per row)")
+        elif eps > 0 and self._sample_seed is None:
+            raise RuntimeError(f"{_WHO}.DQNPolicy.act: no exploration stream: call policy.set_sampling(seed) or pass uniforms")
+        if row_offset is None:
+            row_offset = self._sample_rows
+            self._sample_rows += B
+        d, _ = _desc(B, F, self.q_net.n_actions, dims, acts, x.device, keep=False)
+        actions = torch.empty(B, device=x.device, dtype=torch.int64)
+        q = torch.empty(B, self.q_net.n_actions, device=x.device)
+        _bridge.launch(x.device, _lib.lib().ocrl_dqn_act, ctypes.byref(d), _lib.ptr(x), _lib.ptrs(ps), self._sample_seed or 0, int(row_offset), eps,
+                       _lib.ptr(uniforms), _lib.ptr(actions), _lib.ptr(q))
+        return actions, q, None
+
+    def forward(self, obs, deterministic: bool = False):
+        return self.act(self.extract_features(obs), deterministic=deterministic)
+
+
+def dqn_loss(policy, features, next_q, actions, rewards, dones, gamma):
+    """DQN's loss of ``policy`` on a feature batch [B, F] (``policy.extract_features(obs)``) against the target network's
+    ``next_q`` [B, n]: (loss, metrics).  ``loss`` is the mean Huber loss of Q[a] - (r + gamma max next_q, or r where done), attached to
+    autograd: ``backward()`` puts the gradients on the head's parameters and on ``features``.  ``metrics`` maps DQN_SCALARS to detached 0-d
+    tensors."""
+    dims, acts = policy.q_net._layout()
+    loss, scal = _DqnFn.apply(features, next_q, actions, rewards, dones, gamma, dims, acts, policy.q_net.n_actions, *policy.q_net._param_list())
+    return loss, {k: scal[i] for i, k in enumerate(DQN_SCALARS)}
+
+
+def exploration_schedule(frac, initial_eps, final_eps, fraction):
+    """epsilon at the share ``frac`` of the run: linear from ``initial_eps`` to ``final_eps`` over the first ``fraction``, then constant"""
+    if frac > fraction:
+        return float(final_eps)
+    return float(initial_eps + frac * (final_eps - initial_eps) / fraction)
+
+
+def _layout(params):
+    """(offsets, length) of a flat buffer over ``params``: each starts on a multiple of 4 floats (OnPolicyAlgorithm._flatten_parameters)"""
+    offs, n = [], 0
+    for p in params:
+        offs.append(n)
+        n += (p.numel() + 3) & ~3
+    return offs, max(n, 4)
+
+
+class DQN:
+    """Deep Q-learning with a target network and a replay buffer for Discrete actions (stable-baselines3's DQN on a VecEnv).  ``env`` as
+    OnPolicyAlgorithm takes it; ``policy`` is a DQNPolicy or its class.  An iteration is ``train_freq`` vec steps, then
+    ``gradient_steps`` updates once ``num_timesteps > learning_starts``.  Every environment flips its own exploration coin."""
+    ALGO = "DQN"
+    HYPER = ("learning_rate", "buffer_size", "learning_starts", "batch_size", "tau", "gamma", "train_freq", "gradient_steps",
+             "target_update_interval", "exploration_fraction", "exploration_initial_eps", "exploration_final_eps", "max_grad_norm")
+
+    def __init__(self, policy, env, learning_rate=1e-4, buffer_size=1_000_000, learning_starts=50_000, batch_size=32, tau=1.0, gamma=0.99,
+                 train_freq=4, gradient_steps=1, target_update_interval=10_000, exploration_fraction=0.1, exploration_initial_eps=1.0,
+                 exploration_final_eps=0.05, max_grad_norm=10, seed=0, device="cuda", policy_kwargs=None, log_interval=100, **ignored_sb3_kwargs):
+        who = self._who = f"{_WHO}.{self.ALGO}"
+        self.learning_rate = _check_constant(who, "learning_rate", learning_rate)
+        if int(gradient_steps) < 1:
+            raise ValueError(f"{who}: gradient_steps >= 1 (got {gradient_steps}; stable-baselines3's -1, as many as steps were collected, is not built)")
+        if int(train_freq) < 1 or int(batch_size) < 1 or int(log_interval) < 1:
+            raise ValueError(f"{who}: train_freq, batch_size and log_interval >= 1 (got {train_freq}, {batch_size}, {log_interval})")
+        if not 0.0 < float(exploration_fraction) <= 1.0:
+            raise ValueError(f"{who}: 0 < exploration_fraction <= 1 (got {exploration_fraction})")
+        self.n_actions = _n_actions(env.action_space)                 # Discrete only: the policy's own message otherwise
+        self.env, self.n_envs = env, int(env.num_envs)
+        self.buffer_size, self.learning_starts, self.batch_size = int(buffer_size), int(learning_starts), int(batch_size)
+        self.tau, self.gamma = float(tau), float(gamma)
+        self.train_freq, self.gradient_steps, self.target_update_interval = int(train_freq), int(gradient_steps), int(target_update_interval)
+        self.exploration_fraction = float(exploration_fraction)
+        self.exploration_initial_eps, self.exploration_final_eps = float(exploration_initial_eps), float(exploration_final_eps)
+        self.max_grad_norm = 0.0 if max_grad_norm is None else float(max_grad_norm)
+        self.seed, self.log_interval = int(seed), int(log_interval)
+        self.device = torch.device(device)
+        if self.device.type == "cuda" and self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        if isinstance(policy, type):
+            torch.manual_seed(self.seed)                              # the initialisation follows the seed, as set_random_seed does
+            policy = policy(env.observation_space, env.action_space, None, **(policy_kwargs or {}))
+        if not isinstance(policy, DQNPolicy):
+            raise TypeError(f"{who}: policy must be an ocrl_amd.sb3s.DQNPolicy (or the class), got {type(policy).__name__}")
+        for m in policy.modules():
+            if isinstance(m, FlatParamModule):
+                raise NotImplementedError(f"{who}: a trainable {m.backend} encoder behind the extractor keeps its own flat buffers and optimiser "
+                                          f"step; stepping it from {self.ALGO} is not built: give the extractor a pre-trained, frozen encoder")
+        self.policy = policy.to(self.device)
+        self.policy.set_sampling(self.seed)
+        self.policy.exploration_rate = self.exploration_initial_eps
+        self._flatten_parameters()
+        self.num_timesteps, self.iteration, self.n_calls, self.n_updates, self.n_target_updates = 0, 0, 0, 0, 0
+        self._total_timesteps = 0
+        self._obs_shape = tuple(env.observation_space.shape)
+        self.replay_buffer = None
+        self._last_obs = None
+        self._ep_ret, self._ep_len = np.zeros(self.n_envs), np.zeros(self.n_envs, dtype=np.int64)
+        self._episodes = collections.deque(maxlen=100)
+        self._successes = collections.deque(maxlen=100)
+        # what the callbacks report: sums of DQN_SCALARS and the gradient norm over the updates since the last one, and the finished
+        # episodes of the vec steps since then (done, success, return, length per step), all on the device until the callback reads them
+        self._acc, self._acc_n = torch.zeros(len(DQN_SCALARS) + 1, device=self.device), 0
+        self._stats = torch.zeros(self.log_interval * self.train_freq, 4, self.n_envs, device=self.device, dtype=torch.float64)
+        self._stats_n = 0
+        self._last_train = self._train_stats([float("nan")] * (len(DQN_SCALARS) + 1), 1)
+
+    n_steps = property(lambda self: self.train_freq)                  # vec steps per iteration (what the entry point's log line prints)
+    exploration_rate = property(lambda self: self.policy.exploration_rate)
+
+    # ---- the optimiser's view of the two policies: flat_p / flat_g / Adam's moments for the online one, flat_target for the target
+    def _flatten_parameters(self):
+        """re-seat every trainable parameter as a view of ``flat_p`` and its .grad as a view of ``flat_g``, in the layout of
+        OnPolicyAlgorithm._flatten_parameters; then build the target policy, a copy whose trainable parameters are views of
+        ``flat_target`` in the same layout and take no gradient.  What has no trainable parameter and is no nn.Module (a frozen encoder's
+        wrapper) is shared between the two, not copied."""
+        params = [p for p in self.policy.parameters() if p.requires_grad]
+        for p in params:
+            if p.dtype != torch.float32 or p.device != self.device:
+                raise RuntimeError(f"{self._who}: parameters must be float32 on {self.device} (got {p.dtype} on {p.device})")
+        offs, n = _layout(params)
+        self.flat_p, self.flat_g, self.flat_target = (torch.zeros(n, device=self.device) for _ in range(3))
+        for p, o in zip(params, offs):
+            view = self.flat_p[o:o + p.numel()].view(p.shape)
+            view.copy_(p.data)
+            p.data = view
+            p.grad = self.flat_g[o:o + p.numel()].view(p.shape)
+        self._params = params
+        ext = self.policy.features_extractor
+        frozen = getattr(ext, "_ocr", None)
+        memo = {id(frozen): frozen} if frozen is not None and not getattr(ext, "_trainable", True) else {}
+        memo[id(self.policy._config)] = self.policy._config
+        for p in params:                                              # the copy must not drag flat_g along
+            p.grad = None
+        self.target = copy.deepcopy(self.policy, memo)
+        for p, o in zip(params, offs):
+            p.grad = self.flat_g[o:o + p.numel()].view(p.shape)
+        tparams = [p for p in self.target.parameters() if p.requires_grad]
+        assert [tuple(p.shape) for p in tparams] == [tuple(p.shape) for p in params]
+        for p, o in zip(tparams, offs):
+            p.data = self.flat_target[o:o + p.numel()].view(p.shape)
+            p.requires_grad_(False)
+        self.flat_target.copy_(self.flat_p)
+        self.target.eval()
+        self._norm = torch.zeros(1, device=self.device)
+        self.flat_m, self.flat_v = (torch.zeros_like(self.flat_p) for _ in range(2))
+        self.adam_step = 0
+        self._ws = torch.empty(_lib.lib().ocrl_flat_clip_adam_ws_floats(), device=self.device)
+
+    def _adam_step(self):
+        """L2 clip of the whole gradient to max_grad_norm, then Adam (eps 1e-8): one C call, no host synchronisation"""
+        self.adam_step += 1
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().ocrl_flat_clip_adam_l2(_lib.ptr(self.flat_p), _lib.ptr(self.flat_g), _lib.ptr(self.flat_m), _lib.ptr(self.flat_v),
+                                                         self.flat_p.numel(), self.max_grad_norm, self.learning_rate, 0.9, 0.999, ADAM_EPS,
+                                                         self.adam_step, _lib.ptr(self._norm), _lib.ptr(self._ws), self._ws.numel(),
+                                                         _lib.stream(self.device)))
+
+    def update_target(self):
+        """the target network follows the online one: a copy at tau = 1 (DQN's hard update), else a step of size tau towards it"""
+        if self.tau == 1.0:
+            self.flat_target.copy_(self.flat_p)
+        else:
+            self.flat_target.lerp_(self.flat_p, self.tau)
+        self.n_target_updates += 1
+
+    _obs = OnPolicyAlgorithm._obs                                     # uint8 frames become floats in [0, 1] on the device
+    ep_rew_mean, ep_len_mean, success_rate = OnPolicyAlgorithm.ep_rew_mean, OnPolicyAlgorithm.ep_len_mean, OnPolicyAlgorithm.success_rate
+    _track_episodes = OnPolicyAlgorithm._track_episodes
+    predict = OnPolicyAlgorithm.predict                               # epsilon-greedy at the current exploration_rate unless deterministic
+
+    # ---- collection
+    def epsilon(self):
+        """the exploration rate of the next step: 1 while the buffer warms up, then the schedule of num_timesteps / total_timesteps"""
+        frac = self.num_timesteps / max(self._total_timesteps, 1)
+        rate = exploration_schedule(frac, self.exploration_initial_eps, self.exploration_final_eps, self.exploration_fraction)
+        self.policy.exploration_rate = rate
+        return 1.0 if self.num_timesteps < self.learning_starts else rate
+
+    def collect_step(self):
+        """one step of every environment into the replay buffer.  An environment with ``on_device`` set (ocrl_amd.envs) is stepped
+        through ``step_device`` and nothing is read from the device."""
+        E = self.n_envs
+        on_device = getattr(self.env, "on_device", False)
+        if self._last_obs is None:
+            self._last_obs = _tensor(self.env.reset(), self.device)
+            self._ep_ret[:], self._ep_len[:] = 0.0, 0
+        if self.replay_buffer is None:
+            self.replay_buffer = ReplayBuffer(self.buffer_size, E, self._obs_shape, self.device, self._last_obs.dtype, self.seed)
+        self.policy.eval()
+        with torch.no_grad():
+            eps = self.epsilon()
+            actions, _, _ = self.policy.act(self.policy.extract_features(self._obs(self._last_obs)), epsilon=eps)
+            if on_device:
+                new_obs, rewards, dones, extras = self.env.step_device(actions)
+                k = self._stats_n
+                self._stats[k, 0], self._stats[k, 1], self._stats[k, 2], self._stats[k, 3] = (dones, extras["is_success"], extras["episode_return"],
+                                                                                              extras["episode_length"])
+                self._stats_n += 1
+            else:
+                new_obs, rewards, dones, _ = self.env.step(actions.cpu().numpy())
+                rewards = np.asarray(rewards.cpu() if isinstance(rewards, torch.Tensor) else rewards, dtype=np.float64).reshape(E)
+                dones = np.asarray(dones.cpu() if isinstance(dones, torch.Tensor) else dones).reshape(E).astype(bool)
+                self._track_episodes(rewards, dones)
+                rewards = torch.as_tensor(rewards, dtype=torch.float32)
+            new_obs = _tensor(new_obs, self.device)
+            self.replay_buffer.add(self._last_obs, new_obs, actions, rewards, dones)
+            self._last_obs = new_obs
+        self.num_timesteps += E
+        self.n_calls += 1
+        if self.n_calls % max(self.target_update_interval // E, 1) == 0:
+            self.update_target()
+        if self._stats_n == self._stats.shape[0]:
+            self._read_episodes()
+
+    def _read_episodes(self):
+        """the finished episodes of the steps since the last read, in (step, environment) order, into the 100-episode windows: one copy"""
+        if self._stats_n == 0:
+            return
+        host = self._stats[:self._stats_n].cpu().numpy()
+        self._stats_n = 0
+        for t, e in zip(*np.nonzero(host[:, 0])):
+            self._episodes.append((float(host[t, 2, e]), int(host[t, 3, e])))
+            self._successes.append(bool(host[t, 1, e]))
+
+    # ---- the update
+    def train_step(self):
+        """one gradient step: a batch from the replay buffer, the target network's Q of the next observations, ``dqn_loss``, the backward
+        through the extractor, clip + Adam.  Nothing is read from the device: the scalars add up in ``_acc`` until a callback reads them."""
+        batch = self.replay_buffer.sample(self.batch_size, self.n_updates)
+        with torch.no_grad():
+            next_q = self.target.q_values(self._obs(batch.next_observations))
+        self.policy.train()
+        self.flat_g.zero_()
+        features = self.policy.extract_features(self._obs(batch.observations))
+        loss, m = dqn_loss(self.policy, features, next_q, batch.actions, batch.rewards, batch.dones, self.gamma)
+        loss.backward()
+        self._adam_step()
+        self.n_updates += 1
+        self._acc += torch.cat([torch.stack([m[k] for k in DQN_SCALARS]), self._norm])
+        self._acc_n += 1
+        return loss
+
+    def _train_stats(self, sums, n):
+        out = {k: sums[i] / n for i, k in enumerate(DQN_SCALARS)}
+        out.update(grad_norm=sums[len(DQN_SCALARS)] / n, n_updates=self.n_updates, exploration_rate=self.policy.exploration_rate)
+        return out
+
+    def train_stats(self):
+        """means of DQN_SCALARS and the gradient norm over the updates since the last call (the last values again when there were none;
+        NaN before the first update), ``n_updates`` and ``exploration_rate``.  Reads the device once."""
+        if self._acc_n:
+            self._last_train = self._train_stats(self._acc.tolist(), self._acc_n)
+            self._acc.zero_()
+            self._acc_n = 0
+        self._last_train.update(n_updates=self.n_updates, exploration_rate=self.policy.exploration_rate)
+        return dict(self._last_train)
+
+    def learn(self, total_timesteps, callback=None):
+        """steps and updates in turn until ``num_timesteps >= total_timesteps``; ``callback(locals_dict)`` every ``log_interval``
+        iterations with the keys PPO's has.  Between the callbacks nothing is read from the device."""
+        self._total_timesteps = int(total_timesteps)
+        while self.num_timesteps < self._total_timesteps:
+            for _ in range(self.train_freq):
+                self.collect_step()
+            if self.num_timesteps > self.learning_starts:
+                for _ in range(self.gradient_steps):
+                    self.train_step()
+            self.iteration += 1
+            if callback is not None and self.iteration % self.log_interval == 0:
+                self._read_episodes()
+                callback(dict(self=self, iteration=self.iteration, num_timesteps=self.num_timesteps, train=self.train_stats(),
+                              ep_rew_mean=self.ep_rew_mean, ep_len_mean=self.ep_len_mean))
+        self._read_episodes()
+        return self
+
+    # ---- checkpoints: plain dicts of tensors and numbers (torch.load(..., weights_only=True) reads them).  The replay buffer's contents
+    # are not saved: a resumed run collects again before it updates (learning_starts counts from 0 only if the caller sets it so)
+    def save(self, path):
+        hyper = {k: getattr(self, k) for k in self.HYPER + ("seed", "num_timesteps", "iteration", "n_calls", "n_updates", "n_target_updates",
+                                                            "_total_timesteps")}
+        opt = {"m": self.flat_m, "v": self.flat_v, "step": self.adam_step, "sampling_rows": self.policy._sample_rows}
+        torch.save({"algo": self.ALGO, "policy": self.policy.state_dict(), "target": self.target.state_dict(), "optimizer": opt, "hyper": hyper,
+                    "exploration_rate": float(self.policy.exploration_rate)}, path)
+
+    def load(self, path):
+        """restore the policy, the target network, Adam's state, the counters and the hyper-parameters saved by ``save`` into this instance
+        (same policy layout); returns self.  The replay buffer stays as it is."""
+        ck = torch.load(path, map_location=self.device, weights_only=True)
+        wrote = ck.get("algo", "PPO")
+        if wrote != self.ALGO:
+            raise ValueError(f"{self._who}.load: {path} was written by {wrote}, not by {self.ALGO} (each algorithm loads its own checkpoints only)")
+        opt = ck["optimizer"]
+        if "m" not in opt or opt["m"].shape != self.flat_m.shape:
+            n = opt["m"].numel() if "m" in opt else "no"
+            raise ValueError(f"{self._who}.load: the checkpoint's optimiser state has {n} Adam entries, this policy's {self.flat_m.numel()}")
+        self.policy.load_state_dict(ck["policy"])                       # copies in place: the parameters stay views of flat_p
+        self.target.load_state_dict(ck["target"])                       # ... and of flat_target
+        self.flat_m.copy_(opt["m"])
+        self.flat_v.copy_(opt["v"])
+        self.adam_step = int(opt["step"])
+        self.policy._sample_rows = int(opt["sampling_rows"])
+        self.policy._sample_seed = int(ck["hyper"]["seed"]) & (2 ** 64 - 1)
+        for k, v in ck["hyper"].items():
+            setattr(self, k, v)
+        self.policy.exploration_rate = float(ck["exploration_rate"])
+        return self
+
+
+__all__ = ["DQN", "DQNPolicy", "QNetwork", "dqn_loss", "exploration_schedule", "DQN_SCALARS"]

@@ -1,5 +1,6 @@
-"""RL entry point with the reference's command line (train_sb3.py:22-120, on this project's config resolver and its own PPO and A2C;
-``sb3=ppo`` or ``sb3=a2c`` chooses, as the reference's ``getattr(sb3, config.sb3.name)``):
+"""RL entry point with the reference's command line (train_sb3.py:22-120, on this project's config resolver and its own PPO, A2C and
+DQN; ``sb3=ppo``, ``sb3=a2c`` or ``sb3=dqn`` chooses, as the reference's ``getattr(sb3, config.sb3.name)``; DQN steps a frozen or
+torch-trained encoder only and calls back every ``sb3.algo_kwargs.log_interval`` (default 100) iterations of ``train_freq`` steps):
 
     python train_sb3.py ocr=slate pooling=transformer sb3=ppo sb3_acnet=mlp env=target-N4C4S3S1 num_envs=16 device=cuda:0 \
         pooling.ocr_checkpoint.local_file=outputs/train_ocr/SLATE-RandomN5C4S4S2/checkpoints/model_best.pth
@@ -30,7 +31,8 @@ from ocrl_amd import envs, sb3s  # noqa: E402
 from ocrl_amd.utils.config import compose  # noqa: E402
 
 log = logging.getLogger("train_sb3")
-ALGOS = {"PPO": sb3s.PPO, "A2C": sb3s.A2C}
+ALGOS = {"PPO": sb3s.PPO, "A2C": sb3s.A2C, "DQN": sb3s.DQN}
+POLICIES = {"DQN": sb3s.DQNPolicy}          # every other algorithm takes the actor-critic policy
 EVAL_ROW_OFFSET = 1 << 40          # the evaluation samples from its own rows of the policy's stream: training draws do not move
 
 
@@ -46,9 +48,9 @@ def build(config):
                   policy_kwargs=dict(config=config, features_extractor_class=sb3s.OCRExtractor, features_extractor_kwargs=dict(config=config)))
     if hasattr(config.sb3, "algo_kwargs"):
         kwargs.update(config.sb3.algo_kwargs.to_dict())
-    if "n_steps" in kwargs:
+    if "n_steps" in kwargs and issubclass(ALGOS[config.sb3.name], sb3s.on_policy.OnPolicyAlgorithm):
         kwargs["n_steps"] = max(1, kwargs["n_steps"] // config.num_envs)
-    return env, eval_env, ALGOS[config.sb3.name](sb3s.CustomActorCriticPolicy, env, **kwargs)
+    return env, eval_env, ALGOS[config.sb3.name](POLICIES.get(config.sb3.name, sb3s.CustomActorCriticPolicy), env, **kwargs)
 
 
 def evaluate(model, env, n_episodes, calls):
