@@ -1,4 +1,4 @@
-"""ctypes binding of libocrl_hip.so, derived from include/ocrl_hip.h and include/ocrl_hip_dqn.h (_abi.py reads them: the struct classes, the constants and every
+"""ctypes binding of libocrl_hip.so, derived from include/ocrl_hip.h, include/ocrl_hip_dqn.h and include/ocrl_hip_rollout.h (_abi.py reads them: the struct classes, the constants and every
 entry point's argtypes / restype come from the header's own declarations).  Fails loudly when the library is not built."""
 import ctypes
 import os
@@ -10,6 +10,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("OCRL_HIP_LIB") or os.path.join(_HERE, "libocrl_hip.so")      # OCRL_HIP_LIB: development builds
 HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "ocrl_hip.h")
 DQN_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "ocrl_hip_dqn.h")      # the DQN entry points: a second, self-contained header
+ROLLOUT_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "ocrl_hip_rollout.h")      # the task datasets' later frames: a third one
 _lib = None
 
 if not os.path.exists(HEADER_PATH):
@@ -29,6 +30,10 @@ with open(DQN_HEADER_PATH) as _f:
     ABI_DQN = _abi.read(_f.read())                      # a table of its own: ABI stays what ocrl_hip.h declares
 QnetDesc = ABI_DQN.structs["ocrl_qnet_desc"]
 QNET_MAX_LAYERS = len(QnetDesc().dims)
+if not os.path.exists(ROLLOUT_HEADER_PATH):
+    raise RuntimeError(f"{ROLLOUT_HEADER_PATH} is missing: ocrl_amd derives its binding of libocrl_hip.so from the header and runs from the source tree.")
+with open(ROLLOUT_HEADER_PATH) as _f:
+    ABI_ROLLOUT = _abi.read(_f.read())                  # no struct of its own: the descriptor is ocrl_hip.h's SpriteEnvDesc, passed with byref()
 
 
 def flat_segments(segs):
@@ -98,7 +103,7 @@ def lib():
     # when it was loaded before torch)
     import torch  # noqa: F401
     L = ctypes.CDLL(LIB_PATH)
-    for abi in (ABI, ABI_DQN):
+    for abi in (ABI, ABI_DQN, ABI_ROLLOUT):
         for name, (restype, argtypes) in abi.functions.items():
             f = getattr(L, name)
             f.argtypes = argtypes

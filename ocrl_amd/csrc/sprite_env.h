@@ -44,6 +44,9 @@ struct TaskScenesOut {              // task_scenes.hip; any of them may be null
 };
 
 int task_scenes_batch_launch(const ocrl_sprite_env_desc& d, unsigned long long seed, const long long* indices, int B, const TaskScenesOut& o, hipStream_t st);
+// the same scenes after a random walk: steps [B] or null (then drawn in [0, max_step]), steps_taken [B] or null
+int task_scenes_rollout_launch(const ocrl_sprite_env_desc& d, unsigned long long seed, const long long* indices, const int* steps, int max_step, int B,
+                               const TaskScenesOut& o, int* steps_taken, hipStream_t st);
 int sprite_env_reset_launch(const ocrl_sprite_env_desc& d, float* rows, int* aux, unsigned long long seed, const unsigned char* mask, long long episode,
                             hipStream_t st);
 int sprite_env_step_launch(const ocrl_sprite_env_desc& d, float* rows, int* aux, unsigned long long seed, const long long* actions, const SpriteStepOut& o,

@@ -29,30 +29,11 @@ __global__ __launch_bounds__(64) void sprite_env_step_kernel(ocrl_sprite_env_des
     int n = a[0], target = a[1];
     n = n < 1 ? 1 : (n > d.hi ? d.hi : n);                                   // a hand-set state cannot index outside the rows
     target = target < 0 ? 0 : (target >= n ? n - 1 : target);
-    float x = q[n * 5 + 3], y = q[n * 5 + 4];
-    const float tx = q[target * 5 + 3], ty = q[target * 5 + 4];
-    const float before = dist2d(tx, ty, x, y);
-    const long long act = actions[e];
-    if (act == 0) y = y + d.step_size;
-    else if (act == 1) x = x - d.step_size;
-    else if (act == 2) y = y - d.step_size;
-    else if (act == 3) x = x + d.step_size;                                  // anything else leaves the agent where it is
-    const float ra = d.agent_scale * 0.5f, top = 1.0f - ra;
-    x = fminf(fmaxf(x, ra), top);
-    y = fminf(fmaxf(y, ra), top);
-    q[n * 5 + 3] = x; q[n * 5 + 4] = y;
+    const SpriteMove m = sprite_move(d, q, n, target, a[2], actions[e]);      // the transition: sprite_episode.h
+    q[n * 5 + 3] = m.x; q[n * 5 + 4] = m.y;
     const int steps = a[2] + 1;
-    bool done = steps >= d.max_steps, success = false;
-    float reward = 0.f;
-    if (d.rew_type == 2) reward = dist2d(tx, ty, x, y) < before ? 0.01f : -0.01f;
-    for (int i = 0; i < n; ++i) {
-        if (dist2d(q[i * 5 + 3], q[i * 5 + 4], x, y) < d.agent_scale) {
-            if (i == target) { reward = 1.0f; success = true; }
-            else reward = d.rew_type == 1 ? 0.1f : 0.f;
-            done = true;
-            break;
-        }
-    }
+    const bool done = m.done, success = m.success;
+    const float reward = m.reward;
     double* ret = reinterpret_cast<double*>(a + 6);
     const double total = *ret + (double)reward;
     const int len = a[4] + 1;

@@ -1,5 +1,6 @@
-// C ABI of the sprite environments (include/ocrl_hip.h: ocrl_sprite_*): the Target and Odd-One-Out tasks of
+// C ABI of the sprite environments (include/ocrl_hip.h: ocrl_sprite_*, ocrl_task_scenes_batch; include/ocrl_hip_rollout.h): the Target and Odd-One-Out tasks of
 // envs/synthetic_envs/{base,target,oddoneout}.py as a vectorised environment.  Stateless: the caller owns the state buffer (ocrl_sprite_env_state_floats floats) and every output.
+#include "../../include/ocrl_hip_rollout.h"
 #include "scenes.h"
 #include "sprite_env.h"
 
@@ -62,6 +63,18 @@ int check_env(const ocrl_sprite_env_desc* d, const char* who) {
     }
     return 0;
 }
+
+// what both task-scene entry points require of their arguments before a launch; `others`: an output besides the three pixel ones is asked for
+int check_task_scenes(const ocrl_sprite_env_desc* d, const char* who, const long long* indices, int B, const float* obs, const unsigned char* obs_u8,
+                      const float* masks, bool others, const char* outputs) {
+    RC(check_env(d, who));
+    OCRL_REQUIRE(B >= 1, "%s: batch >= 1 (got %d)", who, B);
+    OCRL_REQUIRE(indices, "%s: null indices", who);
+    OCRL_REQUIRE(obs || obs_u8 || masks || others, "%s: no output requested (%s are all null)", who, outputs);
+    OCRL_REQUIRE(((uintptr_t)obs | (uintptr_t)masks) % 16 == 0 && (uintptr_t)obs_u8 % 4 == 0, "%s: obs and masks must be 16-byte aligned, obs_u8 4-byte aligned", who);
+    OCRL_REQUIRE((long long)B * cdiv(d->H, scenes_band_rows(d->H)) < (1LL << 31), "%s: %d scenes of %d rows exceed one launch", who, B, d->H);
+    return 0;
+}
 }  // namespace
 
 extern "C" {
@@ -108,14 +121,19 @@ int ocrl_sprite_state_obs(const float* rows, int E, int R, float* out, void* str
 
 int ocrl_task_scenes_batch(const ocrl_sprite_env_desc* d, unsigned long long seed, const long long* indices, int B, float* obs, unsigned char* obs_u8,
                            float* masks, float* objs, long long* labels, void* stream) {
-    RC(check_env(d, "ocrl_task_scenes_batch"));
-    OCRL_REQUIRE(B >= 1, "ocrl_task_scenes_batch: batch >= 1 (got %d)", B);
-    OCRL_REQUIRE(indices, "ocrl_task_scenes_batch: null indices");
-    OCRL_REQUIRE(obs || obs_u8 || masks || objs || labels, "ocrl_task_scenes_batch: no output requested (obs, obs_u8, masks, objs and labels are all null)");
-    OCRL_REQUIRE(((uintptr_t)obs | (uintptr_t)masks) % 16 == 0 && (uintptr_t)obs_u8 % 4 == 0,
-                 "ocrl_task_scenes_batch: obs and masks must be 16-byte aligned, obs_u8 4-byte aligned");
-    OCRL_REQUIRE((long long)B * cdiv(d->H, scenes_band_rows(d->H)) < (1LL << 31), "ocrl_task_scenes_batch: %d scenes of %d rows exceed one launch", B, d->H);
+    RC(check_task_scenes(d, "ocrl_task_scenes_batch", indices, B, obs, obs_u8, masks, objs || labels, "obs, obs_u8, masks, objs and labels"));
     return task_scenes_batch_launch(*d, seed, indices, B, TaskScenesOut{obs, obs_u8, masks, objs, labels}, static_cast<hipStream_t>(stream));
+}
+
+int ocrl_task_scenes_rollout_batch(const void* desc, unsigned long long seed, const long long* indices, const int* steps, int max_step, int B, float* obs,
+                                   unsigned char* obs_u8, float* masks, float* objs, long long* labels, int* steps_taken, void* stream) {
+    const ocrl_sprite_env_desc* d = static_cast<const ocrl_sprite_env_desc*>(desc);
+    OCRL_REQUIRE(steps || (max_step >= 0 && max_step <= 255),
+                 "ocrl_task_scenes_rollout_batch: max_step lies in [0, 255] when steps is null, the step is drawn in [0, max_step] (got %d)", max_step);
+    RC(check_task_scenes(d, "ocrl_task_scenes_rollout_batch", indices, B, obs, obs_u8, masks, objs || labels || steps_taken,
+                         "obs, obs_u8, masks, objs, labels and steps_taken"));
+    return task_scenes_rollout_launch(*d, seed, indices, steps, max_step, B, TaskScenesOut{obs, obs_u8, masks, objs, labels}, steps_taken,
+                                      static_cast<hipStream_t>(stream));
 }
 
 int ocrl_sprite_env_uniforms(unsigned long long seed, long long env0, int n_envs, long long episode, int first, int n, float* out, void* stream) {

@@ -1,6 +1,6 @@
 // How an episode of the sprite tasks is made (the Target and Odd-One-Out episodes, include/ocrl_hip.h: "The draws"), for every kernel
-// that starts one: the environments' reset and step (sprite_env.hip) and the task datasets' first frames (task_scenes.hip).  An episode
-// is a function of (seed, e, k) alone, so both see the same one.  Every file that includes this is compiled with -ffp-contract=off:
+// that starts one: the environments' reset and step (sprite_env.hip) and the task datasets' frames (task_scenes.hip).  An episode
+// is a function of (seed, e, k) alone, so both see the same one; how a step moves it is written once too (sprite_move).  Every file that includes this is compiled with -ffp-contract=off:
 // each position is the written sequence of fp32 roundings (tests/sprite_env_ref.py and tests/oddoneout_ref.py follow it bit for bit).
 #pragma once
 #include "sprite_env.h"
@@ -175,5 +175,44 @@ __device__ void new_episode(const ocrl_sprite_env_desc& d, float* __restrict__ q
     aux[0] = n; aux[1] = target; aux[2] = 0; aux[3] = (int)k; aux[4] = 0; aux[5] = kind;
     *reinterpret_cast<double*>(aux + 6) = 0.0;
 }
+
+// ---------------------------------------------------------------------------------------------------------------- the transition
+// One step of the environment (include/ocrl_hip.h: _step) from the rows q of an episode with n objects, `step_count` steps in: where the
+// agent stands afterwards, what the step pays and whether it ends the episode.  Nothing is written: the environment's step
+// (sprite_env.hip) commits the position or starts the next episode, the task datasets' walk (task_scenes.hip) commits it only while the
+// episode goes on.  Both call this, so a walked frame is a frame the environment shows.
+struct SpriteMove {
+    float x, y, reward;
+    bool done, success;
+};
+__device__ inline SpriteMove sprite_move(const ocrl_sprite_env_desc& d, const float* q, int n, int target, int step_count, long long act) {
+    float x = q[n * 5 + 3], y = q[n * 5 + 4];
+    const float tx = q[target * 5 + 3], ty = q[target * 5 + 4];
+    const float before = dist2d(tx, ty, x, y);
+    if (act == 0) y = y + d.step_size;
+    else if (act == 1) x = x - d.step_size;
+    else if (act == 2) y = y - d.step_size;
+    else if (act == 3) x = x + d.step_size;                                  // anything else leaves the agent where it is
+    const float ra = d.agent_scale * 0.5f, top = 1.0f - ra;
+    x = fminf(fmaxf(x, ra), top);
+    y = fminf(fmaxf(y, ra), top);
+    bool done = step_count + 1 >= d.max_steps, success = false;
+    float reward = 0.f;
+    if (d.rew_type == 2) reward = dist2d(tx, ty, x, y) < before ? 0.01f : -0.01f;
+    for (int i = 0; i < n; ++i) {
+        if (dist2d(q[i * 5 + 3], q[i * 5 + 4], x, y) < d.agent_scale) {
+            if (i == target) { reward = 1.0f; success = true; }
+            else reward = d.rew_type == 1 ? 0.1f : 0.f;
+            done = true;
+            break;
+        }
+    }
+    return SpriteMove{x, y, reward, done, success};
+}
+
+// the walk of a task dataset's later frames (include/ocrl_hip_rollout.h): the uniform random policy's action s is draw 2^19 + s of the
+// episode's own stream and the drawn step count draw 2^19 - 1; an episode's own draws stop below 72 002 (sprite_env.h: SPRITE_MAX_DRAWS)
+#define SPRITE_WALK_DRAW0 (1u << 19)
+#define SPRITE_WALK_MAX_STEPS (1 << 19)     // draws 2^19 .. 2^20 - 1: what the 20 bits of j leave
 
 }  // namespace

@@ -5,6 +5,8 @@
 // finds which rows cover each of them once, and writes every requested output from that: the fp32 planes with 16-byte stores, the bytes
 // as three words.  No atomics; every loop is bounded.  Compiled with -ffp-contract=off, as sprite_env.hip is: the same episode, bit for
 // bit, and the pixels are those of ocrl_sprite_render (the same predicates, sprite_shapes.h).
+// The rollout form (include/ocrl_hip_rollout.h; only_initial: False) is the same scene t steps later: after the episode the first thread
+// walks it under a uniform random policy with the environment's own transition (sprite_move, sprite_episode.h), then the same bands render.
 #include "scenes.h"
 #include "sprite_episode.h"
 
@@ -17,8 +19,19 @@ namespace {
 // workgroups at one band each gives a workgroup several bands of its scene instead, down to one workgroup per scene.
 #define TASK_SCENES_WORKGROUPS 1024
 
-__global__ __launch_bounds__(256) void task_scenes_batch_kernel(ocrl_sprite_env_desc d, int band_rows, int bands, int per_scene, unsigned long long seed,
-                                                                const long long* __restrict__ indices, TaskScenesOut o) {
+// what the rollout form adds to a scene (include/ocrl_hip_rollout.h); the first-frame kernel never reads it
+struct TaskWalk {
+    const int* steps;               // [B] or null: then the step is drawn in [0, max_step]
+    int max_step;
+    int* steps_taken;               // [B] or null
+};
+
+// One scene: the workgroup's first thread makes the episode into LDS and, with WALK, walks it there under the uniform random policy;
+// then the band loop renders that state.  The walk is the environment's own transition (sprite_move) on the episode's own stream: at
+// most min(t, max_steps) iterations of a few fp32 operations and n distances each, after the episode's much longer chain.
+template <bool WALK>
+__device__ __forceinline__ void task_scene(const ocrl_sprite_env_desc& d, int band_rows, int bands, int per_scene, unsigned long long seed,
+                                           const long long* __restrict__ indices, const TaskScenesOut& o, const TaskWalk& w) {
     __shared__ float s_rows[SPRITE_MAX_ROWS * 5];
     __shared__ __align__(8) int s_aux[SPRITE_AUX];
     __shared__ float s_cx[SPRITE_MAX_ROWS], s_cy[SPRITE_MAX_ROWS], s_r[SPRITE_MAX_ROWS];
@@ -28,7 +41,22 @@ __global__ __launch_bounds__(256) void task_scenes_batch_kernel(ocrl_sprite_env_
     const int b = blockIdx.x / per_scene, first = blockIdx.x % per_scene;       // this workgroup's bands: first, first + per_scene, ..
     if (threadIdx.x == 0) {
         const uint64_t i = (uint64_t)indices[b] & ((1ull << TASK_SCENES_INDEX_BITS) - 1ull);
-        new_episode(d, s_rows, s_aux, seed, (uint32_t)(i >> 24), (uint32_t)(i & 0xFFFFFFu));
+        const uint32_t e = (uint32_t)(i >> 24), k = (uint32_t)(i & 0xFFFFFFu);
+        new_episode(d, s_rows, s_aux, seed, e, k);
+        if constexpr (WALK) {
+            int t = w.steps ? w.steps[b] : (int)((env_bits24(seed, e, k, SPRITE_WALK_DRAW0 - 1u) * (uint32_t)(w.max_step + 1)) >> 24);
+            const int most = d.max_steps < SPRITE_WALK_MAX_STEPS ? d.max_steps : SPRITE_WALK_MAX_STEPS;
+            t = t < 0 ? 0 : (t > most ? most : t);
+            const int n = s_aux[0], target = s_aux[1];
+            int taken = 0;
+            for (; taken < t; ++taken) {                                     // step `taken` of the walk; its step_count is `taken`
+                const long long act = (long long)((env_bits24(seed, e, k, SPRITE_WALK_DRAW0 + (uint32_t)taken) * 4u) >> 24);
+                const SpriteMove m = sprite_move(d, s_rows, n, target, taken, act);
+                if (m.done) break;                                           // a step that ends the episode is not committed: no terminal frame
+                s_rows[n * 5 + 3] = m.x; s_rows[n * 5 + 4] = m.y;
+            }
+            if (w.steps_taken && first == 0) w.steps_taken[b] = taken;
+        }
     }
     __syncthreads();
     if (threadIdx.x < R) {                                                   // the sprite table of sprite_render_kernel; the state observation
@@ -103,14 +131,41 @@ __global__ __launch_bounds__(256) void task_scenes_batch_kernel(ocrl_sprite_env_
     }
 }
 
+
+__global__ __launch_bounds__(256) void task_scenes_batch_kernel(ocrl_sprite_env_desc d, int band_rows, int bands, int per_scene, unsigned long long seed,
+                                                                const long long* __restrict__ indices, TaskScenesOut o) {
+    task_scene<false>(d, band_rows, bands, per_scene, seed, indices, o, TaskWalk{nullptr, 0, nullptr});
+}
+
+__global__ __launch_bounds__(256) void task_scenes_rollout_kernel(ocrl_sprite_env_desc d, int band_rows, int bands, int per_scene, unsigned long long seed,
+                                                                  const long long* __restrict__ indices, TaskScenesOut o, TaskWalk w) {
+    task_scene<true>(d, band_rows, bands, per_scene, seed, indices, o, w);
+}
+
+}  // namespace
+
+namespace {
+// workgroups to a scene; each takes every per_scene-th band
+int task_scenes_per_scene(int B, int bands, const TaskScenesOut& o) {
+    int per_scene = TASK_SCENES_WORKGROUPS / B;
+    per_scene = per_scene < 1 ? 1 : (per_scene > bands ? bands : per_scene);
+    return (o.obs || o.obs_u8 || o.masks) ? per_scene : 1;                                 // rows and labels alone: one workgroup per scene
+}
 }  // namespace
 
 int task_scenes_batch_launch(const ocrl_sprite_env_desc& d, unsigned long long seed, const long long* indices, int B, const TaskScenesOut& o, hipStream_t st) {
     const int band_rows = scenes_band_rows(d.H), bands = cdiv(d.H, band_rows);
-    int per_scene = TASK_SCENES_WORKGROUPS / B;                                            // workgroups to a scene; each takes every per_scene-th band
-    per_scene = per_scene < 1 ? 1 : (per_scene > bands ? bands : per_scene);
-    if (!(o.obs || o.obs_u8 || o.masks)) per_scene = 1;                                   // rows and labels alone: one workgroup per scene
+    const int per_scene = task_scenes_per_scene(B, bands, o);
     hipLaunchKernelGGL(task_scenes_batch_kernel, dim3((unsigned)((long long)B * per_scene)), dim3(256), 0, st, d, band_rows, bands, per_scene, seed, indices, o);
     OCRL_CHECK_LAUNCH("task_scenes_batch");
+    return 0;
+}
+int task_scenes_rollout_launch(const ocrl_sprite_env_desc& d, unsigned long long seed, const long long* indices, const int* steps, int max_step, int B,
+                               const TaskScenesOut& o, int* steps_taken, hipStream_t st) {
+    const int band_rows = scenes_band_rows(d.H), bands = cdiv(d.H, band_rows);
+    const int per_scene = task_scenes_per_scene(B, bands, o);
+    hipLaunchKernelGGL(task_scenes_rollout_kernel, dim3((unsigned)((long long)B * per_scene)), dim3(256), 0, st, d, band_rows, bands, per_scene, seed, indices, o,
+                       TaskWalk{steps, max_step, steps_taken});
+    OCRL_CHECK_LAUNCH("task_scenes_rollout");
     return 0;
 }

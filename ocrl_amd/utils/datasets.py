@@ -4,7 +4,7 @@ scenes deterministically per index.  With raw_uint8 (the default of get_dataload
 it — "obss_u8", uint8 HWC — and the permute + /255 of utils/datasets.py:17 runs on the GPU (ocrl_obs_u8_to_f32) after a 4x smaller
 upload; raw_uint8=False gives the reference's float CHW "obss".  With dataset.on_device the synthetic scenes never exist on the host:
 device_scenes.py makes each batch on the GPU; so it does the task datasets (target-*, odd-one-out-*), the first frames of the sprite
-tasks' episodes, which exist on the device only."""
+tasks' episodes or (dataset.only_initial=False) frames from later steps of a random walk, which exist on the device only."""
 import os
 
 import numpy as np
@@ -86,13 +86,18 @@ def _device_loaders(config, batch_size, rank, world, seed, device, datafile):
 
 
 def _task_loaders(config, batch_size, rank, world, seed, device):
-    """a dataset config with a `task` mapping (an env config): the first frames of that task's episodes (device_scenes.py:
-    DeviceTaskScenes).  The descriptor is the environment's, so every refusal of ocrl_amd.envs applies; the frame size is the dataset's"""
+    """a dataset config with a `task` mapping (an env config): frames of that task's episodes (device_scenes.py: DeviceTaskScenes).  The
+    descriptor is the environment's, so every refusal of ocrl_amd.envs applies; the frame size is the dataset's.  dataset.only_initial
+    (default True): the first frame of every episode; False: one frame per episode at a step drawn in [0, dataset.rollout_steps] of a
+    uniform random policy's walk (default task.max_steps - 1, the last step an episode can show, capped at 255)"""
     from ..envs import env_desc
     from .device_scenes import DeviceTaskScenes
     desc = env_desc(config.task, 1)
     desc.H = int(config.obs_size)
     kw = dict(with_masks=bool(config.get("with_masks", False)), with_objs=bool(config.get("with_objs", False)))
+    if not config.get("only_initial", True):
+        steps = config.get("rollout_steps", None)
+        kw["rollout_steps"] = min(int(config.task.max_steps) - 1, 255) if steps is None else int(steps)
     train = DeviceTaskScenes(desc, config.get("synthetic_train", 100000), seed * 2 + 1, batch_size, device, shuffle=True, drop_last=True, rank=rank,
                              world=world, **kw)
     val = DeviceTaskScenes(desc, config.get("synthetic_val", 1000), seed * 2 + 2, batch_size, device, **kw)

@@ -3,6 +3,8 @@ exist on the host.  Scene i of a seed is a function of (seed, i) alone, so an ep
 integers (``epoch_indices``, pure torch), uploads them once per epoch, and every batch is one ocrl_scenes_batch call on the current
 stream.  Nothing is read back.  Same distribution and draw order as ocrl_amd/utils/data.py:random_sprite_scenes, not numpy's bit stream:
 dataset.on_device=True trains on other scenes of the same kind than the host loader does."""
+import ctypes
+
 import torch
 
 from .. import _bridge, _lib
@@ -119,13 +121,18 @@ class DeviceScenes(_DeviceLoader):
 
 
 class DeviceTaskScenes(_DeviceLoader):
-    """the first frames of a sprite task's episodes (ocrl_task_scenes_batch; ``desc`` from ocrl_amd.envs.env_desc, its H the frame size):
-    batches {"obss": fp32 [B,3,H,W], "masks": [B,hi+2,H,W,1] (with_masks: each row alone, the agent's after the objects', the background
-    last), "objs": [B,hi+1,5] and "labels": int64 [B,1], the target's row (with_objs)}.  Scene i is episode i of environment 0 of the
-    seed's streams: what a vectorised environment of that seed shows when it starts that episode."""
+    """frames of a sprite task's episodes (``desc`` from ocrl_amd.envs.env_desc, its H the frame size): batches {"obss": fp32 [B,3,H,W],
+    "masks": [B,hi+2,H,W,1] (with_masks: each row alone, the agent's after the objects', the background last), "objs": [B,hi+1,5] and
+    "labels": int64 [B,1], the target's row (with_objs)}.  Scene i is episode i of environment 0 of the seed's streams.
+    rollout_steps=None: its first frame (ocrl_task_scenes_batch), what a vectorised environment of that seed shows when it starts that
+    episode.  rollout_steps=T, an integer in [0, 255]: one frame of that episode at a step drawn uniformly in [0, T] from the episode's own
+    stream, reached under a uniform random policy (ocrl_task_scenes_rollout_batch, include/ocrl_hip_rollout.h): still a function of (seed, i)
+    alone, and never a terminal frame -- an episode that ends sooner gives its last frame before the end."""
 
-    def __init__(self, desc, n, seed, batch_size, device, with_masks=False, with_objs=False, shuffle=False, drop_last=False, rank=0, world=1):
+    def __init__(self, desc, n, seed, batch_size, device, with_masks=False, with_objs=False, shuffle=False, drop_last=False, rank=0, world=1,
+                 rollout_steps=None):
         self._desc = desc
+        self.rollout_steps = None if rollout_steps is None else int(rollout_steps)
         super().__init__(n, desc.H, seed, batch_size, device, with_masks, with_objs, shuffle, drop_last, rank, world)
 
     def _check(self):
@@ -137,16 +144,27 @@ class DeviceTaskScenes(_DeviceLoader):
                              "after the agent of a smaller episode would be matched as an object")
         if self.n > 1 << 24:
             raise ValueError(f"DeviceTaskScenes: at most 2^24 scenes, the episodes of one environment's stream (got {self.n})")
+        if self.rollout_steps is not None and not 0 <= self.rollout_steps <= 255:
+            raise ValueError(f"DeviceTaskScenes: rollout_steps is None (first frames) or an integer in [0, 255] (got {self.rollout_steps})")
 
-    def batch(self, idx):
-        """the scenes of idx (int64 [B] on the device, contiguous) as one ocrl_task_scenes_batch call on the current stream"""
+    def batch(self, idx, steps=None):
+        """the scenes of idx (int64 [B] on the device, contiguous) as one call on the current stream: ocrl_task_scenes_batch for first
+        frames, ocrl_task_scenes_rollout_batch at a drawn step (rollout_steps) or at ``steps`` (int32 [B] on the device, contiguous:
+        frame steps[b] of episode idx[b], whatever rollout_steps is)"""
         B, H, R = idx.shape[0], self.size, self._desc.hi + 1
         obs = torch.empty(B, 3, H, H, dtype=torch.float32, device=self.device)
         masks = torch.empty(B, R + 1, H, H, dtype=torch.float32, device=self.device) if self.with_masks else None
         objs = torch.empty(B, R, 5, dtype=torch.float32, device=self.device) if self.with_objs else None
         labels = torch.empty(B, 1, dtype=torch.int64, device=self.device) if self.with_objs else None
-        _bridge.launch(self.device, _lib.lib().ocrl_task_scenes_batch, self._desc, self.seed & 0xFFFFFFFFFFFFFFFF, _lib.ptr(idx), B,
-                       _lib.ptr(obs), None, _lib.ptr(masks), _lib.ptr(objs), _lib.ptr(labels))
+        seed = self.seed & 0xFFFFFFFFFFFFFFFF
+        if steps is None and self.rollout_steps is None:
+            _bridge.launch(self.device, _lib.lib().ocrl_task_scenes_batch, self._desc, seed, _lib.ptr(idx), B, _lib.ptr(obs), None, _lib.ptr(masks),
+                           _lib.ptr(objs), _lib.ptr(labels))
+        else:
+            if steps is not None and (steps.dtype != torch.int32 or steps.shape != (B,) or steps.device != idx.device or not steps.is_contiguous()):
+                raise ValueError(f"DeviceTaskScenes.batch: steps is a contiguous int32 [{B}] tensor beside idx (got {steps.dtype} {tuple(steps.shape)} on {steps.device})")
+            _bridge.launch(self.device, _lib.lib().ocrl_task_scenes_rollout_batch, ctypes.byref(self._desc), seed, _lib.ptr(idx), _lib.ptr(steps),
+                           self.rollout_steps or 0, B, _lib.ptr(obs), None, _lib.ptr(masks), _lib.ptr(objs), _lib.ptr(labels), None)
         out = {"obss": obs}
         if masks is not None:
             out["masks"] = masks.unsqueeze(-1)
