@@ -579,8 +579,9 @@ int ocrl_gae(const float* rewards, const float* values, const float* episode_sta
  *      (ocrl_sprite_env_state_floats floats, 256-byte aligned, zero before the first reset) and every output; everything is enqueued on
  *      `stream` with no host synchronisation, no atomics and no unbounded loop; reset and step run one thread per environment.
  * desc: E environments, H x H frames (H a multiple of 4 in [8, 512]); num_objects_range [lo, hi], 1 <= lo <= hi <= 15 (easy mode: within
- *   [2, 4]; normal mode: [4, 4], the modes' boxes); colour ids 0..6 = blue, green, yellow, red, cyan, pink, brown; shape ids 0..3 = square,
- *   triangle, star_4, circle (the other names of the reference's list are not drawn and are rejected); scales in (0, 1).  Anything else
+ *   [2, 4]; normal mode: [4, 4], the modes' boxes); colour ids 0..6 = blue, green, yellow, red, cyan, pink, brown; shape ids = the names' indices
+ *   in the reference's SHAPES list, of which six are drawn: 0 square, 1 triangle, 2 star_4, 3 circle, 7 star_5, 9 spoke_4 (ids 4, 5, 6, 8, 10, 11,
+ *   the list's other names, and anything outside the list are rejected with "shape id <N>"); scales in (0, 1).  Anything else
  *   is rejected: state_floats == 0, the other entry points return non-zero, with a message.
  * state: rows [E, hi + 1, 5] fp32 = (colour id, shape id, scale, x, y): objects 0..n-1, the agent in row n, zero rows after it; then,
  *   at the next multiple of 64 floats, 8 int32 words per environment: n, target index, step_count, episode index, episode length, the
@@ -621,8 +622,11 @@ int ocrl_gae(const float* rewards, const float* values, const float* episode_sta
  *   else 0.1 under rew_type 1 (normal) and 0 otherwise.  rewards fp32, dones and success bytes, ep_return (double; the rewards summed in
  *   double in step order) and ep_length of the episode that ended with this step (0 elsewhere), all [E].  A finished environment starts
  *   its next episode in the same launch.
- * _render: rows [E, R, 5] of any origin, R <= 16, painted in row order (a later row overwrites; colour -1, an unknown id or scale <= 0:
- *   not drawn) on black with the shape predicates of the pre-training scenes, pixel centre (i + 0.5) / H, the row index growing with y.
+ * _render: rows [E, R, 5] of any origin, R <= 16, painted in row order (a later row overwrites; a row is painted when its colour id is in
+ *   0..6, its shape id, truncated to an integer, is one of the six drawn ones and its scale > 0: colour -1, any other shape id and an empty
+ *   row are not drawn) on black with the shape predicates of the pre-training scenes and, for ids 7 and 9, star_5 (a ten-vertex star, tips
+ *   at 1.25 r, 72 degrees apart from straight up, notches at 0.63 r halfway between them; r = scale / 2, up = -y) and spoke_4 (an upright
+ *   Greek cross, bars of half width 0.4 r and half length 1.25 r), pixel centre (i + 0.5) / H, the row index growing with y.
  *   mode 0: uint8 [E, 3, H, W]; 1: [E, H, W, 3]; 2: masks [E, R + 1, H, W, 1] of 0 / 1: each row alone and unoccluded, the background
  *   (no row covers the pixel) last.
  * _state_obs: the observation of render_mode "state" (base.py:365-394) of rows [E, R, 5], R <= 16 -> out fp32 [E, R, 5]: columns 0, 1, 3, 4

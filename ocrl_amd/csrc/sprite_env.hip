@@ -88,7 +88,7 @@ __global__ __launch_bounds__(256) void sprite_render_kernel(const float* __restr
         if (j < R) {
             const float* q = rows + ((size_t)e * R + j) * 5;
             const float c = q[0], h = q[1], z = q[2];
-            if (c >= 0.f && c < 7.f && h >= 0.f && h < 4.f && z > 0.f) {     // colour -1, an unknown id or an empty row: not drawn
+            if (sprite_row_drawn(c, h, z)) {                                 // colour -1, an id that is not drawn or an empty row: not drawn
                 shape = (int)h; rgb = SPRITE_RGB[(int)c]; r = z * 0.5f; cx = q[3]; cy = q[4];
             }
         }
@@ -106,8 +106,8 @@ __global__ __launch_bounds__(256) void sprite_render_kernel(const float* __restr
             uint32_t any = 0;
             for (int j = 0; j < R; ++j) {
                 uint32_t m = 0;
-                if (s_shape[j] >= 0) {
-                    const float dy = py - s_cy[j];
+                const float dy = py - s_cy[j];
+                if (s_shape[j] >= 0 && sprite_in_reach(dy, s_r[j])) {
 #pragma unroll
                     for (int p = 0; p < 4; ++p) {
                         const float dx = ((float)(x4 + p) + 0.5f) / fH - s_cx[j];
@@ -122,8 +122,8 @@ __global__ __launch_bounds__(256) void sprite_render_kernel(const float* __restr
         }
         uint32_t px[4] = {0u, 0u, 0u, 0u};
         for (int j = 0; j < R; ++j) {                                        // painter's order: a later row overwrites
-            if (s_shape[j] < 0) continue;
             const float dy = py - s_cy[j];
+            if (s_shape[j] < 0 || !sprite_in_reach(dy, s_r[j])) continue;
 #pragma unroll
             for (int p = 0; p < 4; ++p) {
                 const float dx = ((float)(x4 + p) + 0.5f) / fH - s_cx[j];

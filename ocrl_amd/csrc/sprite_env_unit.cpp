@@ -3,6 +3,7 @@
 #include "../../include/ocrl_hip_rollout.h"
 #include "scenes.h"
 #include "sprite_env.h"
+#include "sprite_shapes.h"
 
 namespace {
 int check_env(const ocrl_sprite_env_desc* d, const char* who) {
@@ -28,7 +29,7 @@ int check_env(const ocrl_sprite_env_desc* d, const char* who) {
     for (int i = 0; i < d->n_shapes + 2; ++i) {
         if (i == d->n_shapes && !targeted) continue;
         const int s = i < d->n_shapes ? d->shapes[i] : (i == d->n_shapes ? d->target_shape : d->agent_shape);
-        OCRL_REQUIRE(s >= 0 && s < 4, "%s: shape id %d is not drawn (0 square, 1 triangle, 2 star_4, 3 circle)", who, s);
+        OCRL_REQUIRE(sprite_shape_drawn(s), "%s: shape id %d is not drawn (0 square, 1 triangle, 2 star_4, 3 circle, 7 star_5, 9 spoke_4)", who, s);
     }
     for (int i = 0; i < d->n_scales + 2; ++i) {
         if (i == d->n_scales && !targeted) continue;

@@ -66,7 +66,7 @@ __device__ __forceinline__ void task_scene(const ocrl_sprite_env_desc& d, int ba
         int shape = -1;
         uint32_t rgb = 0;
         float cx = 0.f, cy = 0.f, r = 0.f;
-        if (c >= 0.f && c < 7.f && h >= 0.f && h < 4.f && z > 0.f) {         // an empty row (the padding after the agent): not drawn
+        if (sprite_row_drawn(c, h, z)) {                                      // an empty row (the padding after the agent): not drawn
             shape = (int)h; rgb = SPRITE_RGB[(int)c]; r = z * 0.5f; cx = x; cy = y;
         }
         s_shape[j] = shape; s_rgb[j] = rgb; s_cx[j] = cx; s_cy[j] = cy; s_r[j] = r;
@@ -101,8 +101,8 @@ __device__ __forceinline__ void task_scene(const ocrl_sprite_env_desc& d, int ba
             bool any[4] = {false, false, false, false};
             for (int j = 0; j < R; ++j) {                                        // painter's order: a later row overwrites
                 bool cov[4] = {false, false, false, false};
-                if (s_shape[j] >= 0) {
-                    const float dy = py - s_cy[j];
+                const float dy = py - s_cy[j];
+                if (s_shape[j] >= 0 && sprite_in_reach(dy, s_r[j])) {
 #pragma unroll
                     for (int p = 0; p < 4; ++p) {
                         cov[p] = sprite_covers(s_shape[j], pxc[p] - s_cx[j], dy, s_r[j]);

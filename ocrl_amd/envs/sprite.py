@@ -12,7 +12,7 @@ from .. import _lib
 
 COLORS = ["blue", "green", "yellow", "red", "cyan", "pink", "brown"]
 SHAPES = ["square", "triangle", "star_4", "circle", "pentagon", "hexagon", "octagon", "star_5", "star_6", "spoke_4", "spoke_5", "spoke_6"]
-DRAWN_SHAPES = SHAPES[:4]                       # the predicates of ocrl_amd.utils.data._mask
+DRAWN_SHAPES = SHAPES[:4] + ["star_5", "spoke_4"]    # the predicates of ocrl_amd.utils.data._mask: ids 0..3, 7 and 9
 COLOR_BYTES = ((0, 0, 255), (0, 255, 0), (255, 255, 0), (255, 0, 0), (0, 255, 255), (255, 192, 203), (165, 42, 42))
 MODES, REW_TYPES = ("easy", "normal", "hard"), ("sparse", "normal", "dense")
 RENDER_MODES = {"image": 0, "rgb_array": 1, "mask": 2}
@@ -47,7 +47,8 @@ def _index(names, name, what, allowed=None):
 
 def env_desc(config, num_envs):
     """SpriteEnvDesc of an env config (configs/env/*.yaml).  Raises NotImplementedError, naming the key, for what is not built and
-    ValueError for a name or a value outside the task's lists; touches neither the library nor the GPU."""
+    ValueError for a name or a value outside the task's lists (a shape outside DRAWN_SHAPES: square, triangle, star_4, circle, star_5
+    and spoke_4 are drawn, the reference's six other names are not); touches neither the library nor the GPU."""
     who = "ocrl_amd.envs"
     name = getattr(config, "env", "TargetEnv")
     if name not in TASKS:
@@ -255,7 +256,9 @@ class SpriteEnv:
         return self._frames(RENDER_MODES[mode])
 
     def render_rows(self, rows, mode="image"):
-        """frames or masks of hand-made rows [E', R, 5] (R <= 16) at this environment's frame size"""
+        """frames or masks of hand-made rows [E', R, 5] (R <= 16) at this environment's frame size.  A row is painted when its colour id
+        is in 0..6, its shape id one of DRAWN_SHAPES' (0 square, 1 triangle, 2 star_4, 3 circle, 7 star_5, 9 spoke_4) and its scale > 0;
+        any other row stays blank"""
         return self._frames(RENDER_MODES[mode], rows)
 
     _AUX = {"n": 0, "target": 1, "step_count": 2, "episode": 3, "episode_length": 4}

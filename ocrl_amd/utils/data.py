@@ -9,9 +9,12 @@ import torch
 
 COLORS = np.array([[0, 0, 255], [0, 255, 0], [255, 255, 0], [255, 0, 0]], dtype=np.uint8)
 SCALES = (0.15, 0.22)
+_COS36, _SIN36 = float(np.cos(np.radians(36.0))), float(np.sin(np.radians(36.0)))
 
 
 def _mask(shape_id, xx, yy, cx, cy, r):
+    """the pixels a sprite covers, for the six drawn shape ids (csrc/sprite_shapes.h holds the same predicates in fp32);
+    random_sprite_scenes draws the first four"""
     dx, dy = xx - cx, yy - cy
     if shape_id == 0:      # square
         return (np.abs(dx) <= r) & (np.abs(dy) <= r)
@@ -20,6 +23,17 @@ def _mask(shape_id, xx, yy, cx, cy, r):
         return (t >= 0) & (t <= 1) & (np.abs(dx) <= r * t)
     if shape_id == 2:      # star_4
         return np.sqrt(np.abs(dx)) + np.sqrt(np.abs(dy)) <= np.sqrt(r) * 1.25
+    if shape_id == 7:      # star_5: tips at 1.25 r, 72 degrees apart from straight up (-y), notches at 0.63 r halfway between them
+        tip, an, bn = 1.25 * r, 0.63 * _COS36 * r, 0.63 * _SIN36 * r
+        m = np.zeros(np.shape(dx), dtype=bool)
+        for k in range(5):     # the tip's triangle: apex at the tip, sides through the two neighbouring notches, cut off at a = 0
+            s, c = np.sin(np.radians(72.0 * k)), np.cos(np.radians(72.0 * k))
+            a, b = dx * s - dy * c, np.abs(dx * c + dy * s)
+            m |= (a >= 0) & (b * (tip - an) <= bn * (tip - a))
+        return m
+    if shape_id == 9:      # spoke_4: an upright Greek cross
+        ax, ay = np.abs(dx), np.abs(dy)
+        return ((ax <= 0.4 * r) & (ay <= 1.25 * r)) | ((ay <= 0.4 * r) & (ax <= 1.25 * r))
     return dx * dx + dy * dy <= r * r   # circle
 
 
