@@ -1,4 +1,4 @@
-"""ctypes binding of libocrl_hip.so, derived from include/ocrl_hip.h, include/ocrl_hip_dqn.h and include/ocrl_hip_rollout.h (_abi.py reads them: the struct classes, the constants and every
+"""ctypes binding of libocrl_hip.so, derived from include/ocrl_hip.h, include/ocrl_hip_dqn.h, include/ocrl_hip_rollout.h and include/ocrl_hip_replay.h (_abi.py reads them: the struct classes, the constants and every
 entry point's argtypes / restype come from the header's own declarations).  Fails loudly when the library is not built."""
 import ctypes
 import os
@@ -11,6 +11,7 @@ LIB_PATH = os.environ.get("OCRL_HIP_LIB") or os.path.join(_HERE, "libocrl_hip.so
 HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "ocrl_hip.h")
 DQN_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "ocrl_hip_dqn.h")      # the DQN entry points: a second, self-contained header
 ROLLOUT_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "ocrl_hip_rollout.h")      # the task datasets' later frames: a third one
+REPLAY_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "ocrl_hip_replay.h")      # DQN's replay extensions: a fourth one
 _lib = None
 
 if not os.path.exists(HEADER_PATH):
@@ -34,6 +35,10 @@ if not os.path.exists(ROLLOUT_HEADER_PATH):
     raise RuntimeError(f"{ROLLOUT_HEADER_PATH} is missing: ocrl_amd derives its binding of libocrl_hip.so from the header and runs from the source tree.")
 with open(ROLLOUT_HEADER_PATH) as _f:
     ABI_ROLLOUT = _abi.read(_f.read())                  # no struct of its own: the descriptor is ocrl_hip.h's SpriteEnvDesc, passed with byref()
+if not os.path.exists(REPLAY_HEADER_PATH):
+    raise RuntimeError(f"{REPLAY_HEADER_PATH} is missing: ocrl_amd derives its binding of libocrl_hip.so from the header and runs from the source tree.")
+with open(REPLAY_HEADER_PATH) as _f:
+    ABI_REPLAY = _abi.read(_f.read())                   # no struct of its own: the TD step's descriptor is ocrl_hip_dqn.h's QnetDesc, passed with byref()
 
 
 def flat_segments(segs):
@@ -103,7 +108,7 @@ def lib():
     # when it was loaded before torch)
     import torch  # noqa: F401
     L = ctypes.CDLL(LIB_PATH)
-    for abi in (ABI, ABI_DQN, ABI_ROLLOUT):
+    for abi in (ABI, ABI_DQN, ABI_ROLLOUT, ABI_REPLAY):
         for name, (restype, argtypes) in abi.functions.items():
             f = getattr(L, name)
             f.argtypes = argtypes

@@ -2,6 +2,7 @@
 // The Q head runs on the actor-critic head's tile code (acnet_tile.h) as AcnetArgs with an empty shared trunk, the hidden layers as the
 // policy trunk, the output Linear as the action head and no value head (wv == null); its plain forward is acnet_fwd_launch itself.
 #pragma once
+#include "../../include/ocrl_hip_dqn.h"
 #include "acnet.h"
 
 #define SITE_DQN_ACT 410u          // rng site of the exploration coin and the random action (acnet.h has 400, sprite_env.h 500 ..)
@@ -38,6 +39,21 @@ struct ReplayGatherArgs {
     float* rewards_out;
     unsigned char* dones_out;
 };
+
+// the Q head's host side (dqn_unit.cpp), shared by the entry points of ocrl_hip_dqn.h and ocrl_hip_replay.h: the limits, the workspace's
+// layout, the head as the tile code's arguments and the fold of the slabs' partial dw
+namespace qnet {
+struct QLay {
+    size_t saved[ACNET_MAX_LAYERS], slab, scal, total;
+    long long off[2 * ACNET_MAX_LAYERS + 3];
+    int np, S, ntiles;
+};
+int check_qnet(const ocrl_qnet_desc* d, const char* who);
+QLay q_layout(const ocrl_qnet_desc* d);
+void fill_args(AcnetArgs& a, const ocrl_qnet_desc* d, const QLay& y, const float* x, const float* const* w, float* ws, bool saved);
+int check_ptrs(const void* const* w, int np, const char* who);
+int reduce_dw(const AcnetArgs& a, const QLay& y, float* const* dw, hipStream_t st);
+}  // namespace qnet
 
 int dqn_act_launch(const AcnetArgs& a, const DqnActArgs& s, hipStream_t st);
 int dqn_act_uniforms_launch(unsigned long long seed, unsigned long long row_offset, long long n, float* out, hipStream_t st);

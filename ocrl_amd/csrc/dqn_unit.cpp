@@ -8,12 +8,10 @@ constexpr int QNET_MAX_LAYERS = ACNET_MAX_LAYERS;
 static_assert(sizeof(ocrl_qnet_desc::dims) == QNET_MAX_LAYERS * sizeof(int) && sizeof(ocrl_qnet_desc::acts) == QNET_MAX_LAYERS * sizeof(int),
               "ocrl_qnet_desc holds the layers of one acnet trunk");
 static_assert(sizeof(ocrl_qnet_desc) == (4 + 2 * QNET_MAX_LAYERS) * sizeof(int), "ocrl_qnet_desc is 20 ints without padding");
+}  // namespace
 
-struct QLay {
-    size_t saved[QNET_MAX_LAYERS], slab, scal, total;
-    long long off[2 * QNET_MAX_LAYERS + 3];
-    int np, S, ntiles;
-};
+// the Q head's host side, shared with replay_ext_unit.cpp (declared in dqn.h)
+namespace qnet {
 
 int check_qnet(const ocrl_qnet_desc* d, const char* who) {
     OCRL_REQUIRE(d, "%s: null descriptor", who);
@@ -89,7 +87,8 @@ int reduce_dw(const AcnetArgs& a, const QLay& y, float* const* dw, hipStream_t s
     for (int q = 0; q < y.np; ++q) r.dst[q] = dw[q];
     return acnet_reduce_launch(r, st);
 }
-}  // namespace
+}  // namespace qnet
+using namespace qnet;
 
 extern "C" {
 

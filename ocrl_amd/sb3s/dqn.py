@@ -5,8 +5,9 @@ Discrete sprite tasks and the same ``OCRExtractor``.
 that package's hyper-parameter names and defaults: none of its text is copied.  The GPU work is the library's (include/ocrl_hip_dqn.h):
 acting is ``ocrl_dqn_act`` (the Q head's forward and the epsilon-greedy choice in one launch after the extractor), the replay buffer
 (replay.py) samples and reads a batch in two launches, the loss is ``dqn_loss`` (``ocrl_dqn_td_fwd_bwd``: the TD target, the Huber loss
-and the head's gradient, fused) and the update ``ocrl_flat_clip_adam_l2`` on one flat parameter buffer.  Where this departs from
-stable-baselines3 is listed in DESIGN.md §7."""
+and the head's gradient, fused) and the update ``ocrl_flat_clip_adam_l2`` on one flat parameter buffer.  Double Q-learning (van Hasselt et al. 2016),
+n-step returns and proportional prioritized replay (Schaul et al. 2016) are keyword arguments of ``DQN``, off by default
+(include/ocrl_hip_replay.h; ``sb3=dqn_per``).  Where this departs from stable-baselines3 and from those papers is listed in DESIGN.md §7."""
 import collections
 import copy
 import ctypes
@@ -20,7 +21,7 @@ from .. import _bridge, _lib
 from ..ocrs.flat_module import FlatParamModule
 from .custom_acnets import _n_actions
 from .on_policy import OnPolicyAlgorithm, _check_constant, _tensor
-from .replay import ReplayBuffer
+from .replay import MAX_N_STEP, ReplayBuffer
 
 _WHO = "ocrl_amd.sb3s"
 _ACT = {"relu": (nn.ReLU, 1), "tanh": (nn.Tanh, 2)}
@@ -89,6 +90,40 @@ class _DqnFn(torch.autograd.Function):
     def backward(ctx, gloss, _gscal):
         dx = None if ctx.dx is None else ctx.dx * gloss
         return (dx, None, None, None, None, None, None, None, None, *[g * gloss for g in ctx.gs])
+
+
+class _DqnExtFn(torch.autograd.Function):
+    """_DqnFn with the optional inputs of ocrl_dqn_td_fwd_bwd_ext (include/ocrl_hip_replay.h); also returns |delta| per row"""
+
+    @staticmethod
+    def forward(ctx, features, next_q, next_q_online, actions, rewards, dones, discounts, weights, gamma, dims, acts, A, *params):
+        x, ps = _bridge.inputs(_WHO, features, params)
+        dev = x.device
+        B, F = x.shape
+        vec = lambda t, dt: None if t is None else t.detach().to(device=dev, dtype=dt).reshape(-1).contiguous()
+        actions, rewards, dones = vec(actions, torch.int64), vec(rewards, torch.float32), vec(dones, torch.uint8)
+        discounts, weights = vec(discounts, torch.float32), vec(weights, torch.float32)
+        next_q, next_q_online = vec(next_q, torch.float32), vec(next_q_online, torch.float32)
+        for name, t, n in (("actions", actions, B), ("rewards", rewards, B), ("dones", dones, B), ("next_q", next_q, B * A),
+                           ("next_q_online", next_q_online, B * A), ("discounts", discounts, B), ("weights", weights, B)):
+            if t is not None and t.numel() != n:
+                raise ValueError(f"{_WHO}.dqn_loss: {name} has {t.numel()} entries for a batch of {B} and {A} actions")
+        d, ws = _desc(B, F, A, dims, acts, dev)
+        scal = torch.empty(3, device=dev, dtype=torch.float32)
+        abs_td = torch.empty(B, device=dev, dtype=torch.float32)
+        gs = [torch.empty_like(p) for p in ps]
+        dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+        _bridge.launch(dev, _lib.lib().ocrl_dqn_td_fwd_bwd_ext, ctypes.byref(d), _lib.ptr(x), _lib.ptrs(ps), _lib.ptr(next_q), _lib.ptr(next_q_online),
+                       _lib.ptr(actions), _lib.ptr(rewards), _lib.ptr(dones), _lib.ptr(discounts), _lib.ptr(weights), float(gamma), _lib.ptr(scal),
+                       _lib.ptr(abs_td), _lib.ptr(dx), _lib.ptrs(gs), _lib.ptr(ws), ws.numel())
+        ctx.gs, ctx.dx = gs, dx
+        ctx.mark_non_differentiable(scal, abs_td)
+        return scal[0].clone(), scal, abs_td
+
+    @staticmethod
+    def backward(ctx, gloss, _gscal, _gtd):
+        dx = None if ctx.dx is None else ctx.dx * gloss
+        return (dx,) + (None,) * 11 + tuple(g * gloss for g in ctx.gs)
 
 
 class QNetwork(nn.Module):
@@ -186,14 +221,24 @@ class DQNPolicy(nn.Module):
         return self.act(self.extract_features(obs), deterministic=deterministic)
 
 
-def dqn_loss(policy, features, next_q, actions, rewards, dones, gamma):
+def dqn_loss(policy, features, next_q, actions, rewards, dones, gamma, next_q_online=None, discounts=None, weights=None, return_abs_td=False):
     """DQN's loss of ``policy`` on a feature batch [B, F] (``policy.extract_features(obs)``) against the target network's
     ``next_q`` [B, n]: (loss, metrics).  ``loss`` is the mean Huber loss of Q[a] - (r + gamma max next_q, or r where done), attached to
     autograd: ``backward()`` puts the gradients on the head's parameters and on ``features``.  ``metrics`` maps DQN_SCALARS to detached 0-d
-    tensors."""
+    tensors.
+
+    The extensions (ocrl_dqn_td_fwd_bwd_ext; with none of them set the call is ocrl_dqn_td_fwd_bwd's, as before): ``next_q_online`` [B, n]
+    chooses the action whose ``next_q`` bootstraps (double Q-learning), ``discounts`` [B] replaces ``gamma`` per row (gamma^m of an n-step
+    return), ``weights`` [B] scales each row's loss and gradient (importance weights), and ``return_abs_td`` adds the rows' |Q[a] - y|
+    [B], detached, as a third result."""
     dims, acts = policy.q_net._layout()
-    loss, scal = _DqnFn.apply(features, next_q, actions, rewards, dones, gamma, dims, acts, policy.q_net.n_actions, *policy.q_net._param_list())
-    return loss, {k: scal[i] for i, k in enumerate(DQN_SCALARS)}
+    if next_q_online is None and discounts is None and weights is None and not return_abs_td:
+        loss, scal = _DqnFn.apply(features, next_q, actions, rewards, dones, gamma, dims, acts, policy.q_net.n_actions, *policy.q_net._param_list())
+        return loss, {k: scal[i] for i, k in enumerate(DQN_SCALARS)}
+    loss, scal, abs_td = _DqnExtFn.apply(features, next_q, next_q_online, actions, rewards, dones, discounts, weights, gamma, dims, acts,
+                                         policy.q_net.n_actions, *policy.q_net._param_list())
+    metrics = {k: scal[i] for i, k in enumerate(DQN_SCALARS)}
+    return (loss, metrics, abs_td) if return_abs_td else (loss, metrics)
 
 
 def exploration_schedule(frac, initial_eps, final_eps, fraction):
@@ -218,11 +263,15 @@ class DQN:
     ``gradient_steps`` updates once ``num_timesteps > learning_starts``.  Every environment flips its own exploration coin."""
     ALGO = "DQN"
     HYPER = ("learning_rate", "buffer_size", "learning_starts", "batch_size", "tau", "gamma", "train_freq", "gradient_steps",
-             "target_update_interval", "exploration_fraction", "exploration_initial_eps", "exploration_final_eps", "max_grad_norm")
+             "target_update_interval", "exploration_fraction", "exploration_initial_eps", "exploration_final_eps", "max_grad_norm",
+             "double_q", "n_step", "prioritized_replay", "prioritized_replay_alpha", "prioritized_replay_beta0", "prioritized_replay_beta_final",
+             "prioritized_replay_eps")
 
     def __init__(self, policy, env, learning_rate=1e-4, buffer_size=1_000_000, learning_starts=50_000, batch_size=32, tau=1.0, gamma=0.99,
                  train_freq=4, gradient_steps=1, target_update_interval=10_000, exploration_fraction=0.1, exploration_initial_eps=1.0,
-                 exploration_final_eps=0.05, max_grad_norm=10, seed=0, device="cuda", policy_kwargs=None, log_interval=100, **ignored_sb3_kwargs):
+                 exploration_final_eps=0.05, max_grad_norm=10, seed=0, device="cuda", policy_kwargs=None, log_interval=100, double_q=False, n_step=1,
+                 prioritized_replay=False, prioritized_replay_alpha=0.6, prioritized_replay_beta0=0.4, prioritized_replay_beta_final=1.0,
+                 prioritized_replay_eps=1e-6, **ignored_sb3_kwargs):
         who = self._who = f"{_WHO}.{self.ALGO}"
         self.learning_rate = _check_constant(who, "learning_rate", learning_rate)
         if int(gradient_steps) < 1:
@@ -233,6 +282,18 @@ class DQN:
             raise ValueError(f"{who}: 0 < exploration_fraction <= 1 (got {exploration_fraction})")
         self.n_actions = _n_actions(env.action_space)                 # Discrete only: the policy's own message otherwise
         self.env, self.n_envs = env, int(env.num_envs)
+        self.double_q, self.n_step, self.prioritized_replay = bool(double_q), int(n_step), bool(prioritized_replay)
+        slots = max(2, int(buffer_size) // self.n_envs)
+        if not 1 <= self.n_step <= MAX_N_STEP or self.n_step >= slots:
+            raise ValueError(f"{who}: n_step must lie in 1 .. {MAX_N_STEP} and below the replay ring's {slots} slots (got {n_step})")
+        for name, v in (("prioritized_replay_alpha", prioritized_replay_alpha), ("prioritized_replay_beta0", prioritized_replay_beta0),
+                        ("prioritized_replay_beta_final", prioritized_replay_beta_final)):
+            if not 0.0 <= float(v) <= 1.0:
+                raise ValueError(f"{who}: 0 <= {name} <= 1 (got {v})")
+        if not float(prioritized_replay_eps) >= 0.0:
+            raise ValueError(f"{who}: prioritized_replay_eps >= 0 (got {prioritized_replay_eps})")
+        self.prioritized_replay_alpha, self.prioritized_replay_eps = float(prioritized_replay_alpha), float(prioritized_replay_eps)
+        self.prioritized_replay_beta0, self.prioritized_replay_beta_final = float(prioritized_replay_beta0), float(prioritized_replay_beta_final)
         self.buffer_size, self.learning_starts, self.batch_size = int(buffer_size), int(learning_starts), int(batch_size)
         self.tau, self.gamma = float(tau), float(gamma)
         self.train_freq, self.gradient_steps, self.target_update_interval = int(train_freq), int(gradient_steps), int(target_update_interval)
@@ -260,6 +321,7 @@ class DQN:
         self._total_timesteps = 0
         self._obs_shape = tuple(env.observation_space.shape)
         self.replay_buffer = None
+        self.last_weights = None                                      # the importance weights [batch_size] of the last prioritized update
         self._last_obs = None
         self._ep_ret, self._ep_len = np.zeros(self.n_envs), np.zeros(self.n_envs, dtype=np.int64)
         self._episodes = collections.deque(maxlen=100)
@@ -352,7 +414,8 @@ class DQN:
             self._last_obs = _tensor(self.env.reset(), self.device)
             self._ep_ret[:], self._ep_len[:] = 0.0, 0
         if self.replay_buffer is None:
-            self.replay_buffer = ReplayBuffer(self.buffer_size, E, self._obs_shape, self.device, self._last_obs.dtype, self.seed)
+            self.replay_buffer = ReplayBuffer(self.buffer_size, E, self._obs_shape, self.device, self._last_obs.dtype, self.seed,
+                                              prioritized=self.prioritized_replay, n_step=self.n_step)
         self.policy.eval()
         with torch.no_grad():
             eps = self.epsilon()
@@ -390,9 +453,51 @@ class DQN:
             self._successes.append(bool(host[t, 1, e]))
 
     # ---- the update
+    def beta(self):
+        """the importance weights' exponent: linear from prioritized_replay_beta0 to prioritized_replay_beta_final over the current
+        ``learn()``'s timesteps, like epsilon"""
+        frac = min(self.num_timesteps / max(self._total_timesteps, 1), 1.0)
+        return self.prioritized_replay_beta0 + frac * (self.prioritized_replay_beta_final - self.prioritized_replay_beta0)
+
+    def _train_step_ext(self):
+        """``train_step`` with any of double_q, n_step > 1 and prioritized_replay: the batch is drawn in proportion to the
+        priorities or among the whole n-step windows, read with its n-step returns, the online network names the bootstrap action, the
+        importance weights scale the loss, and the rows' |TD error| go back into the priority store.  No host read either."""
+        buf = self.replay_buffer
+        if len(buf) == 0:
+            raise RuntimeError(f"{self._who}.train_step: learning_starts = {self.learning_starts} leaves {buf.pos} vec steps in the replay ring at "
+                               f"the first update, fewer than n_step = {self.n_step}: raise learning_starts to at least "
+                               f"{self.n_step * self.n_envs} timesteps")
+        weights = None
+        if self.prioritized_replay:
+            idx, weights = buf.sample_prioritized(self.batch_size, self.n_updates, self.beta())
+        else:
+            idx = buf.sample_indices(self.batch_size, self.n_updates, self.n_step)
+        batch = buf.gather(idx, self.n_step, self.gamma) if self.n_step > 1 else buf.gather(idx)
+        self.policy.train()
+        next_obs = self._obs(batch.next_observations)
+        with torch.no_grad():
+            next_q = self.target.q_values(next_obs)
+            next_q_online = self.policy.q_values(next_obs) if self.double_q else None
+        self.flat_g.zero_()
+        features = self.policy.extract_features(self._obs(batch.observations))
+        loss, m, abs_td = dqn_loss(self.policy, features, next_q, batch.actions, batch.rewards, batch.dones, self.gamma, next_q_online=next_q_online,
+                                   discounts=batch.discounts, weights=weights, return_abs_td=True)
+        loss.backward()
+        self._adam_step()
+        if self.prioritized_replay:
+            buf.update_priorities(idx, abs_td, self.prioritized_replay_alpha, self.prioritized_replay_eps)
+            self.last_weights = weights
+        self.n_updates += 1
+        self._acc += torch.cat([torch.stack([m[k] for k in DQN_SCALARS]), self._norm])
+        self._acc_n += 1
+        return loss
+
     def train_step(self):
         """one gradient step: a batch from the replay buffer, the target network's Q of the next observations, ``dqn_loss``, the backward
         through the extractor, clip + Adam.  Nothing is read from the device: the scalars add up in ``_acc`` until a callback reads them."""
+        if self.double_q or self.n_step > 1 or self.prioritized_replay:
+            return self._train_step_ext()
         batch = self.replay_buffer.sample(self.batch_size, self.n_updates)
         with torch.no_grad():
             next_q = self.target.q_values(self._obs(batch.next_observations))
@@ -451,7 +556,8 @@ class DQN:
 
     def load(self, path):
         """restore the policy, the target network, Adam's state, the counters and the hyper-parameters saved by ``save`` into this instance
-        (same policy layout); returns self.  The replay buffer stays as it is."""
+        (same policy layout); returns self.  The replay buffer stays as it is, unless the loaded ``n_step`` / ``prioritized_replay`` are not
+        the ones it was built with: then it is dropped, and the next ``collect_step`` builds one that fits."""
         ck = torch.load(path, map_location=self.device, weights_only=True)
         wrote = ck.get("algo", "PPO")
         if wrote != self.ALGO:
@@ -470,6 +576,9 @@ class DQN:
         for k, v in ck["hyper"].items():
             setattr(self, k, v)
         self.policy.exploration_rate = float(ck["exploration_rate"])
+        buf = self.replay_buffer
+        if buf is not None and (buf.prioritized, buf.n_step) != (self.prioritized_replay, self.n_step):
+            self.replay_buffer = None
         return self
 
 
