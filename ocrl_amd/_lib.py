@@ -1,4 +1,4 @@
-"""ctypes binding of libocrl_hip.so, derived from include/ocrl_hip.h, include/ocrl_hip_dqn.h, include/ocrl_hip_rollout.h and include/ocrl_hip_replay.h (_abi.py reads them: the struct classes, the constants and every
+"""ctypes binding of libocrl_hip.so, derived from include/ocrl_hip.h, include/ocrl_hip_dqn.h, include/ocrl_hip_rollout.h, include/ocrl_hip_replay.h and include/ocrl_hip_c51.h (_abi.py reads them: the struct classes, the constants and every
 entry point's argtypes / restype come from the header's own declarations).  Fails loudly when the library is not built."""
 import ctypes
 import os
@@ -12,6 +12,7 @@ HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "ocrl_hip.h")
 DQN_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "ocrl_hip_dqn.h")      # the DQN entry points: a second, self-contained header
 ROLLOUT_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "ocrl_hip_rollout.h")      # the task datasets' later frames: a third one
 REPLAY_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "ocrl_hip_replay.h")      # DQN's replay extensions: a fourth one
+C51_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "ocrl_hip_c51.h")      # DQN's categorical head: a fifth one
 _lib = None
 
 if not os.path.exists(HEADER_PATH):
@@ -39,6 +40,11 @@ if not os.path.exists(REPLAY_HEADER_PATH):
     raise RuntimeError(f"{REPLAY_HEADER_PATH} is missing: ocrl_amd derives its binding of libocrl_hip.so from the header and runs from the source tree.")
 with open(REPLAY_HEADER_PATH) as _f:
     ABI_REPLAY = _abi.read(_f.read())                   # no struct of its own: the TD step's descriptor is ocrl_hip_dqn.h's QnetDesc, passed with byref()
+if not os.path.exists(C51_HEADER_PATH):
+    raise RuntimeError(f"{C51_HEADER_PATH} is missing: ocrl_amd derives its binding of libocrl_hip.so from the header and runs from the source tree.")
+with open(C51_HEADER_PATH) as _f:
+    ABI_C51 = _abi.read(_f.read())                      # a struct of its own: the categorical head's descriptor
+C51Desc = ABI_C51.structs["ocrl_c51_desc"]
 
 
 def flat_segments(segs):
@@ -65,6 +71,16 @@ def qnet_desc(B, F, A, dims, acts):
     if len(dims) > QNET_MAX_LAYERS or len(acts) != len(dims):
         raise ValueError(f"ocrl_amd: at most {QNET_MAX_LAYERS} hidden layers, one activation code each (got {len(dims)}, {len(acts)})")
     d = QnetDesc(B=B, F=F, A=A, n=len(dims))
+    for l, (w, a) in enumerate(zip(dims, acts)):
+        d.dims[l], d.acts[l] = int(w), int(a)
+    return d
+
+
+def c51_desc(B, F, A, Z, dims, acts, dueling=False):
+    """C51Desc of a categorical head: Z atoms per action, dims / acts as qnet_desc takes them, dueling = the value Linear beside the advantages"""
+    if len(dims) > len(C51Desc().dims) or len(acts) != len(dims):
+        raise ValueError(f"ocrl_amd: at most {len(C51Desc().dims)} hidden layers, one activation code each (got {len(dims)}, {len(acts)})")
+    d = C51Desc(B=B, F=F, A=A, Z=Z, n=len(dims), dueling=int(bool(dueling)))
     for l, (w, a) in enumerate(zip(dims, acts)):
         d.dims[l], d.acts[l] = int(w), int(a)
     return d
@@ -108,14 +124,14 @@ def lib():
     # when it was loaded before torch)
     import torch  # noqa: F401
     L = ctypes.CDLL(LIB_PATH)
-    for abi in (ABI, ABI_DQN, ABI_ROLLOUT, ABI_REPLAY):
+    for abi in (ABI, ABI_DQN, ABI_ROLLOUT, ABI_REPLAY, ABI_C51):
         for name, (restype, argtypes) in abi.functions.items():
             f = getattr(L, name)
             f.argtypes = argtypes
             if restype is not ctypes.c_int:     # ctypes' default
                 f.restype = restype
-    for name, cls in {**ABI.structs, **ABI_DQN.structs}.items():        # every struct whose size the library reports
-        if name + "_size" in {**ABI.functions, **ABI_DQN.functions} and getattr(L, name + "_size")() != ctypes.sizeof(cls):
+    for name, cls in {**ABI.structs, **ABI_DQN.structs, **ABI_C51.structs}.items():        # every struct whose size the library reports
+        if name + "_size" in {**ABI.functions, **ABI_DQN.functions, **ABI_C51.functions} and getattr(L, name + "_size")() != ctypes.sizeof(cls):
             raise RuntimeError(f"libocrl_hip.so: {name} is {getattr(L, name + '_size')()} bytes, this binding's {cls.__name__} {ctypes.sizeof(cls)}")
     if L.ocrl_abi_version() != CONSTANTS["OCRL_ABI_VERSION"]:
         raise RuntimeError(f"libocrl_hip.so ABI version mismatch: the library is {L.ocrl_abi_version()}, include/ocrl_hip.h {CONSTANTS['OCRL_ABI_VERSION']}")

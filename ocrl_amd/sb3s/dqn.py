@@ -7,7 +7,9 @@ acting is ``ocrl_dqn_act`` (the Q head's forward and the epsilon-greedy choice i
 (replay.py) samples and reads a batch in two launches, the loss is ``dqn_loss`` (``ocrl_dqn_td_fwd_bwd``: the TD target, the Huber loss
 and the head's gradient, fused) and the update ``ocrl_flat_clip_adam_l2`` on one flat parameter buffer.  Double Q-learning (van Hasselt et al. 2016),
 n-step returns and proportional prioritized replay (Schaul et al. 2016) are keyword arguments of ``DQN``, off by default
-(include/ocrl_hip_replay.h; ``sb3=dqn_per``).  Where this departs from stable-baselines3 and from those papers is listed in DESIGN.md §7."""
+(include/ocrl_hip_replay.h; ``sb3=dqn_per``).  ``n_atoms >= 2`` replaces the scalar head by the categorical one (C51, Bellemare et al.
+2017) and ``dueling`` adds its value stream (c51.py, include/ocrl_hip_c51.h; ``sb3=dqn_c51``); both are off by default.  Where this
+departs from stable-baselines3 and from those papers is listed in DESIGN.md §7."""
 import collections
 import copy
 import ctypes
@@ -19,12 +21,14 @@ from torch import nn
 
 from .. import _bridge, _lib
 from ..ocrs.flat_module import FlatParamModule
+from .c51 import CategoricalQNetwork, c51_loss
 from .custom_acnets import _n_actions
 from .on_policy import OnPolicyAlgorithm, _check_constant, _tensor
 from .replay import MAX_N_STEP, ReplayBuffer
 
 _WHO = "ocrl_amd.sb3s"
 _ACT = {"relu": (nn.ReLU, 1), "tanh": (nn.Tanh, 2)}
+MAX_ATOMS, MAX_LOGITS = 64, 256   # of the categorical head: atoms per action, n_actions * n_atoms (include/ocrl_hip_c51.h)
 ADAM_EPS = 1e-8                 # stable-baselines3's DQNPolicy builds torch's default Adam (the actor-critic policy: 1e-5)
 DQN_SCALARS = ("loss", "mean_q", "mean_target")
 
@@ -157,10 +161,11 @@ class DQNPolicy(nn.Module):
     """features_extractor -> QNetwork.  ``features_extractor`` is a module with ``features_dim`` (an OCRExtractor), or
     ``features_extractor_class(observation_space, **features_extractor_kwargs)``; without either the observations are flattened.
     ``exploration_rate`` is the epsilon ``act`` explores with (DQN sets it before every step); the target network is a second DQNPolicy
-    (DQN builds it)."""
+    (DQN builds it).  ``n_atoms >= 2`` makes the head a CategoricalQNetwork on the support [v_min, v_max] (``dueling``: with its value
+    stream); ``q_values`` is then the expectation of the distribution and ``act`` is ``ocrl_c51_act``."""
 
     def __init__(self, observation_space, action_space, lr_schedule=None, config=None, features_extractor=None, features_extractor_class=None,
-                 features_extractor_kwargs=None, net_arch=(64, 64), activation="relu", **kwargs):
+                 features_extractor_kwargs=None, net_arch=(64, 64), activation="relu", n_atoms=1, v_min=0.0, v_max=2.0, dueling=False, **kwargs):
         super().__init__()
         self._config = config
         self.observation_space, self.action_space = observation_space, action_space
@@ -173,7 +178,14 @@ class DQNPolicy(nn.Module):
         else:
             self.features_dim = int(features_extractor.features_dim)
         self.features_extractor = features_extractor
-        self.q_net = QNetwork(self.features_dim, n, net_arch, activation)
+        self.n_atoms, self.dueling = int(n_atoms), bool(dueling)
+        if self.n_atoms >= 2:
+            self.q_net = CategoricalQNetwork(self.features_dim, n, self.n_atoms, v_min, v_max, net_arch, activation, self.dueling)
+        elif self.n_atoms == 1 and not self.dueling:
+            self.q_net = QNetwork(self.features_dim, n, net_arch, activation)
+        else:
+            raise ValueError(f"{_WHO}.DQNPolicy: n_atoms is 1 (the scalar head) or >= 2 (the categorical head), and dueling is built for the "
+                             f"categorical head only (got n_atoms {n_atoms}, dueling {dueling})")
         self.exploration_rate = 0.0
 
     def extract_features(self, obs):
@@ -197,8 +209,7 @@ class DQNPolicy(nn.Module):
         ``deterministic``: 0) a uniform random action, otherwise the lowest index of the maximum Q.  Row r draws from (the set_sampling
         seed, row_offset + r); ``row_offset=None`` takes and advances the policy's own row counter.  ``uniforms`` [B, 2] in [0, 1)
         replaces the draw."""
-        dims, acts = self.q_net._layout()
-        x, ps = _bridge.inputs(_WHO, features.detach(), self.q_net._param_list())
+        x = _bridge.gpu_input(_WHO, features.detach())
         B, F = x.shape
         eps = 0.0 if deterministic else float(self.exploration_rate if epsilon is None else epsilon)
         if uniforms is not None:
@@ -210,6 +221,10 @@ class DQNPolicy(nn.Module):
         if row_offset is None:
             row_offset = self._sample_rows
             self._sample_rows += B
+        if self.n_atoms >= 2:
+            return (*self.q_net.act(x, self._sample_seed or 0, row_offset, eps, uniforms), None)
+        dims, acts = self.q_net._layout()
+        x, ps = _bridge.inputs(_WHO, x, self.q_net._param_list())
         d, _ = _desc(B, F, self.q_net.n_actions, dims, acts, x.device, keep=False)
         actions = torch.empty(B, device=x.device, dtype=torch.int64)
         q = torch.empty(B, self.q_net.n_actions, device=x.device)
@@ -265,13 +280,13 @@ class DQN:
     HYPER = ("learning_rate", "buffer_size", "learning_starts", "batch_size", "tau", "gamma", "train_freq", "gradient_steps",
              "target_update_interval", "exploration_fraction", "exploration_initial_eps", "exploration_final_eps", "max_grad_norm",
              "double_q", "n_step", "prioritized_replay", "prioritized_replay_alpha", "prioritized_replay_beta0", "prioritized_replay_beta_final",
-             "prioritized_replay_eps")
+             "prioritized_replay_eps", "n_atoms", "v_min", "v_max", "dueling")
 
     def __init__(self, policy, env, learning_rate=1e-4, buffer_size=1_000_000, learning_starts=50_000, batch_size=32, tau=1.0, gamma=0.99,
                  train_freq=4, gradient_steps=1, target_update_interval=10_000, exploration_fraction=0.1, exploration_initial_eps=1.0,
                  exploration_final_eps=0.05, max_grad_norm=10, seed=0, device="cuda", policy_kwargs=None, log_interval=100, double_q=False, n_step=1,
                  prioritized_replay=False, prioritized_replay_alpha=0.6, prioritized_replay_beta0=0.4, prioritized_replay_beta_final=1.0,
-                 prioritized_replay_eps=1e-6, **ignored_sb3_kwargs):
+                 prioritized_replay_eps=1e-6, n_atoms=1, v_min=0.0, v_max=2.0, dueling=False, **ignored_sb3_kwargs):
         who = self._who = f"{_WHO}.{self.ALGO}"
         self.learning_rate = _check_constant(who, "learning_rate", learning_rate)
         if int(gradient_steps) < 1:
@@ -294,6 +309,15 @@ class DQN:
             raise ValueError(f"{who}: prioritized_replay_eps >= 0 (got {prioritized_replay_eps})")
         self.prioritized_replay_alpha, self.prioritized_replay_eps = float(prioritized_replay_alpha), float(prioritized_replay_eps)
         self.prioritized_replay_beta0, self.prioritized_replay_beta_final = float(prioritized_replay_beta0), float(prioritized_replay_beta_final)
+        self.n_atoms, self.v_min, self.v_max, self.dueling = int(n_atoms), float(v_min), float(v_max), bool(dueling)
+        if self.n_atoms != 1 and not 2 <= self.n_atoms <= MAX_ATOMS:
+            raise ValueError(f"{who}: n_atoms is 1 (the scalar head) or lies in 2 .. {MAX_ATOMS} (got {n_atoms})")
+        if self.n_atoms > 1 and self.n_actions * self.n_atoms > MAX_LOGITS:
+            raise ValueError(f"{who}: n_actions * n_atoms <= {MAX_LOGITS} (got {self.n_actions} actions and n_atoms = {n_atoms})")
+        if self.n_atoms > 1 and not self.v_min < self.v_max:
+            raise ValueError(f"{who}: v_min < v_max (got {v_min}, {v_max})")
+        if self.dueling and self.n_atoms == 1:
+            raise ValueError(f"{who}: dueling is built for the categorical head only: set n_atoms >= 2 (got dueling=True with n_atoms=1)")
         self.buffer_size, self.learning_starts, self.batch_size = int(buffer_size), int(learning_starts), int(batch_size)
         self.tau, self.gamma = float(tau), float(gamma)
         self.train_freq, self.gradient_steps, self.target_update_interval = int(train_freq), int(gradient_steps), int(target_update_interval)
@@ -306,9 +330,16 @@ class DQN:
             self.device = torch.device("cuda", torch.cuda.current_device())
         if isinstance(policy, type):
             torch.manual_seed(self.seed)                              # the initialisation follows the seed, as set_random_seed does
-            policy = policy(env.observation_space, env.action_space, None, **(policy_kwargs or {}))
+            head = dict(n_atoms=self.n_atoms, v_min=self.v_min, v_max=self.v_max, dueling=self.dueling) if self.n_atoms > 1 else {}
+            policy = policy(env.observation_space, env.action_space, None, **dict(policy_kwargs or {}, **head))
         if not isinstance(policy, DQNPolicy):
             raise TypeError(f"{who}: policy must be an ocrl_amd.sb3s.DQNPolicy (or the class), got {type(policy).__name__}")
+        if (policy.n_atoms, policy.dueling) != (self.n_atoms, self.dueling):
+            raise ValueError(f"{who}: the policy's head has n_atoms = {policy.n_atoms}, dueling = {policy.dueling}; the arguments say n_atoms = "
+                             f"{self.n_atoms}, dueling = {self.dueling}")
+        if self.n_atoms > 1 and (policy.q_net.v_min, policy.q_net.v_max) != (self.v_min, self.v_max):
+            raise ValueError(f"{who}: the policy's head has v_min, v_max = {policy.q_net.v_min}, {policy.q_net.v_max}; the arguments say "
+                             f"{self.v_min}, {self.v_max}")
         for m in policy.modules():
             if isinstance(m, FlatParamModule):
                 raise NotImplementedError(f"{who}: a trainable {m.backend} encoder behind the extractor keeps its own flat buffers and optimiser "
@@ -493,9 +524,50 @@ class DQN:
         self._acc_n += 1
         return loss
 
+    def _train_step_c51(self):
+        """``train_step`` of the categorical head, with or without double_q, n_step > 1 and prioritized_replay: the batch
+        is drawn and read as ``_train_step_ext`` does, the target network gives the next observations' distribution, the online network
+        names the bootstrap action under double_q, ``c51_loss`` projects, and the rows' cross-entropies go back into the priority store
+        in place of |TD error|.  No host read either."""
+        buf = self.replay_buffer
+        idx, weights = None, None
+        if self.prioritized_replay or self.n_step > 1:
+            if len(buf) == 0:
+                raise RuntimeError(f"{self._who}.train_step: learning_starts = {self.learning_starts} leaves {buf.pos} vec steps in the replay ring "
+                                   f"at the first update, fewer than n_step = {self.n_step}: raise learning_starts to at least "
+                                   f"{self.n_step * self.n_envs} timesteps")
+            if self.prioritized_replay:
+                idx, weights = buf.sample_prioritized(self.batch_size, self.n_updates, self.beta())
+            else:
+                idx = buf.sample_indices(self.batch_size, self.n_updates, self.n_step)
+            batch = buf.gather(idx, self.n_step, self.gamma) if self.n_step > 1 else buf.gather(idx)
+        else:
+            batch = buf.sample(self.batch_size, self.n_updates)
+        self.policy.train()
+        with torch.no_grad():
+            next_features = self.target.extract_features(self._obs(batch.next_observations))
+            next_probs, next_q = self.target.q_net.distribution(next_features)
+            if self.double_q:
+                _, next_q = self.policy.q_net.distribution(self.policy.extract_features(self._obs(batch.next_observations)))
+        self.flat_g.zero_()
+        features = self.policy.extract_features(self._obs(batch.observations))
+        loss, m, row_loss = c51_loss(self.policy, features, next_probs, next_q, batch.actions, batch.rewards, batch.dones, self.gamma,
+                                     discounts=batch.discounts, weights=weights)
+        loss.backward()
+        self._adam_step()
+        if self.prioritized_replay:
+            buf.update_priorities(idx, row_loss, self.prioritized_replay_alpha, self.prioritized_replay_eps)
+            self.last_weights = weights
+        self.n_updates += 1
+        self._acc += torch.cat([torch.stack([m[k] for k in DQN_SCALARS]), self._norm])
+        self._acc_n += 1
+        return loss
+
     def train_step(self):
         """one gradient step: a batch from the replay buffer, the target network's Q of the next observations, ``dqn_loss``, the backward
         through the extractor, clip + Adam.  Nothing is read from the device: the scalars add up in ``_acc`` until a callback reads them."""
+        if self.n_atoms > 1:
+            return self._train_step_c51()
         if self.double_q or self.n_step > 1 or self.prioritized_replay:
             return self._train_step_ext()
         batch = self.replay_buffer.sample(self.batch_size, self.n_updates)
@@ -562,6 +634,10 @@ class DQN:
         wrote = ck.get("algo", "PPO")
         if wrote != self.ALGO:
             raise ValueError(f"{self._who}.load: {path} was written by {wrote}, not by {self.ALGO} (each algorithm loads its own checkpoints only)")
+        hyper = ck["hyper"]
+        if self.n_atoms > 1 and (float(hyper.get("v_min", self.v_min)), float(hyper.get("v_max", self.v_max))) != (self.v_min, self.v_max):
+            raise ValueError(f"{self._who}.load: the checkpoint's support v_min, v_max = {hyper['v_min']}, {hyper['v_max']} is not this "
+                             f"policy's {self.v_min}, {self.v_max}")
         opt = ck["optimizer"]
         if "m" not in opt or opt["m"].shape != self.flat_m.shape:
             n = opt["m"].numel() if "m" in opt else "no"
@@ -582,4 +658,4 @@ class DQN:
         return self
 
 
-__all__ = ["DQN", "DQNPolicy", "QNetwork", "dqn_loss", "exploration_schedule", "DQN_SCALARS"]
+__all__ = ["DQN", "DQNPolicy", "QNetwork", "CategoricalQNetwork", "dqn_loss", "c51_loss", "exploration_schedule", "DQN_SCALARS"]
