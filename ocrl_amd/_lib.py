@@ -1,4 +1,4 @@
-"""ctypes binding of libocrl_hip.so, derived from include/ocrl_hip.h, include/ocrl_hip_dqn.h, include/ocrl_hip_rollout.h, include/ocrl_hip_replay.h and include/ocrl_hip_c51.h (_abi.py reads them: the struct classes, the constants and every
+"""ctypes binding of libocrl_hip.so, derived from include/ocrl_hip.h, include/ocrl_hip_dqn.h, include/ocrl_hip_rollout.h, include/ocrl_hip_replay.h, include/ocrl_hip_c51.h and include/ocrl_hip_noisy.h (_abi.py reads them: the struct classes, the constants and every
 entry point's argtypes / restype come from the header's own declarations).  Fails loudly when the library is not built."""
 import ctypes
 import os
@@ -13,6 +13,7 @@ DQN_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "ocrl_hip_dqn.h")   
 ROLLOUT_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "ocrl_hip_rollout.h")      # the task datasets' later frames: a third one
 REPLAY_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "ocrl_hip_replay.h")      # DQN's replay extensions: a fourth one
 C51_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "ocrl_hip_c51.h")      # DQN's categorical head: a fifth one
+NOISY_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "ocrl_hip_noisy.h")      # DQN's noisy linear layers: a sixth one
 _lib = None
 
 if not os.path.exists(HEADER_PATH):
@@ -45,6 +46,12 @@ if not os.path.exists(C51_HEADER_PATH):
 with open(C51_HEADER_PATH) as _f:
     ABI_C51 = _abi.read(_f.read())                      # a struct of its own: the categorical head's descriptor
 C51Desc = ABI_C51.structs["ocrl_c51_desc"]
+if not os.path.exists(NOISY_HEADER_PATH):
+    raise RuntimeError(f"{NOISY_HEADER_PATH} is missing: ocrl_amd derives its binding of libocrl_hip.so from the header and runs from the source tree.")
+with open(NOISY_HEADER_PATH) as _f:
+    ABI_NOISY = _abi.read(_f.read())                    # a struct of its own: the layer table of the noisy layers
+NoisyDesc = ABI_NOISY.structs["ocrl_noisy_desc"]
+NOISY_MAX_LAYERS = len(NoisyDesc().out)
 
 
 def flat_segments(segs):
@@ -86,6 +93,17 @@ def c51_desc(B, F, A, Z, dims, acts, dueling=False):
     return d
 
 
+def noisy_desc(layers):
+    """NoisyDesc of a sequence of Linear layers: layers = (in, out) per layer"""
+    layers = list(layers)
+    if not 1 <= len(layers) <= NOISY_MAX_LAYERS:
+        raise ValueError(f"ocrl_amd: 1 .. {NOISY_MAX_LAYERS} noisy layers (got {len(layers)})")
+    d = NoisyDesc(n_layers=len(layers))
+    for l, (i, o) in enumerate(layers):
+        getattr(d, "in")[l], d.out[l] = int(i), int(o)
+    return d
+
+
 def gemm_desc(**kw):
     """GemmDesc with the defaults of GemmArgs (alpha = 1, one batch, no split, the dispatch rule) and the given fields"""
     d = GemmDesc(batch=1, batch_inner=1, splitk=1, alpha=1.0, x_scale=1.0, e_scale=1.0, force_sb=-1)
@@ -124,14 +142,14 @@ def lib():
     # when it was loaded before torch)
     import torch  # noqa: F401
     L = ctypes.CDLL(LIB_PATH)
-    for abi in (ABI, ABI_DQN, ABI_ROLLOUT, ABI_REPLAY, ABI_C51):
+    for abi in (ABI, ABI_DQN, ABI_ROLLOUT, ABI_REPLAY, ABI_C51, ABI_NOISY):
         for name, (restype, argtypes) in abi.functions.items():
             f = getattr(L, name)
             f.argtypes = argtypes
             if restype is not ctypes.c_int:     # ctypes' default
                 f.restype = restype
-    for name, cls in {**ABI.structs, **ABI_DQN.structs, **ABI_C51.structs}.items():        # every struct whose size the library reports
-        if name + "_size" in {**ABI.functions, **ABI_DQN.functions, **ABI_C51.functions} and getattr(L, name + "_size")() != ctypes.sizeof(cls):
+    for name, cls in {**ABI.structs, **ABI_DQN.structs, **ABI_C51.structs, **ABI_NOISY.structs}.items():        # every struct whose size the library reports
+        if name + "_size" in {**ABI.functions, **ABI_DQN.functions, **ABI_C51.functions, **ABI_NOISY.functions} and getattr(L, name + "_size")() != ctypes.sizeof(cls):
             raise RuntimeError(f"libocrl_hip.so: {name} is {getattr(L, name + '_size')()} bytes, this binding's {cls.__name__} {ctypes.sizeof(cls)}")
     if L.ocrl_abi_version() != CONSTANTS["OCRL_ABI_VERSION"]:
         raise RuntimeError(f"libocrl_hip.so ABI version mismatch: the library is {L.ocrl_abi_version()}, include/ocrl_hip.h {CONSTANTS['OCRL_ABI_VERSION']}")

@@ -11,6 +11,7 @@ import torch
 from torch import nn
 
 from .. import _bridge, _lib
+from .noisy import effective_params, linear
 
 _WHO = "ocrl_amd.sb3s"
 
@@ -91,9 +92,12 @@ class CategoricalQNetwork(nn.Module):
     a * n_atoms + j; with ``dueling`` a second Linear(last, n_atoms), ``value_net``, on the same latent:
     logit[a, j] = V[j] + Adv[a, j] - mean_a' Adv[a', j].  The parameters sit in ``q_net``, an nn.Sequential with QNetwork's keys
     (``q_net.{2i}.weight|bias``), and in ``value_net``; neither container's ``forward`` is called.  ``n_actions``, ``n_atoms`` and the
-    support ``atoms`` [n_atoms] = v_min + j (v_max - v_min) / (n_atoms - 1) are attributes.  No CPU fallback: a CPU tensor raises."""
+    support ``atoms`` [n_atoms] = v_min + j (v_max - v_min) / (n_atoms - 1) are attributes.  ``noisy``: every Linear, the advantage and
+    the value layer included, is a NoisyLinear, as QNetwork's.  No CPU fallback: a CPU tensor raises."""
+    _noise = None
 
-    def __init__(self, features_dim, n_actions, n_atoms, v_min, v_max, net_arch=(64, 64), activation="relu", dueling=False):
+    def __init__(self, features_dim, n_actions, n_atoms, v_min, v_max, net_arch=(64, 64), activation="relu", dueling=False, noisy=False,
+                 noisy_sigma0=0.5):
         super().__init__()
         from .dqn import _ACT                                 # dqn.py imports this module: its names are taken when they are used
         if activation not in _ACT:
@@ -103,13 +107,14 @@ class CategoricalQNetwork(nn.Module):
         if self.n_atoms < 2 or not self.v_min < self.v_max:
             raise ValueError(f"{_WHO}.CategoricalQNetwork: n_atoms >= 2 and v_min < v_max (got {n_atoms}, {v_min}, {v_max})")
         self._dims, self._act = tuple(int(w) for w in net_arch), _ACT[activation][1]
+        self.noisy, self.noisy_sigma0 = bool(noisy), float(noisy_sigma0)
         layers, in_dim = [], int(features_dim)
         for w in self._dims:
-            layers += [nn.Linear(in_dim, w), _ACT[activation][0]()]
+            layers += [linear(in_dim, w, self.noisy, self.noisy_sigma0), _ACT[activation][0]()]
             in_dim = w
-        self.q_net = nn.Sequential(*layers, nn.Linear(in_dim, self.n_actions * self.n_atoms))
+        self.q_net = nn.Sequential(*layers, linear(in_dim, self.n_actions * self.n_atoms, self.noisy, self.noisy_sigma0))
         if self.dueling:
-            self.value_net = nn.Linear(in_dim, self.n_atoms)
+            self.value_net = linear(in_dim, self.n_atoms, self.noisy, self.noisy_sigma0)
         self.register_buffer("atoms", torch.linspace(self.v_min, self.v_max, self.n_atoms), persistent=False)
 
     def _layout(self):
@@ -121,8 +126,9 @@ class CategoricalQNetwork(nn.Module):
         return (self.n_actions, self.n_atoms, *self._layout(), self.dueling, self.v_min, self.v_max)
 
     def _param_list(self):
-        ps = [p for m in self.q_net if isinstance(m, nn.Linear) for p in (m.weight, m.bias)]
-        return ps + ([self.value_net.weight, self.value_net.bias] if self.dueling else [])
+        """(weight, bias) per Linear as the kernels take them; with ``noisy`` the effective tensors of the current draw"""
+        mods = [m for m in self.q_net if isinstance(m, nn.Linear)] + ([self.value_net] if self.dueling else [])
+        return effective_params(mods, self._noise if self.noisy else None)
 
     def logits(self, features):
         """[B, n_actions, n_atoms], attached to autograd"""

@@ -8,8 +8,10 @@ acting is ``ocrl_dqn_act`` (the Q head's forward and the epsilon-greedy choice i
 and the head's gradient, fused) and the update ``ocrl_flat_clip_adam_l2`` on one flat parameter buffer.  Double Q-learning (van Hasselt et al. 2016),
 n-step returns and proportional prioritized replay (Schaul et al. 2016) are keyword arguments of ``DQN``, off by default
 (include/ocrl_hip_replay.h; ``sb3=dqn_per``).  ``n_atoms >= 2`` replaces the scalar head by the categorical one (C51, Bellemare et al.
-2017) and ``dueling`` adds its value stream (c51.py, include/ocrl_hip_c51.h; ``sb3=dqn_c51``); both are off by default.  Where this
-departs from stable-baselines3 and from those papers is listed in DESIGN.md §7."""
+2017) and ``dueling`` adds its value stream (c51.py, include/ocrl_hip_c51.h; ``sb3=dqn_c51``); both are off by default.  ``noisy`` makes
+every Linear of the head a noisy layer (Fortunato et al. 2018) whose learned parameter noise replaces the epsilon-greedy coin (noisy.py,
+include/ocrl_hip_noisy.h; ``sb3=rainbow``, the six components of Hessel et al. 2018 together); off by default.  Where this departs from
+stable-baselines3 and from those papers is listed in DESIGN.md §7."""
 import collections
 import copy
 import ctypes
@@ -23,6 +25,7 @@ from .. import _bridge, _lib
 from ..ocrs.flat_module import FlatParamModule
 from .c51 import CategoricalQNetwork, c51_loss
 from .custom_acnets import _n_actions
+from .noisy import effective_params, linear
 from .on_policy import OnPolicyAlgorithm, _check_constant, _tensor
 from .replay import MAX_N_STEP, ReplayBuffer
 
@@ -133,25 +136,30 @@ class _DqnExtFn(torch.autograd.Function):
 class QNetwork(nn.Module):
     """features [B, F] -> len(net_arch) x [Linear, activation] -> Linear(last, n_actions).  The parameters sit in ``q_net``, an
     nn.Sequential whose ``state_dict()`` keys are ``q_net.{2i}.weight|bias``; the container's ``forward`` is never called: the arithmetic
-    is ``ocrl_qnet_fwd`` / ``ocrl_qnet_bwd`` under a ``torch.autograd.Function``.  No CPU fallback: a CPU tensor raises."""
+    is ``ocrl_qnet_fwd`` / ``ocrl_qnet_bwd`` under a ``torch.autograd.Function``.  ``noisy``: every Linear is a NoisyLinear (sigmas start at
+    ``noisy_sigma0 / sqrt(in)``) and the kernels receive the effective parameters of the draw ``_noise`` = (seed, draw) names
+    (DQNPolicy.set_noise; None: the means).  No CPU fallback: a CPU tensor raises."""
+    _noise = None
 
-    def __init__(self, features_dim, n_actions, net_arch=(64, 64), activation="relu"):
+    def __init__(self, features_dim, n_actions, net_arch=(64, 64), activation="relu", noisy=False, noisy_sigma0=0.5):
         super().__init__()
         if activation not in _ACT:
             raise ValueError(f"{_WHO}.QNetwork: activation {activation!r} is not one of {', '.join(_ACT)}")
         self.n_actions, self._dims, self._act = int(n_actions), tuple(int(w) for w in net_arch), _ACT[activation][1]
+        self.noisy, self.noisy_sigma0 = bool(noisy), float(noisy_sigma0)
         layers, in_dim = [], int(features_dim)
         for w in self._dims:
-            layers += [nn.Linear(in_dim, w), _ACT[activation][0]()]
+            layers += [linear(in_dim, w, self.noisy, self.noisy_sigma0), _ACT[activation][0]()]
             in_dim = w
-        self.q_net = nn.Sequential(*layers, nn.Linear(in_dim, self.n_actions))
+        self.q_net = nn.Sequential(*layers, linear(in_dim, self.n_actions, self.noisy, self.noisy_sigma0))
 
     def _layout(self):
         """(hidden widths, activation codes), as the C ABI takes them"""
         return self._dims, (self._act,) * len(self._dims)
 
     def _param_list(self):
-        return [p for m in self.q_net if isinstance(m, nn.Linear) for p in (m.weight, m.bias)]
+        """(weight, bias) per Linear as the kernels take them; with ``noisy`` the effective tensors of the current draw"""
+        return effective_params([m for m in self.q_net if isinstance(m, nn.Linear)], self._noise if self.noisy else None)
 
     def forward(self, features):
         return _QnetFn.apply(features, *self._layout(), self.n_actions, *self._param_list())
@@ -162,10 +170,13 @@ class DQNPolicy(nn.Module):
     ``features_extractor_class(observation_space, **features_extractor_kwargs)``; without either the observations are flattened.
     ``exploration_rate`` is the epsilon ``act`` explores with (DQN sets it before every step); the target network is a second DQNPolicy
     (DQN builds it).  ``n_atoms >= 2`` makes the head a CategoricalQNetwork on the support [v_min, v_max] (``dueling``: with its value
-    stream); ``q_values`` is then the expectation of the distribution and ``act`` is ``ocrl_c51_act``."""
+    stream); ``q_values`` is then the expectation of the distribution and ``act`` is ``ocrl_c51_act``.  ``noisy`` builds the head of noisy
+    layers (``noisy_sigma0``: the sigmas' start); which draw of the noise the head uses is set explicitly with ``set_noise`` and does not
+    follow ``train()`` / ``eval()``."""
 
     def __init__(self, observation_space, action_space, lr_schedule=None, config=None, features_extractor=None, features_extractor_class=None,
-                 features_extractor_kwargs=None, net_arch=(64, 64), activation="relu", n_atoms=1, v_min=0.0, v_max=2.0, dueling=False, **kwargs):
+                 features_extractor_kwargs=None, net_arch=(64, 64), activation="relu", n_atoms=1, v_min=0.0, v_max=2.0, dueling=False, noisy=False,
+                 noisy_sigma0=0.5, **kwargs):
         super().__init__()
         self._config = config
         self.observation_space, self.action_space = observation_space, action_space
@@ -179,10 +190,14 @@ class DQNPolicy(nn.Module):
             self.features_dim = int(features_extractor.features_dim)
         self.features_extractor = features_extractor
         self.n_atoms, self.dueling = int(n_atoms), bool(dueling)
+        self.noisy, self.noisy_sigma0 = bool(noisy), float(noisy_sigma0)
+        if not self.noisy_sigma0 >= 0.0:
+            raise ValueError(f"{_WHO}.DQNPolicy: noisy_sigma0 >= 0 (got {noisy_sigma0})")
+        noise = dict(noisy=True, noisy_sigma0=self.noisy_sigma0) if self.noisy else {}
         if self.n_atoms >= 2:
-            self.q_net = CategoricalQNetwork(self.features_dim, n, self.n_atoms, v_min, v_max, net_arch, activation, self.dueling)
+            self.q_net = CategoricalQNetwork(self.features_dim, n, self.n_atoms, v_min, v_max, net_arch, activation, self.dueling, **noise)
         elif self.n_atoms == 1 and not self.dueling:
-            self.q_net = QNetwork(self.features_dim, n, net_arch, activation)
+            self.q_net = QNetwork(self.features_dim, n, net_arch, activation, **noise)
         else:
             raise ValueError(f"{_WHO}.DQNPolicy: n_atoms is 1 (the scalar head) or >= 2 (the categorical head), and dueling is built for the "
                              f"categorical head only (got n_atoms {n_atoms}, dueling {dueling})")
@@ -203,12 +218,28 @@ class DQNPolicy(nn.Module):
         self._sample_seed = None if seed is None else int(seed) & (2 ** 64 - 1)
         self._sample_rows = 0
 
+    def set_noise(self, draw):
+        """choose the noisy head's parameters for the calls that follow: the integer ``draw`` names that draw of the policy's noise
+        stream (seeded by ``set_sampling``), ``None`` the mean weights (nothing is launched for them).  Without ``noisy`` there is
+        nothing to choose and the call changes nothing."""
+        if not self.noisy:
+            return
+        if draw is not None and self._sample_seed is None:
+            raise RuntimeError(f"{_WHO}.DQNPolicy.set_noise: no noise stream: call policy.set_sampling(seed) first")
+        self.q_net._noise = None if draw is None else (self._sample_seed, int(draw))
+
     def act(self, features, row_offset=None, deterministic: bool = False, uniforms=None, epsilon=None):
         """(actions int64 [B], q [B, n], None) of a feature batch in one kernel launch, detached (the collection step; the rule is
         include/ocrl_hip_dqn.h's).  Each row flips its own coin: with probability ``epsilon`` (``None``: ``exploration_rate``;
         ``deterministic``: 0) a uniform random action, otherwise the lowest index of the maximum Q.  Row r draws from (the set_sampling
         seed, row_offset + r); ``row_offset=None`` takes and advances the policy's own row counter.  ``uniforms`` [B, 2] in [0, 1)
-        replaces the draw."""
+        replaces the draw.  A noisy head acts on the draw ``set_noise`` chose, and on the mean weights when ``deterministic``."""
+        if deterministic and self.noisy and self.q_net._noise is not None:
+            chosen, self.q_net._noise = self.q_net._noise, None
+            try:
+                return self.act(features, row_offset, True, uniforms, epsilon)
+            finally:
+                self.q_net._noise = chosen
         x = _bridge.gpu_input(_WHO, features.detach())
         B, F = x.shape
         eps = 0.0 if deterministic else float(self.exploration_rate if epsilon is None else epsilon)
@@ -275,18 +306,25 @@ def _layout(params):
 class DQN:
     """Deep Q-learning with a target network and a replay buffer for Discrete actions (stable-baselines3's DQN on a VecEnv).  ``env`` as
     OnPolicyAlgorithm takes it; ``policy`` is a DQNPolicy or its class.  An iteration is ``train_freq`` vec steps, then
-    ``gradient_steps`` updates once ``num_timesteps > learning_starts``.  Every environment flips its own exploration coin."""
+    ``gradient_steps`` updates once ``num_timesteps > learning_starts``.  Every environment flips its own exploration coin.
+
+    ``noisy=True``: the head is built of noisy layers and epsilon is 0 at every step, warm-up included; the three
+    ``exploration_*`` arguments are accepted and unused.  ``noise_draws`` counts the draws handed out: one per ``collect_step``, shared by
+    all its rows, and two per ``train_step``, the first for the online network (its forward on the observations and, under ``double_q``,
+    its evaluation of the next observations share it), the second for the target network.  The online network's noise stream is seeded
+    with ``seed``, the target network's with ``seed + 1``."""
     ALGO = "DQN"
     HYPER = ("learning_rate", "buffer_size", "learning_starts", "batch_size", "tau", "gamma", "train_freq", "gradient_steps",
              "target_update_interval", "exploration_fraction", "exploration_initial_eps", "exploration_final_eps", "max_grad_norm",
              "double_q", "n_step", "prioritized_replay", "prioritized_replay_alpha", "prioritized_replay_beta0", "prioritized_replay_beta_final",
-             "prioritized_replay_eps", "n_atoms", "v_min", "v_max", "dueling")
+             "prioritized_replay_eps", "n_atoms", "v_min", "v_max", "dueling", "noisy", "noisy_sigma0")
 
     def __init__(self, policy, env, learning_rate=1e-4, buffer_size=1_000_000, learning_starts=50_000, batch_size=32, tau=1.0, gamma=0.99,
                  train_freq=4, gradient_steps=1, target_update_interval=10_000, exploration_fraction=0.1, exploration_initial_eps=1.0,
                  exploration_final_eps=0.05, max_grad_norm=10, seed=0, device="cuda", policy_kwargs=None, log_interval=100, double_q=False, n_step=1,
                  prioritized_replay=False, prioritized_replay_alpha=0.6, prioritized_replay_beta0=0.4, prioritized_replay_beta_final=1.0,
-                 prioritized_replay_eps=1e-6, n_atoms=1, v_min=0.0, v_max=2.0, dueling=False, **ignored_sb3_kwargs):
+                 prioritized_replay_eps=1e-6, n_atoms=1, v_min=0.0, v_max=2.0, dueling=False, noisy=False, noisy_sigma0=0.5,
+                 **ignored_sb3_kwargs):
         who = self._who = f"{_WHO}.{self.ALGO}"
         self.learning_rate = _check_constant(who, "learning_rate", learning_rate)
         if int(gradient_steps) < 1:
@@ -318,6 +356,9 @@ class DQN:
             raise ValueError(f"{who}: v_min < v_max (got {v_min}, {v_max})")
         if self.dueling and self.n_atoms == 1:
             raise ValueError(f"{who}: dueling is built for the categorical head only: set n_atoms >= 2 (got dueling=True with n_atoms=1)")
+        self.noisy, self.noisy_sigma0 = bool(noisy), float(noisy_sigma0)
+        if not self.noisy_sigma0 >= 0.0:
+            raise ValueError(f"{who}: noisy_sigma0 >= 0 (got {noisy_sigma0})")
         self.buffer_size, self.learning_starts, self.batch_size = int(buffer_size), int(learning_starts), int(batch_size)
         self.tau, self.gamma = float(tau), float(gamma)
         self.train_freq, self.gradient_steps, self.target_update_interval = int(train_freq), int(gradient_steps), int(target_update_interval)
@@ -331,6 +372,8 @@ class DQN:
         if isinstance(policy, type):
             torch.manual_seed(self.seed)                              # the initialisation follows the seed, as set_random_seed does
             head = dict(n_atoms=self.n_atoms, v_min=self.v_min, v_max=self.v_max, dueling=self.dueling) if self.n_atoms > 1 else {}
+            if self.noisy:
+                head.update(noisy=True, noisy_sigma0=self.noisy_sigma0)
             policy = policy(env.observation_space, env.action_space, None, **dict(policy_kwargs or {}, **head))
         if not isinstance(policy, DQNPolicy):
             raise TypeError(f"{who}: policy must be an ocrl_amd.sb3s.DQNPolicy (or the class), got {type(policy).__name__}")
@@ -340,14 +383,19 @@ class DQN:
         if self.n_atoms > 1 and (policy.q_net.v_min, policy.q_net.v_max) != (self.v_min, self.v_max):
             raise ValueError(f"{who}: the policy's head has v_min, v_max = {policy.q_net.v_min}, {policy.q_net.v_max}; the arguments say "
                              f"{self.v_min}, {self.v_max}")
+        if policy.noisy != self.noisy:
+            raise ValueError(f"{who}: the policy's head has noisy = {policy.noisy}; the arguments say noisy = {self.noisy}")
         for m in policy.modules():
             if isinstance(m, FlatParamModule):
                 raise NotImplementedError(f"{who}: a trainable {m.backend} encoder behind the extractor keeps its own flat buffers and optimiser "
                                           f"step; stepping it from {self.ALGO} is not built: give the extractor a pre-trained, frozen encoder")
         self.policy = policy.to(self.device)
         self.policy.set_sampling(self.seed)
-        self.policy.exploration_rate = self.exploration_initial_eps
+        self.policy.exploration_rate = 0.0 if self.noisy else self.exploration_initial_eps
         self._flatten_parameters()
+        self.noise_draws = 0                                          # noisy: the draws handed out so far
+        if self.noisy:
+            self.target.set_sampling(self.seed + 1)                   # the target network's noise stream is its own
         self.num_timesteps, self.iteration, self.n_calls, self.n_updates, self.n_target_updates = 0, 0, 0, 0, 0
         self._total_timesteps = 0
         self._obs_shape = tuple(env.observation_space.shape)
@@ -431,6 +479,9 @@ class DQN:
     # ---- collection
     def epsilon(self):
         """the exploration rate of the next step: 1 while the buffer warms up, then the schedule of num_timesteps / total_timesteps"""
+        if self.noisy:                                                # the noise explores: no coin, the warm-up included
+            self.policy.exploration_rate = 0.0
+            return 0.0
         frac = self.num_timesteps / max(self._total_timesteps, 1)
         rate = exploration_schedule(frac, self.exploration_initial_eps, self.exploration_final_eps, self.exploration_fraction)
         self.policy.exploration_rate = rate
@@ -450,6 +501,9 @@ class DQN:
         self.policy.eval()
         with torch.no_grad():
             eps = self.epsilon()
+            if self.noisy:                                            # one fresh draw, shared by all rows of the step
+                self.policy.set_noise(self.noise_draws)
+                self.noise_draws += 1
             actions, _, _ = self.policy.act(self.policy.extract_features(self._obs(self._last_obs)), epsilon=eps)
             if on_device:
                 new_obs, rewards, dones, extras = self.env.step_device(actions)
@@ -490,6 +544,13 @@ class DQN:
         frac = min(self.num_timesteps / max(self._total_timesteps, 1), 1.0)
         return self.prioritized_replay_beta0 + frac * (self.prioritized_replay_beta_final - self.prioritized_replay_beta0)
 
+    def _draw_train_noise(self):
+        """noisy: the two fresh draws of a gradient step, one for every use of the online network in it, one for the target network"""
+        if self.noisy:
+            self.policy.set_noise(self.noise_draws)
+            self.target.set_noise(self.noise_draws + 1)
+            self.noise_draws += 2
+
     def _train_step_ext(self):
         """``train_step`` with any of double_q, n_step > 1 and prioritized_replay: the batch is drawn in proportion to the
         priorities or among the whole n-step windows, read with its n-step returns, the online network names the bootstrap action, the
@@ -506,6 +567,7 @@ class DQN:
             idx = buf.sample_indices(self.batch_size, self.n_updates, self.n_step)
         batch = buf.gather(idx, self.n_step, self.gamma) if self.n_step > 1 else buf.gather(idx)
         self.policy.train()
+        self._draw_train_noise()
         next_obs = self._obs(batch.next_observations)
         with torch.no_grad():
             next_q = self.target.q_values(next_obs)
@@ -544,6 +606,7 @@ class DQN:
         else:
             batch = buf.sample(self.batch_size, self.n_updates)
         self.policy.train()
+        self._draw_train_noise()
         with torch.no_grad():
             next_features = self.target.extract_features(self._obs(batch.next_observations))
             next_probs, next_q = self.target.q_net.distribution(next_features)
@@ -571,6 +634,7 @@ class DQN:
         if self.double_q or self.n_step > 1 or self.prioritized_replay:
             return self._train_step_ext()
         batch = self.replay_buffer.sample(self.batch_size, self.n_updates)
+        self._draw_train_noise()
         with torch.no_grad():
             next_q = self.target.q_values(self._obs(batch.next_observations))
         self.policy.train()
@@ -621,7 +685,7 @@ class DQN:
     # are not saved: a resumed run collects again before it updates (learning_starts counts from 0 only if the caller sets it so)
     def save(self, path):
         hyper = {k: getattr(self, k) for k in self.HYPER + ("seed", "num_timesteps", "iteration", "n_calls", "n_updates", "n_target_updates",
-                                                            "_total_timesteps")}
+                                                            "_total_timesteps", "noise_draws")}
         opt = {"m": self.flat_m, "v": self.flat_v, "step": self.adam_step, "sampling_rows": self.policy._sample_rows}
         torch.save({"algo": self.ALGO, "policy": self.policy.state_dict(), "target": self.target.state_dict(), "optimizer": opt, "hyper": hyper,
                     "exploration_rate": float(self.policy.exploration_rate)}, path)
@@ -649,6 +713,11 @@ class DQN:
         self.adam_step = int(opt["step"])
         self.policy._sample_rows = int(opt["sampling_rows"])
         self.policy._sample_seed = int(ck["hyper"]["seed"]) & (2 ** 64 - 1)
+        if bool(hyper.get("noisy", False)) != self.noisy:
+            raise ValueError(f"{self._who}.load: the checkpoint was written with noisy = {bool(hyper.get('noisy', False))}, this instance has "
+                             f"noisy = {self.noisy}")
+        if self.noisy:
+            self.target._sample_seed = (int(ck["hyper"]["seed"]) + 1) & (2 ** 64 - 1)
         for k, v in ck["hyper"].items():
             setattr(self, k, v)
         self.policy.exploration_rate = float(ck["exploration_rate"])
