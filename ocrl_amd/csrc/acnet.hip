@@ -140,14 +140,7 @@ __device__ void ppo_rows(const AcnetArgs& p, long long row0, int rows, bool firs
         for (int j = 0; j < 6; ++j) rs[r][j] = t[j];
     }
     __syncthreads();
-    if (threadIdx.x < 5) {
-        float s = 0.f;
-#pragma unroll
-        for (int q = 0; q < TR; ++q) s += rs[q][threadIdx.x];
-        float* d = p.scal_slab + (long long)blockIdx.x * 8 + threadIdx.x;
-        *d = first ? s : *d + s;
-    }
-    __syncthreads();
+    tile_scalars<5>(rs, first, p.scal_slab);
 }
 
 __global__ __launch_bounds__(256) void acnet_ppo_kernel(AcnetArgs p) {
@@ -205,14 +198,7 @@ __device__ void a2c_rows(const AcnetArgs& p, long long row0, int rows, bool firs
         for (int j = 0; j < 3; ++j) rs[r][j] = t[j];
     }
     __syncthreads();
-    if (threadIdx.x < 3) {
-        float s = 0.f;
-#pragma unroll
-        for (int q = 0; q < TR; ++q) s += rs[q][threadIdx.x];
-        float* d = p.scal_slab + (long long)blockIdx.x * 8 + threadIdx.x;
-        *d = first ? s : *d + s;
-    }
-    __syncthreads();
+    tile_scalars<3>(rs, first, p.scal_slab);
 }
 
 __global__ __launch_bounds__(256) void acnet_a2c_kernel(AcnetArgs p) {

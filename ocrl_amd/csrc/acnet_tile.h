@@ -1,4 +1,4 @@
-// The row-tile steps of the small-Linear-chain heads, shared by acnet.hip (actor-critic) and dqn.hip (the Q head): one workgroup (4 waves)
+// The row-tile steps of the small-Linear-chain heads, shared by acnet.hip (actor-critic), dqn.hip (the Q head), c51.hip and classifier.hip: one workgroup (4 waves)
 // owns a tile of 16 batch rows and walks a chain of Linear layers with the activations in LDS; see acnet.hip for the order of every sum.
 // Device code in an unnamed namespace: each translation unit that includes this compiles its own copy into its kernels.
 #pragma once
@@ -109,6 +109,21 @@ __device__ void fwd_tile(const AcnetArgs& p, long long row0, int rows, float* bu
         lin_fwd_tile(lv, p.wv, p.bv, Kv, 1, 0, vl, 1, p.values ? p.values + row0 : nullptr, nullptr, rows);
         __syncthreads();
     }
+}
+
+// The fold of a tile's scalar terms: the row threads left term j of row r in rs[r][j] and a barrier has passed.  Thread j < N adds the 16
+// rows' terms in row order into the workgroup's row of scal_slab [S][8]: written when `first`, else added to (the tiles of a slab in tile
+// order).  Ends on a barrier.
+template <int N, int M>
+__device__ void tile_scalars(const float (*rs)[M], bool first, float* scal_slab) {
+    if (threadIdx.x < N) {
+        float sum = 0.f;
+#pragma unroll
+        for (int q = 0; q < TR; ++q) sum += rs[q][threadIdx.x];
+        float* d = scal_slab + (long long)blockIdx.x * 8 + threadIdx.x;
+        *d = first ? sum : *d + sum;
+    }
+    __syncthreads();
 }
 
 // Backward of y = act(x W^T + b) on a tile.  dy [16][ldd] (LDS) holds dL/dy and is turned into dL/d(pre-activation) in place (rows past

@@ -2,7 +2,7 @@
 // specification).  The chain runs on the actor-critic head's per-layer tile steps (acnet_tile.h) as the policy trunk of an AcnetArgs;
 // the advantage Linear [A * Z, last] sits in wa / ba and the dueling value Linear [Z, last] in wv / bv (null: no dueling), each with its
 // slab offsets; AcnetArgs::A is the number of actions.  The fold of the partial dw is acnet_reduce_launch, the fold of the three scalars
-// dqn_scalars_launch.
+// head_scalars_launch.
 #pragma once
 #include "../../include/ocrl_hip_c51.h"
 #include "acnet.h"

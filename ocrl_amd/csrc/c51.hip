@@ -11,7 +11,7 @@
 //              written over the logits in place, and the backward, per row tile in one kernel.  Once the heads have run the two chain
 //              tiles are free (the backward reads the saved layer outputs from the workspace): they hold the bootstrap action's
 //              next_probs, beta and m.  Partial dw go to the workgroup's slab, the three scalar sums to its row of scal_slab
-// The fold of the slabs is acnet_reduce (slab order), the fold of the scalars dqn_scalars (slab order).
+// The fold of the slabs is acnet_reduce (slab order), the fold of the scalars head_scalars (slab order).
 // Order of every sum: acnet.hip's for the layers and the slabs; the sums over actions and atoms are serial in ascending index; a tile's
 // scalar terms are added in row order, the tiles of a slab in tile order.  The expectation accumulates with fused multiply-adds
 // (z_j = fma(j, dz, v_min), q = fma(p_j, z_j, q)) so that every kernel here forms the same q.  No atomics.
@@ -283,14 +283,7 @@ __device__ void c51_td_rows(const AcnetArgs& p, const C51Args& c, const C51TdArg
         }
         lg[r * LD + n] = v;
     }
-    if (tid < 3) {
-        float sum = 0.f;
-#pragma unroll
-        for (int q = 0; q < TR; ++q) sum += t.rs[q][tid];
-        float* d = p.scal_slab + (long long)blockIdx.x * 8 + tid;
-        *d = first ? sum : *d + sum;
-    }
-    __syncthreads();
+    tile_scalars<3>(t.rs, first, p.scal_slab);
 }
 
 __global__ __launch_bounds__(256) void c51_td_kernel(AcnetArgs p, C51Args c, C51TdArgs s) {

@@ -4,8 +4,8 @@
 //   clf_ce            forward, soft-max cross-entropy, accuracy, dz and the backward per row tile in one kernel; z and the layer cotangents
 //                     never leave LDS.  Partial dw go to the workgroup's slab, the three scalar sums to its row of scal_slab.  Evaluating,
 //                     the tile stops after the loss
-//   clf_scalars       mean loss, accuracy and the count of valid rows from the slabs' partial sums, in slab order (dw is folded by
-//                     acnet_reduce)
+// Mean loss, accuracy and the count of valid rows come from the slabs' partial sums in slab order (dqn.hip's head_scalars); dw is folded
+// by acnet_reduce.
 // Order of every sum: acnet.hip's for the layers and the slabs; a row's exponentials are added in class order, a tile's scalar terms in
 // row order, the tiles of a slab in tile order, the slabs in slab order.  No atomics.
 #include "acnet_tile.h"
@@ -45,14 +45,7 @@ __device__ void ce_rows(const AcnetArgs& p, const ClfCeArgs& s, long long row0, 
         for (int j = 0; j < 3; ++j) rs[r][j] = t[j];
     }
     __syncthreads();
-    if (threadIdx.x < 3) {
-        float sum = 0.f;
-#pragma unroll
-        for (int q = 0; q < TR; ++q) sum += rs[q][threadIdx.x];
-        float* d = p.scal_slab + (long long)blockIdx.x * 8 + threadIdx.x;
-        *d = first ? sum : *d + sum;
-    }
-    __syncthreads();
+    tile_scalars<3>(rs, first, p.scal_slab);
 }
 
 __global__ __launch_bounds__(256) void clf_ce_kernel(AcnetArgs p, ClfCeArgs s) {
@@ -72,24 +65,10 @@ __global__ __launch_bounds__(256) void clf_ce_kernel(AcnetArgs p, ClfCeArgs s) {
     }
 }
 
-// out = {sum l / B, sum hit / B, the count of valid rows}
-__global__ __launch_bounds__(64) void clf_scalars_kernel(const float* __restrict__ scal_slab, int S, int B, float* __restrict__ out) {
-    const int j = threadIdx.x;
-    if (j >= 3) return;
-    float s = 0.f;
-    for (int k = 0; k < S; ++k) s += scal_slab[k * 8 + j];
-    out[j] = j < 2 ? s / (float)B : s;
-}
-
 }  // namespace
 
 int clf_ce_launch(const AcnetArgs& a, const ClfCeArgs& s, hipStream_t st) {
     hipLaunchKernelGGL(clf_ce_kernel, dim3(a.S), dim3(256), 0, st, a, s);
     OCRL_CHECK_LAUNCH("clf_ce");
-    return 0;
-}
-int clf_scalars_launch(const float* scal_slab, int S, int B, float* out, hipStream_t st) {
-    hipLaunchKernelGGL(clf_scalars_kernel, dim3(1), dim3(64), 0, st, scal_slab, S, B, out);
-    OCRL_CHECK_LAUNCH("clf_scalars");
     return 0;
 }

@@ -16,13 +16,18 @@ struct DqnActArgs {
     long long* actions;                               // [B]
 };
 
-// the TD target's inputs, each [B] but next_q [B, A]
+// the TD target's inputs, each [B] but next_q and next_q_online [B, A]; the optional ones (null: not given) are read by the `ext` kernel
+// alone
 struct DqnTdArgs {
     const float* next_q;
     const long long* actions;
     const float* rewards;
     const unsigned char* dones;
     float gamma;
+    const float* next_q_online;                       // optional: where the maximum is looked for (double Q-learning)
+    const float* discounts;                           // optional: replaces gamma
+    const float* weights;                             // optional: scales a row's loss and gradient
+    float* abs_td;                                    // optional, out
 };
 
 // the ring [N, E, ...] and one batch read of it
@@ -40,24 +45,10 @@ struct ReplayGatherArgs {
     unsigned char* dones_out;
 };
 
-// the Q head's host side (dqn_unit.cpp), shared by the entry points of ocrl_hip_dqn.h and ocrl_hip_replay.h: the limits, the workspace's
-// layout, the head as the tile code's arguments and the fold of the slabs' partial dw
-namespace qnet {
-struct QLay {
-    size_t saved[ACNET_MAX_LAYERS], slab, scal, total;
-    long long off[2 * ACNET_MAX_LAYERS + 3];
-    int np, S, ntiles;
-};
-int check_qnet(const ocrl_qnet_desc* d, const char* who);
-QLay q_layout(const ocrl_qnet_desc* d);
-void fill_args(AcnetArgs& a, const ocrl_qnet_desc* d, const QLay& y, const float* x, const float* const* w, float* ws, bool saved);
-int check_ptrs(const void* const* w, int np, const char* who);
-int reduce_dw(const AcnetArgs& a, const QLay& y, float* const* dw, hipStream_t st);
-}  // namespace qnet
-
 int dqn_act_launch(const AcnetArgs& a, const DqnActArgs& s, hipStream_t st);
 int dqn_act_uniforms_launch(unsigned long long seed, unsigned long long row_offset, long long n, float* out, hipStream_t st);
-int dqn_td_launch(const AcnetArgs& a, const DqnTdArgs& s, hipStream_t st);
-int dqn_scalars_launch(const float* scal_slab, int S, int B, float* out, hipStream_t st);
+int dqn_td_launch(const AcnetArgs& a, const DqnTdArgs& s, bool ext, hipStream_t st);      // ext: the kernel that reads the optional inputs
+// out[0..2] = the slabs' three scalar sums over B; count2: out[2] stays the sum (C51 and the classifier fold their scalars here too)
+int head_scalars_launch(const float* scal_slab, int S, int B, bool count2, float* out, hipStream_t st);
 int replay_gather_launch(const ReplayGatherArgs& g, hipStream_t st);
 int replay_sample_launch(unsigned long long seed, unsigned long long update, int B, int N, int E, int pos, int full, long long* idx, hipStream_t st);

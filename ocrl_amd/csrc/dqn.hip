@@ -4,8 +4,11 @@
 //   dqn_act           the forward with the choice in the same launch: lane r of a tile flips row r's coin and takes the random action or
 //                     the lowest index of the maximum Q
 //   dqn_td            forward, TD target, Huber loss, dQ and the backward per row tile in one kernel; Q and the layer cotangents never
-//                     leave LDS.  Partial dw go to the workgroup's slab, the three scalar sums to its row of scal_slab
-//   dqn_scalars       loss, mean Q[a], mean y from the slabs' partial sums, in slab order (dw is folded by acnet_reduce)
+//                     leave LDS.  Partial dw go to the workgroup's slab, the three scalar sums to its row of scal_slab.  Two
+//                     instantiations: the plain step, and the one with the optional inputs of ocrl_hip_replay.h (double Q-learning,
+//                     per-row discounts, importance weights, |delta| out): the same tiles, the same order of every sum
+//   head_scalars      loss, mean Q[a], mean y from the slabs' partial sums, in slab order (dw is folded by acnet_reduce); C51's and the
+//                     classifier's three scalars too
 //   replay_gather     obs, next_obs, actions, rewards, dones of B transitions: workgroup (b, chunk) copies a stretch of both observations
 //   replay_sample     one thread per row: a valid slot and an environment from the counter RNG
 // Order of every sum: acnet.hip's for the layers and the slabs; a tile's scalar terms are added in row order, the tiles of a slab in tile
@@ -57,7 +60,9 @@ __global__ __launch_bounds__(256) void dqn_act_uniforms_kernel(unsigned long lon
 }
 
 // The TD step of one tile after its forward: thread r < 16 owns row r.  Replaces the Q values in lg by dL/dQ (L = the mean loss) and adds
-// the row's three terms (Huber loss, Q[a], y) to the slab's partial sums.
+// the row's three terms (Huber loss, Q[a], y) to the slab's partial sums.  EXT compiles the target's optional inputs in (ocrl_hip_replay.h);
+// where one is not given the operations are the plain step's own, in its order.
+template <bool EXT>
 __device__ void td_rows(const AcnetArgs& p, const DqnTdArgs& s, long long row0, int rows, bool first, float* lg, float (*rs)[3]) {
     const int r = threadIdx.x;
     if (r < TR) {
@@ -75,13 +80,30 @@ __device__ void td_rows(const AcnetArgs& p, const DqnTdArgs& s, long long row0, 
             if (!s.dones[row]) {                        // a select: next_q of a finished row is not read
                 const float* nq = s.next_q + row * A;
                 float m = nq[0];
-                for (int k = 1; k < A; ++k) m = nq[k] > m ? nq[k] : m;
-                y += s.gamma * m;
+                if (EXT && s.next_q_online) {           // the target's value where the online network has its (lowest) maximum
+                    const float* on = s.next_q_online + row * A;
+                    float mo = on[0];
+                    int best = 0;
+                    for (int k = 1; k < A; ++k)
+                        if (on[k] > mo) { mo = on[k]; best = k; }
+                    m = nq[best];
+                } else {
+                    for (int k = 1; k < A; ++k) m = nq[k] > m ? nq[k] : m;
+                }
+                const float disc = EXT && s.discounts ? s.discounts[row] : s.gamma;
+                y += disc * m;
             }
             const float delta = q - y, ad = fabsf(delta);
-            t[0] = ad < 1.f ? 0.5f * delta * delta : ad - 0.5f;
-            t[1] = q; t[2] = y;
-            g = fminf(fmaxf(delta, -1.f), 1.f) / (float)p.B;
+            float l = ad < 1.f ? 0.5f * delta * delta : ad - 0.5f;
+            float c = fminf(fmaxf(delta, -1.f), 1.f);
+            if (EXT && s.weights) {
+                const float w = s.weights[row];
+                l = w * l;
+                c = w * c;
+            }
+            t[0] = l; t[1] = q; t[2] = y;
+            g = c / (float)p.B;
+            if (EXT && s.abs_td) s.abs_td[row] = ad;
         }
         for (int k = 0; k < A; ++k) z[k] = 0.f;
         z[act] = g;
@@ -89,16 +111,10 @@ __device__ void td_rows(const AcnetArgs& p, const DqnTdArgs& s, long long row0, 
         for (int j = 0; j < 3; ++j) rs[r][j] = t[j];
     }
     __syncthreads();
-    if (threadIdx.x < 3) {
-        float sum = 0.f;
-#pragma unroll
-        for (int q = 0; q < TR; ++q) sum += rs[q][threadIdx.x];
-        float* d = p.scal_slab + (long long)blockIdx.x * 8 + threadIdx.x;
-        *d = first ? sum : *d + sum;
-    }
-    __syncthreads();
+    tile_scalars<3>(rs, first, p.scal_slab);
 }
 
+template <bool EXT>
 __global__ __launch_bounds__(256) void dqn_td_kernel(AcnetArgs p, DqnTdArgs s) {
     __shared__ __attribute__((aligned(16))) float buf[3 * TR * LD];
     __shared__ __attribute__((aligned(16))) float lg[TR * LA];
@@ -108,18 +124,19 @@ __global__ __launch_bounds__(256) void dqn_td_kernel(AcnetArgs p, DqnTdArgs s) {
         const int rows = p.B - row0 < TR ? (int)(p.B - row0) : TR;
         const bool first = tile == (int)blockIdx.x;
         fwd_tile(p, row0, rows, buf, lg, nullptr);
-        td_rows(p, s, row0, rows, first, lg, rs);
+        td_rows<EXT>(p, s, row0, rows, first, lg, rs);
         bwd_tile(p, row0, rows, first, buf, lg, nullptr);
         __syncthreads();
     }
 }
 
-__global__ __launch_bounds__(64) void dqn_scalars_kernel(const float* __restrict__ scal_slab, int S, int B, float* __restrict__ out) {
+// out[j] = the slabs' partial sums of scalar j in slab order, over B; `count2` leaves scalar 2 a count (the classifier's valid rows)
+__global__ __launch_bounds__(64) void head_scalars_kernel(const float* __restrict__ scal_slab, int S, int B, int count2, float* __restrict__ out) {
     const int j = threadIdx.x;
     if (j >= 3) return;
     float s = 0.f;
     for (int k = 0; k < S; ++k) s += scal_slab[k * 8 + j];
-    out[j] = s / (float)B;
+    out[j] = count2 && j == 2 ? s : s / (float)B;
 }
 
 // Workgroup (b, c): transition b, units c * 256 + t, + 256 gridDim.y, ... of its two observations; V is the access (16 or 4 bytes).
@@ -169,14 +186,17 @@ int dqn_act_uniforms_launch(unsigned long long seed, unsigned long long row_offs
     OCRL_CHECK_LAUNCH("dqn_act_uniforms");
     return 0;
 }
-int dqn_td_launch(const AcnetArgs& a, const DqnTdArgs& s, hipStream_t st) {
-    hipLaunchKernelGGL(dqn_td_kernel, dim3(a.S), dim3(256), 0, st, a, s);
-    OCRL_CHECK_LAUNCH("dqn_td");
+int dqn_td_launch(const AcnetArgs& a, const DqnTdArgs& s, bool ext, hipStream_t st) {
+    if (ext)
+        hipLaunchKernelGGL(dqn_td_kernel<true>, dim3(a.S), dim3(256), 0, st, a, s);
+    else
+        hipLaunchKernelGGL(dqn_td_kernel<false>, dim3(a.S), dim3(256), 0, st, a, s);
+    OCRL_CHECK_LAUNCH(ext ? "dqn_td_ext" : "dqn_td");
     return 0;
 }
-int dqn_scalars_launch(const float* scal_slab, int S, int B, float* out, hipStream_t st) {
-    hipLaunchKernelGGL(dqn_scalars_kernel, dim3(1), dim3(64), 0, st, scal_slab, S, B, out);
-    OCRL_CHECK_LAUNCH("dqn_scalars");
+int head_scalars_launch(const float* scal_slab, int S, int B, bool count2, float* out, hipStream_t st) {
+    hipLaunchKernelGGL(head_scalars_kernel, dim3(1), dim3(64), 0, st, scal_slab, S, B, count2 ? 1 : 0, out);
+    OCRL_CHECK_LAUNCH("head_scalars");
     return 0;
 }
 int replay_gather_launch(const ReplayGatherArgs& g, hipStream_t st) {

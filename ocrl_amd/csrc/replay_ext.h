@@ -1,5 +1,6 @@
 // Kernel arguments and launchers of DQN's replay extensions (replay_ext.hip; C entry points in replay_ext_unit.cpp;
-// include/ocrl_hip_replay.h is the specification): the n-step sampling and batch read, the extended TD step and the priority store.
+// include/ocrl_hip_replay.h is the specification): the n-step sampling and batch read and the priority store; the
+// extended TD step is dqn_td_launch of dqn.h.
 #pragma once
 #include "dqn.h"
 
@@ -9,19 +10,6 @@
 #define PER_MAX_LEVELS 6           // ceil(31 / 6): levels of sums above fewer than 2^31 leaves
 #define PER_Q_ONE 65536u           // the fixed point's 1
 #define PER_Q_MAX 16777216u        // 2^24: the largest stored priority (exact as a float)
-
-// the TD target's inputs of dqn.h's DqnTdArgs and the optional per-row arrays (null: not given)
-struct DqnTdExtArgs {
-    const float* next_q;
-    const float* next_q_online;                       // [B, A]: where the maximum is looked for (double Q-learning)
-    const long long* actions;
-    const float* rewards;
-    const unsigned char* dones;
-    const float* discounts;                           // [B]: replaces gamma
-    const float* weights;                             // [B]: scales a row's loss and gradient
-    float gamma;
-    float* abs_td;                                    // [B] out
-};
 
 struct ReplayGatherNstepArgs {
     ReplayGatherArgs g;                               // rewards_out takes the returns
@@ -43,7 +31,6 @@ struct PerTree {
 int replay_sample_nstep_launch(unsigned long long seed, unsigned long long update, int B, int N, int E, int pos, int full, int n, long long* idx,
                                hipStream_t st);
 int replay_gather_nstep_launch(const ReplayGatherNstepArgs& a, hipStream_t st);
-int dqn_td_ext_launch(const AcnetArgs& a, const DqnTdExtArgs& s, hipStream_t st);
 int per_init_launch(const PerTree& t, hipStream_t st);
 int per_set_range_launch(const PerTree& t, long long first, long long count, int mode, hipStream_t st);
 int per_update_launch(const PerTree& t, const long long* idx, const float* abs_td, int B, float alpha, float eps, hipStream_t st);

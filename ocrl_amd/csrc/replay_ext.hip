@@ -1,14 +1,12 @@
-// DQN's replay extensions on the device (include/ocrl_hip_replay.h): n-step returns read from the ring, the TD step with double
-// Q-learning, per-row discounts and importance weights, and the proportional priority store.
+// DQN's replay extensions on the device (include/ocrl_hip_replay.h): n-step returns read from the ring and the proportional priority
+// store.  The TD step with double Q-learning, per-row discounts and importance weights is dqn.hip's dqn_td with its options compiled in.
 //   replay_sample_nstep  one thread per row: a slot whose n-step window is stored and an environment, from the counter RNG
 //   replay_gather_nstep  workgroup (b, chunk) as replay_gather; every thread walks the window's dones (uniform reads), so that the
 //                        workgroup knows which slot holds the observation after the return
-//   dqn_td_ext           dqn.hip's dqn_td with the target's optional inputs: the same tiles, the same order of every sum
 //   per_*                the priority store: uint32 leaves under levels of exact uint64 sums with fan-out 64.  A wave owns a node: lane i
 //                        reads child i, the wave adds (rebuild) or scans (the sampler's descent).  Integer sums: no order to fix.
 // No atomics.  A workgroup that rebuilds several levels in turn puts a barrier between them: the nodes of a level are written and read
 // by waves of that one workgroup.
-#include "acnet_tile.h"
 #include "replay_ext.h"
 
 namespace {
@@ -65,80 +63,6 @@ __global__ __launch_bounds__(256) void replay_gather_nstep_kernel(ReplayGatherNs
         g.rewards_out[b] = R;
         g.dones_out[b] = stop;
         a.discounts_out[b] = disc;
-    }
-}
-
-// dqn.hip's td_rows with the optional inputs.  Where an input is not given the operations are td_rows' own, in its order.
-__device__ void td_rows_ext(const AcnetArgs& p, const DqnTdExtArgs& s, long long row0, int rows, bool first, float* lg, float (*rs)[3]) {
-    const int r = threadIdx.x;
-    if (r < TR) {
-        float t[3] = {0.f, 0.f, 0.f};
-        float* z = lg + r * LA;
-        const int A = p.A;
-        float g = 0.f;
-        int act = 0;
-        if (r < rows) {
-            const long long row = row0 + r;
-            long long a = s.actions[row];
-            act = (int)(a < 0 ? 0 : a >= A ? A - 1 : a);
-            const float q = z[act];
-            float y = s.rewards[row];
-            if (!s.dones[row]) {                        // a select: next_q of a finished row is not read
-                const float* nq = s.next_q + row * A;
-                float m = nq[0];
-                if (s.next_q_online) {                  // the target's value where the online network has its (lowest) maximum
-                    const float* on = s.next_q_online + row * A;
-                    float mo = on[0];
-                    int best = 0;
-                    for (int k = 1; k < A; ++k)
-                        if (on[k] > mo) { mo = on[k]; best = k; }
-                    m = nq[best];
-                } else {
-                    for (int k = 1; k < A; ++k) m = nq[k] > m ? nq[k] : m;
-                }
-                const float disc = s.discounts ? s.discounts[row] : s.gamma;
-                y += disc * m;
-            }
-            const float delta = q - y, ad = fabsf(delta);
-            float l = ad < 1.f ? 0.5f * delta * delta : ad - 0.5f;
-            float c = fminf(fmaxf(delta, -1.f), 1.f);
-            if (s.weights) {
-                const float w = s.weights[row];
-                l = w * l;
-                c = w * c;
-            }
-            t[0] = l; t[1] = q; t[2] = y;
-            g = c / (float)p.B;
-            if (s.abs_td) s.abs_td[row] = ad;
-        }
-        for (int k = 0; k < A; ++k) z[k] = 0.f;
-        z[act] = g;
-#pragma unroll
-        for (int j = 0; j < 3; ++j) rs[r][j] = t[j];
-    }
-    __syncthreads();
-    if (threadIdx.x < 3) {
-        float sum = 0.f;
-#pragma unroll
-        for (int q = 0; q < TR; ++q) sum += rs[q][threadIdx.x];
-        float* d = p.scal_slab + (long long)blockIdx.x * 8 + threadIdx.x;
-        *d = first ? sum : *d + sum;
-    }
-    __syncthreads();
-}
-
-__global__ __launch_bounds__(256) void dqn_td_ext_kernel(AcnetArgs p, DqnTdExtArgs s) {
-    __shared__ __attribute__((aligned(16))) float buf[3 * TR * LD];
-    __shared__ __attribute__((aligned(16))) float lg[TR * LA];
-    __shared__ float rs[TR][3];
-    for (int tile = blockIdx.x; tile < p.ntiles; tile += p.S) {
-        const long long row0 = (long long)tile * TR;
-        const int rows = p.B - row0 < TR ? (int)(p.B - row0) : TR;
-        const bool first = tile == (int)blockIdx.x;
-        fwd_tile(p, row0, rows, buf, lg, nullptr);
-        td_rows_ext(p, s, row0, rows, first, lg, rs);
-        bwd_tile(p, row0, rows, first, buf, lg, nullptr);
-        __syncthreads();
     }
 }
 
@@ -328,11 +252,6 @@ int replay_gather_nstep_launch(const ReplayGatherNstepArgs& a, hipStream_t st) {
     else
         hipLaunchKernelGGL(replay_gather_nstep_kernel<uint32_t>, dim3(a.g.B, chunks), dim3(256), 0, st, a);
     OCRL_CHECK_LAUNCH("replay_gather_nstep");
-    return 0;
-}
-int dqn_td_ext_launch(const AcnetArgs& a, const DqnTdExtArgs& s, hipStream_t st) {
-    hipLaunchKernelGGL(dqn_td_ext_kernel, dim3(a.S), dim3(256), 0, st, a, s);
-    OCRL_CHECK_LAUNCH("dqn_td_ext");
     return 0;
 }
 int per_init_launch(const PerTree& t, hipStream_t st) {

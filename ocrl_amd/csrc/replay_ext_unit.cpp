@@ -1,9 +1,8 @@
 // C ABI of DQN's replay extensions (include/ocrl_hip_replay.h: ocrl_replay_*_nstep, ocrl_dqn_td_fwd_bwd_ext, ocrl_per_*).  Stateless: the
-// caller owns the ring, the priority store's buffer, parameters, gradients and the workspace.  The Q head's host side is dqn_unit.cpp's.
+// caller owns the ring, the priority store's buffer, parameters, gradients and the workspace.  The Q head's host side is acnet_host.h's.
 #include "../../include/ocrl_hip_replay.h"
+#include "acnet_host.h"
 #include "replay_ext.h"
-
-using namespace qnet;
 
 namespace {
 
@@ -79,19 +78,17 @@ int ocrl_dqn_td_fwd_bwd_ext(const void* dv, const float* features, const float* 
     const char* who = "ocrl_dqn_td_fwd_bwd_ext";
     const ocrl_qnet_desc* d = static_cast<const ocrl_qnet_desc*>(dv);
     RC(check_qnet(d, who));
-    const QLay y = q_layout(d);
+    const HeadSpec s = qnet_spec(d);
+    const HeadLay y = head_layout(s);
     OCRL_REQUIRE(features && w && next_q && actions && rewards && dones && scalars && dw && ws, "%s: null argument", who);
-    RC(check_ptrs((const void* const*)w, y.np, who));
-    RC(check_ptrs((const void* const*)dw, y.np, who));
-    OCRL_REQUIRE(ws_floats >= y.total, "%s: workspace too small (%zu < %zu floats)", who, ws_floats, y.total);
     hipStream_t st = static_cast<hipStream_t>(stream);
     AcnetArgs a;
-    fill_args(a, d, y, features, w, ws, true);
+    RC(head_begin(a, s, y, who, features, w, dw, ws, ws_floats));
     a.dx = dfeatures;
-    const DqnTdExtArgs s{next_q, next_q_online, actions, rewards, dones, discounts, weights, gamma, abs_td};
-    RC(dqn_td_ext_launch(a, s, st));
+    const DqnTdArgs t{next_q, actions, rewards, dones, gamma, next_q_online, discounts, weights, abs_td};
+    RC(dqn_td_launch(a, t, true, st));
     RC(reduce_dw(a, y, dw, st));
-    return dqn_scalars_launch(a.scal_slab, y.S, d->B, scalars, st);
+    return head_scalars_launch(a.scal_slab, y.S, d->B, false, scalars, st);
 }
 
 size_t ocrl_per_bytes(long long NE) {

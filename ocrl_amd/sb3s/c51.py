@@ -8,10 +8,9 @@ distribution onto the support, the cross-entropy and the head's gradient, fused)
 import ctypes
 
 import torch
-from torch import nn
 
 from .. import _bridge, _lib
-from .noisy import effective_params, linear
+from .qhead import DQN_SCALARS, QHead, coerce, scaled_grads
 
 _WHO = "ocrl_amd.sb3s"
 
@@ -61,14 +60,11 @@ class _C51TdFn(torch.autograd.Function):
         x, ps = _bridge.inputs(_WHO, features, params)
         dev = x.device
         B, F = x.shape
-        vec = lambda t, dt: None if t is None else t.detach().to(device=dev, dtype=dt).reshape(-1).contiguous()
-        actions, rewards, dones = vec(actions, torch.int64), vec(rewards, torch.float32), vec(dones, torch.uint8)
-        discounts, weights = vec(discounts, torch.float32), vec(weights, torch.float32)
-        next_probs, next_q = vec(next_probs, torch.float32), vec(next_q, torch.float32)
-        for name, t, n in (("actions", actions, B), ("rewards", rewards, B), ("dones", dones, B), ("next_probs", next_probs, B * A * Z),
-                           ("next_q", next_q, B * A), ("discounts", discounts, B), ("weights", weights, B)):
-            if t is not None and t.numel() != n:
-                raise ValueError(f"{_WHO}.c51_loss: {name} has {t.numel()} entries for a batch of {B}, {A} actions and {Z} atoms")
+        f32 = torch.float32
+        actions, rewards, dones, next_probs, next_q, discounts, weights = coerce(
+            f"{_WHO}.c51_loss", dev, f"a batch of {B}, {A} actions and {Z} atoms", ("actions", actions, torch.int64, B),
+            ("rewards", rewards, f32, B), ("dones", dones, torch.uint8, B), ("next_probs", next_probs, f32, B * A * Z),
+            ("next_q", next_q, f32, B * A), ("discounts", discounts, f32, B), ("weights", weights, f32, B))
         d, ws = _desc(B, F, A, Z, dims, acts, dueling, dev)
         scal = torch.empty(3, device=dev, dtype=torch.float32)
         row_loss = torch.empty(B, device=dev, dtype=torch.float32)
@@ -83,52 +79,35 @@ class _C51TdFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gloss, _gscal, _grow):
-        dx = None if ctx.dx is None else ctx.dx * gloss
-        return (dx,) + (None,) * 9 + tuple(g * gloss for g in ctx.gs)
+        return scaled_grads(ctx, gloss, 9)
 
 
-class CategoricalQNetwork(nn.Module):
+class CategoricalQNetwork(QHead):
     """features [B, F] -> len(net_arch) x [Linear, activation] -> Linear(last, n_actions * n_atoms), atom j of action a in column
     a * n_atoms + j; with ``dueling`` a second Linear(last, n_atoms), ``value_net``, on the same latent:
     logit[a, j] = V[j] + Adv[a, j] - mean_a' Adv[a', j].  The parameters sit in ``q_net``, an nn.Sequential with QNetwork's keys
-    (``q_net.{2i}.weight|bias``), and in ``value_net``; neither container's ``forward`` is called.  ``n_actions``, ``n_atoms`` and the
+    (``q_net.{2i}.weight|bias``; QHead), and in ``value_net``; neither container's ``forward`` is called.  ``n_actions``, ``n_atoms`` and the
     support ``atoms`` [n_atoms] = v_min + j (v_max - v_min) / (n_atoms - 1) are attributes.  ``noisy``: every Linear, the advantage and
     the value layer included, is a NoisyLinear, as QNetwork's.  No CPU fallback: a CPU tensor raises."""
-    _noise = None
 
     def __init__(self, features_dim, n_actions, n_atoms, v_min, v_max, net_arch=(64, 64), activation="relu", dueling=False, noisy=False,
                  noisy_sigma0=0.5):
-        super().__init__()
-        from .dqn import _ACT                                 # dqn.py imports this module: its names are taken when they are used
-        if activation not in _ACT:
-            raise ValueError(f"{_WHO}.CategoricalQNetwork: activation {activation!r} is not one of {', '.join(_ACT)}")
+        super().__init__(features_dim, int(n_actions) * int(n_atoms), net_arch, activation, noisy, noisy_sigma0)
         self.n_actions, self.n_atoms, self.dueling = int(n_actions), int(n_atoms), bool(dueling)
         self.v_min, self.v_max = float(v_min), float(v_max)
         if self.n_atoms < 2 or not self.v_min < self.v_max:
             raise ValueError(f"{_WHO}.CategoricalQNetwork: n_atoms >= 2 and v_min < v_max (got {n_atoms}, {v_min}, {v_max})")
-        self._dims, self._act = tuple(int(w) for w in net_arch), _ACT[activation][1]
-        self.noisy, self.noisy_sigma0 = bool(noisy), float(noisy_sigma0)
-        layers, in_dim = [], int(features_dim)
-        for w in self._dims:
-            layers += [linear(in_dim, w, self.noisy, self.noisy_sigma0), _ACT[activation][0]()]
-            in_dim = w
-        self.q_net = nn.Sequential(*layers, linear(in_dim, self.n_actions * self.n_atoms, self.noisy, self.noisy_sigma0))
         if self.dueling:
-            self.value_net = linear(in_dim, self.n_atoms, self.noisy, self.noisy_sigma0)
+            self.value_net = self._linear(self.latent_dim, self.n_atoms)
         self.register_buffer("atoms", torch.linspace(self.v_min, self.v_max, self.n_atoms), persistent=False)
-
-    def _layout(self):
-        """(hidden widths, activation codes), as the C ABI takes them"""
-        return self._dims, (self._act,) * len(self._dims)
 
     def _head(self):
         """what the autograd functions need of the head besides its parameters"""
         return (self.n_actions, self.n_atoms, *self._layout(), self.dueling, self.v_min, self.v_max)
 
     def _param_list(self):
-        """(weight, bias) per Linear as the kernels take them; with ``noisy`` the effective tensors of the current draw"""
-        mods = [m for m in self.q_net if isinstance(m, nn.Linear)] + ([self.value_net] if self.dueling else [])
-        return effective_params(mods, self._noise if self.noisy else None)
+        """QHead's list with the value Linear's pair at its end"""
+        return super()._param_list(*([self.value_net] if self.dueling else []))
 
     def logits(self, features):
         """[B, n_actions, n_atoms], attached to autograd"""
@@ -169,7 +148,6 @@ def c51_loss(policy, features, next_probs, next_q, actions, rewards, dones, gamm
     the head's distribution of the action taken, attached to autograd: ``backward()`` puts the gradients on the head's parameters and on
     ``features``.  ``metrics`` maps DQN_SCALARS to detached 0-d tensors (loss, the mean expected q of the action taken, the mean of the
     projected target); ``row_loss`` [B], detached, is each row's cross-entropy, unweighted: the priority of prioritized replay."""
-    from .dqn import DQN_SCALARS
     net = policy.q_net
     if not isinstance(net, CategoricalQNetwork):
         raise TypeError(f"{_WHO}.c51_loss: the policy's head is a {type(net).__name__}, not a CategoricalQNetwork (build it with n_atoms >= 2)")

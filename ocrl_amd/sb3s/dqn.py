@@ -25,15 +25,13 @@ from .. import _bridge, _lib
 from ..ocrs.flat_module import FlatParamModule
 from .c51 import CategoricalQNetwork, c51_loss
 from .custom_acnets import _n_actions
-from .noisy import effective_params, linear
 from .on_policy import OnPolicyAlgorithm, _check_constant, _tensor
+from .qhead import DQN_SCALARS, QHead, coerce, scaled_grads
 from .replay import MAX_N_STEP, ReplayBuffer
 
 _WHO = "ocrl_amd.sb3s"
-_ACT = {"relu": (nn.ReLU, 1), "tanh": (nn.Tanh, 2)}
 MAX_ATOMS, MAX_LOGITS = 64, 256   # of the categorical head: atoms per action, n_actions * n_atoms (include/ocrl_hip_c51.h)
 ADAM_EPS = 1e-8                 # stable-baselines3's DQNPolicy builds torch's default Adam (the actor-critic policy: 1e-5)
-DQN_SCALARS = ("loss", "mean_q", "mean_target")
 
 
 def _desc(B, F, A, dims, acts, dev, keep=True):
@@ -71,95 +69,50 @@ class _QnetFn(torch.autograd.Function):
         return (dx, None, None, None, *gs)
 
 
-class _DqnFn(torch.autograd.Function):
+class _DqnTdFn(torch.autograd.Function):
+    """the fused TD step: (loss, scalars [3], |delta| per row or None); the gradients are the forward's own outputs.  With none of
+    the optional inputs of ocrl_dqn_td_fwd_bwd_ext (include/ocrl_hip_replay.h) given and no ``want_abs_td`` the call is
+    ocrl_dqn_td_fwd_bwd's"""
+
     @staticmethod
-    def forward(ctx, features, next_q, actions, rewards, dones, gamma, dims, acts, A, *params):
+    def forward(ctx, features, next_q, next_q_online, actions, rewards, dones, discounts, weights, gamma, want_abs_td, dims, acts, A, *params):
         x, ps = _bridge.inputs(_WHO, features, params)
         dev = x.device
         B, F = x.shape
-        vec = lambda t, dt: t.to(device=dev, dtype=dt).reshape(-1).contiguous()
-        actions, rewards, dones = vec(actions, torch.int64), vec(rewards, torch.float32), vec(dones, torch.uint8)
-        next_q = next_q.detach().to(device=dev, dtype=torch.float32).contiguous()
-        for name, t, n in (("actions", actions, B), ("rewards", rewards, B), ("dones", dones, B), ("next_q", next_q, B * A)):
-            if t.numel() != n:
-                raise ValueError(f"{_WHO}.dqn_loss: {name} has {t.numel()} entries for a batch of {B} and {A} actions")
+        f32 = torch.float32
+        actions, rewards, dones, next_q, next_q_online, discounts, weights = coerce(
+            f"{_WHO}.dqn_loss", dev, f"a batch of {B} and {A} actions", ("actions", actions, torch.int64, B), ("rewards", rewards, f32, B),
+            ("dones", dones, torch.uint8, B), ("next_q", next_q, f32, B * A), ("next_q_online", next_q_online, f32, B * A),
+            ("discounts", discounts, f32, B), ("weights", weights, f32, B))
         d, ws = _desc(B, F, A, dims, acts, dev)
-        scal = torch.empty(3, device=dev, dtype=torch.float32)
+        scal = torch.empty(3, device=dev, dtype=f32)
         gs = [torch.empty_like(p) for p in ps]
         dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
-        _bridge.launch(dev, _lib.lib().ocrl_dqn_td_fwd_bwd, ctypes.byref(d), _lib.ptr(x), _lib.ptrs(ps), _lib.ptr(next_q), _lib.ptr(actions),
-                       _lib.ptr(rewards), _lib.ptr(dones), float(gamma), _lib.ptr(scal), _lib.ptr(dx), _lib.ptrs(gs), _lib.ptr(ws), ws.numel())
+        abs_td = None
+        if next_q_online is None and discounts is None and weights is None and not want_abs_td:
+            _bridge.launch(dev, _lib.lib().ocrl_dqn_td_fwd_bwd, ctypes.byref(d), _lib.ptr(x), _lib.ptrs(ps), _lib.ptr(next_q), _lib.ptr(actions),
+                           _lib.ptr(rewards), _lib.ptr(dones), float(gamma), _lib.ptr(scal), _lib.ptr(dx), _lib.ptrs(gs), _lib.ptr(ws), ws.numel())
+        else:
+            abs_td = torch.empty(B, device=dev, dtype=f32)
+            _bridge.launch(dev, _lib.lib().ocrl_dqn_td_fwd_bwd_ext, ctypes.byref(d), _lib.ptr(x), _lib.ptrs(ps), _lib.ptr(next_q),
+                           _lib.ptr(next_q_online), _lib.ptr(actions), _lib.ptr(rewards), _lib.ptr(dones), _lib.ptr(discounts), _lib.ptr(weights),
+                           float(gamma), _lib.ptr(scal), _lib.ptr(abs_td), _lib.ptr(dx), _lib.ptrs(gs), _lib.ptr(ws), ws.numel())
         ctx.gs, ctx.dx = gs, dx              # the gradients are the forward's own outputs: the backward reads nothing else again
-        ctx.mark_non_differentiable(scal)
-        return scal[0].clone(), scal
-
-    @staticmethod
-    def backward(ctx, gloss, _gscal):
-        dx = None if ctx.dx is None else ctx.dx * gloss
-        return (dx, None, None, None, None, None, None, None, None, *[g * gloss for g in ctx.gs])
-
-
-class _DqnExtFn(torch.autograd.Function):
-    """_DqnFn with the optional inputs of ocrl_dqn_td_fwd_bwd_ext (include/ocrl_hip_replay.h); also returns |delta| per row"""
-
-    @staticmethod
-    def forward(ctx, features, next_q, next_q_online, actions, rewards, dones, discounts, weights, gamma, dims, acts, A, *params):
-        x, ps = _bridge.inputs(_WHO, features, params)
-        dev = x.device
-        B, F = x.shape
-        vec = lambda t, dt: None if t is None else t.detach().to(device=dev, dtype=dt).reshape(-1).contiguous()
-        actions, rewards, dones = vec(actions, torch.int64), vec(rewards, torch.float32), vec(dones, torch.uint8)
-        discounts, weights = vec(discounts, torch.float32), vec(weights, torch.float32)
-        next_q, next_q_online = vec(next_q, torch.float32), vec(next_q_online, torch.float32)
-        for name, t, n in (("actions", actions, B), ("rewards", rewards, B), ("dones", dones, B), ("next_q", next_q, B * A),
-                           ("next_q_online", next_q_online, B * A), ("discounts", discounts, B), ("weights", weights, B)):
-            if t is not None and t.numel() != n:
-                raise ValueError(f"{_WHO}.dqn_loss: {name} has {t.numel()} entries for a batch of {B} and {A} actions")
-        d, ws = _desc(B, F, A, dims, acts, dev)
-        scal = torch.empty(3, device=dev, dtype=torch.float32)
-        abs_td = torch.empty(B, device=dev, dtype=torch.float32)
-        gs = [torch.empty_like(p) for p in ps]
-        dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
-        _bridge.launch(dev, _lib.lib().ocrl_dqn_td_fwd_bwd_ext, ctypes.byref(d), _lib.ptr(x), _lib.ptrs(ps), _lib.ptr(next_q), _lib.ptr(next_q_online),
-                       _lib.ptr(actions), _lib.ptr(rewards), _lib.ptr(dones), _lib.ptr(discounts), _lib.ptr(weights), float(gamma), _lib.ptr(scal),
-                       _lib.ptr(abs_td), _lib.ptr(dx), _lib.ptrs(gs), _lib.ptr(ws), ws.numel())
-        ctx.gs, ctx.dx = gs, dx
-        ctx.mark_non_differentiable(scal, abs_td)
+        ctx.mark_non_differentiable(*(t for t in (scal, abs_td) if t is not None))
         return scal[0].clone(), scal, abs_td
 
     @staticmethod
     def backward(ctx, gloss, _gscal, _gtd):
-        dx = None if ctx.dx is None else ctx.dx * gloss
-        return (dx,) + (None,) * 11 + tuple(g * gloss for g in ctx.gs)
+        return scaled_grads(ctx, gloss, 12)
 
 
-class QNetwork(nn.Module):
-    """features [B, F] -> len(net_arch) x [Linear, activation] -> Linear(last, n_actions).  The parameters sit in ``q_net``, an
-    nn.Sequential whose ``state_dict()`` keys are ``q_net.{2i}.weight|bias``; the container's ``forward`` is never called: the arithmetic
-    is ``ocrl_qnet_fwd`` / ``ocrl_qnet_bwd`` under a ``torch.autograd.Function``.  ``noisy``: every Linear is a NoisyLinear (sigmas start at
-    ``noisy_sigma0 / sqrt(in)``) and the kernels receive the effective parameters of the draw ``_noise`` = (seed, draw) names
-    (DQNPolicy.set_noise; None: the means).  No CPU fallback: a CPU tensor raises."""
-    _noise = None
+class QNetwork(QHead):
+    """features [B, F] -> len(net_arch) x [Linear, activation] -> Linear(last, n_actions).  The parameters sit in ``q_net`` (QHead); the
+    arithmetic is ``ocrl_qnet_fwd`` / ``ocrl_qnet_bwd`` under a ``torch.autograd.Function``.  No CPU fallback: a CPU tensor raises."""
 
     def __init__(self, features_dim, n_actions, net_arch=(64, 64), activation="relu", noisy=False, noisy_sigma0=0.5):
-        super().__init__()
-        if activation not in _ACT:
-            raise ValueError(f"{_WHO}.QNetwork: activation {activation!r} is not one of {', '.join(_ACT)}")
-        self.n_actions, self._dims, self._act = int(n_actions), tuple(int(w) for w in net_arch), _ACT[activation][1]
-        self.noisy, self.noisy_sigma0 = bool(noisy), float(noisy_sigma0)
-        layers, in_dim = [], int(features_dim)
-        for w in self._dims:
-            layers += [linear(in_dim, w, self.noisy, self.noisy_sigma0), _ACT[activation][0]()]
-            in_dim = w
-        self.q_net = nn.Sequential(*layers, linear(in_dim, self.n_actions, self.noisy, self.noisy_sigma0))
-
-    def _layout(self):
-        """(hidden widths, activation codes), as the C ABI takes them"""
-        return self._dims, (self._act,) * len(self._dims)
-
-    def _param_list(self):
-        """(weight, bias) per Linear as the kernels take them; with ``noisy`` the effective tensors of the current draw"""
-        return effective_params([m for m in self.q_net if isinstance(m, nn.Linear)], self._noise if self.noisy else None)
+        super().__init__(features_dim, int(n_actions), net_arch, activation, noisy, noisy_sigma0)
+        self.n_actions = int(n_actions)
 
     def forward(self, features):
         return _QnetFn.apply(features, *self._layout(), self.n_actions, *self._param_list())
@@ -278,11 +231,8 @@ def dqn_loss(policy, features, next_q, actions, rewards, dones, gamma, next_q_on
     return), ``weights`` [B] scales each row's loss and gradient (importance weights), and ``return_abs_td`` adds the rows' |Q[a] - y|
     [B], detached, as a third result."""
     dims, acts = policy.q_net._layout()
-    if next_q_online is None and discounts is None and weights is None and not return_abs_td:
-        loss, scal = _DqnFn.apply(features, next_q, actions, rewards, dones, gamma, dims, acts, policy.q_net.n_actions, *policy.q_net._param_list())
-        return loss, {k: scal[i] for i, k in enumerate(DQN_SCALARS)}
-    loss, scal, abs_td = _DqnExtFn.apply(features, next_q, next_q_online, actions, rewards, dones, discounts, weights, gamma, dims, acts,
-                                         policy.q_net.n_actions, *policy.q_net._param_list())
+    loss, scal, abs_td = _DqnTdFn.apply(features, next_q, next_q_online, actions, rewards, dones, discounts, weights, gamma, bool(return_abs_td),
+                                        dims, acts, policy.q_net.n_actions, *policy.q_net._param_list())
     metrics = {k: scal[i] for i, k in enumerate(DQN_SCALARS)}
     return (loss, metrics, abs_td) if return_abs_td else (loss, metrics)
 
@@ -551,12 +501,11 @@ class DQN:
             self.target.set_noise(self.noise_draws + 1)
             self.noise_draws += 2
 
-    def _train_step_ext(self):
-        """``train_step`` with any of double_q, n_step > 1 and prioritized_replay: the batch is drawn in proportion to the
-        priorities or among the whole n-step windows, read with its n-step returns, the online network names the bootstrap action, the
-        importance weights scale the loss, and the rows' |TD error| go back into the priority store.  No host read either."""
+    def _draw_batch(self):
+        """(batch, transition ids, importance weights or None) of this update: drawn in proportion to the priorities, among the whole
+        n-step windows or uniformly, and read with its n-step returns where n_step > 1.  The draw is a function of (seed, n_updates)."""
         buf = self.replay_buffer
-        if len(buf) == 0:
+        if (self.prioritized_replay or self.n_step > 1) and len(buf) == 0:
             raise RuntimeError(f"{self._who}.train_step: learning_starts = {self.learning_starts} leaves {buf.pos} vec steps in the replay ring at "
                                f"the first update, fewer than n_step = {self.n_step}: raise learning_starts to at least "
                                f"{self.n_step * self.n_envs} timesteps")
@@ -566,83 +515,59 @@ class DQN:
         else:
             idx = buf.sample_indices(self.batch_size, self.n_updates, self.n_step)
         batch = buf.gather(idx, self.n_step, self.gamma) if self.n_step > 1 else buf.gather(idx)
+        return batch, idx, weights
+
+    def _online_turn(self):
+        """the online network's turn in a gradient step: train mode and a zeroed ``flat_g``.  The steps call it once the target
+        network's launches are queued, so that the walk over the policy's modules runs while the GPU works on them."""
         self.policy.train()
-        self._draw_train_noise()
+        self.flat_g.zero_()
+
+    def _train_step_dqn(self, batch, weights):
+        """the scalar head's part of ``train_step``: (loss, metrics, the rows' |TD error| under prioritized replay).  The target network
+        gives the next observations' Q, the online network names the bootstrap action under double_q; with neither that nor n_step > 1
+        nor prioritized replay the step is ocrl_dqn_td_fwd_bwd's (``dqn_loss``)."""
         next_obs = self._obs(batch.next_observations)
         with torch.no_grad():
             next_q = self.target.q_values(next_obs)
-            next_q_online = self.policy.q_values(next_obs) if self.double_q else None
-        self.flat_g.zero_()
+        self._online_turn()
+        next_q_online = None
+        if self.double_q:
+            with torch.no_grad():
+                next_q_online = self.policy.q_values(next_obs)
         features = self.policy.extract_features(self._obs(batch.observations))
-        loss, m, abs_td = dqn_loss(self.policy, features, next_q, batch.actions, batch.rewards, batch.dones, self.gamma, next_q_online=next_q_online,
-                                   discounts=batch.discounts, weights=weights, return_abs_td=True)
-        loss.backward()
-        self._adam_step()
-        if self.prioritized_replay:
-            buf.update_priorities(idx, abs_td, self.prioritized_replay_alpha, self.prioritized_replay_eps)
-            self.last_weights = weights
-        self.n_updates += 1
-        self._acc += torch.cat([torch.stack([m[k] for k in DQN_SCALARS]), self._norm])
-        self._acc_n += 1
-        return loss
+        out = dqn_loss(self.policy, features, next_q, batch.actions, batch.rewards, batch.dones, self.gamma, next_q_online=next_q_online,
+                       discounts=batch.discounts, weights=weights, return_abs_td=self.prioritized_replay)
+        return out if self.prioritized_replay else (*out, None)
 
-    def _train_step_c51(self):
-        """``train_step`` of the categorical head, with or without double_q, n_step > 1 and prioritized_replay: the batch
-        is drawn and read as ``_train_step_ext`` does, the target network gives the next observations' distribution, the online network
-        names the bootstrap action under double_q, ``c51_loss`` projects, and the rows' cross-entropies go back into the priority store
-        in place of |TD error|.  No host read either."""
-        buf = self.replay_buffer
-        idx, weights = None, None
-        if self.prioritized_replay or self.n_step > 1:
-            if len(buf) == 0:
-                raise RuntimeError(f"{self._who}.train_step: learning_starts = {self.learning_starts} leaves {buf.pos} vec steps in the replay ring "
-                                   f"at the first update, fewer than n_step = {self.n_step}: raise learning_starts to at least "
-                                   f"{self.n_step * self.n_envs} timesteps")
-            if self.prioritized_replay:
-                idx, weights = buf.sample_prioritized(self.batch_size, self.n_updates, self.beta())
-            else:
-                idx = buf.sample_indices(self.batch_size, self.n_updates, self.n_step)
-            batch = buf.gather(idx, self.n_step, self.gamma) if self.n_step > 1 else buf.gather(idx)
-        else:
-            batch = buf.sample(self.batch_size, self.n_updates)
-        self.policy.train()
-        self._draw_train_noise()
+    def _train_step_c51(self, batch, weights):
+        """the categorical head's part of ``train_step``: (loss, metrics, the rows' cross-entropies, which take the place
+        of |TD error| in the priority store).  The target network gives the next observations' distribution, the online network names
+        the bootstrap action under double_q, ``c51_loss`` projects."""
+        next_obs = self._obs(batch.next_observations)
         with torch.no_grad():
-            next_features = self.target.extract_features(self._obs(batch.next_observations))
-            next_probs, next_q = self.target.q_net.distribution(next_features)
-            if self.double_q:
-                _, next_q = self.policy.q_net.distribution(self.policy.extract_features(self._obs(batch.next_observations)))
-        self.flat_g.zero_()
+            next_probs, next_q = self.target.q_net.distribution(self.target.extract_features(next_obs))
+        self._online_turn()
+        if self.double_q:
+            with torch.no_grad():
+                _, next_q = self.policy.q_net.distribution(self.policy.extract_features(next_obs))
         features = self.policy.extract_features(self._obs(batch.observations))
-        loss, m, row_loss = c51_loss(self.policy, features, next_probs, next_q, batch.actions, batch.rewards, batch.dones, self.gamma,
-                                     discounts=batch.discounts, weights=weights)
-        loss.backward()
-        self._adam_step()
-        if self.prioritized_replay:
-            buf.update_priorities(idx, row_loss, self.prioritized_replay_alpha, self.prioritized_replay_eps)
-            self.last_weights = weights
-        self.n_updates += 1
-        self._acc += torch.cat([torch.stack([m[k] for k in DQN_SCALARS]), self._norm])
-        self._acc_n += 1
-        return loss
+        return c51_loss(self.policy, features, next_probs, next_q, batch.actions, batch.rewards, batch.dones, self.gamma,
+                        discounts=batch.discounts, weights=weights)
 
     def train_step(self):
-        """one gradient step: a batch from the replay buffer, the target network's Q of the next observations, ``dqn_loss``, the backward
-        through the extractor, clip + Adam.  Nothing is read from the device: the scalars add up in ``_acc`` until a callback reads them."""
-        if self.n_atoms > 1:
-            return self._train_step_c51()
-        if self.double_q or self.n_step > 1 or self.prioritized_replay:
-            return self._train_step_ext()
-        batch = self.replay_buffer.sample(self.batch_size, self.n_updates)
+        """one gradient step: a batch from the replay buffer (``_draw_batch``), the head's loss against the target network
+        (``_train_step_dqn`` or, with n_atoms > 1, ``_train_step_c51``), the backward through the extractor, clip + Adam, and under
+        prioritized replay the rows' errors back into the priority store.  Nothing is read from the device: the scalars
+        add up in ``_acc`` until a callback reads them."""
+        batch, idx, weights = self._draw_batch()
         self._draw_train_noise()
-        with torch.no_grad():
-            next_q = self.target.q_values(self._obs(batch.next_observations))
-        self.policy.train()
-        self.flat_g.zero_()
-        features = self.policy.extract_features(self._obs(batch.observations))
-        loss, m = dqn_loss(self.policy, features, next_q, batch.actions, batch.rewards, batch.dones, self.gamma)
+        loss, m, row_err = (self._train_step_c51 if self.n_atoms > 1 else self._train_step_dqn)(batch, weights)
         loss.backward()
         self._adam_step()
+        if self.prioritized_replay:
+            self.replay_buffer.update_priorities(idx, row_err, self.prioritized_replay_alpha, self.prioritized_replay_eps)
+            self.last_weights = weights
         self.n_updates += 1
         self._acc += torch.cat([torch.stack([m[k] for k in DQN_SCALARS]), self._norm])
         self._acc_n += 1
