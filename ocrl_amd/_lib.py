@@ -1,4 +1,4 @@
-"""ctypes binding of libocrl_hip.so, derived from include/ocrl_hip.h, include/ocrl_hip_dqn.h, include/ocrl_hip_rollout.h, include/ocrl_hip_replay.h, include/ocrl_hip_c51.h, include/ocrl_hip_noisy.h and include/ocrl_hip_classifier.h (_abi.py reads them: the struct classes, the constants and every
+"""ctypes binding of libocrl_hip.so, derived from include/ocrl_hip.h, include/ocrl_hip_dqn.h, include/ocrl_hip_rollout.h, include/ocrl_hip_replay.h, include/ocrl_hip_c51.h, include/ocrl_hip_noisy.h, include/ocrl_hip_classifier.h and include/ocrl_hip_iodine.h (_abi.py reads them: the struct classes, the constants and every
 entry point's argtypes / restype come from the header's own declarations).  Fails loudly when the library is not built."""
 import ctypes
 import os
@@ -15,6 +15,7 @@ REPLAY_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "ocrl_hip_replay.
 C51_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "ocrl_hip_c51.h")      # DQN's categorical head: a fifth one
 NOISY_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "ocrl_hip_noisy.h")      # DQN's noisy linear layers: a sixth one
 CLASSIFIER_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "ocrl_hip_classifier.h")      # the MLP classifier's step: a seventh one
+IODINE_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "ocrl_hip_iodine.h")      # the IODINE / broadcast-decoder kernels one by one: an eighth one
 _lib = None
 
 if not os.path.exists(HEADER_PATH):
@@ -57,6 +58,10 @@ if not os.path.exists(CLASSIFIER_HEADER_PATH):
     raise RuntimeError(f"{CLASSIFIER_HEADER_PATH} is missing: ocrl_amd derives its binding of libocrl_hip.so from the header and runs from the source tree.")
 with open(CLASSIFIER_HEADER_PATH) as _f:
     ABI_CLASSIFIER = _abi.read(_f.read())               # no struct of its own: the head's descriptor is ocrl_hip_dqn.h's QnetDesc, passed with byref()
+if not os.path.exists(IODINE_HEADER_PATH):
+    raise RuntimeError(f"{IODINE_HEADER_PATH} is missing: ocrl_amd derives its binding of libocrl_hip.so from the header and runs from the source tree.")
+with open(IODINE_HEADER_PATH) as _f:
+    ABI_IODINE = _abi.read(_f.read())                   # no struct: every entry takes plain pointers and integers
 
 
 def flat_segments(segs):
@@ -147,7 +152,7 @@ def lib():
     # when it was loaded before torch)
     import torch  # noqa: F401
     L = ctypes.CDLL(LIB_PATH)
-    for abi in (ABI, ABI_DQN, ABI_ROLLOUT, ABI_REPLAY, ABI_C51, ABI_NOISY, ABI_CLASSIFIER):
+    for abi in (ABI, ABI_DQN, ABI_ROLLOUT, ABI_REPLAY, ABI_C51, ABI_NOISY, ABI_CLASSIFIER, ABI_IODINE):
         for name, (restype, argtypes) in abi.functions.items():
             f = getattr(L, name)
             f.argtypes = argtypes

@@ -425,8 +425,9 @@ int bc_c4_wgrad_blocks(int Bn, int S) {
     const int nt = cdiv(S, BT_W) * cdiv(S, BT_H) * Bn;
     return nt < 1024 ? nt : 1024;
 }
-int bc_c4_wgrad_launch(const float* X, const float* dY, float* part, int Bn, int S, hipStream_t st) {
-    if (sw::process<sw::OCRL_BC_WGRAD>() != 1) {       // 1: the VALU form
+// form: 0 = as the process switch decides (OCRL_BC_WGRAD=1: the VALU form), 1 = the VALU form, 2 = the MFMA form
+int bc_c4_wgrad_launch(const float* X, const float* dY, float* part, int Bn, int S, hipStream_t st, int form) {
+    if (form == 2 || (form == 0 && sw::process<sw::OCRL_BC_WGRAD>() != 1)) {
         hipLaunchKernelGGL(bc_c4_wgrad_mfma_kernel, dim3(bc_c4_wgrad_blocks(Bn, S)), dim3(256), 0, st, X, dY, part, Bn, S);
         OCRL_CHECK_LAUNCH("bc_c4_wgrad_mfma");
         return 0;

@@ -635,20 +635,21 @@ int io_latent_launch(const float* mu, const float* ls, const float* eps, const f
     OCRL_CHECK_LAUNCH("io_latent");
     return 0;
 }
-int io_im2col_launch(const float* x, float* col, long long Bn, int C, int Hi, int Wi, int ldc, hipStream_t st) {
+// force_generic: the 64-bit-index kernel whatever the pointers and ldc allow (the unit tests reach both forms by name)
+int io_im2col_launch(const float* x, float* col, long long Bn, int C, int Hi, int Wi, int ldc, hipStream_t st, int force_generic) {
     const int Ho = (Hi - 1) / 2 + 1, Wo = (Wi - 1) / 2 + 1;
     const long long rows = Bn * Ho * Wo;
-    if ((ldc & 3) == 0 && (((uintptr_t)col) & 15) == 0 && (((uintptr_t)x) & 15) == 0 && Ho <= 65535 && Bn <= 65535)
+    if (!force_generic && (ldc & 3) == 0 && (((uintptr_t)col) & 15) == 0 && (((uintptr_t)x) & 15) == 0 && Ho <= 65535 && Bn <= 65535)
         hipLaunchKernelGGL(io_im2col4_kernel, dim3((unsigned)((Wo * (ldc >> 2) + 255) / 256), (unsigned)Ho, (unsigned)Bn), dim3(256), 0, st, x, col, C, Hi, Wi, Ho, Wo, ldc);
     else
         hipLaunchKernelGGL(io_im2col_kernel, IO_GRID(rows * ldc), 0, st, x, col, rows, C, Hi, Wi, Ho, Wo, ldc);
     OCRL_CHECK_LAUNCH("io_im2col");
     return 0;
 }
-int io_col2im_launch(const float* dcol, const float* act, float* dx, long long Bn, int C, int Hi, int Wi, int ldc, hipStream_t st) {
+int io_col2im_launch(const float* dcol, const float* act, float* dx, long long Bn, int C, int Hi, int Wi, int ldc, hipStream_t st, int force_generic) {
     const int Ho = (Hi - 1) / 2 + 1, Wo = (Wi - 1) / 2 + 1;
     const long long n = Bn * Hi * Wi * C;
-    if (Hi <= 65535 && Bn <= 65535)
+    if (!force_generic && Hi <= 65535 && Bn <= 65535)
         hipLaunchKernelGGL(io_col2im3_kernel, dim3((unsigned)((Wi * C + 255) / 256), (unsigned)Hi, (unsigned)Bn), dim3(256), 0, st, dcol, act, dx, C, Hi, Wi, Ho, Wo, ldc);
     else
         hipLaunchKernelGGL(io_col2im_kernel, IO_GRID(n), 0, st, dcol, act, dx, n, C, Hi, Wi, Ho, Wo, ldc);

@@ -555,7 +555,7 @@ int bc_c4_pack_launch(const float* W, float* Wk, float* Wb, int co_n, hipStream_
 int bc_c4_fwd_launch(const float* X, const float* Wk, const float* bias4, float* Y, int Bn, int S, hipStream_t st);
 int bc_c4_bwd_data_launch(const float* dY, const float* Wb, const float* act, float* dX, int Bn, int S, hipStream_t st, int elu = 0);
 int bc_c4_wgrad_blocks(int Bn, int S);
-int bc_c4_wgrad_launch(const float* X, const float* dY, float* part, int Bn, int S, hipStream_t st);
+int bc_c4_wgrad_launch(const float* X, const float* dY, float* part, int Bn, int S, hipStream_t st, int form = 0);
 int bc_mix_launch(const float* out4, const float* obs, float* recon, float* dout4, float* loss_out, int B, int K, int S, int C, float* ws,
                   size_t ws_floats, hipStream_t st);
 
@@ -569,8 +569,9 @@ int io_enc_norm_launch(float* enc, const float* st1, float* st2, long long BK, i
 int io_elbo_bwd_launch(const float* out4, const float* obs, const float* denc, int B, int K, int S, float sigma, float cw, float* dout4, hipStream_t st);
 int io_latent_launch(const float* mu, const float* ls, const float* eps, const float* ds, float* latent, long long BK, int L, float beta, int layer_norm,
                      int ld, hipStream_t st);
-int io_im2col_launch(const float* x, float* col, long long Bn, int C, int Hi, int Wi, int ldc, hipStream_t st);
-int io_col2im_launch(const float* dcol, const float* act, float* dx, long long Bn, int C, int Hi, int Wi, int ldc, hipStream_t st);
+int io_im2col_launch(const float* x, float* col, long long Bn, int C, int Hi, int Wi, int ldc, hipStream_t st, int force_generic = 0);
+int io_col2im_launch(const float* dcol, const float* act, float* dx, long long Bn, int C, int Hi, int Wi, int ldc, hipStream_t st,
+                     int force_generic = 0);
 int io_refw_pack_launch(const float* W, float* Wp, int C, int ldc, hipStream_t st);
 int io_refw_unpack_launch(const float* dWp, float* dW, int C, int ldc, hipStream_t st);
 int io_pool_launch(const float* r, float* pool, long long BK, int n, hipStream_t st);

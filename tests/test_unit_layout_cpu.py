@@ -85,6 +85,14 @@ TABLE = [
     ('mae', (2, 16, 4, 64, 2, 2, 32, 1, 2, 0, 0), 33655552),
     ('mae', (2, 16, 4, 64, 2, 2, 32, 1, 2, 4, 1), 33614208),
     ('probe_match', (16, 4), 96),
+    # the IODINE / broadcast-decoder kernel entries (include/ocrl_hip_iodine.h), newer than that commit: the launchers' own scratch rules
+    # (66 floats per 256-pixel block of the ELBO, one float per sampled element, the two packed 64 -> 4 weight tensors, 1024 loss partials)
+    ('iodine_elbo', (2, 3, 32), 528),
+    ('iodine_elbo', (1, 16, 16), 66),
+    ('iodine_elbo', (1, 3, 48), 594),
+    ('iodine_sample', (3077,), 3077),
+    ('bcdec_c4', (), 4608),
+    ('bcdec_mix', (), 1024),
 ]
 
 
