@@ -1,4 +1,4 @@
-"""ctypes binding of libocrl_hip.so, derived from include/ocrl_hip.h, include/ocrl_hip_dqn.h, include/ocrl_hip_rollout.h, include/ocrl_hip_replay.h, include/ocrl_hip_c51.h, include/ocrl_hip_noisy.h, include/ocrl_hip_classifier.h and include/ocrl_hip_iodine.h (_abi.py reads them: the struct classes, the constants and every
+"""ctypes binding of libocrl_hip.so, derived from include/ocrl_hip.h, include/ocrl_hip_dqn.h, include/ocrl_hip_rollout.h, include/ocrl_hip_replay.h, include/ocrl_hip_c51.h, include/ocrl_hip_noisy.h, include/ocrl_hip_classifier.h, include/ocrl_hip_iodine.h and include/ocrl_hip_qr.h (_abi.py reads them: the struct classes, the constants and every
 entry point's argtypes / restype come from the header's own declarations).  Fails loudly when the library is not built."""
 import ctypes
 import os
@@ -16,6 +16,7 @@ C51_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "ocrl_hip_c51.h")   
 NOISY_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "ocrl_hip_noisy.h")      # DQN's noisy linear layers: a sixth one
 CLASSIFIER_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "ocrl_hip_classifier.h")      # the MLP classifier's step: a seventh one
 IODINE_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "ocrl_hip_iodine.h")      # the IODINE / broadcast-decoder kernels one by one: an eighth one
+QR_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "ocrl_hip_qr.h")      # DQN's quantile head: a ninth one
 _lib = None
 
 if not os.path.exists(HEADER_PATH):
@@ -62,6 +63,11 @@ if not os.path.exists(IODINE_HEADER_PATH):
     raise RuntimeError(f"{IODINE_HEADER_PATH} is missing: ocrl_amd derives its binding of libocrl_hip.so from the header and runs from the source tree.")
 with open(IODINE_HEADER_PATH) as _f:
     ABI_IODINE = _abi.read(_f.read())                   # no struct: every entry takes plain pointers and integers
+if not os.path.exists(QR_HEADER_PATH):
+    raise RuntimeError(f"{QR_HEADER_PATH} is missing: ocrl_amd derives its binding of libocrl_hip.so from the header and runs from the source tree.")
+with open(QR_HEADER_PATH) as _f:
+    ABI_QR = _abi.read(_f.read())                       # a struct of its own: the quantile head's descriptor
+QrDesc = ABI_QR.structs["ocrl_qr_desc"]
 
 
 def flat_segments(segs):
@@ -98,6 +104,16 @@ def c51_desc(B, F, A, Z, dims, acts, dueling=False):
     if len(dims) > len(C51Desc().dims) or len(acts) != len(dims):
         raise ValueError(f"ocrl_amd: at most {len(C51Desc().dims)} hidden layers, one activation code each (got {len(dims)}, {len(acts)})")
     d = C51Desc(B=B, F=F, A=A, Z=Z, n=len(dims), dueling=int(bool(dueling)))
+    for l, (w, a) in enumerate(zip(dims, acts)):
+        d.dims[l], d.acts[l] = int(w), int(a)
+    return d
+
+
+def qr_desc(B, F, A, N, dims, acts, dueling=False):
+    """QrDesc of a quantile head: N quantile values per action, dims / acts as qnet_desc takes them, dueling = the value Linear beside the advantages"""
+    if len(dims) > len(QrDesc().dims) or len(acts) != len(dims):
+        raise ValueError(f"ocrl_amd: at most {len(QrDesc().dims)} hidden layers, one activation code each (got {len(dims)}, {len(acts)})")
+    d = QrDesc(B=B, F=F, A=A, N=N, n=len(dims), dueling=int(bool(dueling)))
     for l, (w, a) in enumerate(zip(dims, acts)):
         d.dims[l], d.acts[l] = int(w), int(a)
     return d
@@ -152,14 +168,14 @@ def lib():
     # when it was loaded before torch)
     import torch  # noqa: F401
     L = ctypes.CDLL(LIB_PATH)
-    for abi in (ABI, ABI_DQN, ABI_ROLLOUT, ABI_REPLAY, ABI_C51, ABI_NOISY, ABI_CLASSIFIER, ABI_IODINE):
+    for abi in (ABI, ABI_DQN, ABI_ROLLOUT, ABI_REPLAY, ABI_C51, ABI_NOISY, ABI_CLASSIFIER, ABI_IODINE, ABI_QR):
         for name, (restype, argtypes) in abi.functions.items():
             f = getattr(L, name)
             f.argtypes = argtypes
             if restype is not ctypes.c_int:     # ctypes' default
                 f.restype = restype
-    for name, cls in {**ABI.structs, **ABI_DQN.structs, **ABI_C51.structs, **ABI_NOISY.structs}.items():        # every struct whose size the library reports
-        if name + "_size" in {**ABI.functions, **ABI_DQN.functions, **ABI_C51.functions, **ABI_NOISY.functions} and getattr(L, name + "_size")() != ctypes.sizeof(cls):
+    for name, cls in {**ABI.structs, **ABI_DQN.structs, **ABI_C51.structs, **ABI_NOISY.structs, **ABI_QR.structs}.items():        # every struct whose size the library reports
+        if name + "_size" in {**ABI.functions, **ABI_DQN.functions, **ABI_C51.functions, **ABI_NOISY.functions, **ABI_QR.functions} and getattr(L, name + "_size")() != ctypes.sizeof(cls):
             raise RuntimeError(f"libocrl_hip.so: {name} is {getattr(L, name + '_size')()} bytes, this binding's {cls.__name__} {ctypes.sizeof(cls)}")
     if L.ocrl_abi_version() != CONSTANTS["OCRL_ABI_VERSION"]:
         raise RuntimeError(f"libocrl_hip.so ABI version mismatch: the library is {L.ocrl_abi_version()}, include/ocrl_hip.h {CONSTANTS['OCRL_ABI_VERSION']}")

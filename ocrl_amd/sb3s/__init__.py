@@ -5,7 +5,8 @@ from .dqn import DQN, DQNPolicy, QNetwork, dqn_loss
 from .noisy import NoisyLinear
 from .ocr_extractor import OCRExtractor
 from .ppo import PPO, RolloutBuffer
+from .qr import QuantileQNetwork, qr_loss
 from .replay import ReplayBuffer
 
 __all__ = ["OCRExtractor", "CustomNetwork", "CustomActorCriticPolicy", "ppo_loss", "a2c_loss", "compute_gae", "PPO", "A2C", "RolloutBuffer",
-           "DQN", "DQNPolicy", "QNetwork", "dqn_loss", "ReplayBuffer", "CategoricalQNetwork", "c51_loss", "NoisyLinear"]
+           "DQN", "DQNPolicy", "QNetwork", "dqn_loss", "ReplayBuffer", "CategoricalQNetwork", "c51_loss", "NoisyLinear", "QuantileQNetwork", "qr_loss"]
