@@ -1,4 +1,4 @@
-"""ctypes binding of libocrl_hip.so, derived from include/ocrl_hip.h, include/ocrl_hip_dqn.h, include/ocrl_hip_rollout.h, include/ocrl_hip_replay.h, include/ocrl_hip_c51.h, include/ocrl_hip_noisy.h, include/ocrl_hip_classifier.h, include/ocrl_hip_iodine.h, include/ocrl_hip_qr.h and include/ocrl_hip_slate_kernels.h (_abi.py reads them: the struct classes, the constants and every
+"""ctypes binding of libocrl_hip.so, derived from include/ocrl_hip.h, include/ocrl_hip_dqn.h, include/ocrl_hip_rollout.h, include/ocrl_hip_replay.h, include/ocrl_hip_c51.h, include/ocrl_hip_noisy.h, include/ocrl_hip_classifier.h, include/ocrl_hip_iodine.h, include/ocrl_hip_qr.h, include/ocrl_hip_slate_kernels.h and include/ocrl_hip_vit_kernels.h (_abi.py reads them: the struct classes, the constants and every
 entry point's argtypes / restype come from the header's own declarations).  Fails loudly when the library is not built."""
 import ctypes
 import os
@@ -18,6 +18,7 @@ CLASSIFIER_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "ocrl_hip_cla
 IODINE_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "ocrl_hip_iodine.h")      # the IODINE / broadcast-decoder kernels one by one: an eighth one
 QR_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "ocrl_hip_qr.h")      # DQN's quantile head: a ninth one
 SLATE_KERNELS_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "ocrl_hip_slate_kernels.h")      # the SLATE token-path and helper kernels one by one: a tenth one
+VIT_KERNELS_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "ocrl_hip_vit_kernels.h")      # the pooling-Transformer and MAE kernels one by one: an eleventh one
 _lib = None
 
 if not os.path.exists(HEADER_PATH):
@@ -73,6 +74,10 @@ if not os.path.exists(SLATE_KERNELS_HEADER_PATH):
     raise RuntimeError(f"{SLATE_KERNELS_HEADER_PATH} is missing: ocrl_amd derives its binding of libocrl_hip.so from the header and runs from the source tree.")
 with open(SLATE_KERNELS_HEADER_PATH) as _f:
     ABI_SLATE_KERNELS = _abi.read(_f.read())            # no struct: every entry takes plain pointers and integers
+if not os.path.exists(VIT_KERNELS_HEADER_PATH):
+    raise RuntimeError(f"{VIT_KERNELS_HEADER_PATH} is missing: ocrl_amd derives its binding of libocrl_hip.so from the header and runs from the source tree.")
+with open(VIT_KERNELS_HEADER_PATH) as _f:
+    ABI_VIT_KERNELS = _abi.read(_f.read())              # no struct: every entry takes plain pointers and integers
 
 
 def flat_segments(segs):
@@ -173,7 +178,7 @@ def lib():
     # when it was loaded before torch)
     import torch  # noqa: F401
     L = ctypes.CDLL(LIB_PATH)
-    for abi in (ABI, ABI_DQN, ABI_ROLLOUT, ABI_REPLAY, ABI_C51, ABI_NOISY, ABI_CLASSIFIER, ABI_IODINE, ABI_QR, ABI_SLATE_KERNELS):
+    for abi in (ABI, ABI_DQN, ABI_ROLLOUT, ABI_REPLAY, ABI_C51, ABI_NOISY, ABI_CLASSIFIER, ABI_IODINE, ABI_QR, ABI_SLATE_KERNELS, ABI_VIT_KERNELS):
         for name, (restype, argtypes) in abi.functions.items():
             f = getattr(L, name)
             f.argtypes = argtypes

@@ -99,6 +99,11 @@ int pool_embed_launch(const float* lin, const float* cls, const float* pos, floa
 int pool_rows_launch(const float* in, float* out, int B, int K, int d, int mode, hipStream_t st);
 int pool_attn_launch(const float* qkv, float* P, float* O, const float* dO, float* dqkv, int B, int S, int d, int h, float p, unsigned long long seed,
                      unsigned site, int backward, hipStream_t st);
+// host only: every shape limit of pool_attn in one direction (0 = runs; else the reason is the error text), its LDS request, and
+// whether the short path runs (K slots of width Din, d_model, nhead) in both directions
+int pool_attn_check(int B, int S, int d, int h, int backward);
+size_t pool_attn_lds_bytes(int S, int d, int h, int backward);
+int pool_short_check(int K, int Din, int d, int h);
 
 // ------------------------------------------------------------------ pool_long.hip (long token sequences: include/ocrl_hip.h ocrl_pool_transformer_long_*)
 int pool_cols_launch(const float* src, int lds, float* dst, int ldd, long long rows, int ncols, int ncopy, hipStream_t st);
@@ -235,7 +240,7 @@ int vae_recon_nchw_launch(const float* r4, float* out, int B, int C, int HW, hip
 int mae_rank_launch(const float* noise, int* restore, int* keep, float* mask, int* restore_out, float* mask_out, int B, int L, int len_keep,
                     hipStream_t st);
 // out [B n, 3 p p]: patch ids[b, i] (null: i) of obs [B, 3, S, S] in (c, ph, pw) order
-int mae_patch_gather_launch(const float* obs, const int* ids, float* out, int B, int n, int S, int p, hipStream_t st);
+int mae_patch_gather_launch(const float* obs, const int* ids, float* out, int B, int n, int S, int p, hipStream_t st, int force_scalar = 0);
 // x0 [B, n + 1, D]: row 0 = cls + pos[0], row 1 + i = embed[b, i] + pos[1 + ids[b, i]] (null: i); backward: dembed [B n, D], dcls [D]
 int mae_tokens_fwd_launch(const float* embed, const float* cls, const float* pos, const int* ids, float* x0, int B, int n, int D, hipStream_t st);
 int mae_tokens_bwd_launch(const float* dx0, float* dembed, float* dcls, int B, int n, int D, hipStream_t st);

@@ -175,17 +175,19 @@ __global__ __launch_bounds__(256) void mae_ln_fwd_kernel(const float* __restrict
     const int lane = threadIdx.x & 63;
     if (row >= R) return;
     const float4* xr = reinterpret_cast<const float4*>(x) + row * F4;
-    const float inv = 1.f / (4.f * F4);
+    // the sums are divided by F, not multiplied by a rounded 1 / F: a row whose sum is exact (a constant row) then has its exact mean;
+    // one ulp of the mean, magnified by rstd <= eps^-1/2, was 1e-4 of y at F = 252
+    const float nF = 4.f * F4;
     float s = 0.f;
     for (int c = lane; c < F4; c += 64) { const float4 v = xr[c]; s += (v.x + v.y) + (v.z + v.w); }
-    const float mu = wave_sum(s) * inv;
+    const float mu = wave_sum(s) / nF;
     float q = 0.f;
     for (int c = lane; c < F4; c += 64) {
         const float4 v = xr[c];
         const float a = v.x - mu, b = v.y - mu, cc = v.z - mu, d = v.w - mu;
         q += (a * a + b * b) + (cc * cc + d * d);
     }
-    const float rs = rsqrtf(wave_sum(q) * inv + eps);
+    const float rs = rsqrtf(wave_sum(q) / nF + eps);
     float4* yr = reinterpret_cast<float4*>(y) + row * F4;
     for (int c = lane; c < F4; c += 64) {
         const float4 v = xr[c], gg = reinterpret_cast<const float4*>(g)[c], bb = reinterpret_cast<const float4*>(bta)[c];
@@ -297,9 +299,9 @@ int mae_rank_launch(const float* noise, int* restore, int* keep, float* mask, in
     return 0;
 }
 
-int mae_patch_gather_launch(const float* obs, const int* ids, float* out, int B, int n, int S, int p, hipStream_t st) {
+int mae_patch_gather_launch(const float* obs, const int* ids, float* out, int B, int n, int S, int p, hipStream_t st, int force_scalar) {
     OCRL_REQUIRE(p >= 1 && S % p == 0 && n >= 1 && n <= (S / p) * (S / p), "mae_patch_gather: bad shape (S %d, patch %d, n %d)", S, p, n);
-    if (p % 4 == 0 && aligned16(obs, out)) {
+    if (!force_scalar && p % 4 == 0 && aligned16(obs, out)) {
         const long long total = (long long)B * n * 3 * p * (p / 4);
         hipLaunchKernelGGL(mae_patch_gather_kernel<4>, GRID1D(total), 0, st, obs, ids, out, total, n, S, p);
     } else {

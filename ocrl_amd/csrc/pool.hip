@@ -59,6 +59,7 @@ int pool_rows_launch(const float* in, float* out, int B, int K, int d, int mode,
 
 #define PA_MAXS 32
 #define PA_T 256
+#define PA_MAX_LDS (160 * 1024)
 __device__ __forceinline__ bool pa_keep(unsigned long long seed, unsigned site, unsigned long long idx, uint32_t thr) {
     return rng_keep(rng_bits4(seed, site, idx >> 2), (int)(idx & 3), thr);
 }
@@ -195,18 +196,41 @@ __global__ __launch_bounds__(PA_T) void pool_attn_bwd_kernel(const float* __rest
     }
 }
 
+// The LDS request of one direction at S tokens: the qkv rows, and for the backward dO, dS and the dropped P as well.
+size_t pool_attn_lds_bytes(int S, int d, int h, int backward) {
+    return backward ? ((size_t)S * 4 * d + 2 * (size_t)h * S * S) * 4 : (size_t)S * 3 * d * 4;
+}
+// Whether pool_attn runs this shape in the given direction; the reason is the error text.  Every limit of the two kernels is here and
+// nowhere else: pool_attn_launch and the admissibility rule of the short path (pool_short_check) both ask it.
+int pool_attn_check(int B, int S, int d, int h, int backward) {
+    OCRL_REQUIRE(B > 0 && S >= 1 && S <= PA_MAXS, "pool_attn: 1 <= tokens <= %d supported (got %d)", PA_MAXS, S);
+    OCRL_REQUIRE(h >= 1 && d >= 1 && d % h == 0, "pool_attn: d_model %d not divisible by nhead %d", d, h);
+    const int hd = d / h;
+    OCRL_REQUIRE(hd == 8 || hd == 16 || hd == 32 || hd == 64, "pool_attn: head size %d not supported (8, 16, 32, 64)", hd);
+    const size_t smem = pool_attn_lds_bytes(S, d, h, backward);
+    OCRL_REQUIRE(smem <= PA_MAX_LDS, "pool_attn %s: LDS request %zu too large (d_model %d, nhead %d, %d tokens; limit %d)", backward ? "bwd" : "fwd", smem,
+                 d, h, S, PA_MAX_LDS);
+    return 0;
+}
+// Whether the short path (ocrl_pool_transformer_fwd / _bwd) runs K slots of width Din at (d_model, nhead) in BOTH directions.
+int pool_short_check(int K, int Din, int d, int h) {
+    OCRL_REQUIRE(K >= 1 && K + 1 <= PA_MAXS, "pool_transformer: 1 <= num_slots <= 31 (got %d)", K);
+    OCRL_REQUIRE(Din >= 4 && Din % 4 == 0 && d >= 64 && d % 64 == 0 && d <= 256,
+                 "pool_transformer: d_model must be a multiple of 64 <= 256, rep_dim/ff multiples of 4");
+    OCRL_REQUIRE(h >= 1 && d % h == 0, "pool_transformer: d_model %d not divisible by nhead %d", d, h);
+    RC(pool_attn_check(1, K + 1, d, h, 0));
+    return pool_attn_check(1, K + 1, d, h, 1);
+}
+
 template <int HD>
 static int pool_attn_k(const float* qkv, float* P, float* O, const float* dO, float* dqkv, int B, int S, int h, float p, unsigned long long seed, unsigned site,
                        int backward, hipStream_t st) {
     const int d = h * HD;
+    const size_t smem = pool_attn_lds_bytes(S, d, h, backward);
     if (backward) {
-        const size_t smem = ((size_t)S * 4 * d + 2 * (size_t)h * S * S) * 4;
-        OCRL_REQUIRE(smem <= 160 * 1024, "pool_attn bwd: LDS request %zu too large", smem);
         OCRL_HIP(hipFuncSetAttribute((const void*)pool_attn_bwd_kernel<HD>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
         hipLaunchKernelGGL((pool_attn_bwd_kernel<HD>), dim3(B), dim3(PA_T), smem, st, qkv, P, dO, dqkv, S, h, p, seed, site);
     } else {
-        const size_t smem = (size_t)S * 3 * d * 4;
-        OCRL_REQUIRE(smem <= 160 * 1024, "pool_attn fwd: LDS request %zu too large", smem);
         OCRL_HIP(hipFuncSetAttribute((const void*)pool_attn_fwd_kernel<HD>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
         hipLaunchKernelGGL((pool_attn_fwd_kernel<HD>), dim3(B), dim3(PA_T), smem, st, qkv, P, O, S, h, p, seed, site);
     }
@@ -215,14 +239,12 @@ static int pool_attn_k(const float* qkv, float* P, float* O, const float* dO, fl
 }
 int pool_attn_launch(const float* qkv, float* P, float* O, const float* dO, float* dqkv, int B, int S, int d, int h, float p, unsigned long long seed,
                      unsigned site, int backward, hipStream_t st) {
-    OCRL_REQUIRE(B > 0 && S >= 1 && S <= PA_MAXS, "pool_attn: 1 <= tokens <= %d supported (got %d)", PA_MAXS, S);
-    OCRL_REQUIRE(h >= 1 && d % h == 0, "pool_attn: d_model %d not divisible by nhead %d", d, h);
+    RC(pool_attn_check(B, S, d, h, backward));
     switch (d / h) {
         case 8: return pool_attn_k<8>(qkv, P, O, dO, dqkv, B, S, h, p, seed, site, backward, st);
         case 16: return pool_attn_k<16>(qkv, P, O, dO, dqkv, B, S, h, p, seed, site, backward, st);
         case 32: return pool_attn_k<32>(qkv, P, O, dO, dqkv, B, S, h, p, seed, site, backward, st);
         case 64: return pool_attn_k<64>(qkv, P, O, dO, dqkv, B, S, h, p, seed, site, backward, st);
     }
-    OCRL_REQUIRE(false, "pool_attn: head size %d not supported (8, 16, 32, 64)", d / h);
     return -1;
 }

@@ -54,10 +54,12 @@ Lay layout(int B, int K, int Din, int d, int h, int ff, int L) {
 }
 
 int check_dims(int B, int K, int Din, int d, int h, int ff, int L) {
-    OCRL_REQUIRE(B > 0 && K >= 1 && K + 1 <= 32, "pool_transformer: 1 <= num_slots <= 31 (got %d)", K);
+    OCRL_REQUIRE(B > 0, "pool_transformer: batch must be >= 1 (got %d)", B);
+    // slots, rep_dim, d_model, nhead, the head size and the LDS request of BOTH directions (pool.hip holds them once): a shape whose
+    // backward would be refused never runs its forward
+    RC(pool_short_check(K, Din, d, h));
     OCRL_REQUIRE(L >= 1 && L <= OCRL_POOL_MAX_LAYERS, "pool_transformer: 1 <= num_layers <= %d (got %d)", OCRL_POOL_MAX_LAYERS, L);
-    OCRL_REQUIRE(Din % 4 == 0 && ff % 4 == 0 && d % 64 == 0 && d <= 256, "pool_transformer: d_model must be a multiple of 64 <= 256, rep_dim/ff multiples of 4");
-    OCRL_REQUIRE(h >= 1 && d % h == 0, "pool_transformer: d_model %d not divisible by nhead %d", d, h);
+    OCRL_REQUIRE(ff >= 4 && ff % 4 == 0, "pool_transformer: d_model must be a multiple of 64 <= 256, rep_dim/ff multiples of 4");
     return 0;
 }
 

@@ -138,6 +138,14 @@ class _PoolFn(torch.autograd.Function):
         B, K, Din = slots.shape
         # token sets beyond the short path's limits (a CNN feature map: thousands of tokens, rep_dim = channels + 3) take the long path
         use_long = K + 1 > 32 or Din % 4 != 0
+        if not use_long and not L.ocrl_vit_pool_short_ok(K, Din, geom[0], geom[1]):
+            # the short path cannot run both directions of this shape (head size, or the LDS request of its backward): the long path
+            # takes it where it can (head size 16 / 32 / 48 / 64), and a shape neither runs is refused here, not at the first backward
+            reason = L.ocrl_last_error().decode()
+            if not L.ocrl_pool_transformer_long_ws_floats(B, K, Din, *geom):
+                raise ValueError(f"{_WHO}: shape not supported: batch {B}, {K} tokens of width {Din}, (d_model, nhead, dim_feedforward, num_layers) "
+                                 f"{tuple(geom)}: {reason}; {L.ocrl_last_error().decode()}")
+            use_long = True
         n = L.ocrl_pool_transformer_long_ws_floats(B, K, Din, *geom) if use_long else L.ocrl_pool_transformer_ws_floats(B, K, *geom)
         ws = _bridge.workspace(_WHO, n, dev, f"batch {B}, {K} tokens of width {Din}, (d_model, nhead, dim_feedforward, num_layers) {tuple(geom)}",
                                reason=None if use_long else "num_layers must be 1 .. 8")   # the short path's size function records no reason
