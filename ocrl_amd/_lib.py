@@ -1,4 +1,4 @@
-"""ctypes binding of libocrl_hip.so, derived from include/ocrl_hip.h, include/ocrl_hip_dqn.h, include/ocrl_hip_rollout.h, include/ocrl_hip_replay.h, include/ocrl_hip_c51.h, include/ocrl_hip_noisy.h, include/ocrl_hip_classifier.h, include/ocrl_hip_iodine.h, include/ocrl_hip_qr.h, include/ocrl_hip_slate_kernels.h and include/ocrl_hip_vit_kernels.h (_abi.py reads them: the struct classes, the constants and every
+"""ctypes binding of libocrl_hip.so, derived from include/ocrl_hip.h, include/ocrl_hip_dqn.h, include/ocrl_hip_rollout.h, include/ocrl_hip_replay.h, include/ocrl_hip_c51.h, include/ocrl_hip_noisy.h, include/ocrl_hip_classifier.h, include/ocrl_hip_iodine.h, include/ocrl_hip_qr.h, include/ocrl_hip_iqn.h, include/ocrl_hip_slate_kernels.h and include/ocrl_hip_vit_kernels.h (_abi.py reads them: the struct classes, the constants and every
 entry point's argtypes / restype come from the header's own declarations).  Fails loudly when the library is not built."""
 import ctypes
 import os
@@ -19,6 +19,7 @@ IODINE_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "ocrl_hip_iodine.
 QR_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "ocrl_hip_qr.h")      # DQN's quantile head: a ninth one
 SLATE_KERNELS_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "ocrl_hip_slate_kernels.h")      # the SLATE token-path and helper kernels one by one: a tenth one
 VIT_KERNELS_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "ocrl_hip_vit_kernels.h")      # the pooling-Transformer and MAE kernels one by one: an eleventh one
+IQN_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "ocrl_hip_iqn.h")      # DQN's implicit quantile head: a twelfth one
 _lib = None
 
 if not os.path.exists(HEADER_PATH):
@@ -78,6 +79,11 @@ if not os.path.exists(VIT_KERNELS_HEADER_PATH):
     raise RuntimeError(f"{VIT_KERNELS_HEADER_PATH} is missing: ocrl_amd derives its binding of libocrl_hip.so from the header and runs from the source tree.")
 with open(VIT_KERNELS_HEADER_PATH) as _f:
     ABI_VIT_KERNELS = _abi.read(_f.read())              # no struct: every entry takes plain pointers and integers
+if not os.path.exists(IQN_HEADER_PATH):
+    raise RuntimeError(f"{IQN_HEADER_PATH} is missing: ocrl_amd derives its binding of libocrl_hip.so from the header and runs from the source tree.")
+with open(IQN_HEADER_PATH) as _f:
+    ABI_IQN = _abi.read(_f.read())                      # a struct of its own: the implicit quantile head's descriptor
+IqnDesc = ABI_IQN.structs["ocrl_iqn_desc"]
 
 
 def flat_segments(segs):
@@ -124,6 +130,16 @@ def qr_desc(B, F, A, N, dims, acts, dueling=False):
     if len(dims) > len(QrDesc().dims) or len(acts) != len(dims):
         raise ValueError(f"ocrl_amd: at most {len(QrDesc().dims)} hidden layers, one activation code each (got {len(dims)}, {len(acts)})")
     d = QrDesc(B=B, F=F, A=A, N=N, n=len(dims), dueling=int(bool(dueling)))
+    for l, (w, a) in enumerate(zip(dims, acts)):
+        d.dims[l], d.acts[l] = int(w), int(a)
+    return d
+
+
+def iqn_desc(B, F, A, N, C, dims, acts):
+    """IqnDesc of an implicit quantile head: N sampled fractions per row of the call, C cosines, dims / acts as qnet_desc takes them"""
+    if len(dims) > len(IqnDesc().dims) or len(acts) != len(dims):
+        raise ValueError(f"ocrl_amd: at most {len(IqnDesc().dims)} hidden layers, one activation code each (got {len(dims)}, {len(acts)})")
+    d = IqnDesc(B=B, F=F, A=A, N=N, C=C, n=len(dims))
     for l, (w, a) in enumerate(zip(dims, acts)):
         d.dims[l], d.acts[l] = int(w), int(a)
     return d
@@ -178,14 +194,14 @@ def lib():
     # when it was loaded before torch)
     import torch  # noqa: F401
     L = ctypes.CDLL(LIB_PATH)
-    for abi in (ABI, ABI_DQN, ABI_ROLLOUT, ABI_REPLAY, ABI_C51, ABI_NOISY, ABI_CLASSIFIER, ABI_IODINE, ABI_QR, ABI_SLATE_KERNELS, ABI_VIT_KERNELS):
+    for abi in (ABI, ABI_DQN, ABI_ROLLOUT, ABI_REPLAY, ABI_C51, ABI_NOISY, ABI_CLASSIFIER, ABI_IODINE, ABI_QR, ABI_IQN, ABI_SLATE_KERNELS, ABI_VIT_KERNELS):
         for name, (restype, argtypes) in abi.functions.items():
             f = getattr(L, name)
             f.argtypes = argtypes
             if restype is not ctypes.c_int:     # ctypes' default
                 f.restype = restype
-    for name, cls in {**ABI.structs, **ABI_DQN.structs, **ABI_C51.structs, **ABI_NOISY.structs, **ABI_QR.structs}.items():        # every struct whose size the library reports
-        if name + "_size" in {**ABI.functions, **ABI_DQN.functions, **ABI_C51.functions, **ABI_NOISY.functions, **ABI_QR.functions} and getattr(L, name + "_size")() != ctypes.sizeof(cls):
+    for name, cls in {**ABI.structs, **ABI_DQN.structs, **ABI_C51.structs, **ABI_NOISY.structs, **ABI_QR.structs, **ABI_IQN.structs}.items():        # every struct whose size the library reports
+        if name + "_size" in {**ABI.functions, **ABI_DQN.functions, **ABI_C51.functions, **ABI_NOISY.functions, **ABI_QR.functions, **ABI_IQN.functions} and getattr(L, name + "_size")() != ctypes.sizeof(cls):
             raise RuntimeError(f"libocrl_hip.so: {name} is {getattr(L, name + '_size')()} bytes, this binding's {cls.__name__} {ctypes.sizeof(cls)}")
     if L.ocrl_abi_version() != CONSTANTS["OCRL_ABI_VERSION"]:
         raise RuntimeError(f"libocrl_hip.so ABI version mismatch: the library is {L.ocrl_abi_version()}, include/ocrl_hip.h {CONSTANTS['OCRL_ABI_VERSION']}")

@@ -12,7 +12,9 @@ n-step returns and proportional prioritized replay (Schaul et al. 2016) are keyw
 every Linear of the head a noisy layer (Fortunato et al. 2018) whose learned parameter noise replaces the epsilon-greedy coin (noisy.py,
 include/ocrl_hip_noisy.h; ``sb3=rainbow``, the six components of Hessel et al. 2018 together); off by default.  ``n_quantiles >= 1``
 replaces the scalar head by the quantile one (QR-DQN, Dabney et al. 2018: the return distribution without a support; qr.py,
-include/ocrl_hip_qr.h; ``sb3=qrdqn``), with ``dueling`` and ``noisy`` as for the categorical head; off by default.  Where this departs
+include/ocrl_hip_qr.h; ``sb3=qrdqn``), with ``dueling`` and ``noisy`` as for the categorical head; off by default.  ``n_tau_samples >= 1``
+replaces it by the implicit quantile one (IQN, Dabney et al. 2018: the quantile values as a function of sampled fractions; iqn.py,
+include/ocrl_hip_iqn.h; ``sb3=iqn``), with ``noisy`` but without ``dueling``; off by default.  Where this departs
 from stable-baselines3 and from those papers is listed in DESIGN.md §7."""
 import collections
 import copy
@@ -26,6 +28,7 @@ from torch import nn
 from .. import _bridge, _lib
 from ..ocrs.flat_module import FlatParamModule
 from .c51 import CategoricalQNetwork, c51_loss
+from .iqn import MAX_COS, MAX_TAU_SAMPLES, TRAIN_SEED_SALT, ImplicitQuantileQNetwork, draw_taus, iqn_loss
 from .custom_acnets import _n_actions
 from .on_policy import OnPolicyAlgorithm, _check_constant, _tensor
 from .qhead import DQN_SCALARS, QHead, coerce, scaled_grads
@@ -128,13 +131,16 @@ class DQNPolicy(nn.Module):
     (DQN builds it).  ``n_atoms >= 2`` makes the head a CategoricalQNetwork on the support [v_min, v_max] (``dueling``: with its value
     stream); ``q_values`` is then the expectation of the distribution and ``act`` is ``ocrl_c51_act``.  ``n_quantiles >= 1`` (with
     ``n_atoms`` 1) makes it a QuantileQNetwork (``dueling``: with its value stream); ``q_values`` is then the mean of the quantiles
-    (``ocrl_qr_fwd``) and ``act`` is ``ocrl_qr_act``.  ``noisy`` builds the head of noisy
+    (``ocrl_qr_fwd``) and ``act`` is ``ocrl_qr_act``.  ``n_tau_samples >= 1`` (with ``n_atoms`` 1, ``n_quantiles`` 0 and no ``dueling``)
+    makes it an ImplicitQuantileQNetwork of ``n_cos`` cosines; ``q_values`` is then the mean over the ``n_act_samples`` midpoint
+    fractions and ``act`` is ``ocrl_iqn_act`` on ``n_act_samples`` fractions per row, drawn from the policy's stream unless
+    ``deterministic``.  ``noisy`` builds the head of noisy
     layers (``noisy_sigma0``: the sigmas' start); which draw of the noise the head uses is set explicitly with ``set_noise`` and does not
     follow ``train()`` / ``eval()``."""
 
     def __init__(self, observation_space, action_space, lr_schedule=None, config=None, features_extractor=None, features_extractor_class=None,
                  features_extractor_kwargs=None, net_arch=(64, 64), activation="relu", n_atoms=1, v_min=0.0, v_max=2.0, dueling=False, noisy=False,
-                 noisy_sigma0=0.5, n_quantiles=0, **kwargs):
+                 noisy_sigma0=0.5, n_quantiles=0, n_tau_samples=0, n_act_samples=32, n_cos=64, **kwargs):
         super().__init__()
         self._config = config
         self.observation_space, self.action_space = observation_space, action_space
@@ -152,7 +158,17 @@ class DQNPolicy(nn.Module):
         if not self.noisy_sigma0 >= 0.0:
             raise ValueError(f"{_WHO}.DQNPolicy: noisy_sigma0 >= 0 (got {noisy_sigma0})")
         noise = dict(noisy=True, noisy_sigma0=self.noisy_sigma0) if self.noisy else {}
-        if self.n_quantiles != 0:
+        self.n_tau_samples, self.n_act_samples, self.n_cos = int(n_tau_samples), int(n_act_samples), int(n_cos)
+        if self.n_tau_samples != 0:
+            if self.n_tau_samples < 0 or self.n_atoms != 1 or self.n_quantiles != 0:
+                raise ValueError(f"{_WHO}.DQNPolicy: n_tau_samples >= 1 (the implicit quantile head) goes with n_atoms = 1 and n_quantiles = 0: "
+                                 f"one return distribution at a time (got n_tau_samples {n_tau_samples}, n_atoms {n_atoms}, n_quantiles "
+                                 f"{n_quantiles})")
+            if self.dueling:
+                raise ValueError(f"{_WHO}.DQNPolicy: dueling is not built for the implicit quantile head (got dueling=True with n_tau_samples "
+                                 f"{n_tau_samples})")
+            self.q_net = ImplicitQuantileQNetwork(self.features_dim, n, self.n_cos, self.n_act_samples, net_arch, activation, **noise)
+        elif self.n_quantiles != 0:
             if self.n_quantiles < 0 or self.n_atoms != 1:
                 raise ValueError(f"{_WHO}.DQNPolicy: n_quantiles >= 1 (the quantile head) goes with n_atoms = 1: one return distribution at a "
                                  f"time (got n_quantiles {n_quantiles}, n_atoms {n_atoms})")
@@ -215,6 +231,11 @@ class DQNPolicy(nn.Module):
         if row_offset is None:
             row_offset = self._sample_rows
             self._sample_rows += B
+        if self.n_tau_samples:
+            if not deterministic and self._sample_seed is None:
+                raise RuntimeError(f"{_WHO}.DQNPolicy.act: no stream for the sampled fractions: call policy.set_sampling(seed) or act "
+                                   "deterministically (the midpoint fractions)")
+            return (*self.q_net.act(x, self._sample_seed or 0, row_offset, eps, uniforms, deterministic=deterministic), None)
         if self.n_atoms >= 2 or self.n_quantiles:
             return (*self.q_net.act(x, self._sample_seed or 0, row_offset, eps, uniforms), None)
         dims, acts = self.q_net._layout()
@@ -275,19 +296,25 @@ class DQN:
     with ``seed``, the target network's with ``seed + 1``.
 
     ``n_quantiles >= 1``: the head learns ``n_quantiles`` quantile values per action with the quantile Huber loss at
-    ``huber_kappa`` (``_train_step_qr``); it takes ``n_atoms = 1`` and combines with every other argument here."""
+    ``huber_kappa`` (``_train_step_qr``); it takes ``n_atoms = 1`` and combines with every other argument here.
+
+    ``n_tau_samples >= 1``: the implicit quantile head (IQN).  An update evaluates the online network at ``n_tau_samples``
+    (N) sampled fractions per row and the target network at ``n_tau_prime_samples`` (N'; 0: N), acting takes ``n_act_samples`` (K),
+    the embedding has ``n_cos`` cosines and the loss is the quantile Huber loss at ``huber_kappa`` (``_train_step_iqn``).  It takes
+    ``n_atoms = 1``, ``n_quantiles = 0`` and no ``dueling`` and combines with double Q, n-step returns, prioritized replay and ``noisy``."""
     ALGO = "DQN"
     HYPER = ("learning_rate", "buffer_size", "learning_starts", "batch_size", "tau", "gamma", "train_freq", "gradient_steps",
              "target_update_interval", "exploration_fraction", "exploration_initial_eps", "exploration_final_eps", "max_grad_norm",
              "double_q", "n_step", "prioritized_replay", "prioritized_replay_alpha", "prioritized_replay_beta0", "prioritized_replay_beta_final",
-             "prioritized_replay_eps", "n_atoms", "v_min", "v_max", "dueling", "noisy", "noisy_sigma0", "n_quantiles", "huber_kappa")
+             "prioritized_replay_eps", "n_atoms", "v_min", "v_max", "dueling", "noisy", "noisy_sigma0", "n_quantiles", "huber_kappa",
+             "n_tau_samples", "n_tau_prime_samples", "n_act_samples", "n_cos")
 
     def __init__(self, policy, env, learning_rate=1e-4, buffer_size=1_000_000, learning_starts=50_000, batch_size=32, tau=1.0, gamma=0.99,
                  train_freq=4, gradient_steps=1, target_update_interval=10_000, exploration_fraction=0.1, exploration_initial_eps=1.0,
                  exploration_final_eps=0.05, max_grad_norm=10, seed=0, device="cuda", policy_kwargs=None, log_interval=100, double_q=False, n_step=1,
                  prioritized_replay=False, prioritized_replay_alpha=0.6, prioritized_replay_beta0=0.4, prioritized_replay_beta_final=1.0,
                  prioritized_replay_eps=1e-6, n_atoms=1, v_min=0.0, v_max=2.0, dueling=False, noisy=False, noisy_sigma0=0.5,
-                 n_quantiles=0, huber_kappa=1.0, **ignored_sb3_kwargs):
+                 n_quantiles=0, huber_kappa=1.0, n_tau_samples=0, n_tau_prime_samples=0, n_act_samples=32, n_cos=64, **ignored_sb3_kwargs):
         who = self._who = f"{_WHO}.{self.ALGO}"
         self.learning_rate = _check_constant(who, "learning_rate", learning_rate)
         if int(gradient_steps) < 1:
@@ -327,6 +354,22 @@ class DQN:
         if self.n_quantiles > 0 and self.n_atoms > 1:
             raise ValueError(f"{who}: n_quantiles > 0 and n_atoms > 1 name two return distributions: one at a time (got n_quantiles = "
                              f"{n_quantiles}, n_atoms = {n_atoms})")
+        self.n_tau_samples, self.n_tau_prime_samples = int(n_tau_samples), int(n_tau_prime_samples)
+        self.n_act_samples, self.n_cos = int(n_act_samples), int(n_cos)
+        if not 0 <= self.n_tau_samples <= MAX_TAU_SAMPLES:
+            raise ValueError(f"{who}: n_tau_samples is 0 (off) or lies in 1 .. {MAX_TAU_SAMPLES} (got {n_tau_samples})")
+        if not 0 <= self.n_tau_prime_samples <= MAX_TAU_SAMPLES:
+            raise ValueError(f"{who}: n_tau_prime_samples is 0 (as n_tau_samples) or lies in 1 .. {MAX_TAU_SAMPLES} (got {n_tau_prime_samples})")
+        if not 1 <= self.n_act_samples <= MAX_TAU_SAMPLES:
+            raise ValueError(f"{who}: n_act_samples lies in 1 .. {MAX_TAU_SAMPLES} (got {n_act_samples})")
+        if not (4 <= self.n_cos <= MAX_COS and self.n_cos % 4 == 0):
+            raise ValueError(f"{who}: n_cos is a multiple of 4 in 4 .. {MAX_COS} (got {n_cos})")
+        if self.n_tau_samples > 0 and (self.n_atoms > 1 or self.n_quantiles > 0):
+            raise ValueError(f"{who}: n_tau_samples > 0 with n_atoms > 1 or n_quantiles > 0 names two return distributions: one at a time (got "
+                             f"n_tau_samples = {n_tau_samples}, n_atoms = {n_atoms}, n_quantiles = {n_quantiles})")
+        if self.n_tau_samples > 0 and self.dueling:
+            raise ValueError(f"{who}: dueling is not built for the implicit quantile head: n_tau_samples = {n_tau_samples} takes dueling = False "
+                             "(got dueling=True)")
         if self.dueling and self.n_atoms == 1 and self.n_quantiles == 0:
             raise ValueError(f"{who}: dueling is built for the categorical head only: set n_atoms >= 2 (got dueling=True with n_atoms=1)")
         self.noisy, self.noisy_sigma0 = bool(noisy), float(noisy_sigma0)
@@ -347,6 +390,8 @@ class DQN:
             head = dict(n_atoms=self.n_atoms, v_min=self.v_min, v_max=self.v_max, dueling=self.dueling) if self.n_atoms > 1 else {}
             if self.n_quantiles > 0:
                 head = dict(n_quantiles=self.n_quantiles, dueling=self.dueling)
+            if self.n_tau_samples > 0:
+                head = dict(n_tau_samples=self.n_tau_samples, n_act_samples=self.n_act_samples, n_cos=self.n_cos)
             if self.noisy:
                 head.update(noisy=True, noisy_sigma0=self.noisy_sigma0)
             policy = policy(env.observation_space, env.action_space, None, **dict(policy_kwargs or {}, **head))
@@ -357,6 +402,11 @@ class DQN:
                              f"{self.n_atoms}, dueling = {self.dueling}")
         if policy.n_quantiles != self.n_quantiles:
             raise ValueError(f"{who}: the policy's head has n_quantiles = {policy.n_quantiles}; the arguments say n_quantiles = {self.n_quantiles}")
+        if bool(policy.n_tau_samples) != bool(self.n_tau_samples) or (self.n_tau_samples and (policy.n_act_samples, policy.n_cos) != (
+                self.n_act_samples, self.n_cos)):
+            raise ValueError(f"{who}: the policy's head has n_tau_samples = {policy.n_tau_samples}, n_act_samples = {policy.n_act_samples}, n_cos = "
+                             f"{policy.n_cos}; the arguments say n_tau_samples = {self.n_tau_samples}, n_act_samples = {self.n_act_samples}, n_cos = "
+                             f"{self.n_cos}")
         if self.n_atoms > 1 and (policy.q_net.v_min, policy.q_net.v_max) != (self.v_min, self.v_max):
             raise ValueError(f"{who}: the policy's head has v_min, v_max = {policy.q_net.v_min}, {policy.q_net.v_max}; the arguments say "
                              f"{self.v_min}, {self.v_max}")
@@ -597,18 +647,46 @@ class DQN:
         return qr_loss(self.policy, features, next_quantiles, next_q, batch.actions, batch.rewards, batch.dones, self.gamma, self.huber_kappa,
                        discounts=batch.discounts, weights=weights)
 
+    def _train_taus(self, k, n):
+        """draw k (0: the online network's N, 1: the target network's N', 2: the online network's N' under double_q) of this update:
+        [batch_size, n] fractions of the training stream, rows (3 n_updates + k) batch_size ..., which no acting row shares"""
+        return draw_taus(self.seed + TRAIN_SEED_SALT, (3 * self.n_updates + k) * self.batch_size, self.batch_size, n, self.device)
+
+    def _train_step_iqn(self, batch, weights):
+        """the implicit quantile head's part of ``train_step``: (loss, metrics, the rows' quantile losses, which take the
+        place of |TD error| in the priority store).  The target network gives the next observations' quantile values at N' fractions
+        of its own and their mean, the online network names the bootstrap action under double_q from N' fractions of its own, and
+        ``iqn_loss`` evaluates the online network at N fractions and does the rest."""
+        N, Np = self.n_tau_samples, self.n_tau_prime_samples or self.n_tau_samples
+        next_obs = self._obs(batch.next_observations)
+        with torch.no_grad():
+            next_quantiles, next_q = self.target.q_net.quantiles(self.target.extract_features(next_obs), self._train_taus(1, Np))
+        self._online_turn()
+        if self.double_q:
+            with torch.no_grad():
+                _, next_q = self.policy.q_net.quantiles(self.policy.extract_features(next_obs), self._train_taus(2, Np))
+        features = self.policy.extract_features(self._obs(batch.observations))
+        return iqn_loss(self.policy, features, self._train_taus(0, N), next_quantiles, next_q, batch.actions, batch.rewards, batch.dones, self.gamma,
+                        self.huber_kappa, discounts=batch.discounts, weights=weights)
+
     def train_step(self):
         """one gradient step: a batch from the replay buffer (``_draw_batch``), the head's loss against the target network
-        (``_train_step_dqn``, with n_atoms > 1 ``_train_step_c51``, with n_quantiles > 0 ``_train_step_qr``), the backward through the
+        (``_train_step_dqn``, with n_atoms > 1 ``_train_step_c51``, with n_quantiles > 0 ``_train_step_qr``, with n_tau_samples > 0
+        ``_train_step_iqn``), the backward through the
         extractor, clip + Adam, and under prioritized replay the rows' errors back into the priority store.  Nothing is read from the device: the scalars
         add up in ``_acc`` until a callback reads them."""
         batch, idx, weights = self._draw_batch()
         self._draw_train_noise()
-        step = self._train_step_qr if self.n_quantiles > 0 else self._train_step_c51 if self.n_atoms > 1 else self._train_step_dqn
+        step = self._train_step_iqn if self.n_tau_samples > 0 else self._train_step_qr if self.n_quantiles > 0 else self._train_step_c51 if self.n_atoms > 1 else self._train_step_dqn
         loss, m, row_err = step(batch, weights)
         loss.backward()
         self._adam_step()
         if self.prioritized_replay:
+            if self.n_tau_samples > 0:
+                # a transition drawn twice sits in two rows with fractions of their own, so its rows' losses differ, and the priority
+                # store takes one value per id (include/ocrl_hip_replay.h): the largest of them, whatever the rows' order
+                same = idx.unsqueeze(1) == idx.unsqueeze(0)
+                row_err = torch.where(same, row_err.unsqueeze(0), row_err.new_full((), -math.inf)).amax(dim=1)
             self.replay_buffer.update_priorities(idx, row_err, self.prioritized_replay_alpha, self.prioritized_replay_eps)
             self.last_weights = weights
         self.n_updates += 1
@@ -673,6 +751,10 @@ class DQN:
         if int(hyper.get("n_quantiles", 0)) != self.n_quantiles:
             raise ValueError(f"{self._who}.load: the checkpoint was written with n_quantiles = {int(hyper.get('n_quantiles', 0))}, this instance "
                              f"has n_quantiles = {self.n_quantiles}")
+        for k, dflt in (("n_tau_samples", 0), ("n_tau_prime_samples", 0), ("n_act_samples", 32), ("n_cos", 64)):
+            have, mine = int(hyper.get(k, dflt)), getattr(self, k)
+            if have != mine and (self.n_tau_samples > 0 or int(hyper.get("n_tau_samples", 0)) > 0):
+                raise ValueError(f"{self._who}.load: the checkpoint was written with {k} = {have}, this instance has {k} = {mine}")
         opt = ck["optimizer"]
         if "m" not in opt or opt["m"].shape != self.flat_m.shape:
             n = opt["m"].numel() if "m" in opt else "no"
@@ -698,4 +780,4 @@ class DQN:
         return self
 
 
-__all__ = ["DQN", "DQNPolicy", "QNetwork", "CategoricalQNetwork", "QuantileQNetwork", "dqn_loss", "c51_loss", "qr_loss", "exploration_schedule", "DQN_SCALARS"]
+__all__ = ["DQN", "DQNPolicy", "QNetwork", "CategoricalQNetwork", "QuantileQNetwork", "ImplicitQuantileQNetwork", "dqn_loss", "c51_loss", "qr_loss", "iqn_loss", "exploration_schedule", "DQN_SCALARS"]
