@@ -1,4 +1,4 @@
-"""ctypes binding of libocrl_hip.so, derived from include/ocrl_hip.h, include/ocrl_hip_dqn.h, include/ocrl_hip_rollout.h, include/ocrl_hip_replay.h, include/ocrl_hip_c51.h, include/ocrl_hip_noisy.h, include/ocrl_hip_classifier.h, include/ocrl_hip_iodine.h, include/ocrl_hip_qr.h, include/ocrl_hip_iqn.h, include/ocrl_hip_slate_kernels.h and include/ocrl_hip_vit_kernels.h (_abi.py reads them: the struct classes, the constants and every
+"""ctypes binding of libocrl_hip.so, derived from include/ocrl_hip.h, include/ocrl_hip_dqn.h, include/ocrl_hip_rollout.h, include/ocrl_hip_replay.h, include/ocrl_hip_c51.h, include/ocrl_hip_noisy.h, include/ocrl_hip_classifier.h, include/ocrl_hip_iodine.h, include/ocrl_hip_qr.h, include/ocrl_hip_iqn.h, include/ocrl_hip_munchausen.h, include/ocrl_hip_slate_kernels.h and include/ocrl_hip_vit_kernels.h (_abi.py reads them: the struct classes, the constants and every
 entry point's argtypes / restype come from the header's own declarations).  Fails loudly when the library is not built."""
 import ctypes
 import os
@@ -20,6 +20,7 @@ QR_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "ocrl_hip_qr.h")     
 SLATE_KERNELS_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "ocrl_hip_slate_kernels.h")      # the SLATE token-path and helper kernels one by one: a tenth one
 VIT_KERNELS_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "ocrl_hip_vit_kernels.h")      # the pooling-Transformer and MAE kernels one by one: an eleventh one
 IQN_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "ocrl_hip_iqn.h")      # DQN's implicit quantile head: a twelfth one
+MUNCHAUSEN_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "ocrl_hip_munchausen.h")      # DQN's Munchausen targets: a thirteenth one
 _lib = None
 
 if not os.path.exists(HEADER_PATH):
@@ -84,6 +85,10 @@ if not os.path.exists(IQN_HEADER_PATH):
 with open(IQN_HEADER_PATH) as _f:
     ABI_IQN = _abi.read(_f.read())                      # a struct of its own: the implicit quantile head's descriptor
 IqnDesc = ABI_IQN.structs["ocrl_iqn_desc"]
+if not os.path.exists(MUNCHAUSEN_HEADER_PATH):
+    raise RuntimeError(f"{MUNCHAUSEN_HEADER_PATH} is missing: ocrl_amd derives its binding of libocrl_hip.so from the header and runs from the source tree.")
+with open(MUNCHAUSEN_HEADER_PATH) as _f:
+    ABI_MUNCHAUSEN = _abi.read(_f.read())               # no struct: the one entry takes plain pointers and numbers
 
 
 def flat_segments(segs):
@@ -194,7 +199,7 @@ def lib():
     # when it was loaded before torch)
     import torch  # noqa: F401
     L = ctypes.CDLL(LIB_PATH)
-    for abi in (ABI, ABI_DQN, ABI_ROLLOUT, ABI_REPLAY, ABI_C51, ABI_NOISY, ABI_CLASSIFIER, ABI_IODINE, ABI_QR, ABI_IQN, ABI_SLATE_KERNELS, ABI_VIT_KERNELS):
+    for abi in (ABI, ABI_DQN, ABI_ROLLOUT, ABI_REPLAY, ABI_C51, ABI_NOISY, ABI_CLASSIFIER, ABI_IODINE, ABI_QR, ABI_IQN, ABI_MUNCHAUSEN, ABI_SLATE_KERNELS, ABI_VIT_KERNELS):
         for name, (restype, argtypes) in abi.functions.items():
             f = getattr(L, name)
             f.argtypes = argtypes

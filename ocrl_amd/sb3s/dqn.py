@@ -14,7 +14,10 @@ include/ocrl_hip_noisy.h; ``sb3=rainbow``, the six components of Hessel et al. 2
 replaces the scalar head by the quantile one (QR-DQN, Dabney et al. 2018: the return distribution without a support; qr.py,
 include/ocrl_hip_qr.h; ``sb3=qrdqn``), with ``dueling`` and ``noisy`` as for the categorical head; off by default.  ``n_tau_samples >= 1``
 replaces it by the implicit quantile one (IQN, Dabney et al. 2018: the quantile values as a function of sampled fractions; iqn.py,
-include/ocrl_hip_iqn.h; ``sb3=iqn``), with ``noisy`` but without ``dueling``; off by default.  Where this departs
+include/ocrl_hip_iqn.h; ``sb3=iqn``), with ``noisy`` but without ``dueling``; off by default.  ``munchausen`` rewrites the rewards
+and the target network's values at the next observation in front of the scalar, quantile and implicit quantile heads' unchanged TD steps
+(Munchausen RL, Vieillard et al. 2020: the clipped log-policy bonus and the soft value of a soft-max policy; munchausen.py,
+include/ocrl_hip_munchausen.h; ``sb3=mdqn``, ``sb3=miqn``); off by default.  Where this departs
 from stable-baselines3 and from those papers is listed in DESIGN.md §7."""
 import collections
 import copy
@@ -29,6 +32,7 @@ from .. import _bridge, _lib
 from ..ocrs.flat_module import FlatParamModule
 from .c51 import CategoricalQNetwork, c51_loss
 from .iqn import MAX_COS, MAX_TAU_SAMPLES, TRAIN_SEED_SALT, ImplicitQuantileQNetwork, draw_taus, iqn_loss
+from .munchausen import check_munchausen, munchausen_targets
 from .custom_acnets import _n_actions
 from .on_policy import OnPolicyAlgorithm, _check_constant, _tensor
 from .qhead import DQN_SCALARS, QHead, coerce, scaled_grads
@@ -301,20 +305,28 @@ class DQN:
     ``n_tau_samples >= 1``: the implicit quantile head (IQN).  An update evaluates the online network at ``n_tau_samples``
     (N) sampled fractions per row and the target network at ``n_tau_prime_samples`` (N'; 0: N), acting takes ``n_act_samples`` (K),
     the embedding has ``n_cos`` cosines and the loss is the quantile Huber loss at ``huber_kappa`` (``_train_step_iqn``).  It takes
-    ``n_atoms = 1``, ``n_quantiles = 0`` and no ``dueling`` and combines with double Q, n-step returns, prioritized replay and ``noisy``."""
+    ``n_atoms = 1``, ``n_quantiles = 0`` and no ``dueling`` and combines with double Q, n-step returns, prioritized replay and ``noisy``.
+
+    ``munchausen=True``: Munchausen targets on the scalar, quantile and implicit quantile heads.  An update evaluates
+    the target network on the observations as well (one pass of 2 ``batch_size`` rows), ``munchausen_targets`` adds ``munchausen_alpha``
+    times the log-policy of the action taken, scaled by ``munchausen_tau`` and clipped to [``munchausen_clip``, 0], to the rewards and
+    puts the soft value of the soft-max policy at temperature ``munchausen_tau`` in place of the target network's values at the next
+    observations; the head's TD step then runs unchanged.  It takes ``n_atoms = 1`` and no ``double_q`` and combines with n-step
+    returns (the bonus is the first action's), prioritized replay, ``noisy`` and ``dueling`` on the quantile head; acting is unchanged."""
     ALGO = "DQN"
     HYPER = ("learning_rate", "buffer_size", "learning_starts", "batch_size", "tau", "gamma", "train_freq", "gradient_steps",
              "target_update_interval", "exploration_fraction", "exploration_initial_eps", "exploration_final_eps", "max_grad_norm",
              "double_q", "n_step", "prioritized_replay", "prioritized_replay_alpha", "prioritized_replay_beta0", "prioritized_replay_beta_final",
              "prioritized_replay_eps", "n_atoms", "v_min", "v_max", "dueling", "noisy", "noisy_sigma0", "n_quantiles", "huber_kappa",
-             "n_tau_samples", "n_tau_prime_samples", "n_act_samples", "n_cos")
+             "n_tau_samples", "n_tau_prime_samples", "n_act_samples", "n_cos", "munchausen", "munchausen_alpha", "munchausen_tau", "munchausen_clip")
 
     def __init__(self, policy, env, learning_rate=1e-4, buffer_size=1_000_000, learning_starts=50_000, batch_size=32, tau=1.0, gamma=0.99,
                  train_freq=4, gradient_steps=1, target_update_interval=10_000, exploration_fraction=0.1, exploration_initial_eps=1.0,
                  exploration_final_eps=0.05, max_grad_norm=10, seed=0, device="cuda", policy_kwargs=None, log_interval=100, double_q=False, n_step=1,
                  prioritized_replay=False, prioritized_replay_alpha=0.6, prioritized_replay_beta0=0.4, prioritized_replay_beta_final=1.0,
                  prioritized_replay_eps=1e-6, n_atoms=1, v_min=0.0, v_max=2.0, dueling=False, noisy=False, noisy_sigma0=0.5,
-                 n_quantiles=0, huber_kappa=1.0, n_tau_samples=0, n_tau_prime_samples=0, n_act_samples=32, n_cos=64, **ignored_sb3_kwargs):
+                 n_quantiles=0, huber_kappa=1.0, n_tau_samples=0, n_tau_prime_samples=0, n_act_samples=32, n_cos=64, munchausen=False,
+                 munchausen_alpha=0.9, munchausen_tau=0.03, munchausen_clip=-1.0, **ignored_sb3_kwargs):
         who = self._who = f"{_WHO}.{self.ALGO}"
         self.learning_rate = _check_constant(who, "learning_rate", learning_rate)
         if int(gradient_steps) < 1:
@@ -375,6 +387,15 @@ class DQN:
         self.noisy, self.noisy_sigma0 = bool(noisy), float(noisy_sigma0)
         if not self.noisy_sigma0 >= 0.0:
             raise ValueError(f"{who}: noisy_sigma0 >= 0 (got {noisy_sigma0})")
+        self.munchausen = bool(munchausen)
+        self.munchausen_alpha, self.munchausen_tau, self.munchausen_clip = float(munchausen_alpha), float(munchausen_tau), float(munchausen_clip)
+        check_munchausen(who, munchausen_alpha, munchausen_tau, munchausen_clip)
+        if self.munchausen and self.n_atoms > 1:
+            raise ValueError(f"{who}: munchausen with n_atoms > 1: the categorical projection of a policy mixture is not built (got "
+                             f"munchausen=True with n_atoms = {n_atoms})")
+        if self.munchausen and self.double_q:
+            raise ValueError(f"{who}: munchausen with double_q=True: the soft value of the target network's policy leaves no bootstrap action "
+                             "to pick (got munchausen=True with double_q=True)")
         self.buffer_size, self.learning_starts, self.batch_size = int(buffer_size), int(learning_starts), int(batch_size)
         self.tau, self.gamma = float(tau), float(gamma)
         self.train_freq, self.gradient_steps, self.target_update_interval = int(train_freq), int(gradient_steps), int(target_update_interval)
@@ -600,10 +621,31 @@ class DQN:
         self.policy.train()
         self.flat_g.zero_()
 
+    def _both_obs(self, batch):
+        """munchausen: the next observations, then the observations, as one batch of 2 batch_size rows for the target network (a row's
+        values do not depend on its position in the batch)"""
+        return self._obs(torch.cat([batch.next_observations, batch.observations]))
+
+    def _munchausen(self, batch, q2, quantiles2=None):
+        """munchausen: (rewards, next_q, next_quantiles) as the heads' losses take them, from the target network's values q2 [2 B, n]
+        (and quantile values [2 B, n, N']) on ``_both_obs``: one ``munchausen_targets`` launch"""
+        B = q2.shape[0] // 2
+        return munchausen_targets(q2[B:], q2[:B], batch.actions, batch.rewards, batch.dones, self.munchausen_alpha, self.munchausen_tau,
+                                  self.munchausen_clip, next_quantiles=None if quantiles2 is None else quantiles2[:B])
+
     def _train_step_dqn(self, batch, weights):
         """the scalar head's part of ``train_step``: (loss, metrics, the rows' |TD error| under prioritized replay).  The target network
         gives the next observations' Q, the online network names the bootstrap action under double_q; with neither that nor n_step > 1
         nor prioritized replay the step is ocrl_dqn_td_fwd_bwd's (``dqn_loss``)."""
+        if self.munchausen:
+            with torch.no_grad():
+                q2 = self.target.q_values(self._both_obs(batch))
+                rewards, next_q, _ = self._munchausen(batch, q2)
+            self._online_turn()
+            features = self.policy.extract_features(self._obs(batch.observations))
+            out = dqn_loss(self.policy, features, next_q, batch.actions, rewards, batch.dones, self.gamma, discounts=batch.discounts,
+                           weights=weights, return_abs_td=self.prioritized_replay)
+            return out if self.prioritized_replay else (*out, None)
         next_obs = self._obs(batch.next_observations)
         with torch.no_grad():
             next_q = self.target.q_values(next_obs)
@@ -636,6 +678,14 @@ class DQN:
         """the quantile head's part of ``train_step``: (loss, metrics, the rows' quantile losses, which take the place of
         |TD error| in the priority store).  The target network gives the next observations' quantiles, the online network names the
         bootstrap action under double_q, ``qr_loss`` does the rest."""
+        if self.munchausen:
+            with torch.no_grad():
+                quantiles2, q2 = self.target.q_net.quantiles(self.target.extract_features(self._both_obs(batch)))
+                rewards, next_q, next_quantiles = self._munchausen(batch, q2, quantiles2)
+            self._online_turn()
+            features = self.policy.extract_features(self._obs(batch.observations))
+            return qr_loss(self.policy, features, next_quantiles, next_q, batch.actions, rewards, batch.dones, self.gamma, self.huber_kappa,
+                           discounts=batch.discounts, weights=weights)
         next_obs = self._obs(batch.next_observations)
         with torch.no_grad():
             next_quantiles, next_q = self.target.q_net.quantiles(self.target.extract_features(next_obs))
@@ -648,7 +698,8 @@ class DQN:
                        discounts=batch.discounts, weights=weights)
 
     def _train_taus(self, k, n):
-        """draw k (0: the online network's N, 1: the target network's N', 2: the online network's N' under double_q) of this update:
+        """draw k (0: the online network's N, 1: the target network's N', 2: the online network's N' under double_q, or the target
+        network's N' at the observations under munchausen, which refuses double_q) of this update:
         [batch_size, n] fractions of the training stream, rows (3 n_updates + k) batch_size ..., which no acting row shares"""
         return draw_taus(self.seed + TRAIN_SEED_SALT, (3 * self.n_updates + k) * self.batch_size, self.batch_size, n, self.device)
 
@@ -658,6 +709,15 @@ class DQN:
         of its own and their mean, the online network names the bootstrap action under double_q from N' fractions of its own, and
         ``iqn_loss`` evaluates the online network at N fractions and does the rest."""
         N, Np = self.n_tau_samples, self.n_tau_prime_samples or self.n_tau_samples
+        if self.munchausen:
+            with torch.no_grad():
+                taus2 = torch.cat([self._train_taus(1, Np), self._train_taus(2, Np)])
+                quantiles2, q2 = self.target.q_net.quantiles(self.target.extract_features(self._both_obs(batch)), taus2)
+                rewards, next_q, next_quantiles = self._munchausen(batch, q2, quantiles2)
+            self._online_turn()
+            features = self.policy.extract_features(self._obs(batch.observations))
+            return iqn_loss(self.policy, features, self._train_taus(0, N), next_quantiles, next_q, batch.actions, rewards, batch.dones, self.gamma,
+                            self.huber_kappa, discounts=batch.discounts, weights=weights)
         next_obs = self._obs(batch.next_observations)
         with torch.no_grad():
             next_quantiles, next_q = self.target.q_net.quantiles(self.target.extract_features(next_obs), self._train_taus(1, Np))
@@ -755,6 +815,10 @@ class DQN:
             have, mine = int(hyper.get(k, dflt)), getattr(self, k)
             if have != mine and (self.n_tau_samples > 0 or int(hyper.get("n_tau_samples", 0)) > 0):
                 raise ValueError(f"{self._who}.load: the checkpoint was written with {k} = {have}, this instance has {k} = {mine}")
+        for k, dflt in (("munchausen", False), ("munchausen_alpha", 0.9), ("munchausen_tau", 0.03), ("munchausen_clip", -1.0)):
+            have, mine = type(dflt)(hyper.get(k, dflt)), getattr(self, k)
+            if have != mine and (self.munchausen or bool(hyper.get("munchausen", False))):
+                raise ValueError(f"{self._who}.load: the checkpoint was written with {k} = {have}, this instance has {k} = {mine}")
         opt = ck["optimizer"]
         if "m" not in opt or opt["m"].shape != self.flat_m.shape:
             n = opt["m"].numel() if "m" in opt else "no"
@@ -780,4 +844,4 @@ class DQN:
         return self
 
 
-__all__ = ["DQN", "DQNPolicy", "QNetwork", "CategoricalQNetwork", "QuantileQNetwork", "ImplicitQuantileQNetwork", "dqn_loss", "c51_loss", "qr_loss", "iqn_loss", "exploration_schedule", "DQN_SCALARS"]
+__all__ = ["DQN", "DQNPolicy", "QNetwork", "CategoricalQNetwork", "QuantileQNetwork", "ImplicitQuantileQNetwork", "dqn_loss", "c51_loss", "qr_loss", "iqn_loss", "munchausen_targets", "exploration_schedule", "DQN_SCALARS"]
