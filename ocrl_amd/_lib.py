@@ -1,4 +1,4 @@
-"""ctypes binding of libocrl_hip.so, derived from include/ocrl_hip.h, include/ocrl_hip_dqn.h, include/ocrl_hip_rollout.h, include/ocrl_hip_replay.h, include/ocrl_hip_c51.h, include/ocrl_hip_noisy.h, include/ocrl_hip_classifier.h, include/ocrl_hip_iodine.h, include/ocrl_hip_qr.h, include/ocrl_hip_iqn.h, include/ocrl_hip_munchausen.h, include/ocrl_hip_slate_kernels.h and include/ocrl_hip_vit_kernels.h (_abi.py reads them: the struct classes, the constants and every
+"""ctypes binding of libocrl_hip.so, derived from include/ocrl_hip.h, include/ocrl_hip_dqn.h, include/ocrl_hip_rollout.h, include/ocrl_hip_replay.h, include/ocrl_hip_c51.h, include/ocrl_hip_noisy.h, include/ocrl_hip_classifier.h, include/ocrl_hip_iodine.h, include/ocrl_hip_qr.h, include/ocrl_hip_iqn.h, include/ocrl_hip_munchausen.h, include/ocrl_hip_fqf.h, include/ocrl_hip_slate_kernels.h and include/ocrl_hip_vit_kernels.h (_abi.py reads them: the struct classes, the constants and every
 entry point's argtypes / restype come from the header's own declarations).  Fails loudly when the library is not built."""
 import ctypes
 import os
@@ -21,6 +21,7 @@ SLATE_KERNELS_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "ocrl_hip_
 VIT_KERNELS_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "ocrl_hip_vit_kernels.h")      # the pooling-Transformer and MAE kernels one by one: an eleventh one
 IQN_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "ocrl_hip_iqn.h")      # DQN's implicit quantile head: a twelfth one
 MUNCHAUSEN_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "ocrl_hip_munchausen.h")      # DQN's Munchausen targets: a thirteenth one
+FQF_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "ocrl_hip_fqf.h")      # DQN's fully parameterized quantile function: a fourteenth one
 _lib = None
 
 if not os.path.exists(HEADER_PATH):
@@ -89,6 +90,11 @@ if not os.path.exists(MUNCHAUSEN_HEADER_PATH):
     raise RuntimeError(f"{MUNCHAUSEN_HEADER_PATH} is missing: ocrl_amd derives its binding of libocrl_hip.so from the header and runs from the source tree.")
 with open(MUNCHAUSEN_HEADER_PATH) as _f:
     ABI_MUNCHAUSEN = _abi.read(_f.read())               # no struct: the one entry takes plain pointers and numbers
+if not os.path.exists(FQF_HEADER_PATH):
+    raise RuntimeError(f"{FQF_HEADER_PATH} is missing: ocrl_amd derives its binding of libocrl_hip.so from the header and runs from the source tree.")
+with open(FQF_HEADER_PATH) as _f:
+    ABI_FQF = _abi.read(_f.read())                      # a struct of its own: the implicit quantile head's descriptor, restated
+FqfDesc = ABI_FQF.structs["ocrl_fqf_desc"]
 
 
 def flat_segments(segs):
@@ -150,6 +156,16 @@ def iqn_desc(B, F, A, N, C, dims, acts):
     return d
 
 
+def fqf_desc(B, F, A, N, C, dims, acts):
+    """FqfDesc of ocrl_fqf_act: the implicit quantile head's descriptor (iqn_desc) with N proposed fractions per row"""
+    if len(dims) > len(FqfDesc().dims) or len(acts) != len(dims):
+        raise ValueError(f"ocrl_amd: at most {len(FqfDesc().dims)} hidden layers, one activation code each (got {len(dims)}, {len(acts)})")
+    d = FqfDesc(B=B, F=F, A=A, N=N, C=C, n=len(dims))
+    for l, (w, a) in enumerate(zip(dims, acts)):
+        d.dims[l], d.acts[l] = int(w), int(a)
+    return d
+
+
 def noisy_desc(layers):
     """NoisyDesc of a sequence of Linear layers: layers = (in, out) per layer"""
     layers = list(layers)
@@ -199,14 +215,14 @@ def lib():
     # when it was loaded before torch)
     import torch  # noqa: F401
     L = ctypes.CDLL(LIB_PATH)
-    for abi in (ABI, ABI_DQN, ABI_ROLLOUT, ABI_REPLAY, ABI_C51, ABI_NOISY, ABI_CLASSIFIER, ABI_IODINE, ABI_QR, ABI_IQN, ABI_MUNCHAUSEN, ABI_SLATE_KERNELS, ABI_VIT_KERNELS):
+    for abi in (ABI, ABI_DQN, ABI_ROLLOUT, ABI_REPLAY, ABI_C51, ABI_NOISY, ABI_CLASSIFIER, ABI_IODINE, ABI_QR, ABI_IQN, ABI_MUNCHAUSEN, ABI_FQF, ABI_SLATE_KERNELS, ABI_VIT_KERNELS):
         for name, (restype, argtypes) in abi.functions.items():
             f = getattr(L, name)
             f.argtypes = argtypes
             if restype is not ctypes.c_int:     # ctypes' default
                 f.restype = restype
-    for name, cls in {**ABI.structs, **ABI_DQN.structs, **ABI_C51.structs, **ABI_NOISY.structs, **ABI_QR.structs, **ABI_IQN.structs}.items():        # every struct whose size the library reports
-        if name + "_size" in {**ABI.functions, **ABI_DQN.functions, **ABI_C51.functions, **ABI_NOISY.functions, **ABI_QR.functions, **ABI_IQN.functions} and getattr(L, name + "_size")() != ctypes.sizeof(cls):
+    for name, cls in {**ABI.structs, **ABI_DQN.structs, **ABI_C51.structs, **ABI_NOISY.structs, **ABI_QR.structs, **ABI_IQN.structs, **ABI_FQF.structs}.items():        # every struct whose size the library reports
+        if name + "_size" in {**ABI.functions, **ABI_DQN.functions, **ABI_C51.functions, **ABI_NOISY.functions, **ABI_QR.functions, **ABI_IQN.functions, **ABI_FQF.functions} and getattr(L, name + "_size")() != ctypes.sizeof(cls):
             raise RuntimeError(f"libocrl_hip.so: {name} is {getattr(L, name + '_size')()} bytes, this binding's {cls.__name__} {ctypes.sizeof(cls)}")
     if L.ocrl_abi_version() != CONSTANTS["OCRL_ABI_VERSION"]:
         raise RuntimeError(f"libocrl_hip.so ABI version mismatch: the library is {L.ocrl_abi_version()}, include/ocrl_hip.h {CONSTANTS['OCRL_ABI_VERSION']}")

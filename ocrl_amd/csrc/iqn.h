@@ -40,5 +40,10 @@ struct IqnTdArgs {
 int iqn_taus_launch(unsigned long long seed, unsigned long long row_offset, int B, int N, float* out, hipStream_t st);
 int iqn_fwd_launch(const AcnetArgs& a, const IqnArgs& c, hipStream_t st);                           // the tiles, and with c.q the fold over s
 int iqn_act_launch(const AcnetArgs& a, const IqnArgs& c, const DqnActArgs& s, hipStream_t st);
+// ocrl_fqf_act (include/ocrl_hip_fqf.h): the act kernel with c.taus = the fractions' boundaries [Bb, N + 1]; iqn_fqf_act (iqn_unit.cpp)
+// checks the descriptor as ocrl_iqn_act does, under the caller's name, and launches it
+int iqn_act_fqf_launch(const AcnetArgs& a, const IqnArgs& c, const DqnActArgs& s, hipStream_t st);
+int iqn_fqf_act(const ocrl_iqn_desc* d, const char* who, const float* features, const float* const* w, const float* taus, const DqnActArgs& t,
+                float* q, hipStream_t st);
 int iqn_bwd_launch(const AcnetArgs& a, const IqnArgs& c, hipStream_t st);                           // the tiles, and with c.dfeat the fold over s
 int iqn_td_launch(const AcnetArgs& a, const IqnArgs& c, const IqnTdArgs& s, hipStream_t st);        // the tiles, then the fold over s

@@ -21,6 +21,7 @@
 // The fold of the slabs is acnet_reduce (slab order), the fold of the scalars head_scalars (slab order).
 // Order of every sum: acnet.hip's for the layers and the slabs; every sum over s, i or j is serial in ascending index.  No atomics.
 #include "acnet_tile.h"
+#include "fqf.h"
 #include "iqn.h"
 
 namespace {
@@ -113,7 +114,9 @@ __global__ __launch_bounds__(256) void iqn_q_kernel(const float* __restrict__ th
     if (e < total) q[e] = iqn_mean(theta + e * N, N);
 }
 
-// One workgroup per batch row.  p.B is the number of expanded rows, c.Bb the grid.
+// One workgroup per batch row.  p.B is the number of expanded rows, c.Bb the grid.  FQF (include/ocrl_hip_fqf.h: ocrl_fqf_act): c.taus is
+// [Bb, N + 1], the proposed fractions' boundaries; sample s sits at their midpoint and q is the fold of fqf.h weighted by the intervals.
+template <bool FQF>
 __global__ __launch_bounds__(256) void iqn_act_kernel(AcnetArgs p, IqnArgs c, DqnActArgs s) {
     __shared__ __attribute__((aligned(16))) float buf[3 * TR * LD];
     __shared__ __attribute__((aligned(16))) float ct[TR * LC];
@@ -128,20 +131,29 @@ __global__ __launch_bounds__(256) void iqn_act_kernel(AcnetArgs p, IqnArgs c, Dq
         const long long e0 = row * N + s0;
         if (tid < TR) {
             float t = 0.f;
-            if (tid < rows) t = c.taus ? c.taus[e0 + tid] : iqn_tau(s.seed, s.row_offset + (unsigned long long)row, s0 + tid);
+            if (FQF) {
+                if (tid < rows) t = fqf_tau_hat(c.taus[row * (N + 1) + s0 + tid], c.taus[row * (N + 1) + s0 + tid + 1]);
+            } else if (tid < rows) {
+                t = c.taus ? c.taus[e0 + tid] : iqn_tau(s.seed, s.row_offset + (unsigned long long)row, s0 + tid);
+            }
             tl[tid] = t;
         }
         __syncthreads();
         iqn_fwd_tile(p, c, e0, rows, tl, buf, ct, ot);
         if (tid < A) {                                  // thread a: the serial sum over s goes on where the last tile left it
             float acc = qs[tid];
-            for (int r = 0; r < rows; ++r) acc += ot[r * LA + tid];
+            if (FQF) {
+                const float* bt = c.taus + row * (N + 1) + s0;
+                for (int r = 0; r < rows; ++r) acc = fqf_q_term(acc, bt[r], bt[r + 1], ot[r * LA + tid]);
+            } else {
+                for (int r = 0; r < rows; ++r) acc += ot[r * LA + tid];
+            }
             qs[tid] = acc;
         }
         __syncthreads();
     }
     if (tid < A) {
-        const float q = qs[tid] * (1.f / (float)N);
+        const float q = FQF ? qs[tid] : qs[tid] * (1.f / (float)N);
         qs[tid] = q;
         if (c.q) c.q[row * A + tid] = q;
     }
@@ -382,8 +394,13 @@ int iqn_fwd_launch(const AcnetArgs& a, const IqnArgs& c, hipStream_t st) {
     return 0;
 }
 int iqn_act_launch(const AcnetArgs& a, const IqnArgs& c, const DqnActArgs& s, hipStream_t st) {
-    hipLaunchKernelGGL(iqn_act_kernel, dim3(c.Bb), dim3(256), 0, st, a, c, s);
+    hipLaunchKernelGGL(iqn_act_kernel<false>, dim3(c.Bb), dim3(256), 0, st, a, c, s);
     OCRL_CHECK_LAUNCH("iqn_act");
+    return 0;
+}
+int iqn_act_fqf_launch(const AcnetArgs& a, const IqnArgs& c, const DqnActArgs& s, hipStream_t st) {
+    hipLaunchKernelGGL(iqn_act_kernel<true>, dim3(c.Bb), dim3(256), 0, st, a, c, s);
+    OCRL_CHECK_LAUNCH("fqf_act");
     return 0;
 }
 int iqn_bwd_launch(const AcnetArgs& a, const IqnArgs& c, hipStream_t st) {

@@ -84,6 +84,20 @@ IqnArgs iqn_args(const ocrl_iqn_desc* d, const float* features, const float* tau
 }
 }  // namespace
 
+int iqn_fqf_act(const ocrl_iqn_desc* d, const char* who, const float* features, const float* const* w, const float* taus, const DqnActArgs& t,
+                float* q, hipStream_t st) {
+    RC(check_iqn(d, who));
+    IqnSpec sp;
+    iqn_spec(d, sp);
+    const HeadLay y = head_layout(sp.s);
+    RC(check_ptrs(w, y.np, who));
+    AcnetArgs a;
+    head_args(a, sp.s, y, nullptr, w, nullptr, false);
+    IqnArgs c = iqn_args(d, features, taus);
+    c.q = q;
+    return iqn_act_fqf_launch(a, c, t, st);
+}
+
 extern "C" {
 
 size_t ocrl_iqn_desc_size(void) { return sizeof(ocrl_iqn_desc); }

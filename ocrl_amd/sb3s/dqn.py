@@ -17,7 +17,9 @@ replaces it by the implicit quantile one (IQN, Dabney et al. 2018: the quantile 
 include/ocrl_hip_iqn.h; ``sb3=iqn``), with ``noisy`` but without ``dueling``; off by default.  ``munchausen`` rewrites the rewards
 and the target network's values at the next observation in front of the scalar, quantile and implicit quantile heads' unchanged TD steps
 (Munchausen RL, Vieillard et al. 2020: the clipped log-policy bonus and the soft value of a soft-max policy; munchausen.py,
-include/ocrl_hip_munchausen.h; ``sb3=mdqn``, ``sb3=miqn``); off by default.  Where this departs
+include/ocrl_hip_munchausen.h; ``sb3=mdqn``, ``sb3=miqn``); off by default.  ``fqf`` lets a small network
+propose the implicit quantile head's fractions per state and trains it on the 1-Wasserstein error of the staircase they make (FQF, Yang
+et al. 2019; fqf.py, include/ocrl_hip_fqf.h; ``sb3=fqf``); off by default.  Where this departs
 from stable-baselines3 and from those papers is listed in DESIGN.md §7."""
 import collections
 import copy
@@ -31,6 +33,7 @@ from torch import nn
 from .. import _bridge, _lib
 from ..ocrs.flat_module import FlatParamModule
 from .c51 import CategoricalQNetwork, c51_loss
+from .fqf import FQF_SCALARS, MAX_FRACTIONS, FullyParameterizedQuantileQNetwork, fqf_fraction_loss
 from .iqn import MAX_COS, MAX_TAU_SAMPLES, TRAIN_SEED_SALT, ImplicitQuantileQNetwork, draw_taus, iqn_loss
 from .munchausen import check_munchausen, munchausen_targets
 from .custom_acnets import _n_actions
@@ -41,6 +44,7 @@ from .replay import MAX_N_STEP, ReplayBuffer
 
 _WHO = "ocrl_amd.sb3s"
 MAX_ATOMS, MAX_LOGITS = 64, 256   # of the categorical head: atoms per action, n_actions * n_atoms (include/ocrl_hip_c51.h)
+FQF_RMS_ALPHA, FQF_RMS_EPS = 0.95, 1e-5   # the fraction proposal's RMSprop (the FQF paper's setting)
 ADAM_EPS = 1e-8                 # stable-baselines3's DQNPolicy builds torch's default Adam (the actor-critic policy: 1e-5)
 
 
@@ -140,11 +144,14 @@ class DQNPolicy(nn.Module):
     fractions and ``act`` is ``ocrl_iqn_act`` on ``n_act_samples`` fractions per row, drawn from the policy's stream unless
     ``deterministic``.  ``noisy`` builds the head of noisy
     layers (``noisy_sigma0``: the sigmas' start); which draw of the noise the head uses is set explicitly with ``set_noise`` and does not
-    follow ``train()`` / ``eval()``."""
+    follow ``train()`` / ``eval()``.  ``fqf`` (with ``n_tau_samples`` in 2 .. 32) makes the head a
+    FullyParameterizedQuantileQNetwork of ``n_tau_samples`` proposed fractions: ``q_values`` and ``act`` evaluate it at the fractions its
+    ``fraction_net`` proposes for the row (``ocrl_fqf_fractions``, then ``ocrl_fqf_act``), ``deterministic`` or not, and ``n_act_samples``
+    is not read."""
 
     def __init__(self, observation_space, action_space, lr_schedule=None, config=None, features_extractor=None, features_extractor_class=None,
                  features_extractor_kwargs=None, net_arch=(64, 64), activation="relu", n_atoms=1, v_min=0.0, v_max=2.0, dueling=False, noisy=False,
-                 noisy_sigma0=0.5, n_quantiles=0, n_tau_samples=0, n_act_samples=32, n_cos=64, **kwargs):
+                 noisy_sigma0=0.5, n_quantiles=0, n_tau_samples=0, n_act_samples=32, n_cos=64, fqf=False, **kwargs):
         super().__init__()
         self._config = config
         self.observation_space, self.action_space = observation_space, action_space
@@ -163,7 +170,11 @@ class DQNPolicy(nn.Module):
             raise ValueError(f"{_WHO}.DQNPolicy: noisy_sigma0 >= 0 (got {noisy_sigma0})")
         noise = dict(noisy=True, noisy_sigma0=self.noisy_sigma0) if self.noisy else {}
         self.n_tau_samples, self.n_act_samples, self.n_cos = int(n_tau_samples), int(n_act_samples), int(n_cos)
-        if self.n_tau_samples != 0:
+        self.fqf = bool(fqf)
+        if self.fqf:
+            _check_fqf(f"{_WHO}.DQNPolicy", self.n_tau_samples, self.n_tau_samples, False, self.dueling, self.n_atoms, self.n_quantiles)
+            self.q_net = FullyParameterizedQuantileQNetwork(self.features_dim, n, self.n_tau_samples, self.n_cos, net_arch, activation, **noise)
+        elif self.n_tau_samples != 0:
             if self.n_tau_samples < 0 or self.n_atoms != 1 or self.n_quantiles != 0:
                 raise ValueError(f"{_WHO}.DQNPolicy: n_tau_samples >= 1 (the implicit quantile head) goes with n_atoms = 1 and n_quantiles = 0: "
                                  f"one return distribution at a time (got n_tau_samples {n_tau_samples}, n_atoms {n_atoms}, n_quantiles "
@@ -235,6 +246,8 @@ class DQNPolicy(nn.Module):
         if row_offset is None:
             row_offset = self._sample_rows
             self._sample_rows += B
+        if self.fqf:                                              # the fractions are proposed, not drawn: no stream of their own
+            return (*self.q_net.act(x, self._sample_seed or 0, row_offset, eps, uniforms), None)
         if self.n_tau_samples:
             if not deterministic and self._sample_seed is None:
                 raise RuntimeError(f"{_WHO}.DQNPolicy.act: no stream for the sampled fractions: call policy.set_sampling(seed) or act "
@@ -270,6 +283,27 @@ def dqn_loss(policy, features, next_q, actions, rewards, dones, gamma, next_q_on
                                         dims, acts, policy.q_net.n_actions, *policy.q_net._param_list())
     metrics = {k: scal[i] for i, k in enumerate(DQN_SCALARS)}
     return (loss, metrics, abs_td) if return_abs_td else (loss, metrics)
+
+
+def _check_fqf(who, n_tau_samples, n_tau_prime_samples, munchausen, dueling, n_atoms, n_quantiles):
+    """what fqf=True refuses, each by the names of both arguments"""
+    if n_tau_samples == 0:
+        raise ValueError(f"{who}: fqf=True proposes n_tau_samples fractions per state: set n_tau_samples in 2 .. {MAX_FRACTIONS} (got fqf=True "
+                         "with n_tau_samples = 0)")
+    if not 2 <= n_tau_samples <= MAX_FRACTIONS:
+        raise ValueError(f"{who}: fqf=True takes n_tau_samples in 2 .. {MAX_FRACTIONS}: the 2 n - 1 fractions of the fraction loss go through "
+                         f"the head in one pass (got fqf=True with n_tau_samples = {n_tau_samples})")
+    if n_tau_prime_samples not in (0, n_tau_samples):
+        raise ValueError(f"{who}: fqf=True evaluates the target network at the online network's own fractions: n_tau_prime_samples is 0 or "
+                         f"n_tau_samples (got fqf=True with n_tau_prime_samples = {n_tau_prime_samples}, n_tau_samples = {n_tau_samples})")
+    if munchausen:
+        raise ValueError(f"{who}: fqf with munchausen=True is not built (got fqf=True with munchausen=True)")
+    if dueling:
+        raise ValueError(f"{who}: fqf with dueling=True is not built: the implicit quantile head has no value stream (got fqf=True with "
+                         "dueling=True)")
+    if n_atoms > 1 or n_quantiles > 0:
+        raise ValueError(f"{who}: fqf=True with n_atoms > 1 or n_quantiles > 0 names two return distributions: one at a time (got fqf=True "
+                         f"with n_atoms = {n_atoms}, n_quantiles = {n_quantiles})")
 
 
 def exploration_schedule(frac, initial_eps, final_eps, fraction):
@@ -312,13 +346,22 @@ class DQN:
     times the log-policy of the action taken, scaled by ``munchausen_tau`` and clipped to [``munchausen_clip``, 0], to the rewards and
     puts the soft value of the soft-max policy at temperature ``munchausen_tau`` in place of the target network's values at the next
     observations; the head's TD step then runs unchanged.  It takes ``n_atoms = 1`` and no ``double_q`` and combines with n-step
-    returns (the bonus is the first action's), prioritized replay, ``noisy`` and ``dueling`` on the quantile head; acting is unchanged."""
+    returns (the bonus is the first action's), prioritized replay, ``noisy`` and ``dueling`` on the quantile head; acting is unchanged.
+
+    ``fqf=True``: FQF on the implicit quantile head.  ``n_tau_samples`` (N, 2 .. 32) fractions per row are proposed by the
+    online network's ``fraction_net`` from the observation's features; an update evaluates both networks at them
+    (``_train_step_fqf``), q is the interval-weighted sum, and the proposal takes the fraction loss's gradient
+    (``fqf_fraction_loss``, with ``fqf_ent_coef`` times the proposal's entropy) and a TF-style RMSprop step of its own at
+    ``fqf_fraction_lr`` on buffers outside ``flat_p`` (``frac_p``, ``frac_g``, ``frac_sq``).  ``n_tau_prime_samples`` is 0 or N,
+    ``n_act_samples`` is not read; it refuses ``munchausen``, ``dueling`` and a second distributional head and combines with double Q,
+    n-step returns, prioritized replay and ``noisy``."""
     ALGO = "DQN"
     HYPER = ("learning_rate", "buffer_size", "learning_starts", "batch_size", "tau", "gamma", "train_freq", "gradient_steps",
              "target_update_interval", "exploration_fraction", "exploration_initial_eps", "exploration_final_eps", "max_grad_norm",
              "double_q", "n_step", "prioritized_replay", "prioritized_replay_alpha", "prioritized_replay_beta0", "prioritized_replay_beta_final",
              "prioritized_replay_eps", "n_atoms", "v_min", "v_max", "dueling", "noisy", "noisy_sigma0", "n_quantiles", "huber_kappa",
-             "n_tau_samples", "n_tau_prime_samples", "n_act_samples", "n_cos", "munchausen", "munchausen_alpha", "munchausen_tau", "munchausen_clip")
+             "n_tau_samples", "n_tau_prime_samples", "n_act_samples", "n_cos", "munchausen", "munchausen_alpha", "munchausen_tau", "munchausen_clip",
+             "fqf", "fqf_fraction_lr", "fqf_ent_coef")
 
     def __init__(self, policy, env, learning_rate=1e-4, buffer_size=1_000_000, learning_starts=50_000, batch_size=32, tau=1.0, gamma=0.99,
                  train_freq=4, gradient_steps=1, target_update_interval=10_000, exploration_fraction=0.1, exploration_initial_eps=1.0,
@@ -326,7 +369,8 @@ class DQN:
                  prioritized_replay=False, prioritized_replay_alpha=0.6, prioritized_replay_beta0=0.4, prioritized_replay_beta_final=1.0,
                  prioritized_replay_eps=1e-6, n_atoms=1, v_min=0.0, v_max=2.0, dueling=False, noisy=False, noisy_sigma0=0.5,
                  n_quantiles=0, huber_kappa=1.0, n_tau_samples=0, n_tau_prime_samples=0, n_act_samples=32, n_cos=64, munchausen=False,
-                 munchausen_alpha=0.9, munchausen_tau=0.03, munchausen_clip=-1.0, **ignored_sb3_kwargs):
+                 munchausen_alpha=0.9, munchausen_tau=0.03, munchausen_clip=-1.0, fqf=False, fqf_fraction_lr=2.5e-9, fqf_ent_coef=0.0,
+                 **ignored_sb3_kwargs):
         who = self._who = f"{_WHO}.{self.ALGO}"
         self.learning_rate = _check_constant(who, "learning_rate", learning_rate)
         if int(gradient_steps) < 1:
@@ -376,6 +420,8 @@ class DQN:
             raise ValueError(f"{who}: n_act_samples lies in 1 .. {MAX_TAU_SAMPLES} (got {n_act_samples})")
         if not (4 <= self.n_cos <= MAX_COS and self.n_cos % 4 == 0):
             raise ValueError(f"{who}: n_cos is a multiple of 4 in 4 .. {MAX_COS} (got {n_cos})")
+        if bool(fqf):
+            _check_fqf(who, self.n_tau_samples, self.n_tau_prime_samples, bool(munchausen), self.dueling, self.n_atoms, self.n_quantiles)
         if self.n_tau_samples > 0 and (self.n_atoms > 1 or self.n_quantiles > 0):
             raise ValueError(f"{who}: n_tau_samples > 0 with n_atoms > 1 or n_quantiles > 0 names two return distributions: one at a time (got "
                              f"n_tau_samples = {n_tau_samples}, n_atoms = {n_atoms}, n_quantiles = {n_quantiles})")
@@ -396,6 +442,11 @@ class DQN:
         if self.munchausen and self.double_q:
             raise ValueError(f"{who}: munchausen with double_q=True: the soft value of the target network's policy leaves no bootstrap action "
                              "to pick (got munchausen=True with double_q=True)")
+        self.fqf, self.fqf_fraction_lr, self.fqf_ent_coef = bool(fqf), float(fqf_fraction_lr), float(fqf_ent_coef)
+        if not (math.isfinite(self.fqf_fraction_lr) and self.fqf_fraction_lr >= 0.0):
+            raise ValueError(f"{who}: fqf_fraction_lr >= 0 and finite (got {fqf_fraction_lr})")
+        if not math.isfinite(self.fqf_ent_coef):
+            raise ValueError(f"{who}: fqf_ent_coef finite (got {fqf_ent_coef})")
         self.buffer_size, self.learning_starts, self.batch_size = int(buffer_size), int(learning_starts), int(batch_size)
         self.tau, self.gamma = float(tau), float(gamma)
         self.train_freq, self.gradient_steps, self.target_update_interval = int(train_freq), int(gradient_steps), int(target_update_interval)
@@ -413,6 +464,8 @@ class DQN:
                 head = dict(n_quantiles=self.n_quantiles, dueling=self.dueling)
             if self.n_tau_samples > 0:
                 head = dict(n_tau_samples=self.n_tau_samples, n_act_samples=self.n_act_samples, n_cos=self.n_cos)
+            if self.fqf:
+                head["fqf"] = True
             if self.noisy:
                 head.update(noisy=True, noisy_sigma0=self.noisy_sigma0)
             policy = policy(env.observation_space, env.action_space, None, **dict(policy_kwargs or {}, **head))
@@ -431,6 +484,9 @@ class DQN:
         if self.n_atoms > 1 and (policy.q_net.v_min, policy.q_net.v_max) != (self.v_min, self.v_max):
             raise ValueError(f"{who}: the policy's head has v_min, v_max = {policy.q_net.v_min}, {policy.q_net.v_max}; the arguments say "
                              f"{self.v_min}, {self.v_max}")
+        if getattr(policy, "fqf", False) != self.fqf or (self.fqf and policy.n_tau_samples != self.n_tau_samples):
+            raise ValueError(f"{who}: the policy's head has fqf = {getattr(policy, 'fqf', False)}, n_tau_samples = {policy.n_tau_samples}; the "
+                             f"arguments say fqf = {self.fqf}, n_tau_samples = {self.n_tau_samples}")
         if policy.noisy != self.noisy:
             raise ValueError(f"{who}: the policy's head has noisy = {policy.noisy}; the arguments say noisy = {self.noisy}")
         for m in policy.modules():
@@ -459,6 +515,8 @@ class DQN:
         self._stats = torch.zeros(self.log_interval * self.train_freq, 4, self.n_envs, device=self.device, dtype=torch.float64)
         self._stats_n = 0
         self._last_train = self._train_stats([float("nan")] * (len(DQN_SCALARS) + 1), 1)
+        if self.fqf:
+            self._last_train.update(dict.fromkeys(FQF_SCALARS, float("nan")))
 
     n_steps = property(lambda self: self.train_freq)                  # vec steps per iteration (what the entry point's log line prints)
     exploration_rate = property(lambda self: self.policy.exploration_rate)
@@ -469,8 +527,9 @@ class DQN:
         OnPolicyAlgorithm._flatten_parameters; then build the target policy, a copy whose trainable parameters are views of
         ``flat_target`` in the same layout and take no gradient.  What has no trainable parameter and is no nn.Module (a frozen encoder's
         wrapper) is shared between the two, not copied."""
-        params = [p for p in self.policy.parameters() if p.requires_grad]
-        for p in params:
+        frac = list(self.policy.q_net.fraction_net.parameters()) if self.fqf else []      # fqf: stepped by an optimiser of its own
+        params = [p for p in self.policy.parameters() if p.requires_grad and not any(p is f for f in frac)]
+        for p in params + frac:
             if p.dtype != torch.float32 or p.device != self.device:
                 raise RuntimeError(f"{self._who}: parameters must be float32 on {self.device} (got {p.dtype} on {p.device})")
         offs, n = _layout(params)
@@ -481,6 +540,14 @@ class DQN:
             p.data = view
             p.grad = self.flat_g[o:o + p.numel()].view(p.shape)
         self._params = params
+        if self.fqf:
+            foffs, fn = _layout(frac)
+            self.frac_p, self.frac_g = (torch.zeros(fn, device=self.device) for _ in range(2))
+            self.frac_sq = torch.ones(fn, device=self.device)         # TF-style RMSprop starts its square average at ones
+            for p, o in zip(frac, foffs):
+                view = self.frac_p[o:o + p.numel()].view(p.shape)
+                view.copy_(p.data)
+                p.data = view
         ext = self.policy.features_extractor
         frozen = getattr(ext, "_ocr", None)
         memo = {id(frozen): frozen} if frozen is not None and not getattr(ext, "_trainable", True) else {}
@@ -490,6 +557,14 @@ class DQN:
         self.target = copy.deepcopy(self.policy, memo)
         for p, o in zip(params, offs):
             p.grad = self.flat_g[o:o + p.numel()].view(p.shape)
+        if self.fqf:
+            for p, o in zip(frac, foffs):
+                p.grad = self.frac_g[o:o + p.numel()].view(p.shape)
+            for p in self.target.q_net.fraction_net.parameters():     # a frozen copy, which nothing reads
+                p.requires_grad_(False)
+            self._frac_norm = torch.zeros(1, device=self.device)
+            self._frac_ws = torch.empty(_lib.lib().ocrl_flat_clip_rmsprop_ws_floats(), device=self.device)
+            self._frac_acc = torch.zeros(len(FQF_SCALARS), device=self.device)
         tparams = [p for p in self.target.parameters() if p.requires_grad]
         assert [tuple(p.shape) for p in tparams] == [tuple(p.shape) for p in params]
         for p, o in zip(tparams, offs):
@@ -510,6 +585,14 @@ class DQN:
                                                          self.flat_p.numel(), self.max_grad_norm, self.learning_rate, 0.9, 0.999, ADAM_EPS,
                                                          self.adam_step, _lib.ptr(self._norm), _lib.ptr(self._ws), self._ws.numel(),
                                                          _lib.stream(self.device)))
+
+    def _fraction_step(self):
+        """fqf: the proposal's own step, the library's TF-style RMSprop (epsilon inside the root, square average from ones) without a
+        clip, at fqf_fraction_lr: one C call, no host synchronisation"""
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().ocrl_flat_clip_rmsprop_l2(_lib.ptr(self.frac_p), _lib.ptr(self.frac_g), _lib.ptr(self.frac_sq), self.frac_p.numel(),
+                                                            0.0, self.fqf_fraction_lr, FQF_RMS_ALPHA, FQF_RMS_EPS, _lib.ptr(self._frac_norm),
+                                                            _lib.ptr(self._frac_ws), self._frac_ws.numel(), _lib.stream(self.device)))
 
     def update_target(self):
         """the target network follows the online one: a copy at tau = 1 (DQN's hard update), else a step of size tau towards it"""
@@ -729,6 +812,27 @@ class DQN:
         return iqn_loss(self.policy, features, self._train_taus(0, N), next_quantiles, next_q, batch.actions, batch.rewards, batch.dones, self.gamma,
                         self.huber_kappa, discounts=batch.discounts, weights=weights)
 
+    def _train_step_fqf(self, batch, weights):
+        """FQF's part of ``train_step``: (loss, metrics, the rows' quantile losses).  Every fraction is the row's own,
+        proposed by the online ``fraction_net`` from the online features of the observation (the paper's Algorithm 1): the target
+        network gives the next observations' quantile values at those tau_hats and their interval-weighted q (the online network's q
+        under double_q), ``iqn_loss`` runs unchanged with N' = N, and one head forward at the 2 N - 1 fractions of eval_taus feeds
+        ``fqf_fraction_loss``, which leaves the proposal's gradient in ``frac_g``."""
+        self._online_turn()
+        features = self.policy.extract_features(self._obs(batch.observations))
+        next_obs = self._obs(batch.next_observations)
+        with torch.no_grad():
+            fr = self.policy.q_net.fractions(features)
+            next_quantiles, next_q = self.target.q_net.quantiles(self.target.extract_features(next_obs), fr.taus)
+            if self.double_q:
+                _, next_q = self.policy.q_net.quantiles(self.policy.extract_features(next_obs), fr.taus)
+        out = iqn_loss(self.policy, features, fr.tau_hats, next_quantiles, next_q, batch.actions, batch.rewards, batch.dones, self.gamma,
+                       self.huber_kappa, discounts=batch.discounts, weights=weights)
+        with torch.no_grad():
+            self._frac_m = fqf_fraction_loss(self.policy, features, batch.actions, weights, self.fqf_ent_coef, fractions=fr)
+        self.last_fractions = fr
+        return out
+
     def train_step(self):
         """one gradient step: a batch from the replay buffer (``_draw_batch``), the head's loss against the target network
         (``_train_step_dqn``, with n_atoms > 1 ``_train_step_c51``, with n_quantiles > 0 ``_train_step_qr``, with n_tau_samples > 0
@@ -737,10 +841,13 @@ class DQN:
         add up in ``_acc`` until a callback reads them."""
         batch, idx, weights = self._draw_batch()
         self._draw_train_noise()
-        step = self._train_step_iqn if self.n_tau_samples > 0 else self._train_step_qr if self.n_quantiles > 0 else self._train_step_c51 if self.n_atoms > 1 else self._train_step_dqn
+        step = self._train_step_fqf if self.fqf else self._train_step_iqn if self.n_tau_samples > 0 else self._train_step_qr if self.n_quantiles > 0 else self._train_step_c51 if self.n_atoms > 1 else self._train_step_dqn
         loss, m, row_err = step(batch, weights)
         loss.backward()
         self._adam_step()
+        if self.fqf:
+            self._fraction_step()
+            self._frac_acc += torch.stack([self._frac_m[k] for k in FQF_SCALARS])
         if self.prioritized_replay:
             if self.n_tau_samples > 0:
                 # a transition drawn twice sits in two rows with fractions of their own, so its rows' losses differ, and the priority
@@ -764,6 +871,9 @@ class DQN:
         NaN before the first update), ``n_updates`` and ``exploration_rate``.  Reads the device once."""
         if self._acc_n:
             self._last_train = self._train_stats(self._acc.tolist(), self._acc_n)
+            if self.fqf:
+                self._last_train.update({k: v / self._acc_n for k, v in zip(FQF_SCALARS, self._frac_acc.tolist())})
+                self._frac_acc.zero_()
             self._acc.zero_()
             self._acc_n = 0
         self._last_train.update(n_updates=self.n_updates, exploration_rate=self.policy.exploration_rate)
@@ -793,6 +903,8 @@ class DQN:
         hyper = {k: getattr(self, k) for k in self.HYPER + ("seed", "num_timesteps", "iteration", "n_calls", "n_updates", "n_target_updates",
                                                             "_total_timesteps", "noise_draws")}
         opt = {"m": self.flat_m, "v": self.flat_v, "step": self.adam_step, "sampling_rows": self.policy._sample_rows}
+        if self.fqf:
+            opt["frac_sq"] = self.frac_sq
         torch.save({"algo": self.ALGO, "policy": self.policy.state_dict(), "target": self.target.state_dict(), "optimizer": opt, "hyper": hyper,
                     "exploration_rate": float(self.policy.exploration_rate)}, path)
 
@@ -819,7 +931,13 @@ class DQN:
             have, mine = type(dflt)(hyper.get(k, dflt)), getattr(self, k)
             if have != mine and (self.munchausen or bool(hyper.get("munchausen", False))):
                 raise ValueError(f"{self._who}.load: the checkpoint was written with {k} = {have}, this instance has {k} = {mine}")
+        for k, dflt in (("fqf", False), ("fqf_fraction_lr", 2.5e-9), ("fqf_ent_coef", 0.0)):
+            have, mine = type(dflt)(hyper.get(k, dflt)), getattr(self, k)
+            if have != mine and (self.fqf or bool(hyper.get("fqf", False))):
+                raise ValueError(f"{self._who}.load: the checkpoint was written with {k} = {have}, this instance has {k} = {mine}")
         opt = ck["optimizer"]
+        if self.fqf and ("frac_sq" not in opt or opt["frac_sq"].shape != self.frac_sq.shape):
+            raise ValueError(f"{self._who}.load: the checkpoint's optimiser state has no frac_sq of this policy's {self.frac_sq.numel()} entries")
         if "m" not in opt or opt["m"].shape != self.flat_m.shape:
             n = opt["m"].numel() if "m" in opt else "no"
             raise ValueError(f"{self._who}.load: the checkpoint's optimiser state has {n} Adam entries, this policy's {self.flat_m.numel()}")
@@ -827,6 +945,8 @@ class DQN:
         self.target.load_state_dict(ck["target"])                       # ... and of flat_target
         self.flat_m.copy_(opt["m"])
         self.flat_v.copy_(opt["v"])
+        if self.fqf:
+            self.frac_sq.copy_(opt["frac_sq"])
         self.adam_step = int(opt["step"])
         self.policy._sample_rows = int(opt["sampling_rows"])
         self.policy._sample_seed = int(ck["hyper"]["seed"]) & (2 ** 64 - 1)
@@ -844,4 +964,4 @@ class DQN:
         return self
 
 
-__all__ = ["DQN", "DQNPolicy", "QNetwork", "CategoricalQNetwork", "QuantileQNetwork", "ImplicitQuantileQNetwork", "dqn_loss", "c51_loss", "qr_loss", "iqn_loss", "munchausen_targets", "exploration_schedule", "DQN_SCALARS"]
+__all__ = ["DQN", "DQNPolicy", "QNetwork", "CategoricalQNetwork", "QuantileQNetwork", "ImplicitQuantileQNetwork", "dqn_loss", "c51_loss", "qr_loss", "iqn_loss", "munchausen_targets", "FullyParameterizedQuantileQNetwork", "fqf_fraction_loss", "exploration_schedule", "DQN_SCALARS"]

@@ -1,5 +1,5 @@
 """RL entry point with the reference's command line (train_sb3.py:22-120, on this project's config resolver and its own PPO, A2C and
-DQN; ``sb3=ppo``, ``sb3=a2c`` or ``sb3=dqn`` (and its extensions ``dqn_per``, ``dqn_c51``, ``rainbow``, ``qrdqn``, ``iqn``, and with Munchausen targets ``sb3=mdqn``, ``sb3=miqn``) chooses, as the reference's ``getattr(sb3, config.sb3.name)``; DQN steps a frozen or
+DQN; ``sb3=ppo``, ``sb3=a2c`` or ``sb3=dqn`` (and its extensions ``dqn_per``, ``dqn_c51``, ``rainbow``, ``qrdqn``, ``iqn``, and with Munchausen targets ``sb3=mdqn``, ``sb3=miqn``, and with proposed fractions ``sb3=fqf``) chooses, as the reference's ``getattr(sb3, config.sb3.name)``; DQN steps a frozen or
 torch-trained encoder only and calls back every ``sb3.algo_kwargs.log_interval`` (default 100) iterations of ``train_freq`` steps):
 
     python train_sb3.py ocr=slate pooling=transformer sb3=ppo sb3_acnet=mlp env=target-N4C4S3S1 num_envs=16 device=cuda:0 \
