@@ -1,4 +1,4 @@
-// The row-tile steps of the small-Linear-chain heads, shared by acnet.hip (actor-critic), dqn.hip (the Q head), c51.hip and classifier.hip: one workgroup (4 waves)
+// The row-tile steps of the small-Linear-chain heads, shared by acnet.hip (actor-critic), dqn.hip (the Q head), classifier.hip and, through qhead_tile.h, the value heads: one workgroup (4 waves)
 // owns a tile of 16 batch rows and walks a chain of Linear layers with the activations in LDS; see acnet.hip for the order of every sum.
 // Device code in an unnamed namespace: each translation unit that includes this compiles its own copy into its kernels.
 #pragma once
@@ -220,6 +220,24 @@ __device__ void seed_rows(Dst d, const float* g, int K, bool accum, int rows) {
     }
 }
 
+// Backward of trunk t's layers, last to first.  cur [16][LD] (LDS) holds the cotangent of the trunk's output; a layer's input cotangent
+// goes to whichever of g0, g1 `cur` is not, and the walk goes on from there.  Layer 0 is the callers' own: x0 [., K0] is its input and its
+// dx goes to *d0, added to when `accum0`; d0 == null sends it to the next tile like every other layer's.  The layers between read their
+// inputs from the saved outputs of the workspace.  Returns the tile the walk ended in: with d0 == null the one that holds layer 0's dx
+// (`cur` itself for an empty trunk).
+__device__ float* bwd_trunk(const AcnetArgs& p, int t, float* cur, float* g0, float* g1, Src x0, int K0, const Dst* d0, bool accum0, float* slab,
+                            bool first, long long row0, int rows) {
+    for (int l = p.n[t] - 1; l >= 0; --l) {
+        const int N = p.dim[t][l], K = l ? p.dim[t][l - 1] : K0;
+        const Src x = l ? Src{p.saved[t][l - 1] + row0 * K, K, rows, false} : x0;
+        float* nxt = cur == g0 ? g1 : g0;
+        lin_bwd_tile(cur, LD, p.saved[t][l] + row0 * N, p.act[t][l], x, p.w[t][l], K, N, slab + p.off_w[t][l], slab + p.off_b[t][l], first,
+                     l || !d0 ? Dst{nxt, LD, TR} : *d0, l ? false : accum0, rows);
+        cur = nxt;
+    }
+    return cur;
+}
+
 // backward of one head + trunk: head cotangent dhead [16][ldh] (LDS, null without heads), latent cotangent dlat (global, may be null);
 // the result is added into dh (`hw`: dh already holds a contribution)
 __device__ void bwd_side(const AcnetArgs& p, int t, float* dhead, int ldh, const float* Wh, long long off_wh, long long off_bh, int NH,
@@ -237,16 +255,7 @@ __device__ void bwd_side(const AcnetArgs& p, int t, float* dhead, int ldh, const
     if (!lw) { seed_rows(dlt, nullptr, Kl, false, rows); lw = true; }
     __syncthreads();
     if (!nl) { hw = lw; return; }
-    float* cur = g0;
-    for (int l = nl - 1; l >= 0; --l) {
-        const int N = p.dim[t][l], K = l ? p.dim[t][l - 1] : Kh;
-        const Src x = l ? Src{p.saved[t][l - 1] + row0 * K, K, rows, false} : h;
-        float* nxt = cur == g0 ? g1 : g0;
-        const Dst d = l ? Dst{nxt, LD, TR} : dh;
-        lin_bwd_tile(cur, LD, p.saved[t][l] + row0 * N, p.act[t][l], x, p.w[t][l], K, N, slab + p.off_w[t][l], slab + p.off_b[t][l], first, d,
-                     l ? false : hw, rows);
-        cur = nxt;
-    }
+    bwd_trunk(p, t, g0, g0, g1, h, Kh, &dh, hw, slab, first, row0, rows);
     if (dh.p) hw = true;
 }
 
@@ -261,16 +270,8 @@ __device__ void bwd_tile(const AcnetArgs& p, long long row0, int rows, bool firs
     bool hw = false;
     bwd_side(p, 1, p.A > 0 ? lg : nullptr, LA, p.wa, p.off_wa, p.off_ba, p.A, p.dlat_pi, h, Kh, dh, hw, g0, g1, slab, first, row0, rows);
     bwd_side(p, 2, p.A > 0 && p.wv ? vl : nullptr, 1, p.wv, p.off_wv, p.off_bv, 1, p.dlat_vf, h, Kh, dh, hw, g0, g1, slab, first, row0, rows);
-    float* cur = gh;
-    for (int l = ns - 1; l >= 0; --l) {
-        const int N = p.dim[0][l], K = l ? p.dim[0][l - 1] : p.F;
-        const Src x = l ? Src{p.saved[0][l - 1] + row0 * K, K, rows, false} : Src{p.x + row0 * p.F, p.F, rows, false};
-        float* nxt = cur == g0 ? g1 : g0;
-        const Dst d = l ? Dst{nxt, LD, TR} : Dst{p.dx ? p.dx + row0 * p.F : nullptr, p.F, rows};
-        lin_bwd_tile(cur, LD, p.saved[0][l] + row0 * N, p.act[0][l], x, p.w[0][l], K, N, slab + p.off_w[0][l], slab + p.off_b[0][l], first, d, false,
-                     rows);
-        cur = nxt;
-    }
+    const Dst dx = Dst{p.dx ? p.dx + row0 * p.F : nullptr, p.F, rows};
+    bwd_trunk(p, 0, gh, g0, g1, Src{p.x + row0 * p.F, p.F, rows, false}, p.F, &dx, false, slab, first, row0, rows);
 }
 
 }  // namespace

@@ -19,15 +19,10 @@ struct C51Args {
     const float* dlogits;                             // c51_bwd: [B, A, Z]
 };
 
-// the TD target's inputs, each [B] but next_probs [B, A, Z] and next_q [B, A]
+// the TD target's inputs: next_probs [B, A, Z] and the shared ones (dqn.h)
 struct C51TdArgs {
-    const float *next_probs, *next_q;
-    const long long* actions;
-    const float* rewards;
-    const unsigned char* dones;
-    const float *discounts, *weights;                 // may be null
-    float gamma;
-    float* row_loss;                                  // may be null
+    const float* next_probs;
+    QTdArgs row;
 };
 
 int c51_fwd_launch(const AcnetArgs& a, const C51Args& c, hipStream_t st);

@@ -1,11 +1,10 @@
 // DQN's categorical head on the device (include/ocrl_hip_c51.h): a chain of small Linear layers, a wide advantage Linear of A * Z
-// columns (atom j of action a in column a * Z + j) and, with dueling, a value Linear of Z columns on the same latent.  A row-tile kernel
-// family of its own on the per-layer steps of acnet_tile.h (run_trunk, lin_fwd_tile, lin_bwd_tile): one workgroup of four waves owns 16
-// batch rows, the chain ping-pongs between the first two LDS activation tiles and the third one holds the logits [16][LD] (A * Z <= 256
-// columns: the 64-column `lg` tile of fwd_tile / bwd_tile is too narrow, so neither is called here); the value head has a [16][LV] tile.
+// columns (atom j of action a in column a * Z + j) and, with dueling, a value Linear of Z columns on the same latent: the wide head of
+// qhead_tile.h (wide_fwd_tile, wide_bwd_tile) with n = Z.  One workgroup of four waves owns 16 batch rows, the chain ping-pongs between the
+// first two LDS activation tiles and the third one holds the logits [16][LD] (A * Z <= 256 columns: the 64-column `lg` tile of fwd_tile /
+// bwd_tile is too narrow, so neither is called here); the value head has a [16][LV] tile.
 //   c51_fwd    chain, heads, the dueling rule, then one thread per (row, action): softmax over the atoms and the expectation q
-//   c51_act    the same, then lane r of a tile flips row r's coin and takes the random action or the lowest index of the maximum q
-//              (dqn_act's rule and words)
+//   c51_act    the same, then lane r of a tile chooses for row r from the q values (eps_greedy)
 //   c51_bwd    cotangent of the logits -> the dueling rule's backward, the heads' and the chain's backward into the workgroup's slab
 //   c51_td     forward, the projected target distribution m (one thread per (row, atom) gathers m_i), the cross-entropy, the cotangent
 //              written over the logits in place, and the backward, per row tile in one kernel.  Once the heads have run the two chain
@@ -15,40 +14,16 @@
 // Order of every sum: acnet.hip's for the layers and the slabs; the sums over actions and atoms are serial in ascending index; a tile's
 // scalar terms are added in row order, the tiles of a slab in tile order.  The expectation accumulates with fused multiply-adds
 // (z_j = fma(j, dz, v_min), q = fma(p_j, z_j, q)) so that every kernel here forms the same q.  No atomics.
-#include "acnet_tile.h"
 #include "c51.h"
+#include "qhead_tile.h"
 
 namespace {
 
-constexpr int LV = C51_MAX_ATOMS + 4;           // row stride of the value head's tile
-constexpr int LQ = ACNET_MAX_ACTIONS;           // row stride of the q tile of c51_act
+static_assert(C51_MAX_ATOMS <= WIDE_MAX_N, "the atoms of an action fit a row of the value head's tile");
 static_assert(C51_MAX_COLS <= ACNET_MAX_WIDTH, "the logits tile is an activation tile");
 static_assert(2 * C51_MAX_ATOMS <= ACNET_MAX_WIDTH, "next_probs and beta share the rows of one chain tile, m takes the other");
 
 __device__ __forceinline__ float atom(const C51Args& c, int j) { return __fmaf_rn((float)j, c.dz, c.v_min); }
-
-// Forward of one tile: leaves the logits in lg [16][LD] (rows past the batch hold the biases' image: finite, never written out) and
-// ends on a barrier.  vt [16][LV] is touched only with dueling.
-__device__ void c51_fwd_tile(const AcnetArgs& p, const C51Args& c, long long row0, int rows, float* buf, float* lg, float* vt) {
-    int K = p.F;
-    const Src lat = run_trunk(p, 1, gsrc(p.x + row0 * p.F, p.F, rows), K, buf, buf + TR * LD, row0, rows, nullptr);
-    const int A = p.A, Z = c.Z;
-    lin_fwd_tile(lat, p.wa, p.ba, K, A * Z, 0, lg, LD, nullptr, nullptr, rows);
-    if (p.wv) lin_fwd_tile(lat, p.wv, p.bv, K, Z, 0, vt, LV, nullptr, nullptr, rows);
-    __syncthreads();
-    if (p.wv) {                                         // one thread per (row, atom): (V + Adv) - mean over the actions
-        const float invA = 1.f / (float)A;
-        for (int e = threadIdx.x; e < TR * Z; e += blockDim.x) {
-            const int r = e / Z, j = e - r * Z;
-            float* col = lg + r * LD + j;
-            float s = 0.f;
-            for (int a = 0; a < A; ++a) s += col[a * Z];
-            const float v = vt[r * LV + j], mean = invA * s;
-            for (int a = 0; a < A; ++a) col[a * Z] = (v + col[a * Z]) - mean;
-        }
-        __syncthreads();
-    }
-}
 
 // max and sum of exponentials of one action's Z logits
 __device__ __forceinline__ void lse_parts(const float* l, int Z, float& m, float& se) {
@@ -85,7 +60,7 @@ __global__ __launch_bounds__(256) void c51_fwd_kernel(AcnetArgs p, C51Args c) {
     float* lg = buf + 2 * TR * LD;
     const long long row0 = (long long)blockIdx.x * TR;
     const int rows = p.B - row0 < TR ? (int)(p.B - row0) : TR;
-    c51_fwd_tile(p, c, row0, rows, buf, lg, vt);
+    wide_fwd_tile(p, c.Z, row0, rows, buf, lg, vt);
     const int NZ = p.A * c.Z;
     if (c.logits)
         for (int e = threadIdx.x; e < rows * NZ; e += blockDim.x) {
@@ -95,7 +70,7 @@ __global__ __launch_bounds__(256) void c51_fwd_kernel(AcnetArgs p, C51Args c) {
     c51_softmax_rows(p, c, row0, rows, lg, nullptr);
 }
 
-// Forward of a tile, then lane r < rows chooses for row r from the q values in LDS: dqn_act_kernel's tail.
+// Forward of a tile, then lane r < rows chooses for row r from the q values in LDS.
 __global__ __launch_bounds__(256) void c51_act_kernel(AcnetArgs p, C51Args c, DqnActArgs s) {
     __shared__ __attribute__((aligned(16))) float buf[3 * TR * LD];
     __shared__ __attribute__((aligned(16))) float vt[TR * LV];
@@ -103,89 +78,17 @@ __global__ __launch_bounds__(256) void c51_act_kernel(AcnetArgs p, C51Args c, Dq
     float* lg = buf + 2 * TR * LD;
     const long long row0 = (long long)blockIdx.x * TR;
     const int rows = p.B - row0 < TR ? (int)(p.B - row0) : TR;
-    c51_fwd_tile(p, c, row0, rows, buf, lg, vt);
+    wide_fwd_tile(p, c.Z, row0, rows, buf, lg, vt);
     c51_softmax_rows(p, c, row0, rows, lg, qs);
     __syncthreads();
     const int r = threadIdx.x;
-    if (r >= rows) return;
-    const long long row = row0 + r;
-    const float* z = qs + r * LQ;
-    const int A = p.A;
-    float m = z[0];
-    int best = 0;
-    for (int a = 1; a < A; ++a)
-        if (z[a] > m) { m = z[a]; best = a; }           // strict: the lowest index of the maximum
-    uint32_t b0, b1;                                    // the 24 bits of u0 and u1
-    if (s.uniforms) {
-        b0 = (uint32_t)(s.uniforms[2 * row] * 16777216.f);
-        b1 = (uint32_t)(s.uniforms[2 * row + 1] * 16777216.f);
-    } else {
-        const uint2 w = rng_bits4(s.seed, SITE_DQN_ACT, s.row_offset + (unsigned long long)row);
-        b0 = w.x >> 8; b1 = w.y >> 8;
-    }
-    const float u0 = (float)b0 * (1.f / 16777216.f);
-    int act = best;
-    if (u0 < s.epsilon) {
-        act = (int)(((unsigned long long)b1 * (unsigned long long)A) >> 24);
-        act = act < A ? act : A - 1;                    // only a given uniform >= 1 gets here
-    }
-    s.actions[row] = act;
-}
-
-// Backward of one tile from the logits' cotangent in lg (LDS): the dueling rule, the two heads into the latent's cotangent, the chain.
-// The chain's tiles are free by now: the layer inputs come from the workspace.
-__device__ void c51_bwd_tile(const AcnetArgs& p, const C51Args& c, long long row0, int rows, bool first, float* buf, float* lg, float* vt) {
-    float* slab = p.slab + (long long)blockIdx.x * p.slab_stride;
-    const int A = p.A, Z = c.Z;
-    if (p.wv) {                                         // dV = sum over the actions, dAdv = dlogit - dV / A
-        const float invA = 1.f / (float)A;
-        for (int e = threadIdx.x; e < TR * Z; e += blockDim.x) {
-            const int r = e / Z, j = e - r * Z;
-            float* col = lg + r * LD + j;
-            float s = 0.f;
-            for (int a = 0; a < A; ++a) s += col[a * Z];
-            vt[r * LV + j] = s;
-            const float mean = invA * s;
-            for (int a = 0; a < A; ++a) col[a * Z] -= mean;
-        }
-        __syncthreads();
-    }
-    const int nl = p.n[1];
-    const int Kl = nl ? p.dim[1][nl - 1] : p.F;
-    const Src feat = Src{p.x + row0 * p.F, p.F, rows, false};
-    const Src lat = nl ? Src{p.saved[1][nl - 1] + row0 * Kl, Kl, rows, false} : feat;
-    float *g0 = buf, *g1 = buf + TR * LD;
-    const Dst dx = Dst{p.dx ? p.dx + row0 * p.F : nullptr, p.F, rows};
-    const Dst dlt = nl ? Dst{g0, LD, TR} : dx;
-    lin_bwd_tile(lg, LD, nullptr, 0, lat, p.wa, Kl, A * Z, slab + p.off_wa, slab + p.off_ba, first, dlt, false, rows);
-    if (p.wv) lin_bwd_tile(vt, LV, nullptr, 0, lat, p.wv, Kl, Z, slab + p.off_wv, slab + p.off_bv, first, dlt, true, rows);
-    float* cur = g0;
-    for (int l = nl - 1; l >= 0; --l) {
-        const int N = p.dim[1][l], K = l ? p.dim[1][l - 1] : p.F;
-        const Src x = l ? Src{p.saved[1][l - 1] + row0 * K, K, rows, false} : feat;
-        float* nxt = cur == g0 ? g1 : g0;
-        lin_bwd_tile(cur, LD, p.saved[1][l] + row0 * N, p.act[1][l], x, p.w[1][l], K, N, slab + p.off_w[1][l], slab + p.off_b[1][l], first,
-                     l ? Dst{nxt, LD, TR} : dx, false, rows);
-        cur = nxt;
-    }
+    if (r < rows) eps_greedy(qs + r * LQ, p.A, row0 + r, s);
 }
 
 __global__ __launch_bounds__(256) void c51_bwd_kernel(AcnetArgs p, C51Args c) {
     __shared__ __attribute__((aligned(16))) float buf[3 * TR * LD];
     __shared__ __attribute__((aligned(16))) float vt[TR * LV];
-    float* lg = buf + 2 * TR * LD;
-    const int NZ = p.A * c.Z;
-    for (int tile = blockIdx.x; tile < p.ntiles; tile += p.S) {
-        const long long row0 = (long long)tile * TR;
-        const int rows = p.B - row0 < TR ? (int)(p.B - row0) : TR;
-        for (int e = threadIdx.x; e < TR * NZ; e += blockDim.x) {
-            const int r = e / NZ, n = e - r * NZ;
-            lg[r * LD + n] = r < rows ? c.dlogits[(row0 + r) * NZ + n] : 0.f;
-        }
-        __syncthreads();
-        c51_bwd_tile(p, c, row0, rows, tile == (int)blockIdx.x, buf, lg, vt);
-        __syncthreads();
-    }
+    wide_bwd_tiles(p, c.Z, c.dlogits, buf, vt);
 }
 
 // what the row threads of c51_td leave for the (row, atom) and (row, column) threads
@@ -205,28 +108,16 @@ __device__ void c51_td_rows(const AcnetArgs& p, const C51Args& c, const C51TdArg
     float* M = buf + TR * LD;
     if (tid < TR) {                                     // thread r: the row's actions, its inputs and the softmax of the action taken
         const int r = tid;
-        int act = 0, star = 0, done = 1;
-        float rw = 0.f, g = 0.f, wt = 0.f, mx = 0.f, se = 1.f, q = 0.f;
+        TdRow in{0, 0, 1, 0.f, 0.f, 0.f};
+        float mx = 0.f, se = 1.f, q = 0.f;
         if (r < rows) {
-            const long long row = row0 + r;
-            const long long a = s.actions[row];
-            act = (int)(a < 0 ? 0 : a >= A ? A - 1 : a);
-            done = s.dones[row] ? 1 : 0;
-            rw = s.rewards[row];
-            g = s.discounts ? s.discounts[row] : s.gamma;
-            wt = s.weights ? s.weights[row] : 1.f;
-            if (!done) {                                // a select: next_q of a finished row is not read
-                const float* nq = s.next_q + row * A;
-                float m = nq[0];
-                for (int k = 1; k < A; ++k)
-                    if (nq[k] > m) { m = nq[k]; star = k; }
-            }
-            const float* l = lg + r * LD + act * Z;
+            in = td_row(s.row, A, row0 + r);
+            const float* l = lg + r * LD + in.act * Z;
             lse_parts(l, Z, mx, se);
             for (int j = 0; j < Z; ++j) q = __fmaf_rn(expf(l[j] - mx) / se, atom(c, j), q);
         }
-        t.act[r] = act; t.star[r] = star; t.done[r] = done;
-        t.rw[r] = rw; t.g[r] = g; t.wt[r] = wt; t.mx[r] = mx; t.se[r] = se;
+        t.act[r] = in.act; t.star[r] = in.star; t.done[r] = in.done;
+        t.rw[r] = in.rw; t.g[r] = in.g; t.wt[r] = in.wt; t.mx[r] = mx; t.se[r] = se;
         t.rs[r][1] = q;
     }
     __syncthreads();
@@ -265,7 +156,7 @@ __device__ void c51_td_rows(const AcnetArgs& p, const C51Args& c, const C51TdArg
                 ce -= m[i] * ((l[i] - mx) - ls);
                 tz += m[i] * atom(c, i);
             }
-            if (s.row_loss) s.row_loss[row0 + r] = ce;
+            if (s.row.row_loss) s.row.row_loss[row0 + r] = ce;
         }
         t.sm[r] = sm;
         t.rs[r][0] = t.wt[r] * ce;
@@ -295,9 +186,9 @@ __global__ __launch_bounds__(256) void c51_td_kernel(AcnetArgs p, C51Args c, C51
         const long long row0 = (long long)tile * TR;
         const int rows = p.B - row0 < TR ? (int)(p.B - row0) : TR;
         const bool first = tile == (int)blockIdx.x;
-        c51_fwd_tile(p, c, row0, rows, buf, lg, vt);
+        wide_fwd_tile(p, c.Z, row0, rows, buf, lg, vt);
         c51_td_rows(p, c, s, row0, rows, first, buf, lg, t);
-        c51_bwd_tile(p, c, row0, rows, first, buf, lg, vt);
+        wide_bwd_tile(p, c.Z, row0, rows, first, buf, lg, vt);
         __syncthreads();
     }
 }

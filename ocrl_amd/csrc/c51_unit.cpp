@@ -120,7 +120,7 @@ int ocrl_c51_td_fwd_bwd(const ocrl_c51_desc* d, const float* features, const flo
     RC(head_begin(a, s, y, who, features, w, dw, ws, ws_floats));
     const C51Args c = c51_args(a, d, v_min, v_max);
     a.dx = dfeatures;
-    const C51TdArgs t{next_probs, next_q, actions, rewards, dones, discounts, weights, gamma, row_loss};
+    const C51TdArgs t{next_probs, {next_q, actions, rewards, dones, discounts, weights, gamma, row_loss}};
     RC(c51_td_launch(a, c, t, st));
     RC(reduce_dw(a, y, dw, st));
     return head_scalars_launch(a.scal_slab, y.S, d->B, false, scalars, st);

@@ -30,6 +30,18 @@ struct DqnTdArgs {
     float* abs_td;                                    // optional, out
 };
 
+// the TD inputs the distributional heads share (C51TdArgs, QrTdArgs and IqnTdArgs hold them as `row`; td_row of qhead_tile.h reads them):
+// each [B] but next_q [B, A], where the bootstrap action is looked for
+struct QTdArgs {
+    const float* next_q;
+    const long long* actions;
+    const float* rewards;
+    const unsigned char* dones;
+    const float *discounts, *weights;                 // may be null
+    float gamma;
+    float* row_loss;                                  // may be null
+};
+
 // the ring [N, E, ...] and one batch read of it
 struct ReplayGatherArgs {
     const unsigned char* obs;

@@ -1,8 +1,7 @@
 // DQN on the device (include/ocrl_hip_dqn.h): the collection step, the fused TD step and the replay ring's sampling and batch read.
 // The Q head is a chain of small Linear layers and runs on the actor-critic head's tile code (acnet_tile.h): a workgroup owns 16 batch
 // rows, the chain's activations stay in LDS and the Q values of the tile end in `lg`.
-//   dqn_act           the forward with the choice in the same launch: lane r of a tile flips row r's coin and takes the random action or
-//                     the lowest index of the maximum Q
+//   dqn_act           the forward with the choice in the same launch: lane r of a tile chooses for row r (eps_greedy of qhead_tile.h)
 //   dqn_td            forward, TD target, Huber loss, dQ and the backward per row tile in one kernel; Q and the layer cotangents never
 //                     leave LDS.  Partial dw go to the workgroup's slab, the three scalar sums to its row of scal_slab.  Two
 //                     instantiations: the plain step, and the one with the optional inputs of ocrl_hip_replay.h (double Q-learning,
@@ -13,8 +12,7 @@
 //   replay_sample     one thread per row: a valid slot and an environment from the counter RNG
 // Order of every sum: acnet.hip's for the layers and the slabs; a tile's scalar terms are added in row order, the tiles of a slab in tile
 // order, the slabs in slab order.  No atomics.
-#include "acnet_tile.h"
-#include "dqn.h"
+#include "qhead_tile.h"
 
 namespace {
 
@@ -26,37 +24,15 @@ __global__ __launch_bounds__(256) void dqn_act_kernel(AcnetArgs p, DqnActArgs s)
     const int rows = p.B - row0 < TR ? (int)(p.B - row0) : TR;
     fwd_tile(p, row0, rows, buf, lg, nullptr);          // ends on a barrier: lg is complete (no value head: vl is not touched)
     const int r = threadIdx.x;
-    if (r >= rows) return;
-    const long long row = row0 + r;
-    const float* z = lg + r * LA;
-    const int A = p.A;
-    float m = z[0];
-    int best = 0;
-    for (int a = 1; a < A; ++a)
-        if (z[a] > m) { m = z[a]; best = a; }           // strict: the lowest index of the maximum
-    uint32_t b0, b1;                                    // the 24 bits of u0 and u1
-    if (s.uniforms) {
-        b0 = (uint32_t)(s.uniforms[2 * row] * 16777216.f);
-        b1 = (uint32_t)(s.uniforms[2 * row + 1] * 16777216.f);
-    } else {
-        const uint2 w = rng_bits4(s.seed, SITE_DQN_ACT, s.row_offset + (unsigned long long)row);
-        b0 = w.x >> 8; b1 = w.y >> 8;
-    }
-    const float u0 = (float)b0 * (1.f / 16777216.f);
-    int act = best;
-    if (u0 < s.epsilon) {
-        act = (int)(((unsigned long long)b1 * (unsigned long long)A) >> 24);
-        act = act < A ? act : A - 1;                    // only a given uniform >= 1 gets here
-    }
-    s.actions[row] = act;
+    if (r < rows) eps_greedy(lg + r * LA, p.A, row0 + r, s);
 }
 
 __global__ __launch_bounds__(256) void dqn_act_uniforms_kernel(unsigned long long seed, unsigned long long row_offset, long long n, float* __restrict__ out) {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     const uint2 w = rng_bits4(seed, SITE_DQN_ACT, row_offset + (unsigned long long)i);
-    out[2 * i] = (float)(w.x >> 8) * (1.f / 16777216.f);
-    out[2 * i + 1] = (float)(w.y >> 8) * (1.f / 16777216.f);
+    out[2 * i] = unit24(w.x >> 8);
+    out[2 * i + 1] = unit24(w.y >> 8);
 }
 
 // The TD step of one tile after its forward: thread r < 16 owns row r.  Replaces the Q values in lg by dL/dQ (L = the mean loss) and adds

@@ -24,16 +24,13 @@ struct IqnArgs {
     float* dfeat;                                     // dfeatures [Bb, F] or null
 };
 
-// the TD target's inputs, each [Bb] but next_quantiles [Bb, A, Np] and next_q [Bb, A]; part / tha [E] are the workspace's blocks
+// the TD target's inputs: next_quantiles [Bb, A, Np], the shared ones (dqn.h, over the Bb batch rows) and the Huber threshold; part / tha
+// [E] are the workspace's blocks
 struct IqnTdArgs {
-    const float *next_quantiles, *next_q;
+    const float* next_quantiles;
     int Np;
-    const long long* actions;
-    const float* rewards;
-    const unsigned char* dones;
-    const float *discounts, *weights;                 // may be null
-    float gamma, kappa;
-    float* row_loss;                                  // may be null
+    QTdArgs row;
+    float kappa;
     float *part, *tha;                                // (1 / Np) sum_j rho_ij and theta[b, a_b, i] of expanded row b * N + i
 };
 

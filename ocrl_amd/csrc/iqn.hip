@@ -8,7 +8,7 @@
 //   iqn_fwd     a tile's forward; theta to [B, A, N] with stride N
 //   iqn_q       one thread per (b, a): q = the mean of theta over s, serial
 //   iqn_act     one workgroup per batch row walks its samples in tiles of 16, ascending: thread a adds theta[s][a] to its sum in s order
-//               (the serial sum of iqn_q), then thread 0 flips the coin and chooses (dqn_act's rule and words)
+//               (the serial sum of iqn_q), then thread 0 chooses for the row (eps_greedy of qhead_tile.h)
 //   iqn_bwd     cotangent of theta -> the output Linear's, the chain's and the embedding's backward into the workgroup's slab; z is
 //               rebuilt from phi in the third tile (the chain's first layer reads it), dz * phi goes to the workspace for dfeatures
 //   iqn_dx      one thread per (b, j): dfeatures = the sum of dz * phi over s, serial
@@ -20,9 +20,9 @@
 //               scalar terms into the slabs' sums (tile_scalars); and dfeatures as iqn_dx
 // The fold of the slabs is acnet_reduce (slab order), the fold of the scalars head_scalars (slab order).
 // Order of every sum: acnet.hip's for the layers and the slabs; every sum over s, i or j is serial in ascending index.  No atomics.
-#include "acnet_tile.h"
 #include "fqf.h"
 #include "iqn.h"
+#include "qhead_tile.h"
 
 namespace {
 
@@ -33,7 +33,7 @@ static_assert((3 * TR * LD + TR * LC + TR * LA) * sizeof(float) + 1024 <= 65536,
 // the fraction of sample s of row R: the top 24 bits of word s & 1 of group 32 R + (s >> 1)
 __device__ __forceinline__ float iqn_tau(unsigned long long seed, unsigned long long R, int s) {
     const uint2 w = rng_bits4(seed, SITE_IQN_TAU, R * 32ull + (unsigned long long)(s >> 1));
-    return (float)(((s & 1) ? w.y : w.x) >> 8) * (1.f / 16777216.f);
+    return unit24(((s & 1) ? w.y : w.x) >> 8);
 }
 
 __global__ __launch_bounds__(256) void iqn_taus_kernel(unsigned long long seed, unsigned long long row_offset, long long total, int N,
@@ -42,13 +42,6 @@ __global__ __launch_bounds__(256) void iqn_taus_kernel(unsigned long long seed, 
     if (e >= total) return;
     const long long b = e / N;
     out[e] = iqn_tau(seed, row_offset + (unsigned long long)b, (int)(e - b * N));
-}
-
-// the serial mean over the fractions: every q of the head is formed by this sum
-__device__ __forceinline__ float iqn_mean(const float* th, int N) {
-    float s = 0.f;
-    for (int i = 0; i < N; ++i) s += th[i];
-    return s * (1.f / (float)N);
 }
 
 // The cosine tile of the 16 expanded rows whose fractions are in tl (LDS; a barrier has passed): ct [16][LC], rows past `rows` zero.
@@ -111,7 +104,7 @@ __global__ __launch_bounds__(256) void iqn_fwd_kernel(AcnetArgs p, IqnArgs c) {
 
 __global__ __launch_bounds__(256) void iqn_q_kernel(const float* __restrict__ theta, long long total, int N, float* __restrict__ q) {
     const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e < total) q[e] = iqn_mean(theta + e * N, N);
+    if (e < total) q[e] = serial_mean(theta + e * N, N);
 }
 
 // One workgroup per batch row.  p.B is the number of expanded rows, c.Bb the grid.  FQF (include/ocrl_hip_fqf.h: ocrl_fqf_act): c.taus is
@@ -158,30 +151,11 @@ __global__ __launch_bounds__(256) void iqn_act_kernel(AcnetArgs p, IqnArgs c, Dq
         if (c.q) c.q[row * A + tid] = q;
     }
     __syncthreads();
-    if (tid) return;
-    float m = qs[0];
-    int best = 0;
-    for (int a = 1; a < A; ++a)
-        if (qs[a] > m) { m = qs[a]; best = a; }         // strict: the lowest index of the maximum
-    uint32_t b0, b1;                                    // the 24 bits of u0 and u1
-    if (s.uniforms) {
-        b0 = (uint32_t)(s.uniforms[2 * row] * 16777216.f);
-        b1 = (uint32_t)(s.uniforms[2 * row + 1] * 16777216.f);
-    } else {
-        const uint2 w = rng_bits4(s.seed, SITE_DQN_ACT, s.row_offset + (unsigned long long)row);
-        b0 = w.x >> 8; b1 = w.y >> 8;
-    }
-    const float u0 = (float)b0 * (1.f / 16777216.f);
-    int act = best;
-    if (u0 < s.epsilon) {
-        act = (int)(((unsigned long long)b1 * (unsigned long long)A) >> 24);
-        act = act < A ? act : A - 1;                    // only a given uniform >= 1 gets here
-    }
-    s.actions[row] = act;
+    if (!tid) eps_greedy(qs, A, row, s);
 }
 
 // Backward of one tile from theta's cotangent in ot (LDS), with the cosines in ct and z in the third tile of buf: the output Linear and
-// the chain into dz (qr_bwd_tile's steps), dz * phi to the workspace, dphi = dz * features in place, the embedding's backward.
+// the chain into dz (bwd_trunk), dz * phi to the workspace, dphi = dz * features in place, the embedding's backward.
 __device__ void iqn_bwd_tile(const AcnetArgs& p, const IqnArgs& c, long long e0, int rows, bool first, float* buf, float* ct, float* ot) {
     float* slab = p.slab + (long long)blockIdx.x * p.slab_stride;
     const int nl = p.n[1], F = p.dim[0][0];
@@ -189,15 +163,7 @@ __device__ void iqn_bwd_tile(const AcnetArgs& p, const IqnArgs& c, long long e0,
     float *g0 = buf, *g1 = buf + TR * LD, *zt = buf + 2 * TR * LD;
     const Src lat = nl ? Src{p.saved[1][nl - 1] + e0 * Kl, Kl, rows, false} : lsrc(zt);
     lin_bwd_tile(ot, LA, nullptr, 0, lat, p.wa, Kl, p.A, slab + p.off_wa, slab + p.off_ba, first, Dst{g0, LD, TR}, false, rows);
-    float* cur = g0;
-    for (int l = nl - 1; l >= 0; --l) {
-        const int W = p.dim[1][l], K = l ? p.dim[1][l - 1] : F;
-        const Src x = l ? Src{p.saved[1][l - 1] + e0 * K, K, rows, false} : lsrc(zt);
-        float* nxt = cur == g0 ? g1 : g0;
-        lin_bwd_tile(cur, LD, p.saved[1][l] + e0 * W, p.act[1][l], x, p.w[1][l], K, W, slab + p.off_w[1][l], slab + p.off_b[1][l], first,
-                     Dst{nxt, LD, TR}, false, rows);
-        cur = nxt;
-    }
+    float* cur = bwd_trunk(p, 1, g0, g0, g1, lsrc(zt), F, nullptr, false, slab, first, e0, rows);       // dz: layer 0's dx stays in LDS
     const float* phi = p.saved[0][0] + e0 * F;
     for (int e = threadIdx.x; e < rows * F; e += blockDim.x) {      // rows past `rows`: lin_bwd_tile reads them as 0
         const int r = e / F, j = e - r * F;
@@ -259,28 +225,6 @@ __global__ __launch_bounds__(256) void iqn_dx_kernel(IqnArgs c, int F) {
     iqn_dx_rows(c, F, b0, c.Bb - b0 < TR ? (int)(c.Bb - b0) : TR);
 }
 
-// a batch row's part of the TD step: what the tiles and the fold both read, formed by the same code
-struct TdRow {
-    int act, star, done;
-    float rw, g, wt;
-};
-__device__ __forceinline__ TdRow iqn_td_row(const IqnTdArgs& s, int A, long long row) {
-    TdRow t;
-    const long long a = s.actions[row];
-    t.act = (int)(a < 0 ? 0 : a >= A ? A - 1 : a);
-    t.done = s.dones[row] ? 1 : 0;
-    t.rw = s.rewards[row];
-    t.g = s.discounts ? s.discounts[row] : s.gamma;
-    t.wt = s.weights ? s.weights[row] : 1.f;
-    t.star = 0;
-    if (!t.done) {                                      // a select: next_q of a finished row is not read
-        const float* nq = s.next_q + row * A;
-        float m = nq[0];
-        for (int k = 1; k < A; ++k)
-            if (nq[k] > m) { m = nq[k]; t.star = k; }
-    }
-    return t;
-}
 // T_j of a row
 __device__ __forceinline__ float iqn_td_target(const IqnTdArgs& s, const TdRow& t, int A, long long row, int j) {
     return t.done ? t.rw : fmaf(t.g, s.next_quantiles[(row * A + t.star) * s.Np + j], t.rw);
@@ -295,7 +239,7 @@ __device__ void iqn_td_rows(const AcnetArgs& p, const IqnArgs& c, const IqnTdArg
     const long long b0 = e0 / N;
     const int nb = (int)((e0 + rows - 1) / N - b0) + 1;             // batch rows present in the tile: at most 16
     float* T = buf;
-    if (tid < nb) tr[tid] = iqn_td_row(s, A, b0 + tid);
+    if (tid < nb) tr[tid] = td_row(s.row, A, b0 + tid);
     __syncthreads();
     for (int e = tid; e < nb * Np; e += blockDim.x) {
         const int lb = e / Np, j = e - lb * Np;
@@ -313,12 +257,7 @@ __device__ void iqn_td_rows(const AcnetArgs& p, const IqnArgs& c, const IqnTdArg
             const float x = th[act], tau = tl[r];
             const float* Tr = T + lb * LD;
             float ls = 0.f, gs = 0.f;
-            for (int j = 0; j < Np; ++j) {
-                const float u = Tr[j] - x, au = fabsf(u);
-                const float w = fabsf(tau - (u < 0.f ? 1.f : 0.f));
-                ls += w * (au <= kappa ? 0.5f * u * u : kappa * (au - 0.5f * kappa));
-                gs += w * fminf(fmaxf(u, -kappa), kappa);
-            }
+            for (int j = 0; j < Np; ++j) qhuber_pair(Tr[j], x, tau, kappa, ls, gs);
             s.part[e0 + r] = invNp * ls;
             s.tha[e0 + r] = x;
             d = -(tr[lb].wt / (float)c.Bb) * invNp * gs;
@@ -357,14 +296,14 @@ __global__ __launch_bounds__(256) void iqn_td_fold_kernel(IqnArgs c, IqnTdArgs s
             float wl = 0.f, q = 0.f, tm = 0.f;
             if (r < rows) {
                 const long long row = b0 + r;
-                const TdRow t = iqn_td_row(s, A, row);
+                const TdRow t = td_row(s.row, A, row);
                 float ql = 0.f;
                 for (int i = 0; i < N; ++i) ql += s.part[row * N + i];
-                q = iqn_mean(s.tha + row * N, N);
+                q = serial_mean(s.tha + row * N, N);
                 float ts = 0.f;
                 for (int j = 0; j < Np; ++j) ts += iqn_td_target(s, t, A, row, j);
                 tm = ts * (1.f / (float)Np);
-                if (s.row_loss) s.row_loss[row] = ql;
+                if (s.row.row_loss) s.row.row_loss[row] = ql;
                 wl = t.wt * ql;
             }
             rs[r][0] = wl; rs[r][1] = q; rs[r][2] = tm;

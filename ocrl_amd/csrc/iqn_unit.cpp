@@ -191,7 +191,7 @@ int ocrl_iqn_td_fwd_bwd(const ocrl_iqn_desc* d, const float* features, const flo
     RC(head_begin(a, sp.s, l.y, who, nullptr, w, dw, ws, ws_floats));
     IqnArgs c = iqn_args(d, features, taus);
     if (dfeatures) { c.dfeat = dfeatures; c.dzphi = ws + l.dzphi; }
-    const IqnTdArgs t{next_quantiles, next_q, Np, actions, rewards, dones, discounts, weights, gamma, kappa, row_loss, ws + l.part, ws + l.tha};
+    const IqnTdArgs t{next_quantiles, Np, {next_q, actions, rewards, dones, discounts, weights, gamma, row_loss}, kappa, ws + l.part, ws + l.tha};
     RC(iqn_td_launch(a, c, t, st));
     RC(reduce_dw(a, l.y, dw, st));
     return head_scalars_launch(a.scal_slab, cdiv(d->B, 16) < ACNET_MAX_SLABS ? cdiv(d->B, 16) : ACNET_MAX_SLABS, d->B, false, scalars, st);

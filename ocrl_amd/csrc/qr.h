@@ -18,15 +18,11 @@ struct QrArgs {
     const float* dquantiles;                          // qr_bwd: [B, A, N]
 };
 
-// the TD target's inputs, each [B] but next_quantiles [B, A, N] and next_q [B, A]
+// the TD target's inputs: next_quantiles [B, A, N], the shared ones (dqn.h) and the Huber threshold
 struct QrTdArgs {
-    const float *next_quantiles, *next_q;
-    const long long* actions;
-    const float* rewards;
-    const unsigned char* dones;
-    const float *discounts, *weights;                 // may be null
-    float gamma, kappa;
-    float* row_loss;                                  // may be null
+    const float* next_quantiles;
+    QTdArgs row;
+    float kappa;
 };
 
 int qr_fwd_launch(const AcnetArgs& a, const QrArgs& c, hipStream_t st);

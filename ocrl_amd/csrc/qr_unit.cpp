@@ -117,7 +117,7 @@ int ocrl_qr_td_fwd_bwd(const ocrl_qr_desc* d, const float* features, const float
     RC(head_begin(a, s, y, who, features, w, dw, ws, ws_floats));
     const QrArgs c = qr_args(a, d);
     a.dx = dfeatures;
-    const QrTdArgs t{next_quantiles, next_q, actions, rewards, dones, discounts, weights, gamma, kappa, row_loss};
+    const QrTdArgs t{next_quantiles, {next_q, actions, rewards, dones, discounts, weights, gamma, row_loss}, kappa};
     RC(qr_td_launch(a, c, t, st));
     RC(reduce_dw(a, y, dw, st));
     return head_scalars_launch(a.scal_slab, y.S, d->B, false, scalars, st);

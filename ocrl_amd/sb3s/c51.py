@@ -133,11 +133,7 @@ class CategoricalQNetwork(QHead):
         x, ps = _bridge.inputs(_WHO, features.detach(), self._param_list())
         B, F = x.shape
         d, _ = _desc(B, F, self.n_actions, self.n_atoms, *self._layout(), self.dueling, x.device, keep=False)
-        actions = torch.empty(B, device=x.device, dtype=torch.int64)
-        q = torch.empty(B, self.n_actions, device=x.device)
-        _bridge.launch(x.device, _lib.lib().ocrl_c51_act, ctypes.byref(d), _lib.ptr(x), _lib.ptrs(ps), self.v_min, self.v_max, int(seed),
-                       int(row_offset), float(epsilon), _lib.ptr(uniforms), _lib.ptr(actions), _lib.ptr(q))
-        return actions, q
+        return self._launch_act(_lib.lib().ocrl_c51_act, d, x, ps, seed, row_offset, epsilon, uniforms, before=(self.v_min, self.v_max))
 
 
 def c51_loss(policy, features, next_probs, next_q, actions, rewards, dones, gamma, discounts=None, weights=None):

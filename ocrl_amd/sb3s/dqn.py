@@ -131,6 +131,12 @@ class QNetwork(QHead):
     def forward(self, features):
         return _QnetFn.apply(features, *self._layout(), self.n_actions, *self._param_list())
 
+    def act(self, features, seed, row_offset, epsilon, uniforms):
+        """(actions int64 [B], q [B, n_actions]) of ``ocrl_dqn_act``: DQNPolicy.act's launch for this head"""
+        x, ps = _bridge.inputs(_WHO, features.detach(), self._param_list())
+        d, _ = _desc(*x.shape, self.n_actions, *self._layout(), x.device, keep=False)
+        return self._launch_act(_lib.lib().ocrl_dqn_act, d, x, ps, seed, row_offset, epsilon, uniforms)
+
 
 class DQNPolicy(nn.Module):
     """features_extractor -> QNetwork.  ``features_extractor`` is a module with ``features_dim`` (an OCRExtractor), or
@@ -147,7 +153,7 @@ class DQNPolicy(nn.Module):
     follow ``train()`` / ``eval()``.  ``fqf`` (with ``n_tau_samples`` in 2 .. 32) makes the head a
     FullyParameterizedQuantileQNetwork of ``n_tau_samples`` proposed fractions: ``q_values`` and ``act`` evaluate it at the fractions its
     ``fraction_net`` proposes for the row (``ocrl_fqf_fractions``, then ``ocrl_fqf_act``), ``deterministic`` or not, and ``n_act_samples``
-    is not read."""
+    is not read.  ``head_kind`` names the head that was built ("dqn", "c51", "qr", "iqn" or "fqf"); ``DQN.train_step`` picks its step by it."""
 
     def __init__(self, observation_space, action_space, lr_schedule=None, config=None, features_extractor=None, features_extractor_class=None,
                  features_extractor_kwargs=None, net_arch=(64, 64), activation="relu", n_atoms=1, v_min=0.0, v_max=2.0, dueling=False, noisy=False,
@@ -173,6 +179,7 @@ class DQNPolicy(nn.Module):
         self.fqf = bool(fqf)
         if self.fqf:
             _check_fqf(f"{_WHO}.DQNPolicy", self.n_tau_samples, self.n_tau_samples, False, self.dueling, self.n_atoms, self.n_quantiles)
+            self.head_kind = "fqf"
             self.q_net = FullyParameterizedQuantileQNetwork(self.features_dim, n, self.n_tau_samples, self.n_cos, net_arch, activation, **noise)
         elif self.n_tau_samples != 0:
             if self.n_tau_samples < 0 or self.n_atoms != 1 or self.n_quantiles != 0:
@@ -182,15 +189,19 @@ class DQNPolicy(nn.Module):
             if self.dueling:
                 raise ValueError(f"{_WHO}.DQNPolicy: dueling is not built for the implicit quantile head (got dueling=True with n_tau_samples "
                                  f"{n_tau_samples})")
+            self.head_kind = "iqn"
             self.q_net = ImplicitQuantileQNetwork(self.features_dim, n, self.n_cos, self.n_act_samples, net_arch, activation, **noise)
         elif self.n_quantiles != 0:
             if self.n_quantiles < 0 or self.n_atoms != 1:
                 raise ValueError(f"{_WHO}.DQNPolicy: n_quantiles >= 1 (the quantile head) goes with n_atoms = 1: one return distribution at a "
                                  f"time (got n_quantiles {n_quantiles}, n_atoms {n_atoms})")
+            self.head_kind = "qr"
             self.q_net = QuantileQNetwork(self.features_dim, n, self.n_quantiles, net_arch, activation, self.dueling, **noise)
         elif self.n_atoms >= 2:
+            self.head_kind = "c51"
             self.q_net = CategoricalQNetwork(self.features_dim, n, self.n_atoms, v_min, v_max, net_arch, activation, self.dueling, **noise)
         elif self.n_atoms == 1 and not self.dueling:
+            self.head_kind = "dqn"
             self.q_net = QNetwork(self.features_dim, n, net_arch, activation, **noise)
         else:
             raise ValueError(f"{_WHO}.DQNPolicy: n_atoms is 1 (the scalar head) or >= 2 (the categorical head), and dueling is built for the "
@@ -235,7 +246,7 @@ class DQNPolicy(nn.Module):
             finally:
                 self.q_net._noise = chosen
         x = _bridge.gpu_input(_WHO, features.detach())
-        B, F = x.shape
+        B = x.shape[0]
         eps = 0.0 if deterministic else float(self.exploration_rate if epsilon is None else epsilon)
         if uniforms is not None:
             uniforms = uniforms.to(device=x.device, dtype=torch.float32).reshape(-1).contiguous()
@@ -246,23 +257,13 @@ class DQNPolicy(nn.Module):
         if row_offset is None:
             row_offset = self._sample_rows
             self._sample_rows += B
-        if self.fqf:                                              # the fractions are proposed, not drawn: no stream of their own
-            return (*self.q_net.act(x, self._sample_seed or 0, row_offset, eps, uniforms), None)
-        if self.n_tau_samples:
+        sampled = {}
+        if self.head_kind == "iqn":                               # the one head that draws fractions of its own (fqf's are proposed)
             if not deterministic and self._sample_seed is None:
                 raise RuntimeError(f"{_WHO}.DQNPolicy.act: no stream for the sampled fractions: call policy.set_sampling(seed) or act "
                                    "deterministically (the midpoint fractions)")
-            return (*self.q_net.act(x, self._sample_seed or 0, row_offset, eps, uniforms, deterministic=deterministic), None)
-        if self.n_atoms >= 2 or self.n_quantiles:
-            return (*self.q_net.act(x, self._sample_seed or 0, row_offset, eps, uniforms), None)
-        dims, acts = self.q_net._layout()
-        x, ps = _bridge.inputs(_WHO, x, self.q_net._param_list())
-        d, _ = _desc(B, F, self.q_net.n_actions, dims, acts, x.device, keep=False)
-        actions = torch.empty(B, device=x.device, dtype=torch.int64)
-        q = torch.empty(B, self.q_net.n_actions, device=x.device)
-        _bridge.launch(x.device, _lib.lib().ocrl_dqn_act, ctypes.byref(d), _lib.ptr(x), _lib.ptrs(ps), self._sample_seed or 0, int(row_offset), eps,
-                       _lib.ptr(uniforms), _lib.ptr(actions), _lib.ptr(q))
-        return actions, q, None
+            sampled = dict(deterministic=deterministic)
+        return (*self.q_net.act(x, self._sample_seed or 0, row_offset, eps, uniforms, **sampled), None)
 
     def forward(self, obs, deterministic: bool = False):
         return self.act(self.extract_features(obs), deterministic=deterministic)
@@ -716,29 +717,29 @@ class DQN:
         return munchausen_targets(q2[B:], q2[:B], batch.actions, batch.rewards, batch.dones, self.munchausen_alpha, self.munchausen_tau,
                                   self.munchausen_clip, next_quantiles=None if quantiles2 is None else quantiles2[:B])
 
+    def _target_obs(self, batch):
+        """the observations the target network is evaluated on: the next ones, or ``_both_obs`` under munchausen"""
+        return self._both_obs(batch) if self.munchausen else self._obs(batch.next_observations)
+
+    def _targets(self, batch, q, quantiles=None):
+        """(rewards, next_q, next_quantiles) as the heads' losses take them, from the target network's values on ``_target_obs``:
+        rewritten by ``_munchausen``, else the batch's rewards and the values as they are"""
+        return self._munchausen(batch, q, quantiles) if self.munchausen else (batch.rewards, q, quantiles)
+
     def _train_step_dqn(self, batch, weights):
         """the scalar head's part of ``train_step``: (loss, metrics, the rows' |TD error| under prioritized replay).  The target network
         gives the next observations' Q, the online network names the bootstrap action under double_q; with neither that nor n_step > 1
         nor prioritized replay the step is ocrl_dqn_td_fwd_bwd's (``dqn_loss``)."""
-        if self.munchausen:
-            with torch.no_grad():
-                q2 = self.target.q_values(self._both_obs(batch))
-                rewards, next_q, _ = self._munchausen(batch, q2)
-            self._online_turn()
-            features = self.policy.extract_features(self._obs(batch.observations))
-            out = dqn_loss(self.policy, features, next_q, batch.actions, rewards, batch.dones, self.gamma, discounts=batch.discounts,
-                           weights=weights, return_abs_td=self.prioritized_replay)
-            return out if self.prioritized_replay else (*out, None)
-        next_obs = self._obs(batch.next_observations)
+        target_obs = self._target_obs(batch)
         with torch.no_grad():
-            next_q = self.target.q_values(next_obs)
+            rewards, next_q, _ = self._targets(batch, self.target.q_values(target_obs))
         self._online_turn()
         next_q_online = None
-        if self.double_q:
+        if self.double_q:                                             # refused with munchausen: target_obs is the next observations
             with torch.no_grad():
-                next_q_online = self.policy.q_values(next_obs)
+                next_q_online = self.policy.q_values(target_obs)
         features = self.policy.extract_features(self._obs(batch.observations))
-        out = dqn_loss(self.policy, features, next_q, batch.actions, batch.rewards, batch.dones, self.gamma, next_q_online=next_q_online,
+        out = dqn_loss(self.policy, features, next_q, batch.actions, rewards, batch.dones, self.gamma, next_q_online=next_q_online,
                        discounts=batch.discounts, weights=weights, return_abs_td=self.prioritized_replay)
         return out if self.prioritized_replay else (*out, None)
 
@@ -761,23 +762,16 @@ class DQN:
         """the quantile head's part of ``train_step``: (loss, metrics, the rows' quantile losses, which take the place of
         |TD error| in the priority store).  The target network gives the next observations' quantiles, the online network names the
         bootstrap action under double_q, ``qr_loss`` does the rest."""
-        if self.munchausen:
-            with torch.no_grad():
-                quantiles2, q2 = self.target.q_net.quantiles(self.target.extract_features(self._both_obs(batch)))
-                rewards, next_q, next_quantiles = self._munchausen(batch, q2, quantiles2)
-            self._online_turn()
-            features = self.policy.extract_features(self._obs(batch.observations))
-            return qr_loss(self.policy, features, next_quantiles, next_q, batch.actions, rewards, batch.dones, self.gamma, self.huber_kappa,
-                           discounts=batch.discounts, weights=weights)
-        next_obs = self._obs(batch.next_observations)
+        target_obs = self._target_obs(batch)
         with torch.no_grad():
-            next_quantiles, next_q = self.target.q_net.quantiles(self.target.extract_features(next_obs))
+            quantiles, q = self.target.q_net.quantiles(self.target.extract_features(target_obs))
+            rewards, next_q, next_quantiles = self._targets(batch, q, quantiles)
         self._online_turn()
-        if self.double_q:
+        if self.double_q:                                             # refused with munchausen: target_obs is the next observations
             with torch.no_grad():
-                _, next_q = self.policy.q_net.quantiles(self.policy.extract_features(next_obs))
+                _, next_q = self.policy.q_net.quantiles(self.policy.extract_features(target_obs))
         features = self.policy.extract_features(self._obs(batch.observations))
-        return qr_loss(self.policy, features, next_quantiles, next_q, batch.actions, batch.rewards, batch.dones, self.gamma, self.huber_kappa,
+        return qr_loss(self.policy, features, next_quantiles, next_q, batch.actions, rewards, batch.dones, self.gamma, self.huber_kappa,
                        discounts=batch.discounts, weights=weights)
 
     def _train_taus(self, k, n):
@@ -792,24 +786,20 @@ class DQN:
         of its own and their mean, the online network names the bootstrap action under double_q from N' fractions of its own, and
         ``iqn_loss`` evaluates the online network at N fractions and does the rest."""
         N, Np = self.n_tau_samples, self.n_tau_prime_samples or self.n_tau_samples
-        if self.munchausen:
-            with torch.no_grad():
-                taus2 = torch.cat([self._train_taus(1, Np), self._train_taus(2, Np)])
-                quantiles2, q2 = self.target.q_net.quantiles(self.target.extract_features(self._both_obs(batch)), taus2)
-                rewards, next_q, next_quantiles = self._munchausen(batch, q2, quantiles2)
-            self._online_turn()
-            features = self.policy.extract_features(self._obs(batch.observations))
-            return iqn_loss(self.policy, features, self._train_taus(0, N), next_quantiles, next_q, batch.actions, rewards, batch.dones, self.gamma,
-                            self.huber_kappa, discounts=batch.discounts, weights=weights)
-        next_obs = self._obs(batch.next_observations)
+        target_obs = self._target_obs(batch)
         with torch.no_grad():
-            next_quantiles, next_q = self.target.q_net.quantiles(self.target.extract_features(next_obs), self._train_taus(1, Np))
+            target_features = self.target.extract_features(target_obs)
+            taus = self._train_taus(1, Np)
+            if self.munchausen:                                       # the observations' rows of _both_obs take draw 2
+                taus = torch.cat([taus, self._train_taus(2, Np)])
+            quantiles, q = self.target.q_net.quantiles(target_features, taus)
+            rewards, next_q, next_quantiles = self._targets(batch, q, quantiles)
         self._online_turn()
-        if self.double_q:
+        if self.double_q:                                             # refused with munchausen: target_obs is the next observations
             with torch.no_grad():
-                _, next_q = self.policy.q_net.quantiles(self.policy.extract_features(next_obs), self._train_taus(2, Np))
+                _, next_q = self.policy.q_net.quantiles(self.policy.extract_features(target_obs), self._train_taus(2, Np))
         features = self.policy.extract_features(self._obs(batch.observations))
-        return iqn_loss(self.policy, features, self._train_taus(0, N), next_quantiles, next_q, batch.actions, batch.rewards, batch.dones, self.gamma,
+        return iqn_loss(self.policy, features, self._train_taus(0, N), next_quantiles, next_q, batch.actions, rewards, batch.dones, self.gamma,
                         self.huber_kappa, discounts=batch.discounts, weights=weights)
 
     def _train_step_fqf(self, batch, weights):
@@ -835,14 +825,12 @@ class DQN:
 
     def train_step(self):
         """one gradient step: a batch from the replay buffer (``_draw_batch``), the head's loss against the target network
-        (``_train_step_dqn``, with n_atoms > 1 ``_train_step_c51``, with n_quantiles > 0 ``_train_step_qr``, with n_tau_samples > 0
-        ``_train_step_iqn``), the backward through the
+        (``_train_step_`` + the policy's ``head_kind``, looked up on the instance at the call), the backward through the
         extractor, clip + Adam, and under prioritized replay the rows' errors back into the priority store.  Nothing is read from the device: the scalars
         add up in ``_acc`` until a callback reads them."""
         batch, idx, weights = self._draw_batch()
         self._draw_train_noise()
-        step = self._train_step_fqf if self.fqf else self._train_step_iqn if self.n_tau_samples > 0 else self._train_step_qr if self.n_quantiles > 0 else self._train_step_c51 if self.n_atoms > 1 else self._train_step_dqn
-        loss, m, row_err = step(batch, weights)
+        loss, m, row_err = getattr(self, "_train_step_" + self.policy.head_kind)(batch, weights)
         loss.backward()
         self._adam_step()
         if self.fqf:
@@ -908,6 +896,12 @@ class DQN:
         torch.save({"algo": self.ALGO, "policy": self.policy.state_dict(), "target": self.target.state_dict(), "optimizer": opt, "hyper": hyper,
                     "exploration_rate": float(self.policy.exploration_rate)}, path)
 
+    # load(): the keys (with the default a checkpoint from before them stands for) that must agree once the row's switch is on in the
+    # checkpoint or in this instance, in the order they are reported
+    _LOAD_GATED = (("n_tau_samples", (("n_tau_samples", 0), ("n_tau_prime_samples", 0), ("n_act_samples", 32), ("n_cos", 64))),
+                   ("munchausen", (("munchausen", False), ("munchausen_alpha", 0.9), ("munchausen_tau", 0.03), ("munchausen_clip", -1.0))),
+                   ("fqf", (("fqf", False), ("fqf_fraction_lr", 2.5e-9), ("fqf_ent_coef", 0.0))))
+
     def load(self, path):
         """restore the policy, the target network, Adam's state, the counters and the hyper-parameters saved by ``save`` into this instance
         (same policy layout); returns self.  The replay buffer stays as it is, unless the loaded ``n_step`` / ``prioritized_replay`` are not
@@ -923,18 +917,12 @@ class DQN:
         if int(hyper.get("n_quantiles", 0)) != self.n_quantiles:
             raise ValueError(f"{self._who}.load: the checkpoint was written with n_quantiles = {int(hyper.get('n_quantiles', 0))}, this instance "
                              f"has n_quantiles = {self.n_quantiles}")
-        for k, dflt in (("n_tau_samples", 0), ("n_tau_prime_samples", 0), ("n_act_samples", 32), ("n_cos", 64)):
-            have, mine = int(hyper.get(k, dflt)), getattr(self, k)
-            if have != mine and (self.n_tau_samples > 0 or int(hyper.get("n_tau_samples", 0)) > 0):
-                raise ValueError(f"{self._who}.load: the checkpoint was written with {k} = {have}, this instance has {k} = {mine}")
-        for k, dflt in (("munchausen", False), ("munchausen_alpha", 0.9), ("munchausen_tau", 0.03), ("munchausen_clip", -1.0)):
-            have, mine = type(dflt)(hyper.get(k, dflt)), getattr(self, k)
-            if have != mine and (self.munchausen or bool(hyper.get("munchausen", False))):
-                raise ValueError(f"{self._who}.load: the checkpoint was written with {k} = {have}, this instance has {k} = {mine}")
-        for k, dflt in (("fqf", False), ("fqf_fraction_lr", 2.5e-9), ("fqf_ent_coef", 0.0)):
-            have, mine = type(dflt)(hyper.get(k, dflt)), getattr(self, k)
-            if have != mine and (self.fqf or bool(hyper.get("fqf", False))):
-                raise ValueError(f"{self._who}.load: the checkpoint was written with {k} = {have}, this instance has {k} = {mine}")
+        for switch, pairs in self._LOAD_GATED:
+            gate = bool(getattr(self, switch)) or bool(hyper.get(switch, False))
+            for k, dflt in pairs:
+                have, mine = type(dflt)(hyper.get(k, dflt)), getattr(self, k)
+                if gate and have != mine:
+                    raise ValueError(f"{self._who}.load: the checkpoint was written with {k} = {have}, this instance has {k} = {mine}")
         opt = ck["optimizer"]
         if self.fqf and ("frac_sq" not in opt or opt["frac_sq"].shape != self.frac_sq.shape):
             raise ValueError(f"{self._who}.load: the checkpoint's optimiser state has no frac_sq of this policy's {self.frac_sq.numel()} entries")

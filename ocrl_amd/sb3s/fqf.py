@@ -101,11 +101,7 @@ class FullyParameterizedQuantileQNetwork(ImplicitQuantileQNetwork):
         B, F = x.shape
         taus = self.fractions(x).taus if taus is None else self._bounds(taus, B, x.device, "FullyParameterizedQuantileQNetwork.act")
         d = _lib.fqf_desc(B, F, self.n_actions, self.n_fractions, self.n_cos, *self._layout())
-        actions = torch.empty(B, device=x.device, dtype=torch.int64)
-        q = torch.empty(B, self.n_actions, device=x.device)
-        _bridge.launch(x.device, _lib.lib().ocrl_fqf_act, ctypes.byref(d), _lib.ptr(x), _lib.ptrs(ps), _lib.ptr(taus), int(seed), int(row_offset),
-                       float(epsilon), _lib.ptr(uniforms), _lib.ptr(actions), _lib.ptr(q))
-        return actions, q
+        return self._launch_act(_lib.lib().ocrl_fqf_act, d, x, ps, seed, row_offset, epsilon, uniforms, before=(_lib.ptr(taus),))
 
 
 def fqf_fraction_loss(policy, features, actions, weights=None, ent_coef=0.0, fractions=None):

@@ -174,11 +174,7 @@ class ImplicitQuantileQNetwork(QHead):
         if taus is not None:
             taus, N = _taus(taus, B, x.device, "ImplicitQuantileQNetwork.act")
         d = _lib.iqn_desc(B, F, self.n_actions, N, self.n_cos, *self._layout())
-        actions = torch.empty(B, device=x.device, dtype=torch.int64)
-        q = torch.empty(B, self.n_actions, device=x.device)
-        _bridge.launch(x.device, _lib.lib().ocrl_iqn_act, ctypes.byref(d), _lib.ptr(x), _lib.ptrs(ps), int(seed), int(row_offset), float(epsilon),
-                       _lib.ptr(uniforms), _lib.ptr(taus), _lib.ptr(actions), _lib.ptr(q))
-        return actions, q
+        return self._launch_act(_lib.lib().ocrl_iqn_act, d, x, ps, seed, row_offset, epsilon, uniforms, after=(_lib.ptr(taus),))
 
 
 def iqn_loss(policy, features, taus, next_quantiles, next_q, actions, rewards, dones, gamma, kappa=1.0, discounts=None, weights=None):

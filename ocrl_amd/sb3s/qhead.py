@@ -1,8 +1,13 @@
-"""What DQN's two heads (dqn.py's QNetwork, c51.py's CategoricalQNetwork) and their fused loss steps share: the stack of hidden layers
-under ``q_net``, the coercion of a step's per-row inputs and the backward of a step whose forward already wrote the gradients."""
+"""What DQN's five heads (dqn.py's QNetwork, c51.py's CategoricalQNetwork, qr.py's QuantileQNetwork, iqn.py's ImplicitQuantileQNetwork and
+fqf.py's FullyParameterizedQuantileQNetwork) and their fused loss steps share: the stack of hidden layers under ``q_net``, the launch
+every head's ``act`` ends on, the coercion of a step's per-row inputs and the backward of a step whose forward already wrote the
+gradients."""
+import ctypes
+
 import torch
 from torch import nn
 
+from .. import _bridge, _lib
 from .noisy import effective_params, linear
 
 _WHO = "ocrl_amd.sb3s"
@@ -41,6 +46,16 @@ class QHead(nn.Module):
         """(weight, bias) per Linear of ``q_net``, then of ``more``, as the kernels take them; with ``noisy`` the effective tensors of
         the current draw"""
         return effective_params([m for m in self.q_net if isinstance(m, nn.Linear)] + list(more), self._noise if self.noisy else None)
+
+    def _launch_act(self, fn, d, x, ps, seed, row_offset, epsilon, uniforms, before=(), after=()):
+        """what every head's ``act`` ends on: (actions int64 [B], q [B, n_actions]) of the launch fn(desc, x, params, *before, seed,
+        row_offset, epsilon, uniforms, *after, actions, q).  ``before`` is what an entry takes ahead of the stream (C51's support, FQF's
+        boundaries), ``after`` behind it (IQN's fractions)"""
+        actions = torch.empty(x.shape[0], device=x.device, dtype=torch.int64)
+        q = torch.empty(x.shape[0], self.n_actions, device=x.device)
+        _bridge.launch(x.device, fn, ctypes.byref(d), _lib.ptr(x), _lib.ptrs(ps), *before, int(seed), int(row_offset), float(epsilon),
+                       _lib.ptr(uniforms), *after, _lib.ptr(actions), _lib.ptr(q))
+        return actions, q
 
 
 def coerce(who, dev, what, *named):

@@ -135,11 +135,7 @@ class QuantileQNetwork(QHead):
         x, ps = _bridge.inputs(_WHO, features.detach(), self._param_list())
         B, F = x.shape
         d, _ = _desc(B, F, self.n_actions, self.n_quantiles, *self._layout(), self.dueling, x.device, keep=False)
-        actions = torch.empty(B, device=x.device, dtype=torch.int64)
-        q = torch.empty(B, self.n_actions, device=x.device)
-        _bridge.launch(x.device, _lib.lib().ocrl_qr_act, ctypes.byref(d), _lib.ptr(x), _lib.ptrs(ps), int(seed), int(row_offset), float(epsilon),
-                       _lib.ptr(uniforms), _lib.ptr(actions), _lib.ptr(q))
-        return actions, q
+        return self._launch_act(_lib.lib().ocrl_qr_act, d, x, ps, seed, row_offset, epsilon, uniforms)
 
 
 def qr_loss(policy, features, next_quantiles, next_q, actions, rewards, dones, gamma, kappa=1.0, discounts=None, weights=None):

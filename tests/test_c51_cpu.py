@@ -54,6 +54,7 @@ def test_header_parses_and_the_library_exports_what_it_declares():
     for part in ("c51.hip", "c51_unit.o", "c51.h", "ocrl_hip_c51.h"):
         assert part in makefile, part
     assert re.search(r"^acnet\.o .*\bc51\.o\b.*: acnet_tile\.h$", makefile, re.M) and re.search(r"^acnet\.o .*\bc51_unit\.o\b.*: acnet\.h$", makefile, re.M)
+    assert re.search(r"^(?:\S+ )*c51\.o(?: \S+)*: qhead_tile\.h$", makefile, re.M) and "qhead_tile.h" in re.search(r"^HDRS = (.*)$", makefile, re.M).group(1).split()
 
 
 def test_descriptor_size_is_the_ctypes_struct():

@@ -67,6 +67,7 @@ def test_struct_layout_matches_the_compiler(tmp_path):
     assert out[:-1] == want and out[-1] == ""
     for part in ("dqn.hip", "dqn_unit.o", "dqn.h", "ocrl_hip_dqn.h"):
         assert part in makefile, part
+    assert re.search(r"^(?:\S+ )*dqn\.o(?: \S+)*: qhead_tile\.h$", makefile, re.M) and "qhead_tile.h" in re.search(r"^HDRS = (.*)$", makefile, re.M).group(1).split()
 
 
 # ---- rejections before any launch

@@ -55,7 +55,9 @@ def test_the_makefile_lists_the_new_parts():
     makefile = open(os.path.join(ROOT, "ocrl_amd", "csrc", "Makefile")).read()
     srcs, objs, hdrs = (re.search(rf"^{k} = (.*)$", makefile, re.M).group(1).split() for k in ("SRCS", "OBJS", "HDRS"))
     assert "iqn.hip" in srcs and "iqn_unit.o" in objs and "iqn.h" in hdrs and "../../include/ocrl_hip_iqn.h" in hdrs
-    for dep, objects in (("acnet.h", ("iqn.o", "iqn_unit.o")), ("acnet_tile.h", ("iqn.o",)), ("acnet_host.h", ("iqn_unit.o",))):
+    assert "qhead_tile.h" in hdrs
+    for dep, objects in (("acnet.h", ("iqn.o", "iqn_unit.o")), ("acnet_tile.h", ("iqn.o",)), ("acnet_host.h", ("iqn_unit.o",)),
+                         ("qhead_tile.h", ("iqn.o",))):
         line = re.search(rf"^([^#\n]*): {re.escape(dep)}$", makefile, re.M).group(1).split()
         assert set(objects) <= set(line), (dep, line)
     for f in ("iqn.hip", "iqn.h", "iqn_unit.cpp"):

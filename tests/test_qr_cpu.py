@@ -49,7 +49,8 @@ def test_the_makefile_lists_the_new_parts():
     makefile = open(os.path.join(ROOT, "ocrl_amd", "csrc", "Makefile")).read()
     srcs, objs, hdrs = (re.search(rf"^{k} = (.*)$", makefile, re.M).group(1).split() for k in ("SRCS", "OBJS", "HDRS"))
     assert "qr.hip" in srcs and "qr_unit.o" in objs and "qr.h" in hdrs and "../../include/ocrl_hip_qr.h" in hdrs
-    for dep, objects in (("acnet.h", ("qr.o", "qr_unit.o")), ("acnet_tile.h", ("qr.o",)), ("acnet_host.h", ("qr_unit.o",))):
+    assert "qhead_tile.h" in hdrs
+    for dep, objects in (("acnet.h", ("qr.o", "qr_unit.o")), ("acnet_tile.h", ("qr.o",)), ("acnet_host.h", ("qr_unit.o",)), ("qhead_tile.h", ("qr.o",))):
         line = re.search(rf"^([^#\n]*): {re.escape(dep)}$", makefile, re.M).group(1).split()
         assert set(objects) <= set(line), (dep, line)
     for f in ("qr.hip", "qr.h", "qr_unit.cpp"):
